@@ -10,6 +10,7 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W   prints ONE J
   * timed region: inputs resident in HBM (model loaded, prompt prefilled, graph captured) before the first event.
   * protocol of the reference's own bench (/root/reference/src/cli/bench.rs:30-33,142-146): warm-up, then `--reps` timed runs of exactly
     K steps each (every run bracketed by a barrier + device synchronise, MAX over ranks), the MEDIAN run is reported; all runs are listed.
+  * --dump-outputs DIR: the last timed step's logits row and greedy id, DIR/logits.npy (float32) and DIR/next_token.npy (float64).
 Extra objects: "roofline" (dominant kernel, pure dispatch time from HIP events on the launch stream vs the 8 TB/s spec peak AND vs the read
 ceiling measured on this device in the same process), "cpu_baseline" (the CPU oracle -- a port, the reference's own --cpu path cannot be
 built here: BASELINE.md 4) and "parity" (GPU vs CPU oracle on the full model: free-running greedy ids, and the CPU ids teacher-forced
@@ -29,6 +30,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
+TOKEN_LOG = 4096        # bz_decode_graph::LOGCAP: a decode graph keeps the ids of its last 4096 replays since the seed
 
 
 def hip_events(stream):
@@ -85,6 +87,20 @@ def pmc_traffic(label):
     return None, "kernel not in the PMC pass"
 
 
+def run_ids(graph, first, n_run, n_head):
+    """[first] + the ids of the first n_head steps of a graph run of n_run replays, as far as the token log still holds them
+    (a run longer than TOKEN_LOG has overwritten its first ids)"""
+    return [first] + [graph.read_token(i) for i in range(min(n_head, n_run) if n_run <= TOKEN_LOG else 0)]
+
+
+def dump_outputs(d, graph, last):
+    """--dump-outputs: what the caller of the timed path received from its last step -- the logits row (float32) and the greedy id it
+    picked (float64) -- as DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs"""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "logits.npy"), graph.read_logits().astype(np.float32))
+    np.save(os.path.join(d, "next_token.npy"), np.array([last], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -103,6 +119,7 @@ def main():
     # measured on the GPU box (256 logical CPUs, its share for one GPU is 16), 64 threads gave 2.6 tok/s against 3.4 with 16 -- the GEMVs are bound by
     # the host's memory system, and oversubscribing the share only adds contention
     ap.add_argument("--cpu-threads", type=int, default=16)
+    ap.add_argument("--dump-outputs", metavar="DIR")         # write the last timed step's outputs as DIR/<name>.npy (dump_outputs)
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -180,11 +197,15 @@ def main():
         runs.append(replicas.aggregate_tokens_per_s(max(gpu_ms, host_ms), args.steps, dist, "cuda" if dist is not None else None) + (gpu_ms, host_ms))
     runs_sorted = sorted(runs, key=lambda r: r[1])
     tok_s, wall_ms, gpu_ms, host_ms = runs_sorted[len(runs_sorted) // 2]      # the median run
-    tokens = [first] + [graph.read_token(i) for i in range(args.warmup + args.steps)]
+    n_run = args.warmup + args.steps
+    last = graph.read_token(n_run - 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, graph, last)      # before profile_step below overwrites the model's logits row
+    tokens = run_ids(graph, first, n_run, max(2, args.cpu_tokens) if want_cpu else 0)
 
     # per-kernel dispatch times of real decode steps (pure kernel time, hipExtLaunchKernelGGL start/stop events)
     pos = args.prompt_len + args.warmup + args.steps
-    prof = lm.profile_step(kv, tokens[-1], min(pos, cfg["max_seq_len"] - 5), iters=4)
+    prof = lm.profile_step(kv, last, min(pos, cfg["max_seq_len"] - 5), iters=4)
     for p in prof:
         p["avg_us"] = 1e3 * p["total_ms"] / max(p["launches"], 1)
         p["gbs"] = (p["algo_bytes"] / 1e9) / (p["total_ms"] / 1e3) if p["total_ms"] > 0 and p["algo_bytes"] > 0 else None
@@ -377,8 +398,12 @@ def bench_aux(args, rank, local_rank, world, dist):
         dist.barrier()
     n_gpus = max(world, 1)
     tok_s, wall_ms = replicas.aggregate_tokens_per_s(max(gpu_ms, host_ms), args.steps, dist, "cuda" if dist is not None else None)
-    tokens = [first] + [graph.read_token(i) for i in range(args.warmup + args.steps)]
-    prof = lm.profile_step_ssm(st, tokens[-1], iters=4) if mamba else lm.profile_step(st, tokens[-1], args.prompt_len + args.warmup + args.steps, iters=4)
+    n_run = args.warmup + args.steps
+    last = graph.read_token(n_run - 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, graph, last)
+    tokens = run_ids(graph, first, n_run, 7)
+    prof = lm.profile_step_ssm(st, last, iters=4) if mamba else lm.profile_step(st, last, args.prompt_len + args.warmup + args.steps, iters=4)
     for p in prof:
         p["avg_us"] = 1e3 * p["total_ms"] / max(p["launches"], 1)
         p["gbs"] = (p["algo_bytes"] / 1e9) / (p["total_ms"] / 1e3) if p["total_ms"] > 0 and p["algo_bytes"] > 0 else None
