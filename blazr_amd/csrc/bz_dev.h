@@ -1,4 +1,4 @@
-// bz_dev.h -- device-side helpers shared by the kernel files (bz_kernels.hip, bz_persist.hip): number formats, the fixed-point accumulator grid,
+// bz_dev.h -- device-side helpers of the kernel file (bz_kernels.hip): number formats, the fixed-point accumulator grid,
 // the signed-nibble activation planes and the V_DOT8_I32_I4 group arithmetic of the int4 path, K/V row addressing.  Not part of the ABI.
 #pragma once
 #include "bz_internal.h"

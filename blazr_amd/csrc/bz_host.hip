@@ -60,9 +60,6 @@ extern "C" int bz_device_open(int id, bz_device** out) {
   d->pinned_bytes = 1 << 20;
   BZ_HIP(hipHostMalloc(&d->pinned, d->pinned_bytes, hipHostMallocDefault));
   BZ_HIP(hipMalloc((void**)&d->scratch, 4096));
-  BZ_HIP(hipMalloc((void**)&d->persist_bar, bzk_persist_bar_words() * 4));
-  BZ_HIP(hipMemset(d->persist_bar, 0, bzk_persist_bar_words() * 4));
-  { void* pe = nullptr; BZ_HIP(hipHostMalloc(&pe, 64, hipHostMallocMapped)); d->persist_err = (volatile unsigned*)pe; *d->persist_err = 0u; }
   *out = d;
   return BZ_OK;
   BZ_API_END
@@ -77,8 +74,6 @@ void bz_dev_release(bz_device* d) {
   for (auto ev : d->events) hipEventDestroy(ev);
   if (d->pinned) hipHostFree(d->pinned);
   if (d->scratch) hipFree(d->scratch);
-  if (d->persist_bar) hipFree(d->persist_bar);
-  if (d->persist_err) hipHostFree((void*)d->persist_err);
   bzk_sample_free(d->samp_ws);
   hipStreamDestroy(d->stream);
   hipStreamDestroy(d->copy_stream);
@@ -93,19 +88,12 @@ extern "C" int bz_device_close(bz_device* d) {
   return BZ_OK;
   BZ_API_END
 }
-// The persistent decode launch (bz_persist.hip) ends with this word set when one of its grid-barrier waits ran into its wall-clock limit (a lost arrival):
-// the results of that step are garbage.  Checked wherever the host has just synchronised with the device; the word is sticky until the device is reopened.
-static int persist_check(bz_device* d) {
-  if (d && d->persist_err && *d->persist_err != 0u)
-    BZ_FAIL(BZ_E_HIP, "persistent decode launch: a grid-barrier wait exceeded its limit (results invalid); set BZ_NO_PERSIST=1 to use the launch-per-phase path");
-  return BZ_OK;
-}
 extern "C" int bz_device_synchronize(bz_device* d) {
   BZ_API_BEGIN
   if (!d) BZ_FAIL(BZ_E_INVALID, "null device");
   BZ_HIP(hipStreamSynchronize(d->stream));
   BZ_HIP(hipStreamSynchronize(d->copy_stream));
-  return persist_check(d);
+  return BZ_OK;
   BZ_API_END
 }
 extern "C" int bz_device_memory_info(bz_device* d, size_t* f, size_t* t) {
@@ -296,7 +284,7 @@ struct bz_model {
   std::vector<DsLayerDev> dlayers;
   float* mla_ws = nullptr; int mla_nsplit = 1;   // MLA decode over context slices: partials [n_heads][nsplit][rank + 2]
   float* mla_scw = nullptr; float* mla_mxw = nullptr;        // exact decode MLA, three-launch form: scores [n_heads][nsplit][ceil(max_seq_len / nsplit) + 1], slice maxima [n_heads][nsplit]
-  double* mla_wsd = nullptr; unsigned* mla_sync = nullptr;   // exact decode MLA (k_mla_attn_x): double partials [n_heads][nsplit][rank + 1]; per-head {maximum, arrivals} words
+  double* mla_wsd = nullptr;   // exact decode MLA: double partials [n_heads][nsplit][rank + 1]
   long long* moe_gu_acc = nullptr;   // fixed-point gate / up of the MoE slots (k_gemv_rows2's MoE form); zeroed by the combine launch
   float* moe_xn = nullptr; float* moe_gu = nullptr; float* moe_out = nullptr; long long* moe_acc = nullptr; int* moe_sel = nullptr; float* moe_w = nullptr; float* moe_lg = nullptr; unsigned* moe_cnt = nullptr;
   // DeepSeek-V2 batched-prefill rows (allocated on first use for dpf_rows prompt rows)
@@ -319,7 +307,6 @@ struct bz_model {
   float* cos_t = nullptr; float* sin_t = nullptr;
   float* rope_cur = nullptr;   // [cos | sin] row of the current position (staged by the embed kernel)
   float* att_ws = nullptr;     // split-KV attention partials (bzk_attn_split_ws_bytes)
-  void* persist_tab = nullptr; // device table of per-layer weight pointers for the persistent decode launch (nullptr: the model does not qualify)
   // workspace
   float* hbuf[2] = {nullptr, nullptr};
   // batched-prefill workspace (bz_prefill.hip), allocated on first use for `pf_rows` prompt rows
@@ -910,27 +897,6 @@ extern "C" int bz_model_finalize(bz_model* m) {
   BZ_TRY(dev_alloc(m, &p, 64)); m->tok_tmp = (long long*)p;
   BZ_TRY(dev_alloc(m, &p, 64)); m->pos_tmp = (int*)p;
 
-  // the persistent decode launch (bz_persist.hip): every layer int4 without act-order / bias, the Llama-3-8B head geometry, f16 activations
-  if (bzk_persist_shape_ok(H, I, nq, nkv, hd, c.act_dtype, BZ_F16) && !c.rope_interleaved) {
-    bool ok = true;
-    for (auto& Ld : m->layers)
-      for (const FusedLinear* F : {&Ld.qkv, &Ld.o, &Ld.gateup, &Ld.down})
-        ok = ok && F->parts.size() == 1 && F->parts[0].kind == LK_Q4G && !F->parts[0].perm && !F->parts[0].bias && F->fix_out;
-    if (ok) {
-      const size_t eb = bzk_persist_layer_bytes();
-      std::vector<char> tab(eb * c.n_layers);
-      for (int l = 0; l < c.n_layers && ok; l++) {
-        const LayerDev& Ld = m->layers[l];
-        ok = bzk_persist_fill_layer(tab.data() + eb * l, Ld.qkv.parts[0], Ld.o.parts[0], Ld.gateup.parts[0], Ld.down.parts[0], Ld.attn_norm, Ld.ffn_norm) == BZ_OK;
-      }
-      if (ok) {
-        BZ_TRY(dev_alloc(m, &p, tab.size()));
-        BZ_HIP(hipMemcpy(p, tab.data(), tab.size(), hipMemcpyHostToDevice));
-        m->persist_tab = p;
-      }
-    }
-  }
-
   // accounting
   size_t act_b = bz_dtype_size(c.act_dtype);
   m->per_token = (size_t)(2 * c.n_layers + 1) * H * act_b + (size_t)H * bz_dtype_size(m->embed_dt);
@@ -1113,7 +1079,6 @@ static int finalize_dsv2(bz_model* m) {
   m->mla_nsplit = bzk_mla_nsplit(NH);
   BZ_TRY(dev_alloc(m, &p, (size_t)NH * m->mla_nsplit * (R + 2) * 4)); m->mla_ws = (float*)p;
   BZ_TRY(dev_alloc(m, &p, (size_t)NH * m->mla_nsplit * (R + 1) * 8)); m->mla_wsd = (double*)p;
-  BZ_TRY(dev_alloc(m, &p, (size_t)(2 * NH + 2) * 4)); m->mla_sync = (unsigned*)p; BZ_HIP(hipMemset(p, 0, (size_t)(2 * NH + 2) * 4));
   BZ_TRY(dev_alloc(m, &p, (size_t)NH * m->mla_nsplit * ((c.max_seq_len + m->mla_nsplit - 1) / m->mla_nsplit + 1) * 4)); m->mla_scw = (float*)p;
   BZ_TRY(dev_alloc(m, &p, (size_t)NH * m->mla_nsplit * 4)); m->mla_mxw = (float*)p;
   BZ_TRY(dev_alloc(m, &p, (size_t)V * 4)); m->logits = (float*)p;
@@ -1417,14 +1382,6 @@ static int run_fused(bz_model* m, const FusedLinear& F, Pro pro, RingState& rs, 
   const int ri = rs.ri, rz = (rs.ri + 1) % 3;
   long long* acc = m->ring[ri];
   float* direct = m->dring[ri];
-  if (F.parts.size() == 1 && F.fix_out && bzk_gemv_cols_ok(F.parts[0], pro, act)) {
-    // the whole K inside one workgroup per 64-column tile: finished values, stored directly (no accumulator to fill or to zero for THIS launch;
-    // the ring protocol's zeroing duty for the buffer after next stays)
-    BZ_TRY(bzk_gemv_cols(st, F.parts[0], pro, direct, rs.dirty[rz] > 0 ? m->ring[rz] : nullptr, rs.dirty[rz]));
-    rs.dirty[rz] = 0; rs.dirty[ri] = 0; rs.ri = rz;
-    out->fix = 0; out->p = (const void*)direct;
-    return BZ_OK;
-  }
   static const bool no_mix = getenv("BZ_NO_GQ_MIX") != nullptr;
   if (!no_mix && F.parts.size() == 2 && F.fix_out && F.n_off[1] == F.parts[0].N && bzk_gq_mix_ok(F.parts[0], F.parts[1], pro)) {
     // GGUF Q4_K_M q/k/v: the Q4_K part (q, k) and the Q6_K part (v) in one launch
@@ -1467,101 +1424,18 @@ static int llama_step(bz_model* m, const StepIO& io) {
     BZ_HIP(hipMemcpyAsync(m->hbuf[cur], io.hidden_in, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
     if (io.prev_in) { prev.p = io.prev_in; prev.fix = 0; }
   }
-  // The layers as ONE persistent launch (bz_persist.hip) -- OPT-IN (BZ_PERSIST=1): measured in round 3 it is slower than the three launches per layer
-  // (profiles/r03_persist_stamps.txt, DESIGN 8: a grid barrier on a CU that has weight requests in flight waits behind them, 5-10 us each).  Applies when the
-  // model qualifies, the context fits the single-launch attention and the step starts without a deferred residual.  Bit-identical to the launch-per-phase
-  // path below (same arithmetic, integer accumulators): tests/test_gpu_persist.py.
-  static const bool no_persist = getenv("BZ_PERSIST") == nullptr || getenv("BZ_NO_PERSIST") != nullptr;
-  int l_first = io.layer_start;
-  if (!no_persist && m->persist_tab && prev.p == nullptr && lend > io.layer_start && io.att_positions == 0 && io.kv.dtype == BZ_F16 && io.kv.hd == c.head_dim && io.d_pos) {
-    BzPersistLaunch pl{};
-    pl.layers = (const char*)m->persist_tab + bzk_persist_layer_bytes() * io.layer_start; pl.n_layers = lend - io.layer_start;
-    pl.h_in = m->hbuf[cur]; pl.h_out = m->hbuf[cur ^ 1];
-    pl.ring_m = m->ring[0]; pl.ring_q = m->ring[1]; pl.ring_o = m->ring[2];
-    pl.rope_cur = m->rope_cur; pl.pos = io.d_pos; pl.kv = io.kv;
-    // the K / V bases of the table's first layer: the kernel indexes layers from 0
-    pl.kv.k = (char*)io.kv.k + (size_t)io.layer_start * io.kv.layer_stride * bz_dtype_size(io.kv.dtype);
-    pl.kv.v = (char*)io.kv.v + (size_t)io.layer_start * io.kv.layer_stride * bz_dtype_size(io.kv.dtype);
-    pl.bar = m->dev->persist_bar; pl.err_host = (unsigned*)m->dev->persist_err; pl.eps = c.rms_eps; pl.I = I;
-    double bytes = 0.0;
-    for (int l = io.layer_start; l < lend; l++)
-      for (const FusedLinear* F : {&m->layers[l].qkv, &m->layers[l].o, &m->layers[l].gateup, &m->layers[l].down}) bytes += (double)F->parts[0].algo_bytes;
-    pl.algo_bytes = bytes;
-    // diagnostic: per-wave phase stamps of layer 1 (workgroups 0 and 131), printed after the launch (eager steps only)
-    static const bool pstamps_on = getenv("BZ_PERSIST_STAMPS") != nullptr;
-    static long long* pstamps = nullptr; static int pstamp_prints = 0;
-    if (pstamps_on && !tl_capture_stream && pstamp_prints < 3) { if (!pstamps) hipMalloc(&pstamps, 2 * 8 * 32 * 8); hipMemsetAsync(pstamps, 0, 2 * 8 * 32 * 8, st); pl.stamps = pstamps; }
-    BZ_TRY(bzk_llama_persist(st, pl));
-    if (pl.stamps) {
-      std::vector<long long> hs(2 * 8 * 32);
-      hipStreamSynchronize(st); hipMemcpy(hs.data(), pstamps, hs.size() * 8, hipMemcpyDeviceToHost); pstamp_prints++;
-      const long long t0 = hs[0];
-      for (int g = 0; g < 2; g++)
-        for (int w = 0; w < 8; w++) {
-          fprintf(stderr, "[bz] persist stamps wg %3d wave %d (us since wg 0 wave 0 entered phase Q of layer 1):", g ? 131 : 0, w);
-          for (int i = 0; i < 18; i++) fprintf(stderr, " %d:%.2f", i, hs[(g * 8 + w) * 32 + i] ? (hs[(g * 8 + w) * 32 + i] - t0) / 100.0 : -1.0);
-          fprintf(stderr, "\n");
-        }
-      { double d; float f1, f2; memcpy(&d, &hs[24], 8); int i1 = (int)hs[25], i2 = (int)hs[26]; memcpy(&f1, &i1, 4); memcpy(&f2, &i2, 4);
-        fprintf(stderr, "[bz] persist row update (last one of the launch, wg 0): ssd %.17g ss %.9g rs %.9g; wave sums:", d, f1, f2);
-        for (int w8 = 0; w8 < 8; w8++) { memcpy(&d, &hs[32 + w8], 8); fprintf(stderr, " %.17g", d); }
-        fprintf(stderr, "\n"); }
-    }
-    cur ^= 1;
-    // ring state after the launch: ring[0] = the last MLP's output (the deferred residual), ring[1] zeroed in its last phase, ring[2] read but not zeroed
-    prev = VSrc{m->ring[0], 1};
-    rs.ri = 1; rs.dirty[0] = H; rs.dirty[1] = 0; rs.dirty[2] = H;
-    l_first = lend;
-  }
-  for (int l = l_first; l < lend; l++) {
+  for (int l = io.layer_start; l < lend; l++) {
     const LayerDev& Ld = m->layers[l];
     Pro pn{}; pn.mode = PRO_NORM; pn.src = prev; pn.h_in = m->hbuf[cur]; pn.h_out = m->hbuf[cur ^ 1]; pn.norm_w = Ld.attn_norm;
     pn.eps = c.rms_eps; pn.H = H; pn.act = act;
-    static long long* qkv_stamps = nullptr;
-    static const bool qkv_stamps_on = getenv("BZ_QKV_STAMPS") != nullptr;
-    if (qkv_stamps_on) {
-      if (!qkv_stamps) { hipMalloc(&qkv_stamps, 256); hipMemset(qkv_stamps, 0, 256); }
-      if (l == 2) {
-        long long hst[16]; hipStreamSynchronize(st); hipMemcpy(hst, qkv_stamps, 128, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[bz] qkv stamps us since block 0 entry: first block");
-        for (int q = 1; q <= 5; q++) fprintf(stderr, " %d:%.2f", q, (hst[q] - hst[0]) / 100.0);
-        fprintf(stderr, " | last block entry %.2f", (hst[8] - hst[0]) / 100.0);
-        for (int q = 1; q <= 5; q++) fprintf(stderr, " %d:%.2f", q, (hst[8 + q] - hst[0]) / 100.0);
-        fprintf(stderr, "\n");
-      }
-      pn.stamps = l == 1 ? qkv_stamps : nullptr;
-    }
     VSrc qkv;
     BZ_TRY(run_fused(m, Ld.qkv, pn, rs, &qkv));
     cur ^= 1;
-    {   // diagnostic (scripts/qkv_dump.py): the raw q/k/v accumulator of one layer, written to a file (eager steps only)
-      static const char* dump = getenv("BZ_DUMP_QKV");
-      static const int dump_layer = getenv("BZ_DUMP_LAYER") ? atoi(getenv("BZ_DUMP_LAYER")) : 0;
-      if (dump && !tl_capture_stream && l == dump_layer && qkv.fix) {
-        std::vector<long long> hq(Ld.qkv.N);
-        hipStreamSynchronize(st); hipMemcpy(hq.data(), qkv.p, hq.size() * 8, hipMemcpyDeviceToHost);
-        FILE* f = fopen(dump, "wb"); if (f) { fwrite(hq.data(), 8, hq.size(), f); fclose(f); }
-      }
-    }
 
     AttnArgs aa{};
     aa.qkv = qkv; aa.cos_t = m->cos_t; aa.sin_t = m->sin_t; aa.interleaved = c.rope_interleaved; aa.pos = io.d_pos; aa.rope_cur = m->rope_cur;
     aa.nq = c.n_heads; aa.nkv = c.n_kv_heads; aa.hd = c.head_dim; aa.act = act; aa.kv = io.kv; aa.layer = l; aa.out = m->attn_out;
     aa.zero_buf = nullptr; aa.zero_n = 0; aa.q_only = 0;
-    static long long* attn_stamps = nullptr;
-    static const bool attn_stamps_on = getenv("BZ_ATTN_STAMPS") != nullptr, attn_stamps_print = getenv("BZ_ATTN_STAMPS_PRINT") != nullptr;
-    if (attn_stamps_on) {
-      if (!attn_stamps) { hipMalloc(&attn_stamps, 512); hipMemset(attn_stamps, 0, 512); }
-      if (l == 1) {
-        if (attn_stamps_print) {
-          long long hst[64]; hipStreamSynchronize(st); hipMemcpy(hst, attn_stamps, 512, hipMemcpyDeviceToHost);
-          fprintf(stderr, "[bz] attn stamps (us since entry):");
-          for (int q = 1; q <= 8; q++) fprintf(stderr, " %d:%.2f", q, (hst[q] - hst[0]) / 100.0);
-          fprintf(stderr, "\n");
-        }
-      }
-      aa.stamps = l == 0 ? attn_stamps : nullptr;
-    }
     VSrc ov;
     static const bool no_fuse = getenv("BZ_NO_ATTN_FUSION") != nullptr;
     // (the f32-cache form has no split-KV partner: beyond the single-launch contexts it stays unfused)
@@ -1756,7 +1630,7 @@ static int dsv2_step(bz_model* m, const StepIO& io) {
     ma.ws = m->mla_ws; ma.nsplit = m->mla_nsplit;
     // exact decode (16-bit models): every sum as the oracle defines it, one maximum over the whole context (BZ_DSV2_F32_SUMS=1: the f32 kernels)
     static const bool f32_mla = getenv("BZ_DSV2_F32_SUMS") != nullptr;
-    if (!f32_mla && (act == BZ_F16 || act == BZ_BF16) && bzk_mla_x_ok(ma, c.max_seq_len)) BZ_TRY(bzk_mla_attn_x(st, ma, c.max_seq_len, m->mla_wsd, m->mla_sync, (unsigned*)m->dev->persist_err, m->mla_scw, m->mla_mxw));
+    if (!f32_mla && (act == BZ_F16 || act == BZ_BF16) && bzk_mla_x_ok(ma, c.max_seq_len)) BZ_TRY(bzk_mla_attn_x(st, ma, c.max_seq_len, m->mla_wsd, m->mla_scw, m->mla_mxw));
     else BZ_TRY(bzk_mla_attn(st, ma, c.max_seq_len));
     Pro pp{}; pp.mode = PRO_PLAIN; pp.src = VSrc{m->attn_out, 0}; pp.act = act; pp.H = 0; pp.f32_sums = 0;
     VSrc ov;
@@ -1787,15 +1661,7 @@ static int dsv2_step(bz_model* m, const StepIO& io) {
         g1.w = L.e_gu; g1.expert_stride = (long long)2 * MI * H; g1.sel = nullptr; g1.N = 2 * MI; g1.K = H; g1.src_stride = 0;
         g1.acc = m->moe_gu_acc; g1.acc_stride = 2 * MI; g1.acc_slots = slots;
         g1.route = RouteArgs{(const long long*)lg.p, E, TK, NS, c.moe_routed_scale, c.moe_norm_topk, m->moe_sel, m->moe_w};
-        static const bool moe_stamps = getenv("BZ_MOE_STAMPS") != nullptr;   // diagnostic: phase stamps of the route + gate/up launch (layer 2, printed once)
-        static long long* stamp_buf = nullptr; static int stamp_prints = 0;
-        if (moe_stamps && l == 2 && stamp_prints < 3 && !tl_capture_stream) { if (!stamp_buf) { hipMalloc(&stamp_buf, 64); } hipMemsetAsync(stamp_buf, 0, 64, st); pg.stamps = stamp_buf; }
         BZ_TRY(bzk_moe_gemv(st, g1, L.e_dt, slots, pg, act, true, (double)slots * 2 * MI * H * es));
-        if (pg.stamps) {
-          long long hs[8]; hipStreamSynchronize(st); hipMemcpy(hs, stamp_buf, 64, hipMemcpyDeviceToHost); stamp_prints++;
-          fprintf(stderr, "[bz] route+gate/up stamps (us since entry): rendezvous %.2f, x published %.2f, top-k done %.2f | tile wave: range 0 done %.2f, ids seen %.2f, end %.2f\n",
-                  (hs[1] - hs[0]) / 100.0, (hs[2] - hs[0]) / 100.0, (hs[3] - hs[0]) / 100.0, (hs[4] - hs[0]) / 100.0, (hs[5] - hs[0]) / 100.0, (hs[6] - hs[0]) / 100.0);
-        }
         MoeGemvArgs g2{};
         g2.w = L.e_dn; g2.expert_stride = (long long)H * MI; g2.sel = m->moe_sel; g2.N = H; g2.K = MI; g2.src_stride = 2 * MI;
         g2.acc = m->moe_acc; g2.acc_stride = H; g2.acc_slots = TK + 1;
@@ -2645,10 +2511,12 @@ __global__ void k_fill_u32(uint32_t* p, size_t n, uint32_t seed) {
 
 // Kernel tuning aid: times the int4 GEMV kernel alone on synthetic weights ([N,K], gs 128) rotated over `nbuf` buffers
 // (so that every launch streams from HBM, not from the 256 MiB Infinity Cache).  mode: 0 plain f32 x, 1 fused
-// residual+RMSNorm prologue (fixed-point prev), 2 SiLU*up prologue (fixed-point gate/up).  Returns the mean dispatch time.
+// residual+RMSNorm prologue (fixed-point prev), 2 SiLU*up prologue (fixed-point gate/up); flags: 0, or 8 = four weight groups in flight
+// per wave instead of two (L.npf).  Returns the mean dispatch time.
 extern "C" int bz_tune_gemv(bz_device* dev, int N, int K, int gw, int mode, int nbuf, int iters, int flags, double* avg_us) {
   BZ_API_BEGIN
-  if (!dev || !avg_us || N % 64 || K % 128 || gw <= 0 || (K / 128) % gw || gw > 16 || nbuf <= 0 || iters <= 0 || mode < 0 || mode > 2) BZ_FAIL(BZ_E_INVALID, "tune_gemv: bad argument");
+  if (!dev || !avg_us || N % 64 || K % 128 || gw <= 0 || (K / 128) % gw || gw > 16 || nbuf <= 0 || iters <= 0 || mode < 0 || mode > 2 || (flags & ~8))
+    BZ_FAIL(BZ_E_INVALID, "tune_gemv: bad argument");
   BZ_HIP(hipSetDevice(dev->id));
   hipStream_t st = dev->stream;
   const size_t G = (size_t)K / 128, wb = (size_t)N * K / 2, sb = (size_t)N * G * 2, zb = (size_t)N * G;
@@ -2674,13 +2542,11 @@ extern "C" int bz_tune_gemv(bz_device* dev, int N, int K, int gw, int mode, int 
   hipMemsetAsync(xs, 0x3c, (size_t)KX * 4, st); hipMemsetAsync(hin, 0x3c, (size_t)K * 4, st); hipMemsetAsync(nw, 0x3c, (size_t)K * 4, st);
   hipMemsetAsync(acc, 0, (size_t)N * 8, st);
   Pro p{};
-  p.act = BZ_F16; p.dbg = flags; p.eps = 1e-5f;
+  p.act = BZ_F16; p.eps = 1e-5f;
   if (mode == 0) { p.mode = PRO_PLAIN; p.src = VSrc{xs, 0}; }
   else if (mode == 1) { p.mode = PRO_NORM; p.src = VSrc{src, 1}; p.h_in = (float*)hin; p.h_out = (float*)hout; p.norm_w = (float*)nw; p.H = K; }
   else { p.mode = PRO_SILU; p.src = VSrc{src, 1}; p.H = K; }
   BzTimingSink sink;
-  long long* stp = nullptr;
-  if (flags & 16) { p.dbg = 0; if (hipMalloc((void**)&stp, 2 * 12 * 8 * 8) == hipSuccess) { hipMemsetAsync(stp, 0, 2 * 12 * 8 * 8, st); p.stamps = stp; bufs.push_back(stp); } }
   for (int i = 0; i < iters + 2 && rc == BZ_OK; i++) {
     GemvOut o{}; o.acc = (long long*)acc;
     if (i == 2) bzk_set_timing_sink(&sink);
@@ -2688,15 +2554,6 @@ extern "C" int bz_tune_gemv(bz_device* dev, int N, int K, int gw, int mode, int 
   }
   bzk_set_timing_sink(nullptr);
   hipStreamSynchronize(st);
-  if (stp) {   // diagnostic: per-wave phase stamps of the slim kernel's workgroups 0 and 97 (10 ns units, relative to the workgroup's first)
-    long long h[192]; hipMemcpy(h, stp, sizeof h, hipMemcpyDeviceToHost);
-    for (int b = 0; b < 2; b++) {
-      long long t0 = INT64_MAX;
-      for (int i = 0; i < 96; i++) if (h[b * 96 + i] > 0) t0 = std::min(t0, h[b * 96 + i]);
-      fprintf(stderr, "[bz] slim stamps, workgroup %s (us): rows = waves 0..11 (0-3 row waves, 4-11 tile waves); entry, loads issued, ssd, rs known, planes published / seen, group 0 done, atomics issued, drained\n", b ? "97" : "0");
-      for (int w = 0; w < 12; w++) { fprintf(stderr, "   "); for (int i = 0; i < 8; i++) fprintf(stderr, " %6.2f", h[(b * 12 + w) * 8 + i] > 0 ? (h[(b * 12 + w) * 8 + i] - t0) / 100.0 : -1.0); fprintf(stderr, "\n"); }
-    }
-  }
   double tot = 0; int n = 0;
   for (auto& r : sink.recs) { float ms = 0.f; if (hipEventElapsedTime(&ms, r.e0, r.e1) == hipSuccess) { tot += ms; n++; } hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
   *avg_us = n ? 1e3 * tot / n : 0.0;
@@ -2758,11 +2615,10 @@ extern "C" int bz_tune_rows(bz_device* dev, int N, int K, int wdt, int mode, int
 }
 
 // Tuning aid for the fused MLP kernel alone: synthetic gate/up [2I,H] and down [H,I] int4 weights in `nbuf` rotating sets (cold HBM), the
-// real launcher, mean dispatch time; stamps_out (optional, 2 x 16 x 16 values): the diagnostic build's per-wave s_memrealtime stamps
-// (100 MHz) of workgroup 0 and workgroup 113, relative to the earliest stamp of each workgroup.
+// real launcher, mean dispatch time.  flags must be 0 and stamps_out NULL (both kept for the ABI).
 extern "C" int bz_tune_mlp(bz_device* dev, int H, int I, int nbuf, int iters, int flags, double* avg_us, long long* stamps_out) {
   BZ_API_BEGIN
-  if (!dev || !avg_us || (H != 2048 && H != 4096) || I % 128 || nbuf <= 0 || iters <= 0) BZ_FAIL(BZ_E_INVALID, "tune_mlp: bad argument");
+  if (!dev || !avg_us || (H != 2048 && H != 4096) || I % 128 || nbuf <= 0 || iters <= 0 || flags != 0 || stamps_out != nullptr) BZ_FAIL(BZ_E_INVALID, "tune_mlp: bad argument");
   BZ_HIP(hipSetDevice(dev->id));
   hipStream_t st = dev->stream;
   std::vector<void*> bufs;
@@ -2779,14 +2635,13 @@ extern "C" int bz_tune_mlp(bz_device* dev, int H, int I, int nbuf, int iters, in
   };
   std::vector<LinearDev> GU(nbuf), DN(nbuf);
   for (int b = 0; b < nbuf && rc == BZ_OK; b++) { mk(2 * I, H, GU[b], 17u * b + 1u); mk(H, I, DN[b], 29u * b + 3u); }
-  void *src = nullptr, *acc = nullptr, *hin = nullptr, *hout = nullptr, *nw = nullptr, *stp = nullptr;
-  alloc((size_t)H * 8, &src); alloc((size_t)H * 8, &acc); alloc((size_t)H * 4, &hin); alloc((size_t)H * 4, &hout); alloc((size_t)H * 4, &nw); alloc(2 * 16 * 16 * 8, &stp);
+  void *src = nullptr, *acc = nullptr, *hin = nullptr, *hout = nullptr, *nw = nullptr;
+  alloc((size_t)H * 8, &src); alloc((size_t)H * 8, &acc); alloc((size_t)H * 4, &hin); alloc((size_t)H * 4, &hout); alloc((size_t)H * 4, &nw);
   if (rc != BZ_OK) { for (void* p : bufs) hipFree(p); BZ_FAIL(BZ_E_OOM, "tune_mlp: out of memory"); }
   hipLaunchKernelGGL(k_fill_u32, dim3(64), dim3(256), 0, st, (uint32_t*)src, (size_t)H * 2, 5u);
-  hipMemsetAsync(hin, 0x3c, (size_t)H * 4, st); hipMemsetAsync(nw, 0x3c, (size_t)H * 4, st); hipMemsetAsync(acc, 0, (size_t)H * 8, st); hipMemsetAsync(stp, 0, 2 * 16 * 16 * 8, st);
+  hipMemsetAsync(hin, 0x3c, (size_t)H * 4, st); hipMemsetAsync(nw, 0x3c, (size_t)H * 4, st); hipMemsetAsync(acc, 0, (size_t)H * 8, st);
   Pro p{};
-  p.mode = PRO_NORM; p.act = BZ_F16; p.eps = 1e-5f; p.src = VSrc{src, 1}; p.h_in = (float*)hin; p.h_out = (float*)hout; p.norm_w = (float*)nw; p.H = H; p.dbg = flags;
-  p.stamps = stamps_out ? (long long*)stp : nullptr;
+  p.mode = PRO_NORM; p.act = BZ_F16; p.eps = 1e-5f; p.src = VSrc{src, 1}; p.h_in = (float*)hin; p.h_out = (float*)hout; p.norm_w = (float*)nw; p.H = H;
   BzTimingSink sink;
   for (int i = 0; i < iters + 2 && rc == BZ_OK; i++) {
     if (i == 2) bzk_set_timing_sink(&sink);
@@ -2797,14 +2652,6 @@ extern "C" int bz_tune_mlp(bz_device* dev, int H, int I, int nbuf, int iters, in
   double tot = 0; int n = 0;
   for (auto& r : sink.recs) { float ms = 0.f; if (hipEventElapsedTime(&ms, r.e0, r.e1) == hipSuccess) { tot += ms; n++; } hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
   *avg_us = n ? 1e3 * tot / n : 0.0;
-  if (stamps_out) {
-    hipMemcpy(stamps_out, stp, 2 * 16 * 16 * 8, hipMemcpyDeviceToHost);
-    for (int b = 0; b < 2; b++) {
-      long long t0 = INT64_MAX;
-      for (int i = 0; i < 256; i++) if (stamps_out[b * 256 + i] > 0) t0 = std::min(t0, stamps_out[b * 256 + i]);
-      for (int i = 0; i < 256; i++) if (stamps_out[b * 256 + i] > 0) stamps_out[b * 256 + i] -= t0; else stamps_out[b * 256 + i] = -1;
-    }
-  }
   for (void* q : bufs) hipFree(q);
   return rc;
   BZ_API_END
@@ -3216,7 +3063,7 @@ extern "C" int bz_decode_graph_read_token(bz_decode_graph* g, int64_t step, int6
   else BZ_HIP(hipEventSynchronize(g->evs[step % g->evs.size()]));
   if (g->replays - step > bz_decode_graph::LOGCAP) BZ_FAIL(BZ_E_INVALID, "read_token: step %lld fell out of the token log", (long long)step);
   *out = ((volatile long long*)g->tok_log)[step % bz_decode_graph::LOGCAP];
-  return persist_check(g->m->dev);
+  return BZ_OK;
   BZ_API_END
 }
 extern "C" int bz_decode_graph_read_logits(bz_decode_graph* g, float* host, size_t n) {

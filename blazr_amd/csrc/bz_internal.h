@@ -50,8 +50,6 @@ struct Pro {
   const int* perm;     // optional: x'[k] = x[perm[k]] (GPTQ act-order)
   int aux;             // GATED / GATED2: number of norm groups
   int aux2;            // GATED2: number of heads (h_in = per-head sums of v^2 from the SSM kernel, src = v = R(y * R(silu z)))
-  long long* stamps;   // diagnostic only (BZ_MLP_STAMPS): s_memrealtime at phase boundaries of block 0
-  int dbg;             // tuning only (bz_tune_gemv): 1 = store instead of atomics, 2 = skip the dot4 work, 4 = skip quantisation
   int f32_sums;        // dense k_gemv_rows2: f32 FMA chains instead of the exact (double) sums -- the DeepSeek-V2 path sets it (k_gemv_rows2's EX)
 };
 
@@ -88,8 +86,6 @@ struct bz_device {
   float* scratch = nullptr;   // 4 KiB device scratch (sampling partials)
   void* samp_ws = nullptr;    // non-greedy sampling workspace (bz_sample.hip), grown on demand
   std::mutex mu;              // guards the per-device scratch / sampling workspace / staging ring (concurrent generate() calls share a device)
-  unsigned* persist_bar = nullptr;             // grid-barrier words of the persistent decode launch (bz_persist.hip), one set per device
-  volatile unsigned* persist_err = nullptr;    // pinned host word the launch sets when a barrier wait ran into its limit (checked wherever the host synchronises)
   int refs = 1;               // the handle itself + every live child object (tensor/model/cache/graph)
 };
 void bz_dev_retain(bz_device* d);
@@ -197,8 +193,6 @@ int bzk_gemm_q4g_rows(hipStream_t s, const LinearDev& L, int xdt, const void* x1
 int bzk_rows_choose_sk(int N, int K);
 bool bzk_mlp_gq_fusable(const LinearDev& gu, const LinearDev& dn, int H, int I, int act);   // GGUF Q4_K gate/up + Q4_K / Q6_K down, f32 activations
 int bzk_mlp_gq(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, int I, const Pro& pro, long long* acc, long long* zero_buf, int zero_n);
-bool bzk_gemv_cols_ok(const LinearDev& L, const Pro& pro, int act);   // full-K int4 GEMV with direct output (q/k/v of the decode step)
-int bzk_gemv_cols(hipStream_t s, const LinearDev& L, const Pro& pro, float* out, long long* zero_buf, int zero_n);
 // dense 16-bit form (k_mlp_dense): down_proj additionally stored slab-major [I / 32][H][32] (bzk_repack_down_slabs at finalize)
 int bzk_repack_down_slabs(hipStream_t s, const void* w, int H, int I, void* out);
 bool bzk_mlp_dense_fusable(const LinearDev& gu, const LinearDev& dn, const void* down_slabs, int H, int I, int act);
@@ -242,7 +236,6 @@ struct AttnArgs {
   float* out;               // [nq*hd] f32 rounded
   long long* zero_buf; int zero_n;
   int q_only;               // op-level test: q given roped in qkv (plain), no insert, len = *pos
-  long long* stamps;        // diagnostic build only (BZ_ATTN_STAMPS): s_memrealtime at phase boundaries of block 0
 };
 int bzk_attn_decode(hipStream_t s, const AttnArgs& a);
 int bzk_attn_oproj_slices(const AttnArgs& a, const LinearDev& L);   // 0: fused form not applicable
@@ -258,20 +251,6 @@ int bzk_attn_merge_oproj(hipStream_t s, const AttnArgs& a, const float* ws, int 
 int bzk_kv_insert(hipStream_t s, const KvView& kv, int layer, const float* k, const float* v, const int* pos, int nkv, int hd);
 int bzk_kv_read(hipStream_t s, const KvView& kv, int layer, int kvh, int which, int len, float* out);
 
-// the layers of a Llama decode step as one persistent launch (bz_persist.hip)
-struct BzPersistLaunch {
-  const void* layers; int n_layers;       // device table of per-layer weight pointers (bzk_persist_fill_layer entries)
-  const float* h_in; float* h_out;
-  long long* ring_m; long long* ring_q; long long* ring_o;
-  const float* rope_cur; const int* pos; KvView kv;
-  unsigned* bar; unsigned* err_host; float eps; int I; double algo_bytes; long long* stamps;
-};
-size_t bzk_persist_smem();
-size_t bzk_persist_layer_bytes();
-size_t bzk_persist_bar_words();
-bool bzk_persist_shape_ok(int H, int I, int nq, int nkv, int hd, int act, int kv_dtype);
-int bzk_persist_fill_layer(void* host_entry, const LinearDev& qkv, const LinearDev& o, const LinearDev& gu, const LinearDev& dn, const float* attn_norm, const float* ffn_norm);
-int bzk_llama_persist(hipStream_t s, const BzPersistLaunch& pl);
 
 // final argmax over partials (or full logits) -> token; optionally advance position and publish token
 struct FinalArgs {
@@ -309,9 +288,10 @@ struct MlaArgs {
   float* ws; int nsplit;    // decode over context slices (nsplit > 1): [n_heads][nsplit][rank + 2] partials (k_mla_attn<SPLIT> -> k_mla_merge)
 };
 int bzk_mla_nsplit(int n_heads);
-// exact decode MLA (bz_kernels.hip k_mla_attn_x / k_mla_merge_x): wsd = n_heads * nsplit * (rank + 1) doubles, sync = 2 * n_heads words (zero), err = one word
+// exact decode MLA (bz_kernels.hip k_mla_scores_x / k_mla_weights_x / k_mla_merge_x): wsd = n_heads * nsplit * (rank + 1) doubles,
+// scw = n_heads * nsplit * (ceil(max_len / nsplit) + 1) floats, mxw = n_heads * nsplit floats
 bool bzk_mla_x_ok(const MlaArgs& a, int max_len);
-int bzk_mla_attn_x(hipStream_t s, const MlaArgs& a, int max_len, double* wsd, unsigned* sync, unsigned* err, float* scw = nullptr, float* mxw = nullptr);   // scw: n_heads * nsplit * (ceil(max_len / nsplit) + 1) floats, mxw: n_heads * nsplit (three-launch form)
+int bzk_mla_attn_x(hipStream_t s, const MlaArgs& a, int max_len, double* wsd, float* scw, float* mxw);
 // prompt rows: latent RMSNorm + k_pe RoPE of rows s = 0 .. S-1 (source row s at kva + s * stride), appended to the cache at position pos0 + s
 int bzk_mla_append_rows(hipStream_t s, const float* kva, long long stride, int S, const float* kv_norm, float eps, int rank, int rope, const float* cos_t, const float* sin_t,
                         int pos0, int act, const KvView& kv, int layer);
@@ -505,7 +485,7 @@ __host__ __device__ __forceinline__ float bz_expf(float x) {
 // f32 -> f16 with the f32 value MATERIALISED first.  Under hipcc's default -ffp-contract=fast the pair "f32 multiply, convert to f16" is fused into
 // v_fma_mixlo_f16, which rounds the EXACT product to f16 once; the oracle (and every kernel whose conversion sits behind a run-time dtype switch) rounds the
 // product to f32 and then to f16.  The two differ whenever the f32 rounding lands on or crosses an f16 midpoint: measured in round 3 on the slim q/k/v
-// kernel (scripts/qkv_dump.py), 5 of the 4096 normalised activations of one layer came out as the other f16 neighbour -- which moved every q/k/v column of
+// kernel (a q/k/v dump hook, since removed), 5 of the 4096 normalised activations of one layer came out as the other f16 neighbour -- which moved every q/k/v column of
 // that layer by ~1e-4.  The empty asm makes the operand opaque, so the multiply keeps its own rounding.
 __device__ __forceinline__ float f16_round(float x) {
   asm volatile("" : "+v"(x));
@@ -516,7 +496,7 @@ __device__ __forceinline__ __half f16_cvt(float x) {
   return __float2half_rn(x);
 }
 // Correctly rounded f32 quotient / square root through double (53 >= 2 * 24 + 2 bits: the double result rounds to the correctly rounded float).  Written out
-// because hipcc does not always give `a / b` and `1.0f / sqrtf(x)` the IEEE sequence: measured in round 3 (scripts/qkv_dump.py), the slim q/k/v kernel's
+// because hipcc does not always give `a / b` and `1.0f / sqrtf(x)` the IEEE sequence: measured in round 3 (a q/k/v dump hook, since removed), the slim q/k/v kernel's
 // 1 / rms came out ONE ULP LOW next to the generic kernel's (same source expression) -- five of 4096 normalised activations then round to the other f16
 // neighbour, and every q/k/v column of the layer is off by ~1e-4.  The oracle's C expressions (IEEE division and sqrtf) are these values.
 __host__ __device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }

@@ -328,7 +328,7 @@ __device__ __forceinline__ void xfinish(const Pro& p, int KR, const XRegs<MODE, 
 // down_proj is a sum over the intermediate dimension, so the slabs combine through the fixed-point accumulator.
 // One launch streams 81 % of a layer's bytes with one fused-norm prologue per block.
 // ---------------------------------------------------------------------------------------------------------
-// Structure of the launch (per-wave stamps of the diagnostic build, profiles/r02_mlp_stamps_*.txt):
+// Structure of the launch (per-wave stamps of a diagnostic build, since removed: profiles/r02_mlp_stamps_*.txt):
 //  * a CU keeps ~40 KiB of HBM loads in flight; a wave that asks for more STALLS AT ISSUE -- in program order, so whatever it would do
 //    next waits too.  Round 1 issued 8 KiB of weights per wave ahead of the norm: waves 10..15 sat in the issue queue until 4.4 us, the
 //    block-wide sum of squares (every wave held 1/16 of the row) was complete at 5.7 us and the planes at 7.8 us; asking for little
@@ -339,7 +339,7 @@ __device__ __forceinline__ void xfinish(const Pro& p, int KR, const XRegs<MODE, 
 //    complete; planes published) instead of workgroup barriers, which a streamer could only reach after its issue stall.
 //  * the row never goes through LDS as f32: a thread normalises its eight elements in registers and builds the six plane words.
 //  * the tail (sum of the waves' partials, SiLU * up, its 64-value quantisation) runs in ONE wave between two barriers instead of four.
-template <int FIX, int GPW, int TPW, int NW, int ACT, int DIAG = 0>   // NW waves per block; GPW k-groups per wave (gate/up), TPW output tiles per wave (down); DIAG: stamp build
+template <int FIX, int GPW, int TPW, int NW, int ACT>   // NW waves per block; GPW k-groups per wave (gate/up), TPW output tiles per wave (down)
 __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ Wgu, const __half* __restrict__ Sgu, const unsigned char* __restrict__ Zgu,
                                                  const float* __restrict__ bgu, const uint4* __restrict__ Wd, const __half* __restrict__ Sd,
                                                  const unsigned char* __restrict__ Zd, const float* __restrict__ bd, int H, int I, Pro pro,
@@ -366,14 +366,6 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
   // all kernel arguments in ONE scalar-load batch (the compiler otherwise fetches late-used ones lazily: a ~0.3 us round trip each time)
   asm volatile("" :: "s"(zero_buf), "s"(zero_n), "s"(acc), "s"(pro.h_in), "s"(pro.src.p), "s"(pro.norm_w), "s"(pro.h_out), "s"(pro.H),
                "s"(H), "s"(I), "s"(Wgu), "s"(Sgu), "s"(Zgu), "s"(Wd), "s"(Sd), "s"(Zd));
-  // diagnostic instantiation only (bz_tune_mlp): s_memrealtime (100 MHz) per wave at phase boundaries, kept in scalar registers and stored
-  // once at the end (a store per stamp would sit in every later vmcnt wait)
-  unsigned long long T[15];
-#define MSTAMP(i) do { if (DIAG) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(T[i]) :: "memory"); \
-    __builtin_amdgcn_sched_barrier(0); } } while (0)
-#pragma unroll
-  for (int i = 0; i < 15; i++) T[i] = 0;
-  MSTAMP(0);
   static_assert(GPW * NW * 128 == NP * 64 * 8, "the prologue half covers the row with eight elements per thread");
   const uint4* wg = Wgu + ((size_t)sl * (H >> 5) + gbeg * 4) * 64 + lane;
   const uint4* wu = Wgu + ((size_t)(NTI + sl) * (H >> 5) + gbeg * 4) * 64 + lane;
@@ -393,7 +385,6 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
     Ag[0] = ldnt(wg); Au[0] = ldnt(wu);
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();                     // the counters are zero (nobody waits for data here)
-    MSTAMP(1);
     // (2p) h' = R(h + R(prev)), sum of squares (exact: double), 1 / rms
     float v[8] = {ha.x, ha.y, ha.z, ha.w, hb.x, hb.y, hb.z, hb.w};
     if (hasprev) {
@@ -411,7 +402,6 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
     if (NP == 8) ssd += ((dred[4] + dred[5]) + (dred[6] + dred[7]));
     const float ss = (float)ssd;                  // the rounded exact sum of squares (oracle: orc_rms_norm)
     const float rs = rms_scale(ss, (float)H, pro.eps);
-    MSTAMP(2);
     // (3p) x = R(w R(h' rs)) in registers -> the octet's six plane words, the group's sums (16 threads)
     const float nwv[8] = {na.x, na.y, na.z, na.w, nb.x, nb.y, nb.z, nb.w};
     float x[8];
@@ -434,7 +424,6 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);                                   // lgkmcnt(0): this wave's LDS stores are done
     if (lane == 0) atomicAdd((unsigned*)&cnt[1], 1u);
-    MSTAMP(4);
     // (4p) the rest of this wave's stream
 #pragma unroll
     for (int c = 1; c < 8; c++) { Ag[c] = ldnt(wg + c * 64); Au[c] = ldnt(wu + c * 64); }
@@ -443,10 +432,7 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
     __syncthreads();                     // the counters are zero
 #pragma unroll
     for (int c = 0; c < 8; c++) { Ag[c] = ldnt(wg + c * 64); Au[c] = ldnt(wu + c * 64); }
-    MSTAMP(1);
     zero_duty<NP * 64>(zero_buf, zero_n);   // (threads 0 .. NP*64-1 are exactly the streamers)
-    MSTAMP(2);
-    MSTAMP(4);
   }
   float sg[2], su[2]; int zg[2], zu[2];
 #pragma unroll
@@ -461,12 +447,8 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
   float sd[TPW]; int zd[TPW];
 #pragma unroll
   for (int b = 0; b < 2; b++) {
-    if (b == 0) MSTAMP(5);
-    if (b == 1) MSTAMP(7);
     if (b == 0) q4g_consume2_at<0>(Ag, Au, gbeg, xpl, gpar, sg[0], zg[0], su[0], zu[0], yg, yu);
     else q4g_consume2_at<4>(Ag, Au, gbeg + 1, xpl, gpar, sg[1], zg[1], su[1], zu[1], yg, yu);
-    if (b == 0) MSTAMP(6);
-    if (b == 1) MSTAMP(8);
     if (b == 0) {
 #pragma unroll
       for (int q = 0; q < TPW; q++) {
@@ -475,7 +457,6 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
       }
     }
   }
-  MSTAMP(9);
   part[wave * 128 + lane] = yg;
   part[wave * 128 + 64 + lane] = yu;
   // the slab's scales / zero points (L2-resident): requested here, under the partial-sum barrier and the tail -- eight registers less across the second group's dots
@@ -485,7 +466,6 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
     sd[q] = __half2float(Sd[si]); zd[q] = Zd[si];
   }
   __syncthreads();
-  MSTAMP(10);
   // (6) wave 0: sum of the waves' k-range partials (exact, fixed order), ONE rounding to f32 (the oracle's definition), + bias, R, SiLU * up,
   //     and the 64 values' planes -- one value per lane, an octet = 8 lanes
   if (wave == 0) {
@@ -519,7 +499,6 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
     if (lane == 0) { apar[0] = make_int4(__float_as_int(cs), sp[0], sp[1], sp[2]); apar[1] = make_int4(sp[3], sp[4], sp[5], xq_pack_low(sp[6], sp[7], lowfl)); }
   }
   __syncthreads();
-  MSTAMP(11);
   // (7) this wave's down slab
 #pragma unroll
   for (int q = 0; q < TPW; q++) {
@@ -527,17 +506,8 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
     q4g_consume_n<2>(D[q], 0, 0, apl, apar, sd[q], zd[q], y);
     const int n = (tbeg + q) * 64 + lane;
     if (bd != nullptr && sl == 0) y += (double)bd[n];
-    if (q == 0) MSTAMP(12);
     atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, ACT));
   }
-  MSTAMP(13);
-  if (DIAG) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-  MSTAMP(14);
-  if (DIAG && pro.stamps && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 113)) {
-#pragma unroll
-    for (int i = 0; i < 15; i++) pro.stamps[((blockIdx.x ? 1 : 0) * 16 + wave) * 16 + i] = (long long)((i == 3) ? T[2] : T[i]);
-  }
-#undef MSTAMP
 }
 
 static size_t mlp_smem(int H) { return (size_t)(H >> 5) * XQ_NP * 16 + (size_t)(H >> 7) * 32 + 16 * 128 * 8 + 2 * XQ_NP * 16 + 32 + 16 * 8 + 64; }   // planes, gpar, part, apl, apar, dred, counters
@@ -551,12 +521,11 @@ int bzk_mlp_q4g(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, 
   if (!bzk_mlp_fusable(gu, dn, H, I) || pro.act != BZ_F16) BZ_FAIL(BZ_E_INVALID, "fused MLP does not apply to this shape / activation dtype");
   const size_t smem = mlp_smem(H);
   const double bytes = (double)gu.algo_bytes + (double)dn.algo_bytes;
-#define LAUNCH_MLP(FIX, GP, TP, W_, DG) BZ_LAUNCH("mlp_q4g<norm+gate/up+silu+down>", bytes, (k_mlp_q4g<FIX, GP, TP, W_, BZ_F16, DG>), dim3(I / 64), dim3(W_ * 64), smem, s, \
+#define LAUNCH_MLP(FIX, GP, TP, W_) BZ_LAUNCH("mlp_q4g<norm+gate/up+silu+down>", bytes, (k_mlp_q4g<FIX, GP, TP, W_, BZ_F16>), dim3(I / 64), dim3(W_ * 64), smem, s, \
     (const uint4*)gu.w, (const __half*)gu.scales, (const unsigned char*)gu.zeros, gu.bias, (const uint4*)dn.w, (const __half*)dn.scales,            \
     (const unsigned char*)dn.zeros, dn.bias, H, I, pro, acc, zero_buf, zero_n)
-  if (H == 4096 && pro.stamps) LAUNCH_MLP(1, 2, 4, 16, 1);     // diagnostic build (bz_tune_mlp)
-  else if (H == 4096) { if (pro.src.fix) LAUNCH_MLP(1, 2, 4, 16, 0); else LAUNCH_MLP(0, 2, 4, 16, 0); }
-  else { if (pro.src.fix) LAUNCH_MLP(1, 2, 4, 8, 0); else LAUNCH_MLP(0, 2, 4, 8, 0); }
+  if (H == 4096) { if (pro.src.fix) LAUNCH_MLP(1, 2, 4, 16); else LAUNCH_MLP(0, 2, 4, 16); }
+  else { if (pro.src.fix) LAUNCH_MLP(1, 2, 4, 8); else LAUNCH_MLP(0, 2, 4, 8); }
 #undef LAUNCH_MLP
   BZ_HIP(hipGetLastError());
   return BZ_OK;
@@ -581,10 +550,6 @@ __global__ __launch_bounds__(256) void k_gemv_q4g(const uint4* __restrict__ W, c
   const bool wave_on = nt * 64 < N;
   const int G = K >> 7;
   const int k0 = ks * KR, g0 = ks * GW;
-  // diagnostic build only (BZ_QKV_STAMPS): s_memrealtime (100 MHz) at phase boundaries of the first and the last block
-#define QSTAMP(i) do { if (pro.stamps && threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1)) \
-    pro.stamps[(blockIdx.x == 0 ? 0 : 8) + (i)] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
-  QSTAMP(0);
 
   zero_duty<256>(zero_buf, zero_n);
 
@@ -615,10 +580,8 @@ __global__ __launch_bounds__(256) void k_gemv_q4g(const uint4* __restrict__ W, c
     for (int c = 0; c < 4; c++) Wb[b][c] = ldnt(wp + (bc * 4 + c) * 64);
   }
 
-  QSTAMP(1);
   // (4) finish the prologue
   xfinish<MODE, FIX, MAXJ, Q4G_E>(pro, KR, xr, xs, red, blockIdx.x == 0);
-  QSTAMP(2);
   {
     unsigned* sSw = (unsigned*)(sS + wave * GW * 64);
     unsigned* sZw = (unsigned*)(sZ + wave * GW * 64);
@@ -627,9 +590,8 @@ __global__ __launch_bounds__(256) void k_gemv_q4g(const uint4* __restrict__ W, c
 #pragma unroll
     for (int j = 0; j < 4; j++) if (lane + 64 * j < GW * 16) sZw[lane + 64 * j] = zreg[j];
   }
-  if (!(pro.dbg & 4)) quant_x128<256>(xs, KR, xpl, gpar);
+  quant_x128<256>(xs, KR, xpl, gpar);
   __syncthreads();
-  QSTAMP(3);
   if (!wave_on) return;
 
   // (5) stream the k-range with NPF groups (NPF * 4 KiB per wave) in flight
@@ -641,8 +603,7 @@ __global__ __launch_bounds__(256) void k_gemv_q4g(const uint4* __restrict__ W, c
       if (g < GW) {
         const float s = __half2float(sS[(wave * GW + g) * 64 + lane]);
         const int z = sZ[(wave * GW + g) * 64 + lane];
-        if (pro.dbg & 2) y += (double)__uint_as_float((Wb[b][0].x ^ Wb[b][1].y ^ Wb[b][2].z ^ Wb[b][3].w) & 0x007fffffu);
-        else q4g_consume(Wb[b], g, xpl, gpar, s, z, y);
+        q4g_consume(Wb[b], g, xpl, gpar, s, z, y);
         if (g + NPF < GW) {
 #pragma unroll
           for (int c = 0; c < 4; c++) Wb[b][c] = ldnt(wp + ((g + NPF) * 4 + c) * 64);
@@ -650,18 +611,14 @@ __global__ __launch_bounds__(256) void k_gemv_q4g(const uint4* __restrict__ W, c
       }
     }
   }
-  QSTAMP(4);
   const int n = nt * 64 + lane;
   if (bias != nullptr && ks == 0) y += (double)bias[n];
-  if (pro.dbg & 1) acc[n] = d2fix(y, pro.act);
-  else atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, pro.act));
-  QSTAMP(5);
-#undef QSTAMP
+  atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, pro.act));
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // "Slim" int4 GEMV with the fused residual + RMSNorm prologue, for the q/k/v projection (N ~ 6K, K = H).
-// The stamp timeline of k_gemv_q4g on this shape (scripts/qkv_stamps.py) shows where its 12.7 us go: 3 us to reach the first
+// The stamp timeline of k_gemv_q4g on this shape (a diagnostic build, since removed) shows where its 12.7 us go: 3 us to reach the first
 // instruction past the load issue, 4.3 us waiting for the prologue's 48 KB per block (h + the 64-bit fixed-point sums of the
 // previous launch: 600 blocks x 48 KB = 29 MB through ~10 B/clk/CU), 1.4 us quantising, 0.6 us of dot products.  The weights
 // were never the problem.  Here a block is 512 threads = 8 waves that share one 256-k slice (so a block quantises 256 activations)
@@ -670,10 +627,10 @@ __global__ __launch_bounds__(256) void k_gemv_q4g(const uint4* __restrict__ W, c
 // ---------------------------------------------------------------------------------------------------------
 // Wave roles (round 2, as in the fused MLP), 12 waves: waves 0-3 hold the row (8 NJ elements per thread), do the norm and build the slice's
 // planes; waves 4-11 own one 64-column tile each (8 KiB of weights, requested at entry) and do the dots once the planes are published.  The
-// halves meet through LDS counters.  Per-wave stamps (scripts/tune_qkv.py, profiles/r02_qkv_stamps.txt): a CU sustains ~27 GB/s, so the
+// halves meet through LDS counters.  Per-wave stamps (a diagnostic build, since removed): a CU sustains ~27 GB/s, so the
 // block's 64 KiB need ~2.4 us from the moment they are requested -- the launch is as long as [request -> data] + dots + atomic drain, and
 // everything else (the prologue's dependent loads, norm, planes: done at ~2.8 us) hides under it.
-template <int FIX, int NJ, int ACT, int DIAG = 0>     // NJ = H / 2048
+template <int FIX, int NJ, int ACT>     // NJ = H / 2048
 __global__ __launch_bounds__(768) void k_gemv_q4g_slim(const uint4* __restrict__ W, const __half* __restrict__ S, const unsigned char* __restrict__ Z,
                                                       const float* __restrict__ bias, int N, int H, Pro pro, long long* acc, long long* zero_buf, int zero_n) {
   __shared__ uint4 xpl[8 * XQ_NP];
@@ -687,14 +644,6 @@ __global__ __launch_bounds__(768) void k_gemv_q4g_slim(const uint4* __restrict__
   const int ksl = blockIdx.x % NKS, tg = blockIdx.x / NKS;
   asm volatile("" :: "s"(zero_buf), "s"(zero_n), "s"(acc), "s"(pro.h_in), "s"(pro.src.p), "s"(pro.norm_w), "s"(pro.h_out), "s"(pro.H),
                "s"(H), "s"(N), "s"(W), "s"(S), "s"(Z), "s"(bias));   // one scalar-load batch for all arguments
-  unsigned long long T[8];
-#define SSTAMP(i) do { if (DIAG) { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(T[i]) :: "memory"); \
-    __builtin_amdgcn_sched_barrier(0); } } while (0)
-#define SFLUSH() do { if (DIAG && pro.stamps && lane == 0 && (blockIdx.x == 0 || blockIdx.x == 97)) { \
-    _Pragma("unroll") for (int i = 0; i < 8; i++) pro.stamps[((blockIdx.x ? 1 : 0) * 12 + wave) * 8 + i] = (long long)T[i]; } } while (0)
-#pragma unroll
-  for (int i = 0; i < 8; i++) T[i] = 0;
-  SSTAMP(0);
   if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
   if (prolog) {
     // (1p) the row: octet j * 256 + pt of thread pt
@@ -717,7 +666,6 @@ __global__ __launch_bounds__(768) void k_gemv_q4g_slim(const uint4* __restrict__
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();                     // counters zeroed; the row's loads are all in the CU's queue AHEAD of the tile waves' weight loads
     __builtin_amdgcn_sched_barrier(0);
-    SSTAMP(1);
     // (2p) h' = R(h + R(prev)), exact sum of squares
     float v[NJ][8];
     double ssd = 0.0;
@@ -734,11 +682,9 @@ __global__ __launch_bounds__(768) void k_gemv_q4g_slim(const uint4* __restrict__
       }
     }
     ssd = wave_sum_d(ssd);
-    SSTAMP(2);
     if (lane == 0) { red[wave] = ssd; __builtin_amdgcn_s_waitcnt(0xc07f); atomicAdd((unsigned*)&cnt[0], 1u); }
     if (p0 / 64 == wave) {               // only the wave that holds the slice goes on (wave-uniform)
       lds_wait_count(&cnt[0], 4);
-      SSTAMP(3);
       const float ss = (float)((red[0] + red[1]) + (red[2] + red[3]));
       const float rs = rms_scale(ss, (float)H, pro.eps);
       float sv[8];
@@ -770,9 +716,7 @@ __global__ __launch_bounds__(768) void k_gemv_q4g_slim(const uint4* __restrict__
       }
       __builtin_amdgcn_s_waitcnt(0xc07f);
       if (lane == 0) atomicAdd((unsigned*)&cnt[1], 1u);
-      SSTAMP(4);
     }
-    SFLUSH();
     return;
   }
   // (1s) tile waves: the rendezvous, then the tile's weights
@@ -787,153 +731,20 @@ __global__ __launch_bounds__(768) void k_gemv_q4g_slim(const uint4* __restrict__
   for (int c = 0; c < 8; c++) Q[c] = ldnt(wq + c * 64);
 #pragma unroll
   for (int b = 0; b < 2; b++) { const size_t ix = ((size_t)tqc * G + ksl * 2 + b) * 64 + lane; sq[b] = __half2float(S[ix]); zq[b] = Z[ix]; }
-  SSTAMP(1);
   if (zero_buf)
     for (int i = blockIdx.x * 512 + (tid - 256); i < zero_n; i += gridDim.x * 512) zero_buf[i] = 0;
   lds_wait_count(&cnt[1], 1);
-  SSTAMP(4);
   if (q_on) {
     double y = 0.0;
 #pragma unroll
     for (int b = 0; b < 2; b++) {
       if (b == 0) q4g_consume_at<0, 4>(Q, 0, 0, xpl, gpar, sq[0], zq[0], y);
       else q4g_consume_at<4, 4>(Q, 4, 2, xpl, gpar, sq[1], zq[1], y);
-      if (b == 0) SSTAMP(5);
     }
     const int n = tq * 64 + lane;
     if (bias != nullptr && ksl == 0) y += (double)bias[n];
     atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, ACT));
   }
-  SSTAMP(6);
-  if (DIAG) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-  SSTAMP(7);
-  SFLUSH();
-#undef SSTAMP
-#undef SFLUSH
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// int4 GEMV with the fused residual + RMSNorm prologue, FULL K per workgroup, direct output (the q/k/v projection of the decode step).
-// The slim kernel above splits K over 16 workgroups per tile group: 49 k 64-bit atomics whose drain the launch waits for (~1.5 us), and a
-// consumer that reads 8-byte fixed point.  Here a workgroup owns ONE 64-column tile over the whole K: its NW waves take 256 k each
-// (8 KiB of weights per wave), meet through LDS, and the block stores 64 finished values -- no atomics, nothing to zero, the attention
-// kernel reads plain f32.  N / 64 workgroups (96 for Llama-3-8B) leave most CUs idle, but the launch is a latency chain, not a stream:
-// 13 MB over 96 CUs is ~2 us, hidden under the prologue's dependent loads.  Same wave roles as the fused MLP: the first half requests its
-// weights at entry, the second half holds the row (an octet per thread), does the norm and publishes the nibble planes.
-// ---------------------------------------------------------------------------------------------------------
-template <int FIX, int NW, int ACT>     // H = NW * 256
-__global__ __launch_bounds__(NW * 64) void k_gemv_q4g_cols(const uint4* __restrict__ W, const __half* __restrict__ S, const unsigned char* __restrict__ Z,
-                                                          const float* __restrict__ bias, int N, int H, Pro pro, float* __restrict__ out, long long* zero_buf, int zero_n) {
-  constexpr int NP = NW / 2;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  uint4* xpl = (uint4*)smem;                       // [H/32 chunks][6 planes]
-  const int G = H >> 7;
-  int4* gpar = (int4*)(xpl + (H >> 5) * XQ_NP);    // [2G]
-  double* part = (double*)(gpar + 2 * G);          // [NW][64]
-  double* dred = part + NW * 64;                   // [NP]
-  volatile unsigned* cnt = (volatile unsigned*)(dred + NW);
-  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const bool prolog = wave >= NP;
-  const int tile = blockIdx.x;
-  asm volatile("" :: "s"(zero_buf), "s"(zero_n), "s"(out), "s"(pro.h_in), "s"(pro.src.p), "s"(pro.norm_w), "s"(pro.h_out), "s"(H), "s"(N), "s"(W), "s"(S), "s"(Z), "s"(bias));
-  const uint4* wq = W + ((size_t)tile * (H >> 5) + wave * 8) * 64 + lane;
-  uint4 Q[8];
-  if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
-  if (prolog) {
-    const bool hasprev = pro.src.p != nullptr;
-    const void* prevp = hasprev ? pro.src.p : (const void*)pro.h_in;
-    const int i0 = (tid - NP * 64) * 8;
-    const float4 ha = *(const float4*)(pro.h_in + i0), hb = *(const float4*)(pro.h_in + i0 + 4);
-    typename RawT<FIX>::T pv[8];
-#pragma unroll
-    for (int e = 0; e < 8; e++) pv[e] = vraw<FIX>(prevp, (FIX || hasprev) ? i0 + e : 0);
-    const float4 na = *(const float4*)(pro.norm_w + i0), nb = *(const float4*)(pro.norm_w + i0 + 4);
-    __builtin_amdgcn_sched_barrier(0);
-    Q[0] = ldnt(wq); Q[1] = ldnt(wq + 64);
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();                     // the counters are zero (nobody waits for data here)
-    float v[8] = {ha.x, ha.y, ha.z, ha.w, hb.x, hb.y, hb.z, hb.w};
-    if (hasprev) {
-#pragma unroll
-      for (int e = 0; e < 8; e++) v[e] = round_t<ACT>(v[e] + round_t<ACT>(FIX ? fix2f((long long)pv[e], ACT) : (float)pv[e]));
-    }
-    if (blockIdx.x == 0 && pro.h_out) { *(float4*)(pro.h_out + i0) = make_float4(v[0], v[1], v[2], v[3]); *(float4*)(pro.h_out + i0 + 4) = make_float4(v[4], v[5], v[6], v[7]); }
-    double ssd = 0.0;
-#pragma unroll
-    for (int e = 0; e < 8; e += 2) ssd += (double)(v[e] * v[e]) + (double)(v[e + 1] * v[e + 1]);
-    ssd = wave_sum_d(ssd);
-    if (lane == 0) { dred[wave - NP] = ssd; __builtin_amdgcn_s_waitcnt(0xc07f); atomicAdd((unsigned*)&cnt[0], 1u); }
-    lds_wait_count(&cnt[0], NP);
-    ssd = ((dred[0] + dred[1]) + (dred[2] + dred[3]));
-    if (NP == 8) ssd += ((dred[4] + dred[5]) + (dred[6] + dred[7]));
-    const float rs = rms_scale((float)ssd, (float)H, pro.eps);
-    const float nwv[8] = {na.x, na.y, na.z, na.w, nb.x, nb.y, nb.z, nb.w};
-    float x[8];
-    float am = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; e++) { x[e] = round_t<ACT>(nwv[e] * round_t<ACT>(v[e] * rs)); am = fmaxf(am, fabsf(x[e])); }
-    am = grp_reduce<16, OpMax>(am);
-    unsigned w[XQ_NP]; int sp[XQ_NP]; float cs;
-    xq_split8(x, am, w, sp, cs);
-#pragma unroll
-    for (int p = 0; p < XQ_NP; p++) sp[p] = grp_reduce<16, OpAdd>(sp[p]);
-    const int4 g2w = xq_gpar_hi<16>(w, sp);
-    const int oct = tid - NP * 64;
-    unsigned* plw = (unsigned*)xpl + ((oct >> 2) * XQ_NP) * 4 + (oct & 3);
-#pragma unroll
-    for (int p = 0; p < XQ_NP; p++) plw[p * 4] = w[p];
-    if ((lane & 15) == 0) {
-      gpar[2 * (oct >> 4)] = make_int4(__float_as_int(cs), sp[0], sp[1], sp[2]);
-      gpar[2 * (oct >> 4) + 1] = g2w;
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    if (lane == 0) atomicAdd((unsigned*)&cnt[1], 1u);
-#pragma unroll
-    for (int c = 2; c < 8; c++) Q[c] = ldnt(wq + c * 64);
-  } else {
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 8; c++) Q[c] = ldnt(wq + c * 64);
-    if (zero_buf)
-      for (int i = blockIdx.x * (NP * 64) + tid; i < zero_n; i += gridDim.x * (NP * 64)) zero_buf[i] = 0;
-  }
-  float sq[2]; int zq[2];
-#pragma unroll
-  for (int b = 0; b < 2; b++) { const size_t ix = ((size_t)tile * G + wave * 2 + b) * 64 + lane; sq[b] = __half2float(S[ix]); zq[b] = Z[ix]; }
-  lds_wait_count(&cnt[1], NP);
-  double y = 0.0;
-#pragma unroll
-  for (int b = 0; b < 2; b++) {
-    if (b == 0) q4g_consume_at<0, 4>(Q, (wave * 2) * 4, 2 * (wave * 2), xpl, gpar, sq[0], zq[0], y);
-    else q4g_consume_at<4, 4>(Q, (wave * 2 + 1) * 4, 2 * (wave * 2 + 1), xpl, gpar, sq[1], zq[1], y);
-  }
-  part[wave * 64 + lane] = y;
-  __syncthreads();
-  if (tid < 64) {
-    double t = 0.0;
-#pragma unroll
-    for (int w2 = 0; w2 < NW; w2++) t += part[w2 * 64 + tid];
-    float f = (float)t;                      // ONE rounding of the exact dot product (the oracle's definition)
-    const int n = tile * 64 + tid;
-    if (bias) f += bias[n];
-    out[n] = round_t<ACT>(f);
-  }
-}
-static size_t q4g_cols_smem(int H) { return (size_t)(H >> 5) * XQ_NP * 16 + (size_t)(H >> 7) * 32 + 16 * 64 * 8 + 16 * 8 + 64; }
-bool bzk_gemv_cols_ok(const LinearDev& L, const Pro& pro, int act) {
-  static const bool off = getenv("BZ_COLS_QKV") == nullptr;   // opt-in: measured slower than the slim kernel (7.8 vs 6.8 us: a CU sustains ~27 GB/s, 96 CUs x 128 KiB take longer than 192 x 64 KiB)
-  return !off && act == BZ_F16 && L.kind == LK_Q4G && !L.perm && pro.mode == PRO_NORM && pro.perm == nullptr && L.K == pro.H && (L.K == 2048 || L.K == 4096) && L.N % 64 == 0 &&
-         L.N <= 16384 && !pro.dbg && !pro.stamps;
-}
-int bzk_gemv_cols(hipStream_t s, const LinearDev& L, const Pro& pro, float* out, long long* zero_buf, int zero_n) {
-  const size_t smem = q4g_cols_smem(L.K);
-#define LAUNCH_COLS(FIX, NW_) BZ_LAUNCH("gemv_q4g<norm,cols>", L.algo_bytes, (k_gemv_q4g_cols<FIX, NW_, BZ_F16>), dim3(L.N / 64), dim3(NW_ * 64), smem, s, (const uint4*)L.w, \
-    (const __half*)L.scales, (const unsigned char*)L.zeros, L.bias, L.N, L.K, pro, out, zero_buf, zero_n)
-  if (L.K == 4096) { if (pro.src.fix) LAUNCH_COLS(1, 16); else LAUNCH_COLS(0, 16); }
-  else { if (pro.src.fix) LAUNCH_COLS(1, 8); else LAUNCH_COLS(0, 8); }
-#undef LAUNCH_COLS
-  BZ_HIP(hipGetLastError());
-  return BZ_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1026,7 +837,7 @@ int bzk_gemm_q4g_rows(hipStream_t s, const LinearDev& L, int xdt, const void* x1
 bool bzk_gemv_slim_ok(const LinearDev& L, const Pro& pro) {
   static const bool off = getenv("BZ_NO_SLIM_QKV") != nullptr;
   return !off && L.kind == LK_Q4G && !L.perm && pro.mode == PRO_NORM && pro.perm == nullptr && L.K == pro.H && (L.K == 2048 || L.K == 4096 || L.K == 8192) && L.N % 64 == 0 &&
-         L.N <= 16384 && !pro.dbg;
+         L.N <= 16384;
 }
 
 // =========================================================================================================
@@ -1730,7 +1541,7 @@ int bzk_mlp_gq(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, i
 
 bool bzk_gq_slim_ok(const LinearDev& L, const Pro& pro) {
   static const bool off = getenv("BZ_NO_GQ_SLIM") != nullptr;
-  if (off || (L.kind != LK_Q4K && L.kind != LK_Q6K) || pro.perm != nullptr || pro.dbg || pro.stamps || L.N % 64 || L.K % 256) return false;
+  if (off || (L.kind != LK_Q4K && L.kind != LK_Q6K) || pro.perm != nullptr || L.N % 64 || L.K % 256) return false;
   if (pro.mode == PRO_NORM) return L.K == pro.H && (L.K == 2048 || L.K == 4096 || L.K == 8192);
   if (pro.mode == PRO_SILU) return L.K == pro.H;
   return false;
@@ -2077,10 +1888,7 @@ __global__ __launch_bounds__(ROUTE ? 832 : 768) void k_gemv_rows2(const void* __
     ub[r] = (segA + 1) * NRG;                      // first unit of the second segment
   }
   const int act = pro.act;
-  // diagnostic only (BZ_MOE_STAMPS): s_memrealtime (100 MHz) of workgroup 0 -- row wave 0: entry, rendezvous, x published, top-k done; tile wave 4: range 0 done, ids seen, end
-#define RSTAMP(i) do { if (ROUTE && pro.stamps && blockIdx.x == 0 && lane == 0) pro.stamps[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
   if (tid == 0) { cnt[0] = 0; cnt[1] = 0; cnt[2] = 0; cnt[3] = 0; }
-  if (wave == 0) RSTAMP(0);
   if (ROUTE && wave == 12) {
     // ---- the routing wave (13th): logits -> softmax + top-k -> expert ids for the tile waves' second range; nobody waits for it before that
     __builtin_amdgcn_s_setprio(3);
@@ -2090,7 +1898,6 @@ __global__ __launch_bounds__(ROUTE ? 832 : 768) void k_gemv_rows2(const void* __
     moe_softmax_topk(lgs, route.E, route.top_k, route.n_shared, route.routed_scale, route.norm_topk, ssel, swgt, lane);
     __builtin_amdgcn_s_waitcnt(0xc07f);
     if (lane == 0) atomicAdd(&cnt[2], 1u);
-    RSTAMP(3);
     if (blockIdx.x == 0)
       for (int j = lane; j < route.top_k + route.n_shared; j += 64) { route.sel_out[j] = ssel[j]; route.w_out[j] = swgt[j]; }
     return;
@@ -2129,7 +1936,6 @@ __global__ __launch_bounds__(ROUTE ? 832 : 768) void k_gemv_rows2(const void* __
           __builtin_amdgcn_sched_barrier(0);
           __syncthreads();                         // rendezvous: these loads are ahead of the weight stream
           first = false;
-          if (wave == 0) RSTAMP(1);
         }
 #pragma unroll
         for (int j = 0; j < 2; j++) {
@@ -2209,7 +2015,6 @@ __global__ __launch_bounds__(ROUTE ? 832 : 768) void k_gemv_rows2(const void* __
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);            // lgkmcnt(0): this wave's part of x is in LDS
     if (lane == 0) atomicAdd(&cnt[1], 1u);
-    if (wave == 0) RSTAMP(2);
     if (shift.cs)                                  // the row waves are done: they take the side duty
       for (int i = blockIdx.x * 256 + tid; i < shift.n; i += gridDim.x * 256) conv_shift_one(shift, i, act);
     return;
@@ -2225,7 +2030,7 @@ __global__ __launch_bounds__(ROUTE ? 832 : 768) void k_gemv_rows2(const void* __
     size_t eoffA = 0, eoffB = 0;
     if (ROUTE) {
       if (r == 0) { eoffA = (size_t)(route.E + slA[0]) * (size_t)slots.expert_stride; eoffB = (size_t)(route.E + slB[0]) * (size_t)slots.expert_stride; }
-      else { if (tw == 0) RSTAMP(4); lds_wait_count(&cnt[2], 1); if (tw == 0) RSTAMP(5); eoffA = (size_t)ssel[slA[1]] * (size_t)slots.expert_stride; eoffB = (size_t)ssel[slB[1]] * (size_t)slots.expert_stride; }
+      else { lds_wait_count(&cnt[2], 1); eoffA = (size_t)ssel[slA[1]] * (size_t)slots.expert_stride; eoffB = (size_t)ssel[slB[1]] * (size_t)slots.expert_stride; }
     } else if (slots.sel) { eoffA = (size_t)slots.sel[slA[0]] * (size_t)slots.expert_stride; eoffB = (size_t)slots.sel[slB[0]] * (size_t)slots.expert_stride; }
     const int ubr = ub[r], kA = kcA[r], kB = kcB[r];
     auto issue = [&](Stage& S, int u) {
@@ -2286,8 +2091,6 @@ __global__ __launch_bounds__(ROUTE ? 832 : 768) void k_gemv_rows2(const void* __
       }
     }
   }
-  if (tw == 0) RSTAMP(6);
-#undef RSTAMP
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2706,11 +2509,10 @@ int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& o
   if (L.kind == LK_Q4G && act == BZ_F16 && bzk_gemv_slim_ok(L, pro)) {
     if (!out.acc) BZ_FAIL(BZ_E_INVALID, "int4 gemv needs a fixed-point accumulator");
     const int nks = L.K / 256, ntg = (L.N / 64 + 7) / 8;
-#define LAUNCH_SLIM(FIX, NJ, DG) BZ_LAUNCH("gemv_q4g<norm>", L.algo_bytes, (k_gemv_q4g_slim<FIX, NJ, BZ_F16, DG>), dim3(nks * ntg), dim3(768), 0, s, (const uint4*)L.w, \
+#define LAUNCH_SLIM(FIX, NJ) BZ_LAUNCH("gemv_q4g<norm>", L.algo_bytes, (k_gemv_q4g_slim<FIX, NJ, BZ_F16>), dim3(nks * ntg), dim3(768), 0, s, (const uint4*)L.w, \
     (const __half*)L.scales, (const unsigned char*)L.zeros, L.bias, L.N, L.K, pro, out.acc, out.zero_buf, out.zero_n)
-#define LAUNCH_SLIM_NJ(FIX) do { if (L.K == 2048) LAUNCH_SLIM(FIX, 1, 0); else if (L.K == 4096) LAUNCH_SLIM(FIX, 2, 0); else LAUNCH_SLIM(FIX, 4, 0); } while (0)
-    if (pro.stamps && L.K == 4096 && pro.src.fix) LAUNCH_SLIM(1, 2, 1);   // diagnostic build (bz_tune_gemv flag 16)
-    else if (pro.src.fix) LAUNCH_SLIM_NJ(1); else LAUNCH_SLIM_NJ(0);
+#define LAUNCH_SLIM_NJ(FIX) do { if (L.K == 2048) LAUNCH_SLIM(FIX, 1); else if (L.K == 4096) LAUNCH_SLIM(FIX, 2); else LAUNCH_SLIM(FIX, 4); } while (0)
+    if (pro.src.fix) LAUNCH_SLIM_NJ(1); else LAUNCH_SLIM_NJ(0);
 #undef LAUNCH_SLIM_NJ
 #undef LAUNCH_SLIM
     BZ_HIP(hipGetLastError());
@@ -3238,7 +3040,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
   constexpr int half = HD / 2, NPC = HD / 8, RPL = 64 / NPC, PW = 256 / NW, NL = PW / RPL, OW = NW > 8 ? 8 : NW, NTH = NW * 64;   // OW waves carry o_proj tiles
   asm volatile("" :: "s"(a.zero_buf), "s"(a.zero_n), "s"(a.kv.k), "s"(a.kv.v), "s"(a.kv.cap), "s"(a.kv.layer_stride), "s"(a.layer), "s"(a.act),
                "s"(a.interleaved), "s"(a.rope_cur), "s"(a.qkv.p), "s"(a.qkv.fix), "s"(a.nq), "s"(a.nkv), "s"(a.q_only), "s"(a.pos), "s"(W), "s"(S),
-               "s"(Z), "s"(bias), "s"(CS), "s"(acc), "s"(a.out), "s"(a.stamps), "s"(a.kv.bs), "s"(a.kv.n_kv));   // one scalar-load batch for all arguments
+               "s"(Z), "s"(bias), "s"(CS), "s"(acc), "s"(a.out), "s"(a.kv.bs), "s"(a.kv.n_kv));   // one scalar-load batch for all arguments
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned* q2 = (unsigned*)smem;             // [64] packed q pairs
   unsigned* k2 = q2 + 64;                     // [64] packed new key
@@ -3253,8 +3055,6 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
   const int hq = FUSE ? blockIdx.x / CS : blockIdx.x, cs = FUSE ? blockIdx.x % CS : 0, kvh = hq / rep;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int piece = lane % NPC, rsub = lane / NPC;
-#define STAMP(i) do { if (a.stamps && blockIdx.x == 0 && tid == 0) a.stamps[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
-  STAMP(0);
   const KvView& kv = a.kv;
   // (0) the position word: issued first, needed late
   const int pos_v = a.pos[0];
@@ -3342,7 +3142,6 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
       }
     }
   }
-  STAMP(1);
   // (2) q/k/v finishing: fixed point -> f32, rounding, RoPE; packed q / new key / new value to LDS; KV append
   const float px0 = vsrc_finish(fixq, r0l, r0h, a.act), px1 = vsrc_finish(fixq, r1l, r1h, a.act);
   if (!a.q_only) {
@@ -3369,7 +3168,6 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
     if (tid < half) q2[tid] = pack2<KVDT>(px0, px1);
     __syncthreads();
   }
-  STAMP(2);
 
   // Exact sums, two passes (the oracle's definition, oracle/orc_ops.c: orc_attn_decode): score = f32(sum q k) * scale with the sum carried in double over exact
   // products; the maximum over ALL positions first, then p = exp(score - max) (bz_expf), L = f32(sum p), O = f32(sum p v), both sums in double -- order-independent
@@ -3409,7 +3207,6 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
     for (int i = 0; i < NL; i++) Mw = fmaxf(Mw, sc_[i]);
   }
   Mw = wave_max(Mw);
-  STAMP(3);
   if (lane == 0) wred[wave] = Mw;
   __syncthreads();
   float Mall = wred[0];
@@ -3455,14 +3252,12 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
     if (NPC == 8) accv[q] += dpp_get<DPP_ROR8>(accv[q]);
     accv[q] = xrow32_d(xrow16_d(accv[q]));
   }
-  STAMP(4);
   if (lane < NPC) {
 #pragma unroll
     for (int q = 0; q < 8; q++) pout[wave * HD + piece * 8 + q] = accv[q];
   }
   if (lane == 0) lred[wave] = lsum;
   __syncthreads();
-  STAMP(5);
   float Orun = 0.f, Lrun = 1.f;
   if (tid < HD) {
     double oc = 0.0, Lc = 0.0;
@@ -3507,10 +3302,8 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
     }
   }
   __syncthreads();
-  STAMP(6);
   quant_x128<NW * 64>(outh, HD, xpl, gpar);
   __syncthreads();
-  STAMP(7);
 #pragma unroll
   for (int t = 0; t < (FUSE == 1 ? TPW : 1); t++) {
     double y = 0.0;
@@ -3519,8 +3312,6 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
     if (bias != nullptr && hq == 0) y += (double)bias[n];
     if (wave < OW) atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, a.act));
   }
-  STAMP(8);
-#undef STAMP
 }
 
 
@@ -4888,13 +4679,11 @@ __global__ __launch_bounds__(256) void k_mla_merge(MlaArgs a) {
 
 // ---------------------------------------------------------------------------------------------------------
 // EXACT decode MLA (round 3): k_mla_attn<SPLIT> / k_mla_merge with every sum as the oracle defines it (orc_dsv2.c: exactly rounded -- double over exact products, one
-// rounding to f32) and ONE maximum over the whole context: the context slices of a head exchange their local maxima through a device word and wait for each other
-// (all n_heads x nsplit workgroups are resident: one per CU), so that p_t = exp(s_t - M) is the oracle's weight and the slices' partial sums simply add up in double
-// -- the f32 form rescales slice partials by exp(m_slice - M), which is not the same number.  rank <= 512, 16 waves, 16-bit cache / kv_b.
-//   ws (double): [n_heads][nsplit][rank + 1] = partial latent sums | partial weight sum        sync (unsigned): [n_heads][2] = ordered-int maximum | arrivals (k_mla_merge_x resets both)
+// rounding to f32) and ONE maximum over the whole context: the context slices of a head write their scores and local maxima (k_mla_scores_x), and after the kernel
+// boundary every slice reads the maximum over all of them (k_mla_weights_x), so that p_t = exp(s_t - M) is the oracle's weight and the slices' partial sums simply
+// add up in double -- the f32 form rescales slice partials by exp(m_slice - M), which is not the same number.  rank <= 512, 16 waves, 16-bit cache / kv_b.
+//   ws (double): [n_heads][nsplit][rank + 1] = partial latent sums | partial weight sum
 // ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned f2ord(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }     // order-preserving map
-__device__ __forceinline__ float ord2f(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
 template <int NW> __device__ __forceinline__ double block_sum_nw_d(double v, double* redd) {   // deterministic; redd: LDS double[NW]
   v = wave_sum_d(v);
   if ((threadIdx.x & 63) == 0) redd[threadIdx.x >> 6] = v;
@@ -4904,183 +4693,6 @@ template <int NW> __device__ __forceinline__ double block_sum_nw_d(double v, dou
   for (int w = 0; w < NW; w++) t += redd[w];
   __syncthreads();
   return t;
-}
-template <int DT>
-__global__ __launch_bounds__(1024) void k_mla_attn_x(MlaArgs a, double* __restrict__ wsd, unsigned* __restrict__ sync, unsigned* __restrict__ err) {
-  constexpr int NW = 16, NTH = 1024, RIF = 8, TIF = 4;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int R = a.rank, DN = a.nope, DR = a.rope;
-  float* ccur = lds; float* kcur = ccur + R; float* qn = kcur + DR; float* qp = qn + DN; float* qabs = qp + DR;
-  double* partd = (double*)(qabs + R + ((2 * R + 2 * DR + DN) & 1));      // [NW][R], 8-byte aligned
-  double* redd = partd + NW * R;                                            // [NW]
-  float* red = (float*)(redd + NW); float* sc = red + 16;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, hd = blockIdx.x;
-  const int pos = a.pos[0], nc = pos;               // cached positions 0 .. pos - 1; the current token comes from LDS
-  const int ts = (nc + a.nsplit - 1) / a.nsplit;
-  const int tlo = min((int)blockIdx.y * ts, nc), thi = min(tlo + ts, nc);
-  const bool own_cur = (int)blockIdx.y == a.nsplit - 1;
-  const int nloc = thi - tlo + (own_cur ? 1 : 0);
-  const int QH = DN + DR, qoff = hd * QH, coff = a.n_heads * QH;
-  auto qsrc = [&](int i) -> float { return vsrc_get(a.qkv, i, a.act); };
-  auto csrc = [&](int i) -> float { return a.kva ? a.kva[i] : vsrc_get(a.qkv, coff + i, a.act); };
-  const size_t rowbase = (size_t)a.layer * a.kv.layer_stride;
-  const int Wd = R + DR;
-  auto rowoff = [&](int p) -> size_t {
-    if (a.kv.paged) return rowbase + ((size_t)a.kv.block_table[p / a.kv.bs] * a.kv.bs + (p % a.kv.bs)) * Wd;
-    return rowbase + (size_t)p * Wd;
-  };
-  const size_t wrow0 = (size_t)hd * (DN + a.vdim);
-  const int col = lane * 8;
-  const bool con = col < R;
-  const int colc = con ? col : 0;
-  // ---- qabs partials first (weights only depend on the head): wave w takes nope rows [w DN/16, (w+1) DN/16) ----
-  const int d0 = wave * (DN / NW), d1 = d0 + DN / NW;
-  float w0[RIF][8];
-#pragma unroll
-  for (int u = 0; u < RIF; u++) ld8t<DT>(a.wkvb, (wrow0 + (size_t)min(d0 + u, d1 - 1)) * R + colc, w0[u]);
-  __builtin_amdgcn_sched_barrier(0);
-  // ---- current token: latent norm (exact sum of squares), k_pe / q_pe rope, q_nope ----
-  const float* cr = a.cos_t + (size_t)pos * (DR / 2); const float* sr = a.sin_t + (size_t)pos * (DR / 2);
-  {
-    double ssd = 0.0;
-    for (int r = tid; r < R; r += NTH) { const float v = csrc(r); ccur[r] = v; ssd += (double)__fmul_rn(v, v); }
-    ssd = block_sum_nw_d<NW>(ssd, redd);
-    const float rs = rms_scale((float)ssd, (float)R, a.eps);
-    for (int r = tid; r < R; r += NTH) ccur[r] = round_act(__fmul_rn(a.kv_norm[r], round_act(__fmul_rn(ccur[r], rs), a.act)), a.act);
-  }
-  for (int j = tid; j < DR / 2; j += NTH) {
-    const float c = cr[j], s = sr[j];
-    const float k0 = csrc(R + 2 * j), k1 = csrc(R + 2 * j + 1);
-    kcur[2 * j] = round_act(rope_lo(k0, k1, c, s), a.act); kcur[2 * j + 1] = round_act(rope_hi(k0, k1, c, s), a.act);
-    const float x0 = qsrc(qoff + DN + 2 * j), x1 = qsrc(qoff + DN + 2 * j + 1);
-    qp[2 * j] = round_act(rope_lo(x0, x1, c, s), a.act); qp[2 * j + 1] = round_act(rope_hi(x0, x1, c, s), a.act);
-  }
-  for (int d = tid; d < DN; d += NTH) qn[d] = qsrc(qoff + d);
-  __syncthreads();
-  if (hd == 0 && blockIdx.y == 0) {
-    size_t wo;
-    if (a.kv.paged) { const int slot = a.kv.slot ? a.kv.slot[0] : (a.kv.block_table[pos / a.kv.bs] * a.kv.bs + pos % a.kv.bs); wo = rowbase + (size_t)slot * Wd; }
-    else wo = rowbase + (size_t)pos * Wd;
-    for (int i = tid; i < Wd; i += NTH) kv_st(a.kv.k, wo + i, a.kv.dtype, i < R ? ccur[i] : kcur[i - R]);
-  }
-  {
-    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // 16-bit q x 16-bit weight: the f32 product is exact, the double carries the sum
-    for (int d = d0; d < d1; d += RIF) {
-      if (d > d0) {
-#pragma unroll
-        for (int u = 0; u < RIF; u++) ld8t<DT>(a.wkvb, (wrow0 + (size_t)min(d + u, d1 - 1)) * R + colc, w0[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < RIF; u++) {
-        const float qd = (d + u < d1) ? qn[d + u] : 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; e++) acc[e] += (double)__fmul_rn(qd, w0[u][e]);
-      }
-    }
-    if (con)
-#pragma unroll
-      for (int e = 0; e < 8; e++) partd[wave * R + colc + e] = acc[e];
-  }
-  __syncthreads();
-  for (int r = tid; r < R; r += NTH) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < NW; w++) t += partd[w * R + r];
-    qabs[r] = round_act((float)t, a.act);
-  }
-  __syncthreads();
-  // ---- scores: wave w takes cached tokens tlo + w, + 16, ...; exact sums (f32 products of 16-bit values are exact) ----
-  float qa[8];
-  const float qpl = (lane < DR) ? qp[lane] : 0.f;
-#pragma unroll
-  for (int e = 0; e < 8; e++) qa[e] = con ? qabs[colc + e] : 0.f;
-  for (int t0 = tlo + wave; t0 < thi; t0 += NW * TIF) {
-    float cv[TIF][8], kp[TIF];
-#pragma unroll
-    for (int u = 0; u < TIF; u++) {
-      const size_t ro = rowoff(min(t0 + NW * u, thi - 1));
-      ld8t<DT>(a.kv.k, ro + colc, cv[u]);
-      kp[u] = ld1t<DT>(a.kv.k, ro + R + min(lane, DR - 1));
-    }
-#pragma unroll
-    for (int u = 0; u < TIF; u++) {
-      double dsum = (lane < DR) ? (double)__fmul_rn(qpl, kp[u]) : 0.0;
-#pragma unroll
-      for (int e = 0; e < 8; e++) dsum += (double)__fmul_rn(qa[e], cv[u][e]);
-      dsum = wave_sum_d(dsum);
-      if (lane == 0 && t0 + NW * u < thi) sc[t0 + NW * u - tlo] = __fmul_rn((float)dsum, a.scale);
-    }
-  }
-  if (own_cur && wave == 0) {
-    double dsum = (lane < DR) ? (double)__fmul_rn(qpl, kcur[lane]) : 0.0;
-    if (con)
-#pragma unroll
-      for (int e = 0; e < 8; e++) dsum += (double)__fmul_rn(qa[e], ccur[colc + e]);
-    dsum = wave_sum_d(dsum);
-    if (lane == 0) sc[thi - tlo] = __fmul_rn((float)dsum, a.scale);
-  }
-  __syncthreads();
-  // ---- the maximum over the WHOLE context: local maximum -> device word of the head -> wait for the other slices ----
-  float mx = -INFINITY;
-  for (int t = tid; t < nloc; t += NTH) mx = fmaxf(mx, sc[t]);
-  mx = wave_max(mx);
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  if (tid == 0) {
-    float m2 = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; w++) m2 = fmaxf(m2, red[w]);
-    unsigned* sw = sync + 2 * hd;
-    if (nloc > 0) __hip_atomic_fetch_max(sw, f2ord(m2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(sw + 1, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);       // release: the maximum above is visible to whoever sees this arrival
-    const long long t_start = (long long)__builtin_amdgcn_s_memrealtime();
-    bool ok = true;
-    while (__hip_atomic_load(sw + 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)a.nsplit) {
-      __builtin_amdgcn_s_sleep(1);
-      if ((long long)__builtin_amdgcn_s_memrealtime() - t_start > 2000000) { ok = false; break; }      // 20 ms at 100 MHz: a slice is missing -> flag, do not hang
-    }
-    if (!ok) atomicExch(err, 1u);
-    red[0] = ord2f(__hip_atomic_load(sw, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT));
-  }
-  __syncthreads();
-  const float M = red[0];
-  __syncthreads();
-  double psum = 0.0;
-  for (int t = tid; t < nloc; t += NTH) { const float pe = bz_expf(sc[t] - M); sc[t] = pe; psum += (double)pe; }
-  psum = block_sum_nw_d<NW>(psum, redd);
-  // ---- partial latent sum: sum_t p_t c_t in double (an f32 weight times a 16-bit value is exact in double) ----
-  {
-    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int t0 = tlo + wave; t0 < thi; t0 += NW * TIF) {
-      float cv[TIF][8];
-#pragma unroll
-      for (int u = 0; u < TIF; u++) ld8t<DT>(a.kv.k, rowoff(min(t0 + NW * u, thi - 1)) + colc, cv[u]);
-#pragma unroll
-      for (int u = 0; u < TIF; u++) {
-        const double pw = (t0 + NW * u < thi) ? (double)sc[t0 + NW * u - tlo] : 0.0;
-#pragma unroll
-        for (int e = 0; e < 8; e++) acc[e] = fma(pw, (double)cv[u][e], acc[e]);
-      }
-    }
-    if (own_cur && wave == 0) {
-      const double pw = (double)sc[thi - tlo];
-      if (con)
-#pragma unroll
-        for (int e = 0; e < 8; e++) acc[e] = fma(pw, (double)ccur[colc + e], acc[e]);
-    }
-    if (con)
-#pragma unroll
-      for (int e = 0; e < 8; e++) partd[wave * R + colc + e] = acc[e];
-  }
-  __syncthreads();
-  double* wsp = wsd + ((size_t)hd * a.nsplit + blockIdx.y) * (R + 1);
-  for (int r = tid; r < R; r += NTH) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < NW; w++) t += partd[w * R + r];
-    wsp[r] = t;
-  }
-  if (tid == 0) wsp[R] = psum;
 }
 template <int DT>
 __global__ __launch_bounds__(1024) void k_mla_scores_x(MlaArgs a, float* __restrict__ scw, float* __restrict__ mxw, int SCS) {
@@ -5273,9 +4885,9 @@ __global__ __launch_bounds__(1024) void k_mla_weights_x(MlaArgs a, const float* 
   }
   if (tid == 0) wsp[R] = psum;
 }
-// merge of the exact partials + Wuv: grid = (n_heads, 4); olat_h = R(f32(sum_s part_s) / f32(sum_s l_s)), out_h = R(f32(Wuv_h . olat_h)); workgroup (h, 0) resets the head's sync words
+// merge of the exact partials + Wuv: grid = (n_heads, 4); olat_h = R(f32(sum_s part_s) / f32(sum_s l_s)), out_h = R(f32(Wuv_h . olat_h))
 template <int DT>
-__global__ __launch_bounds__(256) void k_mla_merge_x(MlaArgs a, const double* __restrict__ wsd, unsigned* __restrict__ sync) {
+__global__ __launch_bounds__(256) void k_mla_merge_x(MlaArgs a, const double* __restrict__ wsd) {
   __shared__ float olat[512];
   __shared__ double lsh;
   const int R = a.rank, DN = a.nope, DV = a.vdim, NSP = a.nsplit;
@@ -5308,7 +4920,6 @@ __global__ __launch_bounds__(256) void k_mla_merge_x(MlaArgs a, const double* __
     }
     olat[r] = round_act(__fmul_rn((float)t, inv), a.act);
   }
-  if (blockIdx.y == 0 && tid == 0) { sync[2 * hd] = 0u; sync[2 * hd + 1] = 0u; }     // (0 = below every ordered float: the next step's atomicMax starts from it)
   __syncthreads();
   float qa[8];
 #pragma unroll
@@ -5336,25 +4947,23 @@ bool bzk_mla_x_ok(const MlaArgs& a, int max_len) {
   return a.batch == 0 && a.rank <= 512 && a.rank % 8 == 0 && a.nsplit > 1 && a.nsplit <= 62 && a.nope % 16 == 0 && a.vdim % 16 == 0 &&
          (a.wdt == BZ_F16 || a.wdt == BZ_BF16) && a.wdt == a.kv.dtype && bzk_mla_x_smem(a, max_len) <= 160 * 1024;
 }
-// exact decode MLA: wsd = n_heads * nsplit * (rank + 1) doubles, sync = 2 * n_heads zeroed words (+ err word)
-int bzk_mla_attn_x(hipStream_t s, const MlaArgs& a, int max_len, double* wsd, unsigned* sync, unsigned* err, float* scw, float* mxw) {
+// exact decode MLA in three launches (scores + slice maxima | weights + partial sums | merge): wsd = n_heads * nsplit * (rank + 1) doubles,
+// scw = n_heads * nsplit * (ceil(max_len / nsplit) + 1) floats, mxw = n_heads * nsplit floats
+int bzk_mla_attn_x(hipStream_t s, const MlaArgs& a, int max_len, double* wsd, float* scw, float* mxw) {
   if (!bzk_mla_x_ok(a, max_len)) BZ_FAIL(BZ_E_UNSUPPORTED, "mla_attn_x: shape not supported by the exact decode kernel");
   const size_t smem = bzk_mla_x_smem(a, max_len);
   const int SCS = (max_len + a.nsplit - 1) / a.nsplit + 1;             // scores per (head, slice) in the workspace
   const size_t smem_w = (size_t)(16 * a.rank + 16) * 8 + (size_t)SCS * 4 + 64;
   const double bytes = (double)a.n_heads * (a.nope + a.vdim) * a.rank * bz_dtype_size(a.wdt);
-  // one launch with the slices waiting for each other's maxima (BZ_MLA_X_WAIT=1), or three launches (scores + slice maxima | weights + partial sums | merge): the
-  // wait is a device word polled from a CU with loads in flight (13 us on V2-Lite), the extra kernel boundary costs less
-  static const bool wait_form = getenv("BZ_MLA_X_WAIT") != nullptr;
+  // (three launches replaced one launch whose slices waited for each other's maxima on a device word: the wait, polled from a CU with loads in flight, cost 13 us
+  // on V2-Lite; the extra kernel boundary costs less)
 #define LAUNCH_MX(DT) do { \
     static bool attr_done = false; \
-    if (!attr_done) { BZ_HIP(hipFuncSetAttribute((const void*)k_mla_attn_x<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-                      BZ_HIP(hipFuncSetAttribute((const void*)k_mla_scores_x<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
+    if (!attr_done) { BZ_HIP(hipFuncSetAttribute((const void*)k_mla_scores_x<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
                       BZ_HIP(hipFuncSetAttribute((const void*)k_mla_weights_x<DT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_done = true; } \
-    if (wait_form || !scw) BZ_LAUNCH("mla_attn<split,exact>", bytes, (k_mla_attn_x<DT>), dim3(a.n_heads, a.nsplit), dim3(1024), smem, s, a, wsd, sync, err); \
-    else { BZ_LAUNCH("mla_scores<exact>", bytes * a.nope / (a.nope + a.vdim), (k_mla_scores_x<DT>), dim3(a.n_heads, a.nsplit), dim3(1024), smem, s, a, scw, mxw, SCS); \
-           BZ_LAUNCH("mla_weights<exact>", 0.0, (k_mla_weights_x<DT>), dim3(a.n_heads, a.nsplit), dim3(1024), smem_w, s, a, (const float*)scw, (const float*)mxw, SCS, wsd); } \
-    BZ_LAUNCH("mla_merge<exact>", bytes * a.vdim / (a.nope + a.vdim), (k_mla_merge_x<DT>), dim3(a.n_heads, 4), dim3(256), 0, s, a, (const double*)wsd, sync); } while (0)
+    BZ_LAUNCH("mla_scores<exact>", bytes * a.nope / (a.nope + a.vdim), (k_mla_scores_x<DT>), dim3(a.n_heads, a.nsplit), dim3(1024), smem, s, a, scw, mxw, SCS); \
+    BZ_LAUNCH("mla_weights<exact>", 0.0, (k_mla_weights_x<DT>), dim3(a.n_heads, a.nsplit), dim3(1024), smem_w, s, a, (const float*)scw, (const float*)mxw, SCS, wsd); \
+    BZ_LAUNCH("mla_merge<exact>", bytes * a.vdim / (a.nope + a.vdim), (k_mla_merge_x<DT>), dim3(a.n_heads, 4), dim3(256), 0, s, a, (const double*)wsd); } while (0)
   if (a.wdt == BZ_F16) LAUNCH_MX(BZ_F16); else LAUNCH_MX(BZ_BF16);
 #undef LAUNCH_MX
   BZ_HIP(hipGetLastError());
@@ -5600,7 +5209,7 @@ static bool mla_split_on(const MlaArgs& a) {
 int bzk_mla_nsplit(int n_heads) {
   static const int env = getenv("BZ_MLA_NSPLIT") ? atoi(getenv("BZ_MLA_NSPLIT")) : 0;     // tuning override (1..62)
   if (env > 0) return std::min(env, 62);
-  // 8 context slices per head: with the exact decode kernel (k_mla_attn_x: the slices wait for each other's maxima) 8 measured 377 tok/s against 365 with 16 on V2-Lite at
+  // 8 context slices per head: with the exact decode kernel (then one launch whose slices waited for each other's maxima) 8 measured 377 tok/s against 365 with 16 on V2-Lite at
   // context ~580; the f32 kernels, which do not wait, preferred 16 (450 vs 439)
   return std::max(1, std::min(8, 256 / std::max(n_heads, 1)));
 }

@@ -8,7 +8,6 @@
 // within a 64-k tile, step s of lane half h takes k = 32 h + 8 s + j -- a lane reads 64 contiguous bytes of its row per tile; no transposes.
 //
 //   k_gemm_nt2        dense 16-bit GEMM, both operands global -> LDS by LDS-DMA (128 x 128 x 64 / 64 x 128 x 64 tiles, split-K, grouped MoE form)
-//   k_gemm_nt         the round-1 form (weights straight to registers, A through LDS), kept for A/B runs (BZ_GEMM_NT_WAVE_TILES)
 //   k_gemm_q4g_lds    W4A16: raw int4 chunks by LDS-DMA, exact (q - z) f16 fragments rebuilt per wave, f32 group scales (square and 64 x 256 wide form)
 //   k_gemm_q4g_mfma   W4A16 single-wave form (<= 16 rows)
 //   k_pf_attn_mfma    flash-style causal attention for prompts;  k_pf_attn: scalar form with scores in LDS (decode batches)
@@ -56,100 +55,12 @@ __device__ __forceinline__ f32x16 mfma16(const uint4& a, const uint4& b, f32x16 
   else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
 
-// Workgroup = 4 waves side by side along N; wave tile = (32 MT) rows x (32 NT) columns.  The A tile (32 MT rows x 64 k) is shared by the four
-// waves through LDS (row stride 144 B: 16-byte fragment reads of 32 consecutive rows spread over all banks); B fragments have no reuse across
-// waves and go straight from global memory to registers.  Double buffered: the loads of tile i+1 (A -> registers -> LDS, B -> registers) are
-// in flight under the MFMAs of tile i; one barrier per tile.
-// grid = (ceil(N / (128 NT)), ceil(S / (32 MT)))
-constexpr int A_STRIDE = 144;   // bytes per LDS row: 64 k x 2 B + 16 B pad
-template <int DT, int MT, int NT>
-__global__ __launch_bounds__(256) void k_gemm_nt(const unsigned short* __restrict__ X, const unsigned short* __restrict__ W, const float* __restrict__ bias,
-                                                 int S, int N, int K, int act, float* __restrict__ Y, const int* __restrict__ g_off, const int* __restrict__ g_cnt,
-                                                 long long w_stride) {
-  __shared__ __attribute__((aligned(16))) unsigned char sA[2][32 * MT * A_STRIDE];
-  if (g_cnt) {   // grouped form (MoE experts over gathered token rows): group blockIdx.z owns rows [g_off, g_off + g_cnt) of X / Y and the z-th weight matrix
-    const int z = blockIdx.z, off = g_off[z];
-    S = g_cnt[z];
-    if ((int)blockIdx.y * 32 * MT >= S) return;
-    X += (size_t)off * K; Y += (size_t)off * N; W += (size_t)z * w_stride;
-  }
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-  const int n0 = (blockIdx.x * 4 + wave) * 32 * NT, m0 = blockIdx.y * 32 * MT;
-  // B: lane (r,h) reads 64 contiguous bytes (k = 32 h .. 32 h + 31) of row n per 64-k tile
-  unsigned woff[NT];                      // element offsets (N K < 2^32 for every matrix on this path)
-#pragma unroll
-  for (int j = 0; j < NT; j++) woff[j] = (unsigned)min(n0 + 32 * j + r, N - 1) * (unsigned)K + 32u * h;
-  // A staging: 32 MT rows x 128 B per tile = 8 MT pieces of 16 B per row-pair...: piece p = tid + 256 i covers row p / 8, 16-byte column p % 8
-  constexpr int APT = MT;                 // 32 MT rows x 8 pieces = 256 MT pieces: exactly MT per thread; piece i of thread t: row (t >> 3) + 32 i, column t & 7
-  unsigned xoff[APT];
-#pragma unroll
-  for (int i = 0; i < APT; i++) xoff[i] = (unsigned)min(m0 + (tid >> 3) + 32 * i, S - 1) * (unsigned)K + 8u * (tid & 7);
-  const int adst0 = (tid >> 3) * A_STRIDE + 16 * (tid & 7);
-  f32x16 acc[MT][NT];
-#pragma unroll
-  for (int t = 0; t < MT; t++)
-#pragma unroll
-    for (int j = 0; j < NT; j++)
-#pragma unroll
-      for (int i = 0; i < 16; i++) acc[t][j][i] = 0.f;
-  uint4 bcur[NT][4], bnext[NT][4], areg[APT];
-#define GEMM_GLOAD(K0, B)                                                                                                          \
-  _Pragma("unroll") for (int j = 0; j < NT; j++)                                                                                   \
-    _Pragma("unroll") for (int s = 0; s < 4; s++)                                                                                  \
-      B[j][s] = __builtin_bit_cast(uint4, __builtin_nontemporal_load((const u32x4*)(W + woff[j] + (K0)) + s));                     \
-  _Pragma("unroll") for (int i = 0; i < APT; i++) areg[i] = *(const uint4*)(X + xoff[i] + (K0));
-#define GEMM_ASTORE(BUF) _Pragma("unroll") for (int i = 0; i < APT; i++) *(uint4*)(&sA[BUF][adst0 + 32 * i * A_STRIDE]) = areg[i];
-  GEMM_GLOAD(0, bcur)
-  GEMM_ASTORE(0)
-  __syncthreads();
-  const int nk = K >> 6;
-  for (int kt = 0; kt < nk; kt++) {
-    const int buf = kt & 1;
-    const int kn = min(kt + 1, nk - 1) << 6;             // clamped: one redundant reload at the tail, never a branch around a load
-    GEMM_GLOAD(kn, bnext)
-    const unsigned char* a0 = &sA[buf][r * A_STRIDE + 64 * h];
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-      uint4 af[MT];
-#pragma unroll
-      for (int t = 0; t < MT; t++) af[t] = *(const uint4*)(a0 + 32 * t * A_STRIDE + 16 * s);
-#pragma unroll
-      for (int t = 0; t < MT; t++)
-#pragma unroll
-        for (int j = 0; j < NT; j++) acc[t][j] = mfma16<DT>(af[t], bcur[j][s], acc[t][j]);
-    }
-    GEMM_ASTORE(buf ^ 1)                                  // the other buffer was last read before the previous barrier
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NT; j++)
-#pragma unroll
-      for (int s = 0; s < 4; s++) bcur[j][s] = bnext[j][s];
-  }
-#undef GEMM_GLOAD
-#undef GEMM_ASTORE
-  // C layout: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-  for (int j = 0; j < NT; j++) {
-    const int n = n0 + 32 * j + r;
-    if (n < N) {
-      const float bv = bias ? bias[n] : 0.f;
-#pragma unroll
-      for (int t = 0; t < MT; t++)
-#pragma unroll
-        for (int i = 0; i < 16; i++) {
-          const int m = m0 + 32 * t + (i & 3) + 8 * (i >> 2) + 4 * h;
-          if (m < S) Y[(size_t)m * N + n] = pf_round(acc[t][j][i] + bv, act);
-        }
-    }
-  }
-}
-
 // LDS-DMA form (every plain GEMM of the prefill paths; scripts/gemm_probe.hip holds the same kernel with a reference check and the timings behind
 // these choices).  Workgroup tile 128 x 128 x 64, 2 x 2 waves of 64 x 64 (2 x 2 MFMA 32x32x16 tiles each).  BOTH operands go global -> LDS with
 // global_load_lds_dwordx4 (no staging registers, no ds_write pass): one wave-instruction fills 8 rows x 128 B = 1 KB, lane-linear, so the LDS rows are
 // un-padded and the 16-byte pieces of a row are XOR-swizzled by (row & 7) -- on the SOURCE address and on the fragment read (conflict-free
 // ds_read_b128).  Two 32 KB buffers: tile i+1 is in flight under the MFMAs of tile i; the wait is a counted vmcnt and the barrier a raw s_barrier, so
-// nothing drains early; two workgroups share a CU.  Measured against the register-staged wave-tile kernel above (k_gemm_nt): Mamba2 in_proj at 512 rows
+// nothing drains early; two workgroups share a CU.  Measured against the round-1 register-staged wave-tile kernel (since removed): Mamba2 in_proj at 512 rows
 // (10576 x 2560) 176 -> 48 us (572 TFLOP/s), out_proj 114 -> 35 us; 2048 x 4096 x 4096 845 TFLOP/s.
 // K can be split over KS workgroups (unrounded f32 partials in `part`, summed in a fixed order by k_q4g_mfma_reduce): a few hundred rows give only tens of
 // tiles.  XCD-aware tile order: consecutive workgroups of one XCD (blockIdx.x % 8) walk the row tiles and K splits of ONE column tile, so a weight tile
@@ -964,7 +875,7 @@ __global__ __launch_bounds__(256) void k_pf_quant_i8(const unsigned short* __res
   }
 }
 
-template <int WPB, int DBG = 0, bool SEQ = true>     // DBG (timing experiments, BZ_I8_DBG): 1 = no fold, 2 = no MFMAs, 3 = no LDS fragment reads, 4 = interleaved tiles
+template <int WPB>
 __global__ __launch_bounds__(WPB * 64) void k_gemm_q4g_i8(const uint4* __restrict__ W, const __half* __restrict__ Sc, const unsigned char* __restrict__ Z, const float* __restrict__ bias,
                                                            int N, int K, const signed char* __restrict__ Xq, size_t plane_stride, const RowPar* __restrict__ par, int S, int act,
                                                            float* __restrict__ Y) {
@@ -1040,10 +951,7 @@ __global__ __launch_bounds__(WPB * 64) void k_gemm_q4g_i8(const uint4* __restric
       for (int cc = 0; cc < 4; cc++) {
         i32x4 a[4];
 #pragma unroll
-        for (int p = 0; p < 4; p++) {
-          if (DBG == 3) a[p] = i32x4{(int)w[cc].x, p, cc, lane};
-          else a[p] = an[p];                                                                 // row c, k 32 cc + 16 h .. + 15
-        }
+        for (int p = 0; p < 4; p++) a[p] = an[p];                                          // row c, k 32 cc + 16 h .. + 15
         if (cc < 3) {
 #pragma unroll
           for (int p = 0; p < 4; p++) an[p] = *(const i32x4*)(buf + p * 4096 + aoff + (((2 * (cc + 1) + h) ^ sw) << 4));
@@ -1055,22 +963,18 @@ __global__ __launch_bounds__(WPB * 64) void k_gemm_q4g_i8(const uint4* __restric
         i32x4 b;
         b.x = (int)((n0 << 4) & 0xF0F0F0F0u); b.y = (int)(n0 & 0xF0F0F0F0u); b.z = (int)((n1 << 4) & 0xF0F0F0F0u); b.w = (int)(n1 & 0xF0F0F0F0u);
 #pragma unroll
-        for (int p = 0; p < 4; p++) {
-          if (DBG == 2) acc[p][cc] += a[p].x ^ b.x;
-          else acc[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[p], b, acc[p], 0, 0, 0);
-        }
+        for (int p = 0; p < 4; p++) acc[p] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[p], b, acc[p], 0, 0, 0);
       }
       const double zz = (double)(8 - zT[T]), sd = (double)sT[T];
 #pragma unroll
       for (int i = 0; i < 16; i++) {
-        if (DBG == 1) { tot[T][i] += (double)(acc[0][i] ^ acc[1][i] ^ acc[2][i] ^ acc[3][i]); continue; }
         const RowPar q = rp[(i & 3) + 8 * (i >> 2) + 4 * h];
         const int lo = acc[0][i] + acc[1][i] * 256, hi = acc[2][i] + acc[3][i] * 256;                 // 16 x the digit-weighted sums: < 2^21 + 2^29
         const double in16 = fma((double)hi, 65536.0, (double)lo);                                    // 16 * sum_k (q_k - 8) code_k
         const double in = fma(zz, q.rsum, in16 * 0.0625);                                            // sum_k (q_k - z) code_k, exact
         tot[T][i] = fma(in * (double)q.c, sd, tot[T][i]);                                            // + s c Int (the product is exact in double)
       }
-      if (SEQ) __builtin_amdgcn_sched_barrier(0);     // SEQ: the two tiles one after the other (64 accumulator registers, two waves per SIMD); else the compiler interleaves them (128, one wave per SIMD)
+      __builtin_amdgcn_sched_barrier(0);     // the two tiles one after the other (64 accumulator registers, two waves per SIMD); interleaved by the compiler they take 128, one wave per SIMD
     }
   }
   if (!cols_on) return;
@@ -1305,51 +1209,31 @@ int bzk_gemm_nt(hipStream_t s, int dt, const void* x16, const void* w, const flo
   if (dt != BZ_F16 && dt != BZ_BF16) BZ_FAIL(BZ_E_UNSUPPORTED, "gemm_nt: 16-bit operands only");
   if (K % 64 || K < 64 || S <= 0 || N <= 0) BZ_FAIL(BZ_E_UNSUPPORTED, "gemm_nt: K=%d must be a positive multiple of 64", K);
   if ((unsigned long long)S * K >= (1ull << 32) || (unsigned long long)N * K >= (1ull << 32)) BZ_FAIL(BZ_E_UNSUPPORTED, "gemm_nt: operand of 2^32 elements or more");
-  static const bool old_kernel = getenv("BZ_GEMM_NT_WAVE_TILES") != nullptr;     // the round-1 kernel (weights straight to registers), kept for A/B runs and the grouped form
   const double flops = 2.0 * S * (double)N * K;
-  if (!old_kernel) {
-    // 128 x 128 tiles (64 x 128 for <= 64 rows); K split (a power of two) so that the chip sees about 256-320 workgroups, partials summed in a fixed order
-    const int TM = S <= 64 ? 1 : 2, BM = 64 * TM;
-    const int mtiles = (S + BM - 1) / BM, ntiles = (N + 127) / 128, nk = K / 64;
-    const long long tiles = (long long)mtiles * ntiles;
-    int KS = 1;
-    if (ws) {
-      while (KS * 2 * tiles <= 320 && KS * 2 <= nk / 2 && KS < 16 && (size_t)KS * 2 * S * N * 4 <= ws_bytes) KS *= 2;
-    }
-    float* part = KS > 1 ? ws : nullptr;
-    const unsigned grid = 8u * (unsigned)((ntiles + 7) / 8) * (unsigned)mtiles * (unsigned)KS;
-#define LAUNCH_G2(DT, M) do { \
-      static bool attr_done = false; \
-      if (!attr_done) { BZ_HIP(hipFuncSetAttribute((const void*)k_gemm_nt2<DT, M>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)); attr_done = true; } \
-      BZ_LAUNCH("gemm_nt_mfma", flops, (k_gemm_nt2<DT, M>), dim3(grid), dim3(256), 2 * (64 * M + 128) * 128, s, (const unsigned short*)x16, (const unsigned short*)w, bias, S, N, K, act, y, part, KS, \
-                mtiles, ntiles, (const int*)nullptr, (const int*)nullptr, 0LL, rscale); } while (0)
-    if (dt == BZ_F16) { if (TM == 1) LAUNCH_G2(BZ_F16, 1); else LAUNCH_G2(BZ_F16, 2); }
-    else { if (TM == 1) LAUNCH_G2(BZ_BF16, 1); else LAUNCH_G2(BZ_BF16, 2); }
-#undef LAUNCH_G2
-    BZ_HIP(hipGetLastError());
-    if (KS > 1) {
-      const size_t SN = (size_t)S * N;
-      hipLaunchKernelGGL(k_q4g_mfma_reduce, dim3((unsigned)std::min<size_t>((SN + 255) / 256, 2048)), dim3(256), 0, s, (const float*)ws, KS, SN, N, bias, act, y, rscale);
-      BZ_HIP(hipGetLastError());
-    }
-    return BZ_OK;
+  // 128 x 128 tiles (64 x 128 for <= 64 rows); K split (a power of two) so that the chip sees about 256-320 workgroups, partials summed in a fixed order
+  const int TM = S <= 64 ? 1 : 2, BM = 64 * TM;
+  const int mtiles = (S + BM - 1) / BM, ntiles = (N + 127) / 128, nk = K / 64;
+  const long long tiles = (long long)mtiles * ntiles;
+  int KS = 1;
+  if (ws) {
+    while (KS * 2 * tiles <= 320 && KS * 2 <= nk / 2 && KS < 16 && (size_t)KS * 2 * S * N * 4 <= ws_bytes) KS *= 2;
   }
-  if (rscale) BZ_FAIL(BZ_E_UNSUPPORTED, "gemm_nt: row scales need the LDS-DMA kernel (unset BZ_GEMM_NT_WAVE_TILES)");
-  // wave tile (32 MT) x (32 NT): as large as the problem allows while still giving the chip >= 512 waves
-  int MT = S > 96 ? 4 : (S > 64 ? 3 : (S > 32 ? 2 : 1)), NT = 2;
-  auto waves = [&](int mt, int nt) { return (long long)((S + 32 * mt - 1) / (32 * mt)) * ((N + 32 * nt - 1) / (32 * nt)); };
-  if (waves(MT, NT) < 512) NT = 1;
-  while (MT > 1 && waves(MT, NT) < 512) MT = MT == 3 ? 2 : MT / 2;
-  const dim3 grid((N + 128 * NT - 1) / (128 * NT), (S + 32 * MT - 1) / (32 * MT));
-#define LAUNCH_GEMM(DT, M, NN) BZ_LAUNCH("gemm_nt_mfma", flops, (k_gemm_nt<DT, M, NN>), grid, dim3(256), 0, s, (const unsigned short*)x16, (const unsigned short*)w, bias, S, N, K, act, y, \
-                                         (const int*)nullptr, (const int*)nullptr, 0LL)
-#define LAUNCH_GEMM_N(DT, M) do { if (NT == 2) LAUNCH_GEMM(DT, M, 2); else LAUNCH_GEMM(DT, M, 1); } while (0)
-#define LAUNCH_GEMM_M(DT) do { if (MT == 4) LAUNCH_GEMM_N(DT, 4); else if (MT == 3) LAUNCH_GEMM_N(DT, 3); else if (MT == 2) LAUNCH_GEMM_N(DT, 2); else LAUNCH_GEMM_N(DT, 1); } while (0)
-  if (dt == BZ_F16) LAUNCH_GEMM_M(BZ_F16); else LAUNCH_GEMM_M(BZ_BF16);
-#undef LAUNCH_GEMM_M
-#undef LAUNCH_GEMM_N
-#undef LAUNCH_GEMM
+  float* part = KS > 1 ? ws : nullptr;
+  const unsigned grid = 8u * (unsigned)((ntiles + 7) / 8) * (unsigned)mtiles * (unsigned)KS;
+#define LAUNCH_G2(DT, M) do { \
+    static bool attr_done = false; \
+    if (!attr_done) { BZ_HIP(hipFuncSetAttribute((const void*)k_gemm_nt2<DT, M>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)); attr_done = true; } \
+    BZ_LAUNCH("gemm_nt_mfma", flops, (k_gemm_nt2<DT, M>), dim3(grid), dim3(256), 2 * (64 * M + 128) * 128, s, (const unsigned short*)x16, (const unsigned short*)w, bias, S, N, K, act, y, part, KS, \
+              mtiles, ntiles, (const int*)nullptr, (const int*)nullptr, 0LL, rscale); } while (0)
+  if (dt == BZ_F16) { if (TM == 1) LAUNCH_G2(BZ_F16, 1); else LAUNCH_G2(BZ_F16, 2); }
+  else { if (TM == 1) LAUNCH_G2(BZ_BF16, 1); else LAUNCH_G2(BZ_BF16, 2); }
+#undef LAUNCH_G2
   BZ_HIP(hipGetLastError());
+  if (KS > 1) {
+    const size_t SN = (size_t)S * N;
+    hipLaunchKernelGGL(k_q4g_mfma_reduce, dim3((unsigned)std::min<size_t>((SN + 255) / 256, 2048)), dim3(256), 0, s, (const float*)ws, KS, SN, N, bias, act, y, rscale);
+    BZ_HIP(hipGetLastError());
+  }
   return BZ_OK;
 }
 
@@ -1360,29 +1244,17 @@ int bzk_gemm_nt_grouped(hipStream_t s, int dt, const void* x16, const void* w, l
   if (dt != BZ_F16 && dt != BZ_BF16) BZ_FAIL(BZ_E_UNSUPPORTED, "gemm_nt_grouped: 16-bit operands only");
   if (K % 64 || K < 64 || N <= 0 || G <= 0) BZ_FAIL(BZ_E_UNSUPPORTED, "gemm_nt_grouped: K=%d must be a positive multiple of 64", K);
   if (max_rows <= 0) return BZ_OK;
-  static const bool old_kernel = getenv("BZ_GEMM_NT_WAVE_TILES") != nullptr;
-  if (!old_kernel) {   // LDS-DMA kernel, one grid row per group; experts see tens of rows each, so the launch is bound by the weight stream, not by the padded row tiles
-    const int mtiles = (max_rows + 63) / 64, ntiles = (N + 127) / 128;
-    const dim3 grid2(8u * (unsigned)((ntiles + 7) / 8) * (unsigned)mtiles, G);
-    const double flops2 = 2.0 * (double)total_rows * N * K;
-#define LAUNCH_GG2(DT) do { \
-      static bool attr_done = false; \
-      if (!attr_done) { BZ_HIP(hipFuncSetAttribute((const void*)k_gemm_nt2<DT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)); attr_done = true; } \
-      BZ_LAUNCH("gemm_nt_mfma<grouped>", flops2, (k_gemm_nt2<DT, 1>), grid2, dim3(256), 2 * (64 + 128) * 128, s, (const unsigned short*)x16, (const unsigned short*)w, (const float*)nullptr, 0, N, K, act, y, \
-                (float*)nullptr, 1, mtiles, ntiles, g_off, g_cnt, w_stride, (const float*)nullptr); } while (0)
-    if (dt == BZ_F16) LAUNCH_GG2(BZ_F16); else LAUNCH_GG2(BZ_BF16);
-#undef LAUNCH_GG2
-    BZ_HIP(hipGetLastError());
-    return BZ_OK;
-  }
-  const int MT = max_rows > 32 ? 2 : 1;        // experts see tens of rows each: small row tiles, the grid is filled by the groups
-  const dim3 grid((N + 127) / 128, (max_rows + 32 * MT - 1) / (32 * MT), G);
+  // LDS-DMA kernel, one grid row per group; experts see tens of rows each, so the launch is bound by the weight stream, not by the padded row tiles
+  const int mtiles = (max_rows + 63) / 64, ntiles = (N + 127) / 128;
+  const dim3 grid(8u * (unsigned)((ntiles + 7) / 8) * (unsigned)mtiles, G);
   const double flops = 2.0 * (double)total_rows * N * K;
-#define LAUNCH_GG(DT, M) BZ_LAUNCH("gemm_nt_mfma<grouped>", flops, (k_gemm_nt<DT, M, 1>), grid, dim3(256), 0, s, (const unsigned short*)x16, (const unsigned short*)w, (const float*)nullptr, \
-                                   0, N, K, act, y, g_off, g_cnt, w_stride)
-  if (dt == BZ_F16) { if (MT == 2) LAUNCH_GG(BZ_F16, 2); else LAUNCH_GG(BZ_F16, 1); }
-  else { if (MT == 2) LAUNCH_GG(BZ_BF16, 2); else LAUNCH_GG(BZ_BF16, 1); }
-#undef LAUNCH_GG
+#define LAUNCH_GG2(DT) do { \
+    static bool attr_done = false; \
+    if (!attr_done) { BZ_HIP(hipFuncSetAttribute((const void*)k_gemm_nt2<DT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)); attr_done = true; } \
+    BZ_LAUNCH("gemm_nt_mfma<grouped>", flops, (k_gemm_nt2<DT, 1>), grid, dim3(256), 2 * (64 + 128) * 128, s, (const unsigned short*)x16, (const unsigned short*)w, (const float*)nullptr, 0, N, K, act, y, \
+              (float*)nullptr, 1, mtiles, ntiles, g_off, g_cnt, w_stride, (const float*)nullptr); } while (0)
+  if (dt == BZ_F16) LAUNCH_GG2(BZ_F16); else LAUNCH_GG2(BZ_BF16);
+#undef LAUNCH_GG2
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
@@ -1573,14 +1445,9 @@ int bzk_gemm_q4g_i8(hipStream_t s, const LinearDev& L, const void* xq, int S, in
   if ((long long)((ntile + 7) / 8) * mt >= 512) WPB = 8;          // large problems: 32 x 512 tiles halve the activation re-reads from L2
   if (wpb_env) WPB = wpb_env;
   const double flops = 2.0 * S * (double)L.N * L.K;
-#define LAUNCH_I8X(W_) BZ_LAUNCH("gemm_q4g_i8_mfma", flops, (k_gemm_q4g_i8<W_, 0, false>), dim3(8u * (unsigned)(((ntile + W_ - 1) / W_ + 7) / 8) * (unsigned)mt), dim3(W_ * 64), 0, s, (const uint4*)L.w, (const __half*)L.scales, \
+#define LAUNCH_I8(W_) BZ_LAUNCH("gemm_q4g_i8_mfma", flops, (k_gemm_q4g_i8<W_>), dim3(8u * (unsigned)(((ntile + W_ - 1) / W_ + 7) / 8) * (unsigned)mt), dim3(W_ * 64), 0, s, (const uint4*)L.w, (const __half*)L.scales, \
               (const unsigned char*)L.zeros, L.bias, L.N, L.K, (const signed char*)xq, (size_t)S * L.K, (const RowPar*)((const char*)xq + po), S, act, y)
-#define LAUNCH_I8D(W_, D_) BZ_LAUNCH("gemm_q4g_i8_mfma", flops, (k_gemm_q4g_i8<W_, D_>), dim3(8u * (unsigned)(((ntile + W_ - 1) / W_ + 7) / 8) * (unsigned)mt), dim3(W_ * 64), 0, s, (const uint4*)L.w, (const __half*)L.scales, \
-              (const unsigned char*)L.zeros, L.bias, L.N, L.K, (const signed char*)xq, (size_t)S * L.K, (const RowPar*)((const char*)xq + po), S, act, y)
-#define LAUNCH_I8(W_) do { if (dbg == 1) LAUNCH_I8D(W_, 1); else if (dbg == 2) LAUNCH_I8D(W_, 2); else if (dbg == 3) LAUNCH_I8D(W_, 3); else if (dbg == 4) LAUNCH_I8X(W_); else LAUNCH_I8D(W_, 0); } while (0)
-  static const int dbg = getenv("BZ_I8_DBG") ? atoi(getenv("BZ_I8_DBG")) : 0;     // timing experiments only: the results are wrong
   if (WPB == 8) LAUNCH_I8(8); else if (WPB == 4) LAUNCH_I8(4); else LAUNCH_I8(2);
-#undef LAUNCH_I8D
 #undef LAUNCH_I8
   BZ_HIP(hipGetLastError());
   return BZ_OK;

@@ -306,11 +306,12 @@ int bz_profile_step(bz_model* m, bz_kv* kv, int64_t token, int position, int ite
 int bz_profile_step_ssm(bz_model* m, bz_ssm_state* state, int64_t token, int iters, bz_kernel_time* out, int max_out, int* n_out);
 
 /* Kernel tuning aid: mean dispatch time of the int4 GEMV kernel alone on synthetic [N,K] gs-128 weights rotated over `nbuf`
- * HBM buffers.  mode 0 plain x / 1 fused residual+RMSNorm prologue / 2 SiLU*up prologue; flags are debugging knobs (0). */
+ * HBM buffers.  mode 0 plain x / 1 fused residual+RMSNorm prologue / 2 SiLU*up prologue; flags 0, or 8 = prefetch depth 4 instead of 2
+ * (any other bit: BZ_E_INVALID). */
 int bz_tune_gemv(bz_device* dev, int N, int K, int groups_per_wg, int mode, int nbuf, int iters, int flags, double* avg_us);
 
-/* the same for the fused MLP kernel (norm + gate/up + SiLU*up + down) on synthetic int4 weights; stamps_out (optional, 2 x 16 x 16 values) receives the
- * diagnostic build's per-wave phase stamps in 10 ns units */
+/* the same for the fused MLP kernel (norm + gate/up + SiLU*up + down) on synthetic int4 weights; flags must be 0 and stamps_out NULL
+ * (otherwise BZ_E_INVALID) */
 int bz_tune_mlp(bz_device* dev, int H, int I, int nbuf, int iters, int flags, double* avg_us, long long* stamps_out);
 
 /* the same for the dense row GEMV (16-bit weights [N,K], wdt BZ_F16 / BZ_BF16); mode 0 plain, 1 residual + RMSNorm prologue, 2 SiLU*up prologue;

@@ -32,7 +32,7 @@ for tok, pos in ((17, 0), (4242, 1), (99, 2)):
     print("token %d at position %d" % (tok, pos))
     for l in range(nl):
         # local: GPU layer l on the oracle's inputs (kv_l holds GPU-computed K/V of oracle-fed layers)
-        if os.environ.get("PRE_ADD"):      # the deferred residual added on the host: the layer starts without one (the persistent launch takes such steps)
+        if os.environ.get("PRE_ADD"):      # the deferred residual added on the host: the layer starts without one
             lh = dev.tensor((oh if opm is None else (oh + opm).astype(np.float16)).astype(np.float32))
             lpm = None
         else:

@@ -22,11 +22,11 @@ for name, (N, K, mode) in SHAPES.items():
     for gw in [g for g in (1, 2, 4, 7, 8, 14, 16) if G % g == 0]:
         wgs = ((N + 255) // 256) * (G // gw)
         row = []
-        for flags in (0, 8, 7, 15):
+        for flags in (0, 8):
             us = run(N, K, gw, mode, flags)
             row.append("%6.1f" % us)
         us0 = float(row[0])
-        print("%-7s gw=%2d wgs=%5d  us[npf2, npf4, npf2-bare, npf4-bare]= %s   -> %.0f GB/s" % (name, gw, wgs, " ".join(row), mb / us0 * 1e3), flush=True)
+        print("%-7s gw=%2d wgs=%5d  us[npf2, npf4]= %s   -> %.0f GB/s" % (name, gw, wgs, " ".join(row), mb / us0 * 1e3), flush=True)
     # plain prologue for comparison on the norm/silu shapes
     if mode:
         us = run(N, K, [g for g in (4, 2, 1) if G % g == 0][0], 0)

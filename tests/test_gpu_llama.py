@@ -758,3 +758,23 @@ def test_generate_reports_the_reference_bench_timings(device, mode):
     assert 0.0 < st["itl_p50_ms"] <= st["itl_p99_ms"] <= st["itl_max_ms"]
     assert abs(st["decode_tok_per_s"] - 39 / ((st["total_ms"] - st["ttft_ms"]) / 1e3)) <= 1e-6 * st["decode_tok_per_s"]
     assert st["itl_max_ms"] * 39 >= st["total_ms"] - st["ttft_ms"] - 1e-6
+
+
+def test_decode_step_matches_the_oracle_to_1e_4(device):
+    """the default decode path against the CPU oracle at the real layer widths (3 layers): every sub-op of the int4 path is bit-identical to the oracle's
+    (scripts/parity_depth.py: zero differing elements per layer), what remains is the dense lm_head's f32 summation order: 1e-4, every step"""
+    model = synth.make_llama("llama3-8b-awq-2l", n_layers=3)
+    cfg = model["config"]
+    lm, om = runtime.LoadedModel.from_synth(device, model), orc_py.OrcLlama(model)
+    kv = runtime.LayeredKvCache(device, cfg["n_layers"], 1, cfg["n_kv_heads"], 40, cfg["max_seq_len"], cfg["head_dim"], L.F16)
+    okv = om.new_kv(40)
+    tok, worst = 11, 0.0
+    for i in range(24):
+        lo = np.asarray(om.forward_kv([tok], okv, i)).reshape(-1)
+        lg = lm.forward_with_kv_cache([tok], kv, i).to_numpy().reshape(-1)
+        err = float(np.linalg.norm(lg.astype(np.float64) - lo) / np.linalg.norm(lo))
+        worst = max(worst, err)
+        assert err <= 1e-4, (i, err)
+        tok = int(lo.argmax())
+    print("decode step vs oracle, 3 layers at 8B widths, 24 steps: worst relative L2 %.3e" % worst)
+    orc_py.lib().orc_kv_free(okv)

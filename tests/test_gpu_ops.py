@@ -340,3 +340,6 @@ def test_tuning_entry_points_run_and_reject_bad_arguments(device):
     assert 100.0 < gbs.value < 9000.0
     assert L.lib().bz_tune_rows(device.h, 256, 1001, L.BF16, 1, 0, 2, 2, C.byref(us)) != 0      # K not a multiple of 8
     assert L.lib().bz_tune_mlp(device.h, 1000, 1024, 2, 2, 0, C.byref(us), None) != 0          # hidden size the fused kernel is not built for
+    assert L.lib().bz_tune_gemv(device.h, 512, 1024, 2, 1, 2, 2, 16, C.byref(us)) != 0        # flag bit other than 8 (the prefetch depth)
+    stamps = (C.c_longlong * 512)()
+    assert L.lib().bz_tune_mlp(device.h, 2048, 1024, 2, 2, 0, C.byref(us), stamps) != 0        # stamps_out must be NULL
