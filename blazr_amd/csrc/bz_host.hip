@@ -2,6 +2,7 @@
 // the Llama-family decode step built from the fused kernels, hipGraph capture, and the decode loop.
 // C-ABI entry points are declared in include/blazr_hip.h (each cites the reference interface it replaces).
 #include "bz_internal.h"
+#include "bz_ggml.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -300,6 +301,7 @@ struct bz_model {
   std::unordered_map<std::string, RawTensor> raw;
   std::vector<LayerDev> layers;
   void* embed = nullptr; int embed_dt = BZ_F16;
+  int embed_ggml = 0;          // != 0: `embed` holds the raw ggml rows of this block type (GGUF token_embd as stored in the file)
   float* final_norm = nullptr;
   FusedLinear lm_head;
   std::unordered_map<std::string, LinearDev> named;  // views for the op-level API
@@ -501,9 +503,12 @@ extern "C" int bz_model_add_gguf(bz_model* m, const char* name, int ggml_type, i
   size_t rowb = 0;
   if (ggml_type == BZ_GGML_Q8_0) rowb = (size_t)K / 32 * 34;
   else if (ggml_type == BZ_GGML_Q4_K) rowb = (size_t)K / 256 * 144;
+  else if (ggml_type == BZ_GGML_Q5_K) rowb = (size_t)K / 256 * 176;
   else if (ggml_type == BZ_GGML_Q6_K) rowb = (size_t)K / 256 * 210;
-  else BZ_FAIL(BZ_E_UNSUPPORTED, "add_gguf '%s': ggml type %d is not implemented (F32, F16, BF16, Q8_0, Q4_K, Q6_K are)", name, ggml_type);
-  if (N % 64 || K % 256) BZ_FAIL(BZ_E_UNSUPPORTED, "add_gguf '%s': N=%lld must be a multiple of 64 and K=%lld of 256", name, (long long)N, (long long)K);
+  else BZ_FAIL(BZ_E_UNSUPPORTED, "add_gguf '%s': ggml type %d is not implemented (F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K are)", name, ggml_type);
+  // N % 64: the column tiles of the repacked GEMV layouts.  The token embedding is gathered by row from the raw blocks: any vocabulary size
+  const bool by_row = strcmp(name, "model.embed_tokens.weight") == 0;
+  if ((!by_row && N % 64) || N <= 0 || K % 256) BZ_FAIL(BZ_E_UNSUPPORTED, "add_gguf '%s': N=%lld must be a multiple of 64 and K=%lld of 256", name, (long long)N, (long long)K);
   RawTensor r; r.kind = 3; r.N = N; r.K = K; r.ggml_type = ggml_type; r.bytes = (size_t)N * rowb;
   r.shape = {N, K};
   BZ_TRY(upload(m->dev, &r.d0, blocks, r.bytes));
@@ -637,10 +642,11 @@ static int build_gq(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L
   const int K = (int)rs[0]->K, type = rs[0]->ggml_type;
   int N = 0;
   for (auto* r : rs) N += (int)r->N;
-  const int kind = type == BZ_GGML_Q8_0 ? LK_Q80 : (type == BZ_GGML_Q4_K ? LK_Q4K : LK_Q6K);
+  const int kind = type == BZ_GGML_Q8_0 ? LK_Q80 : type == BZ_GGML_Q4_K ? LK_Q4K : type == BZ_GGML_Q5_K ? LK_Q5K : LK_Q6K;
   size_t wqb, whb = 0, hdb = 0, ddb;
   if (kind == LK_Q80) { wqb = (size_t)N * K; ddb = (size_t)N * (K / 32) * 2; }
   else if (kind == LK_Q4K) { wqb = (size_t)N * K / 2; hdb = (size_t)N * (K / 256) * 16; ddb = 0; }
+  else if (kind == LK_Q5K) { wqb = (size_t)N * K / 2; whb = (size_t)N * K / 8; hdb = (size_t)N * (K / 256) * 16; ddb = 0; }
   else { wqb = (size_t)N * K / 2; whb = (size_t)N * K / 4; hdb = (size_t)N * (K / 256) * 16; ddb = (size_t)N * (K / 256) * 2; }
   void *wq = nullptr, *wh = nullptr, *hd = nullptr, *dd = nullptr;
   BZ_TRY(dev_alloc(m, &wq, wqb));
@@ -662,7 +668,7 @@ static int build_gq(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L
   L->kind = kind; L->N = N; L->K = K; L->gs = kind == LK_Q80 ? 32 : 256; L->w = wq; L->zeros = wh; L->hdr = hd; L->scales = dd;
   L->gw = choose_sbw(N, K, gemv_target_wgs());
   L->bytes = wqb + whb + hdb + ddb;
-  L->algo_bytes = L->bytes;     // the repack keeps the ggml bytes per weight (34/32, 144/256, 210/256)
+  L->algo_bytes = L->bytes;     // the repack keeps the ggml bytes per weight (34/32, 144/256, 176/256, 210/256)
   return BZ_OK;
 }
 
@@ -716,6 +722,7 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
         const size_t t0 = (size_t)sub / 64, K = (size_t)L.K;
         if (L.kind == LK_Q80) { V.w = (char*)L.w + t0 * 64 * K; V.scales = (char*)L.scales + t0 * (K / 32) * 64 * 2; }
         else if (L.kind == LK_Q4K) { V.w = (char*)L.w + t0 * 32 * K; V.hdr = (char*)L.hdr + t0 * (K / 256) * 64 * 16; }
+        else if (L.kind == LK_Q5K) { V.w = (char*)L.w + t0 * 32 * K; V.zeros = (char*)L.zeros + t0 * 8 * K; V.hdr = (char*)L.hdr + t0 * (K / 256) * 64 * 16; }
         else { V.w = (char*)L.w + t0 * 32 * K; V.zeros = (char*)L.zeros + t0 * 16 * K; V.hdr = (char*)L.hdr + t0 * (K / 256) * 64 * 16;
                V.scales = (char*)L.scales + t0 * (K / 256) * 64 * 2; }
         V.gw = choose_sbw(V.N, V.K, gemv_target_wgs());
@@ -848,20 +855,32 @@ extern "C" int bz_model_finalize(bz_model* m) {
   }
   BZ_HIP(hipStreamSynchronize(m->dev->stream));
   BZ_TRY(take_vector_f32(m, "model.norm.weight", H, &m->final_norm));
-  // embeddings stay in their storage dtype (rows are gathered); tied lm_head reads the same buffer
+  // embeddings stay in their storage dtype (rows are gathered); tied lm_head reads the same buffer.  A GGUF block-quantised table (Q8_0 / Q4_K / Q5_K /
+  // Q6_K token_embd) stays as the file's raw rows, decoded per gathered row; its tied lm_head is a repacked copy on the block-quant GEMV path
   {
     auto it = m->raw.find("model.embed_tokens.weight");
     if (it == m->raw.end()) BZ_FAIL(BZ_E_NOTFOUND, "finalize: 'model.embed_tokens.weight' was not added");
     RawTensor& r = it->second;
-    if (r.kind != 0 || r.N != V || r.K != H) BZ_FAIL(BZ_E_INVALID, "finalize: embed_tokens must be dense [vocab, hidden]");
-    m->embed = r.d0; m->embed_dt = r.dtype; r.d0 = nullptr; m->owned.push_back(m->embed); r.consumed = true;
+    const bool qemb = r.kind == 3 && (r.ggml_type == BZ_GGML_Q8_0 || r.ggml_type == BZ_GGML_Q4_K || r.ggml_type == BZ_GGML_Q5_K || r.ggml_type == BZ_GGML_Q6_K);
+    if ((r.kind != 0 && !qemb) || r.N != V || r.K != H) BZ_FAIL(BZ_E_INVALID, "finalize: embed_tokens must be dense or GGUF Q8_0/Q4_K/Q5_K/Q6_K [vocab, hidden]");
+    const bool tied = c.tie_embeddings || !m->raw.count("lm_head.weight");
+    if (qemb && tied) {
+      if (V % 64) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: tied lm_head over a quantised embedding needs a vocabulary that is a multiple of 64 (vocab %d)", V);
+      LinearDev L;
+      BZ_TRY(build_gq(m, {&r}, &L));   // repacked copy of the same raw rows (counted in resident below)
+      m->lm_head.parts.push_back(L); m->lm_head.n_off.push_back(0); m->lm_head.N = V; m->lm_head.K = H; m->lm_head.fix_out = true;
+      LinearDev Vw = L; Vw.owned = false;
+      m->named["lm_head.weight"] = Vw;
+    }
+    m->embed = r.d0; m->embed_dt = qemb ? BZ_U8 : r.dtype; m->embed_ggml = qemb ? r.ggml_type : 0;
+    r.d0 = nullptr; m->owned.push_back(m->embed); r.consumed = true;
     m->resident += r.bytes;
-    if (c.tie_embeddings || !m->raw.count("lm_head.weight")) {
+    if (tied && !qemb) {
       LinearDev L; L.kind = LK_ROWS; L.N = V; L.K = H; L.wdt = m->embed_dt; L.w = m->embed; L.owned = false;
       L.bytes = 0; L.algo_bytes = r.bytes;
       m->lm_head.parts.push_back(L); m->lm_head.n_off.push_back(0); m->lm_head.N = V; m->lm_head.K = H; m->lm_head.fix_out = false;
       m->named["lm_head.weight"] = L;
-    } else {
+    } else if (!tied) {
       BZ_TRY(build_fused(m, {"lm_head"}, &m->lm_head));
       force_direct(&m->lm_head);
       if (m->lm_head.N != V || m->lm_head.K != H) BZ_FAIL(BZ_E_INVALID, "finalize: lm_head shape does not match the config");
@@ -899,7 +918,7 @@ extern "C" int bz_model_finalize(bz_model* m) {
 
   // accounting
   size_t act_b = bz_dtype_size(c.act_dtype);
-  m->per_token = (size_t)(2 * c.n_layers + 1) * H * act_b + (size_t)H * bz_dtype_size(m->embed_dt);
+  m->per_token = (size_t)(2 * c.n_layers + 1) * H * act_b + (m->embed_ggml ? ggml_blk_row_bytes(m->embed_ggml, H) : (size_t)H * bz_dtype_size(m->embed_dt));
   for (auto& Ld : m->layers)
     for (FusedLinear* F : {&Ld.qkv, &Ld.o, &Ld.gateup, &Ld.down})
       for (auto& L : F->parts) { m->resident += L.bytes; m->per_token += L.algo_bytes; }
@@ -1418,7 +1437,7 @@ static int llama_step(bz_model* m, const StepIO& io) {
   RingState rs;
   VSrc prev{nullptr, 0};
   if (io.do_embed) {
-    BZ_TRY(bzk_embed(st, m->embed, m->embed_dt, io.d_tok, H, act, m->hbuf[cur], io.d_pos, m->cos_t, m->sin_t, c.head_dim / 2, m->rope_cur));
+    BZ_TRY(bzk_embed(st, m->embed, m->embed_dt, m->embed_ggml, io.d_tok, H, act, m->hbuf[cur], io.d_pos, m->cos_t, m->sin_t, c.head_dim / 2, m->rope_cur));
   } else {
     if (io.d_pos && lend > io.layer_start) BZ_TRY(bzk_rope_row(st, io.d_pos, m->cos_t, m->sin_t, c.head_dim / 2, m->rope_cur));
     BZ_HIP(hipMemcpyAsync(m->hbuf[cur], io.hidden_in, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
@@ -1554,7 +1573,7 @@ static int mamba_step(bz_model* m, const StepIO& io) {
   int cur = 0;
   RingState rs;
   VSrc prev{nullptr, 0};
-  BZ_TRY(bzk_embed(st, m->embed, m->embed_dt, io.d_tok, D, act, m->hbuf[cur]));
+  BZ_TRY(bzk_embed(st, m->embed, m->embed_dt, m->embed_ggml, io.d_tok, D, act, m->hbuf[cur]));
   for (int l = 0; l < c.n_layers; l++) {
     const MambaLayerDev& L = m->mlayers[l];
     Pro pn{}; pn.mode = PRO_NORM; pn.src = prev; pn.h_in = m->hbuf[cur]; pn.h_out = m->hbuf[cur ^ 1]; pn.norm_w = L.norm; pn.eps = c.rms_eps; pn.H = D; pn.act = act;
@@ -1607,7 +1626,7 @@ static int dsv2_step(bz_model* m, const StepIO& io) {
   int cur = 0;
   RingState rs;
   VSrc prev{nullptr, 0};
-  BZ_TRY(bzk_embed(st, m->embed, m->embed_dt, io.d_tok, H, act, m->hbuf[cur]));
+  BZ_TRY(bzk_embed(st, m->embed, m->embed_dt, m->embed_ggml, io.d_tok, H, act, m->hbuf[cur]));
   for (int l = 0; l < c.n_layers; l++) {
     const DsLayerDev& L = m->dlayers[l];
     Pro pn{}; pn.mode = PRO_NORM; pn.src = prev; pn.h_in = m->hbuf[cur]; pn.h_out = m->hbuf[cur ^ 1]; pn.norm_w = L.attn_norm; pn.eps = c.rms_eps; pn.H = H; pn.act = act; pn.f32_sums = 0;
@@ -1905,7 +1924,7 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
     // starting at sequence s0 gets the table advanced to its first row (sequences >= 512 read another sequence's blocks)
     KvView vw = view;
     if (rc.row_pos && vw.block_table) vw.block_table = view.block_table + (size_t)s0 * rc.table_stride;
-    BZ_TRY(bzk_pf_embed(st, m->embed, m->embed_dt, d_tok + s0, n, H, act, m->pf_h));
+    BZ_TRY(bzk_pf_embed(st, m->embed, m->embed_dt, m->embed_ggml, d_tok + s0, n, H, act, m->pf_h));
     const float* prev = nullptr;
     for (int l = 0; l < c.n_layers; l++) {
       const LayerDev& L = m->layers[l];
@@ -2024,7 +2043,7 @@ static int dsv2_prefill(bz_model* m, const long long* d_tok, int S, const KvView
   std::vector<int> hcnt(std::max(E, 1));
   for (int s0 = 0; s0 < S; s0 += CH) {
     const int n = std::min(CH, S - s0), p0 = pos0 + s0;
-    BZ_TRY(bzk_pf_embed(st, m->embed, m->embed_dt, d_tok + s0, n, H, act, m->pf_h));
+    BZ_TRY(bzk_pf_embed(st, m->embed, m->embed_dt, m->embed_ggml, d_tok + s0, n, H, act, m->pf_h));
     const float* prev = nullptr;
     for (int l = 0; l < c.n_layers; l++) {
       const DsLayerDev& L = m->dlayers[l];
@@ -2307,7 +2326,7 @@ static int mamba_prefill(bz_model* m, const long long* d_tok, int S, bz_ssm_stat
   }
   for (int s0 = 0; s0 < S; s0 += CH) {
     const int n = std::min(CH, S - s0);
-    BZ_TRY(bzk_pf_embed(st, m->embed, m->embed_dt, d_tok + s0, n, D, act, m->mpf_h));
+    BZ_TRY(bzk_pf_embed(st, m->embed, m->embed_dt, m->embed_ggml, d_tok + s0, n, D, act, m->mpf_h));
     const float* prev = nullptr;
     for (int l = 0; l < c.n_layers; l++) {
       const MambaLayerDev& L = m->mlayers[l];
@@ -2367,7 +2386,7 @@ extern "C" int bz_forward_embed(bz_model* m, const bz_tensor* tokens, int S, bz_
   const int H = m->cfg.hidden;
   if (!hidden_out || hidden_out->dtype != BZ_F32 || hidden_out->nbytes < (size_t)S * H * 4) BZ_FAIL(BZ_E_INVALID, "forward_embed: hidden_out must be F32 [S,hidden]");
   for (int s = 0; s < S; s++)
-    BZ_TRY(bzk_embed(m->dev->stream, m->embed, m->embed_dt, (const long long*)tokens->ptr + s, H, m->cfg.act_dtype, (float*)hidden_out->ptr + (size_t)s * H));
+    BZ_TRY(bzk_embed(m->dev->stream, m->embed, m->embed_dt, m->embed_ggml, (const long long*)tokens->ptr + s, H, m->cfg.act_dtype, (float*)hidden_out->ptr + (size_t)s * H));
   return BZ_OK;
   BZ_API_END
 }

@@ -53,7 +53,7 @@ struct Pro {
   int f32_sums;        // dense k_gemv_rows2: f32 FMA chains instead of the exact (double) sums -- the DeepSeek-V2 path sets it (k_gemv_rows2's EX)
 };
 
-enum { LK_NONE = 0, LK_Q4G = 1, LK_ROWS = 2, LK_Q4K = 3, LK_Q6K = 4, LK_Q80 = 5 };
+enum { LK_NONE = 0, LK_Q4G = 1, LK_ROWS = 2, LK_Q4K = 3, LK_Q6K = 4, LK_Q80 = 5, LK_Q5K = 6 };
 
 // Device-resident linear layer in kernel layout.
 struct LinearDev {
@@ -219,7 +219,7 @@ int bzk_pf_quant_i8(hipStream_t s, const void* x16, int S, int K, void* xq);
 int bzk_gemm_q4g_i8(hipStream_t s, const LinearDev& L, const void* xq, int S, int act, float* y);
 int bzk_pf_split3(hipStream_t s, const float* x, int S, int K, void* xs, float* rscale, const float* wscale);
 int bzk_argmax_partials(hipStream_t s, const float* v, long long n, float* pval, int* pidx, int nb);
-int bzk_embed(hipStream_t s, const void* table, int tdt, const long long* tok, int H, int act, float* h_out, const int* pos = nullptr,
+int bzk_embed(hipStream_t s, const void* table, int tdt, int gg, const long long* tok, int H, int act, float* h_out, const int* pos = nullptr,
               const float* cos_t = nullptr, const float* sin_t = nullptr, int half = 0, float* rope_cur = nullptr);   // rope_cur: stage [cos|sin] of *pos
 int bzk_rope_row(hipStream_t s, const int* pos, const float* cos_t, const float* sin_t, int half, float* rope_cur);
 int bzk_fix_to_f32(hipStream_t s, const long long* acc, int n, int act, float* out);
@@ -322,7 +322,7 @@ int bzk_gemm_nt(hipStream_t s, int dt, const void* x16, const void* w, const flo
 int bzk_gemm_nt_grouped(hipStream_t s, int dt, const void* x16, const void* w, long long w_stride, int G, const int* g_off, const int* g_cnt, int max_rows, long long total_rows,
                         int N, int K, int act, float* y);
 int bzk_pf_cvt16(hipStream_t s, int dt, const float* x, size_t n, void* y);
-int bzk_pf_embed(hipStream_t s, const void* table, int tdt, const long long* tok, int S, int H, int act, float* out);
+int bzk_pf_embed(hipStream_t s, const void* table, int tdt, int gg, const long long* tok, int S, int H, int act, float* out);
 int bzk_pf_norm(hipStream_t s, int dt, float* hbuf, const float* prev, const float* w, int S, int H, float eps, int act, void* x16);
 int bzk_pf_rope_kv(hipStream_t s, float* qkv, int S, int nq, int nkv, int hd, const float* cos_t, const float* sin_t, int interleaved, int pos0, int act,
                    const KvView& kv, int layer, const int* slots, const int* row_pos = nullptr);

@@ -19,6 +19,7 @@
 //     stages the group scales/zeros for its tile in LDS.
 #include "bz_internal.h"
 #include "bz_dev.h"
+#include "bz_ggml.h"
 #include <math.h>
 
 #include <hip/hip_ext.h>
@@ -851,12 +852,14 @@ bool bzk_gemv_slim_ok(const LinearDev& L, const Pro& pro) {
 //   Q4_K : q  [N/64][K/32][64][16 B] nibbles (A/B order as Q4G), hdr [N/64][K/256][64][16 B] = {d, dmin, scales[12]} verbatim
 //   Q6_K : ql [N/64][K/32][64][16 B] low nibbles (A/B order),    qh [N/64][K/32][64][8 B] 2-bit highs,
 //          sc [N/64][K/256][64][16 B] int8 x16,                  d  [N/64][K/256][64] f16
+//   Q5_K : q  [N/64][K/32][64][16 B] low nibbles (A/B order),    qh [N/64][K/256][64][8 x 4 B] 5th bits: word c = chunk c, bit 8 b + F = k 4 F + b,
+//          hdr [N/64][K/256][64][16 B] = {d, dmin, scales[12]} verbatim (Q4_K's)      -- 128 + 32 + 16 = ggml's 176 B per 256 weights
 // per-chunk activation parameters in LDS (2 x int4 per chunk):
 //   P0 = { sx (f32 bits), Sa_h, Sa_m, Sa_l }   P1 = { Sb_h, Sb_m, Sb_l, 0 }
-//   Q4_K: Sa = sum over the chunk, Sb = sum over k%8 >= 4 (for the signed high-nibble trick);  Q6_K: Sa / Sb = sums over the
+//   Q4_K: Sa = sum over the chunk, Sb = sum over k%8 >= 4 (for the signed high-nibble trick);  Q5_K: Sa only;  Q6_K: Sa / Sb = sums over the
 //   first / second 16;  Q8_0: unused.
 // =========================================================================================================
-enum { GQ_Q80 = 0, GQ_Q4K = 1, GQ_Q6K = 2, GQ_MIX = 3 };   // MIX: Q4_K tiles followed by Q6_K tiles in one launch (the Q4_K_M q/k + v split)
+enum { GQ_Q80 = 0, GQ_Q4K = 1, GQ_Q6K = 2, GQ_MIX = 3, GQ_Q5K = 4 };   // MIX: Q4_K tiles followed by Q6_K tiles in one launch (the Q4_K_M q/k + v split)
 #define XQ_MAX 8355000.0f  // < 127*65536 + 127*256 + 127: the largest magnitude of three balanced int8 planes
 
 // one thread's octet (8 consecutive k of a 32-k chunk; the chunk's four octets sit in four consecutive lanes, quad-aligned) -> three int8 planes
@@ -882,7 +885,7 @@ __device__ __forceinline__ void quant8_x32(const float (&v)[8], int e0, bool on,
     wm[i >> 2] |= ((unsigned)mid & 255u) << (8 * (i & 3));
     wl[i >> 2] |= ((unsigned)lo & 255u) << (8 * (i & 3));
     if (FMT == GQ_Q4K || FMT == GQ_MIX) { sa[0] += hi; sa[1] += mid; sa[2] += lo; if (i >= 4) { sb[0] += hi; sb[1] += mid; sb[2] += lo; } }
-    if (FMT == GQ_Q6K) { sa[0] += hi; sa[1] += mid; sa[2] += lo; }   // per-thread sum; halves are separated below
+    if (FMT == GQ_Q6K || FMT == GQ_Q5K) { sa[0] += hi; sa[1] += mid; sa[2] += lo; }   // per-thread sum; halves are separated below
   }
   if (FMT == GQ_Q6K || FMT == GQ_MIX) {
     // lanes 0,1 of the 4-lane group hold k 0..15 (first half), lanes 2,3 hold k 16..31
@@ -905,6 +908,10 @@ __device__ __forceinline__ void quant8_x32(const float (&v)[8], int e0, bool on,
       sa[q] = grp_reduce<4, OpAdd>(sa[q]);
       sb[q] = grp_reduce<4, OpAdd>(sb[q]);
     }
+  }
+  if (FMT == GQ_Q5K) {
+#pragma unroll
+    for (int q = 0; q < 3; q++) sa[q] = grp_reduce<4, OpAdd>(sa[q]);
   }
   if (on) {
     *(uint2*)(xh + e0 / 4) = make_uint2(wh[0], wh[1]);
@@ -961,6 +968,27 @@ __device__ __forceinline__ void q4k_scale_min(const unsigned (&hw)[4], int j, in
   else { sc = (int)((sbyte(j + 4) & 15u) | ((sbyte(j - 4) >> 6) << 4)); mn = (int)((sbyte(j + 4) >> 4) | ((sbyte(j) >> 6) << 4)); }
 }
 
+// Q5_K: one 32-k chunk as 8 words of q in 0..31 (positive int8, k order A0,B0,A1,B1,...): the low nibbles of the Q4_K-style word pair plus the
+// 5th bits, bit 8 b + F of the chunk's bit word being byte b of k-order word F
+__device__ __forceinline__ void q5k_words(const uint4& nib, unsigned hb, unsigned (&w)[8]) {
+  const unsigned ww[4] = {nib.x, nib.y, nib.z, nib.w};
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    w[2 * j] = (ww[j] & 0x0F0F0F0Fu) | (((hb >> (2 * j)) & 0x01010101u) << 4);
+    w[2 * j + 1] = ((ww[j] >> 4) & 0x0F0F0F0Fu) | (((hb >> (2 * j + 1)) & 0x01010101u) << 4);
+  }
+}
+// y term of one Q5_K chunk: chunk scale x ((d sc) sum q x - (dmin m) sum x), the sums on the three planes
+__device__ __forceinline__ float q5k_chunk(const unsigned (&w)[8], const uint4* xh4, const uint4* xm4, const uint4* xl4, int cc, const int4* cpar,
+                                           const unsigned (&hw)[4], int c, float d, float dmin) {
+  int u[3] = {0, 0, 0};
+  dot_chunk8(w, xh4, xm4, xl4, cc, u);
+  const int4 p0 = cpar[2 * cc];
+  int sc, mn;
+  q4k_scale_min(hw, c, sc, mn);
+  return __int_as_float(p0.x) * ((d * (float)sc) * planes_f(u[0], u[1], u[2]) - (dmin * (float)mn) * planes_f(p0.y, p0.z, p0.w));
+}
+
 #define GQ_E 8   // slice elements per thread (KR <= 2048)
 
 template <int FMT, int MODE, int FIX, int MAXJ>
@@ -992,6 +1020,7 @@ __global__ __launch_bounds__(256) void k_gemv_gq(const uint4* __restrict__ Wq, c
   const int sb0 = ks * SBW;
   uint4 q[16];          // Q8_0: 16 x 16 B (256 int8) ; Q4_K / Q6_K: 8 x 16 B nibbles
   uint2 qh[8];          // Q6_K highs
+  uint4 q5h[2];         // Q5_K 5th bits (8 chunk words)
   uint4 hd = make_uint4(0, 0, 0, 0);
   __half dv[8];         // Q8_0: the 8 block scales of the superblock ; Q6_K: dv[0] = d
   auto load_sb = [&](int sb) {
@@ -1011,6 +1040,10 @@ __global__ __launch_bounds__(256) void k_gemv_gq(const uint4* __restrict__ Wq, c
 #pragma unroll
         for (int i = 0; i < 8; i++) qh[i] = ph[i * 64];
         dv[0] = Dd[((size_t)ntc * SB + sb) * 64 + lane];
+      }
+      if (FMT == GQ_Q5K) {
+        const uint4* ph = (const uint4*)Wh + ((size_t)ntc * SB + sb) * 128 + lane * 2;
+        q5h[0] = ldnt(ph); q5h[1] = ldnt(ph + 1);
       }
     }
   };
@@ -1070,6 +1103,17 @@ __global__ __launch_bounds__(256) void k_gemv_gq(const uint4* __restrict__ Wq, c
         int sc, mn;
         q4k_scale_min(hw, c, sc, mn);
         y += __int_as_float(p0.x) * ((d * (float)sc) * qx - (dmin * (float)mn) * sx_);
+      }
+    } else if (FMT == GQ_Q5K) {
+      const unsigned hw[4] = {hd.x, hd.y, hd.z, hd.w};
+      const unsigned hb[8] = {q5h[0].x, q5h[0].y, q5h[0].z, q5h[0].w, q5h[1].x, q5h[1].y, q5h[1].z, q5h[1].w};
+      const float d = __half2float(__ushort_as_half((unsigned short)(hw[0] & 0xffffu)));
+      const float dmin = __half2float(__ushort_as_half((unsigned short)(hw[0] >> 16)));
+#pragma unroll
+      for (int c = 0; c < 8; c++) {     // chunk = one sub-block
+        unsigned w[8];
+        q5k_words(q[c], hb[c], w);
+        y += q5k_chunk(w, xh4, xm4, xl4, s * 8 + c, cpar, hw, c, d, dmin);
       }
     } else {  // Q6_K
       const unsigned sw[4] = {hd.x, hd.y, hd.z, hd.w};   // 16 int8 scales
@@ -1179,7 +1223,7 @@ __global__ __launch_bounds__(512) void k_gemv_gq_slim(const uint4* __restrict__ 
   }
   __builtin_amdgcn_sched_barrier(0);
   // (2) this wave's superblock: 8 x 16 B of nibbles (+ Q6_K: 8 x 8 B of high bits), header, all in flight now
-  uint4 q[8]; uint2 qh[8]; uint4 hd; __half dsb = __float2half(0.f);
+  uint4 q[8]; uint2 qh[8]; uint4 q5h[2]; uint4 hd; __half dsb = __float2half(0.f);
   {
     const uint4* p = Wq_ + ((size_t)tqc * C32 + (size_t)ksl * 8) * 64 + lane;
 #pragma unroll
@@ -1191,6 +1235,10 @@ __global__ __launch_bounds__(512) void k_gemv_gq_slim(const uint4* __restrict__ 
 #pragma unroll
       for (int i = 0; i < 8; i++) qh[i] = ph[i * 64];
       dsb = Dd_[((size_t)t6 * SB + ksl) * 64 + lane];
+    }
+    if (FMT == GQ_Q5K) {
+      const uint4* ph = (const uint4*)Wh_ + ((size_t)tqc * SB + ksl) * 128 + lane * 2;
+      q5h[0] = ldnt(ph); q5h[1] = ldnt(ph + 1);
     }
   }
   // (3) the activation slice
@@ -1229,7 +1277,18 @@ __global__ __launch_bounds__(512) void k_gemv_gq_slim(const uint4* __restrict__ 
   const uint4* xm4 = (const uint4*)xm;
   const uint4* xl4 = (const uint4*)xl;
   float y = 0.f;
-  if (!is6) {
+  if (FMT == GQ_Q5K) {
+    const unsigned hw[4] = {hd.x, hd.y, hd.z, hd.w};
+    const unsigned hb[8] = {q5h[0].x, q5h[0].y, q5h[0].z, q5h[0].w, q5h[1].x, q5h[1].y, q5h[1].z, q5h[1].w};
+    const float d = __half2float(__ushort_as_half((unsigned short)(hw[0] & 0xffffu)));
+    const float dmin = __half2float(__ushort_as_half((unsigned short)(hw[0] >> 16)));
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      unsigned w[8];
+      q5k_words(q[c], hb[c], w);
+      y += q5k_chunk(w, xh4, xm4, xl4, c, cpar, hw, c, d, dmin);
+    }
+  } else if (!is6) {
     const unsigned hw[4] = {hd.x, hd.y, hd.z, hd.w};
     const float d = __half2float(__ushort_as_half((unsigned short)(hw[0] & 0xffffu)));
     const float dmin = __half2float(__ushort_as_half((unsigned short)(hw[0] >> 16)));
@@ -1541,7 +1600,7 @@ int bzk_mlp_gq(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, i
 
 bool bzk_gq_slim_ok(const LinearDev& L, const Pro& pro) {
   static const bool off = getenv("BZ_NO_GQ_SLIM") != nullptr;
-  if (off || (L.kind != LK_Q4K && L.kind != LK_Q6K) || pro.perm != nullptr || L.N % 64 || L.K % 256) return false;
+  if (off || (L.kind != LK_Q4K && L.kind != LK_Q5K && L.kind != LK_Q6K) || pro.perm != nullptr || L.N % 64 || L.K % 256) return false;
   if (pro.mode == PRO_NORM) return L.K == pro.H && (L.K == 2048 || L.K == 4096 || L.K == 8192);
   if (pro.mode == PRO_SILU) return L.K == pro.H;
   return false;
@@ -2308,19 +2367,7 @@ static bool bzk_rows2_ok(const LinearDev& L, const Pro& pro, const GemvOut& out)
 }
 int bzk_gemv_rows_blocks(const LinearDev& L) { int r = rows_per_wg_for(L.N); return (L.N + r - 1) / r; }
 
-// ---- GGUF: load-time repack from raw row-major ggml blocks ([N][K/blk] blocks of 34 / 144 / 210 bytes) -----------
-__device__ __forceinline__ unsigned q4k_raw_nib(const unsigned char* blk, int k) {   // weight k (0..255) of a raw block_q4_K
-  const int j64 = k >> 6, l = k & 63;
-  const unsigned char b = blk[16 + j64 * 32 + (l & 31)];
-  return l < 32 ? (b & 15u) : (unsigned)(b >> 4);
-}
-__device__ __forceinline__ unsigned q6k_raw(const unsigned char* blk, int k) {       // 6-bit value (0..63) of weight k of a raw block_q6_K
-  const int n128 = k >> 7, l = k & 127, quad = l >> 5, pos = l & 31;
-  const unsigned char qlb = blk[n128 * 64 + (quad & 1) * 32 + pos];
-  const unsigned lo = quad < 2 ? (qlb & 15u) : (unsigned)(qlb >> 4);
-  const unsigned hi = (blk[128 + n128 * 32 + pos] >> (2 * quad)) & 3u;
-  return lo | (hi << 4);
-}
+// ---- GGUF: load-time repack from raw row-major ggml blocks ([N][K/blk] blocks of 34 / 144 / 176 / 210 bytes; raw decoders in bz_ggml.h) -----------
 
 __global__ void k_repack_gq(int fmt, const unsigned char* raw, int N, int K, uint32_t* wq, uint32_t* wh, uint32_t* hd, __half* dd) {
   const size_t gsz = (size_t)gridDim.x * blockDim.x, gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2345,7 +2392,7 @@ __global__ void k_repack_gq(int fmt, const unsigned char* raw, int N, int K, uin
     }
     return;
   }
-  const size_t bsz = fmt == GQ_Q4K ? 144 : 210;
+  const size_t bsz = fmt == GQ_Q4K ? 144 : (fmt == GQ_Q5K ? 176 : 210);
   const size_t rb = (size_t)(K / 256) * bsz;
   const size_t total = (size_t)N * (K >> 3);                   // nibble words (8 weights each)
   for (size_t idx = gid; idx < total; idx += gsz) {
@@ -2361,6 +2408,9 @@ __global__ void k_repack_gq(int fmt, const unsigned char* raw, int N, int K, uin
       if (fmt == GQ_Q4K) {
         const unsigned q1 = q4k_raw_nib(blk, kb + bb), q2 = q4k_raw_nib(blk, kb + 4 + bb);
         word |= (q1 | ((q2 ^ 8u) << 4)) << (8 * bb);
+      } else if (fmt == GQ_Q5K) {
+        const unsigned q1 = q5k_raw(blk, kb + bb) & 15u, q2 = q5k_raw(blk, kb + 4 + bb) & 15u;
+        word |= (q1 | (q2 << 4)) << (8 * bb);
       } else {
         const unsigned q1 = q6k_raw(blk, kb + bb) & 15u, q2 = q6k_raw(blk, kb + 4 + bb) & 15u;
         word |= (q1 | (q2 << 4)) << (8 * bb);
@@ -2386,19 +2436,32 @@ __global__ void k_repack_gq(int fmt, const unsigned char* raw, int N, int K, uin
       wh[idx] = word;
     }
   }
+  if (fmt == GQ_Q5K) {
+    const size_t th = (size_t)N * (K >> 5);                    // one 5th-bit word per (chunk, lane), the superblock's 8 words contiguous per lane
+    for (size_t idx = gid; idx < th; idx += gsz) {
+      const int c = idx & 7, lane = (idx >> 3) & 63;
+      const size_t t = idx >> 9;
+      const int sb = (int)(t % (size_t)(K >> 8)), nt = (int)(t / (size_t)(K >> 8));
+      const unsigned char* blk = raw + (size_t)(nt * 64 + lane) * rb + (size_t)sb * bsz;
+      unsigned word = 0;
+      for (int r = 0; r < 32; r++) word |= (q5k_raw(blk, c * 32 + r) >> 4) << (8 * (r & 3) + (r >> 2));
+      wh[idx] = word;
+    }
+  }
   const size_t nsb = (size_t)N * (K >> 8);
   for (size_t idx = gid; idx < nsb * 4; idx += gsz) {          // 16-byte header per (superblock, lane)
     const int wi = idx & 3, lane = (idx >> 2) & 63;
     const size_t t = idx >> 8;
     const int sb = (int)(t % (size_t)(K >> 8)), nt = (int)(t / (size_t)(K >> 8));
     const unsigned char* blk = raw + (size_t)(nt * 64 + lane) * rb + (size_t)sb * bsz;
-    const unsigned char* src = fmt == GQ_Q4K ? blk + wi * 4 : blk + 192 + wi * 4;   // Q4_K: d,dmin,scales[12] ; Q6_K: scales[16]
+    const unsigned char* src = fmt != GQ_Q6K ? blk + wi * 4 : blk + 192 + wi * 4;   // Q4_K / Q5_K: d,dmin,scales[12] ; Q6_K: scales[16]
     hd[idx] = (unsigned)src[0] | ((unsigned)src[1] << 8) | ((unsigned)src[2] << 16) | ((unsigned)src[3] << 24);
     if (fmt == GQ_Q6K && wi == 0) dd[((size_t)nt * (K >> 8) + sb) * 64 + lane] = __ushort_as_half((unsigned short)(blk[208] | (blk[209] << 8)));
   }
 }
+static int gq_fmt_of(int kind) { return kind == LK_Q80 ? GQ_Q80 : kind == LK_Q4K ? GQ_Q4K : kind == LK_Q5K ? GQ_Q5K : GQ_Q6K; }
 int bzk_repack_gq(hipStream_t s, int kind, const void* raw, int N, int K, void* wq, void* wh, void* hd, void* dd) {
-  const int fmt = kind == LK_Q80 ? GQ_Q80 : (kind == LK_Q4K ? GQ_Q4K : GQ_Q6K);
+  const int fmt = gq_fmt_of(kind);
   hipLaunchKernelGGL(k_repack_gq, dim3(2048), dim3(256), 0, s, fmt, (const unsigned char*)raw, N, K, (uint32_t*)wq, (uint32_t*)wh, (uint32_t*)hd, (__half*)dd);
   BZ_HIP(hipGetLastError());
   return BZ_OK;
@@ -2425,6 +2488,13 @@ __device__ __forceinline__ float gq_elem(int fmt, const uint32_t* wq, const uint
     return (d * (float)sc) * q - (dmin * (float)mn);
   }
   const unsigned lo = rr < 4 ? (byte & 15u) : (byte >> 4);
+  if (fmt == GQ_Q5K) {   // ggml's order, uncontracted: (d sc) q - dmin m
+    const unsigned hb = (wh[(((size_t)nt * (K >> 8) + (k >> 8)) * 64 + lane) * 8 + (kc & 7)] >> (8 * (r & 3) + (r >> 2))) & 1u;
+    const float d = __half2float(__ushort_as_half((unsigned short)(hw[0] & 0xffffu))), dmin = __half2float(__ushort_as_half((unsigned short)(hw[0] >> 16)));
+    int sc, mn;
+    q4k_scale_min(hw, (k & 255) >> 5, sc, mn);
+    return __fsub_rn(__fmul_rn(__fmul_rn(d, (float)sc), (float)(lo | (hb << 4))), __fmul_rn(dmin, (float)mn));
+  }
   const int F = r >> 2;   // k-order word
   const unsigned hword = wh[(((size_t)nt * (K >> 5) + kc) * 64 + lane) * 2 + (F >> 2)];
   const unsigned hi2 = (hword >> (8 * (r & 3) + 2 * (F & 3))) & 3u;
@@ -2439,7 +2509,7 @@ __global__ void k_dequant_gq(int fmt, const uint32_t* wq, const uint32_t* wh, co
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x)
     out[idx] = gq_elem(fmt, wq, wh, hd, dd, K, (int)(idx / (size_t)K), (int)(idx % (size_t)K));
 }
-static int gq_fmt(const LinearDev& L) { return L.kind == LK_Q80 ? GQ_Q80 : (L.kind == LK_Q4K ? GQ_Q4K : GQ_Q6K); }
+static int gq_fmt(const LinearDev& L) { return gq_fmt_of(L.kind); }
 int bzk_dequant_gq(hipStream_t s, const LinearDev& L, float* out) {
   hipLaunchKernelGGL(k_dequant_gq, dim3(2048), dim3(256), 0, s, gq_fmt(L), (const uint32_t*)L.w, (const uint32_t*)L.zeros, (const uint32_t*)L.hdr,
                      (const __half*)L.scales, L.N, L.K, out);
@@ -2483,7 +2553,7 @@ __global__ __launch_bounds__(256) void k_gq_split3(int fmt, const uint32_t* wq, 
     *(uint4*)(o + 2 * K) = make_uint4(c[0] | ((unsigned)c[1] << 16), c[2] | ((unsigned)c[3] << 16), c[4] | ((unsigned)c[5] << 16), c[6] | ((unsigned)c[7] << 16));
   }
 }
-bool bzk_gq_split_ok(const LinearDev& L) { return (L.kind == LK_Q80 || L.kind == LK_Q4K || L.kind == LK_Q6K) && L.K % 64 == 0 && L.N % 64 == 0; }
+bool bzk_gq_split_ok(const LinearDev& L) { return (L.kind == LK_Q80 || L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K) && L.K % 64 == 0 && L.N % 64 == 0; }
 // amax: device word holding the running maximum of the fused linear's parts (zeroed by the caller before the first part)
 int bzk_gq_absmax(hipStream_t s, const LinearDev& L, unsigned* amax) {
   hipLaunchKernelGGL(k_gq_absmax, dim3(2048), dim3(256), 0, s, gq_fmt(L), (const uint32_t*)L.w, (const uint32_t*)L.zeros, (const uint32_t*)L.hdr, (const __half*)L.scales, L.N, L.K, amax);
@@ -2585,23 +2655,23 @@ int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& o
     BZ_HIP(hipGetLastError());
     return BZ_OK;
   }
-  if ((L.kind == LK_Q4K || L.kind == LK_Q6K) && bzk_gq_slim_ok(L, pro)) {
+  if ((L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K) && bzk_gq_slim_ok(L, pro)) {
     if (!out.acc) BZ_FAIL(BZ_E_INVALID, "block-quant gemv needs a fixed-point accumulator");
     const int nsb = L.K / 256, ntg = (L.N / 64 + 7) / 8;
-    const char* label = L.kind == LK_Q4K ? "gemv_q4_K<slim>" : "gemv_q6_K<slim>";
+    const char* label = L.kind == LK_Q4K ? "gemv_q4_K<slim>" : (L.kind == LK_Q5K ? "gemv_q5_K<slim>" : "gemv_q6_K<slim>");
 #define LAUNCH_GQS(FMT, MODE, FIX, NJ) BZ_LAUNCH(label, L.algo_bytes, (k_gemv_gq_slim<FMT, MODE, FIX, NJ>), dim3(nsb * ntg), dim3(512), 0, s, (const uint4*)L.w, \
     (const uint2*)L.zeros, (const uint4*)L.hdr, (const __half*)L.scales, L.bias, L.N, L.K, pro, out.acc, out.zero_buf, out.zero_n, GqMix{})
 #define LAUNCH_GQS_NJ(FMT, FIX) do { if (pro.mode == PRO_SILU) LAUNCH_GQS(FMT, PRO_SILU, FIX, 1); else if (L.K == 2048) LAUNCH_GQS(FMT, PRO_NORM, FIX, 1); \
     else if (L.K == 4096) LAUNCH_GQS(FMT, PRO_NORM, FIX, 2); else LAUNCH_GQS(FMT, PRO_NORM, FIX, 4); } while (0)
 #define LAUNCH_GQS_F(FMT) do { if (pro.src.fix) LAUNCH_GQS_NJ(FMT, 1); else LAUNCH_GQS_NJ(FMT, 0); } while (0)
-    if (L.kind == LK_Q4K) LAUNCH_GQS_F(GQ_Q4K); else LAUNCH_GQS_F(GQ_Q6K);
+    if (L.kind == LK_Q4K) LAUNCH_GQS_F(GQ_Q4K); else if (L.kind == LK_Q5K) LAUNCH_GQS_F(GQ_Q5K); else LAUNCH_GQS_F(GQ_Q6K);
 #undef LAUNCH_GQS_F
 #undef LAUNCH_GQS_NJ
 #undef LAUNCH_GQS
     BZ_HIP(hipGetLastError());
     return BZ_OK;
   }
-  if (L.kind == LK_Q80 || L.kind == LK_Q4K || L.kind == LK_Q6K) {
+  if (L.kind == LK_Q80 || L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K) {
     if (!out.acc) BZ_FAIL(BZ_E_INVALID, "block-quant gemv needs a fixed-point accumulator");
     const int SB = L.K / 256, SBW = L.gw;
     if (SBW <= 0 || SB % SBW || SBW > 8) BZ_FAIL(BZ_E_INVALID, "block-quant gemv: bad k-slice %d of %d superblocks", SBW, SB);
@@ -2609,14 +2679,15 @@ int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& o
     const int grid = nst * (SB / SBW);
     const size_t smem = gq_smem(SBW);
     const int maxj = pro.mode == PRO_NORM ? (pro.H + 1023) / 1024 : 1;
-    const char* label = L.kind == LK_Q80 ? "gemv_q8_0" : (L.kind == LK_Q4K ? "gemv_q4_K" : "gemv_q6_K");
+    const char* label = L.kind == LK_Q80 ? "gemv_q8_0" : L.kind == LK_Q4K ? "gemv_q4_K" : L.kind == LK_Q5K ? "gemv_q5_K" : "gemv_q6_K";
 #define LAUNCH_GQ(FMT, MODE, FIX, MJ) BZ_LAUNCH(label, L.algo_bytes, (k_gemv_gq<FMT, MODE, FIX, MJ>), dim3(grid), dim3(256), smem, s, (const uint4*)L.w, \
     (const uint2*)L.zeros, (const uint4*)L.hdr, (const __half*)L.scales, L.bias, L.N, L.K, SBW, nst, pro, out.acc, out.zero_buf, out.zero_n)
 #define LAUNCH_GQ_F(FMT, MODE, MJ) do { if (pro.src.fix) LAUNCH_GQ(FMT, MODE, 1, MJ); else LAUNCH_GQ(FMT, MODE, 0, MJ); } while (0)
 #define LAUNCH_GQ_M(FMT) do { if (pro.mode == PRO_PLAIN) LAUNCH_GQ_F(FMT, PRO_PLAIN, 1); else if (pro.mode == PRO_SILU) LAUNCH_GQ_F(FMT, PRO_SILU, 1); \
     else if (maxj <= 1) LAUNCH_GQ_F(FMT, PRO_NORM, 1); else if (maxj <= 2) LAUNCH_GQ_F(FMT, PRO_NORM, 2); else if (maxj <= 4) LAUNCH_GQ_F(FMT, PRO_NORM, 4); \
     else if (maxj <= 8) LAUNCH_GQ_F(FMT, PRO_NORM, 8); else BZ_FAIL(BZ_E_UNSUPPORTED, "hidden size %d too large for the fused norm prologue", pro.H); } while (0)
-    if (L.kind == LK_Q80) LAUNCH_GQ_M(GQ_Q80); else if (L.kind == LK_Q4K) LAUNCH_GQ_M(GQ_Q4K); else LAUNCH_GQ_M(GQ_Q6K);
+    if (L.kind == LK_Q80) LAUNCH_GQ_M(GQ_Q80); else if (L.kind == LK_Q4K) LAUNCH_GQ_M(GQ_Q4K); else if (L.kind == LK_Q5K) LAUNCH_GQ_M(GQ_Q5K);
+    else LAUNCH_GQ_M(GQ_Q6K);
 #undef LAUNCH_GQ_M
 #undef LAUNCH_GQ_F
 #undef LAUNCH_GQ
@@ -2758,7 +2829,8 @@ int bzk_dequant_rows(hipStream_t s, const LinearDev& L, float* out) {
 // ---------------------------------------------------------------------------------------------------------
 // embedding row of the new token; block 0 also stages the RoPE row of the new position at a FIXED address ([cos half | sin half]), so that the
 // attention kernels' cos/sin loads do not depend on the position word (one memory latency off every layer's critical path)
-__global__ void k_embed(const void* table, int tdt, const long long* tok, int H, int act, float* h, const int* pos, const float* cos_t,
+// gg != 0: the table is raw ggml rows of that block type (a GGUF token_embd kept as the file's bytes), decoded by ggml's formula
+__global__ void k_embed(const void* table, int tdt, int gg, const long long* tok, int H, int act, float* h, const int* pos, const float* cos_t,
                         const float* sin_t, int half, float* rope_cur) {
   if (rope_cur != nullptr && blockIdx.x == 0 && threadIdx.x < 2 * half) {
     const int p = pos[0], i = threadIdx.x % half;
@@ -2766,6 +2838,11 @@ __global__ void k_embed(const void* table, int tdt, const long long* tok, int H,
   }
   if (table == nullptr) return;
   const long long t = tok[0];
+  if (gg != 0) {
+    const unsigned char* row = (const unsigned char*)table + (size_t)t * ggml_blk_row_bytes(gg, H);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < H; i += gridDim.x * blockDim.x) h[i] = round_act(ggml_row_elem(gg, row, i), act);
+    return;
+  }
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < H; i += gridDim.x * blockDim.x) {
     const size_t idx = (size_t)t * H + i;
     float v;
@@ -2775,17 +2852,19 @@ __global__ void k_embed(const void* table, int tdt, const long long* tok, int H,
     h[i] = round_act(v, act);
   }
 }
-int bzk_embed(hipStream_t s, const void* table, int tdt, const long long* tok, int H, int act, float* h, const int* pos, const float* cos_t,
+int bzk_embed(hipStream_t s, const void* table, int tdt, int gg, const long long* tok, int H, int act, float* h, const int* pos, const float* cos_t,
               const float* sin_t, int half, float* rope_cur) {
   if (rope_cur != nullptr && (2 * half > 256 || !pos || !cos_t || !sin_t)) BZ_FAIL(BZ_E_INVALID, "embed: bad RoPE staging arguments");
-  BZ_LAUNCH("embed", (double)H * (tdt == BZ_F32 ? 4 : 2), k_embed, dim3((H + 255) / 256), dim3(256), 0, s, table, tdt, tok, H, act, h, pos, cos_t, sin_t,
+  if (gg != 0 && (ggml_blk_row_bytes(gg, H) == 0 || H % (gg == BZ_GGML_Q8_0 ? 32 : 256))) BZ_FAIL(BZ_E_INVALID, "embed: ggml type %d rows of %d", gg, H);
+  const double bytes = gg != 0 ? (double)ggml_blk_row_bytes(gg, H) : (double)H * (tdt == BZ_F32 ? 4 : 2);
+  BZ_LAUNCH("embed", bytes, k_embed, dim3((H + 255) / 256), dim3(256), 0, s, table, tdt, gg, tok, H, act, h, pos, cos_t, sin_t,
             half, rope_cur);
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
 int bzk_rope_row(hipStream_t s, const int* pos, const float* cos_t, const float* sin_t, int half, float* rope_cur) {
   if (2 * half > 256 || !pos || !cos_t || !sin_t || !rope_cur) BZ_FAIL(BZ_E_INVALID, "rope_row: bad arguments");
-  hipLaunchKernelGGL(k_embed, dim3(1), dim3(256), 0, s, (const void*)nullptr, 0, (const long long*)nullptr, 0, 0, (float*)nullptr, pos, cos_t, sin_t, half, rope_cur);
+  hipLaunchKernelGGL(k_embed, dim3(1), dim3(256), 0, s, (const void*)nullptr, 0, 0, (const long long*)nullptr, 0, 0, (float*)nullptr, pos, cos_t, sin_t, half, rope_cur);
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }

@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include "bz_internal.h"
+#include "bz_ggml.h"
 #include <type_traits>
 
 namespace {
@@ -565,8 +566,13 @@ template <int DT>
 __global__ void k_pf_cvt16(const float* x, size_t n, unsigned short* y) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) y[i] = to16<DT>(x[i]);
 }
-__global__ void k_pf_embed(const void* table, int tdt, const long long* tok, int S, int H, int act, float* out) {
+__global__ void k_pf_embed(const void* table, int tdt, int gg, const long long* tok, int S, int H, int act, float* out) {
   const int s = blockIdx.x;
+  if (gg != 0) {   // raw ggml rows (bz_ggml.h), as k_embed
+    const unsigned char* qrow = (const unsigned char*)table + (size_t)tok[s] * ggml_blk_row_bytes(gg, H);
+    for (int i = threadIdx.x; i < H; i += blockDim.x) out[(size_t)s * H + i] = pf_round(ggml_row_elem(gg, qrow, i), act);
+    return;
+  }
   const size_t row = (size_t)tok[s] * H;
   for (int i = threadIdx.x; i < H; i += blockDim.x) {
     float v;
@@ -1360,8 +1366,9 @@ int bzk_pf_cvt16(hipStream_t s, int dt, const float* x, size_t n, void* y) {
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
-int bzk_pf_embed(hipStream_t s, const void* table, int tdt, const long long* tok, int S, int H, int act, float* out) {
-  hipLaunchKernelGGL(k_pf_embed, dim3(S), dim3(256), 0, s, table, tdt, tok, S, H, act, out);
+int bzk_pf_embed(hipStream_t s, const void* table, int tdt, int gg, const long long* tok, int S, int H, int act, float* out) {
+  if (gg != 0 && (ggml_blk_row_bytes(gg, H) == 0 || H % (gg == BZ_GGML_Q8_0 ? 32 : 256))) BZ_FAIL(BZ_E_INVALID, "pf_embed: ggml type %d rows of %d", gg, H);
+  hipLaunchKernelGGL(k_pf_embed, dim3(S), dim3(256), 0, s, table, tdt, gg, tok, S, H, act, out);
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
