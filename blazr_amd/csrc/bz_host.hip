@@ -1466,22 +1466,23 @@ static int llama_step(bz_model* m, const StepIO& io) {
     // the fused single-launch kernel reads the context once per column slice, which only pays while the context is short
     const bool fuse_o = fuse_cap && (io.att_positions == 0 || (split_wanted && merge_fused));
     const bool split = split_wanted && (!fuse_o || merge_fused);
-    int SPL = 0, nsplit = 0;
+    int nsplit = 0;
     if (split) {
-      // long context: split-KV partials (all query heads of a group share the K/V rows), then merge (+ o_proj)
-      bzk_attn_split_plan(io.att_positions, &SPL, &nsplit);
-      BZ_TRY(bzk_attn_split(st, aa, SPL, nsplit, m->att_ws));
+      // long context: split-KV partials (all query heads of a group share the K/V rows), then merge (+ o_proj); the grid covers
+      // att_positions, the kernels slice the live context (position + 1) the same way for every grid
+      nsplit = bzk_attn_split_slices(io.att_positions);
+      BZ_TRY(bzk_attn_split(st, aa, nsplit, m->att_ws));
     }
     if (fuse_o) {
       // attention + o_proj in one launch: same ring protocol as a GEMV launch
       const int rz = (rs.ri + 1) % 3;
       aa.zero_buf = rs.dirty[rz] > 0 ? m->ring[rz] : nullptr; aa.zero_n = rs.dirty[rz];
-      if (split) BZ_TRY(bzk_attn_merge_oproj(st, aa, m->att_ws, SPL, nsplit, Ld.o.parts[0], m->ring[rs.ri]));
+      if (split) BZ_TRY(bzk_attn_merge_oproj(st, aa, m->att_ws, nsplit, Ld.o.parts[0], m->ring[rs.ri]));
       else BZ_TRY(bzk_attn_oproj(st, aa, Ld.o.parts[0], m->ring[rs.ri]));
       ov = VSrc{m->ring[rs.ri], 1};
       rs.dirty[rz] = 0; rs.dirty[rs.ri] = Ld.o.N; rs.ri = rz;
     } else {
-      if (split) BZ_TRY(bzk_attn_merge(st, aa, m->att_ws, SPL, nsplit));
+      if (split) BZ_TRY(bzk_attn_merge(st, aa, m->att_ws, nsplit));
       else BZ_TRY(bzk_attn_decode(st, aa));
       Pro pp{}; pp.mode = PRO_PLAIN; pp.src = VSrc{m->attn_out, 0}; pp.act = act; pp.H = 0;
       BZ_TRY(run_fused(m, Ld.o, pp, rs, &ov));
@@ -1759,6 +1760,7 @@ static int prefill_min_rows() {
   static const int v = getenv("BZ_NO_MFMA_PREFILL") ? (1 << 30) : (getenv("BZ_PREFILL_MIN") ? atoi(getenv("BZ_PREFILL_MIN")) : 8);
   return v;
 }
+static int prefill_exact(const bz_model* m, int n, bool decode_batch);
 static bool prefill_eligible(const bz_model* m, int S, int total_len, bool decode_batch = false) {
   const bz_model_config& c = m->cfg;
   static const bool no_gq = getenv("BZ_NO_GGUF_PREFILL") != nullptr;
@@ -1766,7 +1768,12 @@ static bool prefill_eligible(const bz_model* m, int S, int total_len, bool decod
   if (c.hidden % 64 || (c.n_heads * c.head_dim) % 64 || c.inter % 64 || c.head_dim % 8 || 256 % (c.head_dim / 8)) return false;
   const int rep = c.n_heads / c.n_kv_heads;
   if (rep != 1 && rep != 2 && rep != 4 && rep != 8) return false;
-  if (!bzk_pf_attn_mfma_ok(c.head_dim, rep) && bzk_pf_attn_smem(c.n_heads, c.n_kv_heads, c.head_dim, total_len) > 160 * 1024) return false;   // (the scalar kernel keeps scores in LDS)
+  // the scalar attention kernel keeps the scores of the whole context in LDS: where prefill_dense would pick it (exact rows, f32 activations, no MFMA
+  // form) and the context does not fit, the prompt runs on the decode step, token by token, whose attention has no context limit
+  const bool attn_exact = !decode_batch && (prefill_exact(m, S, false) != 0 || c.act_dtype == BZ_F32);
+  const bool attn_mfma = !decode_batch && c.act_dtype != BZ_F32 && !attn_exact && bzk_pf_attn_mfma_ok(c.head_dim, rep);
+  if (!attn_mfma && (!decode_batch || !bzk_pf_attn_mfma_ok(c.head_dim, rep)) &&
+      bzk_pf_attn_smem(c.n_heads, c.n_kv_heads, c.head_dim, total_len, attn_exact) > 160 * 1024) return false;
   // every projection either dense in the activation dtype (MFMA GEMM) or int4 without act-order (multi-row dot4 GEMM)
   if (c.act_dtype == BZ_F32) {
     // f32 activations (GGUF models): every projection in a block format, no bias, same K in all parts of a fused linear; the head stays the decode GEMV

@@ -3688,19 +3688,28 @@ int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long lo
 //   k_attn_merge[_oproj]: merges the live partials of a head (weights exp(m_s - M)), then -- fused form -- multiplies by the o_proj slab exactly
 //                        like k_attn2's tail.
 // The grid of k_attn_split is sized for the cache CAPACITY so that a captured graph is valid at every position; blocks beyond the
-// context return at once.
+// context return at once.  The slice length is derived on the device from the live context (att_split_len), never from the grid, so a
+// graph captured for a large capacity slices a context exactly as the eager step does (same partials, same merge, same bits).
 // ---------------------------------------------------------------------------------------------------------
 #define ATT_PSTRIDE 132   // floats per partial: [0] m, [1] l, [4..131] o
+#define ATT_MAX_SPLITS 128
+
+// positions per slice for a context of `len` positions: 128, doubled until at most ATT_MAX_SPLITS slices cover the context
+__host__ __device__ __forceinline__ int att_split_len(int len) {
+  int spl = 128;
+  while ((len + spl - 1) / spl > ATT_MAX_SPLITS) spl *= 2;
+  return spl;
+}
 
 template <int KVDT, int PAGED, int REP>
-__global__ __launch_bounds__(REP == 8 ? 512 : 256) void k_attn_split(AttnArgs a, int SPL, int nsplit, float* __restrict__ ws) {
+__global__ __launch_bounds__(REP == 8 ? 512 : 256) void k_attn_split(AttnArgs a, int nsplit, float* __restrict__ ws) {
   constexpr int HD = 128, half = 64, NW = REP == 8 ? 8 : 4, NTH = NW * 64, PW = 128 / NW, NL = PW / 4;
   __shared__ __attribute__((aligned(16))) unsigned q2[REP][64];
   __shared__ __attribute__((aligned(16))) unsigned k2[64], v2[64];
   __shared__ float wred[REP][NW], lred[REP][NW];
   __shared__ __attribute__((aligned(16))) float pout[NW][REP][128];
   asm volatile("" :: "s"(a.kv.k), "s"(a.kv.v), "s"(a.kv.cap), "s"(a.kv.layer_stride), "s"(a.layer), "s"(a.act), "s"(a.interleaved), "s"(a.rope_cur),
-               "s"(a.qkv.p), "s"(a.qkv.fix), "s"(a.nq), "s"(a.nkv), "s"(a.pos), "s"(SPL), "s"(nsplit), "s"(ws), "s"(a.kv.bs), "s"(a.kv.n_kv),
+               "s"(a.qkv.p), "s"(a.qkv.fix), "s"(a.nq), "s"(a.nkv), "s"(a.pos), "s"(nsplit), "s"(ws), "s"(a.kv.bs), "s"(a.kv.n_kv),
                "s"(a.zero_buf), "s"(a.zero_n));
   const int kvh = blockIdx.x / nsplit, s = blockIdx.x % nsplit;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -3726,6 +3735,7 @@ __global__ __launch_bounds__(REP == 8 ? 512 : 256) void k_attn_split(AttnArgs a,
     for (int z = blockIdx.x * NTH + tid; z < a.zero_n; z += gridDim.x * NTH) a.zero_buf[z] = 0;
   const int pos = __builtin_amdgcn_readfirstlane(pos_v);
   const int len = pos + 1, pmax = pos > 0 ? pos - 1 : 0;
+  const int SPL = att_split_len(len);
   const int p0 = s * SPL;
   if (p0 >= len) return;                    // split beyond the context (the grid covers the capacity)
   const int p1 = min(p0 + SPL, len);
@@ -3908,18 +3918,18 @@ __device__ __forceinline__ void att_merge_512(const float* __restrict__ ws, int 
   if (tid < 128) outh[tid] = round_act(((osum[0][tid] + osum[1][tid]) + (osum[2][tid] + osum[3][tid])) / L, act);
 }
 
-__global__ __launch_bounds__(512) void k_attn_merge(AttnArgs a, const float* __restrict__ ws, int SPL, int nsplit) {
+__global__ __launch_bounds__(512) void k_attn_merge(AttnArgs a, const float* __restrict__ ws, int nsplit) {
   __shared__ float wS[128], red[16], osum[4][128], outh[128];
   const int hq = blockIdx.x;
-  const int pos = a.pos[0];
-  const int ns = (pos + 1 + SPL - 1) / SPL;
+  const int len = a.pos[0] + 1, SPL = att_split_len(len);
+  const int ns = (len + SPL - 1) / SPL;
   att_merge_512(ws, hq, nsplit, ns, a.act, wS, red, osum, outh);
   __syncthreads();
   if (threadIdx.x < 128) a.out[(size_t)hq * 128 + threadIdx.x] = outh[threadIdx.x];
 }
 
 template <int TPW>
-__global__ __launch_bounds__(512) void k_attn_merge_oproj(AttnArgs a, const float* __restrict__ ws, int SPL, int nsplit, const uint4* __restrict__ W,
+__global__ __launch_bounds__(512) void k_attn_merge_oproj(AttnArgs a, const float* __restrict__ ws, int nsplit, const uint4* __restrict__ W,
                                                           const __half* __restrict__ S, const unsigned char* __restrict__ Z,
                                                           const float* __restrict__ bias, int CS, long long* acc) {
   constexpr int HD = 128;
@@ -3927,7 +3937,7 @@ __global__ __launch_bounds__(512) void k_attn_merge_oproj(AttnArgs a, const floa
   __shared__ __attribute__((aligned(16))) float outh[128];
   __shared__ uint4 xpl[4 * XQ_NP];
   __shared__ int4 gpar[2];
-  asm volatile("" :: "s"(a.pos), "s"(a.act), "s"(a.nq), "s"(ws), "s"(SPL), "s"(nsplit), "s"(W), "s"(S), "s"(Z), "s"(bias), "s"(CS), "s"(acc),
+  asm volatile("" :: "s"(a.pos), "s"(a.act), "s"(a.nq), "s"(ws), "s"(nsplit), "s"(W), "s"(S), "s"(Z), "s"(bias), "s"(CS), "s"(acc),
                "s"(a.zero_buf), "s"(a.zero_n));
   const int hq = blockIdx.x / CS, cs = blockIdx.x % CS;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -3952,8 +3962,8 @@ __global__ __launch_bounds__(512) void k_attn_merge_oproj(AttnArgs a, const floa
   }
   if (a.zero_buf)
     for (int z = blockIdx.x * 512 + tid; z < a.zero_n; z += gridDim.x * 512) a.zero_buf[z] = 0;
-  const int pos = __builtin_amdgcn_readfirstlane(pos_v);
-  const int ns = (pos + 1 + SPL - 1) / SPL;
+  const int len = __builtin_amdgcn_readfirstlane(pos_v) + 1, SPL = att_split_len(len);
+  const int ns = (len + SPL - 1) / SPL;
   att_merge_512(ws, hq, nsplit, ns, a.act, wS, red, osum, outh);
   __syncthreads();
   quant_x128<512>(outh, HD, xpl, gpar);
@@ -3968,12 +3978,11 @@ __global__ __launch_bounds__(512) void k_attn_merge_oproj(AttnArgs a, const floa
   }
 }
 
-// split plan from the positions the launch must cover: SPL positions per block (multiple of 128), at most 128 splits
-void bzk_attn_split_plan(int positions, int* SPL, int* nsplit) {
-  int spl = 128;
-  while ((positions + spl - 1) / spl > 128) spl *= 2;
-  *SPL = spl; *nsplit = (positions + spl - 1) / spl;
-  if (*nsplit < 1) *nsplit = 1;
+// grid of the split launches: enough slices for every context of up to `positions` positions (the most slices any such context uses;
+// the kernels derive the live slice length and count from the position)
+int bzk_attn_split_slices(int positions) {
+  // up to 128 * 128 positions every context uses 128-position slices; beyond, the slice length doubles and the count stays <= ATT_MAX_SPLITS
+  return std::min((std::max(positions, 1) + 127) / 128, ATT_MAX_SPLITS);
 }
 int bzk_attn_split_ok(const AttnArgs& a) {
   const int rep = a.nkv > 0 ? a.nq / a.nkv : 0;
@@ -3982,10 +3991,10 @@ int bzk_attn_split_ok(const AttnArgs& a) {
 }
 size_t bzk_attn_split_ws_bytes(int nq) { return (size_t)nq * 128 * ATT_PSTRIDE * 4; }
 
-int bzk_attn_split(hipStream_t s, const AttnArgs& a, int SPL, int nsplit, float* ws) {
-  if (!bzk_attn_split_ok(a) || nsplit < 1 || nsplit > 128 || SPL % 128) BZ_FAIL(BZ_E_INVALID, "split attention does not apply to this shape");
+int bzk_attn_split(hipStream_t s, const AttnArgs& a, int nsplit, float* ws) {
+  if (!bzk_attn_split_ok(a) || nsplit < 1 || nsplit > ATT_MAX_SPLITS) BZ_FAIL(BZ_E_INVALID, "split attention does not apply to this shape");
   const int rep = a.nq / a.nkv;
-#define LAUNCH_SP(DT, PG, R) BZ_LAUNCH("attn_split", 0.0, (k_attn_split<DT, PG, R>), dim3(a.nkv * nsplit), dim3(R == 8 ? 512 : 256), 0, s, a, SPL, nsplit, ws)
+#define LAUNCH_SP(DT, PG, R) BZ_LAUNCH("attn_split", 0.0, (k_attn_split<DT, PG, R>), dim3(a.nkv * nsplit), dim3(R == 8 ? 512 : 256), 0, s, a, nsplit, ws)
 #define LAUNCH_SP_R(DT, PG) do { if (rep == 1) LAUNCH_SP(DT, PG, 1); else if (rep == 2) LAUNCH_SP(DT, PG, 2); else if (rep == 4) LAUNCH_SP(DT, PG, 4); \
                                  else LAUNCH_SP(DT, PG, 8); } while (0)
 #define LAUNCH_SP_P(DT) do { if (a.kv.paged) LAUNCH_SP_R(DT, 1); else LAUNCH_SP_R(DT, 0); } while (0)
@@ -3996,18 +4005,18 @@ int bzk_attn_split(hipStream_t s, const AttnArgs& a, int SPL, int nsplit, float*
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
-int bzk_attn_merge(hipStream_t s, const AttnArgs& a, const float* ws, int SPL, int nsplit) {
-  BZ_LAUNCH("attn_merge", 0.0, k_attn_merge, dim3(a.nq), dim3(512), 0, s, a, ws, SPL, nsplit);
+int bzk_attn_merge(hipStream_t s, const AttnArgs& a, const float* ws, int nsplit) {
+  BZ_LAUNCH("attn_merge", 0.0, k_attn_merge, dim3(a.nq), dim3(512), 0, s, a, ws, nsplit);
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
 int bzk_attn_merge_oproj_ok(const AttnArgs& a, const LinearDev& L) { int nw; return attn_oproj_plan(a, L, nw) > 0 && nw == 8; }
-int bzk_attn_merge_oproj(hipStream_t s, const AttnArgs& a, const float* ws, int SPL, int nsplit, const LinearDev& L, long long* acc) {
+int bzk_attn_merge_oproj(hipStream_t s, const AttnArgs& a, const float* ws, int nsplit, const LinearDev& L, long long* acc) {
   int NW;
   const int CS = attn_oproj_plan(a, L, NW);
   if (CS <= 0 || NW != 8) BZ_FAIL(BZ_E_INVALID, "attn merge + o_proj fusion does not apply to this shape");
   const int TPW = (L.N / 64) / (CS * 8);
-#define LAUNCH_MO(T) BZ_LAUNCH("attn_merge+o_proj", L.algo_bytes, (k_attn_merge_oproj<T>), dim3(a.nq * CS), dim3(512), 0, s, a, ws, SPL, nsplit, \
+#define LAUNCH_MO(T) BZ_LAUNCH("attn_merge+o_proj", L.algo_bytes, (k_attn_merge_oproj<T>), dim3(a.nq * CS), dim3(512), 0, s, a, ws, nsplit, \
     (const uint4*)L.w, (const __half*)L.scales, (const unsigned char*)L.zeros, L.bias, CS, acc)
   if (TPW == 1) LAUNCH_MO(1); else LAUNCH_MO(2);
 #undef LAUNCH_MO

@@ -286,6 +286,30 @@ class OrcLinear:
         return out
 
 
+def kv_rows(kv):
+    """numpy view [layer][kv_head][capacity][head_dim] of an orc_kv's K and V (writable: tests inject cached rows directly)"""
+    c = kv.contents
+    shape = (c.n_layers, c.n_kv_heads, c.capacity, c.head_dim)
+    view = lambda p: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=shape)
+    return view(c.k), view(c.v)
+
+
+def kv_inject(kv, layer, K, V):
+    """write rows 0..T-1 of one layer (K, V: [T, n_kv_heads, head_dim], values already representable in the activation dtype) and make T the
+    cache's length"""
+    k, v = kv_rows(kv)
+    T = K.shape[0]
+    k[layer, :, :T] = np.asarray(K, np.float32).transpose(1, 0, 2)
+    v[layer, :, :T] = np.asarray(V, np.float32).transpose(1, 0, 2)
+    kv.contents.seq_len = max(kv.contents.seq_len, T)
+
+
+def mla_rows(cache):
+    """numpy view [layer][capacity][kv_lora_rank + rope_dim] of an orc_mla_cache's latent rows (writable: tests inject cached latents directly)"""
+    c = cache.contents
+    return np.ctypeslib.as_array(C.cast(c.lat, C.POINTER(C.c_float)), shape=(c.n_layers, c.capacity, c.width))
+
+
 def ggml_dequant(ggml_type, blocks, n):
     blocks = np.ascontiguousarray(blocks, dtype=np.uint8)
     out = np.empty(n, dtype=np.float32)

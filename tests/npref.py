@@ -120,9 +120,25 @@ def linear(spec, x):
 
 
 def rope_tables(cfg):
+    """cos / sin [max_seq_len, head_dim / 2] as HF builds them: inverse frequencies in float64, then the angle position * inv_freq as a
+    float32 product (HF multiplies float32 tensors), its cos / sin evaluated in float64 and rounded to float32 (times YaRN's attention
+    factor).  At 131 072 positions the f32 angle is what the tables hold, not the exact one: every implementation must round it the same way."""
     hd, P = cfg["head_dim"], cfg["max_seq_len"]
-    inv = 1.0 / (np.float64(cfg["rope_theta"]) ** (np.arange(0, hd, 2, dtype=np.float64) / hd))
+    theta = np.float64(cfg["rope_theta"])
+    inv = 1.0 / (theta ** (np.arange(0, hd, 2, dtype=np.float64) / hd))
     rs = cfg.get("rope_scaling")
+    af = np.float32(1.0)
+    if rs and rs["type"] == "yarn":
+        # HF _compute_yarn_parameters: correction range in dims from beta_fast / beta_slow, linear ramp between interpolation and extrapolation
+        f, old = rs["factor"], rs["original_max_position_embeddings"]
+        dim_of = lambda rot: hd * np.log(old / (rot * 2 * np.pi)) / (2 * np.log(theta))
+        lo = max(np.floor(dim_of(rs.get("beta_fast") or 32.0)), 0.0)
+        hi = min(np.ceil(dim_of(rs.get("beta_slow") or 1.0)), hd - 1.0)
+        if lo == hi:
+            hi += 0.001
+        ramp = np.clip((np.arange(hd // 2, dtype=np.float64) - lo) / (hi - lo), 0.0, 1.0)
+        inv = (inv / f) * ramp + inv * (1.0 - ramp)
+        af = np.float32(rs.get("attention_factor") or (0.1 * np.log(f) + 1.0 if f > 1.0 else 1.0))
     if rs and rs["type"] == "linear":
         inv = inv / rs["factor"]
     elif rs and rs["type"] == "llama3":
@@ -132,7 +148,7 @@ def rope_tables(cfg):
         mid = (1 - smooth) * inv / f + smooth * inv
         inv = np.where(wl > old / lo, inv / f, np.where(wl < old / hi, inv, mid))
     ang = np.arange(P, dtype=np.float32)[:, None] * inv.astype(np.float32)[None, :]
-    return np.cos(ang.astype(np.float64)).astype(np.float32), np.sin(ang.astype(np.float64)).astype(np.float32)
+    return np.cos(ang.astype(np.float64)).astype(np.float32) * af, np.sin(ang.astype(np.float64)).astype(np.float32) * af
 
 
 def rope(v, c, s, interleaved):
@@ -172,6 +188,17 @@ class NpLlama:
         y = x @ self.W[l][name].T
         b = self.B[l][name]
         return (y + b.astype(np.float32)) if b is not None else y
+
+    def qkv0(self, token, pos):
+        """layer 0's roped q [n_heads, head_dim], roped k and v [n_kv_heads, head_dim] for `token` at `pos`, rounded as step() rounds them"""
+        c = self.cfg
+        R = lambda a: round_act(a, c["act_dtype"])
+        nq, nkv, hd = c["n_heads"], c["n_kv_heads"], c["head_dim"]
+        xn = rms_norm(R(self.emb[token]), self.m["layers"][0]["attn_norm"], c["rms_eps"], c["act_dtype"])
+        q = R(self._lin(0, "q", xn)).reshape(nq, hd)
+        k = R(self._lin(0, "k", xn)).reshape(nkv, hd)
+        v = R(self._lin(0, "v", xn)).reshape(nkv, hd)
+        return (R(rope(q, self.cos[pos], self.sin[pos], c["rope_interleaved"])), R(rope(k, self.cos[pos], self.sin[pos], c["rope_interleaved"])), v)
 
     def step(self, token, pos):
         c = self.cfg
@@ -227,6 +254,12 @@ class NpLlamaTruth:
         self.emb = dequant(dict(kind="dense", weight=model["embed"]))
         self.K = [[] for _ in model["layers"]]
         self.V = [[] for _ in model["layers"]]
+        self.hist = None
+
+    def set_history(self, hist):
+        """hist: one (K, V) pair per layer, each [T, n_kv_heads, head_dim] -- the cached rows of positions 0..T-1.  Until it is replaced (or
+        set to None), every step() attends over these rows plus its own, instead of the rows earlier steps appended, and appends nothing."""
+        self.hist = [(np.asarray(k, np.float64), np.asarray(v, np.float64)) for k, v in hist]
 
     def _lin(self, l, name, x):
         y = self.W[l][name] @ x
@@ -246,9 +279,13 @@ class NpLlamaTruth:
             q = rope(self._lin(l, "q", xn).reshape(nq, hd), self.cos[pos], self.sin[pos], c["rope_interleaved"])
             k = rope(self._lin(l, "k", xn).reshape(nkv, hd), self.cos[pos], self.sin[pos], c["rope_interleaved"])
             v = self._lin(l, "v", xn).reshape(nkv, hd)
-            self.K[l].append(k)
-            self.V[l].append(v)
-            Kc, Vc = np.stack(self.K[l], axis=1), np.stack(self.V[l], axis=1)
+            if self.hist is not None:
+                Kc = np.concatenate([self.hist[l][0], k[None]]).transpose(1, 0, 2)
+                Vc = np.concatenate([self.hist[l][1], v[None]]).transpose(1, 0, 2)
+            else:
+                self.K[l].append(k)
+                self.V[l].append(v)
+                Kc, Vc = np.stack(self.K[l], axis=1), np.stack(self.V[l], axis=1)
             rep = nq // nkv
             o = np.empty((nq, hd), dtype=np.float64)
             for hh in range(nq):
