@@ -505,7 +505,8 @@ extern "C" int bz_model_add_gguf(bz_model* m, const char* name, int ggml_type, i
   else if (ggml_type == BZ_GGML_Q4_K) rowb = (size_t)K / 256 * 144;
   else if (ggml_type == BZ_GGML_Q5_K) rowb = (size_t)K / 256 * 176;
   else if (ggml_type == BZ_GGML_Q6_K) rowb = (size_t)K / 256 * 210;
-  else BZ_FAIL(BZ_E_UNSUPPORTED, "add_gguf '%s': ggml type %d is not implemented (F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K are)", name, ggml_type);
+  else if (ggml_is_legacy(ggml_type)) rowb = (size_t)K / 32 * ggml_blk_row_bytes(ggml_type, 32);   // 18 / 20 / 22 / 24 B per 32 weights
+  else BZ_FAIL(BZ_E_UNSUPPORTED, "add_gguf '%s': ggml type %d is not implemented (F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q4_K, Q5_K, Q6_K are)", name, ggml_type);
   // N % 64: the column tiles of the repacked GEMV layouts.  The token embedding is gathered by row from the raw blocks: any vocabulary size
   const bool by_row = strcmp(name, "model.embed_tokens.weight") == 0;
   if ((!by_row && N % 64) || N <= 0 || K % 256) BZ_FAIL(BZ_E_UNSUPPORTED, "add_gguf '%s': N=%lld must be a multiple of 64 and K=%lld of 256", name, (long long)N, (long long)K);
@@ -642,9 +643,14 @@ static int build_gq(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L
   const int K = (int)rs[0]->K, type = rs[0]->ggml_type;
   int N = 0;
   for (auto* r : rs) N += (int)r->N;
-  const int kind = type == BZ_GGML_Q8_0 ? LK_Q80 : type == BZ_GGML_Q4_K ? LK_Q4K : type == BZ_GGML_Q5_K ? LK_Q5K : LK_Q6K;
+  const int kind = type == BZ_GGML_Q8_0 ? LK_Q80 : type == BZ_GGML_Q4_K ? LK_Q4K : type == BZ_GGML_Q5_K ? LK_Q5K : type == BZ_GGML_Q4_0 ? LK_Q40
+                 : type == BZ_GGML_Q4_1 ? LK_Q41 : type == BZ_GGML_Q5_0 ? LK_Q50 : type == BZ_GGML_Q5_1 ? LK_Q51 : LK_Q6K;
   size_t wqb, whb = 0, hdb = 0, ddb;
   if (kind == LK_Q80) { wqb = (size_t)N * K; ddb = (size_t)N * (K / 32) * 2; }
+  else if (kind >= LK_Q40) {   // nibbles, [Q5: 5th-bit plane,] per-chunk d [and m]
+    wqb = (size_t)N * K / 2; whb = (kind == LK_Q50 || kind == LK_Q51) ? (size_t)N * K / 8 : 0;
+    hdb = (size_t)N * (K / 256) * ((kind == LK_Q41 || kind == LK_Q51) ? 32 : 16); ddb = 0;
+  }
   else if (kind == LK_Q4K) { wqb = (size_t)N * K / 2; hdb = (size_t)N * (K / 256) * 16; ddb = 0; }
   else if (kind == LK_Q5K) { wqb = (size_t)N * K / 2; whb = (size_t)N * K / 8; hdb = (size_t)N * (K / 256) * 16; ddb = 0; }
   else { wqb = (size_t)N * K / 2; whb = (size_t)N * K / 4; hdb = (size_t)N * (K / 256) * 16; ddb = (size_t)N * (K / 256) * 2; }
@@ -668,7 +674,7 @@ static int build_gq(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L
   L->kind = kind; L->N = N; L->K = K; L->gs = kind == LK_Q80 ? 32 : 256; L->w = wq; L->zeros = wh; L->hdr = hd; L->scales = dd;
   L->gw = choose_sbw(N, K, gemv_target_wgs());
   L->bytes = wqb + whb + hdb + ddb;
-  L->algo_bytes = L->bytes;     // the repack keeps the ggml bytes per weight (34/32, 144/256, 176/256, 210/256)
+  L->algo_bytes = L->bytes;     // the repack keeps the ggml bytes per weight (34/32, 144/256, 176/256, 210/256; Q4_0..Q5_1 18, 20, 22, 24 / 32)
   return BZ_OK;
 }
 
@@ -723,6 +729,11 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
         if (L.kind == LK_Q80) { V.w = (char*)L.w + t0 * 64 * K; V.scales = (char*)L.scales + t0 * (K / 32) * 64 * 2; }
         else if (L.kind == LK_Q4K) { V.w = (char*)L.w + t0 * 32 * K; V.hdr = (char*)L.hdr + t0 * (K / 256) * 64 * 16; }
         else if (L.kind == LK_Q5K) { V.w = (char*)L.w + t0 * 32 * K; V.zeros = (char*)L.zeros + t0 * 8 * K; V.hdr = (char*)L.hdr + t0 * (K / 256) * 64 * 16; }
+        else if (L.kind >= LK_Q40) {
+          V.w = (char*)L.w + t0 * 32 * K;
+          if (L.zeros) V.zeros = (char*)L.zeros + t0 * 8 * K;
+          V.hdr = (char*)L.hdr + t0 * (K / 256) * 64 * ((L.kind == LK_Q41 || L.kind == LK_Q51) ? 32 : 16);
+        }
         else { V.w = (char*)L.w + t0 * 32 * K; V.zeros = (char*)L.zeros + t0 * 16 * K; V.hdr = (char*)L.hdr + t0 * (K / 256) * 64 * 16;
                V.scales = (char*)L.scales + t0 * (K / 256) * 64 * 2; }
         V.gw = choose_sbw(V.N, V.K, gemv_target_wgs());
@@ -855,14 +866,17 @@ extern "C" int bz_model_finalize(bz_model* m) {
   }
   BZ_HIP(hipStreamSynchronize(m->dev->stream));
   BZ_TRY(take_vector_f32(m, "model.norm.weight", H, &m->final_norm));
-  // embeddings stay in their storage dtype (rows are gathered); tied lm_head reads the same buffer.  A GGUF block-quantised table (Q8_0 / Q4_K / Q5_K /
-  // Q6_K token_embd) stays as the file's raw rows, decoded per gathered row; its tied lm_head is a repacked copy on the block-quant GEMV path
+  // embeddings stay in their storage dtype (rows are gathered); tied lm_head reads the same buffer.  A GGUF block-quantised table (Q4_0 / Q4_1 / Q5_0 /
+  // Q5_1 / Q8_0 / Q4_K / Q5_K / Q6_K token_embd) stays as the file's raw rows, decoded per gathered row; its tied lm_head is a repacked copy on the block-quant
+  // GEMV path
   {
     auto it = m->raw.find("model.embed_tokens.weight");
     if (it == m->raw.end()) BZ_FAIL(BZ_E_NOTFOUND, "finalize: 'model.embed_tokens.weight' was not added");
     RawTensor& r = it->second;
-    const bool qemb = r.kind == 3 && (r.ggml_type == BZ_GGML_Q8_0 || r.ggml_type == BZ_GGML_Q4_K || r.ggml_type == BZ_GGML_Q5_K || r.ggml_type == BZ_GGML_Q6_K);
-    if ((r.kind != 0 && !qemb) || r.N != V || r.K != H) BZ_FAIL(BZ_E_INVALID, "finalize: embed_tokens must be dense or GGUF Q8_0/Q4_K/Q5_K/Q6_K [vocab, hidden]");
+    const bool qemb = r.kind == 3 && (r.ggml_type == BZ_GGML_Q8_0 || r.ggml_type == BZ_GGML_Q4_K || r.ggml_type == BZ_GGML_Q5_K || r.ggml_type == BZ_GGML_Q6_K ||
+                                      ggml_is_legacy(r.ggml_type));
+    if ((r.kind != 0 && !qemb) || r.N != V || r.K != H)
+      BZ_FAIL(BZ_E_INVALID, "finalize: embed_tokens must be dense or GGUF Q4_0/Q4_1/Q5_0/Q5_1/Q8_0/Q4_K/Q5_K/Q6_K [vocab, hidden]");
     const bool tied = c.tie_embeddings || !m->raw.count("lm_head.weight");
     if (qemb && tied) {
       if (V % 64) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: tied lm_head over a quantised embedding needs a vocabulary that is a multiple of 64 (vocab %d)", V);

@@ -53,7 +53,7 @@ struct Pro {
   int f32_sums;        // dense k_gemv_rows2: f32 FMA chains instead of the exact (double) sums -- the DeepSeek-V2 path sets it (k_gemv_rows2's EX)
 };
 
-enum { LK_NONE = 0, LK_Q4G = 1, LK_ROWS = 2, LK_Q4K = 3, LK_Q6K = 4, LK_Q80 = 5, LK_Q5K = 6 };
+enum { LK_NONE = 0, LK_Q4G = 1, LK_ROWS = 2, LK_Q4K = 3, LK_Q6K = 4, LK_Q80 = 5, LK_Q5K = 6, LK_Q40 = 7, LK_Q41 = 8, LK_Q50 = 9, LK_Q51 = 10 };
 
 // Device-resident linear layer in kernel layout.
 struct LinearDev {

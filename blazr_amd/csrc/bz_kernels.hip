@@ -842,24 +842,32 @@ bool bzk_gemv_slim_ok(const LinearDev& L, const Pro& pro) {
 }
 
 // =========================================================================================================
-// GGUF block-quantised GEMV: Q8_0 / Q4_K / Q6_K  (formats = public GGML block layouts, gguf.rs:33 hands
+// GGUF block-quantised GEMV: Q8_0 / Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1 / Q5_0 / Q5_1  (formats = public GGML block layouts, gguf.rs:33 hands
 // the blocks over opaquely).  Same skeleton as k_gemv_q4g -- lane == output column, split-K over k-slices, fused
 // prologues, 3-plane int8 activations on V_DOT4_I32_I8, fixed-point atomics -- with the activation slice scaled per
 // 32-k chunk so that every format's sub-block structure (32 for Q8_0/Q4_K, 16 for Q6_K) falls on chunk boundaries.
 //
-// HBM layouts after the load-time repack (bytes per weight unchanged: 34/32, 144/256, 210/256):
+// HBM layouts after the load-time repack (bytes per weight unchanged: 34/32, 144/256, 176/256, 210/256, 18/20/22/24 per 32):
 //   Q8_0 : q  [N/64][K/16][64][16 B] int8,                      d  [N/64][K/32][64] f16
 //   Q4_K : q  [N/64][K/32][64][16 B] nibbles (A/B order as Q4G), hdr [N/64][K/256][64][16 B] = {d, dmin, scales[12]} verbatim
 //   Q6_K : ql [N/64][K/32][64][16 B] low nibbles (A/B order),    qh [N/64][K/32][64][8 B] 2-bit highs,
 //          sc [N/64][K/256][64][16 B] int8 x16,                  d  [N/64][K/256][64] f16
 //   Q5_K : q  [N/64][K/32][64][16 B] low nibbles (A/B order),    qh [N/64][K/256][64][8 x 4 B] 5th bits: word c = chunk c, bit 8 b + F = k 4 F + b,
 //          hdr [N/64][K/256][64][16 B] = {d, dmin, scales[12]} verbatim (Q4_K's)      -- 128 + 32 + 16 = ggml's 176 B per 256 weights
+//   Q4_0 / Q4_1 / Q5_0 / Q5_1 (the legacy 32-weight blocks: chunk c of a superblock = one ggml block):
+//          q  [N/64][K/32][64][16 B] plain nibbles (A/B order, as Q5_K),  Q5_0 / Q5_1: qh exactly Q5_K's 5th-bit plane,
+//          hdr [N/64][K/256][64][8 x f16 d] (Q4_0 / Q5_0, 16 B)  or  [N/64][K/256][64][8 x {f16 d, f16 m}] (Q4_1 / Q5_1, 32 B)
+//          -- 144 / 160 / 176 / 192 B per 256 weights = ggml's 18 / 20 / 22 / 24 B per 32
 // per-chunk activation parameters in LDS (2 x int4 per chunk):
 //   P0 = { sx (f32 bits), Sa_h, Sa_m, Sa_l }   P1 = { Sb_h, Sb_m, Sb_l, 0 }
-//   Q4_K: Sa = sum over the chunk, Sb = sum over k%8 >= 4 (for the signed high-nibble trick);  Q5_K: Sa only;  Q6_K: Sa / Sb = sums over the
-//   first / second 16;  Q8_0: unused.
+//   Q4_K: Sa = sum over the chunk, Sb = sum over k%8 >= 4 (for the signed high-nibble trick);  Q5_K and the legacy formats: Sa only;  Q6_K: Sa / Sb
+//   = sums over the first / second 16;  Q8_0: unused.
 // =========================================================================================================
-enum { GQ_Q80 = 0, GQ_Q4K = 1, GQ_Q6K = 2, GQ_MIX = 3, GQ_Q5K = 4 };   // MIX: Q4_K tiles followed by Q6_K tiles in one launch (the Q4_K_M q/k + v split)
+enum { GQ_Q80 = 0, GQ_Q4K = 1, GQ_Q6K = 2, GQ_MIX = 3, GQ_Q5K = 4, GQ_Q40 = 5, GQ_Q41 = 6, GQ_Q50 = 7, GQ_Q51 = 8 };   // MIX: Q4_K tiles followed by Q6_K
+                                                                                                                    // tiles in one launch (the Q4_K_M q/k + v split)
+__host__ __device__ constexpr bool gq_legacy(int f) { return f == GQ_Q40 || f == GQ_Q41 || f == GQ_Q50 || f == GQ_Q51; }
+__host__ __device__ constexpr bool gq_has5(int f) { return f == GQ_Q50 || f == GQ_Q51; }     // legacy formats with a 5th-bit plane
+__host__ __device__ constexpr bool gq_affine(int f) { return f == GQ_Q41 || f == GQ_Q51; }   // legacy formats with an offset m (32-byte header)
 #define XQ_MAX 8355000.0f  // < 127*65536 + 127*256 + 127: the largest magnitude of three balanced int8 planes
 
 // one thread's octet (8 consecutive k of a 32-k chunk; the chunk's four octets sit in four consecutive lanes, quad-aligned) -> three int8 planes
@@ -885,7 +893,7 @@ __device__ __forceinline__ void quant8_x32(const float (&v)[8], int e0, bool on,
     wm[i >> 2] |= ((unsigned)mid & 255u) << (8 * (i & 3));
     wl[i >> 2] |= ((unsigned)lo & 255u) << (8 * (i & 3));
     if (FMT == GQ_Q4K || FMT == GQ_MIX) { sa[0] += hi; sa[1] += mid; sa[2] += lo; if (i >= 4) { sb[0] += hi; sb[1] += mid; sb[2] += lo; } }
-    if (FMT == GQ_Q6K || FMT == GQ_Q5K) { sa[0] += hi; sa[1] += mid; sa[2] += lo; }   // per-thread sum; halves are separated below
+    if (FMT == GQ_Q6K || FMT == GQ_Q5K || gq_legacy(FMT)) { sa[0] += hi; sa[1] += mid; sa[2] += lo; }   // per-thread sum; halves are separated below
   }
   if (FMT == GQ_Q6K || FMT == GQ_MIX) {
     // lanes 0,1 of the 4-lane group hold k 0..15 (first half), lanes 2,3 hold k 16..31
@@ -909,7 +917,7 @@ __device__ __forceinline__ void quant8_x32(const float (&v)[8], int e0, bool on,
       sb[q] = grp_reduce<4, OpAdd>(sb[q]);
     }
   }
-  if (FMT == GQ_Q5K) {
+  if (FMT == GQ_Q5K || gq_legacy(FMT)) {
 #pragma unroll
     for (int q = 0; q < 3; q++) sa[q] = grp_reduce<4, OpAdd>(sa[q]);
   }
@@ -989,6 +997,39 @@ __device__ __forceinline__ float q5k_chunk(const unsigned (&w)[8], const uint4* 
   return __int_as_float(p0.x) * ((d * (float)sc) * planes_f(u[0], u[1], u[2]) - (dmin * (float)mn) * planes_f(p0.y, p0.z, p0.w));
 }
 
+// y term of one legacy chunk (one ggml block): nibbles `nib` (A/B order), Q5: 5th-bit word hb; dm = {f16 d, f16 m} (m only for Q4_1 / Q5_1).  With sx the
+// chunk's activation scale and U = sum q x over the three planes (q the stored 4- / 5-bit value):
+//   Q4_0: sx d (U - 8 Sa)    Q5_0: sx d (U - 16 Sa)    Q4_1 / Q5_1: sx (d U + m Sa)
+template <int FMT>
+__device__ __forceinline__ float legacy_chunk(const uint4& nib, unsigned hb, unsigned dm, const uint4* xh4, const uint4* xm4, const uint4* xl4, int cc,
+                                              const int4* cpar) {
+  unsigned w[8];
+  if (gq_has5(FMT)) {
+    q5k_words(nib, hb, w);
+  } else {
+    const unsigned ww[4] = {nib.x, nib.y, nib.z, nib.w};
+#pragma unroll
+    for (int j = 0; j < 4; j++) { w[2 * j] = ww[j] & 0x0F0F0F0Fu; w[2 * j + 1] = (ww[j] >> 4) & 0x0F0F0F0Fu; }
+  }
+  int u[3] = {0, 0, 0};
+  dot_chunk8(w, xh4, xm4, xl4, cc, u);
+  const int4 p0 = cpar[2 * cc];
+  const float d = __half2float(__ushort_as_half((unsigned short)(dm & 0xffffu)));
+  if (gq_affine(FMT)) {
+    const float m = __half2float(__ushort_as_half((unsigned short)(dm >> 16)));
+    return __int_as_float(p0.x) * (d * planes_f(u[0], u[1], u[2]) + m * planes_f(p0.y, p0.z, p0.w));
+  }
+  const int off = FMT == GQ_Q40 ? 8 : 16;
+  return __int_as_float(p0.x) * (d * planes_f(u[0] - off * p0.y, u[1] - off * p0.z, u[2] - off * p0.w));
+}
+// the 8 chunk words {d, m} of a legacy superblock from its header (Q4_0 / Q5_0: 8 x f16 d in hd; Q4_1 / Q5_1: 8 x {d, m} in hd, hd2)
+template <int FMT>
+__device__ __forceinline__ void legacy_dm(const uint4& hd, const uint4& hd2, unsigned (&dm)[8]) {
+  const unsigned a[8] = {hd.x, hd.y, hd.z, hd.w, hd2.x, hd2.y, hd2.z, hd2.w};
+#pragma unroll
+  for (int c = 0; c < 8; c++) dm[c] = gq_affine(FMT) ? a[c] : (a[c >> 1] >> (16 * (c & 1)));
+}
+
 #define GQ_E 8   // slice elements per thread (KR <= 2048)
 
 template <int FMT, int MODE, int FIX, int MAXJ>
@@ -1020,8 +1061,8 @@ __global__ __launch_bounds__(256) void k_gemv_gq(const uint4* __restrict__ Wq, c
   const int sb0 = ks * SBW;
   uint4 q[16];          // Q8_0: 16 x 16 B (256 int8) ; Q4_K / Q6_K: 8 x 16 B nibbles
   uint2 qh[8];          // Q6_K highs
-  uint4 q5h[2];         // Q5_K 5th bits (8 chunk words)
-  uint4 hd = make_uint4(0, 0, 0, 0);
+  uint4 q5h[2];         // Q5_K / Q5_0 / Q5_1 5th bits (8 chunk words)
+  uint4 hd = make_uint4(0, 0, 0, 0), hd2 = make_uint4(0, 0, 0, 0);   // hd2: second half of a Q4_1 / Q5_1 header
   __half dv[8];         // Q8_0: the 8 block scales of the superblock ; Q6_K: dv[0] = d
   auto load_sb = [&](int sb) {
     if (FMT == GQ_Q80) {
@@ -1034,14 +1075,19 @@ __global__ __launch_bounds__(256) void k_gemv_gq(const uint4* __restrict__ Wq, c
       const uint4* p = Wq + ((size_t)ntc * C32 + (size_t)sb * 8) * 64 + lane;
 #pragma unroll
       for (int i = 0; i < 8; i++) q[i] = ldnt(p + i * 64);
-      hd = Hd[((size_t)ntc * SB + sb) * 64 + lane];
+      if (gq_affine(FMT)) {
+        const uint4* ph = Hd + (((size_t)ntc * SB + sb) * 64 + lane) * 2;
+        hd = ph[0]; hd2 = ph[1];
+      } else {
+        hd = Hd[((size_t)ntc * SB + sb) * 64 + lane];
+      }
       if (FMT == GQ_Q6K) {
         const uint2* ph = Wh + ((size_t)ntc * C32 + (size_t)sb * 8) * 64 + lane;
 #pragma unroll
         for (int i = 0; i < 8; i++) qh[i] = ph[i * 64];
         dv[0] = Dd[((size_t)ntc * SB + sb) * 64 + lane];
       }
-      if (FMT == GQ_Q5K) {
+      if (FMT == GQ_Q5K || gq_has5(FMT)) {
         const uint4* ph = (const uint4*)Wh + ((size_t)ntc * SB + sb) * 128 + lane * 2;
         q5h[0] = ldnt(ph); q5h[1] = ldnt(ph + 1);
       }
@@ -1115,6 +1161,12 @@ __global__ __launch_bounds__(256) void k_gemv_gq(const uint4* __restrict__ Wq, c
         q5k_words(q[c], hb[c], w);
         y += q5k_chunk(w, xh4, xm4, xl4, s * 8 + c, cpar, hw, c, d, dmin);
       }
+    } else if (gq_legacy(FMT)) {
+      const unsigned hb[8] = {q5h[0].x, q5h[0].y, q5h[0].z, q5h[0].w, q5h[1].x, q5h[1].y, q5h[1].z, q5h[1].w};
+      unsigned dm[8];
+      legacy_dm<FMT>(hd, hd2, dm);
+#pragma unroll
+      for (int c = 0; c < 8; c++) y += legacy_chunk<FMT>(q[c], gq_has5(FMT) ? hb[c] : 0u, dm[c], xh4, xm4, xl4, s * 8 + c, cpar);
     } else {  // Q6_K
       const unsigned sw[4] = {hd.x, hd.y, hd.z, hd.w};   // 16 int8 scales
       const float d = __half2float(dv[0]);
@@ -1163,7 +1215,7 @@ __global__ __launch_bounds__(256) void k_gemv_gq(const uint4* __restrict__ Wq, c
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Slim form of the GGUF block-quant GEMV (Q4_K / Q6_K): the structure of k_gemv_q4g_slim -- 8 waves share ONE 256-k slice, which here is
+// Slim form of the GGUF block-quant GEMV (Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1 / Q5_0 / Q5_1): the structure of k_gemv_q4g_slim -- 8 waves share ONE 256-k slice, which here is
 // exactly one superblock, each wave owns one 64-column tile (its 8 KiB of nibbles + header in flight before the prologue) -- with the
 // per-32-k-chunk activation planes and the block arithmetic of k_gemv_gq.  The generic kernel holds > 256 registers per lane (one
 // workgroup of 4 waves per CU) and runs q/k/v in two rounds: 18.2 us against 7.0 us for the same bytes in AWQ form.
@@ -1223,12 +1275,17 @@ __global__ __launch_bounds__(512) void k_gemv_gq_slim(const uint4* __restrict__ 
   }
   __builtin_amdgcn_sched_barrier(0);
   // (2) this wave's superblock: 8 x 16 B of nibbles (+ Q6_K: 8 x 8 B of high bits), header, all in flight now
-  uint4 q[8]; uint2 qh[8]; uint4 q5h[2]; uint4 hd; __half dsb = __float2half(0.f);
+  uint4 q[8]; uint2 qh[8]; uint4 q5h[2]; uint4 hd, hd2 = make_uint4(0, 0, 0, 0); __half dsb = __float2half(0.f);
   {
     const uint4* p = Wq_ + ((size_t)tqc * C32 + (size_t)ksl * 8) * 64 + lane;
 #pragma unroll
     for (int i = 0; i < 8; i++) q[i] = ldnt(p + i * 64);
-    hd = Hd_[((size_t)tqc * SB + ksl) * 64 + lane];
+    if (gq_affine(FMT)) {
+      const uint4* ph = Hd_ + (((size_t)tqc * SB + ksl) * 64 + lane) * 2;
+      hd = ph[0]; hd2 = ph[1];
+    } else {
+      hd = Hd_[((size_t)tqc * SB + ksl) * 64 + lane];
+    }
     if (FMT == GQ_Q6K || FMT == GQ_MIX) {
       const int t6 = is6 ? tqc : 0;              // (MIX, Q4_K wave: harmless loads of tile 0)
       const uint2* ph = Wh_ + ((size_t)t6 * C32 + (size_t)ksl * 8) * 64 + lane;
@@ -1236,7 +1293,7 @@ __global__ __launch_bounds__(512) void k_gemv_gq_slim(const uint4* __restrict__ 
       for (int i = 0; i < 8; i++) qh[i] = ph[i * 64];
       dsb = Dd_[((size_t)t6 * SB + ksl) * 64 + lane];
     }
-    if (FMT == GQ_Q5K) {
+    if (FMT == GQ_Q5K || gq_has5(FMT)) {
       const uint4* ph = (const uint4*)Wh_ + ((size_t)tqc * SB + ksl) * 128 + lane * 2;
       q5h[0] = ldnt(ph); q5h[1] = ldnt(ph + 1);
     }
@@ -1277,7 +1334,13 @@ __global__ __launch_bounds__(512) void k_gemv_gq_slim(const uint4* __restrict__ 
   const uint4* xm4 = (const uint4*)xm;
   const uint4* xl4 = (const uint4*)xl;
   float y = 0.f;
-  if (FMT == GQ_Q5K) {
+  if (gq_legacy(FMT)) {
+    const unsigned hb[8] = {q5h[0].x, q5h[0].y, q5h[0].z, q5h[0].w, q5h[1].x, q5h[1].y, q5h[1].z, q5h[1].w};
+    unsigned dm[8];
+    legacy_dm<FMT>(hd, hd2, dm);
+#pragma unroll
+    for (int c = 0; c < 8; c++) y += legacy_chunk<FMT>(q[c], gq_has5(FMT) ? hb[c] : 0u, dm[c], xh4, xm4, xl4, c, cpar);
+  } else if (FMT == GQ_Q5K) {
     const unsigned hw[4] = {hd.x, hd.y, hd.z, hd.w};
     const unsigned hb[8] = {q5h[0].x, q5h[0].y, q5h[0].z, q5h[0].w, q5h[1].x, q5h[1].y, q5h[1].z, q5h[1].w};
     const float d = __half2float(__ushort_as_half((unsigned short)(hw[0] & 0xffffu)));
@@ -1600,7 +1663,8 @@ int bzk_mlp_gq(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, i
 
 bool bzk_gq_slim_ok(const LinearDev& L, const Pro& pro) {
   static const bool off = getenv("BZ_NO_GQ_SLIM") != nullptr;
-  if (off || (L.kind != LK_Q4K && L.kind != LK_Q5K && L.kind != LK_Q6K) || pro.perm != nullptr || L.N % 64 || L.K % 256) return false;
+  const bool kind_ok = L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K || L.kind == LK_Q40 || L.kind == LK_Q41 || L.kind == LK_Q50 || L.kind == LK_Q51;
+  if (off || !kind_ok || pro.perm != nullptr || L.N % 64 || L.K % 256) return false;
   if (pro.mode == PRO_NORM) return L.K == pro.H && (L.K == 2048 || L.K == 4096 || L.K == 8192);
   if (pro.mode == PRO_SILU) return L.K == pro.H;
   return false;
@@ -2367,7 +2431,7 @@ static bool bzk_rows2_ok(const LinearDev& L, const Pro& pro, const GemvOut& out)
 }
 int bzk_gemv_rows_blocks(const LinearDev& L) { int r = rows_per_wg_for(L.N); return (L.N + r - 1) / r; }
 
-// ---- GGUF: load-time repack from raw row-major ggml blocks ([N][K/blk] blocks of 34 / 144 / 176 / 210 bytes; raw decoders in bz_ggml.h) -----------
+// ---- GGUF: load-time repack from raw row-major ggml blocks ([N][K/blk] blocks of 18 / 20 / 22 / 24 / 34 / 144 / 176 / 210 bytes; raw decoders in bz_ggml.h) ---
 
 __global__ void k_repack_gq(int fmt, const unsigned char* raw, int N, int K, uint32_t* wq, uint32_t* wh, uint32_t* hd, __half* dd) {
   const size_t gsz = (size_t)gridDim.x * blockDim.x, gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2389,6 +2453,54 @@ __global__ void k_repack_gq(int fmt, const unsigned char* raw, int N, int K, uin
       const int b = (int)(t % (size_t)(K >> 5)), nt = (int)(t / (size_t)(K >> 5));
       const unsigned char* p = raw + (size_t)(nt * 64 + lane) * rb + (size_t)b * 34;
       dd[idx] = __ushort_as_half((unsigned short)(p[0] | (p[1] << 8)));
+    }
+    return;
+  }
+  if (gq_legacy(fmt)) {
+    const int type = fmt == GQ_Q40 ? BZ_GGML_Q4_0 : fmt == GQ_Q41 ? BZ_GGML_Q4_1 : fmt == GQ_Q50 ? BZ_GGML_Q5_0 : BZ_GGML_Q5_1;
+    const size_t bsz = ggml_blk_row_bytes(type, 32), rb = (size_t)(K >> 5) * bsz;
+    auto qv = [&](const unsigned char* blk, int j) -> unsigned {   // the 4- / 5-bit value of weight j of a raw block
+      return fmt == GQ_Q40 ? q4_0_raw(blk, j) : fmt == GQ_Q41 ? q4_1_raw(blk, j) : fmt == GQ_Q50 ? q5_0_raw(blk, j) : q5_1_raw(blk, j);
+    };
+    const size_t total = (size_t)N * (K >> 3);                 // nibble words (8 weights each), chunk kc = ggml block kc
+    for (size_t idx = gid; idx < total; idx += gsz) {
+      const int j = idx & 3, lane = (idx >> 2) & 63;
+      const size_t t = idx >> 8;
+      const int kc = (int)(t % (size_t)(K >> 5)), nt = (int)(t / (size_t)(K >> 5));
+      const unsigned char* blk = raw + (size_t)(nt * 64 + lane) * rb + (size_t)kc * bsz;
+      unsigned word = 0;
+#pragma unroll
+      for (int bb = 0; bb < 4; bb++) word |= ((qv(blk, j * 8 + bb) & 15u) | ((qv(blk, j * 8 + 4 + bb) & 15u) << 4)) << (8 * bb);
+      wq[idx] = word;
+    }
+    if (gq_has5(fmt)) {                                        // Q5_K's 5th-bit plane
+      const size_t th = (size_t)N * (K >> 5);
+      for (size_t idx = gid; idx < th; idx += gsz) {
+        const int c = idx & 7, lane = (idx >> 3) & 63;
+        const size_t t = idx >> 9;
+        const int sb = (int)(t % (size_t)(K >> 8)), nt = (int)(t / (size_t)(K >> 8));
+        const unsigned char* blk = raw + (size_t)(nt * 64 + lane) * rb + (size_t)(sb * 8 + c) * bsz;
+        unsigned word = 0;
+        for (int r = 0; r < 32; r++) word |= (qv(blk, r) >> 4) << (8 * (r & 3) + (r >> 2));
+        wh[idx] = word;
+      }
+    }
+    // header: one 32-bit word per chunk {d, m} (Q4_1 / Q5_1: the block's first 4 bytes) or per chunk pair {d_2i, d_2i+1} (Q4_0 / Q5_0)
+    const int wpl = gq_affine(fmt) ? 8 : 4;                    // header words per (superblock, lane)
+    const size_t nh = (size_t)N * (K >> 8) * wpl;
+    for (size_t idx = gid; idx < nh; idx += gsz) {
+      const int wi = (int)(idx % wpl), lane = (int)((idx / wpl) & 63);
+      const size_t t = idx / wpl >> 6;
+      const int sb = (int)(t % (size_t)(K >> 8)), nt = (int)(t / (size_t)(K >> 8));
+      const unsigned char* row = raw + (size_t)(nt * 64 + lane) * rb;
+      if (gq_affine(fmt)) {
+        const unsigned char* b = row + (size_t)(sb * 8 + wi) * bsz;
+        hd[idx] = (unsigned)b[0] | ((unsigned)b[1] << 8) | ((unsigned)b[2] << 16) | ((unsigned)b[3] << 24);
+      } else {
+        const unsigned char* b0 = row + (size_t)(sb * 8 + 2 * wi) * bsz;
+        const unsigned char* b1 = b0 + bsz;
+        hd[idx] = (unsigned)b0[0] | ((unsigned)b0[1] << 8) | ((unsigned)b1[0] << 16) | ((unsigned)b1[1] << 24);
+      }
     }
     return;
   }
@@ -2459,7 +2571,10 @@ __global__ void k_repack_gq(int fmt, const unsigned char* raw, int N, int K, uin
     if (fmt == GQ_Q6K && wi == 0) dd[((size_t)nt * (K >> 8) + sb) * 64 + lane] = __ushort_as_half((unsigned short)(blk[208] | (blk[209] << 8)));
   }
 }
-static int gq_fmt_of(int kind) { return kind == LK_Q80 ? GQ_Q80 : kind == LK_Q4K ? GQ_Q4K : kind == LK_Q5K ? GQ_Q5K : GQ_Q6K; }
+static int gq_fmt_of(int kind) {
+  return kind == LK_Q80 ? GQ_Q80 : kind == LK_Q4K ? GQ_Q4K : kind == LK_Q5K ? GQ_Q5K : kind == LK_Q40 ? GQ_Q40 : kind == LK_Q41 ? GQ_Q41 : kind == LK_Q50 ? GQ_Q50
+       : kind == LK_Q51 ? GQ_Q51 : GQ_Q6K;
+}
 int bzk_repack_gq(hipStream_t s, int kind, const void* raw, int N, int K, void* wq, void* wh, void* hd, void* dd) {
   const int fmt = gq_fmt_of(kind);
   hipLaunchKernelGGL(k_repack_gq, dim3(2048), dim3(256), 0, s, fmt, (const unsigned char*)raw, N, K, (uint32_t*)wq, (uint32_t*)wh, (uint32_t*)hd, (__half*)dd);
@@ -2478,6 +2593,16 @@ __device__ __forceinline__ float gq_elem(int fmt, const uint32_t* wq, const uint
   const int kc = k >> 5, r = k & 31, j = r >> 3, rr = r & 7;
   const unsigned word = wq[(((size_t)nt * (K >> 5) + kc) * 64 + lane) * 4 + j];
   const unsigned byte = (word >> (8 * (rr & 3))) & 255u;
+  if (gq_legacy(fmt)) {   // ggml's order, uncontracted: (q - 8 | 16) d ; q d + m
+    const size_t sl = ((size_t)nt * (K >> 8) + (k >> 8)) * 64 + lane;   // (superblock, lane)
+    const int c = kc & 7;
+    unsigned q = rr < 4 ? (byte & 15u) : (byte >> 4);
+    if (gq_has5(fmt)) q |= ((wh[sl * 8 + c] >> (8 * (r & 3) + (r >> 2))) & 1u) << 4;
+    const unsigned dm = gq_affine(fmt) ? hd[sl * 8 + c] : (hd[sl * 4 + (c >> 1)] >> (16 * (c & 1)));
+    const float d = __half2float(__ushort_as_half((unsigned short)(dm & 0xffffu)));
+    if (gq_affine(fmt)) return __fadd_rn(__fmul_rn((float)q, d), __half2float(__ushort_as_half((unsigned short)(dm >> 16))));
+    return __fmul_rn((float)((int)q - (fmt == GQ_Q40 ? 8 : 16)), d);
+  }
   const size_t hi = (((size_t)nt * (K >> 8) + (k >> 8)) * 64 + lane) * 4;
   const unsigned hw[4] = {hd[hi], hd[hi + 1], hd[hi + 2], hd[hi + 3]};
   if (fmt == GQ_Q4K) {
@@ -2553,7 +2678,10 @@ __global__ __launch_bounds__(256) void k_gq_split3(int fmt, const uint32_t* wq, 
     *(uint4*)(o + 2 * K) = make_uint4(c[0] | ((unsigned)c[1] << 16), c[2] | ((unsigned)c[3] << 16), c[4] | ((unsigned)c[5] << 16), c[6] | ((unsigned)c[7] << 16));
   }
 }
-bool bzk_gq_split_ok(const LinearDev& L) { return (L.kind == LK_Q80 || L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K) && L.K % 64 == 0 && L.N % 64 == 0; }
+bool bzk_gq_split_ok(const LinearDev& L) {
+  return (L.kind == LK_Q80 || L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K || L.kind == LK_Q40 || L.kind == LK_Q41 || L.kind == LK_Q50 ||
+          L.kind == LK_Q51) && L.K % 64 == 0 && L.N % 64 == 0;
+}
 // amax: device word holding the running maximum of the fused linear's parts (zeroed by the caller before the first part)
 int bzk_gq_absmax(hipStream_t s, const LinearDev& L, unsigned* amax) {
   hipLaunchKernelGGL(k_gq_absmax, dim3(2048), dim3(256), 0, s, gq_fmt(L), (const uint32_t*)L.w, (const uint32_t*)L.zeros, (const uint32_t*)L.hdr, (const __half*)L.scales, L.N, L.K, amax);
@@ -2655,23 +2783,26 @@ int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& o
     BZ_HIP(hipGetLastError());
     return BZ_OK;
   }
-  if ((L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K) && bzk_gq_slim_ok(L, pro)) {
+  if (bzk_gq_slim_ok(L, pro)) {
     if (!out.acc) BZ_FAIL(BZ_E_INVALID, "block-quant gemv needs a fixed-point accumulator");
     const int nsb = L.K / 256, ntg = (L.N / 64 + 7) / 8;
-    const char* label = L.kind == LK_Q4K ? "gemv_q4_K<slim>" : (L.kind == LK_Q5K ? "gemv_q5_K<slim>" : "gemv_q6_K<slim>");
+    const char* label = L.kind == LK_Q4K ? "gemv_q4_K<slim>" : L.kind == LK_Q5K ? "gemv_q5_K<slim>" : L.kind == LK_Q6K ? "gemv_q6_K<slim>"
+                      : L.kind == LK_Q40 ? "gemv_q4_0<slim>" : L.kind == LK_Q41 ? "gemv_q4_1<slim>" : L.kind == LK_Q50 ? "gemv_q5_0<slim>" : "gemv_q5_1<slim>";
 #define LAUNCH_GQS(FMT, MODE, FIX, NJ) BZ_LAUNCH(label, L.algo_bytes, (k_gemv_gq_slim<FMT, MODE, FIX, NJ>), dim3(nsb * ntg), dim3(512), 0, s, (const uint4*)L.w, \
     (const uint2*)L.zeros, (const uint4*)L.hdr, (const __half*)L.scales, L.bias, L.N, L.K, pro, out.acc, out.zero_buf, out.zero_n, GqMix{})
 #define LAUNCH_GQS_NJ(FMT, FIX) do { if (pro.mode == PRO_SILU) LAUNCH_GQS(FMT, PRO_SILU, FIX, 1); else if (L.K == 2048) LAUNCH_GQS(FMT, PRO_NORM, FIX, 1); \
     else if (L.K == 4096) LAUNCH_GQS(FMT, PRO_NORM, FIX, 2); else LAUNCH_GQS(FMT, PRO_NORM, FIX, 4); } while (0)
 #define LAUNCH_GQS_F(FMT) do { if (pro.src.fix) LAUNCH_GQS_NJ(FMT, 1); else LAUNCH_GQS_NJ(FMT, 0); } while (0)
-    if (L.kind == LK_Q4K) LAUNCH_GQS_F(GQ_Q4K); else if (L.kind == LK_Q5K) LAUNCH_GQS_F(GQ_Q5K); else LAUNCH_GQS_F(GQ_Q6K);
+    if (L.kind == LK_Q4K) LAUNCH_GQS_F(GQ_Q4K); else if (L.kind == LK_Q5K) LAUNCH_GQS_F(GQ_Q5K); else if (L.kind == LK_Q6K) LAUNCH_GQS_F(GQ_Q6K);
+    else if (L.kind == LK_Q40) LAUNCH_GQS_F(GQ_Q40); else if (L.kind == LK_Q41) LAUNCH_GQS_F(GQ_Q41); else if (L.kind == LK_Q50) LAUNCH_GQS_F(GQ_Q50);
+    else LAUNCH_GQS_F(GQ_Q51);
 #undef LAUNCH_GQS_F
 #undef LAUNCH_GQS_NJ
 #undef LAUNCH_GQS
     BZ_HIP(hipGetLastError());
     return BZ_OK;
   }
-  if (L.kind == LK_Q80 || L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K) {
+  if (L.kind == LK_Q80 || L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K || L.kind == LK_Q40 || L.kind == LK_Q41 || L.kind == LK_Q50 || L.kind == LK_Q51) {
     if (!out.acc) BZ_FAIL(BZ_E_INVALID, "block-quant gemv needs a fixed-point accumulator");
     const int SB = L.K / 256, SBW = L.gw;
     if (SBW <= 0 || SB % SBW || SBW > 8) BZ_FAIL(BZ_E_INVALID, "block-quant gemv: bad k-slice %d of %d superblocks", SBW, SB);
@@ -2679,7 +2810,8 @@ int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& o
     const int grid = nst * (SB / SBW);
     const size_t smem = gq_smem(SBW);
     const int maxj = pro.mode == PRO_NORM ? (pro.H + 1023) / 1024 : 1;
-    const char* label = L.kind == LK_Q80 ? "gemv_q8_0" : L.kind == LK_Q4K ? "gemv_q4_K" : L.kind == LK_Q5K ? "gemv_q5_K" : "gemv_q6_K";
+    const char* label = L.kind == LK_Q80 ? "gemv_q8_0" : L.kind == LK_Q4K ? "gemv_q4_K" : L.kind == LK_Q5K ? "gemv_q5_K" : L.kind == LK_Q6K ? "gemv_q6_K"
+                      : L.kind == LK_Q40 ? "gemv_q4_0" : L.kind == LK_Q41 ? "gemv_q4_1" : L.kind == LK_Q50 ? "gemv_q5_0" : "gemv_q5_1";
 #define LAUNCH_GQ(FMT, MODE, FIX, MJ) BZ_LAUNCH(label, L.algo_bytes, (k_gemv_gq<FMT, MODE, FIX, MJ>), dim3(grid), dim3(256), smem, s, (const uint4*)L.w, \
     (const uint2*)L.zeros, (const uint4*)L.hdr, (const __half*)L.scales, L.bias, L.N, L.K, SBW, nst, pro, out.acc, out.zero_buf, out.zero_n)
 #define LAUNCH_GQ_F(FMT, MODE, MJ) do { if (pro.src.fix) LAUNCH_GQ(FMT, MODE, 1, MJ); else LAUNCH_GQ(FMT, MODE, 0, MJ); } while (0)
@@ -2687,7 +2819,8 @@ int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& o
     else if (maxj <= 1) LAUNCH_GQ_F(FMT, PRO_NORM, 1); else if (maxj <= 2) LAUNCH_GQ_F(FMT, PRO_NORM, 2); else if (maxj <= 4) LAUNCH_GQ_F(FMT, PRO_NORM, 4); \
     else if (maxj <= 8) LAUNCH_GQ_F(FMT, PRO_NORM, 8); else BZ_FAIL(BZ_E_UNSUPPORTED, "hidden size %d too large for the fused norm prologue", pro.H); } while (0)
     if (L.kind == LK_Q80) LAUNCH_GQ_M(GQ_Q80); else if (L.kind == LK_Q4K) LAUNCH_GQ_M(GQ_Q4K); else if (L.kind == LK_Q5K) LAUNCH_GQ_M(GQ_Q5K);
-    else LAUNCH_GQ_M(GQ_Q6K);
+    else if (L.kind == LK_Q6K) LAUNCH_GQ_M(GQ_Q6K); else if (L.kind == LK_Q40) LAUNCH_GQ_M(GQ_Q40); else if (L.kind == LK_Q41) LAUNCH_GQ_M(GQ_Q41);
+    else if (L.kind == LK_Q50) LAUNCH_GQ_M(GQ_Q50); else LAUNCH_GQ_M(GQ_Q51);
 #undef LAUNCH_GQ_M
 #undef LAUNCH_GQ_F
 #undef LAUNCH_GQ
@@ -2855,7 +2988,7 @@ __global__ void k_embed(const void* table, int tdt, int gg, const long long* tok
 int bzk_embed(hipStream_t s, const void* table, int tdt, int gg, const long long* tok, int H, int act, float* h, const int* pos, const float* cos_t,
               const float* sin_t, int half, float* rope_cur) {
   if (rope_cur != nullptr && (2 * half > 256 || !pos || !cos_t || !sin_t)) BZ_FAIL(BZ_E_INVALID, "embed: bad RoPE staging arguments");
-  if (gg != 0 && (ggml_blk_row_bytes(gg, H) == 0 || H % (gg == BZ_GGML_Q8_0 ? 32 : 256))) BZ_FAIL(BZ_E_INVALID, "embed: ggml type %d rows of %d", gg, H);
+  if (gg != 0 && (ggml_blk_row_bytes(gg, H) == 0 || H % ggml_blk_k(gg))) BZ_FAIL(BZ_E_INVALID, "embed: ggml type %d rows of %d", gg, H);
   const double bytes = gg != 0 ? (double)ggml_blk_row_bytes(gg, H) : (double)H * (tdt == BZ_F32 ? 4 : 2);
   BZ_LAUNCH("embed", bytes, k_embed, dim3((H + 255) / 256), dim3(256), 0, s, table, tdt, gg, tok, H, act, h, pos, cos_t, sin_t,
             half, rope_cur);

@@ -687,7 +687,8 @@ std::string gguf_to_hf_name_mamba2(const std::string& n) {
 }
 
 size_t ggml_row_bytes(int type, int64_t K) {
-  switch (type) { case 0: return (size_t)K * 4; case 1: case 30: return (size_t)K * 2; case 8: return (size_t)(K / 32) * 34; case 12: return (size_t)(K / 256) * 144;
+  switch (type) { case 0: return (size_t)K * 4; case 1: case 30: return (size_t)K * 2; case 2: return (size_t)(K / 32) * 18;
+                  case 3: return (size_t)(K / 32) * 20; case 6: return (size_t)(K / 32) * 22; case 7: return (size_t)(K / 32) * 24; case 8: return (size_t)(K / 32) * 34; case 12: return (size_t)(K / 256) * 144;
                   case 13: return (size_t)(K / 256) * 176; case 14: return (size_t)(K / 256) * 210; default: return 0; }
 }
 
@@ -713,7 +714,7 @@ int load_gguf(bz_device* dev, const std::string& path, bz_model** out, bz_model_
     if (t.ne.empty() || t.ne.size() > 2) { rc = BZ_E_UNSUPPORTED; bz_set_error("GGUF tensor '%s': rank %zu", t.name.c_str(), t.ne.size()); break; }
     const int64_t K = t.ne[0], N = t.ne.size() == 2 ? t.ne[1] : 1;      // ne[0] is the contiguous dimension
     const size_t rb = ggml_row_bytes(t.type, K);
-    if (!rb) { rc = BZ_E_UNSUPPORTED; bz_set_error("GGUF tensor '%s': ggml type %d is not implemented (F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K)", t.name.c_str(), t.type); break; }
+    if (!rb) { rc = BZ_E_UNSUPPORTED; bz_set_error("GGUF tensor '%s': ggml type %d is not implemented (F32, F16, BF16, Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q4_K, Q5_K, Q6_K)", t.name.c_str(), t.type); break; }
     {   // checked: offset / extents are file-controlled 64-bit values
       const size_t room = g.file.n - g.data_off;
       size_t need = 0;

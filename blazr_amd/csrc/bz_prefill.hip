@@ -1367,7 +1367,7 @@ int bzk_pf_cvt16(hipStream_t s, int dt, const float* x, size_t n, void* y) {
   return BZ_OK;
 }
 int bzk_pf_embed(hipStream_t s, const void* table, int tdt, int gg, const long long* tok, int S, int H, int act, float* out) {
-  if (gg != 0 && (ggml_blk_row_bytes(gg, H) == 0 || H % (gg == BZ_GGML_Q8_0 ? 32 : 256))) BZ_FAIL(BZ_E_INVALID, "pf_embed: ggml type %d rows of %d", gg, H);
+  if (gg != 0 && (ggml_blk_row_bytes(gg, H) == 0 || H % ggml_blk_k(gg))) BZ_FAIL(BZ_E_INVALID, "pf_embed: ggml type %d rows of %d", gg, H);
   hipLaunchKernelGGL(k_pf_embed, dim3(S), dim3(256), 0, s, table, tdt, gg, tok, S, H, act, out);
   BZ_HIP(hipGetLastError());
   return BZ_OK;

@@ -43,7 +43,7 @@ enum {
 enum { BZ_F32 = 0, BZ_F16 = 1, BZ_BF16 = 2, BZ_I64 = 3, BZ_I32 = 4, BZ_U32 = 5, BZ_U8 = 6 };
 
 /* ggml type ids accepted by bz_model_add_gguf (format::Gguf tensor_info().ggml_type, loader/gguf.rs:33) */
-enum { BZ_GGML_F32 = 0, BZ_GGML_F16 = 1, BZ_GGML_Q8_0 = 8, BZ_GGML_Q4_K = 12, BZ_GGML_Q5_K = 13, BZ_GGML_Q6_K = 14, BZ_GGML_BF16 = 30 };
+enum { BZ_GGML_F32 = 0, BZ_GGML_F16 = 1, BZ_GGML_Q4_0 = 2, BZ_GGML_Q4_1 = 3, BZ_GGML_Q5_0 = 6, BZ_GGML_Q5_1 = 7, BZ_GGML_Q8_0 = 8, BZ_GGML_Q4_K = 12, BZ_GGML_Q5_K = 13, BZ_GGML_Q6_K = 14, BZ_GGML_BF16 = 30 };
 
 enum { BZ_ARCH_LLAMA = 0, BZ_ARCH_MAMBA2 = 1, BZ_ARCH_DEEPSEEK2 = 2 };
 enum { BZ_ROPE_NONE = 0, BZ_ROPE_LINEAR = 1, BZ_ROPE_LLAMA3 = 2, BZ_ROPE_YARN = 3 };
