@@ -2052,6 +2052,8 @@ __global__ void k_acc_rows(float* acc, const float* y, size_t n, int first) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) acc[i] = first ? y[i] : acc[i] + y[i];
 }
 static int dsv2_prefill(bz_model* m, const long long* d_tok, int S, const KvView& view, int pos0, bool all, bz_tensor* logits_out) {
+  // (a chunk whose batched rows round to the decode step's bits is told apart by this line: test_gpu_dsv2_prefill.py, "no-shared")
+  BZ_TRACE("dsv2_prefill: S=%d position=%d", S, pos0);
   const bz_model_config& c = m->cfg;
   hipStream_t st = m->dev->stream;
   const int H = c.hidden, NH = c.n_heads, R = c.mla_kv_lora_rank, DN = c.mla_nope_dim, DR = c.mla_rope_dim, DV = c.mla_v_dim, act = c.act_dtype, dt = c.act_dtype;

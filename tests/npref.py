@@ -372,6 +372,12 @@ class NpDsv2:
                 w.update({k: dq(lay[k]) for k in ("gate", "up", "down")})
             self.W.append(w)
         self.lat = [[] for _ in model["layers"]]
+        self.gaps = []        # per step: the routing gap of every MoE layer (routing_gaps)
+
+    def routing_gaps(self):
+        """[steps, MoE layers]: each step's gap between the k-th and the (k+1)-th router probability, relative to the k-th (inf where every
+        expert is selected).  A row with a tiny gap may select another expert in an implementation whose router sums differ in the last bit."""
+        return np.array(self.gaps, dtype=np.float64).reshape(len(self.gaps), -1)
 
     def _rope(self, v, pos):
         c = self.cfg
@@ -396,6 +402,7 @@ class NpDsv2:
         silu = lambda a: a / (1.0 + np.exp(-a))
         mlp = lambda w, x: R(R(R(silu(R(x @ w["gate"].T))) * R(x @ w["up"].T)) @ w["down"].T)
         h = R(self.emb[token])
+        gaps = []
         for l, lay in enumerate(self.m["layers"]):
             w = self.W[l]
             xn = rms_norm_(h, lay["attn_norm"], c["rms_eps"], act)
@@ -420,6 +427,8 @@ class NpDsv2:
                 s = np.exp(lg - lg.max())
                 s = s / s.sum()
                 sel = np.argsort(-s, kind="stable")[:c["top_k"]]
+                srt = np.sort(s)[::-1]
+                gaps.append(float((srt[c["top_k"] - 1] - srt[c["top_k"]]) / srt[c["top_k"] - 1]) if c["top_k"] < len(s) else np.inf)
                 wt = s[sel] / (s[sel].sum() + 1e-20) * c["routed_scale"] if c["norm_topk"] else s[sel] * c["routed_scale"]
                 routed = np.zeros_like(h)
                 for e, we in zip(sel, wt):
@@ -428,5 +437,6 @@ class NpDsv2:
                 if "shared" in w:
                     out = R(out + mlp(w["shared"], xn))
             h = R(h + out)
+        self.gaps.append(gaps)
         xn = rms_norm_(h, self.m["final_norm"], c["rms_eps"], act)
         return R(xn @ self.lm.T)

@@ -121,7 +121,8 @@ def test_paged_latent_cache_generation_equals_contiguous(pair, mode):
 
 
 def test_paged_latent_cache_forward_scattered_blocks(pair, device):
-    """prompt chunk (batched rows where the model has that path) + decode steps over a scattered block table == the contiguous cache, bit for bit"""
+    """a 13-token prompt (short enough for the decode step, BZ_EXACT_PREFILL_MAX) + decode steps over a scattered block table == the contiguous cache,
+    bit for bit.  The batched prompt path over a paged cache: test_gpu_dsv2_prefill.py::test_paged_batched_prompt_equals_contiguous"""
     model, lm, om = pair
     cfg = model["config"]
     W = cfg["kv_lora_rank"] + cfg["rope_dim"]
