@@ -11,10 +11,14 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W   prints ONE J
   * protocol of the reference's own bench (/root/reference/src/cli/bench.rs:30-33,142-146): warm-up, then `--reps` timed runs of exactly
     K steps each (every run bracketed by a barrier + device synchronise, MAX over ranks), the MEDIAN run is reported; all runs are listed.
   * --dump-outputs DIR: the last timed step's logits row and greedy id, DIR/logits.npy (float32) and DIR/next_token.npy (float64).
-Extra objects: "roofline" (dominant kernel, pure dispatch time from HIP events on the launch stream vs the 8 TB/s spec peak AND vs the read
-ceiling measured on this device in the same process), "cpu_baseline" (the CPU oracle -- a port, the reference's own --cpu path cannot be
-built here: BASELINE.md 4) and "parity" (GPU vs CPU oracle on the full model: free-running greedy ids, and the CPU ids teacher-forced
-through bz_forward_kv with per-step logit errors).
+  * a plain run does only that: load, prefill, probe the read ceiling (so that the timed steps start from the same device state whatever
+    the options), capture, warm up, time, dump, print.  Its "roofline" holds the whole step's fractions of the 8 TB/s spec peak and of the
+    measured read ceiling alone (tokens/s x algorithmic bytes per token: no run of their own).
+--full adds what takes runs of its own, after the timed region: "roofline" in full (dominant kernel,
+pure dispatch time from HIP events on the launch stream vs the 8 TB/s spec peak AND vs the read ceiling measured on this device in the same
+process) and "kernels", "cpu_baseline" (the CPU oracle -- a port, the reference's own --cpu path cannot be built here: BASELINE.md 4),
+"parity" (GPU vs CPU oracle on the full model: free-running greedy ids, and the CPU ids teacher-forced through bz_forward_kv with per-step
+logit errors), "prefill" (the prompt phase on its own) and "latency" (the reference bench's TTFT / ITL matrix).
 """
 import argparse
 import ctypes as C
@@ -120,6 +124,9 @@ def main():
     # the host's memory system, and oversubscribing the share only adds contention
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--dump-outputs", metavar="DIR")         # write the last timed step's outputs as DIR/<name>.npy (dump_outputs)
+    # also measure what the headline does not need (docstring): roofline and per-kernel figures, CPU baseline + parity, prompt phase, latency matrix;
+    # --no-cpu-baseline / --no-latency / --cpu-tokens / --cpu-threads apply to such a run
+    ap.add_argument("--full", action="store_true")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -145,7 +152,7 @@ def main():
         cfg["max_seq_len"] = need
     dev = runtime.Device(local_rank)
     t0 = time.time()
-    want_cpu = (rank == 0 and world == 1 and not args.no_cpu_baseline)
+    want_cpu = (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline)
     lm = runtime.LoadedModel(dev, cfg)
     host_layers = []
     for i in range(cfg["n_layers"]):
@@ -168,7 +175,8 @@ def main():
     logits = lm.forward_with_kv_cache(prompt, kv, 0)                       # prefill (untimed)
     prefill_row = logits.to_numpy().reshape(-1).copy()
     first = int(runtime.logits_to_token(dev, logits, [], []).to_numpy()[0])  # argmax_on_gpu (cuda_graphs.rs:149-163)
-    # the read ceiling of this device, measured in this process before the timed region (rotating 1 GiB buffers, no arithmetic)
+    # the read ceiling of this device, measured in this process before the timed region (rotating 1 GiB buffers, no arithmetic); a plain run
+    # keeps it too, so that the timed steps start from the same device state as in a --full run
     peak_meas = C.c_double()
     L.check(L.lib().bz_probe_hbm_read(dev.h, 1 << 30, 6, C.byref(peak_meas)))
     graph = runtime.DecodeGraph(lm, kv)
@@ -203,21 +211,25 @@ def main():
         dump_outputs(args.dump_outputs, graph, last)      # before profile_step below overwrites the model's logits row
     tokens = run_ids(graph, first, n_run, max(2, args.cpu_tokens) if want_cpu else 0)
 
-    # per-kernel dispatch times of real decode steps (pure kernel time, hipExtLaunchKernelGGL start/stop events)
     pos = args.prompt_len + args.warmup + args.steps
-    prof = lm.profile_step(kv, last, min(pos, cfg["max_seq_len"] - 5), iters=4)
-    for p in prof:
-        p["avg_us"] = 1e3 * p["total_ms"] / max(p["launches"], 1)
-        p["gbs"] = (p["algo_bytes"] / 1e9) / (p["total_ms"] / 1e3) if p["total_ms"] > 0 and p["algo_bytes"] > 0 else None
-    dom = max(prof, key=lambda p: p["total_ms"])
-    traffic, traffic_note = pmc_traffic(dom["name"])
     pm = float(peak_meas.value)
-    roof = {"bound": "hbm", "kernel": dom["name"], "achieved": round(dom["gbs"], 1) if dom["gbs"] else None, "peak": HBM_PEAK_GBS,
-            "unit": "GB/s", "frac": round(dom["gbs"] / HBM_PEAK_GBS, 4) if dom["gbs"] else None, "traffic": traffic, "traffic_note": traffic_note,
-            "peak_measured": round(pm, 1), "frac_of_measured": round(dom["gbs"] / pm, 4) if dom["gbs"] and pm > 0 else None,
-            "bytes_per_launch": dom["algo_bytes"] / max(dom["launches"], 1), "avg_launch_us": round(dom["avg_us"], 2),
-            "whole_step_frac": round(algo_bytes * (tok_s / n_gpus) / (HBM_PEAK_GBS * 1e9), 4),
-            "whole_step_frac_of_measured": round(algo_bytes * (tok_s / n_gpus) / (pm * 1e9), 4) if pm > 0 else None}
+    whole_step_frac = round(algo_bytes * (tok_s / n_gpus) / (HBM_PEAK_GBS * 1e9), 4)
+    whole_step_frac_of_measured = round(algo_bytes * (tok_s / n_gpus) / (pm * 1e9), 4) if pm > 0 else None
+    roof = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "peak_measured": round(pm, 1),
+            "whole_step_frac": whole_step_frac, "whole_step_frac_of_measured": whole_step_frac_of_measured}
+    if args.full:
+        # per-kernel dispatch times of real decode steps (pure kernel time, hipExtLaunchKernelGGL start/stop events)
+        prof = lm.profile_step(kv, last, min(pos, cfg["max_seq_len"] - 5), iters=4)
+        for p in prof:
+            p["avg_us"] = 1e3 * p["total_ms"] / max(p["launches"], 1)
+            p["gbs"] = (p["algo_bytes"] / 1e9) / (p["total_ms"] / 1e3) if p["total_ms"] > 0 and p["algo_bytes"] > 0 else None
+        dom = max(prof, key=lambda p: p["total_ms"])
+        traffic, traffic_note = pmc_traffic(dom["name"])
+        roof = {"bound": "hbm", "kernel": dom["name"], "achieved": round(dom["gbs"], 1) if dom["gbs"] else None, "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": round(dom["gbs"] / HBM_PEAK_GBS, 4) if dom["gbs"] else None, "traffic": traffic, "traffic_note": traffic_note,
+                "peak_measured": round(pm, 1), "frac_of_measured": round(dom["gbs"] / pm, 4) if dom["gbs"] and pm > 0 else None,
+                "bytes_per_launch": dom["algo_bytes"] / max(dom["launches"], 1), "avg_launch_us": round(dom["avg_us"], 2),
+                "whole_step_frac": whole_step_frac, "whole_step_frac_of_measured": whole_step_frac_of_measured}
 
     out = {"metric": "decode tokens/sec, Llama-3-8B AWQ-INT4 seq=1 on MI355X (and HBM-roofline fraction)", "value": round(tok_s, 2),
            "unit": "tokens/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(wall_ms / args.steps, 5),
@@ -227,9 +239,10 @@ def main():
                       "resident_weight_bytes": resident, "context_at_end": pos},
            "runs": {"protocol": "%d warm-up steps + %d timed steps per run, %d runs, median reported (cli/bench.rs:30-33,142-146)" % (args.warmup, args.steps, len(runs)),
                     "tokens_per_s": [round(r[0], 2) for r in runs], "ms": [round(r[1], 3) for r in runs]},
-           "roofline": roof,
-           "kernels": [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in p.items()} for p in prof],
-           "gpu_ms_events": round(gpu_ms, 3), "host_ms": round(host_ms, 3), "load_s": round(load_s, 1)}
+           "roofline": roof}
+    if args.full:
+        out["kernels"] = [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in p.items()} for p in prof]
+    out.update({"gpu_ms_events": round(gpu_ms, 3), "host_ms": round(host_ms, 3), "load_s": round(load_s, 1)})
 
     if want_cpu:
         # CPU baseline: the oracle (a port -- BASELINE.md 4), same weights, same prompt, bounded sample; and the parity gate
@@ -295,7 +308,7 @@ def main():
 
     # the prompt phase on its own (outside the timed decode region): a 512-token prompt through the batched prefill (matrix-core GEMMs + flash attention),
     # 1 warm-up + 2 timed passes, best of the two; 2 FLOP per linear weight per token against the dense 16-bit MFMA peak
-    if cfg["act_dtype"] in ("f16", "bf16") and cfg["max_seq_len"] >= 520:
+    if args.full and cfg["act_dtype"] in ("f16", "bf16") and cfg["max_seq_len"] >= 520:
         pf_len = 512
         kv2 = runtime.LayeredKvCache(dev, cfg["n_layers"], 1, cfg["n_kv_heads"], pf_len + 8, cfg["max_seq_len"], cfg["head_dim"], kv_dt)
         p2 = synth.prompt_tokens(pf_len, cfg["vocab"], seed=11)
@@ -316,7 +329,7 @@ def main():
     # the reference bench's own report (cli/bench.rs:24-33,142-160): prompt lengths 32 / 128 / 512, 1 warm-up + 3 measured generations of `--steps` tokens
     # each through the whole generate loop (prefill, first token, graph capture, one replay per token, event-synchronised token reads); TTFT / total: median
     # over the runs, inter-token latency: percentiles over all gaps of all runs, decode tok/s = (tokens - 1) / (total - TTFT), median.  Not part of `value`.
-    if rank == 0 and not args.no_latency:
+    if args.full and rank == 0 and not args.no_latency:
         out["latency"] = latency_matrix(runtime, synth, lm, cfg, max(args.steps, 16))
     if rank == 0:
         print(json.dumps(out))
@@ -365,7 +378,9 @@ def bench_aux(args, rank, local_rank, world, dist):
     prompt = synth.prompt_tokens(args.prompt_len, cfg["vocab"])
     ptimer = hip_events(C.c_void_p(dev.stream()))
     pf_ms = []
-    for rep_i in range(3):          # prompt prefill, timed on its own (BASELINE.json configs[4]: "prefill 512 (MFMA) + decode 128"); first pass = warm-up
+    # prompt prefill; --full times it on its own (BASELINE.json configs[4]: "prefill 512 (MFMA) + decode 128"): 3 passes, first pass = warm-up.
+    # The decode starts from the state of the last pass either way
+    for rep_i in range(3 if args.full else 1):
         if mamba:
             st = runtime.LayeredSsmState(lm)
         else:
@@ -375,7 +390,6 @@ def bench_aux(args, rank, local_rank, world, dist):
         logits = lm.forward_with_ssm_state(prompt, st) if mamba else lm.forward_with_kv_cache(prompt, st, 0)
         ptimer.stop()
         pf_ms.append(ptimer.ms())
-    prefill_ms = sorted(pf_ms[1:])[0]
     first = int(runtime.logits_to_token(dev, logits, [], []).to_numpy()[0])
     graph = runtime.DecodeGraph(lm, st)
     graph.seed_next_token(first, args.prompt_len)
@@ -403,30 +417,36 @@ def bench_aux(args, rank, local_rank, world, dist):
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, graph, last)
     tokens = run_ids(graph, first, n_run, 7)
-    prof = lm.profile_step_ssm(st, last, iters=4) if mamba else lm.profile_step(st, last, args.prompt_len + args.warmup + args.steps, iters=4)
-    for p in prof:
-        p["avg_us"] = 1e3 * p["total_ms"] / max(p["launches"], 1)
-        p["gbs"] = (p["algo_bytes"] / 1e9) / (p["total_ms"] / 1e3) if p["total_ms"] > 0 and p["algo_bytes"] > 0 else None
-    dom = max(prof, key=lambda p: p["total_ms"])
     algo = w_bytes + s_bytes
+    whole_step_frac = round(algo * (tok_s / n_gpus) / (HBM_PEAK_GBS * 1e9), 4)
+    roof = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "whole_step_frac": whole_step_frac}
+    if args.full:
+        prof = lm.profile_step_ssm(st, last, iters=4) if mamba else lm.profile_step(st, last, args.prompt_len + args.warmup + args.steps, iters=4)
+        for p in prof:
+            p["avg_us"] = 1e3 * p["total_ms"] / max(p["launches"], 1)
+            p["gbs"] = (p["algo_bytes"] / 1e9) / (p["total_ms"] / 1e3) if p["total_ms"] > 0 and p["algo_bytes"] > 0 else None
+        dom = max(prof, key=lambda p: p["total_ms"])
+        roof = {"bound": "hbm", "kernel": dom["name"], "achieved": round(dom["gbs"], 1) if dom["gbs"] else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(dom["gbs"] / HBM_PEAK_GBS, 4) if dom["gbs"] else None, "traffic": None, "whole_step_frac": whole_step_frac}
     out = {"metric": "decode tokens/sec, %s seq=1 on MI355X (and HBM-roofline fraction)" % args.preset, "value": round(tok_s, 2), "unit": "tokens/s",
            "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(wall_ms / args.steps, 5), "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": cfg["act_dtype"], "data": "synthetic",
            "config": {"workload": "%s greedy decode, batch 1, prompt %d, whole step as one hipGraph" % (args.preset, args.prompt_len),
                       "algorithmic_bytes_per_token": algo, "weight_bytes": w_bytes, "state_bytes_rw": s_bytes, "resident_weight_bytes": resident},
-           "roofline": {"bound": "hbm", "kernel": dom["name"], "achieved": round(dom["gbs"], 1) if dom["gbs"] else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(dom["gbs"] / HBM_PEAK_GBS, 4) if dom["gbs"] else None, "traffic": None,
-                        "whole_step_frac": round(algo * (tok_s / n_gpus) / (HBM_PEAK_GBS * 1e9), 4)},
-           "kernels": [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in p.items()} for p in prof],
-           "gpu_ms_events": round(gpu_ms, 3), "host_ms": round(host_ms, 3), "load_s": round(load_s, 1), "tokens_head": tokens[:8]}
-    # the prompt phase: 2 FLOP per active weight per token (embedding row and norms excluded), against the dense 16-bit MFMA peak
-    active_params = w_bytes / {"f16": 2, "bf16": 2, "f32": 4}[cfg["act_dtype"]]
-    pf_flops = 2.0 * active_params * args.prompt_len
-    out["prefill"] = {"tokens": args.prompt_len, "ms": round(prefill_ms, 3), "tokens_per_s": round(args.prompt_len / (prefill_ms / 1e3), 1),
-                      "tflops": round(pf_flops / (prefill_ms / 1e3) / 1e12, 2), "mfma_peak_tflops": 2500.0,
-                      "frac_of_mfma_peak": round(pf_flops / (prefill_ms / 1e3) / 2.5e15, 4), "runs_ms": [round(v, 3) for v in pf_ms],
-                      "note": "whole prompt phase (GEMMs on the matrix cores + attention / scan + routing), 2 x active weights x tokens FLOP"}
-    if mamba and rank == 0 and world == 1 and not args.no_cpu_baseline:
+           "roofline": roof}
+    if args.full:
+        out["kernels"] = [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in p.items()} for p in prof]
+    out.update({"gpu_ms_events": round(gpu_ms, 3), "host_ms": round(host_ms, 3), "load_s": round(load_s, 1), "tokens_head": tokens[:8]})
+    if args.full:
+        # the prompt phase: 2 FLOP per active weight per token (embedding row and norms excluded), against the dense 16-bit MFMA peak
+        prefill_ms = sorted(pf_ms[1:])[0]
+        active_params = w_bytes / {"f16": 2, "bf16": 2, "f32": 4}[cfg["act_dtype"]]
+        pf_flops = 2.0 * active_params * args.prompt_len
+        out["prefill"] = {"tokens": args.prompt_len, "ms": round(prefill_ms, 3), "tokens_per_s": round(args.prompt_len / (prefill_ms / 1e3), 1),
+                          "tflops": round(pf_flops / (prefill_ms / 1e3) / 1e12, 2), "mfma_peak_tflops": 2500.0,
+                          "frac_of_mfma_peak": round(pf_flops / (prefill_ms / 1e3) / 2.5e15, 4), "runs_ms": [round(v, 3) for v in pf_ms],
+                          "note": "whole prompt phase (GEMMs on the matrix cores + attention / scan + routing), 2 x active weights x tokens FLOP"}
+    if args.full and mamba and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # CPU baseline + parity gate for the Mamba2 workload: the oracle on the same synthetic weights (a second, host-resident copy of the model: 2 bytes per
         # weight), the prompt token by token (the step kernels under test from the first position on) and `--cpu-tokens` teacher-forced steps
         from oracle import orc_py
@@ -460,7 +480,7 @@ def bench_aux(args, rank, local_rank, world, dist):
                                             "logits_differing": int(sum(int((g != c.astype(np.float32)).sum()) for g, c in zip(gpu_rows, cpu_rows))), "logits_compared": int(sum(g.size for g in gpu_rows))},
                          "note": "prompt row + teacher-forced decode rows of the step kernels against the CPU oracle (exact sums on both sides: DESIGN 4)"}
         del lm2
-    if rank == 0 and not args.no_latency:
+    if args.full and rank == 0 and not args.no_latency:
         out["latency"] = latency_matrix(runtime, synth, lm, cfg, max(args.steps, 16))
     if rank == 0:
         print(json.dumps(out))

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-end measurements on the GPU box (run through gpurun from the repo root, after scripts/profile_round.sh):
-#   1. the bench line of every BASELINE config (defaults: 1 warm-up + 3 timed repetitions, CPU baseline leg included)
+#   1. the bench line of every BASELINE config (--full, defaults: 1 warm-up + 3 timed repetitions, CPU baseline leg included)
 #   2. prompt-phase timings (scripts/bench_prefill*.py), batched decode (scripts/bench_batch.py --graph)
 #   3. rocprofv3 per-kernel summary of a 2048-token prompt on 8 layers of the 8B AWQ shape, and one --pmc pass (MFMA busy cycles; kernel trace only)
 # Outputs under gpurun_out/final/ ; copy the summaries into profiles/ afterwards.
@@ -8,9 +8,9 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/final
 rm -rf $O && mkdir -p $O
-python3 bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+python3 bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 for p in mistral-7b-q4km llama3.2-1b-bf16 mamba2-2.7b deepseek-v2-lite; do
-  python3 bench.py --preset $p > $O/bench_$p.json 2> $O/bench_$p.err
+  python3 bench.py --full --preset $p > $O/bench_$p.json 2> $O/bench_$p.err
   echo "$p done"
 done
 python3 scripts/bench_prefill.py --preset llama3-8b-awq > $O/prefill_llama3-8b-awq.json 2> $O/pf1.err
