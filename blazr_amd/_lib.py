@@ -25,6 +25,8 @@ OK, E_INVALID, E_NODEVICE, E_HIP, E_UNSUPPORTED, E_NOTFOUND, E_OOM = 0, -1, -2, 
 F32, F16, BF16, I64, I32, U32, U8 = range(7)
 ABI_VERSION = 4
 FWD_ALL_LOGITS = 1
+GRAMMAR_REGULAR = 1
+GRAMMAR_LDS_MAX_STATES = 128
 ROPE_NONE, ROPE_LINEAR, ROPE_LLAMA3, ROPE_YARN = 0, 1, 2, 3
 ARCH_LLAMA = 0
 ARCH_MAMBA2 = 1
@@ -196,6 +198,22 @@ SYMBOLS = {
     "bz_paged_attn_decode": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P]),
     "bz_kv_insert": (C.c_int, [P, P, C.c_int, C.c_int, P, P]),
     "bz_rope_caches": (C.c_int, [P, P, P]),
+    "bz_grammar_compile": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(P)]),
+    "bz_grammar_from_table": (C.c_int, [C.c_int, P, P, C.POINTER(P)]),
+    "bz_grammar_table": (C.c_int, [P, P, P]),
+    "bz_grammar_num_states": (C.c_int, [P]),
+    "bz_grammar_current_state": (C.c_int, [P]),
+    "bz_grammar_is_accepting": (C.c_int, [P]),
+    "bz_grammar_reset": (C.c_int, [P]),
+    "bz_grammar_free": (C.c_int, [P]),
+    "bz_grammar_advance": (C.c_int, [P, P, C.c_size_t, C.POINTER(C.c_int)]),
+    "bz_grammar_token_mask": (C.c_int, [P, P, P, C.c_int64, P]),
+    "bz_grammar_to_device": (C.c_int, [P, P, P, P, C.c_int64, C.POINTER(P)]),
+    "bz_device_grammar_set_state": (C.c_int, [P, C.c_uint32]),
+    "bz_device_grammar_info": (C.c_int, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
+    "bz_device_grammar_free": (C.c_int, [P]),
+    "bz_grammar_dfa_mask_logits": (C.c_int, [P, P, C.c_int64, C.c_int64, P, P]),
+    "bz_generate_grammar": (C.c_int, [P, P, C.c_int, C.POINTER(GenConfig), P, P, P, C.c_int64, P, C.POINTER(GenStats)]),
 }
 
 

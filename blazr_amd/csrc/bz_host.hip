@@ -3153,9 +3153,15 @@ static int penalty_window(const std::vector<uint32_t>& hist, int last_n, std::ve
   return (int)ids.size();
 }
 
-extern "C" int bz_generate(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int64_t* out_tokens, bz_gen_stats* stats) {
+extern "C" int bz_generate(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int64_t* out_tokens, bz_gen_stats* stats) { return bz_generate_grammar(m, prompt, n_prompt, gc, nullptr, nullptr, nullptr, 0, out_tokens, stats); }
+
+// the loop itself; `g` (nullable) = gen_config.grammar compiled (executor_generate.rs:96-121): masked on the device before every logits_to_token, advanced on the host
+// with the bytes of every token that comes back
+extern "C" int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, bz_grammar* g, const uint8_t* vocab_bytes,
+                                   const int64_t* offsets, int64_t V, int64_t* out_tokens, bz_gen_stats* stats) {
   BZ_API_BEGIN
   if (!m || !m->finalized || !prompt || !gc || !out_tokens) BZ_FAIL(BZ_E_INVALID, "generate: bad argument");
+  if (g && (!offsets || V != m->cfg.vocab)) BZ_FAIL(BZ_E_INVALID, "generate: a grammar needs the bytes of all %d tokens of the model's vocabulary (got V = %lld)", m->cfg.vocab, (long long)V);
   if (n_prompt <= 0) { if (stats) memset(stats, 0, sizeof(*stats)); return BZ_OK; }  // executor_generate.rs:75-77
   const bz_model_config& c = m->cfg;
   bz_device* dev = m->dev;
@@ -3171,6 +3177,8 @@ extern "C" int bz_generate(bz_model* m, const int64_t* prompt, int n_prompt, con
   int rc = BZ_OK;
   bz_tensor *t_prompt = nullptr, *t_logits = nullptr, *t_tok = nullptr, *t_ids = nullptr, *t_cnts = nullptr, *t_slot = nullptr, *t_bt = nullptr;
   bz_kv* kv = nullptr; bz_paged_kv* pkv = nullptr; bz_decode_graph* graph = nullptr; bz_ssm_state* ssm = nullptr; bz_mirostat* mstate = nullptr;
+  bz_device_grammar* dg = nullptr;
+  const bool use_graph = gc->use_graph && !g;   // graph mode knows no grammar (cuda_graphs.rs): with one, the eager loop runs
   const bool mamba = c.arch == BZ_ARCH_MAMBA2;   // executor_generate.rs:123-181
   auto mamba_arch = [](const bz_model_config& cc) { return cc.arch == BZ_ARCH_MAMBA2; };
   std::vector<uint32_t> history(prompt, prompt + n_prompt);
@@ -3189,6 +3197,7 @@ extern "C" int bz_generate(bz_model* m, const int64_t* prompt, int n_prompt, con
   GEN_TRY(bz_tensor_zeros(dev, BZ_I64, sh1, 1, &t_tok));
   GEN_TRY(bz_tensor_zeros(dev, BZ_I64, sh64, 1, &t_ids));
   GEN_TRY(bz_tensor_zeros(dev, BZ_I32, sh64, 1, &t_cnts));
+  if (g) GEN_TRY(bz_grammar_to_device(dev, g, vocab_bytes, offsets, V, &dg));     // :114 dfa.to_device(&vocab_bytes, &self.device)
   if (mamba) {
     GEN_TRY(bz_ssm_state_create(m, 1, c.act_dtype, &ssm));                       // :131-133 LayeredSsmState::new
     GEN_TRY(bz_forward_ssm(m, t_prompt, n_prompt, ssm, t_logits, 0));            // :137
@@ -3214,9 +3223,9 @@ extern "C" int bz_generate(bz_model* m, const int64_t* prompt, int n_prompt, con
   GEN_TRY(bz_device_synchronize(dev));
   T1 = std::chrono::steady_clock::now();
   BZ_TRACE("phase=\"prefill_end\" backend=\"%s\"", backend);                                   // :139,264,360
-  BZ_TRACE("phase=\"decode_start\" backend=\"%s\" max_tokens=%d graph=%d", backend, max_tokens, gc->use_graph);   // :140,265,361
+  BZ_TRACE("phase=\"decode_start\" backend=\"%s\" max_tokens=%d graph=%d", backend, max_tokens, (int)use_graph);   // :140,265,361
 
-  if (gc->use_graph) {
+  if (use_graph) {
     // cuda_graphs.rs:149-189: first token from the prefill logits, then one graph launch per token
     int64_t tok;
     GEN_TRY(bz_argmax_to_buf(dev, t_logits, 1, c.vocab, t_tok));
@@ -3245,16 +3254,26 @@ extern "C" int bz_generate(bz_model* m, const int64_t* prompt, int n_prompt, con
     const bool needs_cpu = gc->dry_multiplier > 0.f || gc->typical_p > 0.f;
     const bool dyn = !greedy && gc->dynatemp_range > 0.f, miro = gc->mirostat_mode >= 2;
     const bool host_row = needs_cpu || gc->n_logit_bias > 0 || dyn || miro;
+    // the grammar mask sits between DRY / typical and the logit bias (sampling.rs:393-429) and runs on the device, so with a grammar the host steps either side of it
+    // see the row separately; without one this is the single round trip it always was.  Mirostat never sees the mask (sampling.rs:101-103).
+    const bool mask = dg && !miro, post = gc->n_logit_bias > 0 || dyn;
     std::vector<float> row(host_row ? (size_t)c.vocab : 0);
     for (int i = 0; i < max_tokens; i++) {
       float temperature = greedy ? 0.0f : gc->temperature;
-      if (host_row) {
+      if (host_row && (!mask || needs_cpu)) {
         GEN_TRY(bz_tensor_to_host(t_logits, row.data(), (size_t)c.vocab * 4));
         if (gc->dry_multiplier > 0.f) GEN_TRY(bz_apply_dry_penalty(row.data(), c.vocab, history.data(), (int64_t)history.size(), gc->dry_multiplier, gc->dry_base > 0 ? gc->dry_base : 2, gc->dry_allowed_length));
         if (gc->typical_p > 0.f) GEN_TRY(bz_apply_typical_filter(row.data(), c.vocab, gc->typical_p));
-        if (!miro && gc->n_logit_bias > 0) GEN_TRY(bz_apply_logit_bias(row.data(), c.vocab, gc->logit_bias_ids, gc->logit_bias_vals, gc->n_logit_bias));
-        if (!miro && dyn) temperature = bz_compute_dynamic_temperature(row.data(), c.vocab, gc->temperature, gc->dynatemp_range, gc->dynatemp_exponent > 0.f ? gc->dynatemp_exponent : 1.0f);
-        if (!miro) GEN_TRY(bz_tensor_copy_from_host(t_logits, row.data(), (size_t)c.vocab * 4));
+      }
+      if (mask) {
+        if (needs_cpu) GEN_TRY(bz_tensor_copy_from_host(t_logits, row.data(), (size_t)c.vocab * 4));
+        GEN_TRY(bz_grammar_dfa_mask_logits(dev, t_logits, 1, c.vocab, dg, t_logits));          // sampling.rs:415-419
+        if (post) GEN_TRY(bz_tensor_to_host(t_logits, row.data(), (size_t)c.vocab * 4));
+      }
+      if (host_row && !miro) {
+        if (gc->n_logit_bias > 0) GEN_TRY(bz_apply_logit_bias(row.data(), c.vocab, gc->logit_bias_ids, gc->logit_bias_vals, gc->n_logit_bias));
+        if (dyn) temperature = bz_compute_dynamic_temperature(row.data(), c.vocab, gc->temperature, gc->dynatemp_range, gc->dynatemp_exponent > 0.f ? gc->dynatemp_exponent : 1.0f);
+        if (!mask || post) GEN_TRY(bz_tensor_copy_from_host(t_logits, row.data(), (size_t)c.vocab * 4));
       }
       if (miro) {       // sampling.rs:96-110,118-150: Mirostat v2 on the CPU row, token goes back to the device
         if (!mstate) GEN_TRY(bz_mirostat_create(gc->mirostat_tau, gc->mirostat_eta, gc->seed, &mstate));
@@ -3290,6 +3309,11 @@ extern "C" int bz_generate(bz_model* m, const int64_t* prompt, int n_prompt, con
       GEN_TRY(bz_tensor_to_host_pipelined(t_tok, ev, &tok, 8));                      // :378 read_token_id
       BZ_TRACE("step=%d token=%lld sync_us=%.1f", i, (long long)tok, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ts0).count());
       out_tokens[n_out++] = tok; history.push_back((uint32_t)tok); tok_t.push_back(std::chrono::steady_clock::now());
+      if (g) {          // :156-166 advance the DFA with the token's bytes, then dg.current_state = dfa.current_state()
+        if (tok < 0 || tok >= V) { bz_set_error("generate: sampled token %lld outside the vocabulary", (long long)tok); rc = BZ_E_INVALID; goto done; }
+        GEN_TRY(bz_grammar_advance(g, vocab_bytes + offsets[tok], (size_t)(offsets[tok + 1] - offsets[tok]), nullptr));
+        GEN_TRY(bz_device_grammar_set_state(dg, (uint32_t)bz_grammar_current_state(g)));
+      }
       if (tok == gc->eos_id) { finish = 1; break; }
     }
   }
@@ -3321,7 +3345,7 @@ done:
   bz_decode_graph_free(graph);
   bz_tensor_free(t_prompt); bz_tensor_free(t_logits); bz_tensor_free(t_tok); bz_tensor_free(t_ids); bz_tensor_free(t_cnts);
   bz_tensor_free(t_slot); bz_tensor_free(t_bt);
-  bz_kv_free(kv); bz_paged_kv_free(pkv); bz_ssm_state_free(ssm); bz_mirostat_free(mstate);
+  bz_kv_free(kv); bz_paged_kv_free(pkv); bz_ssm_state_free(ssm); bz_mirostat_free(mstate); bz_device_grammar_free(dg);
   return rc;
 #undef GEN_TRY
   BZ_API_END

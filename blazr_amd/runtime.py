@@ -7,7 +7,8 @@ Names and argument meaning follow the reference so that parity tests read like t
 * ``LoadedModel.forward_embed / forward_layers_range / forward_head``  /root/reference/src/cli/swarm_forward.rs:205,239-263
 * ``LayeredKvCache.new_positional(...)``, ``LayeredPagedKvCache(...)``  executor_generate.rs:350-353, :208-210
 * ``logits_to_token(...)``  /root/reference/src/engine/sampling.rs:445-460
-* ``Executor.generate``  executor_generate.rs:341-410 (the loop itself runs in C++: ``bz_generate``)
+* ``Executor.generate``  executor_generate.rs:341-410 (the loop itself runs in C++: ``bz_generate`` / ``bz_generate_grammar``)
+* ``GrammarDfa`` / ``DeviceGrammarDfa``  /root/reference/src/engine/grammar.rs:21-159, sampling.rs:415-419
 
 All compute happens in libblazr_hip.so on the GPU; numpy arrays are only the host view of inputs/outputs.
 """
@@ -700,6 +701,110 @@ def logits_to_token(dev, logits, ids, cnts, repeat_penalty=1.0, frequency_penalt
     return out
 
 
+def pack_vocab(vocab_bytes):
+    """A vocabulary as the C ABI takes it: list of bytes objects (or an already packed (flat u8, offsets i64) pair) -> (flat u8, offsets i64[V+1])."""
+    if isinstance(vocab_bytes, tuple):
+        flat, off = vocab_bytes
+        return np.ascontiguousarray(flat, dtype=np.uint8), np.ascontiguousarray(off, dtype=np.int64)
+    off = np.zeros(len(vocab_bytes) + 1, dtype=np.int64)
+    np.cumsum([len(t) for t in vocab_bytes], out=off[1:])
+    flat = np.frombuffer(b"".join(vocab_bytes), dtype=np.uint8)
+    return np.ascontiguousarray(flat), off
+
+
+class GrammarDfa:
+    """engine::grammar::GrammarDfa (grammar.rs:21-64): compile_grammar_to_dfa(gbnf) (regular=False: the reference's semantics; regular=True: the regular
+    subset of GBNF compiled properly), or a caller-compiled table.  Host only: no device is needed."""
+
+    def __init__(self, gbnf=None, regular=False, table=None, accepting=None):
+        h = C.c_void_p()
+        if table is not None:
+            t = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, 256)
+            a = np.ascontiguousarray(accepting, dtype=np.uint8)
+            if len(a) != len(t):
+                raise ValueError("accepting must have one entry per state")
+            L.check(L.lib().bz_grammar_from_table(len(t), _ptr(t), _ptr(a), C.byref(h)))
+        else:
+            text = gbnf.encode("utf-8") if isinstance(gbnf, str) else bytes(gbnf)
+            L.check(L.lib().bz_grammar_compile(text, L.GRAMMAR_REGULAR if regular else 0, C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if self.h and L.alive:
+                L.lib().bz_grammar_free(self.h)
+        except Exception:
+            pass
+
+    def num_states(self):
+        return L.lib().bz_grammar_num_states(self.h)
+
+    def current_state(self):
+        return L.lib().bz_grammar_current_state(self.h)
+
+    def is_accepting(self):
+        return bool(L.lib().bz_grammar_is_accepting(self.h))
+
+    def reset(self):
+        L.check(L.lib().bz_grammar_reset(self.h))
+
+    def advance(self, data):
+        """advance() per byte as the generate loop calls it; returns the number of bytes that had no transition (the state stays put on those)."""
+        b = np.frombuffer(bytes(data), dtype=np.uint8)
+        rej = C.c_int()
+        L.check(L.lib().bz_grammar_advance(self.h, _ptr(b) if len(b) else None, len(b), C.byref(rej)))
+        return rej.value
+
+    def table(self):
+        """(int32 [num_states, 256] with -1 = no transition, uint8 [num_states] accepting)"""
+        n = self.num_states()
+        t = np.empty((n, 256), dtype=np.int32)
+        a = np.empty(n, dtype=np.uint8)
+        L.check(L.lib().bz_grammar_table(self.h, _ptr(t), _ptr(a)))
+        return t, a
+
+    def compute_token_mask(self, vocab_bytes):
+        flat, off = pack_vocab(vocab_bytes)
+        out = np.empty(len(off) - 1, dtype=np.uint8)
+        L.check(L.lib().bz_grammar_token_mask(self.h, _ptr(flat), _ptr(off), len(off) - 1, _ptr(out)))
+        return out.astype(bool)
+
+    def to_device(self, dev, vocab_bytes):
+        return DeviceGrammarDfa(dev, self, vocab_bytes)
+
+
+class DeviceGrammarDfa:
+    """boostr::DeviceGrammarDfa as GrammarDfa::to_device builds it (grammar.rs:90-139) + GrammarDfaOps::grammar_dfa_mask_logits (sampling.rs:415-419)."""
+
+    def __init__(self, dev, dfa, vocab_bytes):
+        flat, off = pack_vocab(vocab_bytes)
+        h = C.c_void_p()
+        L.check(L.lib().bz_grammar_to_device(dev.h, dfa.h, _ptr(flat), _ptr(off), len(off) - 1, C.byref(h)))
+        self.h, self.dev = h, dev
+
+    def __del__(self):
+        try:
+            if self.h and L.alive:
+                L.lib().bz_device_grammar_free(self.h)
+        except Exception:
+            pass
+
+    def set_state(self, state):
+        L.check(L.lib().bz_device_grammar_set_state(self.h, int(state)))
+
+    def info(self):
+        n, v, s, lds = C.c_int32(), C.c_int64(), C.c_uint32(), C.c_int32()
+        L.check(L.lib().bz_device_grammar_info(self.h, C.byref(n), C.byref(v), C.byref(s), C.byref(lds)))
+        return dict(num_states=n.value, vocab=v.value, state=s.value, lds_table=bool(lds.value))
+
+    def mask_logits(self, logits, out=None):
+        """logits: F32 [rows, vocab] device tensor; the last row is masked.  out=None masks in place."""
+        rows, vocab = logits.shape
+        out = logits if out is None else out
+        L.check(L.lib().bz_grammar_dfa_mask_logits(self.dev.h, logits.h, rows, vocab, self.h, out.h))
+        return out
+
+
 class BatchDecodeGraph:
     """Executor::capture_batched_graph / replay_batched_graph + BatchedGraphState (cuda_graphs_batched.rs:43-257): one hipGraph per decode step of N
     sequences over a shared paged cache; tokens, positions and slots live on the device between replays."""
@@ -798,7 +903,9 @@ class Executor:
     def generate(self, prompt_tokens, max_tokens, temperature=0.0, repeat_penalty=1.0, repeat_last_n=64, frequency_penalty=0.0,
                  presence_penalty=0.0, eos_id=-1, use_graph=False, paged=False, block_size=16, seed=0, top_k=0, top_p=1.0, min_p=0.0,
                  dry_multiplier=0.0, dry_base=2, dry_allowed_length=0, typical_p=0.0, dynatemp_range=0.0, dynatemp_exponent=1.0, mirostat_mode=0,
-                 mirostat_tau=5.0, mirostat_eta=0.1, logit_bias=None):
+                 mirostat_tau=5.0, mirostat_eta=0.1, logit_bias=None, grammar=None, vocab_bytes=None):
+        """grammar: a GrammarDfa (used from its current state, left in its final state) with vocab_bytes = the bytes of every token of the model's vocabulary
+        (gen_config.grammar, executor_generate.rs:96-121)."""
         g = L.GenConfig()
         g.max_tokens, g.temperature, g.repeat_penalty, g.repeat_last_n = max_tokens, temperature, repeat_penalty, repeat_last_n
         g.frequency_penalty, g.presence_penalty = frequency_penalty, presence_penalty
@@ -814,7 +921,13 @@ class Executor:
         p = np.ascontiguousarray(prompt_tokens, dtype=np.int64)
         out = np.zeros(max(max_tokens, 1), dtype=np.int64)
         st = L.GenStats()
-        L.check(L.lib().bz_generate(self.model.h, _ptr(p), len(p), C.byref(g), _ptr(out), C.byref(st)))
+        if grammar is None:
+            L.check(L.lib().bz_generate(self.model.h, _ptr(p), len(p), C.byref(g), _ptr(out), C.byref(st)))
+        else:
+            if vocab_bytes is None:
+                raise ValueError("generate: a grammar needs vocab_bytes")
+            flat, off = pack_vocab(vocab_bytes)
+            L.check(L.lib().bz_generate_grammar(self.model.h, _ptr(p), len(p), C.byref(g), grammar.h, _ptr(flat), _ptr(off), len(off) - 1, _ptr(out), C.byref(st)))
         self.last_stats = dict(prefill_ms=st.prefill_ms, decode_ms=st.decode_ms, n_generated=st.n_generated, finish_reason=st.finish_reason,
                                ttft_ms=st.ttft_ms, total_ms=st.total_ms, itl_p50_ms=st.itl_p50_ms, itl_p99_ms=st.itl_p99_ms, itl_max_ms=st.itl_max_ms,
                                decode_tok_per_s=st.decode_tok_per_s)

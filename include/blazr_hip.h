@@ -296,6 +296,67 @@ int bz_mirostat_free(bz_mirostat* s);
 /* prompt: host i64[n_prompt]; out_tokens: host i64[max_tokens] */
 int bz_generate(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int64_t* out_tokens, bz_gen_stats* stats);
 
+/* ---- grammar-constrained decoding (GrammarDfaOps, engine/executor.rs:67-80; engine/grammar.rs, engine/grammar_parser.rs) ------------------
+ * bz_grammar = GrammarDfa (grammar.rs:21-64): transitions, accepting set, current state.  Host code: none of the bz_grammar_* functions needs a device.
+ * A vocabulary is passed as its tokens' bytes back to back (`vocab_bytes`) and offsets[V+1] into them (offsets[0] == 0); blazr builds the same list
+ * from tokenizer.decode(&[i]) (executor_generate.rs:104-113).  A token without bytes is allowed in every state (EOS and the other specials). */
+typedef struct bz_grammar bz_grammar;
+typedef struct bz_device_grammar bz_device_grammar;
+#define BZ_GRAMMAR_REGULAR 1u
+/* compile_grammar_to_dfa (grammar.rs:165-277) over parse_gbnf (grammar_parser.rs:47-190).
+ *   flags == 0: the reference's semantics, quirks included (lines split at the first "::=", bodies at every '|' even inside quotes, '#' comment lines, escapes
+ *     \n \t \" \\, class members `ch as u8`, only the first `root` rule expanded, a literal byte by byte, a class one state, EVERY OTHER element -- rule reference,
+ *     negated class, name* name+ name? -- one byte of 0..=127; no `root` rule: one state, no transitions).  Differences, all unavoidable: the reference numbers
+ *     states in HashMap order, here the numbering is canonical (breadth first from state 0, bytes ascending), so equality with the reference is equality of the
+ *     language and of prefix viability; input on which the reference's parser never returns ('(' ')' or * + ? after a literal or a class: grammar_parser.rs:153-185
+ *     consumes nothing) is BZ_E_UNSUPPORTED with line and column; so is a non-ASCII character outside quotes and brackets (char::is_alphanumeric is not carried).
+ *     "Invalid GBNF rule: <line>" and "No rules found in GBNF grammar" are BZ_E_INVALID with the reference's messages.
+ *   flags == BZ_GRAMMAR_REGULAR (beyond the reference): the regular subset of GBNF.  Quotes and brackets are honoured before '|'; groups ( ... ) with nested
+ *     alternatives; * + ? after a literal, class, group or rule reference; [^...] = every byte 0..255 outside the ranges (classes are sets of bytes: UTF-8 passes
+ *     through a negated class, a non-ASCII member is refused); any rule of the file may be referenced and is inlined (first definition of a name wins); a rule is
+ *     one line.  Same escape table.  A recursive rule reachable from root, an undefined rule (root included), an unbalanced group or quote, more than 65535 DFA
+ *     states: BZ_E_UNSUPPORTED.  Transitions into states that cannot reach an accepting state are removed; the DFA is not minimised. */
+int bz_grammar_compile(const char* gbnf, uint32_t flags, bz_grammar** out);
+/* a caller-compiled DFA (the fields of DeviceGrammarDfa are plain tensors, grammar.rs:130-138): table [num_states*256], -1 = no transition, every other entry
+ * a state below num_states (else BZ_E_INVALID); accepting [num_states]; at most 65535 states */
+int bz_grammar_from_table(int num_states, const int32_t* table, const uint8_t* accepting, bz_grammar** out);
+int bz_grammar_table(const bz_grammar* g, int32_t* table_out /*[num_states*256], nullable*/, uint8_t* accepting_out /*[num_states], nullable*/);
+int bz_grammar_num_states(const bz_grammar* g);      /* grammar.rs:62-64 */
+int bz_grammar_current_state(const bz_grammar* g);   /* :57-59 */
+int bz_grammar_is_accepting(const bz_grammar* g);    /* :47-49 */
+int bz_grammar_reset(bz_grammar* g);                 /* :52-54 */
+int bz_grammar_free(bz_grammar* g);
+/* GrammarDfa::advance (grammar.rs:37-44) per byte exactly as the generate loop uses it (executor_generate.rs:159-161, the bool is dropped): a byte with no
+ * transition leaves the state where it is and the loop goes on.  n_rejected (nullable): how many bytes had no transition. */
+int bz_grammar_advance(bz_grammar* g, const uint8_t* bytes, size_t n, int* n_rejected);
+/* compute_token_mask (grammar.rs:69-84) from the current state: allowed_out[V] = 1 / 0.  The library-side checker of the kernel below. */
+int bz_grammar_token_mask(const bz_grammar* g, const uint8_t* vocab_bytes, const int64_t* offsets, int64_t V, uint8_t* allowed_out);
+/* GrammarDfa::to_device (grammar.rs:90-139).  The reference ships four f32 tensors because that is its tensor type system; here the next-state table is
+ * uint16_t [num_states*256] with 0xFFFF = none (the value of boostr's INVALID_STATE, grammar.rs:9, is not visible), bytes are uint8_t packed into aligned words and
+ * offsets uint32_t, and the tokens are stored in ascending byte length (results land at the caller's token index).  current_state is copied from g. */
+int bz_grammar_to_device(bz_device* dev, const bz_grammar* g, const uint8_t* vocab_bytes, const int64_t* offsets, int64_t V, bz_device_grammar** out);
+/* dg.current_state = dfa.current_state() (executor_generate.rs:163-165): a host field passed to the kernel as an argument, no device round trip */
+int bz_device_grammar_set_state(bz_device_grammar* dg, uint32_t state);
+/* the kernel stages the whole table in LDS up to this many states (64 KiB, so that two workgroups share a CU's 160 KiB) and reads it through L2 beyond;
+ * bz_device_grammar_info reports which of the two a handle takes (lds_table 1 / 0).  Every out pointer is nullable. */
+#define BZ_GRAMMAR_LDS_MAX_STATES 128
+int bz_device_grammar_info(const bz_device_grammar* dg, int32_t* num_states, int64_t* vocab, uint32_t* state, int32_t* lds_table);
+int bz_device_grammar_free(bz_device_grammar* dg);
+/* GrammarDfaOps::grammar_dfa_mask_logits(&logits, grammar) (sampling.rs:415-419).  logits F32 [rows, vocab]; logits_out may be logits.  The LAST row is masked
+ * (the only row logits_to_token reads; which rows boostr's kernel masks is not visible: a named assumption), other rows are copied unchanged.  A token is walked
+ * from the current state through its bytes; a missing transition sets its logit to -inf, every other logit is copied bit for bit (mask_logits, grammar.rs:142-158).
+ * vocab != the uploaded V: BZ_E_INVALID.  Enqueued on the device stream; no host synchronisation, no device-to-host copy.  A state that admits no token leaves an
+ * all -inf row (the reference leaves that case undefined): bz_argmax_to_buf then returns what it returns for any all -inf row and the sampled path some id in [0, V). */
+int bz_grammar_dfa_mask_logits(bz_device* dev, const bz_tensor* logits, int64_t rows, int64_t vocab, const bz_device_grammar* dg, bz_tensor* logits_out);
+/* bz_generate with gen_config.grammar (executor_generate.rs:96-121): g == NULL is bz_generate.  With a grammar every branch (contiguous, paged, SSM) does per token
+ * what the reference does, in its order (sampling.rs:385-460): host DRY / typical -> device mask -> logit bias -> penalties / temperature / logits_to_token; once the
+ * token id is on the host, bz_grammar_advance with that token's bytes and set_state (executor_generate.rs:156-166, 302-312, 383-393).  Mirostat skips the mask
+ * (sampling.rs:101-103) but still advances.  g is used from its current state and left in its final state; V must be the model's vocab.
+ * use_graph = 1 with a grammar takes the eager loop: the reference's graph mode ignores grammars altogether (cuda_graphs.rs is pure argmax_to_buf), and a
+ * device-resident DFA state inside the captured step is not built. */
+int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, bz_grammar* g /*nullable*/, const uint8_t* vocab_bytes,
+                        const int64_t* offsets, int64_t V, int64_t* out_tokens, bz_gen_stats* stats);
+
 /* ---- measurement (methodology of /root/reference/src/cli/bench.rs:24-33,299-306) ----------------------- */
 typedef struct { char name[48]; int32_t launches; double total_ms; double algo_bytes; } bz_kernel_time;
 /* Runs `iters` eager decode steps (token at position, position+1, ...) with every kernel launched through

@@ -5,6 +5,9 @@
 //
 //   bz-run <model dir | .safetensors | .gguf> --prompt 1,2,3 [--max-tokens N] [--temperature T] [--top-k K] [--top-p P] [--min-p P]
 //          [--repeat-penalty R] [--seed S] [--graphs] [--paged-attention] [--device D] [--stats]
+//          [--grammar FILE --vocab-bytes FILE [--grammar-regular]]
+// --grammar: a GBNF file (gen_config.grammar, executor_generate.rs:96-121), compiled with the reference's semantics or, with --grammar-regular, as the regular subset of
+// GBNF.  --vocab-bytes: the bytes of every token, which blazr takes from its tokenizer (executor_generate.rs:104-113): u32 V, u32 offsets[V+1], then the bytes.
 // prints the generated ids, comma separated, on stdout.
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +16,15 @@
 #include <vector>
 
 #include "../include/blazr_hip.h"
+
+static bool read_file(const std::string& path, std::string& out) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  char buf[65536]; size_t n;
+  while ((n = fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, n);
+  fclose(f);
+  return true;
+}
 
 static int fail(const char* what) { fprintf(stderr, "bz-run: %s: %s\n", what, bz_last_error()); return 1; }
 
@@ -25,6 +37,7 @@ int main(int argc, char** argv) {
   gc.max_tokens = 32; gc.temperature = 0.0f; gc.repeat_penalty = 1.0f; gc.repeat_last_n = 64; gc.top_p = 1.0f; gc.eos_id = -1; gc.block_size = 16;
   gc.dry_base = 2; gc.dynatemp_exponent = 1.0f;
   int device_id = 0; bool stats_on = false;
+  std::string grammar_path, vocab_path; bool grammar_regular = false;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&](const char* name) -> const char* { if (i + 1 >= argc) { fprintf(stderr, "bz-run: %s needs a value\n", name); exit(2); } return argv[++i]; };
@@ -41,21 +54,45 @@ int main(int argc, char** argv) {
     else if (a == "--paged-attention") gc.paged = 1;
     else if (a == "--device") device_id = atoi(next("--device"));
     else if (a == "--stats") stats_on = true;
+    else if (a == "--grammar") grammar_path = next("--grammar");
+    else if (a == "--vocab-bytes") vocab_path = next("--vocab-bytes");
+    else if (a == "--grammar-regular") grammar_regular = true;
     else { fprintf(stderr, "bz-run: unknown option %s\n", a.c_str()); return 2; }
   }
   if (prompt.empty()) { fprintf(stderr, "bz-run: --prompt id,id,... is required\n"); return 2; }
+  if (grammar_path.empty() != vocab_path.empty()) { fprintf(stderr, "bz-run: --grammar and --vocab-bytes go together\n"); return 2; }
+  bz_grammar* grammar = nullptr;
+  std::vector<uint8_t> vbytes; std::vector<int64_t> voff;
+  if (!grammar_path.empty()) {
+    std::string text;
+    if (!read_file(grammar_path, text)) { fprintf(stderr, "bz-run: cannot read %s\n", grammar_path.c_str()); return 2; }
+    if (text.find('\0') != std::string::npos) { fprintf(stderr, "bz-run: %s holds a NUL byte\n", grammar_path.c_str()); return 2; }
+    if (bz_grammar_compile(text.c_str(), grammar_regular ? BZ_GRAMMAR_REGULAR : 0u, &grammar) != BZ_OK) return fail("grammar");
+    std::string raw;
+    if (!read_file(vocab_path, raw) || raw.size() < 8) { fprintf(stderr, "bz-run: cannot read %s\n", vocab_path.c_str()); return 2; }
+    uint32_t V = 0;
+    memcpy(&V, raw.data(), 4);
+    const size_t head = 4 + ((size_t)V + 1) * 4;
+    if (V == 0 || raw.size() < head) { fprintf(stderr, "bz-run: %s is shorter than its offset table\n", vocab_path.c_str()); return 2; }
+    voff.resize((size_t)V + 1);
+    for (size_t i = 0; i <= V; i++) { uint32_t o; memcpy(&o, raw.data() + 4 + 4 * i, 4); voff[i] = o; }
+    if ((size_t)voff[V] != raw.size() - head) { fprintf(stderr, "bz-run: %s: the last offset does not match the number of bytes\n", vocab_path.c_str()); return 2; }
+    vbytes.assign(raw.begin() + head, raw.end());
+  }
   bz_device* dev = nullptr;
   if (bz_device_open(device_id, &dev) != BZ_OK) return fail("device");                    // CudaDevice::new + CudaClient::new (run.rs:70-81)
   bz_model* m = nullptr; bz_model_config cfg;
   if (bz_load_model(dev, model.c_str(), &m, &cfg) != BZ_OK) return fail("load");          // detect_model_source + load_model (run.rs:88-118)
   std::vector<int64_t> out((size_t)(gc.max_tokens > 0 ? gc.max_tokens : 1));
   bz_gen_stats st;
-  if (bz_generate(m, prompt.data(), (int)prompt.size(), &gc, out.data(), &st) != BZ_OK) return fail("generate");
+  if (bz_generate_grammar(m, prompt.data(), (int)prompt.size(), &gc, grammar, vbytes.data(), grammar ? voff.data() : nullptr, (int64_t)voff.size() - (grammar ? 1 : 0), out.data(), &st) != BZ_OK)
+    return fail("generate");
   for (int i = 0; i < st.n_generated; i++) printf(i ? ",%lld" : "%lld", (long long)out[i]);
   printf("\n");
   if (stats_on)   // cli/bench.rs:299-306 decode tok/s = (tokens - 1) / (total - TTFT)
     fprintf(stderr, "prefill %.2f ms, decode %.2f ms, %d tokens, %.1f tok/s decode, finish=%s\n", st.prefill_ms, st.decode_ms, st.n_generated,
             st.n_generated > 1 ? (st.n_generated - 1) / (st.decode_ms / 1e3) : 0.0, st.finish_reason ? "eos" : "length");
+  bz_grammar_free(grammar);
   bz_model_free(m);
   bz_device_close(dev);
   return 0;
