@@ -52,7 +52,8 @@ class ModelConfig(C.Structure):
                 ("mla_v_dim", C.c_int32), ("moe_n_experts", C.c_int32), ("moe_top_k", C.c_int32), ("moe_n_shared", C.c_int32),
                 ("moe_inter", C.c_int32), ("moe_first_dense", C.c_int32), ("moe_norm_topk", C.c_int32), ("moe_routed_scale", C.c_float),
                 ("rope_beta_fast", C.c_float), ("rope_beta_slow", C.c_float), ("rope_attn_factor", C.c_float), ("mla_softmax_mscale", C.c_float),
-                ("reserved", C.c_int32 * 4)]
+                ("sliding_window", C.c_int32), ("sliding_window_pattern", C.c_int32),   # took two of the four reserved slots: 0 = full attention
+                ("reserved", C.c_int32 * 2)]
 
 
 class GenConfig(C.Structure):

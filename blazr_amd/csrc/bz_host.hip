@@ -383,6 +383,10 @@ extern "C" int bz_model_create(bz_device* dev, const bz_model_config* cfg, bz_mo
   if (cfg->hidden % 8 || cfg->head_dim % 8 || cfg->inter % 8) BZ_FAIL(BZ_E_UNSUPPORTED, "config: hidden/head_dim/inter must be multiples of 8");
   }
   if (cfg->act_dtype != BZ_F32 && cfg->act_dtype != BZ_F16 && cfg->act_dtype != BZ_BF16) BZ_FAIL(BZ_E_INVALID, "config: bad act_dtype");
+  if (cfg->sliding_window < 0 || cfg->sliding_window_pattern < 0) BZ_FAIL(BZ_E_INVALID, "config: negative sliding_window / sliding_window_pattern");
+  if (cfg->arch != BZ_ARCH_LLAMA && (cfg->sliding_window > 0 || cfg->sliding_window_pattern > 0))
+    BZ_FAIL(BZ_E_UNSUPPORTED, "config: sliding_window %d (pattern %d) is implemented for the Llama family only, not for arch %d", cfg->sliding_window,
+            cfg->sliding_window_pattern, cfg->arch);
   bz_model* m = new bz_model();
   m->dev = dev; m->cfg = *cfg;
   if (cfg->arch == BZ_ARCH_DEEPSEEK2) { m->cfg.n_kv_heads = 1; m->cfg.head_dim = cfg->mla_kv_lora_rank + cfg->mla_rope_dim; }   // shape of the latent cache
@@ -1388,6 +1392,18 @@ static hipStream_t step_stream(const bz_model* m) { return tl_capture_stream ? t
 // contexts beyond this many positions take the split-KV attention path (two launches; the fused single launch wins below it)
 static int att_split_min() { const char* e = getenv("BZ_SPLIT_MIN"); return e ? atoi(e) : 512; }   // read per call: tests move it
 static int att_positions_for(int len) { return len > att_split_min() ? len : 0; }
+// sliding window of layer l (0: full attention): every layer, or -- sliding_window_pattern n > 1 -- every layer but each n-th (l % n == n - 1)
+static int layer_window(const bz_model_config& c, int l) {
+  if (c.sliding_window <= 0) return 0;
+  const int n = c.sliding_window_pattern;
+  return (n > 1 && l % n == n - 1) ? 0 : c.sliding_window;
+}
+// the most keys any layer's query reads at a context of `len` positions
+static int window_keys(const bz_model_config& c, int len) {
+  bool all = c.sliding_window > 0;
+  for (int l = 0; all && l < c.n_layers; l++) all = layer_window(c, l) > 0;
+  return all ? std::min(len, c.sliding_window) : len;
+}
 
 struct StepIO {
   KvView kv;
@@ -1468,23 +1484,27 @@ static int llama_step(bz_model* m, const StepIO& io) {
     AttnArgs aa{};
     aa.qkv = qkv; aa.cos_t = m->cos_t; aa.sin_t = m->sin_t; aa.interleaved = c.rope_interleaved; aa.pos = io.d_pos; aa.rope_cur = m->rope_cur;
     aa.nq = c.n_heads; aa.nkv = c.n_kv_heads; aa.hd = c.head_dim; aa.act = act; aa.kv = io.kv; aa.layer = l; aa.out = m->attn_out;
-    aa.zero_buf = nullptr; aa.zero_n = 0; aa.q_only = 0;
+    aa.zero_buf = nullptr; aa.zero_n = 0; aa.q_only = 0; aa.window = layer_window(c, l);
+    // a windowed layer reads min(len, W) keys: the choice of path is made on that many positions, so a long context with a window that fits the single-pass
+    // kernel goes back to it (att_positions: position + 1 in eager steps, the capacity in a graph -- both sides of W give the same choice)
+    const int att_positions = aa.window > 0 ? att_positions_for(std::min(io.att_positions, aa.window)) : io.att_positions;
     VSrc ov;
     static const bool no_fuse = getenv("BZ_NO_ATTN_FUSION") != nullptr;
     // (the f32-cache form has no split-KV partner: beyond the single-launch contexts it stays unfused)
-    const bool fuse_cap = !no_fuse && Ld.o.parts.size() == 1 && Ld.o.fix_out && bzk_attn_oproj_slices(aa, Ld.o.parts[0]) > 0;
+    const bool fuse_shape = !no_fuse && Ld.o.parts.size() == 1 && Ld.o.fix_out;
+    const bool fuse_cap = fuse_shape && bzk_attn_oproj_slices(aa, Ld.o.parts[0]) > 0;
     static const bool no_split = getenv("BZ_NO_ATTN_SPLIT") != nullptr;
-    const bool split_wanted = !no_split && io.att_positions > 0 && m->att_ws && bzk_attn_split_ok(aa);
-    const bool merge_fused = fuse_cap && Ld.o.parts[0].kind == LK_Q4G && bzk_attn_merge_oproj_ok(aa, Ld.o.parts[0]);
+    const bool split_wanted = !no_split && att_positions > 0 && m->att_ws && bzk_attn_split_ok(aa);
+    const bool merge_fused = fuse_shape && Ld.o.parts[0].kind == LK_Q4G && bzk_attn_merge_oproj_ok(aa, Ld.o.parts[0]);
     // long contexts: split-KV attention merged with the o_proj where that form exists (int4); otherwise attention (split or not) and a separate o_proj launch --
     // the fused single-launch kernel reads the context once per column slice, which only pays while the context is short
-    const bool fuse_o = fuse_cap && (io.att_positions == 0 || (split_wanted && merge_fused));
+    const bool fuse_o = (fuse_cap && att_positions == 0) || (split_wanted && merge_fused);
     const bool split = split_wanted && (!fuse_o || merge_fused);
     int nsplit = 0;
     if (split) {
       // long context: split-KV partials (all query heads of a group share the K/V rows), then merge (+ o_proj); the grid covers
       // att_positions, the kernels slice the live context (position + 1) the same way for every grid
-      nsplit = bzk_attn_split_slices(io.att_positions);
+      nsplit = bzk_attn_split_slices(att_positions);
       BZ_TRY(bzk_attn_split(st, aa, nsplit, m->att_ws));
     }
     if (fuse_o) {
@@ -1787,7 +1807,7 @@ static bool prefill_eligible(const bz_model* m, int S, int total_len, bool decod
   const bool attn_exact = !decode_batch && (prefill_exact(m, S, false) != 0 || c.act_dtype == BZ_F32);
   const bool attn_mfma = !decode_batch && c.act_dtype != BZ_F32 && !attn_exact && bzk_pf_attn_mfma_ok(c.head_dim, rep);
   if (!attn_mfma && (!decode_batch || !bzk_pf_attn_mfma_ok(c.head_dim, rep)) &&
-      bzk_pf_attn_smem(c.n_heads, c.n_kv_heads, c.head_dim, total_len, attn_exact) > 160 * 1024) return false;
+      bzk_pf_attn_smem(c.n_heads, c.n_kv_heads, c.head_dim, window_keys(c, total_len), attn_exact) > 160 * 1024) return false;   // (a row's scores: its window)
   // every projection either dense in the activation dtype (MFMA GEMM) or int4 without act-order (multi-row dot4 GEMM)
   if (c.act_dtype == BZ_F32) {
     // f32 activations (GGUF models): every projection in a block format, no bias, same K in all parts of a fused linear; the head stays the decode GEMV
@@ -1939,6 +1959,7 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
   BZ_TRY(prefill_ws(m, std::min(S, CH)));
   const int exact = prefill_exact(m, S, rc.row_pos != nullptr);
   const bool attn_exact = exact != 0 || act == BZ_F32;       // f32 models: the oracle's double-precision sums cost little next to the f32 cache reads
+  BZ_TRACE("prefill: S=%d position=%d rows=%s exact=%d window=%d", S, pos0, rc.row_pos ? "decode-batch" : "prompt", exact, c.sliding_window);
   for (int s0 = 0; s0 < S; s0 += CH) {
     const int n = std::min(CH, S - s0), p0 = pos0 + s0;
     // decode batch (row_pos set): one block-table row per sequence -- the kernels index rows by the row number INSIDE the chunk, so the chunk
@@ -1954,7 +1975,8 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
       BZ_TRY(gq ? pf_gemm_gq(m, L.qkv, (const float*)m->pf_x16, n, m->pf_qkv) : pf_gemm(m, L.qkv.parts[0], m->pf_x16, n, m->pf_qkv, exact));
       BZ_TRY(bzk_pf_rope_kv(st, m->pf_qkv, n, nq, nkv, hd, m->cos_t, m->sin_t, c.rope_interleaved, p0, act, vw, l, slots ? slots + s0 : nullptr,
                             rc.row_pos ? rc.row_pos + s0 : nullptr));
-      BZ_TRY(bzk_pf_attn(st, dt, m->pf_qkv, n, nq, nkv, hd, p0, act, vw, l, m->pf_x16, rc.row_pos ? rc.row_pos + s0 : nullptr, rc.table_stride, rc.max_len, attn_exact));
+      BZ_TRY(bzk_pf_attn(st, dt, m->pf_qkv, n, nq, nkv, hd, p0, act, vw, l, m->pf_x16, rc.row_pos ? rc.row_pos + s0 : nullptr, rc.table_stride, rc.max_len, attn_exact,
+                         layer_window(c, l)));
       BZ_TRY(gq ? pf_gemm_gq(m, L.o, (const float*)m->pf_x16, n, m->pf_t) : pf_gemm(m, L.o.parts[0], m->pf_x16, n, m->pf_t, exact));
       BZ_TRY(bzk_pf_norm(st, dt, m->pf_h, m->pf_t, L.ffn_norm, n, H, c.rms_eps, act, m->pf_x16));
       BZ_TRY(gq ? pf_gemm_gq(m, L.gateup, (const float*)m->pf_x16, n, m->pf_gu) : pf_gemm(m, L.gateup.parts[0], m->pf_x16, n, m->pf_gu, exact));
@@ -3083,6 +3105,8 @@ extern "C" int bz_decode_graph_replay(bz_decode_graph* g) {
             g->m->cfg.max_seq_len);
   // the position of this replay is known on the host (seeded position + replays since): long contexts replay the split-KV variant,
   // captured on first need over the same device words and sized for the cache capacity
+  // (the variant is chosen on the context alone; inside it every layer decides on min(capacity, its window), so a model whose windows all fit the single-pass
+  //  kernel captures a long variant with the same launches as the short one: one capture more than needed, the same step)
   if (!g->ssm && g->capacity > 0 && att_positions_for((int)(g->seed_pos + g->replays + 1)) > 0) {
     if (!g->exec_long) {
       BZ_HIP(hipSetDevice(g->m->dev->id));
@@ -3629,7 +3653,7 @@ static int attn_common(bz_model* m, const bz_tensor* q, const KvView& view, int 
   AttnArgs aa{};
   aa.qkv = VSrc{q->ptr, 0}; aa.cos_t = m->cos_t; aa.sin_t = m->sin_t; aa.interleaved = c.rope_interleaved; aa.pos = m->pos_tmp;
   aa.nq = c.n_heads; aa.nkv = c.n_kv_heads; aa.hd = c.head_dim; aa.act = c.act_dtype; aa.kv = view; aa.layer = layer; aa.out = (float*)out->ptr;
-  aa.q_only = 1;
+  aa.q_only = 1; aa.window = layer_window(c, layer);   // the query is the one at position len - 1
   BZ_TRY(bzk_attn_decode(st, aa));
   BZ_HIP(hipStreamSynchronize(st));
   return BZ_OK;

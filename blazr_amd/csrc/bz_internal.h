@@ -236,7 +236,10 @@ struct AttnArgs {
   float* out;               // [nq*hd] f32 rounded
   long long* zero_buf; int zero_n;
   int q_only;               // op-level test: q given roped in qkv (plain), no insert, len = *pos
+  int window;               // sliding window W of this layer (0: none): the kernels read keys [att_lo(len, W), len) only -- lo is derived on the device from *pos
 };
+// first key a query sees under a window of W keys (W <= 0: none), len = the query's position + 1
+__host__ __device__ __forceinline__ int att_lo(int len, int W) { return W > 0 && len > W ? len - W : 0; }
 int bzk_attn_decode(hipStream_t s, const AttnArgs& a);
 int bzk_attn_oproj_slices(const AttnArgs& a, const LinearDev& L);   // 0: fused form not applicable
 int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long long* acc);
@@ -327,7 +330,7 @@ int bzk_pf_norm(hipStream_t s, int dt, float* hbuf, const float* prev, const flo
 int bzk_pf_rope_kv(hipStream_t s, float* qkv, int S, int nq, int nkv, int hd, const float* cos_t, const float* sin_t, int interleaved, int pos0, int act,
                    const KvView& kv, int layer, const int* slots, const int* row_pos = nullptr);
 int bzk_pf_attn(hipStream_t s, int dt, const float* qkv, int S, int nq, int nkv, int hd, int pos0, int act, const KvView& kv, int layer, void* out16,
-                const int* row_pos = nullptr, int table_stride = 0, int max_len = 0, bool exact = false);
+                const int* row_pos = nullptr, int table_stride = 0, int max_len = 0, bool exact = false, int window = 0);   // window: see AttnArgs (every row its own lo)
 // Mamba2 batched prefill (bz_prefill.hip): conv over the prompt rows (+ carried conv state), in-kernel scan over the tokens, gated RMSNorm rows
 struct BzSsmScan {
   const float* xbc; int conv_dim; const float* zx; int ld; int dt_off; const float* dt_bias; const float* A_log; const float* D; void* state;

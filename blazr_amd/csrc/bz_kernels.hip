@@ -3107,7 +3107,7 @@ struct KvRow {
   }
 };
 
-template <int HD, int KVDT>
+template <int HD, int KVDT, int WIN = 0>   // WIN: sliding window (a.window > 0) -- the streams start at the window's first key instead of key 0
 __global__ __launch_bounds__(256) void k_attn_decode(AttnArgs a) {
   // grid = nq query heads.  All 256 lanes of the workgroup are position streams of ONE query head (position p -> lane
   // p % 256), merged once through LDS.  Workgroups of one GQA group recompute the (tiny) k/v finishing redundantly; the
@@ -3126,6 +3126,7 @@ __global__ __launch_bounds__(256) void k_attn_decode(AttnArgs a) {
   const int pos = a.pos[0];
   const int len = a.q_only ? pos : pos + 1;
   const int ncache = pos;                 // positions [0, ncache) come from the cache; `pos` itself (if any) from LDS
+  const int lo = WIN ? att_lo(len, a.window) : 0;
   const KvView& kv = a.kv;
   zero_duty<256>(a.zero_buf, a.zero_n);
 
@@ -3160,7 +3161,7 @@ __global__ __launch_bounds__(256) void k_attn_decode(AttnArgs a) {
   float o[HD];
 #pragma unroll
   for (int i = 0; i < HD; i++) o[i] = 0.f;
-  for (int p = tid; p < len; p += 256) {
+  for (int p = lo + tid; p < len; p += 256) {
     KvRow<HD, KVDT> kr, vr;
     const size_t ro = p < ncache ? kv_row_off(kv, a.layer, kvh, p) : 0;
     if (p < ncache) kr.load(kv.k, ro); else kr.from_f32(knew);
@@ -3195,7 +3196,7 @@ __global__ __launch_bounds__(256) void k_attn_decode(AttnArgs a) {
   const float w = (m == -INFINITY) ? 0.f : bz_expf(m - M);
   const float ws = wave_sum(l * w);
   if (lane == 0) wred[4 + wave] = ws;
-  const int nrows = min(len, 256);
+  const int nrows = min(len - lo, 256);
   if (tid < nrows) {
 #pragma unroll
     for (int i = 0; i < HD; i += 4) *(float4*)(ored + tid * LDR + i) = make_float4(o[i] * w, o[i + 1] * w, o[i + 2] * w, o[i + 3] * w);
@@ -3228,7 +3229,7 @@ __global__ __launch_bounds__(256) void k_attn_decode(AttnArgs a) {
 // FUSE: block (head, column slice) multiplies the head output by its slab of Wo (o_proj = sum over heads of Wo[:, head slab] . attn_head) -- slab loads are
 // issued at kernel entry and stay in flight through the whole attention.
 // ---------------------------------------------------------------------------------------------------------
-template <int KVDT, int FUSE, int TPW, int NW, int PAGED, int HD = 128>   // NW waves per block: each owns 256/NW positions of a chunk; HD = 128 or 64 (64: not fused)
+template <int KVDT, int FUSE, int TPW, int NW, int PAGED, int HD = 128, int WIN = 0>   // WIN: sliding window (see below); NW waves per block: each owns 256/NW positions of a chunk; HD = 128 or 64 (64: not fused)
 __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __restrict__ W, const __half* __restrict__ S,
                                                const unsigned char* __restrict__ Z, const float* __restrict__ bias, int CS, long long* acc) {
   // Mapping: a chunk is 256 positions in row groups of RPL = 512 / HD whole rows (one wave-wide 16-byte load: 1 KiB contiguous in the contiguous cache; 4 rows of
@@ -3320,6 +3321,9 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
   const int pos = __builtin_amdgcn_readfirstlane(pos_v);
   const int pmax = pos > 0 ? pos - 1 : 0;
   const int len = a.q_only ? pos : pos + 1;
+  // WIN (a.window > 0): keys [lo, len) only.  The chunk walk starts at the 256-position chunk that holds lo (cb) -- rows of that chunk below lo are read and
+  // masked (< 256 of them), every chunk below it is never touched -- so the chunk / wave / lane decomposition of a context is the one the plain kernel has.
+  const int lo = WIN ? att_lo(len, a.window) : 0, cb = WIN ? (lo & ~255) : 0;
   const unsigned short* kb0 = (const unsigned short*)kv.k + (size_t)a.layer * kv.layer_stride;
   const unsigned short* vb0 = (const unsigned short*)kv.v + (size_t)a.layer * kv.layer_stride;
   uint4 kr[NL], vr[NL];
@@ -3327,14 +3331,14 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
   for (int i = 0; i < NL; i++) { kr[i] = make_uint4(0, 0, 0, 0); vr[i] = make_uint4(0, 0, 0, 0); }
 #define ATT_ROW(i) (((i) * NW + wave) * RPL + rsub)                 /* row of load i inside a chunk */
 #define ATT_LIVE(c0_, i) ((c0_) + ((i) * NW + wave) * RPL < len)    /* wave-uniform: the row group has a position of the context */
-  if (wave * RPL < len) {
+  if (cb + wave * RPL < len) {
     if (!PAGED) {
       const unsigned short* kb = kb0 + (size_t)kvh * kv.cap * HD;
       const unsigned short* vb = vb0 + (size_t)kvh * kv.cap * HD;
 #pragma unroll
       for (int i = 0; i < NL; i++) {
-        if (ATT_LIVE(0, i)) {
-          const unsigned off = (unsigned)min(ATT_ROW(i), pmax) * HD + piece * 8;
+        if (ATT_LIVE(cb, i)) {
+          const unsigned off = (unsigned)min(cb + ATT_ROW(i), pmax) * HD + piece * 8;
           kr[i] = *(const uint4*)(kb + off);
           vr[i] = *(const uint4*)(vb + off);
         }
@@ -3342,11 +3346,11 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
     } else {
       int blk[NL];
 #pragma unroll
-      for (int i = 0; i < NL; i++) blk[i] = ATT_LIVE(0, i) ? kv.block_table[min(ATT_ROW(i), pmax) / kv.bs] : 0;
+      for (int i = 0; i < NL; i++) blk[i] = ATT_LIVE(cb, i) ? kv.block_table[min(cb + ATT_ROW(i), pmax) / kv.bs] : 0;
 #pragma unroll
       for (int i = 0; i < NL; i++) {
-        if (ATT_LIVE(0, i)) {
-          const int pp = min(ATT_ROW(i), pmax);
+        if (ATT_LIVE(cb, i)) {
+          const int pp = min(cb + ATT_ROW(i), pmax);
           const size_t off = (((size_t)blk[i] * kv.n_kv + kvh) * kv.bs + (pp % kv.bs)) * HD + piece * 8;
           kr[i] = *(const uint4*)(kb0 + off);
           vr[i] = *(const uint4*)(vb0 + off);
@@ -3390,7 +3394,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
   const uint4 qq = ((const uint4*)q2)[piece];
   float qf[8];
   unpack2<KVDT>(qq.x, qf[0], qf[1]); unpack2<KVDT>(qq.y, qf[2], qf[3]); unpack2<KVDT>(qq.z, qf[4], qf[5]); unpack2<KVDT>(qq.w, qf[6], qf[7]);
-  const bool single = len <= 256;
+  const bool single = len - cb <= 256;
   float sc_[NL];
   float Mw = -INFINITY;
 #define ATT_SCORES(c0_)                                                                                                    \
@@ -3404,12 +3408,12 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
     double d = 0.0;                                                                                                        \
     _Pragma("unroll") for (int e = 0; e < 8; e++) d = fma((double)kf[e], (double)qf[e], d);                                \
     d = grp_sum_d<NPC>(d);                                                                                                 \
-    sc_[i] = (p < len) ? (float)d * scale : -INFINITY;                                                                     \
+    sc_[i] = (p < len && (!WIN || p >= lo)) ? (float)d * scale : -INFINITY;                                                \
   }
-  for (int c0 = 0; c0 < len; c0 += 256) {
+  for (int c0 = cb; c0 < len; c0 += 256) {
     const bool won = c0 + wave * RPL < len;   // wave-uniform: this wave has live positions in the chunk
     if (!won) continue;
-    if (c0 > 0) {
+    if (c0 > cb) {
 #pragma unroll
       for (int i = 0; i < NL; i++)
         if (ATT_LIVE(c0, i)) kr[i] = *(const uint4*)(kb0 + kv_row_off_t<PAGED>(kv, 0, kvh, min(c0 + ATT_ROW(i), pmax)) + piece * 8);
@@ -3426,7 +3430,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
   for (int w = 1; w < NW; w++) Mall = fmaxf(Mall, wred[w]);
   double accv[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   double lsum = 0.0;
-  for (int c0 = 0; c0 < len; c0 += 256) {
+  for (int c0 = cb; c0 < len; c0 += 256) {
     const bool won = c0 + wave * RPL < len;
     if (!won) continue;
     if (!single) {
@@ -3535,7 +3539,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
 // tile cs * 8 + w and the head's 128 k of it -- four 32-k chunks of superblock hq / 2 (a 256-k superblock spans two heads) with that superblock's
 // header --, requested at entry; the head output is quantised per 32-k chunk (quant8_x32) and the tile's partial goes to the fixed-point ring.
 // ---------------------------------------------------------------------------------------------------------
-template <int PAGED, int FUSE = 0>
+template <int PAGED, int FUSE = 0, int WIN = 0>   // WIN: sliding window, as in k_attn2 (the chunk walk starts at the chunk that holds the window's first key)
 __global__ __launch_bounds__(512) void k_attn2f(AttnArgs a, const uint4* __restrict__ Wq, const uint4* __restrict__ Hd, const float* __restrict__ bias, int CS, long long* acc) {
   constexpr int HD = 128, half = 64, NW = 8, PW = 256 / NW, NL = PW / 4, NTH = NW * 64;
   __shared__ __attribute__((aligned(16))) float qf[HD], kf[HD], vf[HD];
@@ -3586,6 +3590,7 @@ __global__ __launch_bounds__(512) void k_attn2f(AttnArgs a, const uint4* __restr
   const int pos = __builtin_amdgcn_readfirstlane(pos_v);
   const int pmax = pos > 0 ? pos - 1 : 0;
   const int len = a.q_only ? pos : pos + 1;
+  const int lo = WIN ? att_lo(len, a.window) : 0, cb = WIN ? (lo & ~255) : 0;
   const float* kb0 = (const float*)kv.k + (size_t)a.layer * kv.layer_stride;
   const float* vb0 = (const float*)kv.v + (size_t)a.layer * kv.layer_stride;
   float4 kr[NL][2], vr[NL][2];
@@ -3594,11 +3599,11 @@ __global__ __launch_bounds__(512) void k_attn2f(AttnArgs a, const uint4* __restr
   // row groups of 4 positions dealt round-robin to the waves (k_attn2's mapping: a short context spreads over all 8 waves, dead iterations are skipped)
 #define ATF_ROW(i) (((i) * NW + wave) * 4 + rsub)
 #define ATF_LIVE(c0_, i) ((c0_) + ((i) * NW + wave) * 4 < len)
-  if (wave * 4 < len) {
+  if (cb + wave * 4 < len) {
 #pragma unroll
     for (int i = 0; i < NL; i++) {
-      if (ATF_LIVE(0, i)) {
-        const size_t off = kv_row_off_t<PAGED>(kv, 0, kvh, min(ATF_ROW(i), pmax)) + piece * 8;
+      if (ATF_LIVE(cb, i)) {
+        const size_t off = kv_row_off_t<PAGED>(kv, 0, kvh, min(cb + ATF_ROW(i), pmax)) + piece * 8;
         kr[i][0] = *(const float4*)(kb0 + off); kr[i][1] = *(const float4*)(kb0 + off + 4);
         vr[i][0] = *(const float4*)(vb0 + off); vr[i][1] = *(const float4*)(vb0 + off + 4);
       }
@@ -3630,9 +3635,9 @@ __global__ __launch_bounds__(512) void k_attn2f(AttnArgs a, const uint4* __restr
   const float scale = div_rn(1.0f, sqrt_rn((float)HD));
   const float4 qa = *(const float4*)(qf + piece * 8), qb = *(const float4*)(qf + piece * 8 + 4);
   float Mrun = -INFINITY, Lrun = 0.f, Orun = 0.f;   // running state (threads < 128 own output d = tid)
-  for (int c0 = 0; c0 < len; c0 += 256) {
+  for (int c0 = cb; c0 < len; c0 += 256) {
     const bool won = c0 + wave * 4 < len;
-    if (c0 > 0) {
+    if (c0 > cb) {
       __syncthreads();
       if (won) {
 #pragma unroll
@@ -3659,7 +3664,7 @@ __global__ __launch_bounds__(512) void k_attn2f(AttnArgs a, const uint4* __restr
         }
         float d = k0.x * qa.x + k0.y * qa.y + k0.z * qa.z + k0.w * qa.w + k1.x * qb.x + k1.y * qb.y + k1.z * qb.z + k1.w * qb.w;
         d = grp_reduce<16, OpAdd>(d);
-        sc_[i] = (p < len) ? d * scale : -INFINITY;
+        sc_[i] = (p < len && (!WIN || p >= lo)) ? d * scale : -INFINITY;
         mloc = fmaxf(mloc, sc_[i]);
       }
       mloc = wave_max(mloc);
@@ -3769,16 +3774,19 @@ int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long lo
   if (a.kv.dtype == BZ_F32) {
     const int CS = attn2f_oproj_slices(a, L);
     if (CS <= 0) BZ_FAIL(BZ_E_INVALID, "attn+o_proj fusion (f32 cache) does not apply to this shape");
-    if (a.kv.paged) BZ_LAUNCH("attn+o_proj<q4_K>", L.algo_bytes, (k_attn2f<1, 1>), dim3(a.nq * CS), dim3(512), 0, s, a, (const uint4*)L.w, (const uint4*)L.hdr, L.bias, CS, acc);
-    else BZ_LAUNCH("attn+o_proj<q4_K>", L.algo_bytes, (k_attn2f<0, 1>), dim3(a.nq * CS), dim3(512), 0, s, a, (const uint4*)L.w, (const uint4*)L.hdr, L.bias, CS, acc);
+#define LAUNCH_AF(PG, WN) BZ_LAUNCH("attn+o_proj<q4_K>", L.algo_bytes, (k_attn2f<PG, 1, WN>), dim3(a.nq * CS), dim3(512), 0, s, a, (const uint4*)L.w, (const uint4*)L.hdr, L.bias, CS, acc)
+    if (a.window > 0) { if (a.kv.paged) LAUNCH_AF(1, 1); else LAUNCH_AF(0, 1); }
+    else { if (a.kv.paged) LAUNCH_AF(1, 0); else LAUNCH_AF(0, 0); }
+#undef LAUNCH_AF
     BZ_HIP(hipGetLastError());
     return BZ_OK;
   }
   if (L.kind == LK_ROWS) {
     const int DL = attn_dense_oproj_loads(a, L);
     if (DL <= 0) BZ_FAIL(BZ_E_INVALID, "attn+o_proj fusion (dense) does not apply to this shape");
-#define LAUNCH_AD(DT, T, PG, HDV) BZ_LAUNCH("attn+o_proj<dense>", L.algo_bytes, (k_attn2<DT, 2, T, 8, PG, HDV>), dim3(a.nq * 8), dim3(512), attn2_smem(8), s, a, \
+#define LAUNCH_AD_(DT, T, PG, HDV, WN) BZ_LAUNCH("attn+o_proj<dense>", L.algo_bytes, (k_attn2<DT, 2, T, 8, PG, HDV, WN>), dim3(a.nq * 8), dim3(512), attn2_smem(8), s, a, \
     (const uint4*)L.w, (const __half*)nullptr, (const unsigned char*)nullptr, L.bias, 8, acc)
+#define LAUNCH_AD(DT, T, PG, HDV) do { if (a.window > 0) LAUNCH_AD_(DT, T, PG, HDV, 1); else LAUNCH_AD_(DT, T, PG, HDV, 0); } while (0)
 #define LAUNCH_AD_P(DT, T, HDV) do { if (a.kv.paged) LAUNCH_AD(DT, T, 1, HDV); else LAUNCH_AD(DT, T, 0, HDV); } while (0)
 #define LAUNCH_AD_T(DT, HDV) do { if (DL == 1) LAUNCH_AD_P(DT, 1, HDV); else if (DL == 2) LAUNCH_AD_P(DT, 2, HDV); else LAUNCH_AD_P(DT, 4, HDV); } while (0)
 #define LAUNCH_AD_H(DT) do { if (a.hd == 64) LAUNCH_AD_T(DT, 64); else LAUNCH_AD_T(DT, 128); } while (0)
@@ -3787,6 +3795,7 @@ int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long lo
 #undef LAUNCH_AD_T
 #undef LAUNCH_AD_P
 #undef LAUNCH_AD
+#undef LAUNCH_AD_
     BZ_HIP(hipGetLastError());
     return BZ_OK;
   }
@@ -3794,8 +3803,9 @@ int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long lo
   const int CS = attn_oproj_plan(a, L, NW);
   if (CS <= 0) BZ_FAIL(BZ_E_INVALID, "attn+o_proj fusion does not apply to this shape");
   const int TPW = (L.N / 64) / (CS * (NW > 8 ? 8 : NW));
-#define LAUNCH_AO(DT, T, W_, PG) BZ_LAUNCH("attn+o_proj", L.algo_bytes, (k_attn2<DT, 1, T, W_, PG>), dim3(a.nq * CS), dim3(W_ * 64), attn2_smem(W_), s, a, \
+#define LAUNCH_AO_(DT, T, W_, PG, WN) BZ_LAUNCH("attn+o_proj", L.algo_bytes, (k_attn2<DT, 1, T, W_, PG, 128, WN>), dim3(a.nq * CS), dim3(W_ * 64), attn2_smem(W_), s, a, \
     (const uint4*)L.w, (const __half*)L.scales, (const unsigned char*)L.zeros, L.bias, CS, acc)
+#define LAUNCH_AO(DT, T, W_, PG) do { if (a.window > 0) LAUNCH_AO_(DT, T, W_, PG, 1); else LAUNCH_AO_(DT, T, W_, PG, 0); } while (0)
 #define LAUNCH_AO_W(DT, T, PG) do { if (NW == 8) LAUNCH_AO(DT, T, 8, PG); else LAUNCH_AO(DT, T, 4, PG); } while (0)
 #define LAUNCH_AO_P(DT, T) do { if (a.kv.paged) LAUNCH_AO_W(DT, T, 1); else LAUNCH_AO_W(DT, T, 0); } while (0)
 #define LAUNCH_AO_T(DT) do { if (TPW == 1) LAUNCH_AO_P(DT, 1); else LAUNCH_AO_P(DT, 2); } while (0)
@@ -3806,6 +3816,7 @@ int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long lo
 #undef LAUNCH_AO_W
 #undef LAUNCH_AO_T
 #undef LAUNCH_AO
+#undef LAUNCH_AO_
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
@@ -3834,7 +3845,7 @@ __host__ __device__ __forceinline__ int att_split_len(int len) {
   return spl;
 }
 
-template <int KVDT, int PAGED, int REP>
+template <int KVDT, int PAGED, int REP, int WIN = 0>   // WIN: sliding window -- the slices are laid over [lo, len), not [0, len)
 __global__ __launch_bounds__(REP == 8 ? 512 : 256) void k_attn_split(AttnArgs a, int nsplit, float* __restrict__ ws) {
   constexpr int HD = 128, half = 64, NW = REP == 8 ? 8 : 4, NTH = NW * 64, PW = 128 / NW, NL = PW / 4;
   __shared__ __attribute__((aligned(16))) unsigned q2[REP][64];
@@ -3868,8 +3879,9 @@ __global__ __launch_bounds__(REP == 8 ? 512 : 256) void k_attn_split(AttnArgs a,
     for (int z = blockIdx.x * NTH + tid; z < a.zero_n; z += gridDim.x * NTH) a.zero_buf[z] = 0;
   const int pos = __builtin_amdgcn_readfirstlane(pos_v);
   const int len = pos + 1, pmax = pos > 0 ? pos - 1 : 0;
-  const int SPL = att_split_len(len);
-  const int p0 = s * SPL;
+  const int lo = WIN ? att_lo(len, a.window) : 0;
+  const int SPL = att_split_len(len - lo);
+  const int p0 = lo + s * SPL;
   if (p0 >= len) return;                    // split beyond the context (the grid covers the capacity)
   const int p1 = min(p0 + SPL, len);
   const bool owner = p1 == len;             // this block's range holds the new position
@@ -4051,17 +4063,18 @@ __device__ __forceinline__ void att_merge_512(const float* __restrict__ ws, int 
   if (tid < 128) outh[tid] = round_act(((osum[0][tid] + osum[1][tid]) + (osum[2][tid] + osum[3][tid])) / L, act);
 }
 
+template <int WIN>
 __global__ __launch_bounds__(512) void k_attn_merge(AttnArgs a, const float* __restrict__ ws, int nsplit) {
   __shared__ float wS[128], red[16], osum[4][128], outh[128];
   const int hq = blockIdx.x;
-  const int len = a.pos[0] + 1, SPL = att_split_len(len);
-  const int ns = (len + SPL - 1) / SPL;
+  const int len = a.pos[0] + 1, wl = len - (WIN ? att_lo(len, a.window) : 0), SPL = att_split_len(wl);   // the slices k_attn_split<.., WIN> wrote
+  const int ns = (wl + SPL - 1) / SPL;
   att_merge_512(ws, hq, nsplit, ns, a.act, wS, red, osum, outh);
   __syncthreads();
   if (threadIdx.x < 128) a.out[(size_t)hq * 128 + threadIdx.x] = outh[threadIdx.x];
 }
 
-template <int TPW>
+template <int TPW, int WIN = 0>
 __global__ __launch_bounds__(512) void k_attn_merge_oproj(AttnArgs a, const float* __restrict__ ws, int nsplit, const uint4* __restrict__ W,
                                                           const __half* __restrict__ S, const unsigned char* __restrict__ Z,
                                                           const float* __restrict__ bias, int CS, long long* acc) {
@@ -4095,8 +4108,8 @@ __global__ __launch_bounds__(512) void k_attn_merge_oproj(AttnArgs a, const floa
   }
   if (a.zero_buf)
     for (int z = blockIdx.x * 512 + tid; z < a.zero_n; z += gridDim.x * 512) a.zero_buf[z] = 0;
-  const int len = __builtin_amdgcn_readfirstlane(pos_v) + 1, SPL = att_split_len(len);
-  const int ns = (len + SPL - 1) / SPL;
+  const int len = __builtin_amdgcn_readfirstlane(pos_v) + 1, wl = len - (WIN ? att_lo(len, a.window) : 0), SPL = att_split_len(wl);
+  const int ns = (wl + SPL - 1) / SPL;
   att_merge_512(ws, hq, nsplit, ns, a.act, wS, red, osum, outh);
   __syncthreads();
   quant_x128<512>(outh, HD, xpl, gpar);
@@ -4127,7 +4140,8 @@ size_t bzk_attn_split_ws_bytes(int nq) { return (size_t)nq * 128 * ATT_PSTRIDE *
 int bzk_attn_split(hipStream_t s, const AttnArgs& a, int nsplit, float* ws) {
   if (!bzk_attn_split_ok(a) || nsplit < 1 || nsplit > ATT_MAX_SPLITS) BZ_FAIL(BZ_E_INVALID, "split attention does not apply to this shape");
   const int rep = a.nq / a.nkv;
-#define LAUNCH_SP(DT, PG, R) BZ_LAUNCH("attn_split", 0.0, (k_attn_split<DT, PG, R>), dim3(a.nkv * nsplit), dim3(R == 8 ? 512 : 256), 0, s, a, nsplit, ws)
+#define LAUNCH_SP_(DT, PG, R, WN) BZ_LAUNCH("attn_split", 0.0, (k_attn_split<DT, PG, R, WN>), dim3(a.nkv * nsplit), dim3(R == 8 ? 512 : 256), 0, s, a, nsplit, ws)
+#define LAUNCH_SP(DT, PG, R) do { if (a.window > 0) LAUNCH_SP_(DT, PG, R, 1); else LAUNCH_SP_(DT, PG, R, 0); } while (0)
 #define LAUNCH_SP_R(DT, PG) do { if (rep == 1) LAUNCH_SP(DT, PG, 1); else if (rep == 2) LAUNCH_SP(DT, PG, 2); else if (rep == 4) LAUNCH_SP(DT, PG, 4); \
                                  else LAUNCH_SP(DT, PG, 8); } while (0)
 #define LAUNCH_SP_P(DT) do { if (a.kv.paged) LAUNCH_SP_R(DT, 1); else LAUNCH_SP_R(DT, 0); } while (0)
@@ -4135,11 +4149,13 @@ int bzk_attn_split(hipStream_t s, const AttnArgs& a, int nsplit, float* ws) {
 #undef LAUNCH_SP_P
 #undef LAUNCH_SP_R
 #undef LAUNCH_SP
+#undef LAUNCH_SP_
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
 int bzk_attn_merge(hipStream_t s, const AttnArgs& a, const float* ws, int nsplit) {
-  BZ_LAUNCH("attn_merge", 0.0, k_attn_merge, dim3(a.nq), dim3(512), 0, s, a, ws, nsplit);
+  if (a.window > 0) BZ_LAUNCH("attn_merge", 0.0, k_attn_merge<1>, dim3(a.nq), dim3(512), 0, s, a, ws, nsplit);
+  else BZ_LAUNCH("attn_merge", 0.0, k_attn_merge<0>, dim3(a.nq), dim3(512), 0, s, a, ws, nsplit);
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
@@ -4149,40 +4165,48 @@ int bzk_attn_merge_oproj(hipStream_t s, const AttnArgs& a, const float* ws, int 
   const int CS = attn_oproj_plan(a, L, NW);
   if (CS <= 0 || NW != 8) BZ_FAIL(BZ_E_INVALID, "attn merge + o_proj fusion does not apply to this shape");
   const int TPW = (L.N / 64) / (CS * 8);
-#define LAUNCH_MO(T) BZ_LAUNCH("attn_merge+o_proj", L.algo_bytes, (k_attn_merge_oproj<T>), dim3(a.nq * CS), dim3(512), 0, s, a, ws, nsplit, \
+#define LAUNCH_MO_(T, WN) BZ_LAUNCH("attn_merge+o_proj", L.algo_bytes, (k_attn_merge_oproj<T, WN>), dim3(a.nq * CS), dim3(512), 0, s, a, ws, nsplit, \
     (const uint4*)L.w, (const __half*)L.scales, (const unsigned char*)L.zeros, L.bias, CS, acc)
+#define LAUNCH_MO(T) do { if (a.window > 0) LAUNCH_MO_(T, 1); else LAUNCH_MO_(T, 0); } while (0)
   if (TPW == 1) LAUNCH_MO(1); else LAUNCH_MO(2);
 #undef LAUNCH_MO
+#undef LAUNCH_MO_
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
 
 int bzk_attn_decode(hipStream_t s, const AttnArgs& a) {
   const size_t smem = (size_t)(3 * a.hd + 8 + 256 * (a.hd + 4)) * 4;
-#define LAUNCH_ATT(HD, DT) BZ_LAUNCH("attn_decode", 0.0, (k_attn_decode<HD, DT>), dim3(a.nq), dim3(256), smem, s, a)
+#define LAUNCH_ATT_(HD, DT, WN) BZ_LAUNCH("attn_decode", 0.0, (k_attn_decode<HD, DT, WN>), dim3(a.nq), dim3(256), smem, s, a)
+#define LAUNCH_ATT(HD, DT) do { if (a.window > 0) LAUNCH_ATT_(HD, DT, 1); else LAUNCH_ATT_(HD, DT, 0); } while (0)
 #define LAUNCH_ATT_DT(HD) do { if (a.kv.dtype == BZ_F16) LAUNCH_ATT(HD, BZ_F16); else if (a.kv.dtype == BZ_BF16) LAUNCH_ATT(HD, BZ_BF16); \
                                else LAUNCH_ATT(HD, BZ_F32); } while (0)
   static const bool no_a64 = getenv("BZ_NO_ATTN2_HD64") != nullptr;
   if ((a.hd == 128 || (a.hd == 64 && a.rope_cur != nullptr && !no_a64)) && a.kv.dtype != BZ_F32) {
     // the 8-wave lane = (row, 8-element piece) kernel: head_dim 128, and 64 (Llama-3.2-1B) with 8 rows per wave-wide load
-#define LAUNCH_A2(DT, PG, HDV) BZ_LAUNCH("attn_decode", 0.0, (k_attn2<DT, 0, 1, 8, PG, HDV>), dim3(a.nq), dim3(512), attn2_smem(8), s, a, (const uint4*)nullptr, \
+#define LAUNCH_A2_(DT, PG, HDV, WN) BZ_LAUNCH("attn_decode", 0.0, (k_attn2<DT, 0, 1, 8, PG, HDV, WN>), dim3(a.nq), dim3(512), attn2_smem(8), s, a, (const uint4*)nullptr, \
     (const __half*)nullptr, (const unsigned char*)nullptr, (const float*)nullptr, 1, (long long*)nullptr)
+#define LAUNCH_A2(DT, PG, HDV) do { if (a.window > 0) LAUNCH_A2_(DT, PG, HDV, 1); else LAUNCH_A2_(DT, PG, HDV, 0); } while (0)
 #define LAUNCH_A2_P(DT, HDV) do { if (a.kv.paged) LAUNCH_A2(DT, 1, HDV); else LAUNCH_A2(DT, 0, HDV); } while (0)
 #define LAUNCH_A2_H(DT) do { if (a.hd == 128) LAUNCH_A2_P(DT, 128); else LAUNCH_A2_P(DT, 64); } while (0)
     if (a.kv.dtype == BZ_F16) LAUNCH_A2_H(BZ_F16); else LAUNCH_A2_H(BZ_BF16);
 #undef LAUNCH_A2_H
 #undef LAUNCH_A2_P
 #undef LAUNCH_A2
+#undef LAUNCH_A2_
   }
   else if (a.hd == 128 && a.kv.dtype == BZ_F32 && a.rope_cur != nullptr && getenv("BZ_NO_ATTN_F32") == nullptr) {
-    if (a.kv.paged) BZ_LAUNCH("attn_decode", 0.0, (k_attn2f<1, 0>), dim3(a.nq), dim3(512), 0, s, a, (const uint4*)nullptr, (const uint4*)nullptr, (const float*)nullptr, 1, (long long*)nullptr);
-    else BZ_LAUNCH("attn_decode", 0.0, (k_attn2f<0, 0>), dim3(a.nq), dim3(512), 0, s, a, (const uint4*)nullptr, (const uint4*)nullptr, (const float*)nullptr, 1, (long long*)nullptr);
+#define LAUNCH_A2F(PG, WN) BZ_LAUNCH("attn_decode", 0.0, (k_attn2f<PG, 0, WN>), dim3(a.nq), dim3(512), 0, s, a, (const uint4*)nullptr, (const uint4*)nullptr, (const float*)nullptr, 1, (long long*)nullptr)
+    if (a.window > 0) { if (a.kv.paged) LAUNCH_A2F(1, 1); else LAUNCH_A2F(0, 1); }
+    else { if (a.kv.paged) LAUNCH_A2F(1, 0); else LAUNCH_A2F(0, 0); }
+#undef LAUNCH_A2F
   }
   else if (a.hd == 64) LAUNCH_ATT_DT(64);
   else if (a.hd == 128) LAUNCH_ATT_DT(128);
   else BZ_FAIL(BZ_E_UNSUPPORTED, "head_dim %d unsupported (64 and 128 are built)", a.hd);
 #undef LAUNCH_ATT_DT
 #undef LAUNCH_ATT
+#undef LAUNCH_ATT_
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }

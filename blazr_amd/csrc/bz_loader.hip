@@ -326,6 +326,19 @@ int hf_config_to_pod(const JVal& j, bz_model_config* c, QuantInfo* q) {
   c->max_seq_len = (int)j.i64("max_position_embeddings", 4096);
   c->rms_eps = (float)j.f64("rms_norm_eps", 1e-5);
   c->rope_theta = (float)j.f64("rope_theta", 10000.0);
+  {
+    // sliding_window: integer or null (Mistral v0.2+ ships null = full attention).  Qwen2 ships a window next to use_sliding_window = false, and with it
+    // true windows only the layers >= max_window_layers: that layer split is not a scheme the config struct carries, so anything but "every layer" is
+    // window off.  sliding_window_pattern n (Gemma3; Gemma2 alternates without naming it): every n-th layer is global.
+    long long w = j.i64("sliding_window", 0);
+    if (j.get("use_sliding_window") && !j.boolean("use_sliding_window", false)) w = 0;
+    if (j.get("use_sliding_window") && j.get("max_window_layers") && j.i64("max_window_layers", 0) > 0) w = 0;
+    if (w > 0 && w < (1ll << 30)) {
+      c->sliding_window = (int)w;
+      const long long pat = j.i64("sliding_window_pattern", lower.find("gemma2") != std::string::npos ? 2 : 0);
+      c->sliding_window_pattern = pat > 1 && pat < (1 << 20) ? (int)pat : 0;
+    }
+  }
   if (const JVal* rs = j.get("rope_scaling")) {
     if (rs->t == JVal::OBJ) {   // safetensors/config.rs:83-95
       std::string ty = rs->str("rope_type", rs->str("type", "llama3").c_str());
@@ -639,6 +652,10 @@ int gguf_config(const Gguf& g, bz_model_config* c, std::string* arch_out) {
   c->n_kv_heads = g.u32(arch + ".attention.head_count_kv", &v) ? (int)v : c->n_heads;
   c->head_dim = g.u32(arch + ".attention.key_length", &v) ? (int)v : (c->n_heads ? c->hidden / c->n_heads : 0);
   c->rope_theta = g.f32(arch + ".rope.freq_base", &f) ? (float)f : 10000.0f;
+  if (g.u32(arch + ".attention.sliding_window", &v) && v > 0 && v < (1ll << 30)) {
+    c->sliding_window = (int)v;
+    c->sliding_window_pattern = arch == "gemma2" ? 2 : 0;   // llama.cpp: gemma2 alternates windowed / global layers without a key for it
+  }
   if (g.u32(arch + ".attention.kv_lora_rank", &v)) {          // gguf.rs:188-196: MLA detection
     c->arch = BZ_ARCH_DEEPSEEK2; c->mla_kv_lora_rank = (int)v;
     c->mla_q_lora_rank = g.u32(arch + ".attention.q_lora_rank", &v) ? (int)v : 0;

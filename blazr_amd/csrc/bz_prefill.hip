@@ -253,12 +253,15 @@ __device__ __forceinline__ void ld_row8(const void* base, size_t off, float (&o)
 // EXACT: the oracle's arithmetic (orc_attn_decode), which is also the decode kernels' (k_attn2): score = f32(sum_double q k) * scale, p = exp(score - max),
 // l = f32(sum_double p), out = f32(sum_double p v) / l (IEEE division).  Products of 16-bit values (and of an f32 weight with one) are exact in double and the
 // sums are order-independent to ~1e-16, so a prompt row's attention output is the same bits as the decode step's.  (Non-exact form: f32 FMAs.)
-template <int DT, int KVDT, int REP, bool EXACT>
+// WIN: sliding window of `window` keys -- the row walks keys [lo, len), lo = att_lo(len, window), and its score buffer holds len - lo <= window entries, so
+// what limits a prompt is the window, not the context.
+template <int DT, int KVDT, int REP, bool EXACT, bool WIN = false>
 __global__ __launch_bounds__(256) void k_pf_attn(const float* qkv, int nq, int nkv, int hd, int pos0, int act, KvView kv, int layer, float scale, void* out16,
-                                                const int* row_pos, int table_stride) {
+                                                const int* row_pos, int table_stride, int window) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   typedef typename std::conditional<EXACT, double, float>::type acc_t;
   const int s = blockIdx.x, kvh = blockIdx.y, len = (row_pos ? row_pos[s] : pos0 + s) + 1;
+  const int lo = WIN ? att_lo(len, window) : 0, wl = len - lo;   // sc is indexed from lo: [REP][wl]
   const int* btab = kv.block_table + (row_pos ? (size_t)s * table_stride : 0);   // decode batch: one block-table row per sequence
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int PR = hd >> 3, RPP = 256 / PR;              // lanes per row, rows per pass
@@ -276,7 +279,7 @@ __global__ __launch_bounds__(256) void k_pf_attn(const float* qkv, int nq, int n
     return (size_t)layer * kv.layer_stride + ((size_t)kvh * kv.cap + p) * kv.hd + 8 * c;
   };
   // ---- scores ----
-  for (int p0 = 0; p0 < len; p0 += 2 * RPP) {
+  for (int p0 = lo; p0 < len; p0 += 2 * RPP) {
     float k0[8], k1[8];
     const int pa = p0 + g, pb = p0 + RPP + g;
     ld_row8<DT, KVDT>(kv.k, row_off(min(pa, len - 1)), k0);
@@ -295,7 +298,7 @@ __global__ __launch_bounds__(256) void k_pf_attn(const float* qkv, int nq, int n
         else if (PR == 8) { d0 = grp_reduce<8, OpAdd>(d0); d1 = grp_reduce<8, OpAdd>(d1); }
         else for (int m = 1; m < PR; m <<= 1) { d0 += __shfl_xor(d0, m, 64); d1 += __shfl_xor(d1, m, 64); }
       }
-      if (c == 0) { if (pa < len) sc[h * len + pa] = (float)d0 * scale; if (pb < len) sc[h * len + pb] = (float)d1 * scale; }
+      if (c == 0) { if (pa < len) sc[h * wl + pa - lo] = (float)d0 * scale; if (pb < len) sc[h * wl + pb - lo] = (float)d1 * scale; }
     }
   }
   __syncthreads();
@@ -303,7 +306,7 @@ __global__ __launch_bounds__(256) void k_pf_attn(const float* qkv, int nq, int n
 #pragma unroll
   for (int h = 0; h < REP; h++) {
     float m = -INFINITY;
-    for (int p = tid; p < len; p += 256) m = fmaxf(m, sc[h * len + p]);
+    for (int p = lo + tid; p < len; p += 256) m = fmaxf(m, sc[h * wl + p - lo]);
     m = wave_max(m);
     if (lane == 0) red[h * 4 + wave] = (acc_t)m;
   }
@@ -312,7 +315,7 @@ __global__ __launch_bounds__(256) void k_pf_attn(const float* qkv, int nq, int n
   for (int h = 0; h < REP; h++) {
     const float m = fmaxf(fmaxf((float)red[h * 4], (float)red[h * 4 + 1]), fmaxf((float)red[h * 4 + 2], (float)red[h * 4 + 3]));
     acc_t sum = 0;
-    for (int p = tid; p < len; p += 256) { const float e = bz_expf(sc[h * len + p] - m); sc[h * len + p] = e; sum += (acc_t)e; }
+    for (int p = lo + tid; p < len; p += 256) { const float e = bz_expf(sc[h * wl + p - lo] - m); sc[h * wl + p - lo] = e; sum += (acc_t)e; }
     if constexpr (EXACT) sum = wave_sum_d(sum); else sum = wave_sum(sum);
     if (lane == 0) red[4 * REP + h * 4 + wave] = sum;
   }
@@ -323,14 +326,14 @@ __global__ __launch_bounds__(256) void k_pf_attn(const float* qkv, int nq, int n
   for (int h = 0; h < REP; h++)
 #pragma unroll
     for (int e = 0; e < 8; e++) acc[h][e] = 0;
-  for (int p0 = 0; p0 < len; p0 += 2 * RPP) {
+  for (int p0 = lo; p0 < len; p0 += 2 * RPP) {
     float v0[8], v1[8];
     const int pa = p0 + g, pb = p0 + RPP + g;
     ld_row8<DT, KVDT>(kv.v, row_off(min(pa, len - 1)), v0);
     ld_row8<DT, KVDT>(kv.v, row_off(min(pb, len - 1)), v1);
 #pragma unroll
     for (int h = 0; h < REP; h++) {
-      const acc_t w0 = pa < len ? (acc_t)sc[h * len + pa] : (acc_t)0, w1 = pb < len ? (acc_t)sc[h * len + pb] : (acc_t)0;
+      const acc_t w0 = pa < len ? (acc_t)sc[h * wl + pa - lo] : (acc_t)0, w1 = pb < len ? (acc_t)sc[h * wl + pb - lo] : (acc_t)0;
 #pragma unroll
       for (int e = 0; e < 8; e++) acc[h][e] += w0 * (acc_t)v0[e] + w1 * (acc_t)v1[e];
     }
@@ -368,9 +371,12 @@ template <int DT> __device__ __forceinline__ uint4 pack8(const float* v) {
   o.z = (unsigned)to16<DT>(v[4]) | ((unsigned)to16<DT>(v[5]) << 16); o.w = (unsigned)to16<DT>(v[6]) | ((unsigned)to16<DT>(v[7]) << 16);
   return o;
 }
-template <int DT, int HD, int REP, bool PAGED>
+// WIN: sliding window of `window` keys.  A query at position q sees keys (q - window, q]: the key tiles start at the 64-key tile that holds the window of the
+// workgroup's first query (tiles wholly below it are never loaded), a wave skips the tiles wholly below its own first query's window, and inside a tile the keys
+// below a query's window are masked like the keys above its position.
+template <int DT, int HD, int REP, bool PAGED, bool WIN = false>
 __global__ __launch_bounds__(256) void k_pf_attn_mfma(const float* __restrict__ qkv, int S, int nq, int nkv, int pos0, int act, KvView kv, int layer, float scale,
-                                                      unsigned short* __restrict__ out16) {
+                                                      unsigned short* __restrict__ out16, int window) {
   constexpr int HW = REP < 4 ? REP : 4, QT = 4 / HW, PR = HD / 8, PK = HD * 2 + 16, PV = 64 * 2 + 8, NC = HD / 16, NDB = HD / 32, KPT = PR / 4;
   __shared__ __attribute__((aligned(16))) unsigned char Ks[64 * PK];
   __shared__ __attribute__((aligned(16))) unsigned char Vt[HD * PV];
@@ -380,6 +386,8 @@ __global__ __launch_bounds__(256) void k_pf_attn_mfma(const float* __restrict__ 
   const int q0 = (wgt * QT + qt) * 32, qrow = min(q0 + r, S - 1), qpos = pos0 + q0 + r;
   const int kmax = pos0 + min(S, (wgt + 1) * 32 * QT);        // this workgroup's keys: [0, kmax)
   const int my_last = pos0 + min(q0 + 31, S - 1);             // last position any query of this wave attends to
+  const int kt_lo = WIN ? (att_lo(pos0 + wgt * QT * 32 + 1, window) & ~63) : 0;   // first key tile of the workgroup
+  const int my_lo = WIN ? att_lo(pos0 + q0 + 1, window) : 0;   // first key any query of this wave attends to
   uint4 qf[NC];
   {
     const float* qp = qkv + (size_t)qrow * (nq + 2 * nkv) * HD + (size_t)head * HD + 8 * h;
@@ -408,8 +416,8 @@ __global__ __launch_bounds__(256) void k_pf_attn_mfma(const float* __restrict__ 
 #pragma unroll
     for (int i = 0; i < 16; i++) o[d][i] = 0.f;
   float m = -INFINITY, l = 0.f;
-  PFA_GLOAD(0)
-  for (int kt0 = 0; kt0 < kmax; kt0 += 64) {
+  PFA_GLOAD(kt_lo)
+  for (int kt0 = kt_lo; kt0 < kmax; kt0 += 64) {
     __syncthreads();                                          // the previous tile's fragment reads are done
 #pragma unroll
     for (int i = 0; i < KPT; i++) {
@@ -424,7 +432,7 @@ __global__ __launch_bounds__(256) void k_pf_attn_mfma(const float* __restrict__ 
     }
     __syncthreads();
     { const int ktn = kt0 + 64 < kmax ? kt0 + 64 : kt0; PFA_GLOAD(ktn) }                  // lands under this tile's arithmetic (last tile: a redundant reload, never a branch around the loads -- under one, hipcc kept the prefetch registers in scratch)
-    if (kt0 <= my_last) {                                     // wave-uniform: later tiles are fully masked for this wave
+    if (kt0 <= my_last && (!WIN || kt0 + 63 >= my_lo)) {      // wave-uniform: later (WIN: and earlier) tiles are fully masked for this wave
       f32x16 st[2];
 #pragma unroll
       for (int kb = 0; kb < 2; kb++) {
@@ -442,11 +450,16 @@ __global__ __launch_bounds__(256) void k_pf_attn_mfma(const float* __restrict__ 
 #pragma unroll
         for (int i = 0; i < 16; i++) {
           const int kp = kt0 + 32 * kb + (i & 3) + 8 * (i >> 2) + 4 * h;
-          const float v = kp > qpos ? -INFINITY : st[kb][i] * scale;
+          const float v = (kp > qpos || (WIN && kp < att_lo(qpos + 1, window))) ? -INFINITY : st[kb][i] * scale;
           st[kb][i] = v; mx = fmaxf(mx, v);
         }
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float mn = fmaxf(m, mx);                          // finite: key 0 is visible to every query and sits in the first tile
+      // plain kernel: the maximum is finite, key 0 is visible to every query and sits in the first tile.  WIN: a wave's tiles start at its FIRST query's window, so
+      // a later query of the wave can find every key of an early tile below its own window: mn_ = -inf, and exp(m - mn_) would be exp(nan).  A finite stand-in
+      // makes alpha and every p of that tile 0 (l and o stay 0), and the next tile with a visible key resets m (alpha = exp(-1e30 - mn) = 0).  Every query sees its
+      // own key in a tile the wave processes, so l > 0 at the end.
+      const float mn_ = fmaxf(m, mx);
+      const float mn = (WIN && mn_ == -INFINITY) ? -1e30f : mn_;
       const float alpha = bz_expf(m - mn);
       float ps = 0.f;
 #pragma unroll
@@ -1394,7 +1407,7 @@ size_t bzk_pf_attn_smem(int nq, int nkv, int hd, int len, bool exact) {
   return (size_t)(8 * REP + RPP * REP * hd) * (exact ? 8 : 4) + (size_t)REP * len * 4 + 64;
 }
 int bzk_pf_attn(hipStream_t s, int dt, const float* qkv, int S, int nq, int nkv, int hd, int pos0, int act, const KvView& kv, int layer, void* out16,
-                const int* row_pos, int table_stride, int max_len, bool exact) {
+                const int* row_pos, int table_stride, int max_len, bool exact, int window) {
   const int REP = nq / nkv;
   if (hd % 8 || hd > 256 || (256 % (hd / 8)) || (REP != 1 && REP != 2 && REP != 4 && REP != 8) || kv.dtype != dt)
     BZ_FAIL(BZ_E_UNSUPPORTED, "prefill attention: head_dim %d / group size %d / cache dtype unsupported", hd, REP);
@@ -1403,30 +1416,34 @@ int bzk_pf_attn(hipStream_t s, int dt, const float* qkv, int S, int nq, int nkv,
     const int HW = REP < 4 ? REP : 4, QT = 4 / HW;
     const dim3 grid((S + 32 * QT - 1) / (32 * QT), nkv, REP / HW);
     const double flops = 4.0 * nq * hd * ((double)S * pos0 + 0.5 * (double)S * S);
-#define LAUNCH_PFM(DT, HD, R) do { if (kv.paged) BZ_LAUNCH("pf_attn_mfma", flops, (k_pf_attn_mfma<DT, HD, R, true>), grid, dim3(256), 0, s, qkv, S, nq, nkv, pos0, act, kv, layer, scale_m, (unsigned short*)out16); \
-                                   else BZ_LAUNCH("pf_attn_mfma", flops, (k_pf_attn_mfma<DT, HD, R, false>), grid, dim3(256), 0, s, qkv, S, nq, nkv, pos0, act, kv, layer, scale_m, (unsigned short*)out16); } while (0)
+#define LAUNCH_PFM_(DT, HD, R, PG, WN) BZ_LAUNCH("pf_attn_mfma", flops, (k_pf_attn_mfma<DT, HD, R, PG, WN>), grid, dim3(256), 0, s, qkv, S, nq, nkv, pos0, act, kv, layer, scale_m, (unsigned short*)out16, window)
+#define LAUNCH_PFM(DT, HD, R) do { if (window > 0) { if (kv.paged) LAUNCH_PFM_(DT, HD, R, true, true); else LAUNCH_PFM_(DT, HD, R, false, true); } \
+                                   else { if (kv.paged) LAUNCH_PFM_(DT, HD, R, true, false); else LAUNCH_PFM_(DT, HD, R, false, false); } } while (0)
 #define LAUNCH_PFM_R(DT, HD) do { if (REP == 1) LAUNCH_PFM(DT, HD, 1); else if (REP == 2) LAUNCH_PFM(DT, HD, 2); else if (REP == 4) LAUNCH_PFM(DT, HD, 4); else LAUNCH_PFM(DT, HD, 8); } while (0)
 #define LAUNCH_PFM_H(DT) do { if (hd == 64) LAUNCH_PFM_R(DT, 64); else LAUNCH_PFM_R(DT, 128); } while (0)
     if (dt == BZ_F16) LAUNCH_PFM_H(BZ_F16); else LAUNCH_PFM_H(BZ_BF16);
 #undef LAUNCH_PFM_H
 #undef LAUNCH_PFM_R
 #undef LAUNCH_PFM
+#undef LAUNCH_PFM_
     BZ_HIP(hipGetLastError());
     return BZ_OK;
   }
-  const int ctx = row_pos ? max_len : pos0 + S;
+  const int ctx_full = row_pos ? max_len : pos0 + S, ctx = window > 0 ? std::min(ctx_full, window) : ctx_full;   // a row's score buffer: its window
   const size_t smem = bzk_pf_attn_smem(nq, nkv, hd, ctx, exact);
   if (smem > 160 * 1024) BZ_FAIL(BZ_E_UNSUPPORTED, "prefill attention: context %d too long for this kernel", ctx);
   const float scale = div_rn(1.0f, sqrt_rn((float)hd));
-#define LAUNCH_PFA(DT, R, EX) do { \
+#define LAUNCH_PFA_(DT, R, EX, WN) do { \
     static bool attr_done = false; \
-    if (!attr_done) { BZ_HIP(hipFuncSetAttribute((const void*)k_pf_attn<DT, DT, R, EX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_done = true; } \
-    hipLaunchKernelGGL((k_pf_attn<DT, DT, R, EX>), dim3(S, nkv), dim3(256), smem, s, qkv, nq, nkv, hd, pos0, act, kv, layer, scale, out16, row_pos, table_stride); } while (0)
+    if (!attr_done) { BZ_HIP(hipFuncSetAttribute((const void*)k_pf_attn<DT, DT, R, EX, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_done = true; } \
+    hipLaunchKernelGGL((k_pf_attn<DT, DT, R, EX, WN>), dim3(S, nkv), dim3(256), smem, s, qkv, nq, nkv, hd, pos0, act, kv, layer, scale, out16, row_pos, table_stride, window); } while (0)
+#define LAUNCH_PFA(DT, R, EX) do { if (window > 0) LAUNCH_PFA_(DT, R, EX, true); else LAUNCH_PFA_(DT, R, EX, false); } while (0)
 #define LAUNCH_PFA_R(DT, EX) do { if (REP == 1) LAUNCH_PFA(DT, 1, EX); else if (REP == 2) LAUNCH_PFA(DT, 2, EX); else if (REP == 4) LAUNCH_PFA(DT, 4, EX); else LAUNCH_PFA(DT, 8, EX); } while (0)
   if (exact) { if (dt == BZ_F16) LAUNCH_PFA_R(BZ_F16, true); else if (dt == BZ_F32) LAUNCH_PFA_R(BZ_F32, true); else LAUNCH_PFA_R(BZ_BF16, true); }
   else { if (dt == BZ_F16) LAUNCH_PFA_R(BZ_F16, false); else if (dt == BZ_F32) LAUNCH_PFA_R(BZ_F32, false); else LAUNCH_PFA_R(BZ_BF16, false); }
 #undef LAUNCH_PFA_R
 #undef LAUNCH_PFA
+#undef LAUNCH_PFA_
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }

@@ -112,6 +112,9 @@ def make_config(cfg):
     """synth/HF-style config dict -> bz_model_config POD."""
     c = L.ModelConfig()
     c.abi_version = L.ABI_VERSION
+    # sliding-window attention (Llama family only; bz_model_create refuses it on the other architectures): 0 / absent = full attention
+    c.sliding_window = int(cfg.get("sliding_window") or 0)
+    c.sliding_window_pattern = int(cfg.get("sliding_window_pattern") or 0)
     if cfg.get("arch") == "mamba2":
         # SsmConfig (loader/gguf.rs:219-262)
         c.arch = L.ARCH_MAMBA2

@@ -83,7 +83,12 @@ typedef struct {
    * defaults): 0 means default (beta_fast 32, beta_slow 1, attention_factor 0.1 ln(factor) + 1).  cos / sin are multiplied by the attention factor.
    * mla_softmax_mscale (DeepSeek-V2 YaRN, mscale_all_dim): the MLA softmax scale is multiplied by its square; 0 = 1. */
   float   rope_beta_fast, rope_beta_slow, rope_attn_factor, mla_softmax_mscale;
-  int32_t reserved[4];
+  /* BZ_ARCH_LLAMA only (AttentionConfig.sliding_window, config/blazr.rs:171): sliding_window W > 0 = the query at position p attends to positions
+   * max(0, p - W + 1) .. p (W keys including itself; HF Mistral semantics), 0 = full attention.  sliding_window_pattern n > 1 = every n-th layer
+   * (l % n == n - 1) is global and the others are windowed (Gemma2: 2); 0 / 1 = every layer windowed.  Both took formerly reserved slots, where zero
+   * means what it always meant.  The KV cache stays full length: rows below the window are not read. */
+  int32_t sliding_window, sliding_window_pattern;
+  int32_t reserved[2];
 } bz_model_config;
 
 /* ---- errors / device ------------------------------------------------------------------------------- */
