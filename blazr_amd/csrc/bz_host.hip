@@ -842,6 +842,9 @@ extern "C" int bz_model_finalize(bz_model* m) {
   if (m->cfg.arch == BZ_ARCH_DEEPSEEK2) return finalize_dsv2(m);
   const bz_model_config& c = m->cfg;
   const int H = c.hidden, nq = c.n_heads, nkv = c.n_kv_heads, hd = c.head_dim, I = c.inter, V = c.vocab;
+  // the attention kernels exist for head_dim 64 and 128 only (bzk_attn_decode): refused here, not at the first forward after the q/k/v launches
+  // (Llama family; the `head_dim` of a DeepSeek-V2 model is the width of its latent cache and never reaches this point)
+  if (hd != 64 && hd != 128) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: head_dim %d is not built (the attention kernels exist for head_dim 64 and 128)", hd);
   char nm[256];
   m->layers.resize(c.n_layers);
   for (int l = 0; l < c.n_layers; l++) {
