@@ -94,6 +94,15 @@ class GenStats(C.Structure):
                 ("itl_p99_ms", C.c_double), ("itl_max_ms", C.c_double), ("decode_tok_per_s", C.c_double)]
 
 
+class SpecConfig(C.Structure):
+    _fields_ = [("num_speculative_tokens", C.c_int32), ("adaptive_depth", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class SpecStats(C.Structure):
+    _fields_ = [("iterations", C.c_int64), ("drafted_tokens", C.c_int64), ("accepted_tokens", C.c_int64), ("rejected_tokens", C.c_int64),
+                ("verify_path", C.c_int32), ("final_depth", C.c_int32), ("draft_ms", C.c_double), ("verify_ms", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/blazr_hip.h declares
 P = C.c_void_p
 SYMBOLS = {
@@ -215,6 +224,11 @@ SYMBOLS = {
     "bz_device_grammar_free": (C.c_int, [P]),
     "bz_grammar_dfa_mask_logits": (C.c_int, [P, P, C.c_int64, C.c_int64, P, P]),
     "bz_generate_grammar": (C.c_int, [P, P, C.c_int, C.POINTER(GenConfig), P, P, P, C.c_int64, P, C.POINTER(GenStats)]),
+    "bz_spec_accept": (C.c_int, [P, P, C.c_int64, C.c_int64, P, P]),
+    "bz_forward_kv_verify": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.POINTER(C.c_int32), P, C.POINTER(C.c_int32)]),
+    "bz_speculative_create": (C.c_int, [P, P, C.POINTER(SpecConfig), C.POINTER(P)]),
+    "bz_speculative_free": (C.c_int, [P]),
+    "bz_generate_speculative": (C.c_int, [P, P, C.c_int, C.POINTER(GenConfig), P, C.POINTER(GenStats), C.POINTER(SpecStats)]),
 }
 
 

@@ -333,6 +333,9 @@ struct bz_model {
   float* scratch = nullptr;
   long long* tok_tmp = nullptr;
   int* pos_tmp = nullptr;
+  // speculative verify workspace (ensure_spec_ws): logits [16][vocab], argmax partials [16][sp_nb], argmax [16], record [17]
+  float* sp_logits = nullptr; float* sp_pval = nullptr; int* sp_pidx = nullptr; int sp_nb = 0;
+  long long* sp_argmax = nullptr; long long* sp_record = nullptr;
   size_t resident = 0, per_token = 0;
 };
 
@@ -1952,9 +1955,12 @@ static int prefill_exact(const bz_model* m, int n, bool decode_batch) {
 // tokens [S] at positions pos0 .. pos0+S-1; `slots` (paged only): device i32 [S].  Logits of the last row (or all rows) -> logits_out.
 // per-row context of a decode batch: row r is its own sequence (position row_pos[r], block-table row r); nullptr row_pos = one prompt
 struct RowsCtx { const int* row_pos = nullptr; int table_stride = 0; int max_len = 0; };
+// speculative verify (llama_verify_rows): the head of all S <= 16 rows is the multi-row exact lm_head (bz_speculative.hip), which streams the matrix once per
+// 8 rows and leaves per-row argmax partials in m->sp_pval / m->sp_pidx; logits [S][vocab] device
+struct SpecHeadOut { float* logits; };
 
 static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvView& view, int pos0, const int* slots, bool all, bz_tensor* logits_out,
-                         const RowsCtx& rc = RowsCtx()) {
+                         const RowsCtx& rc = RowsCtx(), const SpecHeadOut* sh = nullptr) {
   const bz_model_config& c = m->cfg;
   hipStream_t st = step_stream(m);     // (a batched decode graph records this function on its capture stream)
   const int H = c.hidden, I = c.inter, nq = c.n_heads, nkv = c.n_kv_heads, hd = c.head_dim, act = c.act_dtype, dt = c.act_dtype;
@@ -1990,6 +1996,14 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
     // head.  Several rows wanted (all_logits, decode batch) and a dense lm_head in the activation dtype: final norm rows + one MFMA GEMM that
     // streams the lm_head once; otherwise the decode lm_head GEMV per row (final norm fused as its prologue)
     const LinearDev& LH = m->lm_head.parts[0];
+    if (sh) {
+      for (int r0 = 0; r0 < n; r0 += 8) {
+        SpecHeadRows hr{m->pf_h + (size_t)r0 * H, prev ? prev + (size_t)r0 * H : nullptr, H, m->final_norm, c.rms_eps, H, act};
+        BZ_TRY(bzk_spec_head(st, LH, hr, std::min(8, n - r0), sh->logits + (size_t)(s0 + r0) * c.vocab, m->sp_pval + (size_t)(s0 + r0) * m->sp_nb,
+                             m->sp_pidx + (size_t)(s0 + r0) * m->sp_nb, m->sp_nb));
+      }
+      continue;
+    }
     if (all && n > 1 && !exact && act != BZ_F32 && LH.wdt == act && LH.K % 64 == 0 && logits_out->nbytes >= (size_t)(s0 + n) * c.vocab * 4) {
       BZ_TRY(bzk_pf_norm(st, dt, m->pf_h, prev, m->final_norm, n, H, c.rms_eps, act, m->pf_x16));
       BZ_TRY(bzk_gemm_nt(st, act, m->pf_x16, LH.w, LH.bias, n, c.vocab, H, act, (float*)logits_out->ptr + (size_t)s0 * c.vocab, m->pf_ws, m->pf_ws_bytes));
@@ -3375,6 +3389,282 @@ done:
   bz_kv_free(kv); bz_paged_kv_free(pkv); bz_ssm_state_free(ssm); bz_mirostat_free(mstate); bz_device_grammar_free(dg);
   return rc;
 #undef GEN_TRY
+  BZ_API_END
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// speculative decoding (reference: engine/generate_text.rs:41-44,61-136, engine/speculative.rs:99-125, config/inference.rs:197-208):
+// a draft model proposes k tokens, the target verifies [t, d1 .. dk] in ONE pass whose rows are the decode step's bits, acceptance is decided on the device
+// ---------------------------------------------------------------------------------------------------------
+static bool spec_head_eligible(const bz_model* m) {
+  return m->lm_head.parts.size() == 1 && !m->lm_head.fix_out && bzk_spec_head_ok(m->lm_head.parts[0], m->cfg.act_dtype, m->cfg.hidden);
+}
+static int ensure_spec_ws(bz_model* m) {
+  if (m->sp_record) return BZ_OK;
+  void* p;
+  m->sp_nb = spec_head_eligible(m) ? bzk_spec_head_blocks(m->lm_head.parts[0]) : 64;
+  BZ_TRY(dev_alloc(m, &p, (size_t)16 * m->cfg.vocab * 4)); m->sp_logits = (float*)p;
+  BZ_TRY(dev_alloc(m, &p, (size_t)16 * m->sp_nb * 4)); m->sp_pval = (float*)p;
+  BZ_TRY(dev_alloc(m, &p, (size_t)16 * m->sp_nb * 4)); m->sp_pidx = (int*)p;
+  BZ_TRY(dev_alloc(m, &p, 16 * 8)); m->sp_argmax = (long long*)p;
+  BZ_TRY(dev_alloc(m, &p, 17 * 8)); m->sp_record = (long long*)p;
+  return BZ_OK;
+}
+// the multi-row exact rows apply: f16 int4 model whose every projection has the multi-row form (prefill_exact == 1), the shapes the row kernels take (as
+// prefill_eligible), the exact attention's scores of position + R keys in LDS, and a head the multi-row lm_head takes
+static bool verify_fast_ok(const bz_model* m, int R, int position) {
+  const bz_model_config& c = m->cfg;
+  if (c.arch != BZ_ARCH_LLAMA || c.act_dtype != BZ_F16 || R > 16 || prefill_exact(m, R, false) != 1) return false;
+  if (c.hidden % 64 || (c.n_heads * c.head_dim) % 64 || c.inter % 64 || c.head_dim % 8 || 256 % (c.head_dim / 8)) return false;
+  const int rep = c.n_heads / c.n_kv_heads;
+  if (rep != 1 && rep != 2 && rep != 4 && rep != 8) return false;
+  if (bzk_pf_attn_smem(c.n_heads, c.n_kv_heads, c.head_dim, window_keys(c, position + R), true) > 160 * 1024) return false;
+  return spec_head_eligible(m);
+}
+
+// rows d_tok[0 .. R) at positions position .. position + R - 1 (1 <= R <= 16): logits [R][vocab] (device), m->sp_argmax [R], then the accept kernel over
+// (argmax, draft = d_tok + 1) -> m->sp_record; next_slot (nullable) receives the correction / bonus token.  Nothing is synchronised here; the caller
+// reads the record and sets kv->seq_len = position + n_accept + 1 (rows past it hold rejected tokens: no kernel reads them, the next forward overwrites them).
+// path: 1 = multi-row exact rows + multi-row lm_head, 0 = the decode step token by token
+static int llama_verify_rows(bz_model* m, const long long* d_tok, int R, bz_kv* kv, int position, float* logits, long long* next_slot, int* path) {
+  const bz_model_config& c = m->cfg;
+  hipStream_t st = m->dev->stream;
+  BZ_TRY(ensure_spec_ws(m));
+  BZ_TRY(kv_grow(kv, position + R));
+  const bool fast = verify_fast_ok(m, R, position);
+  BZ_TRACE("verify: R=%d position=%d path=%d", R, position, (int)fast);
+  if (fast) {
+    SpecHeadOut sh{logits};
+    BZ_TRY(prefill_dense(m, d_tok, R, view_of(kv), position, nullptr, true, nullptr, RowsCtx(), &sh));
+    BZ_TRY(bzk_spec_argmax_final(st, m->sp_pval, m->sp_pidx, m->sp_nb, R, m->sp_argmax));
+  } else {
+    for (int r = 0; r < R; r++) {
+      hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, m->pos_tmp, position + r);
+      StepIO io{};
+      io.kv = view_of(kv); io.d_tok = d_tok + r; io.d_pos = m->pos_tmp; io.att_positions = att_positions_for(position + r + 1); io.do_head = true;
+      FinalArgs fa{};
+      fa.tok_out = m->sp_argmax + r;
+      io.final_args = &fa;
+      BZ_TRY(llama_step(m, io));
+      BZ_HIP(hipMemcpyAsync(logits + (size_t)r * c.vocab, m->logits, (size_t)c.vocab * 4, hipMemcpyDeviceToDevice, st));
+    }
+  }
+  BZ_TRY(bzk_spec_accept(st, m->sp_argmax, d_tok + 1, R, m->sp_record, next_slot));
+  if (path) *path = fast ? 1 : 0;
+  return BZ_OK;
+}
+// the record's one trip to the host: an event behind the accept kernel, the copy on the copy stream (the path of bz_tensor_to_host_pipelined)
+static int spec_read_record(bz_device* d, const long long* rec, int n, long long* host) {
+  uint64_t ev;
+  BZ_TRY(bz_event_record(d, &ev));
+  std::lock_guard<std::mutex> dlock__(d->mu);
+  BZ_HIP(hipStreamWaitEvent(d->copy_stream, d->events[ev], 0));
+  BZ_HIP(hipMemcpyAsync(host, rec, (size_t)n * 8, hipMemcpyDeviceToHost, d->copy_stream));
+  BZ_HIP(hipStreamSynchronize(d->copy_stream));
+  return BZ_OK;
+}
+
+extern "C" int bz_spec_accept(bz_device* dev, const bz_tensor* logits, int64_t R, int64_t V, const bz_tensor* draft, bz_tensor* record) {
+  BZ_API_BEGIN
+  if (!dev || !logits || !record || R < 1 || R > 16 || V < 1 || V > 0x7fffffff) BZ_FAIL(BZ_E_INVALID, "spec_accept: bad argument (1 <= R <= 16)");
+  if (logits->dtype != BZ_F32 || logits->nbytes < (size_t)R * V * 4) BZ_FAIL(BZ_E_INVALID, "spec_accept: logits must be F32 [R,V]");
+  if (R > 1 && (!draft || draft->dtype != BZ_I64 || draft->nbytes < (size_t)(R - 1) * 8)) BZ_FAIL(BZ_E_INVALID, "spec_accept: draft must be I64 [R-1]");
+  if (record->dtype != BZ_I64 || record->nbytes < (size_t)(R + 1) * 8) BZ_FAIL(BZ_E_INVALID, "spec_accept: record must be I64 [R+1]");
+  std::lock_guard<std::mutex> dlock__(dev->mu);
+  BZ_HIP(hipSetDevice(dev->id));
+  // the device's 4 KiB scratch: 16 partials per row [16][16] values, [16][16] indices, then argmax [16]
+  const int nb = 16;
+  float* pval = dev->scratch; int* pidx = (int*)(dev->scratch + 256); long long* amax = (long long*)(dev->scratch + 512);
+  BZ_TRY(bzk_spec_row_partials(dev->stream, (const float*)logits->ptr, (int)R, V, pval, pidx, nb));
+  BZ_TRY(bzk_spec_argmax_final(dev->stream, pval, pidx, nb, (int)R, amax));
+  return bzk_spec_accept(dev->stream, amax, R > 1 ? (const long long*)draft->ptr : nullptr, (int)R, (long long*)record->ptr, nullptr);
+  BZ_API_END
+}
+
+extern "C" int bz_forward_kv_verify(bz_model* m, const bz_tensor* tokens, int R, bz_kv* kv, int position, bz_tensor* logits_out, int32_t* n_accept,
+                                    int64_t* tokens_out, int32_t* path) {
+  BZ_API_BEGIN
+  BZ_TRY(check_fwd(m, tokens, R));
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  if (m->cfg.arch != BZ_ARCH_LLAMA) BZ_FAIL(BZ_E_UNSUPPORTED, "forward_kv_verify: Llama-family models only (Mamba2 state rollback and the DeepSeek-V2 latent cache are not built)");
+  if (R > 16) BZ_FAIL(BZ_E_INVALID, "forward_kv_verify: R = %d rows (1..16)", R);
+  if (!kv || kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "forward_kv_verify: cache does not match the model");
+  if (position < 0 || position + R > m->cfg.max_seq_len) BZ_FAIL(BZ_E_INVALID, "forward_kv_verify: position %d + R %d exceeds max_seq_len %d", position, R, m->cfg.max_seq_len);
+  if (logits_out && (logits_out->dtype != BZ_F32 || logits_out->nbytes < (size_t)R * m->cfg.vocab * 4)) BZ_FAIL(BZ_E_INVALID, "forward_kv_verify: logits_out must be F32 [R,vocab]");
+  if (!n_accept || !tokens_out) BZ_FAIL(BZ_E_INVALID, "forward_kv_verify: n_accept / tokens_out required");
+  BZ_TRY(ensure_spec_ws(m));
+  int pth = 0;
+  BZ_TRY(llama_verify_rows(m, (const long long*)tokens->ptr, R, kv, position, logits_out ? (float*)logits_out->ptr : m->sp_logits, nullptr, &pth));
+  long long rec[17];
+  BZ_TRY(spec_read_record(m->dev, m->sp_record, R + 1, rec));
+  const int a = (int)rec[0];
+  if (a < 0 || a >= R) BZ_FAIL(BZ_E_INVALID, "forward_kv_verify: accept record out of range (%d)", a);
+  *n_accept = a;
+  for (int i = 0; i < R; i++) tokens_out[i] = i <= a ? rec[1 + i] : -1;
+  kv->seq_len = position + a + 1;
+  if (path) *path = pth;
+  return BZ_OK;
+  BZ_API_END
+}
+
+struct bz_speculative { bz_model* target = nullptr; bz_model* draft = nullptr; int k = 5; int adaptive = 0; };
+
+extern "C" int bz_speculative_create(bz_model* target, bz_model* draft, const bz_spec_config* sc, bz_speculative** out) {
+  BZ_API_BEGIN
+  if (!target || !draft || !out || !target->finalized || !draft->finalized) BZ_FAIL(BZ_E_INVALID, "speculative: target and draft must be finalized models");
+  for (const bz_model* mm : {target, draft})
+    if (mm->cfg.arch != BZ_ARCH_LLAMA)
+      BZ_FAIL(BZ_E_UNSUPPORTED, "speculative: the %s model is %s; only Llama-family models are built (Mamba2 needs state rollback, DeepSeek-V2 a latent-cache verify)",
+              mm == target ? "target" : "draft", mm->cfg.arch == BZ_ARCH_MAMBA2 ? "Mamba2" : "DeepSeek-V2");
+  if (target->dev != draft->dev) BZ_FAIL(BZ_E_INVALID, "speculative: target and draft must live on the same device handle");
+  if (target->cfg.vocab != draft->cfg.vocab) BZ_FAIL(BZ_E_INVALID, "speculative: vocabularies differ (target %d, draft %d)", target->cfg.vocab, draft->cfg.vocab);
+  int k = sc ? sc->num_speculative_tokens : 0;
+  if (k == 0) k = 5;     // config/inference.rs:197-208 default
+  if (k < 1 || k > 15) BZ_FAIL(BZ_E_INVALID, "speculative: num_speculative_tokens = %d (1..15: a verify pass takes at most 16 rows)", k);
+  bz_speculative* sp = new bz_speculative();
+  sp->target = target; sp->draft = draft; sp->k = k; sp->adaptive = sc ? (sc->adaptive_depth != 0) : 0;
+  *out = sp;
+  return BZ_OK;
+  BZ_API_END
+}
+extern "C" int bz_speculative_free(bz_speculative* sp) { delete sp; return BZ_OK; }
+
+extern "C" int bz_generate_speculative(bz_speculative* sp, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int64_t* out_tokens, bz_gen_stats* stats,
+                                       bz_spec_stats* sstats) {
+  BZ_API_BEGIN
+  if (!sp || !prompt || !gc || !out_tokens) BZ_FAIL(BZ_E_INVALID, "generate_speculative: bad argument");
+  if (gc->temperature != 0.0f) BZ_FAIL(BZ_E_UNSUPPORTED, "generate_speculative: greedy only (temperature = %g; rejection-sampling acceptance is not built)", (double)gc->temperature);
+  if (gc->repeat_penalty != 1.0f || gc->frequency_penalty != 0.f || gc->presence_penalty != 0.f)
+    BZ_FAIL(BZ_E_UNSUPPORTED, "generate_speculative: penalties are not built (repeat_penalty %g, frequency_penalty %g, presence_penalty %g; need 1, 0, 0)",
+            (double)gc->repeat_penalty, (double)gc->frequency_penalty, (double)gc->presence_penalty);
+  if (gc->dry_multiplier > 0.f || gc->typical_p > 0.f || gc->dynatemp_range > 0.f || gc->mirostat_mode >= 2 || gc->n_logit_bias != 0)
+    BZ_FAIL(BZ_E_UNSUPPORTED, "generate_speculative: DRY, typical, dynatemp, Mirostat and logit bias are not built");
+  if (gc->paged) BZ_FAIL(BZ_E_UNSUPPORTED, "generate_speculative: paged attention is not built (contiguous caches only)");
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (sstats) { memset(sstats, 0, sizeof(*sstats)); sstats->verify_path = -1; sstats->final_depth = sp->k; }
+  if (n_prompt <= 0) return BZ_OK;
+  bz_model* tm = sp->target; bz_model* dm = sp->draft;
+  const bz_model_config& tc = tm->cfg; const bz_model_config& dc = dm->cfg;
+  bz_device* dev = tm->dev;
+  BZ_HIP(hipSetDevice(dev->id));
+  for (int i = 0; i < n_prompt; i++) if (prompt[i] < 0 || prompt[i] >= tc.vocab) BZ_FAIL(BZ_E_INVALID, "generate_speculative: prompt token %lld out of vocab", (long long)prompt[i]);
+  if (n_prompt > dc.max_seq_len) BZ_FAIL(BZ_E_INVALID, "generate_speculative: the prompt (%d tokens) exceeds the draft's max_seq_len %d", n_prompt, dc.max_seq_len);
+  const int max_tokens = std::min(gc->max_tokens, std::max(0, tc.max_seq_len - n_prompt));
+  std::lock_guard<std::recursive_mutex> lock_t(tm->mu);
+  std::lock_guard<std::recursive_mutex> lock_d(dm->mu);
+  int rc = BZ_OK;
+  bz_tensor *t_prompt = nullptr, *t_logits = nullptr, *t_dlogits = nullptr, *t_vt = nullptr;
+  bz_kv *kv = nullptr, *dkv = nullptr;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  int n_out = 0, finish = 0, kcur = sp->k, path_all = -1, k_prev = 0;
+  long long it = 0, drafted = 0, accepted = 0;
+  double draft_ms = 0.0, verify_ms = 0.0;
+  auto T0 = std::chrono::steady_clock::now();
+  auto T1 = T0;
+  std::vector<std::chrono::steady_clock::time_point> tok_t;
+  tok_t.reserve((size_t)std::max(max_tokens, 0));
+  hipStream_t st = dev->stream;
+  int64_t shp[1] = {n_prompt}, shv[2] = {1, tc.vocab}, sh16[1] = {16};
+#define GEN_TRY(x) do { rc = (x); if (rc != BZ_OK) goto done; } while (0)
+#define GEN_HIP(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { bz_set_error("%s failed: %s", #x, hipGetErrorString(e__)); rc = BZ_E_HIP; goto done; } } while (0)
+  GEN_TRY(ensure_spec_ws(tm));
+  GEN_TRY(bz_tensor_from_host(dev, BZ_I64, shp, 1, prompt, &t_prompt));
+  GEN_TRY(bz_tensor_zeros(dev, BZ_F32, shv, 2, &t_logits));
+  GEN_TRY(bz_tensor_zeros(dev, BZ_F32, shv, 2, &t_dlogits));
+  GEN_TRY(bz_tensor_zeros(dev, BZ_I64, sh16, 1, &t_vt));          // the verify row [t, d1 .. dk]: slot 0 is written by the accept kernel, slot i + 1 by draft step i
+  for (int i = 0; i < 3; i++) GEN_HIP(hipEventCreate(&ev[i]));
+  GEN_TRY(bz_kv_create(dev, tc.n_layers, 1, tc.n_kv_heads, std::max(std::min(n_prompt + max_tokens, tc.max_seq_len), 1), tc.max_seq_len, tc.head_dim, tc.act_dtype, &kv));
+  GEN_TRY(bz_kv_create(dev, dc.n_layers, 1, dc.n_kv_heads, std::max(std::min(n_prompt + max_tokens, dc.max_seq_len), 1), dc.max_seq_len, dc.head_dim, dc.act_dtype, &dkv));
+  // both models take the prompt through their ordinary path; the first token is the target's argmax
+  GEN_TRY(bz_forward_kv(tm, t_prompt, n_prompt, kv, 0, t_logits, 0));
+  GEN_TRY(bz_forward_kv(dm, t_prompt, n_prompt, dkv, 0, t_dlogits, 0));
+  GEN_TRY(bz_device_synchronize(dev));
+  T1 = std::chrono::steady_clock::now();
+  if (max_tokens > 0) {
+    long long* vt = (long long*)t_vt->ptr;
+    int64_t tok;
+    GEN_TRY(bz_argmax_to_buf(dev, t_logits, 1, tc.vocab, t_vt));
+    GEN_TRY(bz_tensor_to_host(t_vt, &tok, 8));
+    out_tokens[n_out++] = tok; tok_t.push_back(std::chrono::steady_clock::now());
+    if (tok == gc->eos_id) finish = 1;
+    while (n_out < max_tokens && !finish) {
+      const int P = n_prompt + n_out - 1;        // position of the last committed token t (vt[0]); the target's cache holds P rows
+      const int k = std::max(0, std::min(std::min(kcur, max_tokens - n_out - 1), std::min(tc.max_seq_len, dc.max_seq_len) - P - 1));
+      GEN_HIP(hipEventRecord(ev[0], st));
+      if (k > 0) {
+        GEN_TRY(kv_grow(dkv, P + k));
+        auto dstep = [&](const long long* tokp, int pos, long long* out_slot) -> int {
+          hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, dm->pos_tmp, pos);
+          StepIO io{};
+          io.kv = view_of(dkv); io.d_tok = tokp; io.d_pos = dm->pos_tmp; io.att_positions = att_positions_for(pos + 1); io.do_head = out_slot != nullptr;
+          FinalArgs fa{};
+          fa.tok_out = out_slot;
+          if (out_slot) io.final_args = &fa;
+          return llama_step(dm, io);
+        };
+        // committed tokens the draft has not seen: after a fully accepted iteration its own k-th proposal (still in slot k_prev) comes first
+        if (dkv->seq_len == P - 1 && k_prev > 0) { GEN_TRY(dstep(vt + k_prev, P - 1, nullptr)); dkv->seq_len = P; }
+        if (dkv->seq_len != P) { bz_set_error("generate_speculative: draft cache at %d, committed position %d", dkv->seq_len, P); rc = BZ_E_INVALID; goto done; }
+        for (int i = 0; i < k; i++) GEN_TRY(dstep(vt + i, P + i, vt + i + 1));
+      }
+      GEN_HIP(hipEventRecord(ev[1], st));
+      int pth = 0;
+      GEN_TRY(llama_verify_rows(tm, vt, k + 1, kv, P, tm->sp_logits, vt, &pth));
+      GEN_HIP(hipEventRecord(ev[2], st));
+      long long rec[17];
+      GEN_TRY(spec_read_record(dev, tm->sp_record, k + 2, rec));        // the iteration's one host synchronisation
+      const int a = (int)rec[0];
+      if (a < 0 || a > k) { bz_set_error("generate_speculative: accept record out of range (%d of %d)", a, k); rc = BZ_E_INVALID; goto done; }
+      kv->seq_len = P + a + 1;
+      if (k > 0) dkv->seq_len = std::min(P + k, P + a + 1);
+      k_prev = k;
+      { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) draft_ms += ms; if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) verify_ms += ms; }
+      it++; drafted += k; accepted += a;
+      path_all = path_all < 0 ? pth : (path_all & pth);
+      const auto now = std::chrono::steady_clock::now();
+      BZ_TRACE("spec iteration=%lld position=%d k=%d accepted=%d path=%d", it, P, k, a, pth);
+      for (int i = 0; i <= a && n_out < max_tokens; i++) {
+        out_tokens[n_out++] = rec[1 + i]; tok_t.push_back(now);
+        if (rec[1 + i] == gc->eos_id) { finish = 1; break; }
+      }
+      if (sp->adaptive && k > 0) {     // ASSUMPTION (boostr's rule is not visible): one deeper after a fully accepted iteration, one shallower after fewer than half
+        if (a == k) kcur = std::min(kcur + 1, 15); else if (2 * a < k) kcur = std::max(1, kcur - 1);
+      }
+    }
+  }
+  GEN_TRY(bz_device_synchronize(dev));
+done:
+  {
+    auto T2 = std::chrono::steady_clock::now();
+    if (stats) {
+      stats->prefill_ms = std::chrono::duration<double, std::milli>(T1 - T0).count();
+      stats->decode_ms = std::chrono::duration<double, std::milli>(T2 - T1).count();
+      stats->n_generated = n_out; stats->finish_reason = finish;
+      if (!tok_t.empty()) {
+        auto ms = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(t - T0).count(); };
+        stats->ttft_ms = ms(tok_t.front()); stats->total_ms = ms(tok_t.back());
+        std::vector<double> itl;
+        for (size_t i = 1; i < tok_t.size(); i++) itl.push_back(std::chrono::duration<double, std::milli>(tok_t[i] - tok_t[i - 1]).count());
+        if (!itl.empty()) {
+          std::sort(itl.begin(), itl.end());
+          auto pct = [&](double p) { size_t q = (size_t)std::ceil(p / 100.0 * (double)itl.size()); q = q ? q - 1 : 0; return itl[std::min(q, itl.size() - 1)]; };
+          stats->itl_p50_ms = pct(50.0); stats->itl_p99_ms = pct(99.0); stats->itl_max_ms = itl.back();
+          const double dec = stats->total_ms - stats->ttft_ms;
+          stats->decode_tok_per_s = dec > 0.0 ? (double)itl.size() / (dec / 1e3) : 0.0;
+        }
+      }
+    }
+    if (sstats) {
+      sstats->iterations = it; sstats->drafted_tokens = drafted; sstats->accepted_tokens = accepted; sstats->rejected_tokens = drafted - accepted;
+      sstats->verify_path = path_all; sstats->final_depth = kcur; sstats->draft_ms = draft_ms; sstats->verify_ms = verify_ms;
+    }
+  }
+  for (int i = 0; i < 3; i++) if (ev[i]) hipEventDestroy(ev[i]);
+  bz_tensor_free(t_prompt); bz_tensor_free(t_logits); bz_tensor_free(t_dlogits); bz_tensor_free(t_vt);
+  bz_kv_free(kv); bz_kv_free(dkv);
+  return rc;
+#undef GEN_TRY
+#undef GEN_HIP
   BZ_API_END
 }
 

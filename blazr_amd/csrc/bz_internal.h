@@ -369,6 +369,18 @@ int bzk_conv_shift(hipStream_t s, const ConvShift& c, int act);   // shifts the 
 int bzk_batch_advance(hipStream_t s, long long* tok, const long long* next, int* pos, int* slot, const int* table, int stride, int bs, int N);
 int bzk_batch_argmax(hipStream_t s, const float* logits, int V, long long* next, long long* log, int* step, int logcap, int N);
 
+// speculative decoding (bz_speculative.hip).  Activation rows of the multi-row lm_head: row r's residual stream at h + r * stride, its deferred
+// residual at prev + r * stride (nullptr: none); the final RMSNorm runs as the kernel's prologue, per row
+struct SpecHeadRows { const float* h; const float* prev; long long stride; const float* norm_w; float eps; int H; int act; };
+bool bzk_spec_head_ok(const LinearDev& L, int act, int H);   // dense 16-bit rows, direct output, f16 activations
+int bzk_spec_head_blocks(const LinearDev& L);                // argmax partials per row
+// 1 <= R <= 8 rows in one pass over the weights: logits [R][N] (each row the bits of the decode lm_head), argmax partials pval / pidx [R][nb]
+int bzk_spec_head(hipStream_t s, const LinearDev& L, const SpecHeadRows& x, int R, float* logits, float* pval, int* pidx, int nb);
+int bzk_spec_row_partials(hipStream_t s, const float* logits, int R, long long V, float* pval, int* pidx, int nb);
+int bzk_spec_argmax_final(hipStream_t s, const float* pval, const int* pidx, int nb, int R, long long* argmax);
+// record [R + 1] = {n_accept, tokens[0 .. n_accept], -1 ...}; next_slot (nullable) <- tokens[n_accept]
+int bzk_spec_accept(hipStream_t s, const long long* argmax, const long long* draft, int R, long long* record, long long* next_slot);
+
 #if defined(__HIPCC__)
 // ---------------------------------------------------------------------------------------------------------
 // device-side cross-lane helpers (shared by the kernel files)

@@ -417,6 +417,16 @@ class LoadedModel:
         L.check(L.lib().bz_forward_kv(self.h, t.h, S, kv.h, position, out.h, L.FWD_ALL_LOGITS if all_logits else 0))
         return out
 
+    def forward_kv_verify(self, tokens, kv, position, want_logits=True):
+        """Speculative verify (bz_forward_kv_verify): tokens = [last committed token, draft tokens ...] at `position`.  Returns (n_accept, tokens[0 .. n_accept], path,
+        logits F32 [R, vocab] device tensor or None); the cache ends at position + n_accept + 1."""
+        t, R = self._tokens(tokens)
+        out = self.dev.zeros((R, self.c.vocab), L.F32) if want_logits else None
+        na, path = C.c_int32(), C.c_int32()
+        toks = np.full(R, -1, dtype=np.int64)
+        L.check(L.lib().bz_forward_kv_verify(self.h, t.h, R, kv.h, position, out.h if out is not None else None, C.byref(na), _ptr(toks), C.byref(path)))
+        return na.value, toks[:na.value + 1].copy(), path.value, out
+
     def forward_with_paged_kv_cache(self, tokens, cache, slot_mapping, block_table, seq_len_k, start_pos, all_logits=False):
         t, S = self._tokens(tokens)
         sm = slot_mapping if isinstance(slot_mapping, Tensor) else self.dev.tensor(np.asarray(slot_mapping, dtype=np.int32))
@@ -704,6 +714,19 @@ def logits_to_token(dev, logits, ids, cnts, repeat_penalty=1.0, frequency_penalt
     return out
 
 
+def spec_accept(dev, logits, draft):
+    """bz_spec_accept: logits F32 [R, V] (device tensor or array), draft I64 [R-1] -> the record as an int64 array [R+1] = {n_accept, tokens[0 .. n_accept], -1 ...}."""
+    lg = logits if isinstance(logits, Tensor) else dev.tensor(np.ascontiguousarray(logits, dtype=np.float32))
+    R, V = lg.shape
+    d = np.ascontiguousarray(draft, dtype=np.int64).reshape(-1)
+    if len(d) != R - 1:
+        raise ValueError("spec_accept: %d draft tokens for %d rows" % (len(d), R))
+    td = dev.tensor(d) if R > 1 else None
+    rec = dev.zeros((R + 1,), L.I64)
+    L.check(L.lib().bz_spec_accept(dev.h, lg.h, R, V, td.h if td is not None else None, rec.h))
+    return rec.to_numpy().reshape(-1)
+
+
 def pack_vocab(vocab_bytes):
     """A vocabulary as the C ABI takes it: list of bytes objects (or an already packed (flat u8, offsets i64) pair) -> (flat u8, offsets i64[V+1])."""
     if isinstance(vocab_bytes, tuple):
@@ -934,4 +957,42 @@ class Executor:
         self.last_stats = dict(prefill_ms=st.prefill_ms, decode_ms=st.decode_ms, n_generated=st.n_generated, finish_reason=st.finish_reason,
                                ttft_ms=st.ttft_ms, total_ms=st.total_ms, itl_p50_ms=st.itl_p50_ms, itl_p99_ms=st.itl_p99_ms, itl_max_ms=st.itl_max_ms,
                                decode_tok_per_s=st.decode_tok_per_s)
+        return out[:st.n_generated]
+
+
+class SpeculativeExecutor:
+    """The reference's speculative path (engine/generate_text.rs:61-136, config/inference.rs:197-208): a draft model proposes, the target verifies in one pass.
+    Greedy only; the tokens are those Executor(target).generate(...) returns."""
+
+    def __init__(self, target, draft, num_speculative_tokens=5, adaptive_depth=False):
+        self.target, self.draft = target, draft
+        sc = L.SpecConfig()
+        sc.num_speculative_tokens, sc.adaptive_depth = int(num_speculative_tokens), int(bool(adaptive_depth))
+        h = C.c_void_p()
+        L.check(L.lib().bz_speculative_create(target.h, draft.h, C.byref(sc), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) and L.alive:
+                L.lib().bz_speculative_free(self.h)
+        except Exception:
+            pass
+
+    def generate(self, prompt_tokens, max_tokens, temperature=0.0, repeat_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0, eos_id=-1, use_graph=False,
+                 paged=False, **sampler):
+        g = L.GenConfig()
+        g.max_tokens, g.temperature, g.repeat_penalty, g.repeat_last_n = max_tokens, temperature, repeat_penalty, 64
+        g.frequency_penalty, g.presence_penalty, g.top_p, g.eos_id = frequency_penalty, presence_penalty, 1.0, eos_id
+        g.use_graph, g.paged, g.block_size = int(use_graph), int(paged), 16
+        for k, v in sampler.items():      # dry_multiplier, typical_p, dynatemp_range, mirostat_mode ...: refused by the library, passed through so that it can say so
+            setattr(g, k, v)
+        p = np.ascontiguousarray(prompt_tokens, dtype=np.int64)
+        out = np.zeros(max(max_tokens, 1), dtype=np.int64)
+        st, ss = L.GenStats(), L.SpecStats()
+        L.check(L.lib().bz_generate_speculative(self.h, _ptr(p), len(p), C.byref(g), _ptr(out), C.byref(st), C.byref(ss)))
+        self.last_stats = dict(prefill_ms=st.prefill_ms, decode_ms=st.decode_ms, n_generated=st.n_generated, finish_reason=st.finish_reason, ttft_ms=st.ttft_ms,
+                               total_ms=st.total_ms, itl_p50_ms=st.itl_p50_ms, itl_p99_ms=st.itl_p99_ms, itl_max_ms=st.itl_max_ms, decode_tok_per_s=st.decode_tok_per_s)
+        self.last_spec_stats = dict(iterations=ss.iterations, drafted_tokens=ss.drafted_tokens, accepted_tokens=ss.accepted_tokens, rejected_tokens=ss.rejected_tokens,
+                                    verify_path=ss.verify_path, final_depth=ss.final_depth, draft_ms=ss.draft_ms, verify_ms=ss.verify_ms)
         return out[:st.n_generated]

@@ -362,6 +362,49 @@ int bz_grammar_dfa_mask_logits(bz_device* dev, const bz_tensor* logits, int64_t 
 int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, bz_grammar* g /*nullable*/, const uint8_t* vocab_bytes,
                         const int64_t* offsets, int64_t V, int64_t* out_tokens, bz_gen_stats* stats);
 
+/* ---- speculative decoding (engine/generate_text.rs:41-44,61-136; engine/speculative.rs:99-125; config/inference.rs:197-208) -----------------
+ * The reference takes this path whenever inference.speculative is configured (draft_model, num_speculative_tokens default 5, adaptive_depth) and hands the
+ * work to boostr's SpeculativeModel::forward.  Here: a draft model proposes k tokens with k decode steps, the target verifies [t, d1 .. dk] (t = the last
+ * committed token) in ONE forward whose rows are the decode step's rows bit for bit, and a kernel decides acceptance on the device.  Greedy only, so a
+ * speculative run emits exactly the tokens bz_generate emits, whatever the draft proposes.  ASSUMPTION: boostr's acceptance rule for temperature > 0
+ * (rejection sampling) is not visible in the reference and is not built; BZ_ABI_VERSION is unchanged (new symbols only).
+ *
+ * bz_spec_accept (op level; also what a caller with its own draft source -- n-gram / prompt lookup -- uses): per-row argmax of logits F32 [R,V] (ties to the lowest
+ * index, as bz_argmax_to_buf), n_accept = length of the longest prefix with draft[i] == argmax[i] (draft I64 [R-1], nullable when R == 1),
+ * record I64 [R+1] = {n_accept, tokens[0 .. n_accept], -1 ...} with tokens[i] = draft[i] for i < n_accept and tokens[n_accept] = argmax[n_accept]
+ * (the correction, or the bonus token when everything was accepted).  1 <= R <= 16.  Enqueued on the device stream, no host synchronisation. */
+int bz_spec_accept(bz_device* dev, const bz_tensor* logits, int64_t R, int64_t V, const bz_tensor* draft, bz_tensor* record);
+/* The verify forward.  tokens I64 [1,R]: the last committed token, then R-1 draft tokens (1 <= R <= 16), at positions position .. position+R-1 of `kv`.
+ * logits_out (nullable) F32 [R,vocab]: row r is what bz_forward_kv returns for token r alone at position+r.  n_accept / tokens_out (host, R entries: tokens[0 ..
+ * n_accept], then -1) as bz_spec_accept defines them; one host synchronisation (the record's event-pipelined read).  Afterwards bz_kv_seq_len == position +
+ * n_accept + 1: rows past it hold rejected tokens, no kernel reads them and the next forward overwrites them (no copy, no rollback).
+ * path: 1 = the multi-row exact rows (f16 int4 model without act-order, GQA group 1/2/4/8, dense 16-bit lm_head, context within the exact row attention's LDS
+ * bound -- about 6 k keys at 32/8 heads x 128): 8 rows per pass over the weights and over the lm_head; 0 = every other Llama-family model or context: the rows run on
+ * the decode step token by token (correct, no gain).  Mamba2 / DeepSeek-V2: BZ_E_UNSUPPORTED. */
+int bz_forward_kv_verify(bz_model* m, const bz_tensor* tokens, int R, bz_kv* kv, int position, bz_tensor* logits_out, int32_t* n_accept,
+                         int64_t* tokens_out, int32_t* path);
+/* SpeculativeConfig (config/inference.rs:197-208).  adaptive_depth -- ASSUMPTION, boostr's rule is not visible: after a fully accepted iteration k = min(k + 1, 15),
+ * after one with fewer than half of its proposals accepted k = max(1, k - 1). */
+typedef struct { int32_t num_speculative_tokens; /* 0 -> 5; 1..15 */ int32_t adaptive_depth; int32_t reserved[6]; } bz_spec_config;
+/* iterations / accepted / rejected: generate_text.rs:130-135.  verify_path: 1 if every verify pass took the multi-row rows, 0 if any ran token by token, -1 if none
+ * ran; final_depth: k after the last iteration; draft_ms / verify_ms: device time of the two phases (HIP events), summed over the iterations. */
+typedef struct { int64_t iterations, drafted_tokens, accepted_tokens, rejected_tokens; int32_t verify_path; int32_t final_depth;
+                 double draft_ms, verify_ms; } bz_spec_stats;
+typedef struct bz_speculative bz_speculative;
+/* Both models BZ_ARCH_LLAMA on one device handle (else BZ_E_UNSUPPORTED / BZ_E_INVALID), equal vocab sizes (else BZ_E_INVALID), num_speculative_tokens in 1..15
+ * (else BZ_E_INVALID).  The handle borrows the models: free it first. */
+int bz_speculative_create(bz_model* target, bz_model* draft, const bz_spec_config* cfg, bz_speculative** out);
+int bz_speculative_free(bz_speculative* s);
+/* generate_text.rs:61-136.  Prompt through both models' bz_forward_kv, first token = the target's argmax; per iteration the draft consumes the committed tokens it
+ * has not seen (one, or two after a fully accepted iteration), proposes k tokens that stay on the device, the target verifies, ONE record read brings
+ * n_accept + 1 tokens to the host.  k is clipped by max_tokens and by both models' max_seq_len.  Stops at the first eos_id among the emitted tokens
+ * (finish_reason 1, nothing after it is written).  BZ_E_UNSUPPORTED: temperature != 0, any penalty (repeat_penalty != 1, frequency / presence != 0), DRY, typical,
+ * dynatemp, Mirostat, logit bias, paged.  use_graph is accepted and ignored (the loop is eager).
+ * bz_gen_stats keeps its definitions: ttft at the first token; inter-token gaps between the moments token ids reach the host -- the tokens of one iteration arrive
+ * together, so gaps inside an iteration are 0 and the gap between iterations carries the whole iteration. */
+int bz_generate_speculative(bz_speculative* s, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int64_t* out_tokens, bz_gen_stats* stats,
+                            bz_spec_stats* spec_stats);
+
 /* ---- measurement (methodology of /root/reference/src/cli/bench.rs:24-33,299-306) ----------------------- */
 typedef struct { char name[48]; int32_t launches; double total_ms; double algo_bytes; } bz_kernel_time;
 /* Runs `iters` eager decode steps (token at position, position+1, ...) with every kernel launched through

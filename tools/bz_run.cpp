@@ -6,6 +6,9 @@
 //   bz-run <model dir | .safetensors | .gguf> --prompt 1,2,3 [--max-tokens N] [--temperature T] [--top-k K] [--top-p P] [--min-p P]
 //          [--repeat-penalty R] [--seed S] [--graphs] [--paged-attention] [--device D] [--stats]
 //          [--grammar FILE --vocab-bytes FILE [--grammar-regular]]
+//          [--draft <checkpoint> [--spec-tokens k] [--spec-adaptive]]
+// --draft: speculative decoding (inference.speculative, config/inference.rs:197-208; generate_text.rs:61-136) with that checkpoint as the draft model: greedy only,
+// the same ids as without it; iterations / accepted / rejected go to stderr (generate_text.rs:130-135).
 // --grammar: a GBNF file (gen_config.grammar, executor_generate.rs:96-121), compiled with the reference's semantics or, with --grammar-regular, as the regular subset of
 // GBNF.  --vocab-bytes: the bytes of every token, which blazr takes from its tokenizer (executor_generate.rs:104-113): u32 V, u32 offsets[V+1], then the bytes.
 // prints the generated ids, comma separated, on stdout.
@@ -38,6 +41,8 @@ int main(int argc, char** argv) {
   gc.dry_base = 2; gc.dynatemp_exponent = 1.0f;
   int device_id = 0; bool stats_on = false;
   std::string grammar_path, vocab_path; bool grammar_regular = false;
+  std::string draft_path; bz_spec_config sc;
+  memset(&sc, 0, sizeof sc);
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&](const char* name) -> const char* { if (i + 1 >= argc) { fprintf(stderr, "bz-run: %s needs a value\n", name); exit(2); } return argv[++i]; };
@@ -57,9 +62,13 @@ int main(int argc, char** argv) {
     else if (a == "--grammar") grammar_path = next("--grammar");
     else if (a == "--vocab-bytes") vocab_path = next("--vocab-bytes");
     else if (a == "--grammar-regular") grammar_regular = true;
+    else if (a == "--draft") draft_path = next("--draft");
+    else if (a == "--spec-tokens") sc.num_speculative_tokens = atoi(next("--spec-tokens"));
+    else if (a == "--spec-adaptive") sc.adaptive_depth = 1;
     else { fprintf(stderr, "bz-run: unknown option %s\n", a.c_str()); return 2; }
   }
   if (prompt.empty()) { fprintf(stderr, "bz-run: --prompt id,id,... is required\n"); return 2; }
+  if (!draft_path.empty() && !grammar_path.empty()) { fprintf(stderr, "bz-run: --draft and --grammar do not go together\n"); return 2; }
   if (grammar_path.empty() != vocab_path.empty()) { fprintf(stderr, "bz-run: --grammar and --vocab-bytes go together\n"); return 2; }
   bz_grammar* grammar = nullptr;
   std::vector<uint8_t> vbytes; std::vector<int64_t> voff;
@@ -85,6 +94,16 @@ int main(int argc, char** argv) {
   if (bz_load_model(dev, model.c_str(), &m, &cfg) != BZ_OK) return fail("load");          // detect_model_source + load_model (run.rs:88-118)
   std::vector<int64_t> out((size_t)(gc.max_tokens > 0 ? gc.max_tokens : 1));
   bz_gen_stats st;
+  if (!draft_path.empty()) {
+    bz_model* dm = nullptr; bz_model_config dcfg; bz_speculative* sp = nullptr; bz_spec_stats ss;
+    if (bz_load_model(dev, draft_path.c_str(), &dm, &dcfg) != BZ_OK) return fail("load draft");
+    if (bz_speculative_create(m, dm, &sc, &sp) != BZ_OK) return fail("speculative");
+    if (bz_generate_speculative(sp, prompt.data(), (int)prompt.size(), &gc, out.data(), &st, &ss) != BZ_OK) return fail("generate");
+    fprintf(stderr, "speculative: iterations %lld, accepted %lld, rejected %lld, verify path %d, final depth %d\n", (long long)ss.iterations, (long long)ss.accepted_tokens,
+            (long long)ss.rejected_tokens, ss.verify_path, ss.final_depth);
+    bz_speculative_free(sp);
+    bz_model_free(dm);
+  } else
   if (bz_generate_grammar(m, prompt.data(), (int)prompt.size(), &gc, grammar, vbytes.data(), grammar ? voff.data() : nullptr, (int64_t)voff.size() - (grammar ? 1 : 0), out.data(), &st) != BZ_OK)
     return fail("generate");
   for (int i = 0; i < st.n_generated; i++) printf(i ? ",%lld" : "%lld", (long long)out[i]);
