@@ -103,6 +103,15 @@ class SpecStats(C.Structure):
                 ("verify_path", C.c_int32), ("final_depth", C.c_int32), ("draft_ms", C.c_double), ("verify_ms", C.c_double)]
 
 
+SAMPLER_WINDOW_MAX = 256
+
+
+class RowSampling(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("min_p", C.c_float), ("repeat_penalty", C.c_float),
+                ("frequency_penalty", C.c_float), ("presence_penalty", C.c_float), ("repeat_last_n", C.c_int32), ("seed", C.c_uint64),
+                ("reserved", C.c_int32 * 4)]
+
+
 # name -> (restype, argtypes); every symbol include/blazr_hip.h declares
 P = C.c_void_p
 SYMBOLS = {
@@ -164,6 +173,11 @@ SYMBOLS = {
     "bz_decode_batch_graph_read_tokens": (C.c_int, [P, C.c_int64, P]),
     "bz_decode_batch_graph_logits": (C.c_int, [P, C.POINTER(P)]),
     "bz_decode_batch_graph_free": (C.c_int, [P]),
+    "bz_batch_sampler_create": (C.c_int, [P, C.c_int, C.c_int64, C.POINTER(P)]),
+    "bz_batch_sampler_free": (C.c_int, [P]),
+    "bz_batch_sampler_set_row": (C.c_int, [P, C.c_int, C.POINTER(RowSampling), P, C.c_int, C.c_int64]),
+    "bz_batch_sampler_sample": (C.c_int, [P, P, P]),
+    "bz_decode_batch_graph_capture_sampled": (C.c_int, [P, P, C.c_int, C.c_int, P, C.POINTER(P)]),
     "bz_generate": (C.c_int, [P, P, C.c_int, C.POINTER(GenConfig), P, C.POINTER(GenStats)]),
     "bz_profile_step": (C.c_int, [P, P, C.c_int64, C.c_int, C.c_int, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),
     "bz_profile_step_ssm": (C.c_int, [P, P, C.c_int64, C.c_int, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),

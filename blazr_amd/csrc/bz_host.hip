@@ -3019,6 +3019,64 @@ extern "C" int bz_decode_batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N
   return BZ_OK;
   BZ_API_END
 }
+// The same capture with the batched sampler's launches (bz_sample_batch.hip) where the argmax sits: every sequence samples with its own parameters,
+// history and draw index (batch_decode.rs:149-168), all device-resident, so replays still need no host work.  The graph borrows the sampler.
+extern "C" int bz_decode_batch_graph_capture_sampled(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_batch_graph** out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || !kv || !out || N < 2 || N > 512 || max_blocks <= 0) BZ_FAIL(BZ_E_INVALID, "batch graph capture: bad argument (2 <= N <= 512)");
+  if (!s) BZ_FAIL(BZ_E_INVALID, "sampled batch graph capture: null sampler");
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  if (m->cfg.arch != BZ_ARCH_LLAMA) BZ_FAIL(BZ_E_UNSUPPORTED, "batch graph capture: llama family only");
+  if (kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "batch graph capture: cache does not match the model");
+  int sN = 0; long long sV = 0;
+  bzk_batch_sampler_dims(s, &sN, &sV);
+  if (sN != N || sV != (long long)m->cfg.vocab)
+    BZ_FAIL(BZ_E_INVALID, "sampled batch graph capture: the sampler is built for N = %d, V = %lld; the graph needs N = %d, V = %d", sN, sV, N, m->cfg.vocab);
+  const int capacity = std::min(max_blocks * kv->block_size, m->cfg.max_seq_len);
+  const LinearDev& LH = m->lm_head.parts[0];
+  if (!prefill_eligible(m, std::max(N, prefill_min_rows()), capacity, true) || LH.wdt != m->cfg.act_dtype || LH.K % 64)
+    BZ_FAIL(BZ_E_UNSUPPORTED, "batch graph capture: the model does not take the weight-sharing multi-row step (int4 without act-order or dense 16-bit weights, 16-bit lm_head)");
+  BZ_HIP(hipSetDevice(m->dev->id));
+  BZ_TRY(prefill_ws(m, N));                      // workspace before the capture (allocation synchronises)
+  bz_batch_graph* g = new bz_batch_graph();
+  bz_dev_retain(m->dev); g->dev = m->dev;
+  g->m = m; g->kv = kv; g->N = N; g->max_blocks = max_blocks; g->capacity = capacity; g->host_pos.assign(N, -1);
+  int rc = BZ_OK;
+  auto fail = [&](int code) { bz_decode_batch_graph_free(g); return code; };
+  if (hipMalloc(&g->tok, (size_t)N * 8) != hipSuccess || hipMalloc(&g->next, (size_t)N * 8) != hipSuccess || hipMalloc(&g->pos, (size_t)N * 4) != hipSuccess ||
+      hipMalloc(&g->slot, (size_t)N * 4) != hipSuccess || hipMalloc(&g->table, (size_t)N * max_blocks * 4) != hipSuccess || hipMalloc(&g->step, 64) != hipSuccess ||
+      hipHostMalloc(&g->log, sizeof(long long) * bz_batch_graph::LOGCAP * N, hipHostMallocDefault) != hipSuccess)
+    return fail(BZ_E_OOM);
+  hipMemset(g->tok, 0, (size_t)N * 8); hipMemset(g->next, 0, (size_t)N * 8); hipMemset(g->pos, 0, (size_t)N * 4); hipMemset(g->slot, 0, (size_t)N * 4);
+  hipMemset(g->table, 0, (size_t)N * max_blocks * 4); hipMemset(g->step, 0, 64);
+  memset(g->log, 0xff, sizeof(long long) * bz_batch_graph::LOGCAP * N);
+  const int64_t shp[2] = {N, m->cfg.vocab};
+  rc = bz_tensor_zeros(m->dev, BZ_F32, shp, 2, &g->logits);
+  if (rc != BZ_OK) return fail(rc);
+  BZ_HIP(hipDeviceSynchronize());
+  hipStream_t cap = nullptr;
+  BZ_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
+  hipError_t eb = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
+  if (eb != hipSuccess) { hipStreamDestroy(cap); bz_decode_batch_graph_free(g); BZ_FAIL(BZ_E_HIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(eb)); }
+  tl_capture_stream = cap;
+  rc = bzk_batch_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N);
+  if (rc == BZ_OK) {
+    RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity;
+    rc = prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, rcx);
+  }
+  if (rc == BZ_OK) rc = bzk_batch_sample(cap, s, (const float*)g->logits->ptr, nullptr, g->next, g->log, g->step, bz_batch_graph::LOGCAP);
+  tl_capture_stream = nullptr;
+  hipGraph_t graph = nullptr;
+  hipError_t e = hipStreamEndCapture(cap, &graph);
+  hipStreamDestroy(cap);
+  if (rc != BZ_OK) { if (graph) hipGraphDestroy(graph); return fail(rc); }
+  if (e != hipSuccess) { bz_decode_batch_graph_free(g); BZ_FAIL(BZ_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e)); }
+  g->graph = graph;
+  if (hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0) != hipSuccess) { bz_decode_batch_graph_free(g); BZ_FAIL(BZ_E_HIP, "hipGraphInstantiate failed"); }
+  *out = g;
+  return BZ_OK;
+  BZ_API_END
+}
 // State BEFORE the first replay: tokens[i] = the token sequence i feeds next, seq_lens[i] = its length INCLUDING that token (its position is
 // seq_lens[i] - 1), block_table = [N, max_blocks] rows (every block a sequence will reach before the next set_block_table call).
 extern "C" int bz_decode_batch_graph_seed(bz_batch_graph* g, const int64_t* tokens, const int32_t* seq_lens, const int32_t* block_table) {

@@ -349,6 +349,10 @@ bool bzk_pf_attn_mfma_ok(int hd, int rep);
 int bzk_sample(hipStream_t s, void** ws, const float* logits, long long V, const long long* ids, const int* cnts, int n, float rp, float fp, float pp,
                float temperature, int top_k, float top_p, float min_p, unsigned long long seed, long long* tok_out);
 int bzk_sample_free(void* ws);
+// batched per-row sampler (bz_sample_batch.hip): its 21 launches on stream s; next / log / step (nullable) are the batch graph's feedback buffer [N], pinned
+// token log [logcap][N] and step counter -- the last launch writes them as bzk_batch_argmax does
+int bzk_batch_sample(hipStream_t s, bz_batch_sampler* bs, const float* logits, long long* tokens_out, long long* next, long long* log, int* step, int logcap);
+int bzk_batch_sampler_dims(const bz_batch_sampler* bs, int* N, long long* V);
 
 // Mamba2 kernels
 struct SsmArgs {

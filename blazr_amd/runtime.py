@@ -831,13 +831,49 @@ class DeviceGrammarDfa:
         return out
 
 
+class BatchSampler:
+    """Per-sequence sampling for a decode batch (batch_decode.rs:149-168: logits_to_token_on_device once per sequence with its own gen_config) as one
+    device-side call: every row keeps its parameters, the ring of its last tokens (the penalty window of sampling.rs:169-191) and its draw index on the device."""
+
+    def __init__(self, dev, n, vocab):
+        h = C.c_void_p()
+        L.check(L.lib().bz_batch_sampler_create(dev.h, int(n), int(vocab), C.byref(h)))
+        self.h, self.dev, self.n, self.vocab = h, dev, int(n), int(vocab)
+
+    def __del__(self):
+        try:
+            if self.h and L.alive:
+                L.lib().bz_batch_sampler_free(self.h)
+        except Exception:
+            pass
+
+    def set_row(self, row, history=(), draw_index=0, temperature=0.0, top_k=0, top_p=1.0, min_p=0.0, repeat_penalty=1.0, frequency_penalty=0.0,
+                presence_penalty=0.0, repeat_last_n=64, seed=0):
+        """Row `row` samples with these parameters from now on, starting from `history` (the sequence so far, prompt included); its next draw uses seed + draw_index."""
+        p = L.RowSampling(temperature=temperature, top_k=int(top_k), top_p=top_p, min_p=min_p, repeat_penalty=repeat_penalty, frequency_penalty=frequency_penalty,
+                          presence_penalty=presence_penalty, repeat_last_n=int(repeat_last_n), seed=int(seed))
+        hist = np.ascontiguousarray(history, dtype=np.int64).reshape(-1)
+        L.check(L.lib().bz_batch_sampler_set_row(self.h, int(row), C.byref(p), _ptr(hist) if len(hist) else None, len(hist), int(draw_index)))
+
+    def sample(self, logits, out=None):
+        """logits F32 [n, vocab] (device tensor) -> I64 [n] device tensor; enqueued on the device stream."""
+        out = self.dev.zeros((self.n,), L.I64) if out is None else out
+        L.check(L.lib().bz_batch_sampler_sample(self.h, logits.h, out.h))
+        return out
+
+
 class BatchDecodeGraph:
     """Executor::capture_batched_graph / replay_batched_graph + BatchedGraphState (cuda_graphs_batched.rs:43-257): one hipGraph per decode step of N
-    sequences over a shared paged cache; tokens, positions and slots live on the device between replays."""
+    sequences over a shared paged cache; tokens, positions and slots live on the device between replays.  With `sampler` (a BatchSampler of the same n and
+    vocabulary) every sequence samples with its own parameters inside the graph; without, the step ends in the greedy argmax."""
 
-    def __init__(self, model, cache, n, max_blocks):
+    def __init__(self, model, cache, n, max_blocks, sampler=None):
         h = C.c_void_p()
-        L.check(L.lib().bz_decode_batch_graph_capture(model.h, cache.h, int(n), int(max_blocks), C.byref(h)))
+        if sampler is None:
+            L.check(L.lib().bz_decode_batch_graph_capture(model.h, cache.h, int(n), int(max_blocks), C.byref(h)))
+        else:
+            L.check(L.lib().bz_decode_batch_graph_capture_sampled(model.h, cache.h, int(n), int(max_blocks), sampler.h, C.byref(h)))
+        self.sampler = sampler                    # the graph borrows it: keep it alive as long as the graph
         self.h, self.model, self.cache, self.n, self.max_blocks = h, model, cache, int(n), int(max_blocks)
 
     def __del__(self):

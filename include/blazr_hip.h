@@ -256,6 +256,33 @@ int bz_decode_batch_graph_read_tokens(bz_batch_graph* g, int64_t step, int64_t* 
 int bz_decode_batch_graph_logits(bz_batch_graph* g, bz_tensor** logits_out);
 int bz_decode_batch_graph_free(bz_batch_graph* g);
 
+/* Batched device sampler: what the reference's batched step does by calling logits_to_token_on_device once per sequence, each with its own gen_config
+ * (engine/batch_decode.rs:149-168), as one fixed sequence of launches over all N rows.  Per row the token is what bz_logits_to_token (sampling.rs:445-460)
+ * gives for that row alone with ids / cnts = the penalty window (sampling.rs:169-191) of the row's device-resident token history and seed = seed + draw index.
+ * The handle owns parameters, history rings, draw counters and all workspace; a sample call allocates nothing, copies nothing from the host and does not
+ * synchronise, so it can be captured into a hipGraph.  1 <= N <= 512, 1 <= V <= 2^20.  New symbols only: BZ_ABI_VERSION is unchanged. */
+#define BZ_SAMPLER_WINDOW_MAX 256
+typedef struct {
+  float   temperature;          /* 0 = greedy on the penalised row, as bz_logits_to_token */
+  int32_t top_k; float top_p, min_p;
+  float   repeat_penalty, frequency_penalty, presence_penalty;
+  int32_t repeat_last_n;        /* 1..BZ_SAMPLER_WINDOW_MAX whenever a penalty is active (default 64); else ignored */
+  uint64_t seed;                /* draw number t of this row uses seed + t, as bz_generate uses gc->seed + i */
+  int32_t reserved[4];
+} bz_row_sampling;
+typedef struct bz_batch_sampler bz_batch_sampler;
+int bz_batch_sampler_create(bz_device* dev, int N /*1..512*/, int64_t V, bz_batch_sampler** out);
+int bz_batch_sampler_free(bz_batch_sampler* s);
+/* (re)configure one row: parameters, the token history it starts from (host, the last n_history tokens of the sequence, prompt included;
+ * only the last BZ_SAMPLER_WINDOW_MAX are kept), and the index of its next draw.  Takes effect at the next sample / replay.  Rows start greedy. */
+int bz_batch_sampler_set_row(bz_batch_sampler* s, int row, const bz_row_sampling* p, const int64_t* history, int n_history, int64_t draw_index);
+/* logits F32 [N,V] -> tokens_out I64 [N]; appends each row's token to its history and increments its draw index.  Enqueued on the device stream. */
+int bz_batch_sampler_sample(bz_batch_sampler* s, const bz_tensor* logits, bz_tensor* tokens_out);
+/* bz_decode_batch_graph_capture with the sampler's launches where the argmax sits: same eligibility and refusals, plus BZ_E_INVALID when the sampler's
+ * N or V differ from the graph's.  seed / replay / read_tokens / set_block_table / logits / free work unchanged; bz_batch_sampler_set_row between replays
+ * reconfigures a row without a recapture.  The graph borrows the sampler: free the graph first. */
+int bz_decode_batch_graph_capture_sampled(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_batch_graph** out);
+
 /* ---- host decode loop (Executor::generate contiguous branch, executor_generate.rs:341-410) ---------------- */
 typedef struct {
   int32_t max_tokens;
