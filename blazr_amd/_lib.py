@@ -27,6 +27,7 @@ ABI_VERSION = 4
 FWD_ALL_LOGITS = 1
 GRAMMAR_REGULAR = 1
 GRAMMAR_LDS_MAX_STATES = 128
+GRAMMAR_ROW_FREE = 0xFFFFFFFF
 ROPE_NONE, ROPE_LINEAR, ROPE_LLAMA3, ROPE_YARN = 0, 1, 2, 3
 ARCH_LLAMA = 0
 ARCH_MAMBA2 = 1
@@ -237,6 +238,17 @@ SYMBOLS = {
     "bz_device_grammar_info": (C.c_int, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "bz_device_grammar_free": (C.c_int, [P]),
     "bz_grammar_dfa_mask_logits": (C.c_int, [P, P, C.c_int64, C.c_int64, P, P]),
+    "bz_grammar_concat": (C.c_int, [C.POINTER(P), C.c_int, C.POINTER(P), C.POINTER(C.c_int32)]),
+    "bz_grammar_advance_tokens": (C.c_int, [P, P, P, C.c_int64, P, C.c_int64, C.POINTER(C.c_int)]),
+    "bz_grammar_cursor_create": (C.c_int, [P, C.c_int, C.POINTER(P)]),
+    "bz_grammar_cursor_free": (C.c_int, [P]),
+    "bz_grammar_cursor_set_row": (C.c_int, [P, C.c_int, C.c_uint32]),
+    "bz_grammar_cursor_read": (C.c_int, [P, P, P]),
+    "bz_grammar_cursor_mask": (C.c_int, [P, P]),
+    "bz_grammar_cursor_advance": (C.c_int, [P, P]),
+    "bz_decode_batch_graph_capture_grammar": (C.c_int, [P, P, C.c_int, C.c_int, P, P, C.POINTER(P)]),
+    "bz_decode_graph_capture_grammar": (C.c_int, [P, P, P, C.POINTER(P)]),
+    "bz_decode_graph_capture_paged_grammar": (C.c_int, [P, P, C.c_int, P, C.POINTER(P)]),
     "bz_generate_grammar": (C.c_int, [P, P, C.c_int, C.POINTER(GenConfig), P, P, P, C.c_int64, P, C.POINTER(GenStats)]),
     "bz_spec_accept": (C.c_int, [P, P, C.c_int64, C.c_int64, P, P]),
     "bz_forward_kv_verify": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.POINTER(C.c_int32), P, C.POINTER(C.c_int32)]),

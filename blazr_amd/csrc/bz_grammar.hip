@@ -56,6 +56,17 @@ struct bz_device_grammar {
   uint32_t* tok_off = nullptr;      // [V] first word of sorted token i
   uint32_t* tok_len = nullptr;      // [V] its byte length
   uint32_t* tok_id = nullptr;       // [V] its index in the caller's vocabulary
+  uint32_t* id_off = nullptr;       // [V] the inverse of the sort: first word of caller token t
+  uint32_t* id_len = nullptr;       // [V] its byte length
+};
+
+// device-resident DFA states, one per row of a decode batch (row r of [N,V] logits); borrows the device grammar
+struct bz_grammar_cursor {
+  bz_device* dev = nullptr;
+  const bz_device_grammar* dg = nullptr;
+  int N = 0;
+  uint32_t* state = nullptr;        // [N] a state below num_states, or BZ_GRAMMAR_ROW_FREE
+  uint32_t* rejected = nullptr;     // [N] bytes without a transition since the row was set
 };
 
 namespace {
@@ -534,6 +545,33 @@ extern "C" int bz_grammar_advance(bz_grammar* g, const uint8_t* bytes, size_t n,
   BZ_API_END
 }
 
+// n DFAs as one: the tables stacked, every transition shifted by its grammar's offset.  No state of block i reaches another block, so a row's
+// state alone decides which language it is in.
+extern "C" int bz_grammar_concat(const bz_grammar* const* gs, int n, bz_grammar** out, int32_t* starts) {
+  BZ_API_BEGIN
+  if (!gs || !out || !starts || n < 1) BZ_FAIL(BZ_E_INVALID, "grammar_concat: bad argument (n >= 1 grammars, out and starts[n] required)");
+  long long total = 0;
+  for (int i = 0; i < n; i++) {
+    if (!gs[i]) BZ_FAIL(BZ_E_INVALID, "grammar_concat: grammar %d is null", i);
+    total += gs[i]->num_states;
+  }
+  if (total > MAX_STATES) BZ_FAIL(BZ_E_UNSUPPORTED, "grammar_concat: %lld states in total, more than %d", total, MAX_STATES);
+  std::unique_ptr<bz_grammar> g(new bz_grammar());
+  g->num_states = (int)total;
+  g->table.reserve((size_t)total * 256); g->accepting.reserve((size_t)total);
+  int32_t off = 0;
+  for (int i = 0; i < n; i++) {
+    starts[i] = off;
+    for (int32_t t : gs[i]->table) g->table.push_back(t < 0 ? -1 : t + off);
+    g->accepting.insert(g->accepting.end(), gs[i]->accepting.begin(), gs[i]->accepting.end());
+    off += gs[i]->num_states;
+  }
+  g->current = starts[0];
+  *out = g.release();
+  return BZ_OK;
+  BZ_API_END
+}
+
 static int check_vocab(const char* who, const uint8_t* vocab_bytes, const int64_t* offsets, int64_t V) {
   if (!offsets || V <= 0) BZ_FAIL(BZ_E_INVALID, "%s: offsets[V+1] with V > 0 required", who);
   if (offsets[0] != 0) BZ_FAIL(BZ_E_INVALID, "%s: offsets[0] must be 0", who);
@@ -541,6 +579,24 @@ static int check_vocab(const char* who, const uint8_t* vocab_bytes, const int64_
   if (offsets[V] > 0 && !vocab_bytes) BZ_FAIL(BZ_E_INVALID, "%s: null vocab_bytes", who);
   if (offsets[V] > 0x7fffffffLL) BZ_FAIL(BZ_E_UNSUPPORTED, "%s: more than 2 GiB of token bytes", who);
   return BZ_OK;
+}
+
+// bz_grammar_advance over the bytes of each token in turn (the generate loop's rule: a byte without a transition leaves the state in place and is counted)
+extern "C" int bz_grammar_advance_tokens(bz_grammar* g, const uint8_t* vocab_bytes, const int64_t* offsets, int64_t V, const int64_t* tokens, int64_t n, int* n_rejected) {
+  BZ_API_BEGIN
+  if (!g || n < 0 || (!tokens && n)) BZ_FAIL(BZ_E_INVALID, "grammar_advance_tokens: bad argument");
+  BZ_TRY(check_vocab("grammar_advance_tokens", vocab_bytes, offsets, V));
+  for (int64_t i = 0; i < n; i++)
+    if (tokens[i] < 0 || tokens[i] >= V) BZ_FAIL(BZ_E_INVALID, "grammar_advance_tokens: token %lld at index %lld is outside the vocabulary [0,%lld)", (long long)tokens[i], (long long)i, (long long)V);
+  int rej = 0;
+  for (int64_t i = 0; i < n; i++)
+    for (int64_t k = offsets[tokens[i]]; k < offsets[tokens[i] + 1]; k++) {
+      const int32_t nx = g->table[(size_t)g->current * 256 + vocab_bytes[k]];
+      if (nx >= 0) g->current = nx; else rej++;
+    }
+  if (n_rejected) *n_rejected = rej;
+  return BZ_OK;
+  BZ_API_END
 }
 
 // compute_token_mask (grammar.rs:69-84); a token without bytes is allowed in every state
@@ -597,6 +653,77 @@ __global__ __launch_bounds__(256) void k_grammar_mask(float* __restrict__ row, c
   if (dead) row[tok_id[i]] = __uint_as_float(0xff800000u);
 }
 
+// The same walk for the N rows of a decode batch, every row from its own device-resident state.  A workgroup owns 256 tokens (grid.x) and a chunk of
+// `rows_per_wg` rows (grid.y): it stages the table once and serves every row of its chunk with it, so the staging is paid once per chunk, not once per
+// row.  A lane reads its token's length, id and first word once; in a constrained state nearly every lane dies inside that word.  state[r] is one uniform
+// load; a FREE row (or any value that is no state) is skipped without touching its logits.
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_grammar_mask_rows(float* __restrict__ logits, const uint16_t* __restrict__ table, int num_states, const uint32_t* __restrict__ state, int N,
+                                                           int rows_per_wg, const uint32_t* __restrict__ words, const uint32_t* __restrict__ tok_off,
+                                                           const uint32_t* __restrict__ tok_len, const uint32_t* __restrict__ tok_id, long long V) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char g_smem[];
+  const uint16_t* T = table;
+  if (LDS) {
+    uint4* dst = (uint4*)g_smem;
+    const uint4* src = (const uint4*)table;
+    const int n16 = num_states * 32;
+    for (int k = threadIdx.x; k < n16; k += 256) dst[k] = src[k];
+    __syncthreads();
+    T = (const uint16_t*)g_smem;
+  }
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= V) return;
+  const unsigned len = tok_len[i];
+  if (len == 0) return;                                // a token without bytes is allowed in every state
+  const uint32_t* w = words + tok_off[i];
+  const unsigned w0 = w[0];
+  const size_t id = tok_id[i];
+  const int r0 = blockIdx.y * rows_per_wg, r1 = min(N, r0 + rows_per_wg);
+  for (int r = r0; r < r1; r++) {
+    unsigned s = state[r];
+    if (s >= (unsigned)num_states) continue;           // BZ_GRAMMAR_ROW_FREE
+    bool dead = false;
+    for (unsigned k = 0; k < len && !dead; k += 4) {
+      unsigned word = k ? w[k >> 2] : w0;
+      const unsigned nb = min(4u, len - k);
+      for (unsigned j = 0; j < nb; j++) {
+        s = T[s * 256u + (word & 0xffu)];
+        if (s == NONE16) { dead = true; break; }
+        word >>= 8;
+      }
+    }
+    if (dead) logits[(size_t)r * (size_t)V + id] = __uint_as_float(0xff800000u);
+  }
+}
+
+// One lane per row: the sampled token's bytes (found through the inverse of the length sort) walked through the global table with the generate loop's
+// rule.  A FREE row, an id outside [0, V) and a token without bytes change nothing.  Lane r reads and writes row r only.
+__global__ __launch_bounds__(64) void k_grammar_advance_rows(uint32_t* __restrict__ state, uint32_t* __restrict__ rejected, const long long* __restrict__ tokens, int N,
+                                                             const uint16_t* __restrict__ table, int num_states, const uint32_t* __restrict__ words,
+                                                             const uint32_t* __restrict__ id_off, const uint32_t* __restrict__ id_len, long long V) {
+  const int r = blockIdx.x * 64 + threadIdx.x;
+  if (r >= N) return;
+  unsigned s = state[r];
+  if (s >= (unsigned)num_states) return;
+  const long long t = tokens[r];
+  if (t < 0 || t >= V) return;
+  const unsigned len = id_len[t];
+  if (len == 0) return;
+  const uint32_t* w = words + id_off[t];
+  unsigned rej = 0;
+  for (unsigned k = 0; k < len; k += 4) {
+    unsigned word = w[k >> 2];
+    const unsigned nb = min(4u, len - k);
+    for (unsigned j = 0; j < nb; j++) {
+      const unsigned nx = table[s * 256u + (word & 0xffu)];
+      if (nx == NONE16) rej++; else s = nx;
+      word >>= 8;
+    }
+  }
+  state[r] = s;
+  if (rej) rejected[r] += rej;
+}
+
 extern "C" int bz_grammar_to_device(bz_device* dev, const bz_grammar* g, const uint8_t* vocab_bytes, const int64_t* offsets, int64_t V, bz_device_grammar** out) {
   BZ_API_BEGIN
   if (!dev || !g || !out) BZ_FAIL(BZ_E_INVALID, "grammar_to_device: null argument");
@@ -621,6 +748,8 @@ extern "C" int bz_grammar_to_device(bz_device* dev, const bz_grammar* g, const u
     }
   }
   if (words.empty()) words.push_back(0);     // as the reference: at least one element
+  std::vector<uint32_t> ioff((size_t)V), ilen((size_t)V);   // the inverse of the sort: what a sampled token id needs to find its bytes
+  for (int64_t i = 0; i < V; i++) { ioff[id[i]] = off[i]; ilen[id[i]] = len[i]; }
   std::lock_guard<std::mutex> dlock__(dev->mu);
   BZ_HIP(hipSetDevice(dev->id));
   std::unique_ptr<bz_device_grammar> dg(new bz_device_grammar());
@@ -639,8 +768,10 @@ extern "C" int bz_grammar_to_device(bz_device* dev, const bz_grammar* g, const u
   up((void**)&dg->tok_off, off.data(), off.size() * 4);
   up((void**)&dg->tok_len, len.data(), len.size() * 4);
   up((void**)&dg->tok_id, id.data(), id.size() * 4);
+  up((void**)&dg->id_off, ioff.data(), ioff.size() * 4);
+  up((void**)&dg->id_len, ilen.data(), ilen.size() * 4);
   if (rc != BZ_OK) {
-    hipFree(dg->table); hipFree(dg->accepting); hipFree(dg->words); hipFree(dg->tok_off); hipFree(dg->tok_len); hipFree(dg->tok_id);
+    hipFree(dg->table); hipFree(dg->accepting); hipFree(dg->words); hipFree(dg->tok_off); hipFree(dg->tok_len); hipFree(dg->tok_id); hipFree(dg->id_off); hipFree(dg->id_len);
     return rc;
   }
   dg->dev = dev;
@@ -674,7 +805,7 @@ extern "C" int bz_device_grammar_free(bz_device_grammar* dg) {
   BZ_API_BEGIN
   if (!dg) return BZ_OK;
   hipStreamSynchronize(dg->dev->stream);
-  hipFree(dg->table); hipFree(dg->accepting); hipFree(dg->words); hipFree(dg->tok_off); hipFree(dg->tok_len); hipFree(dg->tok_id);
+  hipFree(dg->table); hipFree(dg->accepting); hipFree(dg->words); hipFree(dg->tok_off); hipFree(dg->tok_len); hipFree(dg->tok_id); hipFree(dg->id_off); hipFree(dg->id_len);
   bz_dev_release(dg->dev);
   delete dg;
   return BZ_OK;
@@ -708,5 +839,125 @@ extern "C" int bz_grammar_dfa_mask_logits(bz_device* dev, const bz_tensor* logit
   }
   BZ_HIP(hipGetLastError());
   return BZ_OK;
+  BZ_API_END
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+// the cursor: one device-resident DFA state per row
+// ---------------------------------------------------------------------------------------------------------------------------------------------------
+// Rows one workgroup of k_grammar_mask_rows serves with one staged table.  64 keeps a batch of up to 64 rows in a one-dimensional grid (the table is
+// staged 501 times at V = 128256, as for one row) and gives N = 512 eight chunks.  Reasoned, not tuned: DESIGN.md 6 has the figures, which favour smaller chunks at N = 64.
+static const int ROWS_PER_WG = 64;
+
+int bzk_grammar_cursor_dims(const bz_grammar_cursor* c, int* N, long long* V, bz_device** dev) { *N = c->N; *V = c->dg->V; *dev = c->dev; return BZ_OK; }
+
+int bzk_grammar_mask_rows(hipStream_t st, bz_grammar_cursor* c, float* logits) {
+  const bz_device_grammar* dg = c->dg;
+  const dim3 grid((unsigned)((dg->V + 255) / 256), (unsigned)((c->N + ROWS_PER_WG - 1) / ROWS_PER_WG));
+  if (dg->lds_table)
+    hipLaunchKernelGGL((k_grammar_mask_rows<true>), grid, dim3(256), (size_t)dg->num_states * 512, st, logits, (const uint16_t*)dg->table, dg->num_states, (const uint32_t*)c->state, c->N,
+                       ROWS_PER_WG, (const uint32_t*)dg->words, (const uint32_t*)dg->tok_off, (const uint32_t*)dg->tok_len, (const uint32_t*)dg->tok_id, dg->V);
+  else
+    hipLaunchKernelGGL((k_grammar_mask_rows<false>), grid, dim3(256), 0, st, logits, (const uint16_t*)dg->table, dg->num_states, (const uint32_t*)c->state, c->N, ROWS_PER_WG,
+                       (const uint32_t*)dg->words, (const uint32_t*)dg->tok_off, (const uint32_t*)dg->tok_len, (const uint32_t*)dg->tok_id, dg->V);
+  BZ_HIP(hipGetLastError());
+  return BZ_OK;
+}
+
+int bzk_grammar_advance_rows(hipStream_t st, bz_grammar_cursor* c, const long long* tokens) {
+  const bz_device_grammar* dg = c->dg;
+  hipLaunchKernelGGL(k_grammar_advance_rows, dim3((c->N + 63) / 64), dim3(64), 0, st, c->state, c->rejected, tokens, c->N, (const uint16_t*)dg->table, dg->num_states,
+                     (const uint32_t*)dg->words, (const uint32_t*)dg->id_off, (const uint32_t*)dg->id_len, dg->V);
+  BZ_HIP(hipGetLastError());
+  return BZ_OK;
+}
+
+extern "C" int bz_grammar_cursor_free(bz_grammar_cursor* c) {
+  BZ_API_BEGIN
+  if (!c) return BZ_OK;
+  if (c->dev) { hipSetDevice(c->dev->id); hipStreamSynchronize(c->dev->stream); }
+  if (c->state) hipFree(c->state);
+  if (c->rejected) hipFree(c->rejected);
+  if (c->dev) bz_dev_release(c->dev);
+  delete c;
+  return BZ_OK;
+  BZ_API_END
+}
+
+extern "C" int bz_grammar_cursor_create(const bz_device_grammar* dg, int N, bz_grammar_cursor** out) {
+  BZ_API_BEGIN
+  if (!out) BZ_FAIL(BZ_E_INVALID, "grammar cursor create: null output pointer");
+  *out = nullptr;
+  if (!dg) BZ_FAIL(BZ_E_INVALID, "grammar cursor create: null device grammar");
+  if (N < 1 || N > 512) BZ_FAIL(BZ_E_INVALID, "grammar cursor create: N = %d out of range (1 <= N <= 512)", N);
+  if (dg->state >= (uint32_t)dg->num_states) BZ_FAIL(BZ_E_INVALID, "grammar cursor create: the grammar's state is out of range");
+  std::lock_guard<std::mutex> dlock__(dg->dev->mu);
+  BZ_HIP(hipSetDevice(dg->dev->id));
+  // dynamic LDS beyond the default needs the attribute; set here so that no capture ever contains the call
+  if (dg->lds_table) BZ_HIP(hipFuncSetAttribute((const void*)k_grammar_mask_rows<true>, hipFuncAttributeMaxDynamicSharedMemorySize, BZ_GRAMMAR_LDS_MAX_STATES * 512));
+  bz_grammar_cursor* c = new bz_grammar_cursor();
+  bz_dev_retain(dg->dev); c->dev = dg->dev;
+  c->dg = dg; c->N = N;
+  std::vector<uint32_t> init((size_t)N, dg->state);
+  if (hipMalloc(&c->state, (size_t)N * 4) != hipSuccess || hipMalloc(&c->rejected, (size_t)N * 4) != hipSuccess) {
+    (void)hipGetLastError(); bz_grammar_cursor_free(c); BZ_FAIL(BZ_E_OOM, "grammar cursor create: out of device memory");
+  }
+  if (hipMemcpy(c->state, init.data(), (size_t)N * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemset(c->rejected, 0, (size_t)N * 4) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess) {
+    bz_grammar_cursor_free(c); BZ_FAIL(BZ_E_HIP, "grammar cursor create: upload failed");
+  }
+  *out = c;
+  return BZ_OK;
+  BZ_API_END
+}
+
+extern "C" int bz_grammar_cursor_set_row(bz_grammar_cursor* c, int row, uint32_t state) {
+  BZ_API_BEGIN
+  if (!c) BZ_FAIL(BZ_E_INVALID, "grammar cursor set_row: null cursor");
+  if (row < 0 || row >= c->N) BZ_FAIL(BZ_E_INVALID, "grammar cursor set_row: row %d out of range (N = %d)", row, c->N);
+  if (state != BZ_GRAMMAR_ROW_FREE && state >= (uint32_t)c->dg->num_states)
+    BZ_FAIL(BZ_E_INVALID, "grammar cursor set_row: state %u is neither below the grammar's %d states nor BZ_GRAMMAR_ROW_FREE", state, c->dg->num_states);
+  const uint32_t zero = 0;
+  std::lock_guard<std::mutex> dlock__(c->dev->mu);
+  BZ_HIP(hipSetDevice(c->dev->id));
+  BZ_HIP(hipMemcpyAsync(c->state + row, &state, 4, hipMemcpyHostToDevice, c->dev->stream));   // stream-ordered: after the replays already enqueued
+  BZ_HIP(hipMemcpyAsync(c->rejected + row, &zero, 4, hipMemcpyHostToDevice, c->dev->stream));
+  BZ_HIP(hipStreamSynchronize(c->dev->stream));
+  return BZ_OK;
+  BZ_API_END
+}
+
+extern "C" int bz_grammar_cursor_read(bz_grammar_cursor* c, uint32_t* states, uint32_t* rejected) {
+  BZ_API_BEGIN
+  if (!c || !states) BZ_FAIL(BZ_E_INVALID, "grammar cursor read: null argument");
+  std::lock_guard<std::mutex> dlock__(c->dev->mu);
+  BZ_HIP(hipSetDevice(c->dev->id));
+  BZ_HIP(hipMemcpyAsync(states, c->state, (size_t)c->N * 4, hipMemcpyDeviceToHost, c->dev->stream));
+  if (rejected) BZ_HIP(hipMemcpyAsync(rejected, c->rejected, (size_t)c->N * 4, hipMemcpyDeviceToHost, c->dev->stream));
+  BZ_HIP(hipStreamSynchronize(c->dev->stream));
+  return BZ_OK;
+  BZ_API_END
+}
+
+extern "C" int bz_grammar_cursor_mask(bz_grammar_cursor* c, bz_tensor* logits) {
+  BZ_API_BEGIN
+  if (!c || !logits) BZ_FAIL(BZ_E_INVALID, "grammar cursor mask: null argument");
+  const size_t N = (size_t)c->N, V = (size_t)c->dg->V;
+  if (logits->dtype != BZ_F32 || logits->nbytes != N * V * 4) BZ_FAIL(BZ_E_INVALID, "grammar cursor mask: logits must be F32 [%zu,%zu] (got dtype %d, %zu bytes)", N, V, logits->dtype, logits->nbytes);
+  if (logits->dev != c->dev) BZ_FAIL(BZ_E_INVALID, "grammar cursor mask: the logits live on another device handle");
+  std::lock_guard<std::mutex> dlock__(c->dev->mu);
+  BZ_HIP(hipSetDevice(c->dev->id));
+  return bzk_grammar_mask_rows(c->dev->stream, c, (float*)logits->ptr);
+  BZ_API_END
+}
+
+extern "C" int bz_grammar_cursor_advance(bz_grammar_cursor* c, const bz_tensor* tokens) {
+  BZ_API_BEGIN
+  if (!c || !tokens) BZ_FAIL(BZ_E_INVALID, "grammar cursor advance: null argument");
+  if (tokens->dtype != BZ_I64 || tokens->nbytes != (size_t)c->N * 8) BZ_FAIL(BZ_E_INVALID, "grammar cursor advance: tokens must be I64 [%d] (got dtype %d, %zu bytes)", c->N, tokens->dtype, tokens->nbytes);
+  if (tokens->dev != c->dev) BZ_FAIL(BZ_E_INVALID, "grammar cursor advance: the tokens live on another device handle");
+  std::lock_guard<std::mutex> dlock__(c->dev->mu);
+  BZ_HIP(hipSetDevice(c->dev->id));
+  return bzk_grammar_advance_rows(c->dev->stream, c, (const long long*)tokens->ptr);
   BZ_API_END
 }

@@ -1423,6 +1423,7 @@ struct StepIO {
   FinalArgs* final_args = nullptr;                          // graph mode: fused argmax + bookkeeping
   bz_ssm_state* ssm = nullptr;                              // Mamba2: recurrent state instead of a KV cache
   int att_positions = 0;    // > 0: long-context step -- split-KV attention sized for this many positions (eager: position + 1; graph: capacity)
+  bz_grammar_cursor* cursor = nullptr;                      // graph mode, Llama family: mask the logits row from the cursor's state before the argmax, advance it on the picked token
 };
 
 // Fixed-point accumulator ring.  Launch j accumulates into ring[j % 3] (which must be zero), reads the output of
@@ -1580,7 +1581,7 @@ static int llama_step(bz_model* m, const StepIO& io) {
       VSrc lv;
       BZ_TRY(run_fused(m, m->lm_head, ph, rs, &lv));
       BZ_TRY(bzk_fix_to_f32(st, (const long long*)lv.p, c.vocab, act, m->logits));
-      BZ_TRY(bzk_argmax_partials(st, m->logits, c.vocab, m->pval, m->pidx, m->nparts));
+      if (!io.cursor) BZ_TRY(bzk_argmax_partials(st, m->logits, c.vocab, m->pval, m->pidx, m->nparts));
       rfin = -1;
     } else {
       GemvOut o{};
@@ -1589,12 +1590,18 @@ static int llama_step(bz_model* m, const StepIO& io) {
       BZ_TRY(bzk_gemv(st, m->lm_head.parts[0], ph, o, act));
       rs.dirty[rb] = 0;
     }
+    if (io.cursor) {
+      // the partials the lm_head produced belong to the unmasked row: mask, then take them again over what is left
+      BZ_TRY(bzk_grammar_mask_rows(st, io.cursor, m->logits));
+      BZ_TRY(bzk_argmax_partials(st, m->logits, c.vocab, m->pval, m->pidx, m->nparts));
+    }
     if (io.final_args) {
       FinalArgs fa = *io.final_args;
       fa.pval = m->pval; fa.pidx = m->pidx; fa.nparts = m->nparts;
       if (rfin >= 0) { fa.zero_buf = rs.dirty[rfin] > 0 ? m->ring[rfin] : nullptr; fa.zero_n = rs.dirty[rfin]; }
       BZ_TRY(bzk_argmax_final(st, fa));
       if (rfin >= 0) rs.dirty[rfin] = 0;
+      if (io.cursor) BZ_TRY(bzk_grammar_advance_rows(st, io.cursor, fa.tok_out));
     }
   }
   // every ring buffer must be zero again when the step ends
@@ -2835,6 +2842,7 @@ struct bz_decode_graph {
   long long* tok_log = nullptr;     // pinned host, written by the final kernel: log[step % LOGCAP]
   int* block_table = nullptr; int max_blocks = 0;
   bz_kv* kv = nullptr; bz_paged_kv* pkv = nullptr; bz_ssm_state* ssm = nullptr;
+  bz_grammar_cursor* cursor = nullptr;   // borrowed: the step masks and advances with it (both variants)
   std::vector<hipEvent_t> evs;
   long long replays = 0;
   static const int LOGCAP = 4096;
@@ -2847,7 +2855,7 @@ static int graph_capture_variant(bz_decode_graph* g, int att_positions, hipGraph
   FinalArgs fa{};
   fa.tok_out = g->tok_buf; fa.tok_log = g->tok_log; fa.step = g->step; fa.logcap = bz_decode_graph::LOGCAP; fa.pos = g->pos;
   StepIO io{};
-  io.kv = g->view; io.d_tok = g->tok_buf; io.d_pos = g->pos; io.final_args = &fa; io.ssm = g->ssm; io.att_positions = att_positions;
+  io.kv = g->view; io.d_tok = g->tok_buf; io.d_pos = g->pos; io.final_args = &fa; io.ssm = g->ssm; io.att_positions = att_positions; io.cursor = g->cursor;
   BZ_TRACE("graph: begin capture");
   hipStream_t cap = nullptr;
   BZ_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
@@ -2884,10 +2892,20 @@ static int graph_capture_common(bz_decode_graph* g, const KvView& view) {
   return BZ_OK;
 }
 
-extern "C" int bz_decode_graph_capture(bz_model* m, bz_kv* kv, bz_decode_graph** out) {
-  BZ_API_BEGIN
-  if (!m || !m->finalized || !kv || !out) BZ_FAIL(BZ_E_INVALID, "graph capture: bad argument");
+// what a cursor must be for the single-sequence step of `m`
+static int check_step_cursor(bz_model* m, bz_grammar_cursor* c) {
+  if (m->cfg.arch != BZ_ARCH_LLAMA) BZ_FAIL(BZ_E_UNSUPPORTED, "graph capture with a grammar: llama family only (Mamba2 and DeepSeek-V2 keep the eager loop)");
+  int cN = 0; long long cV = 0; bz_device* cdev = nullptr;
+  bzk_grammar_cursor_dims(c, &cN, &cV, &cdev);
+  if (cN != 1) BZ_FAIL(BZ_E_INVALID, "graph capture with a grammar: the grammar cursor has N = %d rows; the single-sequence step needs N = 1", cN);
+  if (cV != (long long)m->cfg.vocab) BZ_FAIL(BZ_E_INVALID, "graph capture with a grammar: the grammar cursor is built for V = %lld; the model's vocab is %d", cV, m->cfg.vocab);
+  if (cdev != m->dev) BZ_FAIL(BZ_E_INVALID, "graph capture with a grammar: the grammar cursor lives on another device handle");
+  return BZ_OK;
+}
+static int decode_graph_capture_kv(bz_model* m, bz_kv* kv, bz_grammar_cursor* c, bz_decode_graph** out) {
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  if (c) BZ_TRY(check_step_cursor(m, c));
+  if (!kv) BZ_FAIL(BZ_E_INVALID, "graph capture: bad argument");
   if (m->cfg.arch == BZ_ARCH_MAMBA2) BZ_FAIL(BZ_E_INVALID, "graph capture: model has no KV cache (use bz_decode_graph_capture_ssm)");
   if (kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "graph capture: cache does not match the model");
   BZ_HIP(hipSetDevice(m->dev->id));
@@ -2895,29 +2913,54 @@ extern "C" int bz_decode_graph_capture(bz_model* m, bz_kv* kv, bz_decode_graph**
   BZ_TRY(kv_grow(kv, kv->max_len));
   bz_decode_graph* g = new bz_decode_graph();
   bz_dev_retain(m->dev); g->dev = m->dev;
-  g->m = m; g->kv = kv; g->capacity = kv->max_len;
+  g->m = m; g->kv = kv; g->capacity = kv->max_len; g->cursor = c;
   int rc = graph_capture_common(g, view_of(kv));
   if (rc != BZ_OK) { bz_decode_graph_free(g); return rc; }
   *out = g;
   return BZ_OK;
-  BZ_API_END
 }
-extern "C" int bz_decode_graph_capture_paged(bz_model* m, bz_paged_kv* kv, int max_blocks, bz_decode_graph** out) {
-  BZ_API_BEGIN
-  if (!m || !m->finalized || !kv || !out || max_blocks <= 0) BZ_FAIL(BZ_E_INVALID, "graph capture: bad argument");
+static int decode_graph_capture_pkv(bz_model* m, bz_paged_kv* kv, int max_blocks, bz_grammar_cursor* c, bz_decode_graph** out) {
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  if (c) BZ_TRY(check_step_cursor(m, c));
+  if (!kv || max_blocks <= 0) BZ_FAIL(BZ_E_INVALID, "graph capture: bad argument");
   if (m->cfg.arch == BZ_ARCH_MAMBA2) BZ_FAIL(BZ_E_INVALID, "graph capture: model has no KV cache (use bz_decode_graph_capture_ssm)");
   if (kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "graph capture: cache does not match the model");
   BZ_HIP(hipSetDevice(m->dev->id));
   bz_decode_graph* g = new bz_decode_graph();
   bz_dev_retain(m->dev); g->dev = m->dev;
-  g->m = m; g->pkv = kv; g->max_blocks = max_blocks; g->capacity = std::min(max_blocks * kv->block_size, m->cfg.max_seq_len);
+  g->m = m; g->pkv = kv; g->max_blocks = max_blocks; g->capacity = std::min(max_blocks * kv->block_size, m->cfg.max_seq_len); g->cursor = c;
   BZ_HIP(hipMalloc(&g->block_table, (size_t)max_blocks * 4));
   BZ_HIP(hipMemset(g->block_table, 0, (size_t)max_blocks * 4));
   int rc = graph_capture_common(g, view_of(kv, g->block_table, nullptr));
   if (rc != BZ_OK) { bz_decode_graph_free(g); return rc; }
   *out = g;
   return BZ_OK;
+}
+extern "C" int bz_decode_graph_capture(bz_model* m, bz_kv* kv, bz_decode_graph** out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || !kv || !out) BZ_FAIL(BZ_E_INVALID, "graph capture: bad argument");
+  return decode_graph_capture_kv(m, kv, nullptr, out);
+  BZ_API_END
+}
+extern "C" int bz_decode_graph_capture_paged(bz_model* m, bz_paged_kv* kv, int max_blocks, bz_decode_graph** out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || !kv || !out || max_blocks <= 0) BZ_FAIL(BZ_E_INVALID, "graph capture: bad argument");
+  return decode_graph_capture_pkv(m, kv, max_blocks, nullptr, out);
+  BZ_API_END
+}
+// the same two captures with a grammar cursor inside the step (Llama family; the architecture is judged before the cache, which such a model may not have)
+extern "C" int bz_decode_graph_capture_grammar(bz_model* m, bz_kv* kv, bz_grammar_cursor* c, bz_decode_graph** out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || !out) BZ_FAIL(BZ_E_INVALID, "graph capture: bad argument");
+  if (!c) BZ_FAIL(BZ_E_INVALID, "graph capture with a grammar: null grammar cursor");
+  return decode_graph_capture_kv(m, kv, c, out);
+  BZ_API_END
+}
+extern "C" int bz_decode_graph_capture_paged_grammar(bz_model* m, bz_paged_kv* kv, int max_blocks, bz_grammar_cursor* c, bz_decode_graph** out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || !out) BZ_FAIL(BZ_E_INVALID, "graph capture: bad argument");
+  if (!c) BZ_FAIL(BZ_E_INVALID, "graph capture with a grammar: null grammar cursor");
+  return decode_graph_capture_pkv(m, kv, max_blocks, c, out);
   BZ_API_END
 }
 extern "C" int bz_decode_graph_capture_ssm(bz_model* m, bz_ssm_state* st, bz_decode_graph** out) {
@@ -2968,12 +3011,27 @@ extern "C" int bz_decode_batch_graph_free(bz_batch_graph* g) {
   return BZ_OK;
   BZ_API_END
 }
-extern "C" int bz_decode_batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_graph** out) {
-  BZ_API_BEGIN
-  if (!m || !m->finalized || !kv || !out || N < 2 || N > 512 || max_blocks <= 0) BZ_FAIL(BZ_E_INVALID, "batch graph capture: bad argument (2 <= N <= 512)");
+// The body the three captures share.  `s` (nullable): the batched sampler's launches (bz_sample_batch.hip) where the argmax sits -- every sequence samples
+// with its own parameters, history and draw index (batch_decode.rs:149-168), all device-resident.  `c` (nullable): the grammar cursor -- mask_rows on the
+// logits before the pick (sampling.rs:415-460: mask, then penalties / temperature / pick), advance_rows on the next-token buffer after it.  One linear
+// chain either way, so replays still need no host work.  The graph borrows both.
+static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_grammar_cursor* c, bz_batch_graph** out) {
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   if (m->cfg.arch != BZ_ARCH_LLAMA) BZ_FAIL(BZ_E_UNSUPPORTED, "batch graph capture: llama family only");
   if (kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "batch graph capture: cache does not match the model");
+  if (s) {
+    int sN = 0; long long sV = 0;
+    bzk_batch_sampler_dims(s, &sN, &sV);
+    if (sN != N || sV != (long long)m->cfg.vocab)
+      BZ_FAIL(BZ_E_INVALID, "sampled batch graph capture: the sampler is built for N = %d, V = %lld; the graph needs N = %d, V = %d", sN, sV, N, m->cfg.vocab);
+  }
+  if (c) {
+    int cN = 0; long long cV = 0; bz_device* cdev = nullptr;
+    bzk_grammar_cursor_dims(c, &cN, &cV, &cdev);
+    if (cN != N || cV != (long long)m->cfg.vocab)
+      BZ_FAIL(BZ_E_INVALID, "grammar batch graph capture: the grammar cursor is built for N = %d, V = %lld; the graph needs N = %d, V = %d", cN, cV, N, m->cfg.vocab);
+    if (cdev != m->dev) BZ_FAIL(BZ_E_INVALID, "grammar batch graph capture: the grammar cursor lives on another device handle");
+  }
   const int capacity = std::min(max_blocks * kv->block_size, m->cfg.max_seq_len);
   const LinearDev& LH = m->lm_head.parts[0];
   if (!prefill_eligible(m, std::max(N, prefill_min_rows()), capacity, true) || LH.wdt != m->cfg.act_dtype || LH.K % 64)
@@ -3006,7 +3064,12 @@ extern "C" int bz_decode_batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N
     RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity;
     rc = prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, rcx);
   }
-  if (rc == BZ_OK) rc = bzk_batch_argmax(cap, (const float*)g->logits->ptr, m->cfg.vocab, g->next, g->log, g->step, bz_batch_graph::LOGCAP, N);
+  if (rc == BZ_OK && c) rc = bzk_grammar_mask_rows(cap, c, (float*)g->logits->ptr);
+  if (rc == BZ_OK) {
+    if (s) rc = bzk_batch_sample(cap, s, (const float*)g->logits->ptr, nullptr, g->next, g->log, g->step, bz_batch_graph::LOGCAP);
+    else rc = bzk_batch_argmax(cap, (const float*)g->logits->ptr, m->cfg.vocab, g->next, g->log, g->step, bz_batch_graph::LOGCAP, N);
+  }
+  if (rc == BZ_OK && c) rc = bzk_grammar_advance_rows(cap, c, g->next);
   tl_capture_stream = nullptr;
   hipGraph_t graph = nullptr;
   hipError_t e = hipStreamEndCapture(cap, &graph);
@@ -3017,64 +3080,25 @@ extern "C" int bz_decode_batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N
   if (hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0) != hipSuccess) { bz_decode_batch_graph_free(g); BZ_FAIL(BZ_E_HIP, "hipGraphInstantiate failed"); }
   *out = g;
   return BZ_OK;
+}
+extern "C" int bz_decode_batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_graph** out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || !kv || !out || N < 2 || N > 512 || max_blocks <= 0) BZ_FAIL(BZ_E_INVALID, "batch graph capture: bad argument (2 <= N <= 512)");
+  return batch_graph_capture(m, kv, N, max_blocks, nullptr, nullptr, out);
   BZ_API_END
 }
-// The same capture with the batched sampler's launches (bz_sample_batch.hip) where the argmax sits: every sequence samples with its own parameters,
-// history and draw index (batch_decode.rs:149-168), all device-resident, so replays still need no host work.  The graph borrows the sampler.
 extern "C" int bz_decode_batch_graph_capture_sampled(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_batch_graph** out) {
   BZ_API_BEGIN
   if (!m || !m->finalized || !kv || !out || N < 2 || N > 512 || max_blocks <= 0) BZ_FAIL(BZ_E_INVALID, "batch graph capture: bad argument (2 <= N <= 512)");
   if (!s) BZ_FAIL(BZ_E_INVALID, "sampled batch graph capture: null sampler");
-  std::lock_guard<std::recursive_mutex> lock__(m->mu);
-  if (m->cfg.arch != BZ_ARCH_LLAMA) BZ_FAIL(BZ_E_UNSUPPORTED, "batch graph capture: llama family only");
-  if (kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "batch graph capture: cache does not match the model");
-  int sN = 0; long long sV = 0;
-  bzk_batch_sampler_dims(s, &sN, &sV);
-  if (sN != N || sV != (long long)m->cfg.vocab)
-    BZ_FAIL(BZ_E_INVALID, "sampled batch graph capture: the sampler is built for N = %d, V = %lld; the graph needs N = %d, V = %d", sN, sV, N, m->cfg.vocab);
-  const int capacity = std::min(max_blocks * kv->block_size, m->cfg.max_seq_len);
-  const LinearDev& LH = m->lm_head.parts[0];
-  if (!prefill_eligible(m, std::max(N, prefill_min_rows()), capacity, true) || LH.wdt != m->cfg.act_dtype || LH.K % 64)
-    BZ_FAIL(BZ_E_UNSUPPORTED, "batch graph capture: the model does not take the weight-sharing multi-row step (int4 without act-order or dense 16-bit weights, 16-bit lm_head)");
-  BZ_HIP(hipSetDevice(m->dev->id));
-  BZ_TRY(prefill_ws(m, N));                      // workspace before the capture (allocation synchronises)
-  bz_batch_graph* g = new bz_batch_graph();
-  bz_dev_retain(m->dev); g->dev = m->dev;
-  g->m = m; g->kv = kv; g->N = N; g->max_blocks = max_blocks; g->capacity = capacity; g->host_pos.assign(N, -1);
-  int rc = BZ_OK;
-  auto fail = [&](int code) { bz_decode_batch_graph_free(g); return code; };
-  if (hipMalloc(&g->tok, (size_t)N * 8) != hipSuccess || hipMalloc(&g->next, (size_t)N * 8) != hipSuccess || hipMalloc(&g->pos, (size_t)N * 4) != hipSuccess ||
-      hipMalloc(&g->slot, (size_t)N * 4) != hipSuccess || hipMalloc(&g->table, (size_t)N * max_blocks * 4) != hipSuccess || hipMalloc(&g->step, 64) != hipSuccess ||
-      hipHostMalloc(&g->log, sizeof(long long) * bz_batch_graph::LOGCAP * N, hipHostMallocDefault) != hipSuccess)
-    return fail(BZ_E_OOM);
-  hipMemset(g->tok, 0, (size_t)N * 8); hipMemset(g->next, 0, (size_t)N * 8); hipMemset(g->pos, 0, (size_t)N * 4); hipMemset(g->slot, 0, (size_t)N * 4);
-  hipMemset(g->table, 0, (size_t)N * max_blocks * 4); hipMemset(g->step, 0, 64);
-  memset(g->log, 0xff, sizeof(long long) * bz_batch_graph::LOGCAP * N);
-  const int64_t shp[2] = {N, m->cfg.vocab};
-  rc = bz_tensor_zeros(m->dev, BZ_F32, shp, 2, &g->logits);
-  if (rc != BZ_OK) return fail(rc);
-  BZ_HIP(hipDeviceSynchronize());
-  hipStream_t cap = nullptr;
-  BZ_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
-  hipError_t eb = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
-  if (eb != hipSuccess) { hipStreamDestroy(cap); bz_decode_batch_graph_free(g); BZ_FAIL(BZ_E_HIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(eb)); }
-  tl_capture_stream = cap;
-  rc = bzk_batch_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N);
-  if (rc == BZ_OK) {
-    RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity;
-    rc = prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, rcx);
-  }
-  if (rc == BZ_OK) rc = bzk_batch_sample(cap, s, (const float*)g->logits->ptr, nullptr, g->next, g->log, g->step, bz_batch_graph::LOGCAP);
-  tl_capture_stream = nullptr;
-  hipGraph_t graph = nullptr;
-  hipError_t e = hipStreamEndCapture(cap, &graph);
-  hipStreamDestroy(cap);
-  if (rc != BZ_OK) { if (graph) hipGraphDestroy(graph); return fail(rc); }
-  if (e != hipSuccess) { bz_decode_batch_graph_free(g); BZ_FAIL(BZ_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e)); }
-  g->graph = graph;
-  if (hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0) != hipSuccess) { bz_decode_batch_graph_free(g); BZ_FAIL(BZ_E_HIP, "hipGraphInstantiate failed"); }
-  *out = g;
-  return BZ_OK;
+  return batch_graph_capture(m, kv, N, max_blocks, s, nullptr, out);
+  BZ_API_END
+}
+extern "C" int bz_decode_batch_graph_capture_grammar(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_grammar_cursor* c, bz_batch_graph** out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || !kv || !out || N < 2 || N > 512 || max_blocks <= 0) BZ_FAIL(BZ_E_INVALID, "batch graph capture: bad argument (2 <= N <= 512)");
+  if (!c) BZ_FAIL(BZ_E_INVALID, "grammar batch graph capture: null grammar cursor");
+  return batch_graph_capture(m, kv, N, max_blocks, s, c, out);
   BZ_API_END
 }
 // State BEFORE the first replay: tokens[i] = the token sequence i feeds next, seq_lens[i] = its length INCLUDING that token (its position is
@@ -3276,8 +3300,12 @@ extern "C" int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_pro
   int rc = BZ_OK;
   bz_tensor *t_prompt = nullptr, *t_logits = nullptr, *t_tok = nullptr, *t_ids = nullptr, *t_cnts = nullptr, *t_slot = nullptr, *t_bt = nullptr;
   bz_kv* kv = nullptr; bz_paged_kv* pkv = nullptr; bz_decode_graph* graph = nullptr; bz_ssm_state* ssm = nullptr; bz_mirostat* mstate = nullptr;
-  bz_device_grammar* dg = nullptr;
-  const bool use_graph = gc->use_graph && !g;   // graph mode knows no grammar (cuda_graphs.rs): with one, the eager loop runs
+  bz_device_grammar* dg = nullptr; bz_grammar_cursor* cursor = nullptr;
+  // the reference's graph mode knows no grammar (cuda_graphs.rs).  Here the captured step carries one for the Llama family; it knows no penalties (they are
+  // ignored in graph mode), so a grammar with an active penalty keeps the eager loop, which applies them -- and so do Mamba2 and DeepSeek-V2.  With nothing to
+  // emit (max_tokens == 0) the eager loop runs too: it leaves g untouched and builds no cursor or graph
+  const bool gen_pen = gc->repeat_penalty != 1.0f || gc->frequency_penalty != 0.f || gc->presence_penalty != 0.f;
+  const bool use_graph = gc->use_graph && (!g || (c.arch == BZ_ARCH_LLAMA && !gen_pen && max_tokens > 0));
   const bool mamba = c.arch == BZ_ARCH_MAMBA2;   // executor_generate.rs:123-181
   auto mamba_arch = [](const bz_model_config& cc) { return cc.arch == BZ_ARCH_MAMBA2; };
   std::vector<uint32_t> history(prompt, prompt + n_prompt);
@@ -3327,11 +3355,22 @@ extern "C" int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_pro
   if (use_graph) {
     // cuda_graphs.rs:149-189: first token from the prefill logits, then one graph launch per token
     int64_t tok;
+    if (dg) GEN_TRY(bz_grammar_dfa_mask_logits(dev, t_logits, 1, c.vocab, dg, t_logits));   // the first token is masked as in the eager loop
     GEN_TRY(bz_argmax_to_buf(dev, t_logits, 1, c.vocab, t_tok));
     GEN_TRY(bz_tensor_to_host(t_tok, &tok, 8));
     const auto t_first = std::chrono::steady_clock::now();   // the first token is on the host here; capturing the graph comes after it
+    if (g) {          // the cursor starts from the state after the first token; from here on the state lives on the device
+      if (tok < 0 || tok >= V) { bz_set_error("generate: sampled token %lld outside the vocabulary", (long long)tok); rc = BZ_E_INVALID; goto done; }
+      GEN_TRY(bz_grammar_advance(g, vocab_bytes + offsets[tok], (size_t)(offsets[tok + 1] - offsets[tok]), nullptr));
+      GEN_TRY(bz_grammar_cursor_create(dg, 1, &cursor));
+      GEN_TRY(bz_grammar_cursor_set_row(cursor, 0, (uint32_t)bz_grammar_current_state(g)));
+    }
     if (mamba) GEN_TRY(bz_decode_graph_capture_ssm(m, ssm, &graph));
-    else if (gc->paged) { GEN_TRY(bz_decode_graph_capture_paged(m, pkv, (int)bt.size(), &graph)); GEN_TRY(bz_decode_graph_set_block_table(graph, bt.data(), (int)bt.size())); }
+    else if (gc->paged) {
+      if (cursor) GEN_TRY(bz_decode_graph_capture_paged_grammar(m, pkv, (int)bt.size(), cursor, &graph));
+      else GEN_TRY(bz_decode_graph_capture_paged(m, pkv, (int)bt.size(), &graph));
+      GEN_TRY(bz_decode_graph_set_block_table(graph, bt.data(), (int)bt.size()));
+    } else if (cursor) GEN_TRY(bz_decode_graph_capture_grammar(m, kv, cursor, &graph));
     else GEN_TRY(bz_decode_graph_capture(m, kv, &graph));
     GEN_TRY(bz_decode_graph_seed(graph, tok, n_prompt));
     BZ_TRACE("generate: graph captured and seeded with token %lld at position %d", (long long)tok, n_prompt);
@@ -3346,9 +3385,10 @@ extern "C" int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_pro
       BZ_TRACE("step=%d token=%lld fwd_launch_us=%.1f sync_us=%.1f", i, (long long)tok, std::chrono::duration<double, std::micro>(tl1 - tl0).count(),
                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tl1).count());   // :313,394 fwd_launch / sync split
     }
+    if (g && n_out > 1) GEN_TRY(bz_grammar_advance_tokens(g, vocab_bytes, offsets, V, out_tokens + 1, n_out - 1, nullptr));   // g ends where the eager loop leaves it
   } else {
     std::vector<int64_t> ids; std::vector<int32_t> cnts;
-    const bool has_pen = gc->repeat_penalty != 1.0f || gc->frequency_penalty != 0.f || gc->presence_penalty != 0.f;
+    const bool has_pen = gen_pen;
     // host-side options (sampling.rs:393-437): the reference pulls the logits to the CPU for these, and so does this loop
     const bool needs_cpu = gc->dry_multiplier > 0.f || gc->typical_p > 0.f;
     const bool dyn = !greedy && gc->dynatemp_range > 0.f, miro = gc->mirostat_mode >= 2;
@@ -3441,7 +3481,7 @@ done:
       }
     }
   }
-  bz_decode_graph_free(graph);
+  bz_decode_graph_free(graph); bz_grammar_cursor_free(cursor);
   bz_tensor_free(t_prompt); bz_tensor_free(t_logits); bz_tensor_free(t_tok); bz_tensor_free(t_ids); bz_tensor_free(t_cnts);
   bz_tensor_free(t_slot); bz_tensor_free(t_bt);
   bz_kv_free(kv); bz_paged_kv_free(pkv); bz_ssm_state_free(ssm); bz_mirostat_free(mstate); bz_device_grammar_free(dg);

@@ -353,6 +353,10 @@ int bzk_sample_free(void* ws);
 // token log [logcap][N] and step counter -- the last launch writes them as bzk_batch_argmax does
 int bzk_batch_sample(hipStream_t s, bz_batch_sampler* bs, const float* logits, long long* tokens_out, long long* next, long long* log, int* step, int logcap);
 int bzk_batch_sampler_dims(const bz_batch_sampler* bs, int* N, long long* V);
+// per-row grammar cursor (bz_grammar.hip): the two launches a captured step takes, on the stream it is captured on
+int bzk_grammar_cursor_dims(const bz_grammar_cursor* c, int* N, long long* V, bz_device** dev);
+int bzk_grammar_mask_rows(hipStream_t s, bz_grammar_cursor* c, float* logits /*[N,V]*/);
+int bzk_grammar_advance_rows(hipStream_t s, bz_grammar_cursor* c, const long long* tokens /*[N]*/);
 
 // Mamba2 kernels
 struct SsmArgs {

@@ -798,6 +798,26 @@ class GrammarDfa:
     def to_device(self, dev, vocab_bytes):
         return DeviceGrammarDfa(dev, self, vocab_bytes)
 
+    @classmethod
+    def concat(cls, dfas):
+        """n DFAs as one table -> (dfa, starts): starts[i] is the state that is dfas[i]'s state 0, so one uploaded table serves rows with different grammars."""
+        dfas = list(dfas)
+        hs = (C.c_void_p * max(len(dfas), 1))(*[d.h if d is not None else None for d in dfas])
+        starts = np.zeros(max(len(dfas), 1), dtype=np.int32)
+        h = C.c_void_p()
+        L.check(L.lib().bz_grammar_concat(hs, len(dfas), C.byref(h), starts.ctypes.data_as(C.POINTER(C.c_int32))))
+        out = cls.__new__(cls)
+        out.h = h
+        return out, [int(x) for x in starts[:len(dfas)]]
+
+    def advance_tokens(self, vocab_bytes, tokens):
+        """advance() over the bytes of each token in turn; returns the number of bytes that had no transition."""
+        flat, off = pack_vocab(vocab_bytes)
+        t = np.ascontiguousarray(tokens, dtype=np.int64).reshape(-1)
+        rej = C.c_int()
+        L.check(L.lib().bz_grammar_advance_tokens(self.h, _ptr(flat) if len(flat) else None, _ptr(off), len(off) - 1, _ptr(t) if len(t) else None, len(t), C.byref(rej)))
+        return rej.value
+
 
 class DeviceGrammarDfa:
     """boostr::DeviceGrammarDfa as GrammarDfa::to_device builds it (grammar.rs:90-139) + GrammarDfaOps::grammar_dfa_mask_logits (sampling.rs:415-419)."""
@@ -829,6 +849,46 @@ class DeviceGrammarDfa:
         out = logits if out is None else out
         L.check(L.lib().bz_grammar_dfa_mask_logits(self.dev.h, logits.h, rows, vocab, self.h, out.h))
         return out
+
+
+class GrammarCursor:
+    """One device-resident DFA state per row of a decode batch over a DeviceGrammarDfa (every row starts at its current state): mask() and advance() run on
+    the device stream without a host step, so they sit inside DecodeGraph / BatchDecodeGraph.  FREE marks an unconstrained row."""
+
+    FREE = L.GRAMMAR_ROW_FREE
+
+    def __init__(self, device_grammar, n):
+        h = C.c_void_p()
+        L.check(L.lib().bz_grammar_cursor_create(device_grammar.h, int(n), C.byref(h)))
+        self.grammar = device_grammar            # the cursor borrows it: keep it alive as long as the cursor
+        self.h, self.dev, self.n = h, device_grammar.dev, int(n)
+
+    def __del__(self):
+        try:
+            if self.h and L.alive:
+                L.lib().bz_grammar_cursor_free(self.h)
+        except Exception:
+            pass
+
+    def set_row(self, row, state):
+        """Row `row` continues from `state` (or FREE) at the next launch / replay; its rejected count restarts at 0."""
+        L.check(L.lib().bz_grammar_cursor_set_row(self.h, int(row), int(state)))
+
+    def read(self):
+        """(states uint32 [n], rejected uint32 [n]); waits for the device."""
+        st = np.empty(self.n, dtype=np.uint32)
+        rej = np.empty(self.n, dtype=np.uint32)
+        L.check(L.lib().bz_grammar_cursor_read(self.h, _ptr(st), _ptr(rej)))
+        return st, rej
+
+    def mask(self, logits):
+        """logits F32 [n, vocab] device tensor, masked in place row by row."""
+        L.check(L.lib().bz_grammar_cursor_mask(self.h, logits.h))
+        return logits
+
+    def advance(self, tokens):
+        """tokens I64 [n] device tensor: every row walks its token's bytes."""
+        L.check(L.lib().bz_grammar_cursor_advance(self.h, tokens.h))
 
 
 class BatchSampler:
@@ -865,15 +925,19 @@ class BatchSampler:
 class BatchDecodeGraph:
     """Executor::capture_batched_graph / replay_batched_graph + BatchedGraphState (cuda_graphs_batched.rs:43-257): one hipGraph per decode step of N
     sequences over a shared paged cache; tokens, positions and slots live on the device between replays.  With `sampler` (a BatchSampler of the same n and
-    vocabulary) every sequence samples with its own parameters inside the graph; without, the step ends in the greedy argmax."""
+    vocabulary) every sequence samples with its own parameters inside the graph; without, the step ends in the greedy argmax.  With `grammar` (a GrammarCursor
+    of the same n and vocabulary) every row's logits are masked from its own DFA state before the pick and the state moves on with the picked token."""
 
-    def __init__(self, model, cache, n, max_blocks, sampler=None):
+    def __init__(self, model, cache, n, max_blocks, sampler=None, grammar=None):
         h = C.c_void_p()
-        if sampler is None:
+        if grammar is not None:
+            L.check(L.lib().bz_decode_batch_graph_capture_grammar(model.h, cache.h, int(n), int(max_blocks), sampler.h if sampler is not None else None, grammar.h,
+                                                                  C.byref(h)))
+        elif sampler is None:
             L.check(L.lib().bz_decode_batch_graph_capture(model.h, cache.h, int(n), int(max_blocks), C.byref(h)))
         else:
             L.check(L.lib().bz_decode_batch_graph_capture_sampled(model.h, cache.h, int(n), int(max_blocks), sampler.h, C.byref(h)))
-        self.sampler = sampler                    # the graph borrows it: keep it alive as long as the graph
+        self.sampler, self.grammar = sampler, grammar   # the graph borrows them: keep them alive as long as the graph
         self.h, self.model, self.cache, self.n, self.max_blocks = h, model, cache, int(n), int(max_blocks)
 
     def __del__(self):
@@ -918,15 +982,21 @@ class BatchDecodeGraph:
 class DecodeGraph:
     """inference::decode_graph::DecodeGraph (cuda_graphs.rs:97-189) as a hipGraph."""
 
-    def __init__(self, model, kv, max_blocks=0):
+    def __init__(self, model, kv, max_blocks=0, grammar=None):
+        """grammar: a GrammarCursor with n == 1 (Llama family): the step masks its logits row from the cursor's state and advances it on the picked token."""
         h = C.c_void_p()
-        if isinstance(kv, LayeredSsmState):
+        if grammar is not None and isinstance(kv, LayeredPagedKvCache):
+            L.check(L.lib().bz_decode_graph_capture_paged_grammar(model.h, kv.h, max_blocks or kv.num_blocks, grammar.h, C.byref(h)))
+        elif grammar is not None:
+            # a model without a KV cache is refused on its architecture before the cache is looked at
+            L.check(L.lib().bz_decode_graph_capture_grammar(model.h, None if isinstance(kv, LayeredSsmState) else kv.h, grammar.h, C.byref(h)))
+        elif isinstance(kv, LayeredSsmState):
             L.check(L.lib().bz_decode_graph_capture_ssm(model.h, kv.h, C.byref(h)))
         elif isinstance(kv, LayeredPagedKvCache):
             L.check(L.lib().bz_decode_graph_capture_paged(model.h, kv.h, max_blocks or kv.num_blocks, C.byref(h)))
         else:
             L.check(L.lib().bz_decode_graph_capture(model.h, kv.h, C.byref(h)))
-        self.h, self.model, self.kv = h, model, kv
+        self.h, self.model, self.kv, self.grammar = h, model, kv, grammar
 
     def __del__(self):
         try:

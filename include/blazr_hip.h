@@ -361,6 +361,14 @@ int bz_grammar_free(bz_grammar* g);
 /* GrammarDfa::advance (grammar.rs:37-44) per byte exactly as the generate loop uses it (executor_generate.rs:159-161, the bool is dropped): a byte with no
  * transition leaves the state where it is and the loop goes on.  n_rejected (nullable): how many bytes had no transition. */
 int bz_grammar_advance(bz_grammar* g, const uint8_t* bytes, size_t n, int* n_rejected);
+/* n DFAs as one (beyond the reference): the result's table is the n tables stacked, every transition shifted by its grammar's offset; starts[i] is the state that
+ * is grammar i's state 0 and the result's own current state is starts[0].  One uploaded table then serves requests with different grammars: a row's state alone
+ * decides which language it is in.  More than 65535 states in total: BZ_E_UNSUPPORTED; n < 1 or a null entry: BZ_E_INVALID. */
+int bz_grammar_concat(const bz_grammar* const* gs, int n, bz_grammar** out, int32_t* starts /*[n]*/);
+/* bz_grammar_advance over the bytes of each of the n tokens in turn (same rule, n_rejected counts over all of them).  A token outside [0, V) is BZ_E_INVALID and
+ * leaves g untouched. */
+int bz_grammar_advance_tokens(bz_grammar* g, const uint8_t* vocab_bytes, const int64_t* offsets, int64_t V, const int64_t* tokens, int64_t n,
+                              int* n_rejected /*nullable*/);
 /* compute_token_mask (grammar.rs:69-84) from the current state: allowed_out[V] = 1 / 0.  The library-side checker of the kernel below. */
 int bz_grammar_token_mask(const bz_grammar* g, const uint8_t* vocab_bytes, const int64_t* offsets, int64_t V, uint8_t* allowed_out);
 /* GrammarDfa::to_device (grammar.rs:90-139).  The reference ships four f32 tensors because that is its tensor type system; here the next-state table is
@@ -380,12 +388,44 @@ int bz_device_grammar_free(bz_device_grammar* dg);
  * vocab != the uploaded V: BZ_E_INVALID.  Enqueued on the device stream; no host synchronisation, no device-to-host copy.  A state that admits no token leaves an
  * all -inf row (the reference leaves that case undefined): bz_argmax_to_buf then returns what it returns for any all -inf row and the sampled path some id in [0, V). */
 int bz_grammar_dfa_mask_logits(bz_device* dev, const bz_tensor* logits, int64_t rows, int64_t vocab, const bz_device_grammar* dg, bz_tensor* logits_out);
+/* The cursor (beyond the reference, whose DFA state lives on the host): one device-resident DFA state per row of a decode batch, so that mask and advance need no
+ * host step between tokens and can sit inside a captured graph.  Every row starts at dg's current state.  The cursor borrows dg: free the cursor first.
+ *   set_row: a state below num_states, or BZ_GRAMMAR_ROW_FREE for an unconstrained row (never masked, never advanced); also zeroes the row's rejected count.
+ *     Takes effect at the next launch or replay without a recapture, as bz_batch_sampler_set_row does.
+ *   read: states[N] and (nullable) rejected[N] = bytes without a transition since the row was set; waits for the device.
+ *   mask: logits F32 [N,V] in place, row r from state[r]: a token that dies gets -inf, nothing else is written (every other logit keeps its bits, FREE rows whole).
+ *     One workgroup stages the table once (up to BZ_GRAMMAR_LDS_MAX_STATES states, else it reads through L2) and serves up to 64 rows with it.
+ *   advance: tokens I64 [N]; row r walks the bytes of tokens[r] with bz_grammar_advance's rule.  A FREE row, an id outside [0, V) or a token without bytes changes
+ *     nothing.  bz_grammar_to_device uploads the inverse of its length sort for this (per caller token id: first word and byte length).
+ * mask and advance are enqueued on the device stream: no allocation, no copy from the host, no synchronisation. */
+typedef struct bz_grammar_cursor bz_grammar_cursor;
+#define BZ_GRAMMAR_ROW_FREE 0xFFFFFFFFu
+int bz_grammar_cursor_create(const bz_device_grammar* dg, int N /*1..512*/, bz_grammar_cursor** out);
+int bz_grammar_cursor_free(bz_grammar_cursor* c);
+int bz_grammar_cursor_set_row(bz_grammar_cursor* c, int row, uint32_t state);
+int bz_grammar_cursor_read(bz_grammar_cursor* c, uint32_t* states /*[N]*/, uint32_t* rejected /*[N], nullable*/);
+int bz_grammar_cursor_mask(bz_grammar_cursor* c, bz_tensor* logits /*F32 [N,V], in place*/);
+int bz_grammar_cursor_advance(bz_grammar_cursor* c, const bz_tensor* tokens /*I64 [N]*/);
+/* The batched step with per-sequence grammars: batch advance -> multi-row forward -> mask_rows on the graph's logits -> the sampler's launches (s != NULL) or the
+ * batch argmax -> advance_rows on the next-token buffer; mask before penalties / temperature / pick as sampling.rs:415-460.  One linear chain.  Eligibility and
+ * refusals are those of bz_decode_batch_graph_capture(_sampled), plus BZ_E_INVALID when the cursor's N or V differ from the graph's or it lives on another device
+ * handle.  seed / replay / read_tokens / set_block_table / logits / free work unchanged (logits shows the masked rows); bz_grammar_cursor_set_row between replays
+ * hands a row to another grammar, or frees it, without a recapture.  The graph borrows the cursor (and the sampler): free the graph first. */
+int bz_decode_batch_graph_capture_grammar(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s /*nullable: argmax*/, bz_grammar_cursor* c,
+                                          bz_batch_graph** out);
+/* bz_decode_graph_capture / _capture_paged with a cursor of N == 1 inside the step (both the short and the split-KV variant): after the head, mask -> argmax over
+ * the masked row -> advance on the token buffer.  bz_decode_graph_read_logits returns the masked row.  Llama family only: Mamba2 and DeepSeek-V2 are
+ * BZ_E_UNSUPPORTED; a cursor with N != 1, another V or another device handle is BZ_E_INVALID.  The graph borrows the cursor. */
+int bz_decode_graph_capture_grammar(bz_model* m, bz_kv* kv, bz_grammar_cursor* c /*N == 1*/, bz_decode_graph** out);
+int bz_decode_graph_capture_paged_grammar(bz_model* m, bz_paged_kv* kv, int max_blocks, bz_grammar_cursor* c, bz_decode_graph** out);
 /* bz_generate with gen_config.grammar (executor_generate.rs:96-121): g == NULL is bz_generate.  With a grammar every branch (contiguous, paged, SSM) does per token
  * what the reference does, in its order (sampling.rs:385-460): host DRY / typical -> device mask -> logit bias -> penalties / temperature / logits_to_token; once the
  * token id is on the host, bz_grammar_advance with that token's bytes and set_state (executor_generate.rs:156-166, 302-312, 383-393).  Mirostat skips the mask
  * (sampling.rs:101-103) but still advances.  g is used from its current state and left in its final state; V must be the model's vocab.
- * use_graph = 1 with a grammar takes the eager loop: the reference's graph mode ignores grammars altogether (cuda_graphs.rs is pure argmax_to_buf), and a
- * device-resident DFA state inside the captured step is not built. */
+ * use_graph = 1 with a grammar (beyond the reference, whose graph mode ignores grammars: cuda_graphs.rs is pure argmax_to_buf): a Llama-family model without an active
+ * penalty (repeat_penalty == 1, frequency / presence == 0) takes the captured step of bz_decode_graph_capture(_paged)_grammar -- first token from the masked prompt
+ * logits, a cursor seeded with the state after it, one replay per token, g brought to its final state with bz_grammar_advance_tokens.  Every other combination
+ * (a penalty, which graph mode would ignore; Mamba2; DeepSeek-V2) takes the eager loop and gives the eager tokens. */
 int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, bz_grammar* g /*nullable*/, const uint8_t* vocab_bytes,
                         const int64_t* offsets, int64_t V, int64_t* out_tokens, bz_gen_stats* stats);
 

@@ -10,7 +10,7 @@
 // --draft: speculative decoding (inference.speculative, config/inference.rs:197-208; generate_text.rs:61-136) with that checkpoint as the draft model: greedy only,
 // the same ids as without it; iterations / accepted / rejected go to stderr (generate_text.rs:130-135).
 // --grammar: a GBNF file (gen_config.grammar, executor_generate.rs:96-121), compiled with the reference's semantics or, with --grammar-regular, as the regular subset of
-// GBNF.  --vocab-bytes: the bytes of every token, which blazr takes from its tokenizer (executor_generate.rs:104-113): u32 V, u32 offsets[V+1], then the bytes.
+// GBNF; with --graphs (Llama family, no penalty) the captured step carries the DFA state on the device.  --vocab-bytes: the bytes of every token, which blazr takes from its tokenizer (executor_generate.rs:104-113): u32 V, u32 offsets[V+1], then the bytes.
 // prints the generated ids, comma separated, on stdout.
 #include <cstdio>
 #include <cstdlib>
