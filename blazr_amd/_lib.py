@@ -113,6 +113,39 @@ class RowSampling(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+ENGINE_MAX_STOP = 8
+SCHED_ADMIT, SCHED_PREFILL, SCHED_LIVE = 0, 1, 2
+
+
+class SchedAction(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("row", C.c_int32), ("id", C.c_int64), ("a", C.c_int32), ("b", C.c_int32)]
+
+
+class SchedInfo(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("num_blocks", C.c_int32), ("park_blocks", C.c_int32), ("free_blocks", C.c_int32), ("owned_blocks", C.c_int32),
+                ("waiting", C.c_int32), ("admitted", C.c_int32), ("live", C.c_int32)]
+
+
+class EngineConfig(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("num_blocks", C.c_int32), ("block_size", C.c_int32), ("max_seq_len", C.c_int32), ("prefill_chunk", C.c_int32),
+                ("depth", C.c_int32), ("use_sampler", C.c_int32), ("reserved", C.c_int32 * 9)]
+
+
+class Request(C.Structure):
+    _fields_ = [("max_tokens", C.c_int32), ("n_stop", C.c_int32), ("stop_ids", C.c_int64 * 8), ("grammar_state", C.c_uint32), ("reserved", C.c_int32 * 3),
+                ("sampling", RowSampling)]
+
+
+class EngineEvent(C.Structure):
+    _fields_ = [("id", C.c_int64), ("token", C.c_int64), ("index", C.c_int32), ("finish_reason", C.c_int32), ("replay", C.c_int64)]
+
+
+class EngineStats(C.Structure):
+    _fields_ = [("replays", C.c_int64), ("free_blocks", C.c_int32), ("total_blocks", C.c_int32), ("park_blocks", C.c_int32), ("live_rows", C.c_int32),
+                ("admitted", C.c_int32), ("waiting", C.c_int32), ("unread", C.c_int32), ("prompt_tokens", C.c_int64), ("generated_tokens", C.c_int64),
+                ("admit_host_ms", C.c_double)]
+
+
 # name -> (restype, argtypes); every symbol include/blazr_hip.h declares
 P = C.c_void_p
 SYMBOLS = {
@@ -250,6 +283,21 @@ SYMBOLS = {
     "bz_decode_graph_capture_grammar": (C.c_int, [P, P, P, C.POINTER(P)]),
     "bz_decode_graph_capture_paged_grammar": (C.c_int, [P, P, C.c_int, P, C.POINTER(P)]),
     "bz_generate_grammar": (C.c_int, [P, P, C.c_int, C.POINTER(GenConfig), P, P, P, C.c_int64, P, C.POINTER(GenStats)]),
+    "bz_sched_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(P)]),
+    "bz_sched_free": (C.c_int, [P]),
+    "bz_sched_submit": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "bz_sched_step": (C.c_int, [P, C.POINTER(SchedAction), C.c_int, C.POINTER(C.c_int)]),
+    "bz_sched_finish": (C.c_int, [P, C.c_int64]),
+    "bz_sched_info": (C.c_int, [P, C.POINTER(SchedInfo)]),
+    "bz_sched_row": (C.c_int, [P, C.c_int, C.POINTER(C.c_int64), P, C.c_int, C.POINTER(C.c_int)]),
+    "bz_engine_create": (C.c_int, [P, C.POINTER(EngineConfig), P, C.POINTER(P)]),
+    "bz_engine_submit": (C.c_int, [P, P, C.c_int, C.POINTER(Request), C.POINTER(C.c_int64)]),
+    "bz_engine_cancel": (C.c_int, [P, C.c_int64]),
+    "bz_engine_step": (C.c_int, [P, C.POINTER(C.c_int)]),
+    "bz_engine_poll": (C.c_int, [P, C.POINTER(EngineEvent), C.c_int, C.POINTER(C.c_int)]),
+    "bz_engine_stats": (C.c_int, [P, C.POINTER(EngineStats)]),
+    "bz_engine_read_status": (C.c_int, [P, C.c_int64, P, C.POINTER(C.c_int32)]),
+    "bz_engine_free": (C.c_int, [P]),
     "bz_spec_accept": (C.c_int, [P, P, C.c_int64, C.c_int64, P, P]),
     "bz_forward_kv_verify": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.POINTER(C.c_int32), P, C.POINTER(C.c_int32)]),
     "bz_speculative_create": (C.c_int, [P, P, C.POINTER(SpecConfig), C.POINTER(P)]),

@@ -927,6 +927,16 @@ extern "C" int bz_grammar_cursor_set_row(bz_grammar_cursor* c, int row, uint32_t
   BZ_API_END
 }
 
+// what the request engine needs: the states (k_engine_finish frees a row that ends) and set_row without the wait (`stage`: pinned, two words)
+uint32_t* bzk_grammar_cursor_states(bz_grammar_cursor* c) { return c->state; }
+int bzk_grammar_cursor_num_states(const bz_grammar_cursor* c) { return c->dg->num_states; }
+int bzk_grammar_cursor_stage_row(hipStream_t st, bz_grammar_cursor* c, int row, uint32_t state, uint32_t* stage) {
+  stage[0] = state; stage[1] = 0;
+  BZ_HIP(hipMemcpyAsync(c->state + row, stage, 4, hipMemcpyHostToDevice, st));
+  BZ_HIP(hipMemcpyAsync(c->rejected + row, stage + 1, 4, hipMemcpyHostToDevice, st));
+  return BZ_OK;
+}
+
 extern "C" int bz_grammar_cursor_read(bz_grammar_cursor* c, uint32_t* states, uint32_t* rejected) {
   BZ_API_BEGIN
   if (!c || !states) BZ_FAIL(BZ_E_INVALID, "grammar cursor read: null argument");

@@ -2985,17 +2985,7 @@ extern "C" int bz_decode_graph_capture_ssm(bz_model* m, bz_ssm_state* st, bz_dec
 // seq_len_k), every sequence has its own device-resident position, the argmax is fed back on the device and the slot comes from the block table,
 // so consecutive replays need no host work until a sequence crosses into a block the table does not hold yet.
 // ---------------------------------------------------------------------------------------------------------
-struct bz_batch_graph {
-  bz_model* m = nullptr; bz_device* dev = nullptr; bz_paged_kv* kv = nullptr;
-  hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-  int N = 0, max_blocks = 0, capacity = 0;
-  long long* tok = nullptr; long long* next = nullptr; int* pos = nullptr; int* slot = nullptr; int* table = nullptr; int* step = nullptr;
-  bz_tensor* logits = nullptr;        // [N, vocab] of the last replay
-  long long* log = nullptr;           // pinned host [LOGCAP][N]
-  std::vector<int> host_pos;          // host copy of the positions (limit checks, cache bookkeeping)
-  long long replays = 0;
-  static const int LOGCAP = 1024;
-};
+// (struct bz_batch_graph: bz_internal.h -- the request engine drives one through its buffers)
 extern "C" int bz_decode_batch_graph_free(bz_batch_graph* g) {
   BZ_API_BEGIN
   if (!g) return BZ_OK;
@@ -3015,7 +3005,10 @@ extern "C" int bz_decode_batch_graph_free(bz_batch_graph* g) {
 // with its own parameters, history and draw index (batch_decode.rs:149-168), all device-resident.  `c` (nullable): the grammar cursor -- mask_rows on the
 // logits before the pick (sampling.rs:415-460: mask, then penalties / temperature / pick), advance_rows on the next-token buffer after it.  One linear
 // chain either way, so replays still need no host work.  The graph borrows both.
-static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_grammar_cursor* c, bz_batch_graph** out) {
+// `er` (nullable): the request engine's row life cycle (bz_engine.hip) -- k_engine_advance where k_batch_advance sits, k_engine_finish as the last launch.
+// Null: node for node the capture without it.
+static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_grammar_cursor* c, bz_batch_graph** out,
+                               const BzEngineRows* er = nullptr) {
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   if (m->cfg.arch != BZ_ARCH_LLAMA) BZ_FAIL(BZ_E_UNSUPPORTED, "batch graph capture: llama family only");
   if (kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "batch graph capture: cache does not match the model");
@@ -3059,7 +3052,8 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
   hipError_t eb = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
   if (eb != hipSuccess) { hipStreamDestroy(cap); bz_decode_batch_graph_free(g); BZ_FAIL(BZ_E_HIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(eb)); }
   tl_capture_stream = cap;
-  rc = bzk_batch_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N);
+  if (er) rc = bzk_engine_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N, er->rows);
+  else rc = bzk_batch_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N);
   if (rc == BZ_OK) {
     RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity;
     rc = prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, rcx);
@@ -3070,6 +3064,8 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
     else rc = bzk_batch_argmax(cap, (const float*)g->logits->ptr, m->cfg.vocab, g->next, g->log, g->step, bz_batch_graph::LOGCAP, N);
   }
   if (rc == BZ_OK && c) rc = bzk_grammar_advance_rows(cap, c, g->next);
+  if (rc == BZ_OK && er)
+    rc = bzk_engine_finish(cap, er->rows, g->next, g->pos, g->table, max_blocks, g->step, bz_batch_graph::LOGCAP, N, er->status, er->nlive, c ? bzk_grammar_cursor_states(c) : nullptr);
   tl_capture_stream = nullptr;
   hipGraph_t graph = nullptr;
   hipError_t e = hipStreamEndCapture(cap, &graph);
@@ -3100,6 +3096,22 @@ extern "C" int bz_decode_batch_graph_capture_grammar(bz_model* m, bz_paged_kv* k
   if (!c) BZ_FAIL(BZ_E_INVALID, "grammar batch graph capture: null grammar cursor");
   return batch_graph_capture(m, kv, N, max_blocks, s, c, out);
   BZ_API_END
+}
+// ---- what the request engine (bz_engine.hip) needs of this file ----
+int bzi_engine_capture(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_grammar_cursor* c, const BzEngineRows* er, bz_batch_graph** out) {
+  return batch_graph_capture(m, kv, N, max_blocks, s, c, out, er);
+}
+int bzi_batch_graph_launch(bz_batch_graph* g) {
+  std::lock_guard<std::recursive_mutex> lock__(g->m->mu);       // a step's kernels share the model's workspace: whole steps interleave, never kernels
+  BZ_HIP(hipGraphLaunch(g->exec, g->m->dev->stream));
+  g->replays++;
+  return BZ_OK;
+}
+bz_device* bzi_model_device(bz_model* m) { return m && m->finalized ? m->dev : nullptr; }   // nullptr: not finalized
+int bzi_prefill_reserve(bz_model* m, int rows) {
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  BZ_HIP(hipSetDevice(m->dev->id));
+  return prefill_ws(m, rows);
 }
 // State BEFORE the first replay: tokens[i] = the token sequence i feeds next, seq_lens[i] = its length INCLUDING that token (its position is
 // seq_lens[i] - 1), block_table = [N, max_blocks] rows (every block a sequence will reach before the next set_block_table call).

@@ -377,6 +377,40 @@ int bzk_conv_shift(hipStream_t s, const ConvShift& c, int act);   // shifts the 
 int bzk_batch_advance(hipStream_t s, long long* tok, const long long* next, int* pos, int* slot, const int* table, int stride, int bs, int N);
 int bzk_batch_argmax(hipStream_t s, const float* logits, int V, long long* next, long long* log, int* step, int logcap, int N);
 
+// The batched decode graph (bz_host.hip); the request engine (bz_engine.hip) drives one through its buffers.
+struct bz_batch_graph {
+  bz_model* m = nullptr; bz_device* dev = nullptr; bz_paged_kv* kv = nullptr;
+  hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+  int N = 0, max_blocks = 0, capacity = 0;
+  long long* tok = nullptr; long long* next = nullptr; int* pos = nullptr; int* slot = nullptr; int* table = nullptr; int* step = nullptr;
+  bz_tensor* logits = nullptr;        // [N, vocab] of the last replay
+  long long* log = nullptr;           // pinned host [LOGCAP][N]
+  std::vector<int> host_pos;          // host copy of the positions (limit checks, cache bookkeeping)
+  long long replays = 0;
+  static const int LOGCAP = 1024;
+};
+// request engine (bz_engine.hip): the row life cycle of a captured step.  One EngRow per row, device-resident; a live row decodes, an idle row feeds token 0
+// at position 0 of its own park block.  status / nlive: pinned host rings [LOGCAP][N] / [LOGCAP] beside the token log.
+#define BZ_ENGINE_MAX_STOP 8
+struct EngRow { int live, left, n_stop, park_block; long long stop[BZ_ENGINE_MAX_STOP]; };
+struct BzEngineRows { EngRow* rows; int* status; int* nlive; };
+enum { ENG_IDLE = 0, ENG_TOKEN = 1, ENG_FINISHED = 2 };   // status word: low 2 bits; a finished row's reason (0 length, 1 stop) sits in bits 2..
+int bzk_engine_advance(hipStream_t s, long long* tok, const long long* next, int* pos, int* slot, const int* table, int stride, int bs, int N, const EngRow* rows);
+int bzk_engine_finish(hipStream_t s, EngRow* rows, const long long* next, int* pos, int* table, int stride, const int* step, int logcap, int N, int* status,
+                      int* nlive, uint32_t* gstate /*nullable: the grammar cursor's states*/);
+// what the engine needs of bz_host.hip: the capture with the row life cycle in it, a launch under the model's lock, the model's device, the prompt workspace
+int bzi_engine_capture(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_grammar_cursor* c, const BzEngineRows* er, bz_batch_graph** out);
+int bzi_batch_graph_launch(bz_batch_graph* g);
+bz_device* bzi_model_device(bz_model* m);
+int bzi_prefill_reserve(bz_model* m, int rows);
+// non-synchronising row writes for the engine: `stage` is pinned host memory the caller keeps untouched until the stream has passed the copies
+size_t bzk_batch_sampler_row_bytes();
+int bzk_batch_sampler_check_row(const bz_row_sampling* p, const char* who);
+int bzk_batch_sampler_stage_row(hipStream_t st, bz_batch_sampler* bs, int row, const bz_row_sampling* p, const int64_t* history, int n_history, int64_t draw_index, void* stage);
+uint32_t* bzk_grammar_cursor_states(bz_grammar_cursor* c);
+int bzk_grammar_cursor_num_states(const bz_grammar_cursor* c);
+int bzk_grammar_cursor_stage_row(hipStream_t st, bz_grammar_cursor* c, int row, uint32_t state, uint32_t* stage /*[2]*/);
+
 // speculative decoding (bz_speculative.hip).  Activation rows of the multi-row lm_head: row r's residual stream at h + r * stride, its deferred
 // residual at prev + r * stride (nullptr: none); the final RMSNorm runs as the kernel's prologue, per row
 struct SpecHeadRows { const float* h; const float* prev; long long stride; const float* norm_w; float eps; int H; int act; };

@@ -454,17 +454,16 @@ extern "C" int bz_batch_sampler_create(bz_device* dev, int N, int64_t V, bz_batc
   BZ_API_END
 }
 
-extern "C" int bz_batch_sampler_set_row(bz_batch_sampler* s, int row, const bz_row_sampling* p, const int64_t* history, int n_history, int64_t draw_index) {
-  BZ_API_BEGIN
-  if (!s || !p) BZ_FAIL(BZ_E_INVALID, "batch sampler set_row: null argument");
-  if (row < 0 || row >= s->a.N) BZ_FAIL(BZ_E_INVALID, "batch sampler set_row: row %d out of range (N = %d)", row, s->a.N);
-  if (!(p->temperature >= 0.0f)) BZ_FAIL(BZ_E_INVALID, "batch sampler set_row: temperature must be >= 0 (got %g)", (double)p->temperature);
+// the parameter checks of set_row; `who` names the caller in the message
+int bzk_batch_sampler_check_row(const bz_row_sampling* p, const char* who) {
+  if (!(p->temperature >= 0.0f)) BZ_FAIL(BZ_E_INVALID, "%s: temperature must be >= 0 (got %g)", who, (double)p->temperature);
   const bool pen = p->repeat_penalty != 1.0f || p->frequency_penalty != 0.0f || p->presence_penalty != 0.0f;
   if (pen && (p->repeat_last_n < 1 || p->repeat_last_n > WIN))
-    BZ_FAIL(BZ_E_INVALID, "batch sampler set_row: repeat_last_n = %d out of range (1 <= repeat_last_n <= %d while a penalty is active)", p->repeat_last_n, WIN);
-  if (n_history < 0 || (n_history > 0 && !history)) BZ_FAIL(BZ_E_INVALID, "batch sampler set_row: bad history (n_history = %d)", n_history);
-  if (draw_index < 0) BZ_FAIL(BZ_E_INVALID, "batch sampler set_row: negative draw index");
-  BsRow r;
+    BZ_FAIL(BZ_E_INVALID, "%s: repeat_last_n = %d out of range (1 <= repeat_last_n <= %d while a penalty is active)", who, p->repeat_last_n, WIN);
+  return BZ_OK;
+}
+static void fill_row(BsRow& r, const bz_row_sampling* p, const int64_t* history, int n_history, int64_t draw_index) {
+  const bool pen = p->repeat_penalty != 1.0f || p->frequency_penalty != 0.0f || p->presence_penalty != 0.0f;
   memset(&r, 0, sizeof(r));
   r.temperature = p->temperature; r.top_k = p->top_k; r.top_p = p->top_p; r.min_p = p->min_p;
   r.rp = p->repeat_penalty; r.fp = p->frequency_penalty; r.pp = p->presence_penalty; r.last_n = pen ? p->repeat_last_n : 0;
@@ -472,6 +471,24 @@ extern "C" int bz_batch_sampler_set_row(bz_batch_sampler* s, int row, const bz_r
   const int w = std::min(n_history, WIN);
   for (int i = 0; i < w; i++) r.ring[i] = history[n_history - w + i];
   r.cnt = w; r.head = w & (WIN - 1);
+}
+size_t bzk_batch_sampler_row_bytes() { return sizeof(BsRow); }
+// set_row without the wait (request engine): the row is built in `stage` (pinned, bzk_batch_sampler_row_bytes(), the caller's until the stream has passed the copy)
+int bzk_batch_sampler_stage_row(hipStream_t st, bz_batch_sampler* s, int row, const bz_row_sampling* p, const int64_t* history, int n_history, int64_t draw_index, void* stage) {
+  fill_row(*(BsRow*)stage, p, history, n_history, draw_index);
+  BZ_HIP(hipMemcpyAsync(s->a.rows + row, stage, sizeof(BsRow), hipMemcpyHostToDevice, st));
+  return BZ_OK;
+}
+
+extern "C" int bz_batch_sampler_set_row(bz_batch_sampler* s, int row, const bz_row_sampling* p, const int64_t* history, int n_history, int64_t draw_index) {
+  BZ_API_BEGIN
+  if (!s || !p) BZ_FAIL(BZ_E_INVALID, "batch sampler set_row: null argument");
+  if (row < 0 || row >= s->a.N) BZ_FAIL(BZ_E_INVALID, "batch sampler set_row: row %d out of range (N = %d)", row, s->a.N);
+  BZ_TRY(bzk_batch_sampler_check_row(p, "batch sampler set_row"));
+  if (n_history < 0 || (n_history > 0 && !history)) BZ_FAIL(BZ_E_INVALID, "batch sampler set_row: bad history (n_history = %d)", n_history);
+  if (draw_index < 0) BZ_FAIL(BZ_E_INVALID, "batch sampler set_row: negative draw index");
+  BsRow r;
+  fill_row(r, p, history, n_history, draw_index);
   std::lock_guard<std::mutex> dlock__(s->dev->mu);
   BZ_HIP(hipSetDevice(s->dev->id));
   BZ_HIP(hipMemcpyAsync(s->a.rows + row, &r, sizeof(r), hipMemcpyHostToDevice, s->dev->stream));   // stream-ordered: after the replays already enqueued

@@ -979,6 +979,135 @@ class BatchDecodeGraph:
         return out
 
 
+class Scheduler:
+    """The engine's host scheduler on its own (bz_sched_*; engine/request_scheduler.rs:105-205): no device is needed."""
+
+    def __init__(self, n_rows, num_blocks, block_size, max_seq_len, prefill_chunk=0):
+        h = C.c_void_p()
+        L.check(L.lib().bz_sched_create(int(n_rows), int(num_blocks), int(block_size), int(max_seq_len), int(prefill_chunk), C.byref(h)))
+        self.h, self.n_rows, self.max_blocks = h, int(n_rows), (int(max_seq_len) + int(block_size) - 1) // int(block_size)
+        self._acts = (L.SchedAction * (3 * self.n_rows))()
+
+    def __del__(self):
+        try:
+            if self.h and L.alive:
+                L.lib().bz_sched_free(self.h)
+        except Exception:
+            pass
+
+    def submit(self, n_prompt, max_tokens):
+        rid = C.c_int64()
+        L.check(L.lib().bz_sched_submit(self.h, int(n_prompt), int(max_tokens), C.byref(rid)))
+        return rid.value
+
+    def step(self):
+        """[(kind, row, id, a, b)]: this step's admissions, prompt chunks and rows going live, in order."""
+        n = C.c_int()
+        L.check(L.lib().bz_sched_step(self.h, self._acts, len(self._acts), C.byref(n)))
+        return [(a.kind, a.row, a.id, a.a, a.b) for a in self._acts[:n.value]]
+
+    def finish(self, rid):
+        L.check(L.lib().bz_sched_finish(self.h, int(rid)))
+
+    def info(self):
+        i = L.SchedInfo()
+        L.check(L.lib().bz_sched_info(self.h, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in L.SchedInfo._fields_}
+
+    def row(self, row):
+        """(request id or -1, its blocks)"""
+        rid, n = C.c_int64(), C.c_int()
+        blocks = np.zeros(self.max_blocks, dtype=np.int32)
+        L.check(L.lib().bz_sched_row(self.h, int(row), C.byref(rid), _ptr(blocks), len(blocks), C.byref(n)))
+        return rid.value, blocks[:n.value].tolist()
+
+
+class BatchEngine:
+    """BatchEngine::run / RequestScheduler::submit (engine/batch_engine.rs:91-169, engine/request_scheduler.rs:105-205) over the batched decode graph: requests
+    come and go while the captured step keeps running; the caller drives with step().  sampler=True: every request samples with its own parameters
+    (the keyword arguments of BatchSampler.set_row); grammar: a GrammarCursor of n_rows rows, borrowed (its rows are handed out by the engine)."""
+
+    def __init__(self, model, n_rows, num_blocks, block_size=16, max_seq_len=None, prefill_chunk=0, depth=2, sampler=True, grammar=None):
+        cfg = L.EngineConfig(n_rows=int(n_rows), num_blocks=int(num_blocks), block_size=int(block_size),
+                             max_seq_len=int(max_seq_len if max_seq_len is not None else model.c.max_seq_len), prefill_chunk=int(prefill_chunk), depth=int(depth),
+                             use_sampler=1 if sampler else 0)
+        h = C.c_void_p()
+        L.check(L.lib().bz_engine_create(model.h, C.byref(cfg), grammar.h if grammar is not None else None, C.byref(h)))
+        self.h, self.model, self.grammar, self.n_rows = h, model, grammar, int(n_rows)
+        self._events = (L.EngineEvent * 256)()
+        self.results = {}
+
+    def __del__(self):
+        try:
+            if self.h and L.alive:
+                L.lib().bz_engine_free(self.h)
+        except Exception:
+            pass
+
+    def submit(self, prompt, max_tokens, stop=(), grammar_state=None, **sampling):
+        p = np.ascontiguousarray(prompt, dtype=np.int64).reshape(-1)
+        stop = [int(t) for t in stop]
+        rq = L.Request(max_tokens=int(max_tokens), n_stop=len(stop), grammar_state=L.GRAMMAR_ROW_FREE if grammar_state is None else int(grammar_state))
+        for i, t in enumerate(stop[:L.ENGINE_MAX_STOP]):
+            rq.stop_ids[i] = t
+        kw = dict(temperature=0.0, top_k=0, top_p=1.0, min_p=0.0, repeat_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0, repeat_last_n=64, seed=0)
+        kw.update(sampling)
+        rq.sampling = L.RowSampling(**kw)
+        rid = C.c_int64()
+        L.check(L.lib().bz_engine_submit(self.h, _ptr(p), len(p), C.byref(rq), C.byref(rid)))
+        return rid.value
+
+    def cancel(self, rid):
+        L.check(L.lib().bz_engine_cancel(self.h, int(rid)))
+
+    def step(self):
+        """One scheduling iteration; False once nothing is waiting, running or unread."""
+        busy = C.c_int()
+        L.check(L.lib().bz_engine_step(self.h, C.byref(busy)))
+        return bool(busy.value)
+
+    def poll(self):
+        """[(id, token, index, finish_reason, replay)] since the last poll; finish_reason -1 running, 0 length, 1 stop, 2 cancelled (token -1)."""
+        out = []
+        while True:
+            n = C.c_int()
+            L.check(L.lib().bz_engine_poll(self.h, self._events, len(self._events), C.byref(n)))
+            out += [(e.id, e.token, e.index, e.finish_reason, e.replay) for e in self._events[:n.value]]
+            if n.value < len(self._events):
+                return out
+
+    def stats(self):
+        s = L.EngineStats()
+        L.check(L.lib().bz_engine_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in L.EngineStats._fields_}
+
+    def read_status(self, replay):
+        """(status words int32 [n_rows]: 0 idle, 1 token, 2 + 4 * reason finished; rows still live after that replay)"""
+        st, live = np.zeros(self.n_rows, dtype=np.int32), C.c_int32()
+        L.check(L.lib().bz_engine_read_status(self.h, int(replay), _ptr(st), C.byref(live)))
+        return st, live.value
+
+    def collect(self, events, into=None):
+        """Fold events into {id: [tokens, finish_reason]}."""
+        into = self.results if into is None else into
+        for rid, tok, _, fin, _ in events:
+            r = into.setdefault(rid, [[], -1])
+            if tok >= 0:
+                r[0].append(int(tok))
+            if fin >= 0:
+                r[1] = fin
+        return into
+
+    def run_until_idle(self):
+        """step() until nothing is left; {id: (tokens, finish_reason)} of everything that produced events since the last call."""
+        res = {}
+        busy = True
+        while busy:
+            busy = self.step()
+            self.collect(self.poll(), res)
+        return {k: (v[0], v[1]) for k, v in res.items()}
+
+
 class DecodeGraph:
     """inference::decode_graph::DecodeGraph (cuda_graphs.rs:97-189) as a hipGraph."""
 

@@ -429,6 +429,73 @@ int bz_decode_graph_capture_paged_grammar(bz_model* m, bz_paged_kv* kv, int max_
 int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, bz_grammar* g /*nullable*/, const uint8_t* vocab_bytes,
                         const int64_t* offsets, int64_t V, int64_t* out_tokens, bz_gen_stats* stats);
 
+/* ---- continuous batching: the request engine (engine/batch_engine.rs:91-169, 172-319, 322-445; engine/request_scheduler.rs:105-205;
+ * config/inference.rs:89-90,136,142: max_batch_size, prefill_chunk_size, kv_pool_blocks) ------------------------------------------------
+ * The scheduler (engine/request_scheduler.rs:105-205; batch_engine.rs:172-272 for the chunked prompt): host only, no device call, a pure function of its inputs.
+ * The pool's last n_rows blocks are the rows' park blocks (row r parks in block num_blocks - n_rows + r); requests share the others.  Admission is FIFO without
+ * skipping ahead: the head of the queue enters when a row is free and ceil((n_prompt + max_tokens) / block_size) blocks are free; it takes the lowest free row and the
+ * lowest free blocks, all of them at once (growing on demand would need preemption).  prefill_chunk (0 = unlimited) prompt tokens per step over the admitted requests
+ * that are not live yet, in admission order; a request prefills prompt[:-1] and becomes live in the step that completes it.  Ids count up from 0.
+ *   step: the actions of one engine step, in order: BZ_SCHED_ADMIT {id, row, a = number of blocks}, BZ_SCHED_PREFILL {id, row, a .. b = prompt range},
+ *         BZ_SCHED_LIVE {id, row}.  At most 3 * n_rows actions.
+ *   finish: the request's end was harvested (or it was cancelled): its row and blocks are free from the next step on; a waiting request just leaves the queue. */
+typedef struct bz_sched bz_sched;
+enum { BZ_SCHED_ADMIT = 0, BZ_SCHED_PREFILL = 1, BZ_SCHED_LIVE = 2 };
+typedef struct { int32_t kind, row; int64_t id; int32_t a, b; } bz_sched_action;
+typedef struct { int32_t n_rows, num_blocks, park_blocks, free_blocks, owned_blocks, waiting, admitted, live; } bz_sched_info_t;
+int bz_sched_create(int n_rows, int num_blocks, int block_size, int max_seq_len, int prefill_chunk, bz_sched** out);
+int bz_sched_free(bz_sched* s);
+int bz_sched_submit(bz_sched* s, int n_prompt, int max_tokens, int64_t* id_out);
+int bz_sched_step(bz_sched* s, bz_sched_action* out, int max_out, int* n_out);
+int bz_sched_finish(bz_sched* s, int64_t id);
+int bz_sched_info(const bz_sched* s, bz_sched_info_t* out);
+int bz_sched_row(const bz_sched* s, int row, int64_t* id_out /*-1: free*/, int32_t* blocks_out /*nullable*/, int max_blocks, int* n_blocks_out);
+/* The engine (batch_engine.rs:91-169 BatchEngine::run, 322-445 the decode step and its harvest): one captured step of n_rows rows over a paged pool the engine owns;
+ * every row is live or idle ON THE DEVICE, a live row ends there (stop id, or max_tokens reached) in the launch that sees its token, so several replays can be in
+ * flight and their records read late.  An idle row feeds token 0 at position 0 of its own park block.  The caller drives: bz_engine_step is one scheduling iteration,
+ * the library starts no thread.  Eligibility and refusals at create are those of bz_decode_batch_graph_capture (Mamba2 / DeepSeek-V2: BZ_E_UNSUPPORTED).
+ *   step, in this order: (1) once `depth` replays are unread, wait for the oldest one's event and turn its record into events, releasing the rows and blocks of
+ *     finished requests; (2) the scheduler's admissions and prompt chunks (bz_forward_paged on prompt[:-1]) and, for a request whose prompt is complete, the row
+ *     writes that make it live (prompt[-1] at seq_len = n_prompt: its first token is draw 0 of the batched step, history = the prompt, masked from grammar_state) --
+ *     all stream-ordered behind the replays already enqueued, without a read from the device or a wait; (3) one replay if any row is live in the host's view, else
+ *     every unread record is drained.  busy_out = 0 when nothing is waiting, admitted or unread.
+ *   submit: BZ_E_INVALID naming the figure when n_prompt + max_tokens > max_seq_len, when the request could never fit the pool, with more than 8 stop ids, with
+ *     sampling other than greedy without penalties on an engine without a sampler, with a grammar state on an engine without a cursor.
+ *   cancel: a waiting request leaves the queue; an admitted one's row is made idle by a stream-ordered write and its row and blocks are released; tokens of it that
+ *     replays in flight still produce are dropped.  One event with finish_reason 2 (token -1) is queued.
+ *   poll: events in order; a stop id is delivered as the request's last token (as bz_generate delivers eos_id).
+ * The engine borrows the model and the cursor (free the engine first) and owns pool, sampler and graph. */
+typedef struct {
+  int32_t n_rows;          /* 2..512 */
+  int32_t num_blocks;      /* the pool, park blocks (n_rows of them) included */
+  int32_t block_size;
+  int32_t max_seq_len;     /* per request: n_prompt + max_tokens; sets the block-table width */
+  int32_t prefill_chunk;   /* prompt tokens per step, 0 = unlimited */
+  int32_t depth;           /* replays in flight before the oldest record is read, 1..64 */
+  int32_t use_sampler;     /* 1: the batched sampler picks (per-request parameters); 0: greedy argmax */
+  int32_t reserved[9];
+} bz_engine_config;
+typedef struct {
+  int32_t max_tokens;
+  int32_t n_stop; int64_t stop_ids[8];
+  uint32_t grammar_state;  /* BZ_GRAMMAR_ROW_FREE: unconstrained */
+  int32_t reserved[3];
+  bz_row_sampling sampling;
+} bz_request;
+typedef struct { int64_t id; int64_t token; int32_t index; int32_t finish_reason; /* -1 running, 0 length, 1 stop, 2 cancelled */ int64_t replay; } bz_engine_event;
+typedef struct { int64_t replays; int32_t free_blocks, total_blocks, park_blocks, live_rows, admitted, waiting, unread; int64_t prompt_tokens, generated_tokens;
+                 double admit_host_ms; /* host time spent enqueueing prompt chunks and row writes */ } bz_engine_stats_t;
+typedef struct bz_engine bz_engine;
+int bz_engine_create(bz_model* m, const bz_engine_config* cfg, bz_grammar_cursor* cursor /*nullable, borrowed*/, bz_engine** out);
+int bz_engine_submit(bz_engine* e, const int64_t* prompt, int n_prompt, const bz_request* rq, int64_t* id_out);
+int bz_engine_cancel(bz_engine* e, int64_t id);
+int bz_engine_step(bz_engine* e, int* busy_out);
+int bz_engine_poll(bz_engine* e, bz_engine_event* out, int max_events, int* n_out);
+int bz_engine_stats(bz_engine* e, bz_engine_stats_t* out);
+/* the status words (0 idle, 1 token, 2 + 4 * reason finished) of replay `replay` (within the last 1024), host [n_rows]; waits for that replay */
+int bz_engine_read_status(bz_engine* e, int64_t replay, int32_t* status_out, int32_t* live_after_out /*nullable*/);
+int bz_engine_free(bz_engine* e);
+
 /* ---- speculative decoding (engine/generate_text.rs:41-44,61-136; engine/speculative.rs:99-125; config/inference.rs:197-208) -----------------
  * The reference takes this path whenever inference.speculative is configured (draft_model, num_speculative_tokens default 5, adaptive_depth) and hands the
  * work to boostr's SpeculativeModel::forward.  Here: a draft model proposes k tokens with k decode steps, the target verifies [t, d1 .. dk] (t = the last

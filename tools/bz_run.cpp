@@ -7,11 +7,17 @@
 //          [--repeat-penalty R] [--seed S] [--graphs] [--paged-attention] [--device D] [--stats]
 //          [--grammar FILE --vocab-bytes FILE [--grammar-regular]]
 //          [--draft <checkpoint> [--spec-tokens k] [--spec-adaptive]]
+//   bz-run <model> --requests FILE --rows N [--pool-blocks B] [--prefill-chunk C] [--depth D] [sampling options, --eos]
+// --requests: continuous batching (BatchEngine::run, engine/batch_engine.rs:91-169; RequestScheduler::submit, engine/request_scheduler.rs:105-205) over N rows.  The file
+// has one request per line, `max_tokens;comma-separated prompt ids`; all are submitted, the engine is stepped until idle, and one line of ids per request is
+// printed in submission order; the engine's statistics go to stderr.  --pool-blocks: the paged pool (default: every row can hold a full-length request);
+// the sampling options apply to every request (request i draws with seed + i), --eos is its stop id.
 // --draft: speculative decoding (inference.speculative, config/inference.rs:197-208; generate_text.rs:61-136) with that checkpoint as the draft model: greedy only,
 // the same ids as without it; iterations / accepted / rejected go to stderr (generate_text.rs:130-135).
 // --grammar: a GBNF file (gen_config.grammar, executor_generate.rs:96-121), compiled with the reference's semantics or, with --grammar-regular, as the regular subset of
 // GBNF; with --graphs (Llama family, no penalty) the captured step carries the DFA state on the device.  --vocab-bytes: the bytes of every token, which blazr takes from its tokenizer (executor_generate.rs:104-113): u32 V, u32 offsets[V+1], then the bytes.
 // prints the generated ids, comma separated, on stdout.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,6 +48,7 @@ int main(int argc, char** argv) {
   int device_id = 0; bool stats_on = false;
   std::string grammar_path, vocab_path; bool grammar_regular = false;
   std::string draft_path; bz_spec_config sc;
+  std::string requests_path; int rows = 0, pool_blocks = 0, prefill_chunk = 0, depth = 2;
   memset(&sc, 0, sizeof sc);
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
@@ -65,7 +72,85 @@ int main(int argc, char** argv) {
     else if (a == "--draft") draft_path = next("--draft");
     else if (a == "--spec-tokens") sc.num_speculative_tokens = atoi(next("--spec-tokens"));
     else if (a == "--spec-adaptive") sc.adaptive_depth = 1;
+    else if (a == "--requests") requests_path = next("--requests");
+    else if (a == "--rows") rows = atoi(next("--rows"));
+    else if (a == "--pool-blocks") pool_blocks = atoi(next("--pool-blocks"));
+    else if (a == "--prefill-chunk") prefill_chunk = atoi(next("--prefill-chunk"));
+    else if (a == "--depth") depth = atoi(next("--depth"));
     else { fprintf(stderr, "bz-run: unknown option %s\n", a.c_str()); return 2; }
+  }
+  if (!requests_path.empty()) {
+    if (rows < 2) { fprintf(stderr, "bz-run: --requests needs --rows N (2..512)\n"); return 2; }
+    if (!draft_path.empty() || !grammar_path.empty() || !prompt.empty()) { fprintf(stderr, "bz-run: --requests goes without --prompt, --draft and --grammar\n"); return 2; }
+    std::string text;
+    if (!read_file(requests_path, text)) { fprintf(stderr, "bz-run: cannot read %s\n", requests_path.c_str()); return 2; }
+    struct Req { int max_tokens; std::vector<int64_t> prompt; std::vector<int64_t> out; };
+    std::vector<Req> reqs;
+    size_t at = 0; int longest = 0;
+    while (at < text.size()) {
+      size_t nl = text.find('\n', at);
+      if (nl == std::string::npos) nl = text.size();
+      const std::string line = text.substr(at, nl - at);
+      at = nl + 1;
+      if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+      const size_t semi = line.find(';');
+      if (semi == std::string::npos) { fprintf(stderr, "bz-run: %s: line %zu is not `max_tokens;id,id,...`\n", requests_path.c_str(), reqs.size() + 1); return 2; }
+      Req r; r.max_tokens = atoi(line.c_str());
+      const char* q = line.c_str() + semi + 1; char* end;
+      while (*q) { const long long v = strtoll(q, &end, 10); if (end == q) break; r.prompt.push_back(v); q = *end == ',' ? end + 1 : end; }
+      if (r.max_tokens < 1 || r.prompt.empty()) { fprintf(stderr, "bz-run: %s: request %zu needs max_tokens >= 1 and a prompt\n", requests_path.c_str(), reqs.size() + 1); return 2; }
+      longest = std::max(longest, (int)r.prompt.size() + r.max_tokens);
+      reqs.push_back(r);
+    }
+    if (reqs.empty()) { fprintf(stderr, "bz-run: %s holds no request\n", requests_path.c_str()); return 2; }
+    bz_device* dev = nullptr;
+    if (bz_device_open(device_id, &dev) != BZ_OK) return fail("device");
+    bz_model* m = nullptr; bz_model_config cfg;
+    if (bz_load_model(dev, model.c_str(), &m, &cfg) != BZ_OK) return fail("load");
+    bz_engine_config ec;
+    memset(&ec, 0, sizeof ec);
+    ec.n_rows = rows; ec.block_size = gc.block_size; ec.max_seq_len = std::min(longest, cfg.max_seq_len); ec.prefill_chunk = prefill_chunk; ec.depth = depth;
+    const int per = (ec.max_seq_len + ec.block_size - 1) / ec.block_size;
+    ec.num_blocks = pool_blocks > 0 ? pool_blocks : rows * per + rows;       // one park block per row on top
+    const bool greedy = gc.temperature == 0.0f && gc.repeat_penalty == 1.0f && gc.frequency_penalty == 0.0f && gc.presence_penalty == 0.0f;
+    ec.use_sampler = greedy ? 0 : 1;
+    bz_engine* e = nullptr;
+    if (bz_engine_create(m, &ec, nullptr, &e) != BZ_OK) return fail("engine");
+    for (size_t i = 0; i < reqs.size(); i++) {
+      bz_request rq;
+      memset(&rq, 0, sizeof rq);
+      rq.max_tokens = reqs[i].max_tokens; rq.grammar_state = BZ_GRAMMAR_ROW_FREE;
+      if (gc.eos_id >= 0) { rq.n_stop = 1; rq.stop_ids[0] = gc.eos_id; }
+      rq.sampling.temperature = gc.temperature; rq.sampling.top_k = gc.top_k; rq.sampling.top_p = gc.top_p; rq.sampling.min_p = gc.min_p;
+      rq.sampling.repeat_penalty = gc.repeat_penalty; rq.sampling.frequency_penalty = gc.frequency_penalty; rq.sampling.presence_penalty = gc.presence_penalty;
+      rq.sampling.repeat_last_n = gc.repeat_last_n; rq.sampling.seed = gc.seed + i;
+      int64_t id = -1;
+      if (bz_engine_submit(e, reqs[i].prompt.data(), (int)reqs[i].prompt.size(), &rq, &id) != BZ_OK) return fail("submit");
+      if (id != (int64_t)i) { fprintf(stderr, "bz-run: request %zu got id %lld\n", i, (long long)id); return 1; }
+    }
+    int busy = 1;
+    bz_engine_event ev[256];
+    while (busy) {
+      if (bz_engine_step(e, &busy) != BZ_OK) return fail("step");
+      int n = 0;
+      do {
+        if (bz_engine_poll(e, ev, 256, &n) != BZ_OK) return fail("poll");
+        for (int k = 0; k < n; k++) if (ev[k].token >= 0) reqs[(size_t)ev[k].id].out.push_back(ev[k].token);
+      } while (n == 256);
+    }
+    for (const Req& r : reqs) {
+      for (size_t k = 0; k < r.out.size(); k++) printf(k ? ",%lld" : "%lld", (long long)r.out[k]);
+      printf("\n");
+    }
+    bz_engine_stats_t es;
+    if (bz_engine_stats(e, &es) != BZ_OK) return fail("stats");
+    fprintf(stderr, "engine: %lld replays, %d / %d blocks free (%d park), %d live rows, %d waiting, %lld prompt tokens, %lld generated tokens, %.2f ms host time in admissions\n",
+            (long long)es.replays, es.free_blocks, es.total_blocks, es.park_blocks, es.live_rows, es.waiting, (long long)es.prompt_tokens, (long long)es.generated_tokens,
+            es.admit_host_ms);
+    bz_engine_free(e);
+    bz_model_free(m);
+    bz_device_close(dev);
+    return 0;
   }
   if (prompt.empty()) { fprintf(stderr, "bz-run: --prompt id,id,... is required\n"); return 2; }
   if (!draft_path.empty() && !grammar_path.empty()) { fprintf(stderr, "bz-run: --draft and --grammar do not go together\n"); return 2; }
