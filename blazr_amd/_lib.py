@@ -114,7 +114,7 @@ class RowSampling(C.Structure):
 
 
 ENGINE_MAX_STOP = 8
-SCHED_ADMIT, SCHED_PREFILL, SCHED_LIVE = 0, 1, 2
+SCHED_ADMIT, SCHED_PREFILL, SCHED_LIVE, SCHED_COPY = 0, 1, 2, 3
 
 
 class SchedAction(C.Structure):
@@ -126,9 +126,20 @@ class SchedInfo(C.Structure):
                 ("waiting", C.c_int32), ("admitted", C.c_int32), ("live", C.c_int32)]
 
 
+class SchedPrefixInfo(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("cached_blocks", C.c_int32), ("evictable_blocks", C.c_int32), ("referenced_blocks", C.c_int32),
+                ("hits", C.c_int64), ("misses", C.c_int64), ("cached_tokens", C.c_int64), ("evictions", C.c_int64)]
+
+
+class EnginePrefixStats(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("cached_blocks", C.c_int32), ("evictable_blocks", C.c_int32), ("referenced_blocks", C.c_int32),
+                ("private_blocks", C.c_int32), ("reserved", C.c_int32), ("hits", C.c_int64), ("misses", C.c_int64), ("cached_tokens", C.c_int64),
+                ("evictions", C.c_int64), ("prompt_tokens_skipped", C.c_int64), ("copy_launches", C.c_int64), ("copied_blocks", C.c_int64)]
+
+
 class EngineConfig(C.Structure):
     _fields_ = [("n_rows", C.c_int32), ("num_blocks", C.c_int32), ("block_size", C.c_int32), ("max_seq_len", C.c_int32), ("prefill_chunk", C.c_int32),
-                ("depth", C.c_int32), ("use_sampler", C.c_int32), ("reserved", C.c_int32 * 9)]
+                ("depth", C.c_int32), ("use_sampler", C.c_int32), ("prefix_cache", C.c_int32), ("reserved", C.c_int32 * 8)]
 
 
 class Request(C.Structure):
@@ -184,6 +195,8 @@ SYMBOLS = {
     "bz_paged_kv_free": (C.c_int, [P]),
     "bz_paged_kv_set_seq_len": (C.c_int, [P, C.c_int]),
     "bz_paged_kv_seq_len": (C.c_int, [P]),
+    "bz_paged_kv_copy_slots": (C.c_int, [P, C.c_int, C.c_int, C.c_int]),
+    "bz_paged_kv_read_block": (C.c_int, [P, C.c_int, C.c_int, C.c_int, P, C.c_size_t]),
     "bz_forward_kv": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.c_uint32]),
     "bz_forward_paged": (C.c_int, [P, P, C.c_int, P, P, P, C.c_int, C.c_int, C.c_int, P, C.c_uint32]),
     "bz_forward_embed": (C.c_int, [P, P, C.c_int, P]),
@@ -290,6 +303,12 @@ SYMBOLS = {
     "bz_sched_finish": (C.c_int, [P, C.c_int64]),
     "bz_sched_info": (C.c_int, [P, C.POINTER(SchedInfo)]),
     "bz_sched_row": (C.c_int, [P, C.c_int, C.POINTER(C.c_int64), P, C.c_int, C.POINTER(C.c_int)]),
+    "bz_sched_enable_prefix": (C.c_int, [P]),
+    "bz_sched_submit_tokens": (C.c_int, [P, P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "bz_sched_prefix_info": (C.c_int, [P, C.POINTER(SchedPrefixInfo)]),
+    "bz_sched_prefix_flush": (C.c_int, [P, C.POINTER(C.c_int)]),
+    "bz_engine_prefix_stats": (C.c_int, [P, C.POINTER(EnginePrefixStats)]),
+    "bz_engine_prefix_flush": (C.c_int, [P, C.POINTER(C.c_int)]),
     "bz_engine_create": (C.c_int, [P, C.POINTER(EngineConfig), P, C.POINTER(P)]),
     "bz_engine_submit": (C.c_int, [P, P, C.c_int, C.POINTER(Request), C.POINTER(C.c_int64)]),
     "bz_engine_cancel": (C.c_int, [P, C.c_int64]),

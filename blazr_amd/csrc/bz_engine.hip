@@ -10,6 +10,8 @@
 //   k_engine_finish    the step's last launch (after the pick and the grammar advance).  Live row: left -= 1; ends on a stop id (reason 1), else on
 //                      left == 0 (reason 0).  A row that ends becomes idle here: live = 0, pos = 0, table[row][0] = its park block, its grammar state FREE.
 //                      One status word per row and the number of rows still live go to pinned rings beside the token log.  One workgroup, N <= 512.
+//   k_kv_copy_slots    the prefix cache's copy-on-write: the first j slots of a cached block into a request's own block, every layer, K and V, every KV head;
+//                      one launch for all copies of a step, the (source, destination, j) triples read from device memory.
 // Parking costs the pool one block per row (the last n_rows blocks).
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -68,6 +70,36 @@ __global__ __launch_bounds__(512) void k_engine_finish(EngRow* rows, const long 
   const int cnt = __syncthreads_count(still);
   if (i == 0) nlive[at] = cnt;
 }
+// The pool is [layer][block][kv_head][block_size][hd]: per (layer, K|V, head) the first j slots of a block are one contiguous run of j * hd elements, a multiple
+// of 16 bytes (hd % 8 == 0, elements of 2 or 4 bytes).  blockIdx.y = the triple, blockIdx.x * 256 + threadIdx.x = the 16-byte vector within the triple's
+// layers * 2 * n_kv runs; the grid is sized by the host for the step's largest j, a thread beyond its own triple's bytes leaves.  A triple out of range copies nothing.
+__global__ __launch_bounds__(256) void k_kv_copy_slots(uint4* k, uint4* v, const int* triples, int layers, int num_blocks, int n_kv, int bs, int row_vecs) {
+  const int* t = triples + 3 * blockIdx.y;
+  const int src = t[0], dst = t[1], j = t[2];
+  if (src < 0 || src >= num_blocks || dst < 0 || dst >= num_blocks || src == dst || j < 1 || j > bs) return;
+  const long long run_vecs = (long long)j * row_vecs;                  // 16-byte vectors per (layer, K|V, head)
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= run_vecs * layers * 2 * n_kv) return;
+  const long long run = i / run_vecs, off = i % run_vecs;
+  const int head = (int)(run % n_kv), which = (int)((run / n_kv) & 1), layer = (int)(run / (2 * n_kv));
+  const long long head_vecs = (long long)bs * row_vecs;
+  uint4* base = which ? v : k;
+  const long long lb = (long long)layer * num_blocks;
+  base[((lb + dst) * n_kv + head) * head_vecs + off] = base[((lb + src) * n_kv + head) * head_vecs + off];
+}
+// n triples (int32 x 3, device memory), max_j = the largest slot count among them (sizes the grid)
+int bzk_kv_copy_slots(hipStream_t s, bz_paged_kv* kv, const int* d_triples, int n, int max_j) {
+  if (n < 1) return BZ_OK;
+  const size_t row_bytes = (size_t)kv->hd * bz_dtype_size(kv->dtype);
+  if (row_bytes % 16) BZ_FAIL(BZ_E_INVALID, "kv copy_slots: a row of %zu bytes (head_dim = %d) is no multiple of 16", row_bytes, kv->hd);
+  if (max_j < 1 || max_j > kv->block_size) BZ_FAIL(BZ_E_INVALID, "kv copy_slots: %d slots outside 1 .. block_size = %d", max_j, kv->block_size);
+  const int row_vecs = (int)(row_bytes / 16);
+  const long long vecs = (long long)max_j * row_vecs * kv->layers * 2 * kv->n_kv;
+  hipLaunchKernelGGL(k_kv_copy_slots, dim3((unsigned)((vecs + 255) / 256), n), dim3(256), 0, s, (uint4*)kv->k, (uint4*)kv->v, d_triples, kv->layers, kv->num_blocks, kv->n_kv,
+                     kv->block_size, row_vecs);
+  BZ_HIP(hipGetLastError());
+  return BZ_OK;
+}
 int bzk_engine_advance(hipStream_t s, long long* tok, const long long* next, int* pos, int* slot, const int* table, int stride, int bs, int N, const EngRow* rows) {
   hipLaunchKernelGGL(k_engine_advance, dim3((N + 63) / 64), dim3(64), 0, s, tok, next, pos, slot, table, stride, bs, N, rows);
   BZ_HIP(hipGetLastError());
@@ -85,7 +117,7 @@ int bzk_engine_finish(hipStream_t s, EngRow* rows, const long long* next, int* p
 // host
 // ---------------------------------------------------------------------------------------------------------
 namespace {
-struct EngReq { int64_t id = -1; std::vector<int64_t> prompt; bz_request rq{}; int row = -1; bool live = false; int produced = 0; long long first_replay = -1; };
+struct EngReq { int64_t id = -1; std::vector<int64_t> prompt; bz_request rq{}; int row = -1; bool live = false; int produced = 0; long long first_replay = -1; int shared = 0; };
 // pinned staging for the stream-ordered writes: a slot is reused only after the stream has passed the copies that read it
 struct Stage { char* host = nullptr; hipEvent_t ev = nullptr; bool pending = false; };
 struct RowMisc { long long next; int pos, pad; EngRow er; uint32_t gram[2]; };
@@ -95,8 +127,8 @@ struct bz_engine {
   bz_grammar_cursor* cursor = nullptr; bz_batch_sampler* sampler = nullptr; bz_paged_kv* kv = nullptr; bz_sched* sched = nullptr; bz_batch_graph* g = nullptr;
   EngRow* d_rows = nullptr; int* status = nullptr; int* nlive = nullptr;
   int max_blocks = 0, max_chunk = 0;
-  long long* d_ptok = nullptr; int* d_pslot = nullptr; int* d_ptable = nullptr; bz_tensor* plogits = nullptr;
-  std::vector<Stage> stages; size_t off_misc = 0, off_bs = 0, off_ptok = 0, off_pslot = 0, stage_bytes = 0; int stage_next = 0;
+  long long* d_ptok = nullptr; int* d_pslot = nullptr; int* d_ptable = nullptr; int* d_copy = nullptr; bz_tensor* plogits = nullptr;
+  std::vector<Stage> stages; size_t off_misc = 0, off_bs = 0, off_ptok = 0, off_pslot = 0, off_copy = 0, stage_bytes = 0; int stage_next = 0;
   std::vector<hipEvent_t> rev;               // one event per replay in flight (ring)
   long long read = 0;                        // records harvested; g->replays = enqueued
   std::map<int64_t, EngReq> reqs;            // waiting and admitted
@@ -104,6 +136,7 @@ struct bz_engine {
   std::vector<bz_sched_action> acts;
   std::deque<bz_engine_event> events;
   long long prompt_tokens = 0, generated = 0; double admit_ms = 0;
+  long long skipped = 0, copy_launches = 0, copied_blocks = 0;   // prefix cache
   static const int EVRING = 128;
 };
 
@@ -125,7 +158,7 @@ extern "C" int bz_engine_free(bz_engine* e) {
   if (e->kv) bz_paged_kv_free(e->kv);
   if (e->sched) bz_sched_free(e->sched);
   if (e->plogits) bz_tensor_free(e->plogits);
-  for (void* p : {(void*)e->d_rows, (void*)e->d_ptok, (void*)e->d_pslot, (void*)e->d_ptable}) if (p) hipFree(p);
+  for (void* p : {(void*)e->d_rows, (void*)e->d_ptok, (void*)e->d_pslot, (void*)e->d_ptable, (void*)e->d_copy}) if (p) hipFree(p);
   if (e->status) hipHostFree(e->status);
   if (e->nlive) hipHostFree(e->nlive);
   for (Stage& s : e->stages) { if (s.host) hipHostFree(s.host); if (s.ev) hipEventDestroy(s.ev); }
@@ -150,6 +183,7 @@ extern "C" int bz_engine_create(bz_model* m, const bz_engine_config* cfg, bz_gra
   if (cfg->max_seq_len < 2 || cfg->max_seq_len > mc.max_seq_len)
     BZ_FAIL(BZ_E_INVALID, "engine create: max_seq_len = %d out of range (2 .. the model's %d)", cfg->max_seq_len, mc.max_seq_len);
   if (cfg->num_blocks <= cfg->n_rows) BZ_FAIL(BZ_E_INVALID, "engine create: num_blocks = %d leaves nothing beside the %d park blocks", cfg->num_blocks, cfg->n_rows);
+  if (cfg->prefix_cache != 0 && cfg->prefix_cache != 1) BZ_FAIL(BZ_E_INVALID, "engine create: prefix_cache = %d (0 = off, 1 = on)", cfg->prefix_cache);
   const int N = cfg->n_rows;
   bz_device* dev = bzi_model_device(m);
   if (!dev) BZ_FAIL(BZ_E_INVALID, "engine create: model not finalized");
@@ -160,10 +194,11 @@ extern "C" int bz_engine_create(bz_model* m, const bz_engine_config* cfg, bz_gra
   e->max_blocks = (cfg->max_seq_len + cfg->block_size - 1) / cfg->block_size;
   e->max_chunk = cfg->prefill_chunk > 0 ? std::min(cfg->prefill_chunk, cfg->max_seq_len) : cfg->max_seq_len;
   e->row_req.assign(N, -1);
-  e->acts.resize(3 * (size_t)N);
+  e->acts.resize((cfg->prefix_cache ? 4 : 3) * (size_t)N);
   int rc = BZ_OK;
   auto fail = [&](int code) { bz_engine_free(e); return code; };
   if ((rc = bz_sched_create(N, cfg->num_blocks, cfg->block_size, cfg->max_seq_len, cfg->prefill_chunk, &e->sched)) != BZ_OK) return fail(rc);
+  if (cfg->prefix_cache && (rc = bz_sched_enable_prefix(e->sched)) != BZ_OK) return fail(rc);
   const int kvdt = mc.act_dtype;
   if ((rc = bz_paged_kv_create(dev, mc.n_layers, cfg->num_blocks, cfg->block_size, mc.n_kv_heads, mc.head_dim, kvdt, &e->kv)) != BZ_OK) return fail(rc);
   if (cfg->use_sampler && (rc = bz_batch_sampler_create(dev, N, mc.vocab, &e->sampler)) != BZ_OK) return fail(rc);
@@ -171,20 +206,21 @@ extern "C" int bz_engine_create(bz_model* m, const bz_engine_config* cfg, bz_gra
   if ((rc = bzi_prefill_reserve(m, std::max(N, e->max_chunk))) != BZ_OK) return fail(rc);
   const size_t ring = (size_t)bz_batch_graph::LOGCAP;
   if (hipMalloc(&e->d_rows, (size_t)N * sizeof(EngRow)) != hipSuccess || hipMalloc(&e->d_ptok, (size_t)e->max_chunk * 8) != hipSuccess ||
-      hipMalloc(&e->d_pslot, (size_t)e->max_chunk * 4) != hipSuccess || hipMalloc(&e->d_ptable, (size_t)e->max_blocks * 4) != hipSuccess ||
+      hipMalloc(&e->d_pslot, (size_t)e->max_chunk * 4) != hipSuccess || hipMalloc(&e->d_ptable, (size_t)e->max_blocks * 4) != hipSuccess || hipMalloc(&e->d_copy, (size_t)N * 12) != hipSuccess ||
       hipHostMalloc(&e->status, ring * N * 4, hipHostMallocDefault) != hipSuccess || hipHostMalloc(&e->nlive, ring * 4, hipHostMallocDefault) != hipSuccess) {
     (void)hipGetLastError(); bz_set_error("engine create: out of memory"); return fail(BZ_E_OOM);
   }
   memset(e->status, 0, ring * N * 4); memset(e->nlive, 0, ring * 4);
   const int64_t shp[2] = {1, mc.vocab};
   if ((rc = bz_tensor_zeros(dev, BZ_F32, shp, 2, &e->plogits)) != BZ_OK) return fail(rc);
-  // staging slots: [table row][RowMisc][sampler row][prompt chunk tokens][prompt chunk slots]
+  // staging slots: [table row][RowMisc][sampler row][prompt chunk tokens][prompt chunk slots][copy triples]
   auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
   e->off_misc = up((size_t)e->max_blocks * 4);
   e->off_bs = e->off_misc + up(sizeof(RowMisc));
   e->off_ptok = e->off_bs + up(bzk_batch_sampler_row_bytes());
   e->off_pslot = e->off_ptok + up((size_t)e->max_chunk * 8);
-  e->stage_bytes = e->off_pslot + up((size_t)e->max_chunk * 4);
+  e->off_copy = e->off_pslot + up((size_t)e->max_chunk * 4);
+  e->stage_bytes = e->off_copy + up((size_t)N * 12);
   e->stages.resize(std::min(64, std::max(8, 2 * N)));
   for (Stage& s : e->stages)
     if (hipHostMalloc((void**)&s.host, e->stage_bytes, hipHostMallocDefault) != hipSuccess || hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) {
@@ -230,7 +266,8 @@ extern "C" int bz_engine_submit(bz_engine* e, const int64_t* prompt, int n_promp
       BZ_FAIL(BZ_E_INVALID, "engine submit: grammar_state = %u is not below the grammar's %d states", rq->grammar_state, bzk_grammar_cursor_num_states(e->cursor));
   }
   int64_t id = -1;
-  BZ_TRY(bz_sched_submit(e->sched, n_prompt, rq->max_tokens, &id));     // (names the figure when the request could never fit the pool)
+  if (e->cfg.prefix_cache) BZ_TRY(bz_sched_submit_tokens(e->sched, prompt, n_prompt, rq->max_tokens, &id));
+  else BZ_TRY(bz_sched_submit(e->sched, n_prompt, rq->max_tokens, &id));  // (names the figure when the request could never fit the pool)
   EngReq& r = e->reqs[id];
   r.id = id; r.prompt.assign(prompt, prompt + n_prompt); r.rq = *rq;
   *id_out = id;
@@ -346,6 +383,16 @@ static int eng_go_live(bz_engine* e, EngReq& q, const int32_t* blocks, int nb) {
   return BZ_OK;
 }
 
+// the step's copy-on-write triples: staged, uploaded and served by one launch, stream-ordered like every other admission write
+static int eng_copies(bz_engine* e, Stage* s, int n, int max_j) {
+  hipStream_t st = e->dev->stream;
+  BZ_HIP(hipMemcpyAsync(e->d_copy, s->host + e->off_copy, (size_t)n * 12, hipMemcpyHostToDevice, st));
+  BZ_TRY(eng_stage_done(e, s));
+  BZ_TRY(bzk_kv_copy_slots(st, e->kv, e->d_copy, n, max_j));
+  e->copy_launches++; e->copied_blocks += n;
+  return BZ_OK;
+}
+
 extern "C" int bz_engine_step(bz_engine* e, int* busy_out) {
   BZ_API_BEGIN
   if (!e) BZ_FAIL(BZ_E_INVALID, "engine step: null engine");
@@ -358,16 +405,27 @@ extern "C" int bz_engine_step(bz_engine* e, int* busy_out) {
   if (na > 0) {
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<int32_t> blocks(e->max_blocks);
+    Stage* cs = nullptr; int ncopy = 0, max_j = 0;         // this step's copies: one launch, ahead of the step's prompt chunks (admissions come first in the list)
     for (int i = 0; i < na; i++) {
       const bz_sched_action& a = e->acts[i];
       EngReq& q = e->reqs.at(a.id);
-      if (a.kind == BZ_SCHED_ADMIT) { q.row = a.row; e->row_req[a.row] = a.id; continue; }
+      if (a.kind == BZ_SCHED_ADMIT) { q.row = a.row; q.shared = a.b; e->row_req[a.row] = a.id; e->skipped += (long long)a.b * e->cfg.block_size; continue; }
       int64_t rid = -1; int nb = 0;
       BZ_TRY(bz_sched_row(e->sched, a.row, &rid, blocks.data(), e->max_blocks, &nb));
+      if (a.kind == BZ_SCHED_COPY) {
+        if (ncopy >= e->cfg.n_rows || q.shared >= nb) BZ_FAIL(BZ_E_INVALID, "engine step: copy %d of a step, destination index %d of %d blocks", ncopy, q.shared, nb);
+        if (!cs) BZ_TRY(eng_stage(e, &cs));
+        int* tr = (int*)(cs->host + e->off_copy) + 3 * ncopy++;
+        tr[0] = a.a; tr[1] = blocks[q.shared]; tr[2] = a.b;
+        max_j = std::max(max_j, a.b); e->skipped += a.b;
+        continue;
+      }
+      if (cs) { BZ_TRY(eng_copies(e, cs, ncopy, max_j)); cs = nullptr; }
       if (a.kind == BZ_SCHED_PREFILL) {
         for (int c0 = a.a; c0 < a.b; c0 += e->max_chunk) BZ_TRY(eng_prefill(e, q, c0, std::min(a.b, c0 + e->max_chunk), blocks.data(), nb));
       } else BZ_TRY(eng_go_live(e, q, blocks.data(), nb));
     }
+    if (cs) BZ_TRY(eng_copies(e, cs, ncopy, max_j));
     e->admit_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
   // (3) one replay while any row is live in the host's view; else drain
@@ -412,6 +470,47 @@ extern "C" int bz_engine_stats(bz_engine* e, bz_engine_stats_t* out) {
   out->live_rows = si.live; out->admitted = si.admitted; out->waiting = si.waiting; out->unread = (int)(e->g->replays - e->read);
   out->prompt_tokens = e->prompt_tokens; out->generated_tokens = e->generated; out->admit_host_ms = e->admit_ms;
   return BZ_OK;
+  BZ_API_END
+}
+
+extern "C" int bz_engine_prefix_stats(bz_engine* e, bz_engine_prefix_stats_t* out) {
+  BZ_API_BEGIN
+  if (!e || !out) BZ_FAIL(BZ_E_INVALID, "engine prefix_stats: null argument");
+  bz_sched_info_t si; bz_sched_prefix_info_t pi;
+  BZ_TRY(bz_sched_info(e->sched, &si));
+  BZ_TRY(bz_sched_prefix_info(e->sched, &pi));
+  memset(out, 0, sizeof(*out));
+  out->enabled = pi.enabled; out->cached_blocks = pi.cached_blocks; out->evictable_blocks = pi.evictable_blocks; out->referenced_blocks = pi.referenced_blocks;
+  out->private_blocks = si.owned_blocks; out->hits = pi.hits; out->misses = pi.misses; out->cached_tokens = pi.cached_tokens; out->evictions = pi.evictions;
+  out->prompt_tokens_skipped = e->skipped; out->copy_launches = e->copy_launches; out->copied_blocks = e->copied_blocks;
+  return BZ_OK;
+  BZ_API_END
+}
+
+extern "C" int bz_engine_prefix_flush(bz_engine* e, int* dropped_out) {
+  BZ_API_BEGIN
+  if (!e) BZ_FAIL(BZ_E_INVALID, "engine prefix_flush: null engine");
+  return bz_sched_prefix_flush(e->sched, dropped_out);
+  BZ_API_END
+}
+
+// ---- the copy kernel on its own ---------------------------------------------------------------------------
+extern "C" int bz_paged_kv_copy_slots(bz_paged_kv* kv, int src, int dst, int n_slots) {
+  BZ_API_BEGIN
+  if (!kv) BZ_FAIL(BZ_E_INVALID, "kv copy_slots: null cache");
+  if (src < 0 || src >= kv->num_blocks || dst < 0 || dst >= kv->num_blocks) BZ_FAIL(BZ_E_INVALID, "kv copy_slots: blocks %d -> %d outside the pool's %d", src, dst, kv->num_blocks);
+  if (src == dst) BZ_FAIL(BZ_E_INVALID, "kv copy_slots: source and destination are both block %d", src);
+  if (n_slots < 1 || n_slots > kv->block_size) BZ_FAIL(BZ_E_INVALID, "kv copy_slots: %d slots outside 1 .. block_size = %d", n_slots, kv->block_size);
+  BZ_HIP(hipSetDevice(kv->dev->id));
+  const int tr[3] = {src, dst, n_slots};
+  int* d = nullptr;
+  BZ_HIP(hipMalloc(&d, sizeof(tr)));
+  int rc = hipMemcpyAsync(d, tr, sizeof(tr), hipMemcpyHostToDevice, kv->dev->stream) == hipSuccess ? BZ_OK : BZ_E_HIP;
+  if (rc == BZ_OK) rc = bzk_kv_copy_slots(kv->dev->stream, kv, d, 1, n_slots);
+  if (hipStreamSynchronize(kv->dev->stream) != hipSuccess && rc == BZ_OK) rc = BZ_E_HIP;
+  hipFree(d);
+  if (rc == BZ_E_HIP) bz_set_error("kv copy_slots: the copy failed on the device");
+  return rc;
   BZ_API_END
 }
 

@@ -1382,6 +1382,21 @@ extern "C" int bz_paged_kv_free(bz_paged_kv* kv) {
   return BZ_OK;
   BZ_API_END
 }
+// test and debug accessor: one block of one layer as stored, raw bytes (the paged pool has no other read-back)
+extern "C" int bz_paged_kv_read_block(const bz_paged_kv* kv, int layer, int block, int which, void* host, size_t nbytes) {
+  BZ_API_BEGIN
+  if (!kv || !host) BZ_FAIL(BZ_E_INVALID, "kv read_block: null argument");
+  const size_t bytes = (size_t)kv->n_kv * kv->block_size * kv->hd * bz_dtype_size(kv->dtype);
+  if (layer < 0 || layer >= kv->layers || block < 0 || block >= kv->num_blocks || (which != 0 && which != 1) || nbytes != bytes)
+    BZ_FAIL(BZ_E_INVALID, "kv read_block: layer %d / block %d / which %d / %zu bytes (a block holds %zu)", layer, block, which, nbytes, bytes);
+  BZ_HIP(hipSetDevice(kv->dev->id));
+  const char* base = (const char*)(which ? kv->v : kv->k) + ((size_t)layer * kv->num_blocks + block) * bytes;
+  BZ_HIP(hipMemcpyAsync(host, base, bytes, hipMemcpyDeviceToHost, kv->dev->stream));
+  BZ_HIP(hipStreamSynchronize(kv->dev->stream));
+  return BZ_OK;
+  BZ_API_END
+}
+
 extern "C" int bz_paged_kv_set_seq_len(bz_paged_kv* kv, int n) { if (!kv || n < 0) BZ_FAIL(BZ_E_INVALID, "bad argument"); kv->seq_len = n; return BZ_OK; }
 extern "C" int bz_paged_kv_seq_len(const bz_paged_kv* kv) { return kv ? kv->seq_len : -1; }
 

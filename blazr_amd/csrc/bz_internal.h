@@ -399,6 +399,7 @@ int bzk_engine_advance(hipStream_t s, long long* tok, const long long* next, int
 int bzk_engine_finish(hipStream_t s, EngRow* rows, const long long* next, int* pos, int* table, int stride, const int* step, int logcap, int N, int* status,
                       int* nlive, uint32_t* gstate /*nullable: the grammar cursor's states*/);
 // what the engine needs of bz_host.hip: the capture with the row life cycle in it, a launch under the model's lock, the model's device, the prompt workspace
+int bzk_kv_copy_slots(hipStream_t s, bz_paged_kv* kv, const int* d_triples, int n, int max_j);
 int bzi_engine_capture(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_grammar_cursor* c, const BzEngineRows* er, bz_batch_graph** out);
 int bzi_batch_graph_launch(bz_batch_graph* g);
 bz_device* bzi_model_device(bz_model* m);

@@ -687,6 +687,16 @@ class LayeredPagedKvCache:
     def block_table_device_format(self):
         return list(self.blocks)
 
+    def copy_slots(self, src, dst, n_slots):
+        """The first n_slots slots of block src -> block dst over every layer, K and V, every KV head (the prefix cache's copy-on-write kernel)."""
+        L.check(L.lib().bz_paged_kv_copy_slots(self.h, int(src), int(dst), int(n_slots)))
+
+    def read_block(self, layer, block, which, n_kv_heads, head_dim, dtype):
+        """One block of one layer as stored: [kv_head][block_size][head_dim], f32 for an f32 pool, the raw 16-bit patterns (uint16) otherwise."""
+        out = np.empty((n_kv_heads, self.block_size, head_dim), dtype=np.float32 if dtype == L.F32 else np.uint16)
+        L.check(L.lib().bz_paged_kv_read_block(self.h, int(layer), int(block), int(which), _ptr(out), out.nbytes))
+        return out
+
 
 def penalty_window(recent_tokens, repeat_last_n):
     """sampling.rs:169-191: unique ids + counts over the last `repeat_last_n` tokens."""
@@ -986,7 +996,7 @@ class Scheduler:
         h = C.c_void_p()
         L.check(L.lib().bz_sched_create(int(n_rows), int(num_blocks), int(block_size), int(max_seq_len), int(prefill_chunk), C.byref(h)))
         self.h, self.n_rows, self.max_blocks = h, int(n_rows), (int(max_seq_len) + int(block_size) - 1) // int(block_size)
-        self._acts = (L.SchedAction * (3 * self.n_rows))()
+        self._acts = (L.SchedAction * (4 * self.n_rows))()
 
     def __del__(self):
         try:
@@ -1000,8 +1010,29 @@ class Scheduler:
         L.check(L.lib().bz_sched_submit(self.h, int(n_prompt), int(max_tokens), C.byref(rid)))
         return rid.value
 
+    def enable_prefix(self):
+        """The prefix cache's switch; before the first submit."""
+        L.check(L.lib().bz_sched_enable_prefix(self.h))
+
+    def submit_tokens(self, prompt, max_tokens):
+        p = np.ascontiguousarray(prompt, dtype=np.int64).reshape(-1)
+        rid = C.c_int64()
+        L.check(L.lib().bz_sched_submit_tokens(self.h, _ptr(p), len(p), int(max_tokens), C.byref(rid)))
+        return rid.value
+
+    def prefix_info(self):
+        i = L.SchedPrefixInfo()
+        L.check(L.lib().bz_sched_prefix_info(self.h, C.byref(i)))
+        return {k: getattr(i, k) for k, _ in L.SchedPrefixInfo._fields_}
+
+    def prefix_flush(self):
+        """Drops every unreferenced cached block; how many."""
+        n = C.c_int()
+        L.check(L.lib().bz_sched_prefix_flush(self.h, C.byref(n)))
+        return n.value
+
     def step(self):
-        """[(kind, row, id, a, b)]: this step's admissions, prompt chunks and rows going live, in order."""
+        """[(kind, row, id, a, b)]: this step's admissions, copies, prompt chunks and rows going live, in order."""
         n = C.c_int()
         L.check(L.lib().bz_sched_step(self.h, self._acts, len(self._acts), C.byref(n)))
         return [(a.kind, a.row, a.id, a.a, a.b) for a in self._acts[:n.value]]
@@ -1027,10 +1058,10 @@ class BatchEngine:
     come and go while the captured step keeps running; the caller drives with step().  sampler=True: every request samples with its own parameters
     (the keyword arguments of BatchSampler.set_row); grammar: a GrammarCursor of n_rows rows, borrowed (its rows are handed out by the engine)."""
 
-    def __init__(self, model, n_rows, num_blocks, block_size=16, max_seq_len=None, prefill_chunk=0, depth=2, sampler=True, grammar=None):
+    def __init__(self, model, n_rows, num_blocks, block_size=16, max_seq_len=None, prefill_chunk=0, depth=2, sampler=True, grammar=None, prefix_cache=False):
         cfg = L.EngineConfig(n_rows=int(n_rows), num_blocks=int(num_blocks), block_size=int(block_size),
                              max_seq_len=int(max_seq_len if max_seq_len is not None else model.c.max_seq_len), prefill_chunk=int(prefill_chunk), depth=int(depth),
-                             use_sampler=1 if sampler else 0)
+                             use_sampler=1 if sampler else 0, prefix_cache=int(prefix_cache))
         h = C.c_void_p()
         L.check(L.lib().bz_engine_create(model.h, C.byref(cfg), grammar.h if grammar is not None else None, C.byref(h)))
         self.h, self.model, self.grammar, self.n_rows = h, model, grammar, int(n_rows)
@@ -1080,6 +1111,19 @@ class BatchEngine:
         s = L.EngineStats()
         L.check(L.lib().bz_engine_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in L.EngineStats._fields_}
+
+    def prefix_stats(self):
+        """The prefix cache's counters (prefix_cache=True): blocks cached / evictable / referenced / private, hits, misses, cached_tokens, evictions,
+        prompt_tokens_skipped, copy launches and copied blocks."""
+        s = L.EnginePrefixStats()
+        L.check(L.lib().bz_engine_prefix_stats(self.h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in L.EnginePrefixStats._fields_ if k != "reserved"}
+
+    def prefix_flush(self):
+        """Drops every unreferenced cached block; how many."""
+        n = C.c_int()
+        L.check(L.lib().bz_engine_prefix_flush(self.h, C.byref(n)))
+        return n.value
 
     def read_status(self, replay):
         """(status words int32 [n_rows]: 0 idle, 1 token, 2 + 4 * reason finished; rows still live after that replay)"""

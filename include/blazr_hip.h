@@ -173,6 +173,12 @@ int bz_paged_kv_create(bz_device* dev, int layers, int num_blocks, int block_siz
                        bz_paged_kv** out);
 int bz_paged_kv_free(bz_paged_kv* kv);
 int bz_paged_kv_set_seq_len(bz_paged_kv* kv, int seq_len);  /* set_seq_len (executor_generate.rs:242,286) */
+/* The first n_slots slots of block src -> block dst: every layer, K and V, every KV head (the prefix cache's copy-on-write; 16-byte vectors, head_dim % 8 == 0).
+ * Waits for the copy.  BZ_E_INVALID for a block outside the pool, src == dst, n_slots outside 1 .. block_size. */
+int bz_paged_kv_copy_slots(bz_paged_kv* kv, int src, int dst, int n_slots);
+/* TEST AND DEBUG ACCESSOR, not part of the serving path: one block of one layer as stored ([kv_head][block_size][hd] in the pool's dtype), raw bytes to the
+ * host; which: 0 = K, 1 = V.  Waits for the stream.  (The paged pool had no read-back; the copy kernel's tests need one.) */
+int bz_paged_kv_read_block(const bz_paged_kv* kv, int layer, int block, int which, void* host, size_t nbytes);
 int bz_paged_kv_seq_len(const bz_paged_kv* kv);
 
 /* LayeredSsmState::new(layers, batch, mamba_config, dtype, device) (executor_generate.rs:131-133): recurrent state
@@ -438,9 +444,42 @@ int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_prompt, const 
  * that are not live yet, in admission order; a request prefills prompt[:-1] and becomes live in the step that completes it.  Ids count up from 0.
  *   step: the actions of one engine step, in order: BZ_SCHED_ADMIT {id, row, a = number of blocks}, BZ_SCHED_PREFILL {id, row, a .. b = prompt range},
  *         BZ_SCHED_LIVE {id, row}.  At most 3 * n_rows actions.
- *   finish: the request's end was harvested (or it was cancelled): its row and blocks are free from the next step on; a waiting request just leaves the queue. */
+ *   finish: the request's end was harvested (or it was cancelled): its row and blocks are free from the next step on; a waiting request just leaves the queue.
+ *
+ * The prefix cache (engine/executor_cache.rs:39-131 prefix_cache_allocate; opt-in: bz_sched_enable_prefix before the first submit, bz_engine_config.prefix_cache).
+ * With the switch off every decision above is unchanged.  With it on, requests submitted with their tokens (bz_sched_submit_tokens) share KV blocks; a request
+ * submitted without tokens (bz_sched_submit) still works and never matches or publishes.
+ *   cacheable: the F = (n_prompt - 1) / block_size full blocks of prompt[:-1].  The block that holds position n_prompt - 1 and every later one is written by decode
+ *     and stays private, so a shared block is never written again.
+ *   index: one entry per cached block, keyed by (parent entry, the block's block_size tokens); entry ids count up from 0, the root is parent -1.  THE KEY COMPARES
+ *     THE TOKENS THEMSELVES.  A hash may speed a lookup but never decides a match: a collision would silently serve another prompt's KV (wrong tokens, no error).
+ *   match at admission: walk the chain from the root over the request's full blocks: m <= F matched blocks.  Then, among the children of the last matched entry
+ *     (of the root when m = 0), the one with the longest common token prefix j >= 1 with prompt[m*bs : n_prompt-1] (ties: the lowest entry id) is the copy
+ *     source; j < block_size always.  The request's table starts with the m matched blocks, the rest are its own; ADMIT carries b = m (0 with the switch off); BZ_SCHED_COPY {id, row, a = source block,
+ *     b = j} follows its ADMIT (the destination is its block at index m, see bz_sched_row), and its prompt starts at done = m*bs + j instead of 0.
+ *     If done == n_prompt - 1 no PREFILL is emitted and LIVE comes in the admission step.
+ *   reference counts: a matched block gains one reference per request using it, an entry a request published holds that request's reference; finish (or cancel)
+ *     drops the references and frees the request's private blocks.  A cached block without a reference stays in the pool as evictable.  Every usable block is in
+ *     exactly one state: free, private to one request, or cached (referenced or not).
+ *   admission test: match first, hold the matched entries and the copy source, then require need - m <= free + evictable, where evictable counts the cached
+ *     blocks that repeated leaf eviction could free: unreferenced, not a copy source named in this step, and with no such entry below them.  FIFO without
+ *     skipping ahead, the lowest free row, the lowest free blocks first, as above.  A failed test changes nothing.
+ *   use counter: one counter for the whole scheduler, incremented at every touch (no clock): at admission the matched entries root first, then the copy source;
+ *     at publication the new entry.  An entry remembers the value of its last touch.
+ *   eviction: only while the free blocks have run out, one block at a time: among the unreferenced entries without children that are not a copy source of this
+ *     step, the one with the lowest use value (ties: the lowest block id) leaves the index and its block becomes free.
+ *   publishing: in the step whose PREFILL covers the last slot of one of its own full prompt blocks, the block enters the index under the entry of the block
+ *     before it (stream order then puts every later reader behind the writer).  If an equal entry exists already the request keeps its private duplicate and the
+ *     chain goes on under the existing entry (untouched); if that entry has been evicted meanwhile the request publishes nothing more.  So a request admitted before
+ *     the donor's chunk was issued does not match: prompts in flight are not deduplicated.
+ *   cost: a lookup scans the children of one entry linearly with a full token compare (no hash), and the match is redone in every step for a queue head that
+ *     keeps waiting: O(children * block_size) per matched block.  A root with thousands of distinct first blocks makes admission that much slower; known, not built.
+ *   step: at most 4 * n_rows actions with the switch on (room for that many is required), 3 * n_rows with it off.
+ *   prefix_info: cached = referenced + unreferenced entries; evictable as in the admission test; hit = an admission with tokens and done > 0, miss = one with
+ *     done == 0; cached_tokens = the sum of done; evictions counts blocks evicted under pressure (flush is not counted).
+ *   prefix_flush: drops every unreferenced cached block (leaf after leaf); *dropped_out (nullable) = how many. */
 typedef struct bz_sched bz_sched;
-enum { BZ_SCHED_ADMIT = 0, BZ_SCHED_PREFILL = 1, BZ_SCHED_LIVE = 2 };
+enum { BZ_SCHED_ADMIT = 0, BZ_SCHED_PREFILL = 1, BZ_SCHED_LIVE = 2, BZ_SCHED_COPY = 3 };
 typedef struct { int32_t kind, row; int64_t id; int32_t a, b; } bz_sched_action;
 typedef struct { int32_t n_rows, num_blocks, park_blocks, free_blocks, owned_blocks, waiting, admitted, live; } bz_sched_info_t;
 int bz_sched_create(int n_rows, int num_blocks, int block_size, int max_seq_len, int prefill_chunk, bz_sched** out);
@@ -450,6 +489,11 @@ int bz_sched_step(bz_sched* s, bz_sched_action* out, int max_out, int* n_out);
 int bz_sched_finish(bz_sched* s, int64_t id);
 int bz_sched_info(const bz_sched* s, bz_sched_info_t* out);
 int bz_sched_row(const bz_sched* s, int row, int64_t* id_out /*-1: free*/, int32_t* blocks_out /*nullable*/, int max_blocks, int* n_blocks_out);
+typedef struct { int32_t enabled, cached_blocks, evictable_blocks, referenced_blocks; int64_t hits, misses, cached_tokens, evictions; } bz_sched_prefix_info_t;
+int bz_sched_enable_prefix(bz_sched* s);
+int bz_sched_submit_tokens(bz_sched* s, const int64_t* prompt, int n_prompt, int max_tokens, int64_t* id_out);
+int bz_sched_prefix_info(const bz_sched* s, bz_sched_prefix_info_t* out);
+int bz_sched_prefix_flush(bz_sched* s, int* dropped_out /*nullable*/);
 /* The engine (batch_engine.rs:91-169 BatchEngine::run, 322-445 the decode step and its harvest): one captured step of n_rows rows over a paged pool the engine owns;
  * every row is live or idle ON THE DEVICE, a live row ends there (stop id, or max_tokens reached) in the launch that sees its token, so several replays can be in
  * flight and their records read late.  An idle row feeds token 0 at position 0 of its own park block.  The caller drives: bz_engine_step is one scheduling iteration,
@@ -473,7 +517,8 @@ typedef struct {
   int32_t prefill_chunk;   /* prompt tokens per step, 0 = unlimited */
   int32_t depth;           /* replays in flight before the oldest record is read, 1..64 */
   int32_t use_sampler;     /* 1: the batched sampler picks (per-request parameters); 0: greedy argmax */
-  int32_t reserved[9];
+  int32_t prefix_cache;    /* 1: the prefix cache (shared prompt blocks, copy-on-write); 0: off (took the first reserved word) */
+  int32_t reserved[8];
 } bz_engine_config;
 typedef struct {
   int32_t max_tokens;
@@ -492,6 +537,15 @@ int bz_engine_cancel(bz_engine* e, int64_t id);
 int bz_engine_step(bz_engine* e, int* busy_out);
 int bz_engine_poll(bz_engine* e, bz_engine_event* out, int max_events, int* n_out);
 int bz_engine_stats(bz_engine* e, bz_engine_stats_t* out);
+/* The prefix cache through the engine (prefix_cache = 1): submit hands the tokens to the scheduler; a step gathers its BZ_SCHED_COPY actions into ONE launch of
+ * k_kv_copy_slots (triples staged in pinned memory, read from device memory; no allocation, no wait), enqueued ahead of that step's prompt chunks; a hit changes
+ * only which positions are prefilled: the sampler's history is the whole prompt and the grammar start state is the request's.  free + private + cached ==
+ * total - park at all times (bz_engine_stats.free_blocks with the counts below).  prompt_tokens_skipped = prompt positions served from cached blocks
+ * (bz_engine_stats.prompt_tokens counts only what was prefilled).  prefix_flush drops every unreferenced cached block (*dropped_out nullable). */
+typedef struct { int32_t enabled, cached_blocks, evictable_blocks, referenced_blocks, private_blocks, reserved; int64_t hits, misses, cached_tokens, evictions,
+                 prompt_tokens_skipped, copy_launches, copied_blocks; } bz_engine_prefix_stats_t;
+int bz_engine_prefix_stats(bz_engine* e, bz_engine_prefix_stats_t* out);
+int bz_engine_prefix_flush(bz_engine* e, int* dropped_out /*nullable*/);
 /* the status words (0 idle, 1 token, 2 + 4 * reason finished) of replay `replay` (within the last 1024), host [n_rows]; waits for that replay */
 int bz_engine_read_status(bz_engine* e, int64_t replay, int32_t* status_out, int32_t* live_after_out /*nullable*/);
 int bz_engine_free(bz_engine* e);

@@ -7,7 +7,13 @@
 (b) an admission: one 128-token prompt into a running batch of 63.  Host time of the step that admits it (and the share spent enqueueing the prompt and the
     row writes), and the wall time a 12-step window gains over the same window without an admission, beside the prompt's own device time.
 (c) churn: 256 requests, 16-token prompts, 16 .. 256 new tokens, over 64 rows, against the same requests as four static batches of 64, each run to its longest member.
-Times are a host clock around work that ends in a device synchronise; medians of `--rounds` rounds, the variants alternating inside a round.  Writes profiles/engine.json."""
+(d) a shared stem (the prefix cache, bz_engine_config.prefix_cache): 64 requests behind one stem of `--stem` tokens with private tails of 8 .. 24 tokens, 32 new tokens
+    each, over 64 rows.  The first request is submitted one step ahead of the others (prompts in flight are not deduplicated).  Run it once with --prefix-cache 0
+    and once with --prefix-cache 1, each in a process of its own (--skip a,b,c --out ...): prompt tokens prefilled, host ms per admission, steps to the first
+    token, wall time; the run asserts that the prompt tokens prefilled are what the scheduler predicts.  The default stem of 520 tokens is 32 whole blocks and 8
+    slots, so every sharer copies 8 slots and the 63 copies of the step are one launch; the launch's time comes from a kernel trace of a run of its own.
+    scripts/merge_prefix_bench.py puts the runs' outputs into profiles/prefix_cache.json.
+Times are a host clock around work that ends in a device synchronise; medians of `--rounds` rounds, the variants alternating inside a round.  Writes profiles/engine.json (or --out)."""
 import argparse
 import json
 import os
@@ -29,7 +35,9 @@ ap.add_argument("--rounds", type=int, default=9)
 ap.add_argument("--steps", type=int, default=24)
 ap.add_argument("--churn-rounds", type=int, default=3)
 ap.add_argument("--churn-requests", type=int, default=256)
-ap.add_argument("--skip", default="", help="comma-separated parts to leave out: a,b,c")
+ap.add_argument("--skip", default="", help="comma-separated parts to leave out: a,b,c,d")
+ap.add_argument("--stem", type=int, default=520)
+ap.add_argument("--prefix-cache", type=int, default=0)
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "engine.json"))
 args = ap.parse_args()
 skip = set(args.skip.split(","))
@@ -40,7 +48,7 @@ V, BS = cfg["vocab"], 16
 lm = runtime.LoadedModel.from_synth_streamed(dev, cfg)
 KW = dict(temperature=0.7, top_k=40, top_p=0.9, min_p=0.0, repeat_penalty=1.1, frequency_penalty=0.1, presence_penalty=0.05, repeat_last_n=64)
 med = statistics.median
-result = {"device": dev.name(), "preset": args.preset, "params": KW, "rounds": args.rounds, "steps": args.steps, "steady": [], "admission": None, "churn": None}
+result = {"device": dev.name(), "preset": args.preset, "params": KW, "rounds": args.rounds, "steps": args.steps, "steady": [], "admission": None, "churn": None, "shared_stem": None}
 
 
 def drain(eng):
@@ -211,6 +219,58 @@ if "c" not in skip:
                        "engine_tokens_per_s": round(total / med(te), 1), "static_s": round(med(ts), 4), "static_replays": static_replays,
                        "static_tokens_per_s": round(total / med(ts), 1), "ratio_engine_over_static": round(med(ts) / med(te), 3)}
     print(json.dumps(result["churn"]), flush=True)
+
+# ---- (d) -----------------------------------------------------------------------------------------------------------------------------------------------
+if "d" not in skip:
+    N, R, NEW = 64, 64, 32
+    on = bool(args.prefix_cache)
+    stem = synth.prompt_tokens(args.stem, V, seed=3000)
+    tails = [synth.prompt_tokens(9 + i % 17, V, seed=3001 + i) for i in range(R)]
+    for i in range(1, R):
+        if tails[i][0] == tails[0][0]:                                # the common part ends with the stem
+            tails[i][0] = (tails[i][0] + 1) % V
+    prompts = [np.concatenate([stem, t]) for t in tails]
+    per = -(-(args.stem + 25 + NEW) // BS)
+    eng = runtime.BatchEngine(lm, N, N * per + N, BS, per * BS, 0, 4, True, **(dict(prefix_cache=True) if on else {}))
+    walls, first_steps, admit, prefilled, last = [], [], [], [], None
+    for rnd in range(args.rounds + 1):
+        if on:
+            eng.prefix_flush()
+        s0 = eng.stats()
+        dev.synchronize()
+        t0 = time.perf_counter()
+        ids = [eng.submit(prompts[0], NEW, seed=0, **KW)]
+        seen, step, busy = {}, 0, True
+        while busy:
+            if step == 1:
+                ids += [eng.submit(prompts[i], NEW, seed=i, **KW) for i in range(1, R)]
+            busy = eng.step() or step == 0
+            for rid, tok, idx, fin, rep_ in eng.poll():
+                seen.setdefault(rid, step)
+            step += 1
+        dev.synchronize()
+        dt = time.perf_counter() - t0
+        s1 = eng.stats()
+        prefilled.append(s1["prompt_tokens"] - s0["prompt_tokens"])
+        if rnd:
+            walls.append(dt)
+            first_steps.append(med([seen[i] - (0 if k == 0 else 1) for k, i in enumerate(ids)]))
+            admit.append((s1["admit_host_ms"] - s0["admit_host_ms"]) / R)
+        if on:
+            p1 = eng.prefix_stats()
+            last = {k: p1[k] for k in ("hits", "misses", "cached_tokens", "copied_blocks", "copy_launches", "evictions")}
+    # what the scheduler predicts: with the cache off everything; with it on the donor prefills everything and every other request what follows the stem
+    total = int(sum(len(p) - 1 for p in prompts))
+    predicted = int(len(prompts[0]) - 1 + sum(len(p) - 1 - args.stem for p in prompts[1:])) if on else total
+    assert all(x == predicted for x in prefilled), (prefilled, predicted)
+    row = {"rows": N, "requests": R, "stem": args.stem, "new_tokens": NEW, "prefix_cache": int(on), "prompt_tokens_total": total, "prompt_tokens_predicted": predicted,
+           "prompt_tokens_prefilled_per_round": int(prefilled[-1]), "admit_host_ms_per_admission": round(med(admit), 4), "median_steps_to_first_token": med(first_steps),
+           "wall_s": round(med(walls), 4), "wall_s_rounds": [round(w, 4) for w in walls]}
+    if on:
+        row["prefix_stats_cumulative"] = last
+    result["shared_stem"] = row
+    print(json.dumps(row), flush=True)
+    del eng
 
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 with open(args.out, "w") as f:

@@ -7,11 +7,12 @@
 //          [--repeat-penalty R] [--seed S] [--graphs] [--paged-attention] [--device D] [--stats]
 //          [--grammar FILE --vocab-bytes FILE [--grammar-regular]]
 //          [--draft <checkpoint> [--spec-tokens k] [--spec-adaptive]]
-//   bz-run <model> --requests FILE --rows N [--pool-blocks B] [--prefill-chunk C] [--depth D] [sampling options, --eos]
+//   bz-run <model> --requests FILE --rows N [--pool-blocks B] [--prefill-chunk C] [--depth D] [--prefix-cache] [sampling options, --eos]
 // --requests: continuous batching (BatchEngine::run, engine/batch_engine.rs:91-169; RequestScheduler::submit, engine/request_scheduler.rs:105-205) over N rows.  The file
 // has one request per line, `max_tokens;comma-separated prompt ids`; all are submitted, the engine is stepped until idle, and one line of ids per request is
 // printed in submission order; the engine's statistics go to stderr.  --pool-blocks: the paged pool (default: every row can hold a full-length request);
-// the sampling options apply to every request (request i draws with seed + i), --eos is its stop id.
+// the sampling options apply to every request (request i draws with seed + i), --eos is its stop id.  --prefix-cache: requests share the cached full blocks of
+// earlier prompts (a request admitted in the same step as its donor does not); hits, cached tokens and evictions go to stderr.
 // --draft: speculative decoding (inference.speculative, config/inference.rs:197-208; generate_text.rs:61-136) with that checkpoint as the draft model: greedy only,
 // the same ids as without it; iterations / accepted / rejected go to stderr (generate_text.rs:130-135).
 // --grammar: a GBNF file (gen_config.grammar, executor_generate.rs:96-121), compiled with the reference's semantics or, with --grammar-regular, as the regular subset of
@@ -48,7 +49,7 @@ int main(int argc, char** argv) {
   int device_id = 0; bool stats_on = false;
   std::string grammar_path, vocab_path; bool grammar_regular = false;
   std::string draft_path; bz_spec_config sc;
-  std::string requests_path; int rows = 0, pool_blocks = 0, prefill_chunk = 0, depth = 2;
+  std::string requests_path; int rows = 0, pool_blocks = 0, prefill_chunk = 0, depth = 2; bool prefix_cache = false;
   memset(&sc, 0, sizeof sc);
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
@@ -77,6 +78,7 @@ int main(int argc, char** argv) {
     else if (a == "--pool-blocks") pool_blocks = atoi(next("--pool-blocks"));
     else if (a == "--prefill-chunk") prefill_chunk = atoi(next("--prefill-chunk"));
     else if (a == "--depth") depth = atoi(next("--depth"));
+    else if (a == "--prefix-cache") prefix_cache = true;
     else { fprintf(stderr, "bz-run: unknown option %s\n", a.c_str()); return 2; }
   }
   if (!requests_path.empty()) {
@@ -114,6 +116,7 @@ int main(int argc, char** argv) {
     ec.num_blocks = pool_blocks > 0 ? pool_blocks : rows * per + rows;       // one park block per row on top
     const bool greedy = gc.temperature == 0.0f && gc.repeat_penalty == 1.0f && gc.frequency_penalty == 0.0f && gc.presence_penalty == 0.0f;
     ec.use_sampler = greedy ? 0 : 1;
+    ec.prefix_cache = prefix_cache ? 1 : 0;
     bz_engine* e = nullptr;
     if (bz_engine_create(m, &ec, nullptr, &e) != BZ_OK) return fail("engine");
     for (size_t i = 0; i < reqs.size(); i++) {
@@ -147,6 +150,13 @@ int main(int argc, char** argv) {
     fprintf(stderr, "engine: %lld replays, %d / %d blocks free (%d park), %d live rows, %d waiting, %lld prompt tokens, %lld generated tokens, %.2f ms host time in admissions\n",
             (long long)es.replays, es.free_blocks, es.total_blocks, es.park_blocks, es.live_rows, es.waiting, (long long)es.prompt_tokens, (long long)es.generated_tokens,
             es.admit_host_ms);
+    if (prefix_cache) {
+      bz_engine_prefix_stats_t ps;
+      if (bz_engine_prefix_stats(e, &ps) != BZ_OK) return fail("prefix stats");
+      fprintf(stderr, "prefix cache: %lld hits, %lld misses, %lld cached tokens, %lld evictions, %d blocks cached, %lld prompt tokens skipped, %lld blocks copied in %lld launches\n",
+              (long long)ps.hits, (long long)ps.misses, (long long)ps.cached_tokens, (long long)ps.evictions, ps.cached_blocks, (long long)ps.prompt_tokens_skipped,
+              (long long)ps.copied_blocks, (long long)ps.copy_launches);
+    }
     bz_engine_free(e);
     bz_model_free(m);
     bz_device_close(dev);
