@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <chrono>
 #include <numeric>
+#include <type_traits>
 #include <unordered_map>
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1441,42 +1442,103 @@ struct StepIO {
   bz_grammar_cursor* cursor = nullptr;                      // graph mode, Llama family: mask the logits row from the cursor's state before the argmax, advance it on the picked token
 };
 
-// Fixed-point accumulator ring.  Launch j accumulates into ring[j % 3] (which must be zero), reads the output of
-// launch j-1 and zeroes ring[(j+1) % 3] -- last written by launch j-2 and last read by launch j-1, both complete by
-// stream order.  `dirty[i]` = number of non-zero entries ring[i] may hold.
-struct RingState { int ri = 0; int dirty[3] = {0, 0, 0}; };
+// Fixed-point accumulator ring: the model's three buffers, all zero between steps.  Launch j accumulates into ring[j % 3] (which must be
+// zero), reads the output of launch j-1 and zeroes ring[(j+1) % 3] -- last written by launch j-2 and last read by launch j-1, both complete
+// by stream order.  `ri` = the buffer the next launch accumulates into (clean); `dirty[i]` = number of non-zero entries ring[i] may hold.
+// A launch that follows the protocol asks take(n): it gets its accumulator and, as zero_buf / zero_n, the duty to zero the buffer after it
+// (zero_buf is null when that buffer holds nothing), and the state moves on as if the launch had run.  The head of a step does not
+// accumulate into the ring: hand_zeroing(i) gives its launches the same duty for one named stale buffer and leaves `ri` where it is.
+struct RingSlot { long long* acc; long long* zero_buf; int zero_n; };
+struct RingState {
+  long long* const* ring;
+  int ri = 0; int dirty[3] = {0, 0, 0};
+  explicit RingState(const bz_model* m) : ring(m->ring) {}
+  RingSlot take(int n) {   // n: non-zero entries the launch leaves in its accumulator
+    const int rz = (ri + 1) % 3;
+    const RingSlot s{ring[ri], dirty[rz] > 0 ? ring[rz] : nullptr, dirty[rz]};
+    dirty[rz] = 0; dirty[ri] = n; ri = rz;
+    return s;
+  }
+  RingSlot hand_zeroing(int i) {
+    const RingSlot s{nullptr, dirty[i] > 0 ? ring[i] : nullptr, dirty[i]};
+    dirty[i] = 0;
+    return s;
+  }
+};
 
 // Launch every part of a fused linear.  Returns the VSrc describing its output.
 static int run_fused(bz_model* m, const FusedLinear& F, Pro pro, RingState& rs, VSrc* out, const ConvShift* shift = nullptr) {
   hipStream_t st = step_stream(m);
   const int act = m->cfg.act_dtype;
-  const int ri = rs.ri, rz = (rs.ri + 1) % 3;
-  long long* acc = m->ring[ri];
-  float* direct = m->dring[ri];
+  float* direct = m->dring[rs.ri];
   static const bool no_mix = getenv("BZ_NO_GQ_MIX") != nullptr;
   if (!no_mix && F.parts.size() == 2 && F.fix_out && F.n_off[1] == F.parts[0].N && bzk_gq_mix_ok(F.parts[0], F.parts[1], pro)) {
     // GGUF Q4_K_M q/k/v: the Q4_K part (q, k) and the Q6_K part (v) in one launch
+    const RingSlot r = rs.take(F.N);
     GemvOut o{};
-    o.acc = acc; o.zero_buf = rs.dirty[rz] > 0 ? m->ring[rz] : nullptr; o.zero_n = rs.dirty[rz];
+    o.acc = r.acc; o.zero_buf = r.zero_buf; o.zero_n = r.zero_n;
     BZ_TRY(bzk_gemv_gq_mix(st, F.parts[0], F.parts[1], pro, o));
-    rs.dirty[rz] = 0; rs.dirty[ri] = F.N; rs.ri = rz;
-    out->fix = 1; out->p = (const void*)acc;
+    out->fix = 1; out->p = (const void*)r.acc;
     return BZ_OK;
   }
+  // only part 0 carries the zeroing duty; a direct (f32) output leaves the accumulator clean
+  const RingSlot r = rs.take(F.fix_out ? F.N : 0);
   for (size_t i = 0; i < F.parts.size(); i++) {
     const LinearDev& L = F.parts[i];
     Pro p = pro; p.perm = L.perm;
     GemvOut o{};
-    o.acc = acc + F.n_off[i]; o.direct = direct + F.n_off[i];
-    o.zero_buf = (i == 0 && rs.dirty[rz] > 0) ? m->ring[rz] : nullptr; o.zero_n = rs.dirty[rz];
+    o.acc = r.acc + F.n_off[i]; o.direct = direct + F.n_off[i];
+    o.zero_buf = i == 0 ? r.zero_buf : nullptr; o.zero_n = r.zero_n;
     if (i == 0 && shift) o.shift = *shift;
     BZ_TRY(bzk_gemv(st, L, p, o, act));
   }
-  rs.dirty[rz] = 0;
-  rs.dirty[ri] = F.fix_out ? F.N : 0;
-  rs.ri = rz;
   out->fix = F.fix_out ? 1 : 0;
-  out->p = F.fix_out ? (const void*)acc : (const void*)direct;
+  out->p = F.fix_out ? (const void*)r.acc : (const void*)direct;
+  return BZ_OK;
+}
+
+// The tail every step shares: final norm + lm_head GEMV with its argmax partials (a quantised lm_head and a grammar cursor: Llama family only,
+// refused for the others at finalize / capture), the final argmax kernel, and the ring left zero.  `prev` / `h_in`: the last layer's output and
+// the residual row it adds to.  Ring indices on entry: rs.ri is clean; (rs.ri+2)%3 holds `prev` when it is fixed point (still needed by the
+// head), (rs.ri+1)%3 is stale
+static int step_tail(bz_model* m, const StepIO& io, RingState& rs, VSrc prev, const float* h_in) {
+  const bz_model_config& c = m->cfg;
+  hipStream_t st = step_stream(m);
+  const int act = c.act_dtype;
+  const int ra = (rs.ri + 2) % 3, rb = (rs.ri + 1) % 3;
+  if (io.do_head) {
+    Pro ph{}; ph.mode = PRO_NORM; ph.src = prev; ph.h_in = h_in; ph.h_out = nullptr; ph.norm_w = m->final_norm;
+    ph.eps = c.rms_eps; ph.H = c.hidden; ph.act = act;
+    int rfin = ra;   // ring buffer the final kernel zeroes
+    if (m->lm_head.fix_out) {
+      // quantised lm_head (GGUF output.weight): split-K GEMV into the ring, then convert + partial argmax
+      VSrc lv;
+      BZ_TRY(run_fused(m, m->lm_head, ph, rs, &lv));
+      BZ_TRY(bzk_fix_to_f32(st, (const long long*)lv.p, c.vocab, act, m->logits));
+      if (!io.cursor) BZ_TRY(bzk_argmax_partials(st, m->logits, c.vocab, m->pval, m->pidx, m->nparts));
+      rfin = -1;
+    } else {
+      const RingSlot z = rs.hand_zeroing(rb);
+      GemvOut o{};
+      o.direct = m->logits; o.amax_val = m->pval; o.amax_idx = m->pidx;
+      o.zero_buf = z.zero_buf; o.zero_n = z.zero_n;
+      BZ_TRY(bzk_gemv(st, m->lm_head.parts[0], ph, o, act));
+    }
+    if (io.cursor) {
+      // the partials the lm_head produced belong to the unmasked row: mask, then take them again over what is left
+      BZ_TRY(bzk_grammar_mask_rows(st, io.cursor, m->logits));
+      BZ_TRY(bzk_argmax_partials(st, m->logits, c.vocab, m->pval, m->pidx, m->nparts));
+    }
+    if (io.final_args) {
+      FinalArgs fa = *io.final_args;
+      fa.pval = m->pval; fa.pidx = m->pidx; fa.nparts = m->nparts;
+      if (rfin >= 0) { const RingSlot z = rs.hand_zeroing(rfin); fa.zero_buf = z.zero_buf; fa.zero_n = z.zero_n; }
+      BZ_TRY(bzk_argmax_final(st, fa));
+      if (io.cursor) BZ_TRY(bzk_grammar_advance_rows(st, io.cursor, fa.tok_out));
+    }
+  }
+  // every ring buffer must be zero again when the step ends
+  for (int i = 0; i < 3; i++) if (rs.dirty[i] > 0) BZ_TRY(bzk_zero64(st, m->ring[i], rs.dirty[i]));
   return BZ_OK;
 }
 
@@ -1486,7 +1548,7 @@ static int llama_step(bz_model* m, const StepIO& io) {
   const int H = c.hidden, I = c.inter, act = c.act_dtype;
   const int lend = io.layer_end < 0 ? c.n_layers : io.layer_end;
   int cur = 0;
-  RingState rs;
+  RingState rs(m);
   VSrc prev{nullptr, 0};
   if (io.do_embed) {
     BZ_TRY(bzk_embed(st, m->embed, m->embed_dt, m->embed_ggml, io.d_tok, H, act, m->hbuf[cur], io.d_pos, m->cos_t, m->sin_t, c.head_dim / 2, m->rope_cur));
@@ -1531,12 +1593,11 @@ static int llama_step(bz_model* m, const StepIO& io) {
     }
     if (fuse_o) {
       // attention + o_proj in one launch: same ring protocol as a GEMV launch
-      const int rz = (rs.ri + 1) % 3;
-      aa.zero_buf = rs.dirty[rz] > 0 ? m->ring[rz] : nullptr; aa.zero_n = rs.dirty[rz];
-      if (split) BZ_TRY(bzk_attn_merge_oproj(st, aa, m->att_ws, nsplit, Ld.o.parts[0], m->ring[rs.ri]));
-      else BZ_TRY(bzk_attn_oproj(st, aa, Ld.o.parts[0], m->ring[rs.ri]));
-      ov = VSrc{m->ring[rs.ri], 1};
-      rs.dirty[rz] = 0; rs.dirty[rs.ri] = Ld.o.N; rs.ri = rz;
+      const RingSlot r = rs.take(Ld.o.N);
+      aa.zero_buf = r.zero_buf; aa.zero_n = r.zero_n;
+      if (split) BZ_TRY(bzk_attn_merge_oproj(st, aa, m->att_ws, nsplit, Ld.o.parts[0], r.acc));
+      else BZ_TRY(bzk_attn_oproj(st, aa, Ld.o.parts[0], r.acc));
+      ov = VSrc{r.acc, 1};
     } else {
       if (split) BZ_TRY(bzk_attn_merge(st, aa, m->att_ws, nsplit));
       else BZ_TRY(bzk_attn_decode(st, aa));
@@ -1548,26 +1609,21 @@ static int llama_step(bz_model* m, const StepIO& io) {
     pf.eps = c.rms_eps; pf.H = H; pf.act = act;
     VSrc dn;
     static const bool no_mlp_fuse = getenv("BZ_NO_MLP_FUSION") != nullptr;
-    if (!no_mlp_fuse && act == BZ_F16 && Ld.gateup.parts.size() == 1 && Ld.down.parts.size() == 1 && bzk_mlp_fusable(Ld.gateup.parts[0], Ld.down.parts[0], H, I)) {
-      // norm + gate/up + SiLU*up + down in one launch (same ring protocol as one GEMV launch)
-      const int rz = (rs.ri + 1) % 3;
-      BZ_TRY(bzk_mlp_q4g(st, Ld.gateup.parts[0], Ld.down.parts[0], H, I, pf, m->ring[rs.ri], rs.dirty[rz] > 0 ? m->ring[rz] : nullptr, rs.dirty[rz]));
-      dn = VSrc{m->ring[rs.ri], 1};
-      rs.dirty[rz] = 0; rs.dirty[rs.ri] = H; rs.ri = rz;
-      cur ^= 1;
-    } else if (!no_mlp_fuse && Ld.gateup.parts.size() == 1 && Ld.down.parts.size() == 1 && bzk_mlp_dense_fusable(Ld.gateup.parts[0], Ld.down.parts[0], Ld.down_slabs, H, I, act)) {
-      // the dense 16-bit form of the same fusion (slab-major down_proj copy)
-      const int rz = (rs.ri + 1) % 3;
-      BZ_TRY(bzk_mlp_dense(st, Ld.gateup.parts[0], Ld.down.parts[0], Ld.down_slabs, H, I, pf, m->ring[rs.ri], rs.dirty[rz] > 0 ? m->ring[rz] : nullptr, rs.dirty[rz]));
-      dn = VSrc{m->ring[rs.ri], 1};
-      rs.dirty[rz] = 0; rs.dirty[rs.ri] = H; rs.ri = rz;
-      cur ^= 1;
-    } else if (!no_mlp_fuse && Ld.gateup.parts.size() == 1 && Ld.down.parts.size() == 1 && bzk_mlp_gq_fusable(Ld.gateup.parts[0], Ld.down.parts[0], H, I, act)) {
-      // the GGUF form of the same fusion (Q4_K gate / up, Q4_K or Q6_K down, f32 activations)
-      const int rz = (rs.ri + 1) % 3;
-      BZ_TRY(bzk_mlp_gq(st, Ld.gateup.parts[0], Ld.down.parts[0], H, I, pf, m->ring[rs.ri], rs.dirty[rz] > 0 ? m->ring[rz] : nullptr, rs.dirty[rz]));
-      dn = VSrc{m->ring[rs.ri], 1};
-      rs.dirty[rz] = 0; rs.dirty[rs.ri] = H; rs.ri = rz;
+    // norm + gate/up + SiLU*up + down in one launch (same ring protocol as one GEMV launch), where one of its three forms takes the layer
+    enum { MLP_SPLIT, MLP_Q4G, MLP_DENSE, MLP_GQ } mlp = MLP_SPLIT;
+    if (!no_mlp_fuse && Ld.gateup.parts.size() == 1 && Ld.down.parts.size() == 1) {
+      const LinearDev& GU = Ld.gateup.parts[0]; const LinearDev& DN = Ld.down.parts[0];
+      if (act == BZ_F16 && bzk_mlp_fusable(GU, DN, H, I)) mlp = MLP_Q4G;
+      else if (bzk_mlp_dense_fusable(GU, DN, Ld.down_slabs, H, I, act)) mlp = MLP_DENSE;   // the dense 16-bit form of the same fusion (slab-major down_proj copy)
+      else if (bzk_mlp_gq_fusable(GU, DN, H, I, act)) mlp = MLP_GQ;   // the GGUF form of the same fusion (Q4_K gate / up, Q4_K or Q6_K down, f32 activations)
+    }
+    if (mlp != MLP_SPLIT) {
+      const LinearDev& GU = Ld.gateup.parts[0]; const LinearDev& DN = Ld.down.parts[0];
+      const RingSlot r = rs.take(H);
+      if (mlp == MLP_Q4G) BZ_TRY(bzk_mlp_q4g(st, GU, DN, H, I, pf, r.acc, r.zero_buf, r.zero_n));
+      else if (mlp == MLP_DENSE) BZ_TRY(bzk_mlp_dense(st, GU, DN, Ld.down_slabs, H, I, pf, r.acc, r.zero_buf, r.zero_n));
+      else BZ_TRY(bzk_mlp_gq(st, GU, DN, H, I, pf, r.acc, r.zero_buf, r.zero_n));
+      dn = VSrc{r.acc, 1};
       cur ^= 1;
     } else {
       VSrc gu;
@@ -1585,43 +1641,7 @@ static int llama_step(bz_model* m, const StepIO& io) {
       else BZ_HIP(hipMemcpyAsync(io.prev_out, prev.p, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
     }
   }
-  // ring indices at this point: rs.ri is clean; (rs.ri+2)%3 holds `prev` (still needed by the head), (rs.ri+1)%3 is stale
-  const int ra = (rs.ri + 2) % 3, rb = (rs.ri + 1) % 3;
-  if (io.do_head) {
-    Pro ph{}; ph.mode = PRO_NORM; ph.src = prev; ph.h_in = m->hbuf[cur]; ph.h_out = nullptr; ph.norm_w = m->final_norm;
-    ph.eps = c.rms_eps; ph.H = H; ph.act = act;
-    int rfin = ra;   // ring buffer the final kernel zeroes
-    if (m->lm_head.fix_out) {
-      // quantised lm_head (GGUF output.weight): split-K GEMV into the ring, then convert + partial argmax
-      VSrc lv;
-      BZ_TRY(run_fused(m, m->lm_head, ph, rs, &lv));
-      BZ_TRY(bzk_fix_to_f32(st, (const long long*)lv.p, c.vocab, act, m->logits));
-      if (!io.cursor) BZ_TRY(bzk_argmax_partials(st, m->logits, c.vocab, m->pval, m->pidx, m->nparts));
-      rfin = -1;
-    } else {
-      GemvOut o{};
-      o.direct = m->logits; o.amax_val = m->pval; o.amax_idx = m->pidx;
-      o.zero_buf = rs.dirty[rb] > 0 ? m->ring[rb] : nullptr; o.zero_n = rs.dirty[rb];
-      BZ_TRY(bzk_gemv(st, m->lm_head.parts[0], ph, o, act));
-      rs.dirty[rb] = 0;
-    }
-    if (io.cursor) {
-      // the partials the lm_head produced belong to the unmasked row: mask, then take them again over what is left
-      BZ_TRY(bzk_grammar_mask_rows(st, io.cursor, m->logits));
-      BZ_TRY(bzk_argmax_partials(st, m->logits, c.vocab, m->pval, m->pidx, m->nparts));
-    }
-    if (io.final_args) {
-      FinalArgs fa = *io.final_args;
-      fa.pval = m->pval; fa.pidx = m->pidx; fa.nparts = m->nparts;
-      if (rfin >= 0) { fa.zero_buf = rs.dirty[rfin] > 0 ? m->ring[rfin] : nullptr; fa.zero_n = rs.dirty[rfin]; }
-      BZ_TRY(bzk_argmax_final(st, fa));
-      if (rfin >= 0) rs.dirty[rfin] = 0;
-      if (io.cursor) BZ_TRY(bzk_grammar_advance_rows(st, io.cursor, fa.tok_out));
-    }
-  }
-  // every ring buffer must be zero again when the step ends
-  for (int i = 0; i < 3; i++) if (rs.dirty[i] > 0) BZ_TRY(bzk_zero64(st, m->ring[i], rs.dirty[i]));
-  return BZ_OK;
+  return step_tail(m, io, rs, prev, m->hbuf[cur]);
 }
 
 
@@ -1634,7 +1654,7 @@ static int mamba_step(bz_model* m, const StepIO& io) {
   const int conv_dim = DI + 2 * G * NS;
   bz_ssm_state* S = io.ssm;
   int cur = 0;
-  RingState rs;
+  RingState rs(m);
   VSrc prev{nullptr, 0};
   BZ_TRY(bzk_embed(st, m->embed, m->embed_dt, m->embed_ggml, io.d_tok, D, act, m->hbuf[cur]));
   for (int l = 0; l < c.n_layers; l++) {
@@ -1657,25 +1677,7 @@ static int mamba_step(bz_model* m, const StepIO& io) {
     BZ_TRY(run_fused(m, L.out_proj, pg, rs, &ov, &shf));
     prev = ov;
   }
-  // ring indices as in llama_step: rs.ri clean, (rs.ri+2)%3 holds `prev` when it is fixed point, (rs.ri+1)%3 stale
-  const int ra = (rs.ri + 2) % 3, rb = (rs.ri + 1) % 3;
-  if (io.do_head) {
-    Pro ph{}; ph.mode = PRO_NORM; ph.src = prev; ph.h_in = m->hbuf[cur]; ph.h_out = nullptr; ph.norm_w = m->final_norm; ph.eps = c.rms_eps; ph.H = D; ph.act = act;
-    GemvOut o{};
-    o.direct = m->logits; o.amax_val = m->pval; o.amax_idx = m->pidx;
-    o.zero_buf = rs.dirty[rb] > 0 ? m->ring[rb] : nullptr; o.zero_n = rs.dirty[rb];
-    BZ_TRY(bzk_gemv(st, m->lm_head.parts[0], ph, o, act));
-    rs.dirty[rb] = 0;
-    if (io.final_args) {
-      FinalArgs fa = *io.final_args;
-      fa.pval = m->pval; fa.pidx = m->pidx; fa.nparts = m->nparts;
-      fa.zero_buf = rs.dirty[ra] > 0 ? m->ring[ra] : nullptr; fa.zero_n = rs.dirty[ra];
-      BZ_TRY(bzk_argmax_final(st, fa));
-      rs.dirty[ra] = 0;
-    }
-  }
-  for (int i = 0; i < 3; i++) if (rs.dirty[i] > 0) BZ_TRY(bzk_zero64(st, m->ring[i], rs.dirty[i]));
-  return BZ_OK;
+  return step_tail(m, io, rs, prev, m->hbuf[cur]);
 }
 
 // DeepSeek-V2 decode step: per layer  [q_proj ; kv_a] GEMV (norm prologue) -> MLA attention over the latent cache -> o_proj GEMV ->
@@ -1687,7 +1689,7 @@ static int dsv2_step(bz_model* m, const StepIO& io) {
   const int H = c.hidden, NH = c.n_heads, R = c.mla_kv_lora_rank, DN = c.mla_nope_dim, DR = c.mla_rope_dim, DV = c.mla_v_dim, act = c.act_dtype;
   const int E = c.moe_n_experts, TK = c.moe_top_k, NS = c.moe_n_shared, MI = c.moe_inter;
   int cur = 0;
-  RingState rs;
+  RingState rs(m);
   VSrc prev{nullptr, 0};
   BZ_TRY(bzk_embed(st, m->embed, m->embed_dt, m->embed_ggml, io.d_tok, H, act, m->hbuf[cur]));
   for (int l = 0; l < c.n_layers; l++) {
@@ -1773,24 +1775,7 @@ static int dsv2_step(bz_model* m, const StepIO& io) {
       prev = VSrc{m->moe_out, 0};
     }
   }
-  const int ra = (rs.ri + 2) % 3, rb = (rs.ri + 1) % 3;
-  if (io.do_head) {
-    Pro ph{}; ph.mode = PRO_NORM; ph.src = prev; ph.h_in = m->hbuf[cur]; ph.h_out = nullptr; ph.norm_w = m->final_norm; ph.eps = c.rms_eps; ph.H = H; ph.act = act;
-    GemvOut o{};
-    o.direct = m->logits; o.amax_val = m->pval; o.amax_idx = m->pidx;
-    o.zero_buf = rs.dirty[rb] > 0 ? m->ring[rb] : nullptr; o.zero_n = rs.dirty[rb];
-    BZ_TRY(bzk_gemv(st, m->lm_head.parts[0], ph, o, act));
-    rs.dirty[rb] = 0;
-    if (io.final_args) {
-      FinalArgs fa = *io.final_args;
-      fa.pval = m->pval; fa.pidx = m->pidx; fa.nparts = m->nparts;
-      fa.zero_buf = rs.dirty[ra] > 0 ? m->ring[ra] : nullptr; fa.zero_n = rs.dirty[ra];
-      BZ_TRY(bzk_argmax_final(st, fa));
-      rs.dirty[ra] = 0;
-    }
-  }
-  for (int i = 0; i < 3; i++) if (rs.dirty[i] > 0) BZ_TRY(bzk_zero64(st, m->ring[i], rs.dirty[i]));
-  return BZ_OK;
+  return step_tail(m, io, rs, prev, m->hbuf[cur]);
 }
 
 static int model_step(bz_model* m, const StepIO& io) {
@@ -1806,9 +1791,27 @@ static int check_fwd(bz_model* m, const bz_tensor* tokens, int S) {
   return BZ_OK;
 }
 
+// One eager step at a host-known position: the position goes into the device word the step reads, the attention path is chosen for the
+// position + 1 keys the step sees.  `step`: model_step, llama_step, or a wrapper around one of them.
+template <class Step> static int step_at(bz_model* m, int position, StepIO& io, Step step) {
+  hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, m->dev->stream, m->pos_tmp, position);
+  io.d_pos = m->pos_tmp; io.att_positions = att_positions_for(position + 1);
+  return step(m, io);
+}
+
+// a cache (bz_kv / bz_paged_kv; null: no match) must have the model's layers, KV heads and head_dim
+template <class Cache> static int check_cache(const bz_model* m, const Cache* kv, const char* who) {
+  if (!kv || kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "%s: cache does not match the model", who);
+  return BZ_OK;
+}
+static int check_logits_out(const bz_model* m, const bz_tensor* logits_out, size_t rows) {
+  if (!logits_out || logits_out->dtype != BZ_F32 || logits_out->nbytes < rows * m->cfg.vocab * 4) BZ_FAIL(BZ_E_INVALID, "forward: logits_out too small");
+  return BZ_OK;
+}
+
 static int emit_logits(bz_model* m, bz_tensor* logits_out, int row) {
   const size_t vb = (size_t)m->cfg.vocab * 4;
-  if (!logits_out || logits_out->dtype != BZ_F32 || logits_out->nbytes < (size_t)(row + 1) * vb) BZ_FAIL(BZ_E_INVALID, "forward: logits_out too small");
+  BZ_TRY(check_logits_out(m, logits_out, (size_t)row + 1));
   BZ_HIP(hipMemcpyAsync((char*)logits_out->ptr + (size_t)row * vb, m->logits, vb, hipMemcpyDeviceToDevice, m->dev->stream));
   return BZ_OK;
 }
@@ -2226,38 +2229,40 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
   BZ_API_END
 }
 
+// What bz_forward_kv and bz_forward_paged share once their arguments are checked: S tokens at positions position .. position + S - 1 over `view`
+// (`slots`: a paged cache's slot of every row, else null), logits of every row (`all`) or of the last one.  The caller sets its cache's seq_len.
+static int forward_core(bz_model* m, const bz_tensor* tokens, int S, const KvView& view, const int* slots, int position, bool all, bz_tensor* logits_out) {
+  const long long* d_tok = (const long long*)tokens->ptr;
+  if (prefill_eligible(m, S, position + S)) {
+    // prompt-sized inputs of dense 16-bit models: batched prefill, GEMMs on the matrix cores
+    BZ_TRY(check_logits_out(m, logits_out, all ? S : 1));
+    return prefill_dense(m, d_tok, S, view, position, slots, all, logits_out);
+  }
+  if (dsv2_prefill_eligible(m, S, position + S, view)) {
+    // (paged: the rows' slots follow from the block table: slot = block_table[p / bs] * bs + p % bs, batch_decode.rs:81-88)
+    BZ_TRY(check_logits_out(m, logits_out, all ? S : 1));
+    return dsv2_prefill(m, d_tok, S, view, position, all, logits_out);
+  }
+  for (int s = 0; s < S; s++) {
+    StepIO io{};
+    io.kv = view; io.kv.slot = slots ? slots + s : nullptr; io.d_tok = d_tok + s;
+    io.do_head = all || s == S - 1;
+    BZ_TRY(step_at(m, position + s, io, model_step));
+    if (io.do_head) BZ_TRY(emit_logits(m, logits_out, all ? s : 0));
+  }
+  return BZ_OK;
+}
+
 extern "C" int bz_forward_kv(bz_model* m, const bz_tensor* tokens, int S, bz_kv* kv, int position, bz_tensor* logits_out, uint32_t flags) {
   BZ_API_BEGIN
   BZ_TRY(check_fwd(m, tokens, S));
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   BZ_TRACE("forward_kv: S=%d position=%d", S, position);
   if (m->cfg.arch == BZ_ARCH_MAMBA2) BZ_FAIL(BZ_E_INVALID, "forward_kv: model has no KV cache (use bz_forward_ssm)");
-  if (!kv || kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "forward_kv: cache does not match the model");
+  BZ_TRY(check_cache(m, kv, "forward_kv"));
   if (position < 0 || position + S > m->cfg.max_seq_len) BZ_FAIL(BZ_E_INVALID, "forward_kv: position %d + S %d exceeds max_seq_len %d", position, S, m->cfg.max_seq_len);
   BZ_TRY(kv_grow(kv, position + S));
-  const bool all = flags & BZ_FWD_ALL_LOGITS;
-  if (prefill_eligible(m, S, position + S)) {
-    // prompt-sized inputs of dense 16-bit models: batched prefill, GEMMs on the matrix cores
-    if (!logits_out || logits_out->dtype != BZ_F32 || logits_out->nbytes < (size_t)(all ? S : 1) * m->cfg.vocab * 4) BZ_FAIL(BZ_E_INVALID, "forward: logits_out too small");
-    BZ_TRY(prefill_dense(m, (const long long*)tokens->ptr, S, view_of(kv), position, nullptr, all, logits_out));
-    kv->seq_len = position + S;
-    return BZ_OK;
-  }
-  if (dsv2_prefill_eligible(m, S, position + S, view_of(kv))) {
-    if (!logits_out || logits_out->dtype != BZ_F32 || logits_out->nbytes < (size_t)(all ? S : 1) * m->cfg.vocab * 4) BZ_FAIL(BZ_E_INVALID, "forward: logits_out too small");
-    BZ_TRY(dsv2_prefill(m, (const long long*)tokens->ptr, S, view_of(kv), position, all, logits_out));
-    kv->seq_len = position + S;
-    return BZ_OK;
-  }
-  for (int s = 0; s < S; s++) {
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, m->dev->stream, m->pos_tmp, position + s);
-    StepIO io{};
-    io.kv = view_of(kv); io.d_tok = (const long long*)tokens->ptr + s; io.d_pos = m->pos_tmp;
-    io.att_positions = att_positions_for(position + s + 1);
-    io.do_head = all || s == S - 1;
-    BZ_TRY(model_step(m, io));
-    if (io.do_head) BZ_TRY(emit_logits(m, logits_out, all ? s : 0));
-  }
+  BZ_TRY(forward_core(m, tokens, S, view_of(kv), nullptr, position, flags & BZ_FWD_ALL_LOGITS, logits_out));
   kv->seq_len = position + S;
   return BZ_OK;
   BZ_API_END
@@ -2269,36 +2274,13 @@ extern "C" int bz_forward_paged(bz_model* m, const bz_tensor* tokens, int S, bz_
   BZ_TRY(check_fwd(m, tokens, S));
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   if (m->cfg.arch == BZ_ARCH_MAMBA2) BZ_FAIL(BZ_E_UNSUPPORTED, "forward_paged: Mamba2 has no KV cache");   // MLA: the latent cache pages like any other (one 'head' of rank + rope values)
-  if (!kv || kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "forward_paged: cache does not match the model");
+  BZ_TRY(check_cache(m, kv, "forward_paged"));
   if (!slot_mapping || slot_mapping->dtype != BZ_I32 || slot_mapping->nbytes < (size_t)S * 4) BZ_FAIL(BZ_E_INVALID, "forward_paged: slot_mapping must be I32[S]");
   if (!block_table || block_table->dtype != BZ_I32 || block_table->nbytes < (size_t)n_table * 4) BZ_FAIL(BZ_E_INVALID, "forward_paged: block_table must be I32[n_table]");
   if (start_pos < 0 || start_pos + S != seq_len_k) BZ_FAIL(BZ_E_INVALID, "forward_paged: start_pos + S must equal seq_len_k");
   if ((seq_len_k + kv->block_size - 1) / kv->block_size > n_table) BZ_FAIL(BZ_E_INVALID, "forward_paged: block_table too short for seq_len_k");
   if (seq_len_k > m->cfg.max_seq_len) BZ_FAIL(BZ_E_INVALID, "forward_paged: seq_len_k exceeds max_seq_len");
-  const bool all = flags & BZ_FWD_ALL_LOGITS;
-  if (prefill_eligible(m, S, seq_len_k)) {
-    if (!logits_out || logits_out->dtype != BZ_F32 || logits_out->nbytes < (size_t)(all ? S : 1) * m->cfg.vocab * 4) BZ_FAIL(BZ_E_INVALID, "forward: logits_out too small");
-    BZ_TRY(prefill_dense(m, (const long long*)tokens->ptr, S, view_of(kv, (const int*)block_table->ptr, nullptr), start_pos, (const int*)slot_mapping->ptr, all, logits_out));
-    kv->seq_len = seq_len_k;
-    return BZ_OK;
-  }
-  if (dsv2_prefill_eligible(m, S, seq_len_k, view_of(kv, (const int*)block_table->ptr, nullptr))) {
-    // (the rows' slots follow from the block table: slot = block_table[p / bs] * bs + p % bs, batch_decode.rs:81-88)
-    if (!logits_out || logits_out->dtype != BZ_F32 || logits_out->nbytes < (size_t)(all ? S : 1) * m->cfg.vocab * 4) BZ_FAIL(BZ_E_INVALID, "forward: logits_out too small");
-    BZ_TRY(dsv2_prefill(m, (const long long*)tokens->ptr, S, view_of(kv, (const int*)block_table->ptr, nullptr), start_pos, all, logits_out));
-    kv->seq_len = seq_len_k;
-    return BZ_OK;
-  }
-  for (int s = 0; s < S; s++) {
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, m->dev->stream, m->pos_tmp, start_pos + s);
-    StepIO io{};
-    io.kv = view_of(kv, (const int*)block_table->ptr, (const int*)slot_mapping->ptr + s);
-    io.d_tok = (const long long*)tokens->ptr + s; io.d_pos = m->pos_tmp;
-    io.att_positions = att_positions_for(start_pos + s + 1);
-    io.do_head = all || s == S - 1;
-    BZ_TRY(model_step(m, io));
-    if (io.do_head) BZ_TRY(emit_logits(m, logits_out, all ? s : 0));
-  }
+  BZ_TRY(forward_core(m, tokens, S, view_of(kv, (const int*)block_table->ptr, nullptr), (const int*)slot_mapping->ptr, start_pos, flags & BZ_FWD_ALL_LOGITS, logits_out));
   kv->seq_len = seq_len_k;
   return BZ_OK;
   BZ_API_END
@@ -2314,7 +2296,7 @@ extern "C" int bz_forward_paged_batch(bz_model* m, const bz_tensor* tokens, int 
   BZ_TRY(check_fwd(m, tokens, N));
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   if (m->cfg.arch != BZ_ARCH_LLAMA) BZ_FAIL(BZ_E_UNSUPPORTED, "forward_paged_batch: llama family only");
-  if (!kv || kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "forward_paged_batch: cache does not match the model");
+  BZ_TRY(check_cache(m, kv, "forward_paged_batch"));
   if (!slot_mapping || slot_mapping->dtype != BZ_I32 || slot_mapping->nbytes < (size_t)N * 4) BZ_FAIL(BZ_E_INVALID, "forward_paged_batch: slot_mapping must be I32[N]");
   if (max_blocks <= 0 || !block_table || block_table->dtype != BZ_I32 || block_table->nbytes < (size_t)N * max_blocks * 4)
     BZ_FAIL(BZ_E_INVALID, "forward_paged_batch: block_table must be I32[N, max_blocks]");
@@ -2344,12 +2326,10 @@ extern "C" int bz_forward_paged_batch(bz_model* m, const bz_tensor* tokens, int 
     return BZ_OK;
   }
   for (int i = 0; i < N; i++) {
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, m->dev->stream, m->pos_tmp, seq_lens[i] - 1);   // the new token's position (batch_decode.rs:79-88)
     StepIO io{};
     io.kv = view_of(kv, (const int*)block_table->ptr + (size_t)i * max_blocks, (const int*)slot_mapping->ptr + i);
-    io.d_tok = (const long long*)tokens->ptr + i; io.d_pos = m->pos_tmp;
-    io.att_positions = att_positions_for(seq_lens[i]);
-    BZ_TRY(model_step(m, io));
+    io.d_tok = (const long long*)tokens->ptr + i;
+    BZ_TRY(step_at(m, seq_lens[i] - 1, io, model_step));   // the new token's position (batch_decode.rs:79-88)
     BZ_TRY(emit_logits(m, logits_out, i));
   }
   if (kv->seq_len < maxlen) kv->seq_len = maxlen;
@@ -2448,7 +2428,7 @@ extern "C" int bz_forward_ssm(bz_model* m, const bz_tensor* tokens, int S, bz_ss
   BZ_TRY(check_ssm(m, st));
   const bool all = flags & BZ_FWD_ALL_LOGITS;
   if (mamba_prefill_eligible(m, S)) {
-    if (!logits_out || logits_out->dtype != BZ_F32 || logits_out->nbytes < (size_t)(all ? S : 1) * m->cfg.vocab * 4) BZ_FAIL(BZ_E_INVALID, "forward: logits_out too small");
+    BZ_TRY(check_logits_out(m, logits_out, all ? S : 1));
     BZ_HIP(hipSetDevice(m->dev->id));
     return mamba_prefill(m, (const long long*)tokens->ptr, S, st, all, logits_out);
   }
@@ -2489,16 +2469,14 @@ extern "C" int bz_forward_layers_range(bz_model* m, bz_tensor* hidden, bz_tensor
   BZ_TRY(kv_grow(kv, position + S));
   if (start == end) return BZ_OK;
   for (int s = 0; s < S; s++) {
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, m->dev->stream, m->pos_tmp, position + s);
     StepIO io{};
-    io.kv = view_of(kv); io.d_tok = nullptr; io.d_pos = m->pos_tmp;
-    io.att_positions = att_positions_for(position + s + 1);
+    io.kv = view_of(kv); io.d_tok = nullptr;
     io.do_embed = false; io.do_head = false; io.layer_start = start; io.layer_end = end;
     io.hidden_in = (float*)hidden->ptr + (size_t)s * H;
     io.prev_in = *has_prev ? (float*)prev_mlp->ptr + (size_t)s * H : nullptr;
     io.hidden_out = (float*)hidden->ptr + (size_t)s * H;
     io.prev_out = (float*)prev_mlp->ptr + (size_t)s * H;
-    BZ_TRY(llama_step(m, io));
+    BZ_TRY(step_at(m, position + s, io, llama_step));
   }
   *has_prev = 1;
   if (end == m->cfg.n_layers) kv->seq_len = position + S;
@@ -2562,15 +2540,16 @@ extern "C" int bz_profile_step(bz_model* m, bz_kv* kv, int64_t token, int positi
   BzTimingSink sink;
   int rc = BZ_OK;
   for (int i = 0; i < iters && rc == BZ_OK; i++) {
-    hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, m->pos_tmp, position + i);
     FinalArgs fa{};
     fa.tok_out = m->tok_tmp + 1;   // scratch: do not feed the sampled token back (same input every iteration)
     StepIO io{};
-    io.kv = view_of(kv); io.d_tok = m->tok_tmp; io.d_pos = m->pos_tmp; io.final_args = &fa;
-    io.att_positions = att_positions_for(position + i + 1);
-    bzk_set_timing_sink(&sink);
-    rc = model_step(m, io);
-    bzk_set_timing_sink(nullptr);
+    io.kv = view_of(kv); io.d_tok = m->tok_tmp; io.final_args = &fa;
+    rc = step_at(m, position + i, io, [&sink](bz_model* mm, const StepIO& sio) {   // the sink sees the step only
+      bzk_set_timing_sink(&sink);
+      const int src = model_step(mm, sio);
+      bzk_set_timing_sink(nullptr);
+      return src;
+    });
   }
   hipStreamSynchronize(st);
   if (kv->seq_len < position + iters) kv->seq_len = position + iters;
@@ -2863,6 +2842,46 @@ struct bz_decode_graph {
   static const int LOGCAP = 4096;
 };
 
+// Owning handle over an object of the C ABI and its bz_*_free function (every one of them takes null): frees on every way out of a scope,
+// until release() hands the object to the caller's out-pointer.  out(): where a create call stores the object.
+template <class T, int (*Free)(T*)> struct Owned {
+  T* p = nullptr;
+  Owned() = default;
+  explicit Owned(T* q) : p(q) {}
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  ~Owned() { Free(p); }
+  T** out() { return &p; }
+  operator T*() const { return p; }
+  T* operator->() const { return p; }
+  T* release() { T* q = p; p = nullptr; return q; }
+};
+
+// Records what `body` enqueues on a private capturing stream (tl_capture_stream is set around the body only) and instantiates it.  Returns graph and
+// executable, or an error with everything made here destroyed again.
+template <class Body> static int capture_graph(Body body, hipGraph_t* graph_out, hipGraphExec_t* exec_out) {
+  BZ_TRACE("graph: begin capture");
+  hipStream_t cap = nullptr;
+  BZ_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
+  hipError_t eb = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
+  if (eb != hipSuccess) { hipStreamDestroy(cap); BZ_FAIL(BZ_E_HIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(eb)); }
+  tl_capture_stream = cap;
+  int rc = body(cap);
+  tl_capture_stream = nullptr;
+  hipGraph_t graph = nullptr;
+  hipError_t e = hipStreamEndCapture(cap, &graph);
+  hipStreamDestroy(cap);
+  BZ_TRACE("graph: end capture rc=%d hip=%d", rc, (int)e);
+  if (rc != BZ_OK) { if (graph) hipGraphDestroy(graph); return rc; }
+  if (e != hipSuccess) BZ_FAIL(BZ_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
+  hipGraphExec_t exec = nullptr;
+  hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+  if (ei != hipSuccess) { hipGraphDestroy(graph); BZ_FAIL(BZ_E_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ei)); }
+  BZ_TRACE("graph: instantiated");
+  *graph_out = graph; *exec_out = exec;
+  return BZ_OK;
+}
+
 // one capture of the decode step over the graph's device-resident token / position / step words; att_positions > 0 records the long-context
 // (split-KV attention) form of the step
 static int graph_capture_variant(bz_decode_graph* g, int att_positions, hipGraph_t* graph_out, hipGraphExec_t* exec_out) {
@@ -2871,29 +2890,10 @@ static int graph_capture_variant(bz_decode_graph* g, int att_positions, hipGraph
   fa.tok_out = g->tok_buf; fa.tok_log = g->tok_log; fa.step = g->step; fa.logcap = bz_decode_graph::LOGCAP; fa.pos = g->pos;
   StepIO io{};
   io.kv = g->view; io.d_tok = g->tok_buf; io.d_pos = g->pos; io.final_args = &fa; io.ssm = g->ssm; io.att_positions = att_positions; io.cursor = g->cursor;
-  BZ_TRACE("graph: begin capture");
-  hipStream_t cap = nullptr;
-  BZ_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
-  hipError_t eb = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
-  if (eb != hipSuccess) { hipStreamDestroy(cap); BZ_FAIL(BZ_E_HIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(eb)); }
-  tl_capture_stream = cap;
-  int rc = model_step(m, io);
-  tl_capture_stream = nullptr;
-  hipGraph_t graph = nullptr;
-  hipError_t e = hipStreamEndCapture(cap, &graph);
-  hipStreamDestroy(cap);
-  BZ_TRACE("graph: end capture rc=%d hip=%d", rc, (int)e);
-  if (rc != BZ_OK) { if (graph) hipGraphDestroy(graph); return rc; }
-  if (e != hipSuccess) BZ_FAIL(BZ_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-  *graph_out = graph;
-  BZ_HIP(hipGraphInstantiate(exec_out, graph, nullptr, nullptr, 0));
-  BZ_TRACE("graph: instantiated");
-  return BZ_OK;
+  return capture_graph([&](hipStream_t) { return model_step(m, io); }, graph_out, exec_out);
 }
 
 static int graph_capture_common(bz_decode_graph* g, const KvView& view) {
-  bz_model* m = g->m;
-  hipStream_t st = m->dev->stream;
   BZ_HIP(hipMalloc(&g->tok_buf, 64));
   BZ_HIP(hipMalloc(&g->pos, 64));
   BZ_HIP(hipMalloc(&g->step, 64));
@@ -2917,39 +2917,47 @@ static int check_step_cursor(bz_model* m, bz_grammar_cursor* c) {
   if (cdev != m->dev) BZ_FAIL(BZ_E_INVALID, "graph capture with a grammar: the grammar cursor lives on another device handle");
   return BZ_OK;
 }
+// What the three single-sequence captures share: a graph object for `m` (it holds a device reference from the start: the free function needs one),
+// owned here until it goes to `out`; `fill` names the cache or state the step runs over, allocates what the graph keeps for it and gives the view.
+template <class Fill> static int decode_graph_build(bz_model* m, bz_decode_graph** out, Fill fill) {
+  Owned<bz_decode_graph, bz_decode_graph_free> g(new bz_decode_graph());
+  bz_dev_retain(m->dev); g->dev = m->dev;
+  g->m = m;
+  KvView view{};
+  BZ_TRY(fill(g, &view));
+  BZ_TRY(graph_capture_common(g, view));
+  *out = g.release();
+  return BZ_OK;
+}
 static int decode_graph_capture_kv(bz_model* m, bz_kv* kv, bz_grammar_cursor* c, bz_decode_graph** out) {
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   if (c) BZ_TRY(check_step_cursor(m, c));
   if (!kv) BZ_FAIL(BZ_E_INVALID, "graph capture: bad argument");
   if (m->cfg.arch == BZ_ARCH_MAMBA2) BZ_FAIL(BZ_E_INVALID, "graph capture: model has no KV cache (use bz_decode_graph_capture_ssm)");
-  if (kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "graph capture: cache does not match the model");
+  BZ_TRY(check_cache(m, kv, "graph capture"));
   BZ_HIP(hipSetDevice(m->dev->id));
   // stable addresses: the cache must sit at full capacity (cuda_graphs.rs:70)
   BZ_TRY(kv_grow(kv, kv->max_len));
-  bz_decode_graph* g = new bz_decode_graph();
-  bz_dev_retain(m->dev); g->dev = m->dev;
-  g->m = m; g->kv = kv; g->capacity = kv->max_len; g->cursor = c;
-  int rc = graph_capture_common(g, view_of(kv));
-  if (rc != BZ_OK) { bz_decode_graph_free(g); return rc; }
-  *out = g;
-  return BZ_OK;
+  return decode_graph_build(m, out, [&](bz_decode_graph* g, KvView* view) -> int {
+    g->kv = kv; g->capacity = kv->max_len; g->cursor = c;
+    *view = view_of(kv);
+    return BZ_OK;
+  });
 }
 static int decode_graph_capture_pkv(bz_model* m, bz_paged_kv* kv, int max_blocks, bz_grammar_cursor* c, bz_decode_graph** out) {
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   if (c) BZ_TRY(check_step_cursor(m, c));
   if (!kv || max_blocks <= 0) BZ_FAIL(BZ_E_INVALID, "graph capture: bad argument");
   if (m->cfg.arch == BZ_ARCH_MAMBA2) BZ_FAIL(BZ_E_INVALID, "graph capture: model has no KV cache (use bz_decode_graph_capture_ssm)");
-  if (kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "graph capture: cache does not match the model");
+  BZ_TRY(check_cache(m, kv, "graph capture"));
   BZ_HIP(hipSetDevice(m->dev->id));
-  bz_decode_graph* g = new bz_decode_graph();
-  bz_dev_retain(m->dev); g->dev = m->dev;
-  g->m = m; g->pkv = kv; g->max_blocks = max_blocks; g->capacity = std::min(max_blocks * kv->block_size, m->cfg.max_seq_len); g->cursor = c;
-  BZ_HIP(hipMalloc(&g->block_table, (size_t)max_blocks * 4));
-  BZ_HIP(hipMemset(g->block_table, 0, (size_t)max_blocks * 4));
-  int rc = graph_capture_common(g, view_of(kv, g->block_table, nullptr));
-  if (rc != BZ_OK) { bz_decode_graph_free(g); return rc; }
-  *out = g;
-  return BZ_OK;
+  return decode_graph_build(m, out, [&](bz_decode_graph* g, KvView* view) -> int {
+    g->pkv = kv; g->max_blocks = max_blocks; g->capacity = std::min(max_blocks * kv->block_size, m->cfg.max_seq_len); g->cursor = c;
+    BZ_HIP(hipMalloc(&g->block_table, (size_t)max_blocks * 4));
+    BZ_HIP(hipMemset(g->block_table, 0, (size_t)max_blocks * 4));
+    *view = view_of(kv, g->block_table, nullptr);
+    return BZ_OK;
+  });
 }
 extern "C" int bz_decode_graph_capture(bz_model* m, bz_kv* kv, bz_decode_graph** out) {
   BZ_API_BEGIN
@@ -2984,13 +2992,7 @@ extern "C" int bz_decode_graph_capture_ssm(bz_model* m, bz_ssm_state* st, bz_dec
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   BZ_TRY(check_ssm(m, st));
   BZ_HIP(hipSetDevice(m->dev->id));
-  bz_decode_graph* g = new bz_decode_graph();
-  bz_dev_retain(m->dev); g->dev = m->dev;
-  g->m = m; g->ssm = st;
-  int rc = graph_capture_common(g, KvView{});
-  if (rc != BZ_OK) { bz_decode_graph_free(g); return rc; }
-  *out = g;
-  return BZ_OK;
+  return decode_graph_build(m, out, [&](bz_decode_graph* g, KvView*) -> int { g->ssm = st; return BZ_OK; });
   BZ_API_END
 }
 // ---------------------------------------------------------------------------------------------------------
@@ -3026,7 +3028,7 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
                                const BzEngineRows* er = nullptr) {
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   if (m->cfg.arch != BZ_ARCH_LLAMA) BZ_FAIL(BZ_E_UNSUPPORTED, "batch graph capture: llama family only");
-  if (kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "batch graph capture: cache does not match the model");
+  BZ_TRY(check_cache(m, kv, "batch graph capture"));
   if (s) {
     int sN = 0; long long sV = 0;
     bzk_batch_sampler_dims(s, &sN, &sV);
@@ -3046,50 +3048,34 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
     BZ_FAIL(BZ_E_UNSUPPORTED, "batch graph capture: the model does not take the weight-sharing multi-row step (int4 without act-order or dense 16-bit weights, 16-bit lm_head)");
   BZ_HIP(hipSetDevice(m->dev->id));
   BZ_TRY(prefill_ws(m, N));                      // workspace before the capture (allocation synchronises)
-  bz_batch_graph* g = new bz_batch_graph();
+  Owned<bz_batch_graph, bz_decode_batch_graph_free> g(new bz_batch_graph());
   bz_dev_retain(m->dev); g->dev = m->dev;
   g->m = m; g->kv = kv; g->N = N; g->max_blocks = max_blocks; g->capacity = capacity; g->host_pos.assign(N, -1);
-  int rc = BZ_OK;
-  auto fail = [&](int code) { bz_decode_batch_graph_free(g); return code; };
   if (hipMalloc(&g->tok, (size_t)N * 8) != hipSuccess || hipMalloc(&g->next, (size_t)N * 8) != hipSuccess || hipMalloc(&g->pos, (size_t)N * 4) != hipSuccess ||
       hipMalloc(&g->slot, (size_t)N * 4) != hipSuccess || hipMalloc(&g->table, (size_t)N * max_blocks * 4) != hipSuccess || hipMalloc(&g->step, 64) != hipSuccess ||
       hipHostMalloc(&g->log, sizeof(long long) * bz_batch_graph::LOGCAP * N, hipHostMallocDefault) != hipSuccess)
-    return fail(BZ_E_OOM);
+    return BZ_E_OOM;
   hipMemset(g->tok, 0, (size_t)N * 8); hipMemset(g->next, 0, (size_t)N * 8); hipMemset(g->pos, 0, (size_t)N * 4); hipMemset(g->slot, 0, (size_t)N * 4);
   hipMemset(g->table, 0, (size_t)N * max_blocks * 4); hipMemset(g->step, 0, 64);
   memset(g->log, 0xff, sizeof(long long) * bz_batch_graph::LOGCAP * N);
   const int64_t shp[2] = {N, m->cfg.vocab};
-  rc = bz_tensor_zeros(m->dev, BZ_F32, shp, 2, &g->logits);
-  if (rc != BZ_OK) return fail(rc);
+  BZ_TRY(bz_tensor_zeros(m->dev, BZ_F32, shp, 2, &g->logits));
   BZ_HIP(hipDeviceSynchronize());
-  hipStream_t cap = nullptr;
-  BZ_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
-  hipError_t eb = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
-  if (eb != hipSuccess) { hipStreamDestroy(cap); bz_decode_batch_graph_free(g); BZ_FAIL(BZ_E_HIP, "hipStreamBeginCapture failed: %s", hipGetErrorString(eb)); }
-  tl_capture_stream = cap;
-  if (er) rc = bzk_engine_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N, er->rows);
-  else rc = bzk_batch_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N);
-  if (rc == BZ_OK) {
+  auto body = [&](hipStream_t cap) -> int {
+    if (er) BZ_TRY(bzk_engine_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N, er->rows));
+    else BZ_TRY(bzk_batch_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N));
     RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity;
-    rc = prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, rcx);
-  }
-  if (rc == BZ_OK && c) rc = bzk_grammar_mask_rows(cap, c, (float*)g->logits->ptr);
-  if (rc == BZ_OK) {
-    if (s) rc = bzk_batch_sample(cap, s, (const float*)g->logits->ptr, nullptr, g->next, g->log, g->step, bz_batch_graph::LOGCAP);
-    else rc = bzk_batch_argmax(cap, (const float*)g->logits->ptr, m->cfg.vocab, g->next, g->log, g->step, bz_batch_graph::LOGCAP, N);
-  }
-  if (rc == BZ_OK && c) rc = bzk_grammar_advance_rows(cap, c, g->next);
-  if (rc == BZ_OK && er)
-    rc = bzk_engine_finish(cap, er->rows, g->next, g->pos, g->table, max_blocks, g->step, bz_batch_graph::LOGCAP, N, er->status, er->nlive, c ? bzk_grammar_cursor_states(c) : nullptr);
-  tl_capture_stream = nullptr;
-  hipGraph_t graph = nullptr;
-  hipError_t e = hipStreamEndCapture(cap, &graph);
-  hipStreamDestroy(cap);
-  if (rc != BZ_OK) { if (graph) hipGraphDestroy(graph); return fail(rc); }
-  if (e != hipSuccess) { bz_decode_batch_graph_free(g); BZ_FAIL(BZ_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e)); }
-  g->graph = graph;
-  if (hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0) != hipSuccess) { bz_decode_batch_graph_free(g); BZ_FAIL(BZ_E_HIP, "hipGraphInstantiate failed"); }
-  *out = g;
+    BZ_TRY(prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, rcx));
+    if (c) BZ_TRY(bzk_grammar_mask_rows(cap, c, (float*)g->logits->ptr));
+    if (s) BZ_TRY(bzk_batch_sample(cap, s, (const float*)g->logits->ptr, nullptr, g->next, g->log, g->step, bz_batch_graph::LOGCAP));
+    else BZ_TRY(bzk_batch_argmax(cap, (const float*)g->logits->ptr, m->cfg.vocab, g->next, g->log, g->step, bz_batch_graph::LOGCAP, N));
+    if (c) BZ_TRY(bzk_grammar_advance_rows(cap, c, g->next));
+    if (er)
+      BZ_TRY(bzk_engine_finish(cap, er->rows, g->next, g->pos, g->table, max_blocks, g->step, bz_batch_graph::LOGCAP, N, er->status, er->nlive, c ? bzk_grammar_cursor_states(c) : nullptr));
+    return BZ_OK;
+  };
+  BZ_TRY(capture_graph(body, &g->graph, &g->exec));
+  *out = g.release();
   return BZ_OK;
 }
 extern "C" int bz_decode_batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_graph** out) {
@@ -3305,6 +3291,43 @@ static int penalty_window(const std::vector<uint32_t>& hist, int last_n, std::ve
 
 extern "C" int bz_generate(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int64_t* out_tokens, bz_gen_stats* stats) { return bz_generate_grammar(m, prompt, n_prompt, gc, nullptr, nullptr, nullptr, 0, out_tokens, stats); }
 
+// What a generation loop has to show on every way out, failure included; fill_gen_stats turns it into bz_gen_stats.
+struct GenRun {
+  std::chrono::steady_clock::time_point T0 = std::chrono::steady_clock::now(), T1 = T0;   // start of the call, end of the prompt
+  std::vector<std::chrono::steady_clock::time_point> tok_t;   // host arrival time of every generated token (cli/bench.rs:285-292: TTFT, inter-token latency)
+  int n_out = 0, finish = 0;
+};
+static void fill_gen_stats(const GenRun& r, std::chrono::steady_clock::time_point T2, bz_gen_stats* stats) {
+  if (!stats) return;
+  memset(stats, 0, sizeof(*stats));
+  stats->prefill_ms = std::chrono::duration<double, std::milli>(r.T1 - r.T0).count();
+  stats->decode_ms = std::chrono::duration<double, std::milli>(T2 - r.T1).count();
+  stats->n_generated = r.n_out; stats->finish_reason = r.finish;
+  if (r.tok_t.empty()) return;   // cli/bench.rs:285-306
+  auto ms = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(t - r.T0).count(); };
+  stats->ttft_ms = ms(r.tok_t.front()); stats->total_ms = ms(r.tok_t.back());
+  std::vector<double> itl;
+  for (size_t i = 1; i < r.tok_t.size(); i++) itl.push_back(std::chrono::duration<double, std::milli>(r.tok_t[i] - r.tok_t[i - 1]).count());
+  if (itl.empty()) return;
+  std::sort(itl.begin(), itl.end());
+  auto pct = [&](double p) { size_t k = (size_t)std::ceil(p / 100.0 * (double)itl.size()); k = k ? k - 1 : 0; return itl[std::min(k, itl.size() - 1)]; };
+  stats->itl_p50_ms = pct(50.0); stats->itl_p99_ms = pct(99.0); stats->itl_max_ms = itl.back();
+  const double dec = stats->total_ms - stats->ttft_ms;
+  stats->decode_tok_per_s = dec > 0.0 ? (double)itl.size() / (dec / 1e3) : 0.0;
+}
+
+// What bz_generate_grammar owns while its loop runs.  Members go last to first: the decode graph and the grammar cursor before the caches and
+// tensors they borrow.
+struct GenLoop {
+  Owned<bz_device_grammar, bz_device_grammar_free> dg; Owned<bz_mirostat, bz_mirostat_free> mstate;
+  Owned<bz_ssm_state, bz_ssm_state_free> ssm; Owned<bz_paged_kv, bz_paged_kv_free> pkv; Owned<bz_kv, bz_kv_free> kv;
+  Owned<bz_tensor, bz_tensor_free> t_bt, t_slot, t_cnts, t_ids, t_tok, t_logits, t_prompt;
+  Owned<bz_grammar_cursor, bz_grammar_cursor_free> cursor; Owned<bz_decode_graph, bz_decode_graph_free> graph;
+  GenRun run;
+  int loop(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int max_tokens, const char* backend, bz_grammar* g, const uint8_t* vocab_bytes,
+           const int64_t* offsets, int64_t V, int64_t* out_tokens);
+};
+
 // the loop itself; `g` (nullable) = gen_config.grammar compiled (executor_generate.rs:96-121): masked on the device before every logits_to_token, advanced on the host
 // with the bytes of every token that comes back
 extern "C" int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, bz_grammar* g, const uint8_t* vocab_bytes,
@@ -3314,108 +3337,111 @@ extern "C" int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_pro
   if (g && (!offsets || V != m->cfg.vocab)) BZ_FAIL(BZ_E_INVALID, "generate: a grammar needs the bytes of all %d tokens of the model's vocabulary (got V = %lld)", m->cfg.vocab, (long long)V);
   if (n_prompt <= 0) { if (stats) memset(stats, 0, sizeof(*stats)); return BZ_OK; }  // executor_generate.rs:75-77
   const bz_model_config& c = m->cfg;
-  bz_device* dev = m->dev;
-  BZ_HIP(hipSetDevice(dev->id));
+  BZ_HIP(hipSetDevice(m->dev->id));
   for (int i = 0; i < n_prompt; i++) if (prompt[i] < 0 || prompt[i] >= c.vocab) BZ_FAIL(BZ_E_INVALID, "generate: prompt token %lld out of vocab", (long long)prompt[i]);
   int max_tokens = std::min(gc->max_tokens, std::max(0, c.max_seq_len - n_prompt));  // :79-82
-  const bool greedy = gc->temperature == 0.0f;
-  if (gc->use_graph && !greedy) BZ_FAIL(BZ_E_INVALID, "generate: graph mode is greedy-only (cli/run.rs:144-157)");
+  if (gc->use_graph && gc->temperature != 0.0f) BZ_FAIL(BZ_E_INVALID, "generate: graph mode is greedy-only (cli/run.rs:144-157)");
   if (gc->use_graph && (gc->dry_multiplier > 0.f || gc->typical_p > 0.f || gc->n_logit_bias > 0 || gc->mirostat_mode >= 2))
     BZ_FAIL(BZ_E_INVALID, "generate: graph mode has no host-side sampler options");
   if (gc->n_logit_bias < 0 || (gc->n_logit_bias > 0 && (!gc->logit_bias_ids || !gc->logit_bias_vals))) BZ_FAIL(BZ_E_INVALID, "generate: bad logit_bias arrays");
+  const char* backend = c.arch == BZ_ARCH_MAMBA2 ? "mamba2" : (gc->paged ? "paged" : "contiguous");
+  GenLoop L;
+  const int rc = L.loop(m, prompt, n_prompt, gc, max_tokens, backend, g, vocab_bytes, offsets, V, out_tokens);
+  const auto T2 = std::chrono::steady_clock::now();
+  BZ_TRACE("phase=\"decode_end\" backend=\"%s\" generated=%d", backend, L.run.n_out);                // :181,340,409
+  fill_gen_stats(L.run, T2, stats);
+  return rc;
+  BZ_API_END
+}
+
+int GenLoop::loop(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int max_tokens, const char* backend, bz_grammar* g, const uint8_t* vocab_bytes,
+                  const int64_t* offsets, int64_t V, int64_t* out_tokens) {
+  const bz_model_config& c = m->cfg;
+  bz_device* dev = m->dev;
+  const bool greedy = gc->temperature == 0.0f;
   const int kv_dt = c.act_dtype;
-  int rc = BZ_OK;
-  bz_tensor *t_prompt = nullptr, *t_logits = nullptr, *t_tok = nullptr, *t_ids = nullptr, *t_cnts = nullptr, *t_slot = nullptr, *t_bt = nullptr;
-  bz_kv* kv = nullptr; bz_paged_kv* pkv = nullptr; bz_decode_graph* graph = nullptr; bz_ssm_state* ssm = nullptr; bz_mirostat* mstate = nullptr;
-  bz_device_grammar* dg = nullptr; bz_grammar_cursor* cursor = nullptr;
   // the reference's graph mode knows no grammar (cuda_graphs.rs).  Here the captured step carries one for the Llama family; it knows no penalties (they are
   // ignored in graph mode), so a grammar with an active penalty keeps the eager loop, which applies them -- and so do Mamba2 and DeepSeek-V2.  With nothing to
   // emit (max_tokens == 0) the eager loop runs too: it leaves g untouched and builds no cursor or graph
   const bool gen_pen = gc->repeat_penalty != 1.0f || gc->frequency_penalty != 0.f || gc->presence_penalty != 0.f;
   const bool use_graph = gc->use_graph && (!g || (c.arch == BZ_ARCH_LLAMA && !gen_pen && max_tokens > 0));
   const bool mamba = c.arch == BZ_ARCH_MAMBA2;   // executor_generate.rs:123-181
-  auto mamba_arch = [](const bz_model_config& cc) { return cc.arch == BZ_ARCH_MAMBA2; };
   std::vector<uint32_t> history(prompt, prompt + n_prompt);
   std::vector<int32_t> bt;
-  int n_out = 0, finish = 0;
-  auto T0 = std::chrono::steady_clock::now();
-  auto T1 = T0;
-  std::vector<std::chrono::steady_clock::time_point> tok_t;   // host arrival time of every generated token (cli/bench.rs:285-292: TTFT, inter-token latency)
+  int& n_out = run.n_out; int& finish = run.finish;
+  std::vector<std::chrono::steady_clock::time_point>& tok_t = run.tok_t;
   tok_t.reserve((size_t)std::max(max_tokens, 0));
-  const char* backend = mamba_arch(c) ? "mamba2" : (gc->paged ? "paged" : "contiguous");
   BZ_TRACE("phase=\"prefill_start\" backend=\"%s\" prompt_tokens=%d", backend, n_prompt);   // executor_generate.rs:136,252,355
   int64_t sh1[1] = {1}, shp[1] = {n_prompt}, shv[2] = {1, c.vocab}, sh64[1] = {4096};
-#define GEN_TRY(x) do { rc = (x); if (rc != BZ_OK) goto done; } while (0)
-  GEN_TRY(bz_tensor_from_host(dev, BZ_I64, shp, 1, prompt, &t_prompt));
-  GEN_TRY(bz_tensor_zeros(dev, BZ_F32, shv, 2, &t_logits));
-  GEN_TRY(bz_tensor_zeros(dev, BZ_I64, sh1, 1, &t_tok));
-  GEN_TRY(bz_tensor_zeros(dev, BZ_I64, sh64, 1, &t_ids));
-  GEN_TRY(bz_tensor_zeros(dev, BZ_I32, sh64, 1, &t_cnts));
-  if (g) GEN_TRY(bz_grammar_to_device(dev, g, vocab_bytes, offsets, V, &dg));     // :114 dfa.to_device(&vocab_bytes, &self.device)
+  BZ_TRY(bz_tensor_from_host(dev, BZ_I64, shp, 1, prompt, t_prompt.out()));
+  BZ_TRY(bz_tensor_zeros(dev, BZ_F32, shv, 2, t_logits.out()));
+  BZ_TRY(bz_tensor_zeros(dev, BZ_I64, sh1, 1, t_tok.out()));
+  BZ_TRY(bz_tensor_zeros(dev, BZ_I64, sh64, 1, t_ids.out()));
+  BZ_TRY(bz_tensor_zeros(dev, BZ_I32, sh64, 1, t_cnts.out()));
+  if (g) BZ_TRY(bz_grammar_to_device(dev, g, vocab_bytes, offsets, V, dg.out()));     // :114 dfa.to_device(&vocab_bytes, &self.device)
   if (mamba) {
-    GEN_TRY(bz_ssm_state_create(m, 1, c.act_dtype, &ssm));                       // :131-133 LayeredSsmState::new
-    GEN_TRY(bz_forward_ssm(m, t_prompt, n_prompt, ssm, t_logits, 0));            // :137
+    BZ_TRY(bz_ssm_state_create(m, 1, c.act_dtype, ssm.out()));                       // :131-133 LayeredSsmState::new
+    BZ_TRY(bz_forward_ssm(m, t_prompt, n_prompt, ssm, t_logits, 0));            // :137
   } else if (gc->paged) {
     const int bs = gc->block_size > 0 ? gc->block_size : 16;
     const int total = n_prompt + max_tokens;
     const int nblocks = (total + bs - 1) / bs + 4;  // executor_generate.rs:191-196
-    GEN_TRY(bz_paged_kv_create(dev, c.n_layers, nblocks, bs, c.n_kv_heads, c.head_dim, kv_dt, &pkv));
+    BZ_TRY(bz_paged_kv_create(dev, c.n_layers, nblocks, bs, c.n_kv_heads, c.head_dim, kv_dt, pkv.out()));
     // CpuBlockAllocator hands out blocks in order; a private allocator gives 0,1,2,...
     bt.resize(nblocks);
     for (int i = 0; i < nblocks; i++) bt[i] = i;
     int64_t shb[1] = {nblocks}, shs[1] = {n_prompt};
-    GEN_TRY(bz_tensor_from_host(dev, BZ_I32, shb, 1, bt.data(), &t_bt));
+    BZ_TRY(bz_tensor_from_host(dev, BZ_I32, shb, 1, bt.data(), t_bt.out()));
     std::vector<int32_t> slots(n_prompt);
     for (int i = 0; i < n_prompt; i++) slots[i] = bt[i / bs] * bs + i % bs;  // compute_slot_mapping (batch_decode.rs:81-88)
-    GEN_TRY(bz_tensor_from_host(dev, BZ_I32, shs, 1, slots.data(), &t_slot));
-    GEN_TRY(bz_forward_paged(m, t_prompt, n_prompt, pkv, t_slot, t_bt, nblocks, n_prompt, 0, t_logits, 0));
+    BZ_TRY(bz_tensor_from_host(dev, BZ_I32, shs, 1, slots.data(), t_slot.out()));
+    BZ_TRY(bz_forward_paged(m, t_prompt, n_prompt, pkv, t_slot, t_bt, nblocks, n_prompt, 0, t_logits, 0));
   } else {
     const int cap = std::min(n_prompt + max_tokens, c.max_seq_len);  // :346
-    GEN_TRY(bz_kv_create(dev, c.n_layers, 1, c.n_kv_heads, std::max(cap, 1), c.max_seq_len, c.head_dim, kv_dt, &kv));
-    GEN_TRY(bz_forward_kv(m, t_prompt, n_prompt, kv, 0, t_logits, 0));
+    BZ_TRY(bz_kv_create(dev, c.n_layers, 1, c.n_kv_heads, std::max(cap, 1), c.max_seq_len, c.head_dim, kv_dt, kv.out()));
+    BZ_TRY(bz_forward_kv(m, t_prompt, n_prompt, kv, 0, t_logits, 0));
   }
-  GEN_TRY(bz_device_synchronize(dev));
-  T1 = std::chrono::steady_clock::now();
+  BZ_TRY(bz_device_synchronize(dev));
+  run.T1 = std::chrono::steady_clock::now();
   BZ_TRACE("phase=\"prefill_end\" backend=\"%s\"", backend);                                   // :139,264,360
   BZ_TRACE("phase=\"decode_start\" backend=\"%s\" max_tokens=%d graph=%d", backend, max_tokens, (int)use_graph);   // :140,265,361
 
   if (use_graph) {
     // cuda_graphs.rs:149-189: first token from the prefill logits, then one graph launch per token
     int64_t tok;
-    if (dg) GEN_TRY(bz_grammar_dfa_mask_logits(dev, t_logits, 1, c.vocab, dg, t_logits));   // the first token is masked as in the eager loop
-    GEN_TRY(bz_argmax_to_buf(dev, t_logits, 1, c.vocab, t_tok));
-    GEN_TRY(bz_tensor_to_host(t_tok, &tok, 8));
+    if (dg) BZ_TRY(bz_grammar_dfa_mask_logits(dev, t_logits, 1, c.vocab, dg, t_logits));   // the first token is masked as in the eager loop
+    BZ_TRY(bz_argmax_to_buf(dev, t_logits, 1, c.vocab, t_tok));
+    BZ_TRY(bz_tensor_to_host(t_tok, &tok, 8));
     const auto t_first = std::chrono::steady_clock::now();   // the first token is on the host here; capturing the graph comes after it
     if (g) {          // the cursor starts from the state after the first token; from here on the state lives on the device
-      if (tok < 0 || tok >= V) { bz_set_error("generate: sampled token %lld outside the vocabulary", (long long)tok); rc = BZ_E_INVALID; goto done; }
-      GEN_TRY(bz_grammar_advance(g, vocab_bytes + offsets[tok], (size_t)(offsets[tok + 1] - offsets[tok]), nullptr));
-      GEN_TRY(bz_grammar_cursor_create(dg, 1, &cursor));
-      GEN_TRY(bz_grammar_cursor_set_row(cursor, 0, (uint32_t)bz_grammar_current_state(g)));
+      if (tok < 0 || tok >= V) BZ_FAIL(BZ_E_INVALID, "generate: sampled token %lld outside the vocabulary", (long long)tok);
+      BZ_TRY(bz_grammar_advance(g, vocab_bytes + offsets[tok], (size_t)(offsets[tok + 1] - offsets[tok]), nullptr));
+      BZ_TRY(bz_grammar_cursor_create(dg, 1, cursor.out()));
+      BZ_TRY(bz_grammar_cursor_set_row(cursor, 0, (uint32_t)bz_grammar_current_state(g)));
     }
-    if (mamba) GEN_TRY(bz_decode_graph_capture_ssm(m, ssm, &graph));
+    if (mamba) BZ_TRY(bz_decode_graph_capture_ssm(m, ssm, graph.out()));
     else if (gc->paged) {
-      if (cursor) GEN_TRY(bz_decode_graph_capture_paged_grammar(m, pkv, (int)bt.size(), cursor, &graph));
-      else GEN_TRY(bz_decode_graph_capture_paged(m, pkv, (int)bt.size(), &graph));
-      GEN_TRY(bz_decode_graph_set_block_table(graph, bt.data(), (int)bt.size()));
-    } else if (cursor) GEN_TRY(bz_decode_graph_capture_grammar(m, kv, cursor, &graph));
-    else GEN_TRY(bz_decode_graph_capture(m, kv, &graph));
-    GEN_TRY(bz_decode_graph_seed(graph, tok, n_prompt));
+      if (cursor) BZ_TRY(bz_decode_graph_capture_paged_grammar(m, pkv, (int)bt.size(), cursor, graph.out()));
+      else BZ_TRY(bz_decode_graph_capture_paged(m, pkv, (int)bt.size(), graph.out()));
+      BZ_TRY(bz_decode_graph_set_block_table(graph, bt.data(), (int)bt.size()));
+    } else if (cursor) BZ_TRY(bz_decode_graph_capture_grammar(m, kv, cursor, graph.out()));
+    else BZ_TRY(bz_decode_graph_capture(m, kv, graph.out()));
+    BZ_TRY(bz_decode_graph_seed(graph, tok, n_prompt));
     BZ_TRACE("generate: graph captured and seeded with token %lld at position %d", (long long)tok, n_prompt);
     for (int i = 0; i < max_tokens; i++) {
       out_tokens[n_out++] = tok; history.push_back((uint32_t)tok); tok_t.push_back(i == 0 ? t_first : std::chrono::steady_clock::now());
       if (tok == gc->eos_id) { finish = 1; break; }
       if (i + 1 == max_tokens) break;
       auto tl0 = std::chrono::steady_clock::now();
-      GEN_TRY(bz_decode_graph_replay(graph));
+      BZ_TRY(bz_decode_graph_replay(graph));
       auto tl1 = std::chrono::steady_clock::now();
-      GEN_TRY(bz_decode_graph_read_token(graph, i, &tok));
+      BZ_TRY(bz_decode_graph_read_token(graph, i, &tok));
       BZ_TRACE("step=%d token=%lld fwd_launch_us=%.1f sync_us=%.1f", i, (long long)tok, std::chrono::duration<double, std::micro>(tl1 - tl0).count(),
                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tl1).count());   // :313,394 fwd_launch / sync split
     }
-    if (g && n_out > 1) GEN_TRY(bz_grammar_advance_tokens(g, vocab_bytes, offsets, V, out_tokens + 1, n_out - 1, nullptr));   // g ends where the eager loop leaves it
+    if (g && n_out > 1) BZ_TRY(bz_grammar_advance_tokens(g, vocab_bytes, offsets, V, out_tokens + 1, n_out - 1, nullptr));   // g ends where the eager loop leaves it
   } else {
     std::vector<int64_t> ids; std::vector<int32_t> cnts;
-    const bool has_pen = gen_pen;
     // host-side options (sampling.rs:393-437): the reference pulls the logits to the CPU for these, and so does this loop
     const bool needs_cpu = gc->dry_multiplier > 0.f || gc->typical_p > 0.f;
     const bool dyn = !greedy && gc->dynatemp_range > 0.f, miro = gc->mirostat_mode >= 2;
@@ -3427,94 +3453,63 @@ extern "C" int bz_generate_grammar(bz_model* m, const int64_t* prompt, int n_pro
     for (int i = 0; i < max_tokens; i++) {
       float temperature = greedy ? 0.0f : gc->temperature;
       if (host_row && (!mask || needs_cpu)) {
-        GEN_TRY(bz_tensor_to_host(t_logits, row.data(), (size_t)c.vocab * 4));
-        if (gc->dry_multiplier > 0.f) GEN_TRY(bz_apply_dry_penalty(row.data(), c.vocab, history.data(), (int64_t)history.size(), gc->dry_multiplier, gc->dry_base > 0 ? gc->dry_base : 2, gc->dry_allowed_length));
-        if (gc->typical_p > 0.f) GEN_TRY(bz_apply_typical_filter(row.data(), c.vocab, gc->typical_p));
+        BZ_TRY(bz_tensor_to_host(t_logits, row.data(), (size_t)c.vocab * 4));
+        if (gc->dry_multiplier > 0.f) BZ_TRY(bz_apply_dry_penalty(row.data(), c.vocab, history.data(), (int64_t)history.size(), gc->dry_multiplier, gc->dry_base > 0 ? gc->dry_base : 2, gc->dry_allowed_length));
+        if (gc->typical_p > 0.f) BZ_TRY(bz_apply_typical_filter(row.data(), c.vocab, gc->typical_p));
       }
       if (mask) {
-        if (needs_cpu) GEN_TRY(bz_tensor_copy_from_host(t_logits, row.data(), (size_t)c.vocab * 4));
-        GEN_TRY(bz_grammar_dfa_mask_logits(dev, t_logits, 1, c.vocab, dg, t_logits));          // sampling.rs:415-419
-        if (post) GEN_TRY(bz_tensor_to_host(t_logits, row.data(), (size_t)c.vocab * 4));
+        if (needs_cpu) BZ_TRY(bz_tensor_copy_from_host(t_logits, row.data(), (size_t)c.vocab * 4));
+        BZ_TRY(bz_grammar_dfa_mask_logits(dev, t_logits, 1, c.vocab, dg, t_logits));          // sampling.rs:415-419
+        if (post) BZ_TRY(bz_tensor_to_host(t_logits, row.data(), (size_t)c.vocab * 4));
       }
       if (host_row && !miro) {
-        if (gc->n_logit_bias > 0) GEN_TRY(bz_apply_logit_bias(row.data(), c.vocab, gc->logit_bias_ids, gc->logit_bias_vals, gc->n_logit_bias));
+        if (gc->n_logit_bias > 0) BZ_TRY(bz_apply_logit_bias(row.data(), c.vocab, gc->logit_bias_ids, gc->logit_bias_vals, gc->n_logit_bias));
         if (dyn) temperature = bz_compute_dynamic_temperature(row.data(), c.vocab, gc->temperature, gc->dynatemp_range, gc->dynatemp_exponent > 0.f ? gc->dynatemp_exponent : 1.0f);
-        if (!mask || post) GEN_TRY(bz_tensor_copy_from_host(t_logits, row.data(), (size_t)c.vocab * 4));
+        if (!mask || post) BZ_TRY(bz_tensor_copy_from_host(t_logits, row.data(), (size_t)c.vocab * 4));
       }
       if (miro) {       // sampling.rs:96-110,118-150: Mirostat v2 on the CPU row, token goes back to the device
-        if (!mstate) GEN_TRY(bz_mirostat_create(gc->mirostat_tau, gc->mirostat_eta, gc->seed, &mstate));
+        if (!mstate) BZ_TRY(bz_mirostat_create(gc->mirostat_tau, gc->mirostat_eta, gc->seed, mstate.out()));
         uint32_t mt = 0;
-        GEN_TRY(bz_mirostat_sample(mstate, row.data(), c.vocab, gc->temperature, &mt, nullptr));
+        BZ_TRY(bz_mirostat_sample(mstate, row.data(), c.vocab, gc->temperature, &mt, nullptr));
         const int64_t mt64 = mt;
-        GEN_TRY(bz_tensor_copy_from_host(t_tok, &mt64, 8));
+        BZ_TRY(bz_tensor_copy_from_host(t_tok, &mt64, 8));
       } else {
-      int n = has_pen ? penalty_window(history, gc->repeat_last_n, ids, cnts) : 0;  // sampling.rs:431
+      int n = gen_pen ? penalty_window(history, gc->repeat_last_n, ids, cnts) : 0;  // sampling.rs:431
       if (n > 4096) { n = 4096; }
-      if (n) { GEN_TRY(bz_tensor_copy_from_host(t_ids, ids.data(), (size_t)n * 8)); GEN_TRY(bz_tensor_copy_from_host(t_cnts, cnts.data(), (size_t)n * 4)); }
-      GEN_TRY(bz_logits_to_token(dev, t_logits, 1, c.vocab, t_ids, t_cnts, n, gc->repeat_penalty, gc->frequency_penalty, gc->presence_penalty,
+      if (n) { BZ_TRY(bz_tensor_copy_from_host(t_ids, ids.data(), (size_t)n * 8)); BZ_TRY(bz_tensor_copy_from_host(t_cnts, cnts.data(), (size_t)n * 4)); }
+      BZ_TRY(bz_logits_to_token(dev, t_logits, 1, c.vocab, t_ids, t_cnts, n, gc->repeat_penalty, gc->frequency_penalty, gc->presence_penalty,
                                  temperature, gc->top_k, gc->top_p, gc->min_p, gc->seed + (uint64_t)i, t_tok));
       }
       uint64_t ev;
-      GEN_TRY(bz_event_record(dev, &ev));                                           // :367 record_event
+      BZ_TRY(bz_event_record(dev, &ev));                                           // :367 record_event
       const bool last = i + 1 == max_tokens;
       // :372 the next forward is launched BEFORE the token is read back (token stays on device)
       if (!last) {
         if (mamba) {
-          GEN_TRY(bz_forward_ssm(m, t_tok, 1, ssm, t_logits, 0));                  // :148
+          BZ_TRY(bz_forward_ssm(m, t_tok, 1, ssm, t_logits, 0));                  // :148
         } else if (gc->paged) {
           const int bs = pkv->block_size, cur = pkv->seq_len;
           int32_t slot = bt[cur / bs] * bs + cur % bs;
-          GEN_TRY(bz_tensor_copy_from_host(t_slot, &slot, 4));
-          GEN_TRY(bz_forward_paged(m, t_tok, 1, pkv, t_slot, t_bt, (int)bt.size(), cur + 1, cur, t_logits, 0));
+          BZ_TRY(bz_tensor_copy_from_host(t_slot, &slot, 4));
+          BZ_TRY(bz_forward_paged(m, t_tok, 1, pkv, t_slot, t_bt, (int)bt.size(), cur + 1, cur, t_logits, 0));
         } else {
-          GEN_TRY(bz_forward_kv(m, t_tok, 1, kv, kv->seq_len, t_logits, 0));
+          BZ_TRY(bz_forward_kv(m, t_tok, 1, kv, kv->seq_len, t_logits, 0));
         }
       }
       int64_t tok;
       auto ts0 = std::chrono::steady_clock::now();
-      GEN_TRY(bz_tensor_to_host_pipelined(t_tok, ev, &tok, 8));                      // :378 read_token_id
+      BZ_TRY(bz_tensor_to_host_pipelined(t_tok, ev, &tok, 8));                      // :378 read_token_id
       BZ_TRACE("step=%d token=%lld sync_us=%.1f", i, (long long)tok, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ts0).count());
       out_tokens[n_out++] = tok; history.push_back((uint32_t)tok); tok_t.push_back(std::chrono::steady_clock::now());
       if (g) {          // :156-166 advance the DFA with the token's bytes, then dg.current_state = dfa.current_state()
-        if (tok < 0 || tok >= V) { bz_set_error("generate: sampled token %lld outside the vocabulary", (long long)tok); rc = BZ_E_INVALID; goto done; }
-        GEN_TRY(bz_grammar_advance(g, vocab_bytes + offsets[tok], (size_t)(offsets[tok + 1] - offsets[tok]), nullptr));
-        GEN_TRY(bz_device_grammar_set_state(dg, (uint32_t)bz_grammar_current_state(g)));
+        if (tok < 0 || tok >= V) BZ_FAIL(BZ_E_INVALID, "generate: sampled token %lld outside the vocabulary", (long long)tok);
+        BZ_TRY(bz_grammar_advance(g, vocab_bytes + offsets[tok], (size_t)(offsets[tok + 1] - offsets[tok]), nullptr));
+        BZ_TRY(bz_device_grammar_set_state(dg, (uint32_t)bz_grammar_current_state(g)));
       }
       if (tok == gc->eos_id) { finish = 1; break; }
     }
   }
-  GEN_TRY(bz_device_synchronize(dev));
-done:
-  {
-    auto T2 = std::chrono::steady_clock::now();
-    BZ_TRACE("phase=\"decode_end\" backend=\"%s\" generated=%d", backend, n_out);                // :181,340,409
-    if (stats) {
-      memset(stats, 0, sizeof(*stats));
-      stats->prefill_ms = std::chrono::duration<double, std::milli>(T1 - T0).count();
-      stats->decode_ms = std::chrono::duration<double, std::milli>(T2 - T1).count();
-      stats->n_generated = n_out; stats->finish_reason = finish;
-      if (!tok_t.empty()) {   // cli/bench.rs:285-306
-        auto ms = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(t - T0).count(); };
-        stats->ttft_ms = ms(tok_t.front()); stats->total_ms = ms(tok_t.back());
-        std::vector<double> itl;
-        for (size_t i = 1; i < tok_t.size(); i++) itl.push_back(std::chrono::duration<double, std::milli>(tok_t[i] - tok_t[i - 1]).count());
-        if (!itl.empty()) {
-          std::sort(itl.begin(), itl.end());
-          auto pct = [&](double p) { size_t k = (size_t)std::ceil(p / 100.0 * (double)itl.size()); k = k ? k - 1 : 0; return itl[std::min(k, itl.size() - 1)]; };
-          stats->itl_p50_ms = pct(50.0); stats->itl_p99_ms = pct(99.0); stats->itl_max_ms = itl.back();
-          const double dec = stats->total_ms - stats->ttft_ms;
-          stats->decode_tok_per_s = dec > 0.0 ? (double)itl.size() / (dec / 1e3) : 0.0;
-        }
-      }
-    }
-  }
-  bz_decode_graph_free(graph); bz_grammar_cursor_free(cursor);
-  bz_tensor_free(t_prompt); bz_tensor_free(t_logits); bz_tensor_free(t_tok); bz_tensor_free(t_ids); bz_tensor_free(t_cnts);
-  bz_tensor_free(t_slot); bz_tensor_free(t_bt);
-  bz_kv_free(kv); bz_paged_kv_free(pkv); bz_ssm_state_free(ssm); bz_mirostat_free(mstate); bz_device_grammar_free(dg);
-  return rc;
-#undef GEN_TRY
-  BZ_API_END
+  return bz_device_synchronize(dev);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -3564,13 +3559,12 @@ static int llama_verify_rows(bz_model* m, const long long* d_tok, int R, bz_kv* 
     BZ_TRY(bzk_spec_argmax_final(st, m->sp_pval, m->sp_pidx, m->sp_nb, R, m->sp_argmax));
   } else {
     for (int r = 0; r < R; r++) {
-      hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, m->pos_tmp, position + r);
       StepIO io{};
-      io.kv = view_of(kv); io.d_tok = d_tok + r; io.d_pos = m->pos_tmp; io.att_positions = att_positions_for(position + r + 1); io.do_head = true;
+      io.kv = view_of(kv); io.d_tok = d_tok + r; io.do_head = true;
       FinalArgs fa{};
       fa.tok_out = m->sp_argmax + r;
       io.final_args = &fa;
-      BZ_TRY(llama_step(m, io));
+      BZ_TRY(step_at(m, position + r, io, llama_step));
       BZ_HIP(hipMemcpyAsync(logits + (size_t)r * c.vocab, m->logits, (size_t)c.vocab * 4, hipMemcpyDeviceToDevice, st));
     }
   }
@@ -3613,7 +3607,7 @@ extern "C" int bz_forward_kv_verify(bz_model* m, const bz_tensor* tokens, int R,
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   if (m->cfg.arch != BZ_ARCH_LLAMA) BZ_FAIL(BZ_E_UNSUPPORTED, "forward_kv_verify: Llama-family models only (Mamba2 state rollback and the DeepSeek-V2 latent cache are not built)");
   if (R > 16) BZ_FAIL(BZ_E_INVALID, "forward_kv_verify: R = %d rows (1..16)", R);
-  if (!kv || kv->layers != m->cfg.n_layers || kv->n_kv != m->cfg.n_kv_heads || kv->hd != m->cfg.head_dim) BZ_FAIL(BZ_E_INVALID, "forward_kv_verify: cache does not match the model");
+  BZ_TRY(check_cache(m, kv, "forward_kv_verify"));
   if (position < 0 || position + R > m->cfg.max_seq_len) BZ_FAIL(BZ_E_INVALID, "forward_kv_verify: position %d + R %d exceeds max_seq_len %d", position, R, m->cfg.max_seq_len);
   if (logits_out && (logits_out->dtype != BZ_F32 || logits_out->nbytes < (size_t)R * m->cfg.vocab * 4)) BZ_FAIL(BZ_E_INVALID, "forward_kv_verify: logits_out must be F32 [R,vocab]");
   if (!n_accept || !tokens_out) BZ_FAIL(BZ_E_INVALID, "forward_kv_verify: n_accept / tokens_out required");
@@ -3654,6 +3648,19 @@ extern "C" int bz_speculative_create(bz_model* target, bz_model* draft, const bz
 }
 extern "C" int bz_speculative_free(bz_speculative* sp) { delete sp; return BZ_OK; }
 
+static int spec_event_free(std::remove_pointer<hipEvent_t>::type* e) { if (e) hipEventDestroy(e); return BZ_OK; }
+// What bz_generate_speculative owns while its loop runs (the events go first, the caches last), and the counters behind bz_spec_stats.
+struct SpecLoop {
+  Owned<bz_kv, bz_kv_free> dkv, kv;
+  Owned<bz_tensor, bz_tensor_free> t_vt, t_dlogits, t_logits, t_prompt;
+  Owned<std::remove_pointer<hipEvent_t>::type, spec_event_free> ev[3];
+  GenRun run;
+  int kcur = 0, path_all = -1;
+  long long it = 0, drafted = 0, accepted = 0;
+  double draft_ms = 0.0, verify_ms = 0.0;
+  int loop(bz_speculative* sp, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int max_tokens, int64_t* out_tokens);
+};
+
 extern "C" int bz_generate_speculative(bz_speculative* sp, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int64_t* out_tokens, bz_gen_stats* stats,
                                        bz_spec_stats* sstats) {
   BZ_API_BEGIN
@@ -3677,69 +3684,75 @@ extern "C" int bz_generate_speculative(bz_speculative* sp, const int64_t* prompt
   const int max_tokens = std::min(gc->max_tokens, std::max(0, tc.max_seq_len - n_prompt));
   std::lock_guard<std::recursive_mutex> lock_t(tm->mu);
   std::lock_guard<std::recursive_mutex> lock_d(dm->mu);
-  int rc = BZ_OK;
-  bz_tensor *t_prompt = nullptr, *t_logits = nullptr, *t_dlogits = nullptr, *t_vt = nullptr;
-  bz_kv *kv = nullptr, *dkv = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  int n_out = 0, finish = 0, kcur = sp->k, path_all = -1, k_prev = 0;
-  long long it = 0, drafted = 0, accepted = 0;
-  double draft_ms = 0.0, verify_ms = 0.0;
-  auto T0 = std::chrono::steady_clock::now();
-  auto T1 = T0;
-  std::vector<std::chrono::steady_clock::time_point> tok_t;
+  SpecLoop L;
+  L.kcur = sp->k;
+  const int rc = L.loop(sp, prompt, n_prompt, gc, max_tokens, out_tokens);
+  fill_gen_stats(L.run, std::chrono::steady_clock::now(), stats);
+  if (sstats) {
+    sstats->iterations = L.it; sstats->drafted_tokens = L.drafted; sstats->accepted_tokens = L.accepted; sstats->rejected_tokens = L.drafted - L.accepted;
+    sstats->verify_path = L.path_all; sstats->final_depth = L.kcur; sstats->draft_ms = L.draft_ms; sstats->verify_ms = L.verify_ms;
+  }
+  return rc;
+  BZ_API_END
+}
+
+int SpecLoop::loop(bz_speculative* sp, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int max_tokens, int64_t* out_tokens) {
+  bz_model* tm = sp->target; bz_model* dm = sp->draft;
+  const bz_model_config& tc = tm->cfg; const bz_model_config& dc = dm->cfg;
+  bz_device* dev = tm->dev;
+  int& n_out = run.n_out; int& finish = run.finish;
+  std::vector<std::chrono::steady_clock::time_point>& tok_t = run.tok_t;
+  int k_prev = 0;
   tok_t.reserve((size_t)std::max(max_tokens, 0));
   hipStream_t st = dev->stream;
   int64_t shp[1] = {n_prompt}, shv[2] = {1, tc.vocab}, sh16[1] = {16};
-#define GEN_TRY(x) do { rc = (x); if (rc != BZ_OK) goto done; } while (0)
-#define GEN_HIP(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { bz_set_error("%s failed: %s", #x, hipGetErrorString(e__)); rc = BZ_E_HIP; goto done; } } while (0)
-  GEN_TRY(ensure_spec_ws(tm));
-  GEN_TRY(bz_tensor_from_host(dev, BZ_I64, shp, 1, prompt, &t_prompt));
-  GEN_TRY(bz_tensor_zeros(dev, BZ_F32, shv, 2, &t_logits));
-  GEN_TRY(bz_tensor_zeros(dev, BZ_F32, shv, 2, &t_dlogits));
-  GEN_TRY(bz_tensor_zeros(dev, BZ_I64, sh16, 1, &t_vt));          // the verify row [t, d1 .. dk]: slot 0 is written by the accept kernel, slot i + 1 by draft step i
-  for (int i = 0; i < 3; i++) GEN_HIP(hipEventCreate(&ev[i]));
-  GEN_TRY(bz_kv_create(dev, tc.n_layers, 1, tc.n_kv_heads, std::max(std::min(n_prompt + max_tokens, tc.max_seq_len), 1), tc.max_seq_len, tc.head_dim, tc.act_dtype, &kv));
-  GEN_TRY(bz_kv_create(dev, dc.n_layers, 1, dc.n_kv_heads, std::max(std::min(n_prompt + max_tokens, dc.max_seq_len), 1), dc.max_seq_len, dc.head_dim, dc.act_dtype, &dkv));
+  BZ_TRY(ensure_spec_ws(tm));
+  BZ_TRY(bz_tensor_from_host(dev, BZ_I64, shp, 1, prompt, t_prompt.out()));
+  BZ_TRY(bz_tensor_zeros(dev, BZ_F32, shv, 2, t_logits.out()));
+  BZ_TRY(bz_tensor_zeros(dev, BZ_F32, shv, 2, t_dlogits.out()));
+  BZ_TRY(bz_tensor_zeros(dev, BZ_I64, sh16, 1, t_vt.out()));          // the verify row [t, d1 .. dk]: slot 0 is written by the accept kernel, slot i + 1 by draft step i
+  for (int i = 0; i < 3; i++) BZ_HIP(hipEventCreate(ev[i].out()));
+  BZ_TRY(bz_kv_create(dev, tc.n_layers, 1, tc.n_kv_heads, std::max(std::min(n_prompt + max_tokens, tc.max_seq_len), 1), tc.max_seq_len, tc.head_dim, tc.act_dtype, kv.out()));
+  BZ_TRY(bz_kv_create(dev, dc.n_layers, 1, dc.n_kv_heads, std::max(std::min(n_prompt + max_tokens, dc.max_seq_len), 1), dc.max_seq_len, dc.head_dim, dc.act_dtype, dkv.out()));
   // both models take the prompt through their ordinary path; the first token is the target's argmax
-  GEN_TRY(bz_forward_kv(tm, t_prompt, n_prompt, kv, 0, t_logits, 0));
-  GEN_TRY(bz_forward_kv(dm, t_prompt, n_prompt, dkv, 0, t_dlogits, 0));
-  GEN_TRY(bz_device_synchronize(dev));
-  T1 = std::chrono::steady_clock::now();
+  BZ_TRY(bz_forward_kv(tm, t_prompt, n_prompt, kv, 0, t_logits, 0));
+  BZ_TRY(bz_forward_kv(dm, t_prompt, n_prompt, dkv, 0, t_dlogits, 0));
+  BZ_TRY(bz_device_synchronize(dev));
+  run.T1 = std::chrono::steady_clock::now();
   if (max_tokens > 0) {
     long long* vt = (long long*)t_vt->ptr;
     int64_t tok;
-    GEN_TRY(bz_argmax_to_buf(dev, t_logits, 1, tc.vocab, t_vt));
-    GEN_TRY(bz_tensor_to_host(t_vt, &tok, 8));
+    BZ_TRY(bz_argmax_to_buf(dev, t_logits, 1, tc.vocab, t_vt));
+    BZ_TRY(bz_tensor_to_host(t_vt, &tok, 8));
     out_tokens[n_out++] = tok; tok_t.push_back(std::chrono::steady_clock::now());
     if (tok == gc->eos_id) finish = 1;
     while (n_out < max_tokens && !finish) {
       const int P = n_prompt + n_out - 1;        // position of the last committed token t (vt[0]); the target's cache holds P rows
       const int k = std::max(0, std::min(std::min(kcur, max_tokens - n_out - 1), std::min(tc.max_seq_len, dc.max_seq_len) - P - 1));
-      GEN_HIP(hipEventRecord(ev[0], st));
+      BZ_HIP(hipEventRecord(ev[0], st));
       if (k > 0) {
-        GEN_TRY(kv_grow(dkv, P + k));
+        BZ_TRY(kv_grow(dkv, P + k));
         auto dstep = [&](const long long* tokp, int pos, long long* out_slot) -> int {
-          hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, dm->pos_tmp, pos);
           StepIO io{};
-          io.kv = view_of(dkv); io.d_tok = tokp; io.d_pos = dm->pos_tmp; io.att_positions = att_positions_for(pos + 1); io.do_head = out_slot != nullptr;
+          io.kv = view_of(dkv); io.d_tok = tokp; io.do_head = out_slot != nullptr;
           FinalArgs fa{};
           fa.tok_out = out_slot;
           if (out_slot) io.final_args = &fa;
-          return llama_step(dm, io);
+          return step_at(dm, pos, io, llama_step);
         };
         // committed tokens the draft has not seen: after a fully accepted iteration its own k-th proposal (still in slot k_prev) comes first
-        if (dkv->seq_len == P - 1 && k_prev > 0) { GEN_TRY(dstep(vt + k_prev, P - 1, nullptr)); dkv->seq_len = P; }
-        if (dkv->seq_len != P) { bz_set_error("generate_speculative: draft cache at %d, committed position %d", dkv->seq_len, P); rc = BZ_E_INVALID; goto done; }
-        for (int i = 0; i < k; i++) GEN_TRY(dstep(vt + i, P + i, vt + i + 1));
+        if (dkv->seq_len == P - 1 && k_prev > 0) { BZ_TRY(dstep(vt + k_prev, P - 1, nullptr)); dkv->seq_len = P; }
+        if (dkv->seq_len != P) BZ_FAIL(BZ_E_INVALID, "generate_speculative: draft cache at %d, committed position %d", dkv->seq_len, P);
+        for (int i = 0; i < k; i++) BZ_TRY(dstep(vt + i, P + i, vt + i + 1));
       }
-      GEN_HIP(hipEventRecord(ev[1], st));
+      BZ_HIP(hipEventRecord(ev[1], st));
       int pth = 0;
-      GEN_TRY(llama_verify_rows(tm, vt, k + 1, kv, P, tm->sp_logits, vt, &pth));
-      GEN_HIP(hipEventRecord(ev[2], st));
+      BZ_TRY(llama_verify_rows(tm, vt, k + 1, kv, P, tm->sp_logits, vt, &pth));
+      BZ_HIP(hipEventRecord(ev[2], st));
       long long rec[17];
-      GEN_TRY(spec_read_record(dev, tm->sp_record, k + 2, rec));        // the iteration's one host synchronisation
+      BZ_TRY(spec_read_record(dev, tm->sp_record, k + 2, rec));        // the iteration's one host synchronisation
       const int a = (int)rec[0];
-      if (a < 0 || a > k) { bz_set_error("generate_speculative: accept record out of range (%d of %d)", a, k); rc = BZ_E_INVALID; goto done; }
+      if (a < 0 || a > k) BZ_FAIL(BZ_E_INVALID, "generate_speculative: accept record out of range (%d of %d)", a, k);
       kv->seq_len = P + a + 1;
       if (k > 0) dkv->seq_len = std::min(P + k, P + a + 1);
       k_prev = k;
@@ -3757,40 +3770,7 @@ extern "C" int bz_generate_speculative(bz_speculative* sp, const int64_t* prompt
       }
     }
   }
-  GEN_TRY(bz_device_synchronize(dev));
-done:
-  {
-    auto T2 = std::chrono::steady_clock::now();
-    if (stats) {
-      stats->prefill_ms = std::chrono::duration<double, std::milli>(T1 - T0).count();
-      stats->decode_ms = std::chrono::duration<double, std::milli>(T2 - T1).count();
-      stats->n_generated = n_out; stats->finish_reason = finish;
-      if (!tok_t.empty()) {
-        auto ms = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(t - T0).count(); };
-        stats->ttft_ms = ms(tok_t.front()); stats->total_ms = ms(tok_t.back());
-        std::vector<double> itl;
-        for (size_t i = 1; i < tok_t.size(); i++) itl.push_back(std::chrono::duration<double, std::milli>(tok_t[i] - tok_t[i - 1]).count());
-        if (!itl.empty()) {
-          std::sort(itl.begin(), itl.end());
-          auto pct = [&](double p) { size_t q = (size_t)std::ceil(p / 100.0 * (double)itl.size()); q = q ? q - 1 : 0; return itl[std::min(q, itl.size() - 1)]; };
-          stats->itl_p50_ms = pct(50.0); stats->itl_p99_ms = pct(99.0); stats->itl_max_ms = itl.back();
-          const double dec = stats->total_ms - stats->ttft_ms;
-          stats->decode_tok_per_s = dec > 0.0 ? (double)itl.size() / (dec / 1e3) : 0.0;
-        }
-      }
-    }
-    if (sstats) {
-      sstats->iterations = it; sstats->drafted_tokens = drafted; sstats->accepted_tokens = accepted; sstats->rejected_tokens = drafted - accepted;
-      sstats->verify_path = path_all; sstats->final_depth = kcur; sstats->draft_ms = draft_ms; sstats->verify_ms = verify_ms;
-    }
-  }
-  for (int i = 0; i < 3; i++) if (ev[i]) hipEventDestroy(ev[i]);
-  bz_tensor_free(t_prompt); bz_tensor_free(t_logits); bz_tensor_free(t_dlogits); bz_tensor_free(t_vt);
-  bz_kv_free(kv); bz_kv_free(dkv);
-  return rc;
-#undef GEN_TRY
-#undef GEN_HIP
-  BZ_API_END
+  return bz_device_synchronize(dev);
 }
 
 // ---------------------------------------------------------------------------------------------------------

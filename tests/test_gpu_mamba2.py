@@ -81,6 +81,32 @@ def test_graph_replay_equals_eager(pair):
     assert ex.generate(p, 16, use_graph=True).tolist() == ex.generate(p, 16).tolist()
 
 
+@pytest.mark.parametrize("pair", ["tiny-mamba2-g2"], indirect=True)
+def test_profile_step_ssm_reports_the_launches_of_one_step(pair):
+    """bz_profile_step_ssm, one step (iters=1) of tiny-mamba2-g2 (2 layers, f32, untied lm_head) after 8 tokens: the kernel names and their launch counts.
+    Per layer mamba_step launches in_proj (norm prologue), the fused conv + SSM step and out_proj (gated-norm prologue); the embedding, the lm_head with its
+    argmax partials and argmax_final launch once each -- the tail every architecture's step shares.  The values are those the library of the commit before
+    the shared tail reported on an MI355X for this fixture:
+
+    | name                      | launches |
+    |---------------------------|----------|
+    | embed                     | 1        |
+    | gemv_rows<norm>           | 2        |  in_proj, one per layer
+    | mamba2_ssm_step           | 2        |  conv1d step + SiLU + recurrence + gate, one per layer
+    | gemv_rows<gated>          | 2        |  out_proj, one per layer
+    | gemv_rows<lm_head+argmax> | 1        |
+    | argmax_final              | 1        |
+    """
+    model, lm, _ = pair
+    want = {"embed": 1, "gemv_rows<norm>": 2, "mamba2_ssm_step": 2, "gemv_rows<gated>": 2, "gemv_rows<lm_head+argmax>": 1, "argmax_final": 1}
+    assert model["config"]["n_layers"] == 2
+    st = runtime.LayeredSsmState(lm)
+    lm.forward_with_ssm_state(synth.prompt_tokens(8, model["config"]["vocab"]), st)
+    got = {r["name"]: r["launches"] for r in lm.profile_step_ssm(st, 5, iters=1)}
+    print(got)
+    assert got == want
+
+
 def test_error_behaviour(pair, device):
     model, lm, _ = pair
     cfg = model["config"]

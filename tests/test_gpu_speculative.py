@@ -75,6 +75,12 @@ def test_greedy_speculative_equals_plain_greedy(device, target_key, kind):
             assert ss["accepted_tokens"] + ss["rejected_tokens"] == ss["drafted_tokens"]
             assert st["n_generated"] == N_GEN == 1 + ss["accepted_tokens"] + ss["iterations"]
             assert 1 <= ss["final_depth"] <= 15 and (adaptive or ss["final_depth"] == k)
+            # the timings the plain loop reports (test_gpu_llama.py: test_generate_reports_the_reference_bench_timings), from the same stats function; the tokens one
+            # iteration accepts share an arrival time, so an inter-token latency may be 0 here
+            assert 0.0 < st["ttft_ms"] <= st["total_ms"]
+            assert st["prefill_ms"] <= st["ttft_ms"] + 1e-6
+            assert 0.0 <= st["itl_p50_ms"] <= st["itl_p99_ms"] <= st["itl_max_ms"]
+            assert abs(st["decode_tok_per_s"] - (st["n_generated"] - 1) / ((st["total_ms"] - st["ttft_ms"]) / 1e3)) <= 1e-6 * st["decode_tok_per_s"]
             if kind == "self":                  # every proposal accepted: the two-token catch-up every iteration
                 assert ss["rejected_tokens"] == 0
                 assert ss["iterations"] == _full_accept_iterations(N_GEN, k, adaptive), (k, adaptive, ss)
