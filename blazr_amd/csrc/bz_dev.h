@@ -309,6 +309,16 @@ __device__ __forceinline__ void lds_wait_count(volatile unsigned* cnt, unsigned 
   asm volatile("" ::: "memory");   // the LDS reads that follow stay behind the wait
 }
 
+// The same wait on a counter that is known to live in LDS.  The volatile read through a generic pointer above is a FLAT load, which the compiler
+// follows with s_waitcnt vmcnt(0) lgkmcnt(0): the wave then also waits for every global load it has in flight.  A read in the LDS address space is
+// a ds_read and waits for lgkmcnt alone, so weights requested before the wait keep flying across it.
+__device__ __forceinline__ void lds_wait_count_ds(volatile unsigned* cnt, unsigned n) {
+  typedef volatile __attribute__((address_space(3))) unsigned lds_u32;
+  lds_u32* c = (lds_u32*)cnt;
+  while (*c < n) __builtin_amdgcn_s_sleep(1);
+  asm volatile("" ::: "memory");   // the LDS reads that follow stay behind the wait
+}
+
 __device__ __forceinline__ size_t kv_row_off(const KvView& kv, int layer, int kvh, int p) {
   if (kv.paged) {
     const int blk = kv.block_table[p / kv.bs];

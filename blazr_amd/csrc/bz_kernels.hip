@@ -336,10 +336,55 @@ __device__ __forceinline__ void xfinish(const Pro& p, int KR, const XRegs<MODE, 
 //    before the norm instead (one chunk per wave) finished the planes at 4 us but left HBM idle from 1.5 to 4 us -- same total.
 //    Now the waves have ROLES: the first half ("streamers") request their whole gate / up range at entry and sit in the issue queue,
 //    which is exactly what keeps HBM busy from 0.2 us on; the second half holds the row (an octet per thread), does the norm and builds
-//    the planes undisturbed, and starts its own stream afterwards.  The two halves meet through two LDS counters (sum of squares
-//    complete; planes published) instead of workgroup barriers, which a streamer could only reach after its issue stall.
+//    the planes undisturbed, and starts its own stream afterwards.
 //  * the row never goes through LDS as f32: a thread normalises its eight elements in registers and builds the six plane words.
-//  * the tail (sum of the waves' partials, SiLU * up, its 64-value quantisation) runs in ONE wave between two barriers instead of four.
+//  * NO workgroup barrier after the rendezvous at entry: the waves meet through five LDS counters (cnt[]: sum of squares complete; planes
+//    published; row waves' gate / up requests issued; partials published; SiLU * up planes published), read with lds_wait_count_ds -- a ds_read,
+//    so a wave's weight loads keep flying across every wait and the compiler's own s_waitcnt vmcnt(N) let each group / tile be used as it lands.
+//  * request order = arrival order: a wave's scales / zero points go ahead of its weights, and NO down tile is requested before every gate / up
+//    request of the block has left the issue stall (cnt[2]); each wave asks for its 8 KiB of the down slab after its second group's dots, behind
+//    its published partials; wave 0 first runs the tail (sum of the waves' partials, SiLU * up, the 64 values' planes) and asks for its tiles last.
+//  * the down phase is tile by tile: wait for the tile's two chunks, dots, one 64-bit atomic per lane, next tile -- the atomics of the early tiles
+//    drain under the rest of the slab's stream instead of in one chip-wide burst after it.
+// The tail of the fused MLP, run by ONE wave once all NW partials are published (cnt_part): sum of the waves' k-range partials (exact, fixed order),
+// ONE rounding to f32 (the oracle's definition), + bias, R, SiLU * up, and the 64 values' planes -- one value per lane, an octet = 8 lanes.
+// Raises cnt_act when apl / apar are in LDS.
+template <int NW, int ACT>
+__device__ __forceinline__ void mlp_q4g_tail(const double* part, const float* __restrict__ bgu, int sl, int I, int lane, uint4* apl, int4* apar,
+                                             volatile unsigned* cnt_part, volatile unsigned* cnt_act) {
+  lds_wait_count_ds(cnt_part, NW);
+  double tg = 0.0, tu = 0.0;
+#pragma unroll
+  for (int w2 = 0; w2 < NW; w2++) { tg += part[w2 * 128 + lane]; tu += part[w2 * 128 + 64 + lane]; }
+  float fg = (float)tg, fu = (float)tu;
+  if (bgu) { fg += bgu[sl * 64 + lane]; fu += bgu[I + sl * 64 + lane]; }
+  const float a = round_t<ACT>(round_t<ACT>(silu_f(round_t<ACT>(fg))) * round_t<ACT>(fu));
+  const float am = wave_max(fabsf(a));
+  const unsigned eb = (__float_as_uint(am) >> 23) & 255u;
+  const bool live = eb >= 32u && eb < 255u;
+  const float inv = live ? __uint_as_float((283u - eb) << 23) : 0.f;
+  const float cs = live ? __uint_as_float((eb - 29u) << 23) : 0.f;
+  const unsigned code = ((unsigned)(int)rintf(a * inv) + 0x88888888u) ^ 0x88888888u;
+  const int lowfl = __builtin_amdgcn_ballot_w64((code & 0xFFu) != 0u) != 0ull;                  // some value of the 64 has bits in the low planes
+  const int o = lane & 7, sh = 4 * (2 * (o & 3) + (o >> 2));                // k offset o -> nibble 2 (o & 3) + (o >> 2)
+  int sp[XQ_NP];
+#pragma unroll
+  for (int p = 0; p < XQ_NP; p++) {
+    const int nib = p < XQ_NM ? p + 2 : p - XQ_NM;                                // plane index -> nibble of the code (xq_split8's order)
+    const int wv = grp_reduce<8, OpOr>((int)(((code >> (4 * nib)) & 15u) << sh));   // the octet's word of plane p, in all of its lanes
+    if (o == 0) ((unsigned*)apl)[((lane >> 5) * XQ_NP + p) * 4 + ((lane >> 3) & 3)] = (unsigned)wv;
+    int t = __builtin_amdgcn_sdot8(wv, 0x11111111, 0, false);                    // the octet's sum (the same in its 8 lanes)
+    t += dpp_get<DPP_ROR8>(t);                                                   // + the other octet of the 16-lane row
+    const bz_u2_t r1 = __builtin_amdgcn_permlane16_swap((unsigned)t, (unsigned)t, false, false);
+    t = (int)r1.x + (int)r1.y;
+    const bz_u2_t r2 = __builtin_amdgcn_permlane32_swap((unsigned)t, (unsigned)t, false, false);
+    sp[p] = (int)r2.x + (int)r2.y;
+  }
+  if (lane == 0) { apar[0] = make_int4(__float_as_int(cs), sp[0], sp[1], sp[2]); apar[1] = make_int4(sp[3], sp[4], sp[5], xq_pack_low(sp[6], sp[7], lowfl)); }
+  __builtin_amdgcn_s_waitcnt(0xc07f);                                     // lgkmcnt(0): the planes are stored
+  if (lane == 0) atomicAdd((unsigned*)cnt_act, 1u);
+}
+
 template <int FIX, int GPW, int TPW, int NW, int ACT>   // NW waves per block; GPW k-groups per wave (gate/up), TPW output tiles per wave (down)
 __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ Wgu, const __half* __restrict__ Sgu, const unsigned char* __restrict__ Zgu,
                                                  const float* __restrict__ bgu, const uint4* __restrict__ Wd, const __half* __restrict__ Sd,
@@ -355,7 +400,9 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
   uint4* apl = (uint4*)(part + NW * 128);     // [2 chunks][6 planes]
   int4* apar = (int4*)(apl + 2 * XQ_NP);      // [2]
   double* dred = (double*)(apar + 2);         // [NP]
-  volatile unsigned* cnt = (volatile unsigned*)(dred + NW);   // [0]: waves whose sum of squares is stored, [1]: waves whose planes are stored
+  // [0]: waves whose sum of squares is stored, [1]: waves whose planes are stored, [2]: row waves whose gate / up requests are all issued,
+  // [3]: waves whose partials are stored, [4]: SiLU * up planes stored
+  volatile unsigned* cnt = (volatile unsigned*)(dred + NW);
 
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const bool prolog = wave >= NP;             // wave-uniform role
@@ -371,7 +418,14 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
   const uint4* wg = Wgu + ((size_t)sl * (H >> 5) + gbeg * 4) * 64 + lane;
   const uint4* wu = Wgu + ((size_t)(NTI + sl) * (H >> 5) + gbeg * 4) * 64 + lane;
   uint4 Ag[8], Au[8];                  // chunk c of this wave's 256-k range: group c >> 2
-  if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
+  float sg[2], su[2]; int zg[2], zu[2];
+  if (tid == 0) { cnt[0] = 0; cnt[1] = 0; cnt[2] = 0; cnt[3] = 0; cnt[4] = 0; }
+  // the two groups' scales / zero points of gate and up (L2-resident)
+#define MLP_GU_PARAMS()                                                                                                              \
+  _Pragma("unroll") for (int b = 0; b < 2; b++) {                                                                                    \
+    const size_t ig = ((size_t)sl * G + gbeg + b) * 64 + lane, iu = ((size_t)(NTI + sl) * G + gbeg + b) * 64 + lane;                 \
+    sg[b] = __half2float(Sgu[ig]); zg[b] = Zgu[ig]; su[b] = __half2float(Sgu[iu]); zu[b] = Zgu[iu];                                  \
+  }
   if (prolog) {
     // (1p) prologue loads: an octet per thread -- h, deferred residual, norm weight; then the head of this wave's stream (2 KiB: no stall)
     const bool hasprev = pro.src.p != nullptr;
@@ -398,7 +452,7 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
     for (int e = 0; e < 8; e += 2) ssd += (double)(v[e] * v[e]) + (double)(v[e + 1] * v[e + 1]);
     ssd = wave_sum_d(ssd);
     if (lane == 0) { dred[wave - NP] = ssd; __builtin_amdgcn_s_waitcnt(0xc07f); atomicAdd((unsigned*)&cnt[0], 1u); }
-    lds_wait_count(&cnt[0], NP);
+    lds_wait_count_ds(&cnt[0], NP);
     ssd = ((dred[0] + dred[1]) + (dred[2] + dred[3]));
     if (NP == 8) ssd += ((dred[4] + dred[5]) + (dred[6] + dred[7]));
     const float ss = (float)ssd;                  // the rounded exact sum of squares (oracle: orc_rms_norm)
@@ -425,82 +479,54 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);                                   // lgkmcnt(0): this wave's LDS stores are done
     if (lane == 0) atomicAdd((unsigned*)&cnt[1], 1u);
-    // (4p) the rest of this wave's stream
+    // (4p) the rest of this wave's stream, behind the groups' scales / zero points (vmcnt retires in issue order)
+    MLP_GU_PARAMS();
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int c = 1; c < 8; c++) { Ag[c] = ldnt(wg + c * 64); Au[c] = ldnt(wu + c * 64); }
+    __builtin_amdgcn_sched_barrier(0);   // the count rises only once the requests above have left the issue stall
+    if (lane == 0) atomicAdd((unsigned*)&cnt[2], 1u);
   } else {
     // (1s) streamers: the whole gate / up range of the wave goes out now (16 KiB; the wave sits in the issue queue, HBM stays busy)
     __syncthreads();                     // the counters are zero
+    MLP_GU_PARAMS();                     // ahead of the stream: vmcnt retires in issue order, the first group must not wait for the second
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int c = 0; c < 8; c++) { Ag[c] = ldnt(wg + c * 64); Au[c] = ldnt(wu + c * 64); }
     zero_duty<NP * 64>(zero_buf, zero_n);   // (threads 0 .. NP*64-1 are exactly the streamers)
   }
-  float sg[2], su[2]; int zg[2], zu[2];
-#pragma unroll
-  for (int b = 0; b < 2; b++) {
-    const size_t ig = ((size_t)sl * G + gbeg + b) * 64 + lane, iu = ((size_t)(NTI + sl) * G + gbeg + b) * 64 + lane;
-    sg[b] = __half2float(Sgu[ig]); zg[b] = Zgu[ig]; su[b] = __half2float(Sgu[iu]); zu[b] = Zgu[iu];
-  }
-  lds_wait_count(&cnt[1], NP);           // the planes of the whole row are in LDS
-  // (5) gate / up dots chunk by chunk (the compiler counts the waits); the down slab goes out behind the first group
+  lds_wait_count_ds(&cnt[1], NP);           // the planes of the whole row are in LDS
+  // (5) gate / up dots chunk by chunk (the compiler counts the waits); the partials are published before anything that can stall
   double yg = 0.0, yu = 0.0;
-  uint4 D[TPW][2];
-  float sd[TPW]; int zd[TPW];
-#pragma unroll
-  for (int b = 0; b < 2; b++) {
-    if (b == 0) q4g_consume2_at<0>(Ag, Au, gbeg, xpl, gpar, sg[0], zg[0], su[0], zu[0], yg, yu);
-    else q4g_consume2_at<4>(Ag, Au, gbeg + 1, xpl, gpar, sg[1], zg[1], su[1], zu[1], yg, yu);
-    if (b == 0) {
-#pragma unroll
-      for (int q = 0; q < TPW; q++) {
-        const uint4* wp = Wd + ((size_t)(tbeg + q) * (I >> 5) + 2 * sl) * 64 + lane;
-        D[q][0] = ldnt(wp); D[q][1] = ldnt(wp + 64);
-      }
-    }
-  }
+  q4g_consume2_at<0>(Ag, Au, gbeg, xpl, gpar, sg[0], zg[0], su[0], zu[0], yg, yu);
+  q4g_consume2_at<4>(Ag, Au, gbeg + 1, xpl, gpar, sg[1], zg[1], su[1], zu[1], yg, yu);
   part[wave * 128 + lane] = yg;
   part[wave * 128 + 64 + lane] = yu;
-  // the slab's scales / zero points (L2-resident): requested here, under the partial-sum barrier and the tail -- eight registers less across the second group's dots
+  __builtin_amdgcn_s_waitcnt(0xc07f);    // lgkmcnt(0): the partials are stored
+  if (lane == 0) atomicAdd((unsigned*)&cnt[3], 1u);
+  __builtin_amdgcn_sched_barrier(0);
+  // (6) the down requests enter the CU's queue behind every gate / up request of the block (cnt[2]); a tile's scale and zero point go AHEAD of the
+  //     tiles (vmcnt retires in issue order: behind them, the first tile would wait for the last).  Wave 0 runs the tail and asks for its tiles
+  //     after it, so that its issue stall delays nobody: its tiles are the last of the block's queue.
+  if (wave == 0) mlp_q4g_tail<NW, ACT>(part, bgu, sl, I, lane, apl, apar, &cnt[3], &cnt[4]);
+  lds_wait_count_ds(&cnt[2], NP);
+  __builtin_amdgcn_sched_barrier(0);
+  uint4 D[TPW][2];
+  float sd[TPW]; int zd[TPW];
 #pragma unroll
   for (int q = 0; q < TPW; q++) {
     const size_t si = ((size_t)(tbeg + q) * GD + gd) * 64 + lane;
     sd[q] = __half2float(Sd[si]); zd[q] = Zd[si];
   }
-  __syncthreads();
-  // (6) wave 0: sum of the waves' k-range partials (exact, fixed order), ONE rounding to f32 (the oracle's definition), + bias, R, SiLU * up,
-  //     and the 64 values' planes -- one value per lane, an octet = 8 lanes
-  if (wave == 0) {
-    double tg = 0.0, tu = 0.0;
+  __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int w2 = 0; w2 < NW; w2++) { tg += part[w2 * 128 + lane]; tu += part[w2 * 128 + 64 + lane]; }
-    float fg = (float)tg, fu = (float)tu;
-    if (bgu) { fg += bgu[sl * 64 + lane]; fu += bgu[I + sl * 64 + lane]; }
-    const float a = round_t<ACT>(round_t<ACT>(silu_f(round_t<ACT>(fg))) * round_t<ACT>(fu));
-    const float am = wave_max(fabsf(a));
-    const unsigned eb = (__float_as_uint(am) >> 23) & 255u;
-    const bool live = eb >= 32u && eb < 255u;
-    const float inv = live ? __uint_as_float((283u - eb) << 23) : 0.f;
-    const float cs = live ? __uint_as_float((eb - 29u) << 23) : 0.f;
-    const unsigned code = ((unsigned)(int)rintf(a * inv) + 0x88888888u) ^ 0x88888888u;
-    const int lowfl = __builtin_amdgcn_ballot_w64((code & 0xFFu) != 0u) != 0ull;                  // some value of the 64 has bits in the low planes
-    const int o = lane & 7, sh = 4 * (2 * (o & 3) + (o >> 2));                // k offset o -> nibble 2 (o & 3) + (o >> 2)
-    int sp[XQ_NP];
-#pragma unroll
-    for (int p = 0; p < XQ_NP; p++) {
-      const int nib = p < XQ_NM ? p + 2 : p - XQ_NM;                                // plane index -> nibble of the code (xq_split8's order)
-      const int wv = grp_reduce<8, OpOr>((int)(((code >> (4 * nib)) & 15u) << sh));   // the octet's word of plane p, in all of its lanes
-      if (o == 0) ((unsigned*)apl)[((lane >> 5) * XQ_NP + p) * 4 + ((lane >> 3) & 3)] = (unsigned)wv;
-      int t = __builtin_amdgcn_sdot8(wv, 0x11111111, 0, false);                    // the octet's sum (the same in its 8 lanes)
-      t += dpp_get<DPP_ROR8>(t);                                                   // + the other octet of the 16-lane row
-      const bz_u2_t r1 = __builtin_amdgcn_permlane16_swap((unsigned)t, (unsigned)t, false, false);
-      t = (int)r1.x + (int)r1.y;
-      const bz_u2_t r2 = __builtin_amdgcn_permlane32_swap((unsigned)t, (unsigned)t, false, false);
-      sp[p] = (int)r2.x + (int)r2.y;
-    }
-    if (lane == 0) { apar[0] = make_int4(__float_as_int(cs), sp[0], sp[1], sp[2]); apar[1] = make_int4(sp[3], sp[4], sp[5], xq_pack_low(sp[6], sp[7], lowfl)); }
+  for (int q = 0; q < TPW; q++) {        // 8 KiB, in the order the tiles are consumed
+    const uint4* wp = Wd + ((size_t)(tbeg + q) * (I >> 5) + 2 * sl) * 64 + lane;
+    D[q][0] = ldnt(wp); D[q][1] = ldnt(wp + 64);
   }
-  __syncthreads();
-  // (7) this wave's down slab
+  __builtin_amdgcn_sched_barrier(0);
+  lds_wait_count_ds(&cnt[4], 1);         // SiLU * up and its planes are in LDS
+  // (7) this wave's down slab, tile by tile as it lands: each tile's atomic leaves while the later tiles are still in flight
 #pragma unroll
   for (int q = 0; q < TPW; q++) {
     double y = 0.0;
@@ -508,7 +534,9 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
     const int n = (tbeg + q) * 64 + lane;
     if (bd != nullptr && sl == 0) y += (double)bd[n];
     atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, ACT));
+    __builtin_amdgcn_sched_barrier(0);   // tile q's atomic is issued before tile q + 1 is waited for
   }
+#undef MLP_GU_PARAMS
 }
 
 static size_t mlp_smem(int H) { return (size_t)(H >> 5) * XQ_NP * 16 + (size_t)(H >> 7) * 32 + 16 * 128 * 8 + 2 * XQ_NP * 16 + 32 + 16 * 8 + 64; }   // planes, gpar, part, apl, apar, dred, counters
