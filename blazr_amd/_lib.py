@@ -143,8 +143,16 @@ class EngineConfig(C.Structure):
 
 
 class Request(C.Structure):
-    _fields_ = [("max_tokens", C.c_int32), ("n_stop", C.c_int32), ("stop_ids", C.c_int64 * 8), ("grammar_state", C.c_uint32), ("reserved", C.c_int32 * 3),
+    _fields_ = [("max_tokens", C.c_int32), ("n_stop", C.c_int32), ("stop_ids", C.c_int64 * 8), ("grammar_state", C.c_uint32), ("lora_slot", C.c_int32), ("reserved", C.c_int32 * 2),
                 ("sampling", RowSampling)]
+
+
+LORA_TARGETS = {"q": 1, "k": 2, "v": 4, "o": 8, "gate": 16, "up": 32, "down": 64}
+LORA_ALL = 127
+
+
+class LoraTableConfig(C.Structure):
+    _fields_ = [("n_slots", C.c_int32), ("max_rank", C.c_int32), ("targets", C.c_uint32), ("reserved", C.c_int32 * 5)]
 
 
 class EngineEvent(C.Structure):
@@ -321,6 +329,17 @@ SYMBOLS = {
     "bz_forward_kv_verify": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.POINTER(C.c_int32), P, C.POINTER(C.c_int32)]),
     "bz_speculative_create": (C.c_int, [P, P, C.POINTER(SpecConfig), C.POINTER(P)]),
     "bz_speculative_free": (C.c_int, [P]),
+    "bz_lora_table_create": (C.c_int, [P, C.POINTER(LoraTableConfig)]),
+    "bz_lora_create": (C.c_int, [P, C.c_int, C.c_float, C.c_int, C.POINTER(P)]),
+    "bz_lora_add": (C.c_int, [P, C.c_char_p, C.c_int, P, C.POINTER(C.c_int64), P, C.POINTER(C.c_int64)]),
+    "bz_lora_free": (C.c_int, [P]),
+    "bz_lora_load": (C.c_int, [P, C.c_char_p, C.POINTER(P)]),
+    "bz_lora_describe": (C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bz_lora_attach": (C.c_int, [P, C.c_int, P]),
+    "bz_lora_detach": (C.c_int, [P, C.c_int]),
+    "bz_model_set_lora": (C.c_int, [P, C.c_int]),
+    "bz_decode_batch_graph_set_adapters": (C.c_int, [P, P]),
+    "bz_lora_apply": (C.c_int, [P, C.c_int, C.c_uint32, P, P, P, C.c_int, C.c_int, P]),
     "bz_generate_speculative": (C.c_int, [P, P, C.c_int, C.POINTER(GenConfig), P, C.POINTER(GenStats), C.POINTER(SpecStats)]),
 }
 

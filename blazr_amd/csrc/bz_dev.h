@@ -368,3 +368,167 @@ __device__ __forceinline__ size_t kv_row_off_t(const KvView& kv, int layer, int 
   return (size_t)layer * kv.layer_stride + ((size_t)kvh * kv.cap + p) * kv.hd;
 }
 
+// deterministic block sum over 256 threads; red: LDS float[4]
+__device__ __forceinline__ float block_sum256(float v, float* red) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return t;
+}
+// ---------------------------------------------------------------------------------------------------------
+// prologue: build the activation slice x[k0, k0+KR) as f32 in LDS
+// ---------------------------------------------------------------------------------------------------------
+// Simple form (loads inside): used by the ROWS kernels, whose slice is all of K.
+// pos(i): LDS position of slice element i (identity, or the ROWS swizzle).
+template <bool SWZ>
+__device__ __forceinline__ int xs_pos(int i) {
+  if (!SWZ) return i;
+  return (i & ~511) + ((i & 4) << 6) + ((i & 511) >> 3 << 2) + (i & 3);
+}
+
+// All global loads of a batch are issued first, unconditionally (clamped index), and converted afterwards: a load under
+// a condition, or a conversion right after its load, makes hipcc wait vmcnt(0) per element and serialises the batch.
+template <bool FIX> struct SrcRaw { typedef float T; };
+template <> struct SrcRaw<true> { typedef long long T; };
+template <bool FIX>
+__device__ __forceinline__ typename SrcRaw<FIX>::T src_raw(const void* p, int i) {
+  if constexpr (FIX) return ((const long long*)p)[i]; else return ((const float*)p)[i];
+}
+template <bool FIX>
+__device__ __forceinline__ float src_cvt(typename SrcRaw<FIX>::T r, int act) {
+  if constexpr (FIX) return round_act(fix2f(r, act), act); else return r;
+}
+
+// NORM pass 1: v = R(h + prev) for the whole row -> sum of squares; slice elements [k0, k0+KR) are parked in xs
+template <bool SWZ, bool FIX, bool PREV>
+__device__ __forceinline__ double norm_pass1(const Pro& p, int k0, int KR, float* xs, bool writer) {
+  const int tid = threadIdx.x;
+  double ss = 0.0;
+  for (int base = 0; base < p.H; base += 4096) {
+    float4 hv[4];
+    typename SrcRaw<FIX>::T pr[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int i = min(base + j * 1024 + tid * 4, p.H - 4);
+      hv[j] = *(const float4*)(p.h_in + i);
+      if (PREV) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) pr[j][e] = src_raw<FIX>(p.src.p, i + e);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int i = base + j * 1024 + tid * 4;
+      float v[4] = {hv[j].x, hv[j].y, hv[j].z, hv[j].w};
+      if (PREV) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) v[e] = round_act(v[e] + src_cvt<FIX>(pr[j][e], p.act), p.act);
+      }
+      if (i < p.H) {
+        ss += ((double)(v[0] * v[0]) + (double)(v[1] * v[1])) + ((double)(v[2] * v[2]) + (double)(v[3] * v[3]));
+        if (writer && p.h_out) *(float4*)(p.h_out + i) = make_float4(v[0], v[1], v[2], v[3]);
+        if (i >= k0 && i < k0 + KR) {       // k0, KR and i are multiples of 4
+#pragma unroll
+          for (int e = 0; e < 4; e++) xs[xs_pos<SWZ>(i - k0 + e)] = v[e];
+        }
+      }
+    }
+  }
+  return ss;
+}
+
+template <bool SWZ, bool FIX, bool SILU>
+__device__ __forceinline__ void plain_fill(const Pro& p, int k0, int KR, float* xs) {
+  const int tid = threadIdx.x;
+  for (int base = 0; base < KR; base += 2048) {
+    typename SrcRaw<FIX>::T a[8], b[8];
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      const int kk = k0 + min(base + e * 256 + tid, KR - 1);
+      a[e] = src_raw<FIX>(p.src.p, kk);
+      if (SILU) b[e] = src_raw<FIX>(p.src.p, p.H + kk);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      const int i = base + e * 256 + tid;
+      float v = src_cvt<FIX>(a[e], p.act);
+      if (SILU) v = round_act(round_act(silu_f(v), p.act) * src_cvt<FIX>(b[e], p.act), p.act);
+      if (i < KR) xs[xs_pos<SWZ>(i)] = v;
+    }
+  }
+}
+
+// Simple form (loads inside): used by the ROWS kernels (no act-order permutation there).  Slice [k0, k0+KR), KR > 0.
+template <bool SWZ>
+__device__ void build_x_simple(const Pro& p, int k0, int KR, float* xs, float* red, bool writer) {
+  const int tid = threadIdx.x;
+  if (KR <= 0) { __syncthreads(); return; }
+  if (p.mode == PRO_NORM) {
+    double ssd;
+    if (p.src.p == nullptr) ssd = norm_pass1<SWZ, false, false>(p, k0, KR, xs, writer);
+    else if (p.src.fix) ssd = norm_pass1<SWZ, true, true>(p, k0, KR, xs, writer);
+    else ssd = norm_pass1<SWZ, false, true>(p, k0, KR, xs, writer);
+    const float ss = (float)block_sum_d<4>(ssd);   // the rounded exact sum (also orders the xs writes of pass 1 before the reads below)
+    const float rs = rms_scale(ss, (float)p.H, p.eps);
+    for (int base = 0; base < KR; base += 2048) {
+      float ww[8];
+#pragma unroll
+      for (int e = 0; e < 8; e++) ww[e] = p.norm_w[k0 + min(base + e * 256 + tid, KR - 1)];
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        const int i = base + e * 256 + tid;
+        if (i < KR) xs[xs_pos<SWZ>(i)] = round_act(ww[e] * round_act(xs[xs_pos<SWZ>(i)] * rs, p.act), p.act);
+      }
+    }
+  } else if (p.mode == PRO_GATED) {
+    // Mamba2 gated RMSNorm: v = R(y * R(silu(z))) ; x = R(w * R(v * rsqrt(mean_group(v^2) + eps)))   (src = y, h_in = z, H = d_inner)
+    // whole-vector form (k0 == 0, KR == H); the decode step uses GATED2, where the SSM kernel has done the gate and the sums
+    const int G = p.aux > 0 ? p.aux : 1, gsz = p.H / G;
+    for (int g = 0; g < G; g++) {
+      float ss = 0.f;
+      for (int i = tid; i < gsz; i += 256) {
+        const int kk = g * gsz + i;
+        const float v = round_act(vsrc_get(p.src, kk, p.act) * round_act(silu_f(p.h_in[kk]), p.act), p.act);
+        xs[xs_pos<SWZ>(kk)] = v;
+        ss += v * v;
+      }
+      ss = block_sum256(ss, red);
+      const float rs = rms_scale(ss, (float)gsz, p.eps);
+      for (int i = tid; i < gsz; i += 256) {
+        const int kk = g * gsz + i;
+        xs[xs_pos<SWZ>(kk)] = round_act(p.norm_w[kk] * round_act(xs[xs_pos<SWZ>(kk)] * rs, p.act), p.act);
+      }
+    }
+  } else if (p.mode == PRO_GATED2) {
+    // gated RMSNorm with the gate and the per-head sums of squares already applied / reduced by the SSM kernel
+    const int G = p.aux > 0 ? p.aux : 1, gsz = p.H / G, hpg = p.aux2 / G;
+    if (tid < G) {
+      double ss = 0.0;                                  // per-head exact sums arrive as hi + lo floats (k_ssm_step)
+      for (int h = 0; h < hpg; h++) ss += (double)p.h_in[2 * (tid * hpg + h)] + (double)p.h_in[2 * (tid * hpg + h) + 1];
+      red[4 + tid] = rms_scale((float)ss, (float)gsz, p.eps);
+    }
+    __syncthreads();
+    for (int base = 0; base < KR; base += 2048) {
+      float vv[8], ww[8];
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        const int kk = k0 + min(base + e * 256 + tid, KR - 1);
+        vv[e] = ((const float*)p.src.p)[kk];
+        ww[e] = p.norm_w[kk];
+      }
+#pragma unroll
+      for (int e = 0; e < 8; e++) {
+        const int i = base + e * 256 + tid;
+        if (i < KR) xs[xs_pos<SWZ>(i)] = round_act(ww[e] * round_act(vv[e] * red[4 + (k0 + i) / gsz], p.act), p.act);
+      }
+    }
+  } else if (p.mode == PRO_SILU) {
+    if (p.src.fix) plain_fill<SWZ, true, true>(p, k0, KR, xs); else plain_fill<SWZ, false, true>(p, k0, KR, xs);
+  } else {
+    if (p.src.fix) plain_fill<SWZ, true, false>(p, k0, KR, xs); else plain_fill<SWZ, false, false>(p, k0, KR, xs);
+  }
+  __syncthreads();
+}
+

@@ -41,7 +41,7 @@ __global__ void k_engine_advance(long long* tok, const long long* next, int* pos
   }
 }
 __global__ __launch_bounds__(512) void k_engine_finish(EngRow* rows, const long long* next, int* pos, int* table, int stride, const int* step, int logcap, int N,
-                                                       int* status, int* nlive, uint32_t* gstate) {
+                                                       int* status, int* nlive, uint32_t* gstate, int* row_lora) {
   const int i = threadIdx.x;
   const int st = *step - 1;                      // the pick has counted this replay already
   const int at = ((st % logcap) + logcap) % logcap;
@@ -62,6 +62,7 @@ __global__ __launch_bounds__(512) void k_engine_finish(EngRow* rows, const long 
         pos[i] = 0;
         table[(size_t)i * stride] = r.park_block;
         if (gstate) gstate[i] = BZ_GRAMMAR_ROW_FREE;
+        if (row_lora) row_lora[i] = -1;
         word = ENG_FINISHED | (reason << 2);
       } else { word = ENG_TOKEN; still = 1; }
     }
@@ -106,9 +107,9 @@ int bzk_engine_advance(hipStream_t s, long long* tok, const long long* next, int
   return BZ_OK;
 }
 int bzk_engine_finish(hipStream_t s, EngRow* rows, const long long* next, int* pos, int* table, int stride, const int* step, int logcap, int N, int* status,
-                      int* nlive, uint32_t* gstate) {
+                      int* nlive, uint32_t* gstate, int* row_lora) {
   if (N > 512) BZ_FAIL(BZ_E_INVALID, "engine finish: N = %d above the 512 rows one workgroup serves", N);
-  hipLaunchKernelGGL(k_engine_finish, dim3(1), dim3(512), 0, s, rows, next, pos, table, stride, step, logcap, N, status, nlive, gstate);
+  hipLaunchKernelGGL(k_engine_finish, dim3(1), dim3(512), 0, s, rows, next, pos, table, stride, step, logcap, N, status, nlive, gstate, row_lora);
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
@@ -120,7 +121,7 @@ namespace {
 struct EngReq { int64_t id = -1; std::vector<int64_t> prompt; bz_request rq{}; int row = -1; bool live = false; int produced = 0; long long first_replay = -1; int shared = 0; };
 // pinned staging for the stream-ordered writes: a slot is reused only after the stream has passed the copies that read it
 struct Stage { char* host = nullptr; hipEvent_t ev = nullptr; bool pending = false; };
-struct RowMisc { long long next; int pos, pad; EngRow er; uint32_t gram[2]; };
+struct RowMisc { long long next; int pos, lora; EngRow er; uint32_t gram[2]; };   // lora: the row's LoRA slot id (-1: none)
 }
 struct bz_engine {
   bz_model* m = nullptr; bz_device* dev = nullptr; bz_engine_config cfg{}; bz_model_config mc{};
@@ -140,6 +141,13 @@ struct bz_engine {
   static const int EVRING = 128;
 };
 
+// a request holds its LoRA slot from submit until it leaves e->reqs (finished, cancelled, engine freed): bz_lora_detach looks at the count
+static int eng_lora_slot(const EngReq& q) { return q.rq.lora_slot - 1; }
+static void eng_lora_release(bz_engine* e, const EngReq& q) {
+  BzLoraTable* T = bzi_model_lora(e->m);
+  if (T && eng_lora_slot(q) >= 0 && eng_lora_slot(q) < T->n_slots && T->users[eng_lora_slot(q)] > 0) T->users[eng_lora_slot(q)]--;
+}
+
 static int eng_stage(bz_engine* e, Stage** out) {
   Stage& s = e->stages[e->stage_next];
   e->stage_next = (e->stage_next + 1) % (int)e->stages.size();
@@ -153,6 +161,7 @@ extern "C" int bz_engine_free(bz_engine* e) {
   BZ_API_BEGIN
   if (!e) return BZ_OK;
   if (e->dev) { hipSetDevice(e->dev->id); hipStreamSynchronize(e->dev->stream); }
+  for (auto& kv : e->reqs) eng_lora_release(e, kv.second);
   if (e->g) bz_decode_batch_graph_free(e->g);
   if (e->sampler) bz_batch_sampler_free(e->sampler);
   if (e->kv) bz_paged_kv_free(e->kv);
@@ -265,11 +274,19 @@ extern "C" int bz_engine_submit(bz_engine* e, const int64_t* prompt, int n_promp
     if (rq->grammar_state >= (uint32_t)bzk_grammar_cursor_num_states(e->cursor))
       BZ_FAIL(BZ_E_INVALID, "engine submit: grammar_state = %u is not below the grammar's %d states", rq->grammar_state, bzk_grammar_cursor_num_states(e->cursor));
   }
+  BzLoraTable* T = bzi_model_lora(e->m);
+  if (rq->lora_slot != 0) {
+    if (!T) BZ_FAIL(BZ_E_INVALID, "engine submit: lora_slot = %d but the model has no LoRA table", rq->lora_slot);
+    if (rq->lora_slot < 0 || rq->lora_slot > T->n_slots || !T->slots[rq->lora_slot - 1])
+      BZ_FAIL(BZ_E_INVALID, "engine submit: lora_slot = %d names slot %d, which is empty or outside the table's %d slots", rq->lora_slot, rq->lora_slot - 1, T->n_slots);
+  }
   int64_t id = -1;
-  if (e->cfg.prefix_cache) BZ_TRY(bz_sched_submit_tokens(e->sched, prompt, n_prompt, rq->max_tokens, &id));
+  // cached KV rows depend on the adapter: a request under one neither looks up nor publishes prefix blocks (submitted without its tokens)
+  if (e->cfg.prefix_cache && rq->lora_slot == 0) BZ_TRY(bz_sched_submit_tokens(e->sched, prompt, n_prompt, rq->max_tokens, &id));
   else BZ_TRY(bz_sched_submit(e->sched, n_prompt, rq->max_tokens, &id));  // (names the figure when the request could never fit the pool)
   EngReq& r = e->reqs[id];
   r.id = id; r.prompt.assign(prompt, prompt + n_prompt); r.rq = *rq;
+  if (rq->lora_slot != 0) T->users[rq->lora_slot - 1]++;
   *id_out = id;
   return BZ_OK;
   BZ_API_END
@@ -283,7 +300,9 @@ static int eng_idle_row(bz_engine* e, int row) {
   RowMisc* mi = (RowMisc*)(s->host + e->off_misc);
   memset(mi, 0, sizeof(*mi));
   mi->er.park_block = e->cfg.num_blocks - e->cfg.n_rows + row;
+  mi->lora = -1;
   int* tb = (int*)s->host; tb[0] = mi->er.park_block;
+  if (bzi_model_lora(e->m)) BZ_HIP(hipMemcpyAsync(e->g->row_lora + row, &mi->lora, 4, hipMemcpyHostToDevice, st));
   BZ_HIP(hipMemcpyAsync(e->d_rows + row, &mi->er, sizeof(EngRow), hipMemcpyHostToDevice, st));
   BZ_HIP(hipMemcpyAsync(e->g->pos + row, &mi->pos, 4, hipMemcpyHostToDevice, st));
   BZ_HIP(hipMemcpyAsync(e->g->table + (size_t)row * e->max_blocks, tb, 4, hipMemcpyHostToDevice, st));
@@ -304,6 +323,7 @@ extern "C" int bz_engine_cancel(bz_engine* e, int64_t id) {
   }
   BZ_TRY(bz_sched_finish(e->sched, id));
   e->events.push_back(bz_engine_event{id, -1, r.produced, 2, e->g->replays});
+  eng_lora_release(e, r);
   e->reqs.erase(it);
   return BZ_OK;
   BZ_API_END
@@ -329,6 +349,7 @@ static int eng_harvest(bz_engine* e) {
       const int64_t id = q.id;
       BZ_TRY(bz_sched_finish(e->sched, id));
       e->row_req[row] = -1;
+      eng_lora_release(e, q);
       e->reqs.erase(id);
     }
   }
@@ -354,7 +375,7 @@ static int eng_prefill(bz_engine* e, EngReq& q, int a, int b, const int32_t* blo
   t_tok.ptr = e->d_ptok; t_tok.dtype = BZ_I64; t_tok.nbytes = (size_t)S * 8; t_tok.shape = {1, S};
   t_slot.ptr = e->d_pslot; t_slot.dtype = BZ_I32; t_slot.nbytes = (size_t)S * 4; t_slot.shape = {S};
   t_tab.ptr = e->d_ptable; t_tab.dtype = BZ_I32; t_tab.nbytes = (size_t)nb * 4; t_tab.shape = {nb};
-  BZ_TRY(bz_forward_paged(e->m, &t_tok, S, e->kv, &t_slot, &t_tab, nb, b, a, e->plogits, 0));
+  BZ_TRY(bzi_forward_paged_lora(e->m, eng_lora_slot(q), &t_tok, S, e->kv, &t_slot, &t_tab, nb, b, a, e->plogits, 0));   // the prompt runs under the request's adapter
   e->prompt_tokens += S;
   return BZ_OK;
 }
@@ -370,6 +391,8 @@ static int eng_go_live(bz_engine* e, EngReq& q, const int32_t* blocks, int nb) {
   RowMisc* mi = (RowMisc*)(s->host + e->off_misc);
   memset(mi, 0, sizeof(*mi));
   mi->next = q.prompt[n - 1]; mi->pos = n - 2;                     // k_engine_advance adds 1
+  mi->lora = eng_lora_slot(q);
+  if (bzi_model_lora(e->m)) BZ_HIP(hipMemcpyAsync(e->g->row_lora + row, &mi->lora, 4, hipMemcpyHostToDevice, st));
   mi->er.live = 1; mi->er.left = q.rq.max_tokens; mi->er.n_stop = q.rq.n_stop; mi->er.park_block = e->cfg.num_blocks - e->cfg.n_rows + row;
   for (int k = 0; k < q.rq.n_stop; k++) mi->er.stop[k] = q.rq.stop_ids[k];
   BZ_HIP(hipMemcpyAsync(e->g->table + (size_t)row * e->max_blocks, tb, (size_t)e->max_blocks * 4, hipMemcpyHostToDevice, st));

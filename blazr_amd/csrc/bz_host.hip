@@ -338,6 +338,7 @@ struct bz_model {
   float* sp_logits = nullptr; float* sp_pval = nullptr; int* sp_pidx = nullptr; int sp_nb = 0;
   long long* sp_argmax = nullptr; long long* sp_record = nullptr;
   size_t resident = 0, per_token = 0;
+  BzLoraTable* lora = nullptr;   // bz_lora_table_create: the adapter slots, the current-slot scalar and the f32 rows the adapted linears' consumers read (bz_lora.hip)
 };
 
 static int dev_alloc(bz_model* m, void** p, size_t bytes) {
@@ -415,6 +416,7 @@ extern "C" int bz_model_free(bz_model* m) {
   hipStreamSynchronize(m->dev->stream);
   for (auto& kv : m->raw) raw_free(kv.second);
   for (void* p : m->owned) hipFree(p);
+  bzl_table_free(m->lora);
   bz_dev_release(m->dev);
   delete m;
   return BZ_OK;
@@ -1542,10 +1544,26 @@ static int step_tail(bz_model* m, const StepIO& io, RingState& rs, VSrc prev, co
   return BZ_OK;
 }
 
+// LoRA in the decode step: after the base launch of a group whose linears are in the table's mask, the group's shrink (x from `px`: the prologue the base
+// launch ran, over state it has left in place) and expand (b from the base launch's VSrc); the consumer then reads the table's f32 row.  The expand takes no
+// ring slot: the accumulator it reads is zeroed by the launch that would have zeroed it anyway.
+static int lora_after(bz_model* m, int layer, int group, const Pro& px, VSrc* v) {
+  const BzLoraTable* T = m->lora;
+  if (!T || !T->group_on(group)) return BZ_OK;
+  hipStream_t st = step_stream(m);
+  const LoraGroup g = bzl_group(T, group);
+  BZ_TRY(bzk_lora_shrink_dec(st, T, layer, g, px));
+  BZ_TRY(bzk_lora_expand_dec(st, T, layer, g, m->cfg.act_dtype, *v, T->out[group]));
+  *v = VSrc{T->out[group], 0};
+  return BZ_OK;
+}
+
 static int llama_step(bz_model* m, const StepIO& io) {
   const bz_model_config& c = m->cfg;
   hipStream_t st = step_stream(m);
   const int H = c.hidden, I = c.inter, act = c.act_dtype;
+  // the launches depend on the table's mask alone (never on what is attached): a captured graph stays valid across attach / detach / set
+  const bool lora_o = m->lora && m->lora->group_on(LG_O), lora_mlp = m->lora && (m->lora->group_on(LG_GATEUP) || m->lora->group_on(LG_DOWN));
   const int lend = io.layer_end < 0 ? c.n_layers : io.layer_end;
   int cur = 0;
   RingState rs(m);
@@ -1564,6 +1582,9 @@ static int llama_step(bz_model* m, const StepIO& io) {
     VSrc qkv;
     BZ_TRY(run_fused(m, Ld.qkv, pn, rs, &qkv));
     cur ^= 1;
+    // the adapter's x is the norm of the residual row the base launch has just written (h', no deferred residual left to add)
+    Pro pxn = pn; pxn.src = VSrc{nullptr, 0}; pxn.h_in = m->hbuf[cur]; pxn.h_out = nullptr; pxn.perm = nullptr;
+    BZ_TRY(lora_after(m, l, LG_QKV, pxn, &qkv));
 
     AttnArgs aa{};
     aa.qkv = qkv; aa.cos_t = m->cos_t; aa.sin_t = m->sin_t; aa.interleaved = c.rope_interleaved; aa.pos = io.d_pos; aa.rope_cur = m->rope_cur;
@@ -1575,7 +1596,7 @@ static int llama_step(bz_model* m, const StepIO& io) {
     VSrc ov;
     static const bool no_fuse = getenv("BZ_NO_ATTN_FUSION") != nullptr;
     // (the f32-cache form has no split-KV partner: beyond the single-launch contexts it stays unfused)
-    const bool fuse_shape = !no_fuse && Ld.o.parts.size() == 1 && Ld.o.fix_out;
+    const bool fuse_shape = !no_fuse && !lora_o && Ld.o.parts.size() == 1 && Ld.o.fix_out;   // an o_proj adapter reads the attention output: two launches
     const bool fuse_cap = fuse_shape && bzk_attn_oproj_slices(aa, Ld.o.parts[0]) > 0;
     static const bool no_split = getenv("BZ_NO_ATTN_SPLIT") != nullptr;
     const bool split_wanted = !no_split && att_positions > 0 && m->att_ws && bzk_attn_split_ok(aa);
@@ -1603,6 +1624,7 @@ static int llama_step(bz_model* m, const StepIO& io) {
       else BZ_TRY(bzk_attn_decode(st, aa));
       Pro pp{}; pp.mode = PRO_PLAIN; pp.src = VSrc{m->attn_out, 0}; pp.act = act; pp.H = 0;
       BZ_TRY(run_fused(m, Ld.o, pp, rs, &ov));
+      BZ_TRY(lora_after(m, l, LG_O, pp, &ov));
     }
 
     Pro pf{}; pf.mode = PRO_NORM; pf.src = ov; pf.h_in = m->hbuf[cur]; pf.h_out = m->hbuf[cur ^ 1]; pf.norm_w = Ld.ffn_norm;
@@ -1611,7 +1633,7 @@ static int llama_step(bz_model* m, const StepIO& io) {
     static const bool no_mlp_fuse = getenv("BZ_NO_MLP_FUSION") != nullptr;
     // norm + gate/up + SiLU*up + down in one launch (same ring protocol as one GEMV launch), where one of its three forms takes the layer
     enum { MLP_SPLIT, MLP_Q4G, MLP_DENSE, MLP_GQ } mlp = MLP_SPLIT;
-    if (!no_mlp_fuse && Ld.gateup.parts.size() == 1 && Ld.down.parts.size() == 1) {
+    if (!no_mlp_fuse && !lora_mlp && Ld.gateup.parts.size() == 1 && Ld.down.parts.size() == 1) {   // a gate / up / down adapter takes the split MLP
       const LinearDev& GU = Ld.gateup.parts[0]; const LinearDev& DN = Ld.down.parts[0];
       if (act == BZ_F16 && bzk_mlp_fusable(GU, DN, H, I)) mlp = MLP_Q4G;
       else if (bzk_mlp_dense_fusable(GU, DN, Ld.down_slabs, H, I, act)) mlp = MLP_DENSE;   // the dense 16-bit form of the same fusion (slab-major down_proj copy)
@@ -1629,8 +1651,11 @@ static int llama_step(bz_model* m, const StepIO& io) {
       VSrc gu;
       BZ_TRY(run_fused(m, Ld.gateup, pf, rs, &gu));
       cur ^= 1;
-      Pro ps{}; ps.mode = PRO_SILU; ps.src = gu; ps.H = I; ps.act = act;
+      Pro pxf = pf; pxf.src = VSrc{nullptr, 0}; pxf.h_in = m->hbuf[cur]; pxf.h_out = nullptr; pxf.perm = nullptr;
+      BZ_TRY(lora_after(m, l, LG_GATEUP, pxf, &gu));
+      Pro ps{}; ps.mode = PRO_SILU; ps.src = gu; ps.H = I; ps.act = act;      // SiLU * up over the ADAPTED gate / up row
       BZ_TRY(run_fused(m, Ld.down, ps, rs, &dn));
+      BZ_TRY(lora_after(m, l, LG_DOWN, ps, &dn));
     }
     prev = dn;
   }
@@ -1979,7 +2004,8 @@ static int prefill_exact(const bz_model* m, int n, bool decode_batch) {
 
 // tokens [S] at positions pos0 .. pos0+S-1; `slots` (paged only): device i32 [S].  Logits of the last row (or all rows) -> logits_out.
 // per-row context of a decode batch: row r is its own sequence (position row_pos[r], block-table row r); nullptr row_pos = one prompt
-struct RowsCtx { const int* row_pos = nullptr; int table_stride = 0; int max_len = 0; };
+// row_lora: device LoRA slot id per row (-1: none); nullptr = every row under the model's current-slot scalar (prompts, the engine's prompt chunks)
+struct RowsCtx { const int* row_pos = nullptr; int table_stride = 0; int max_len = 0; const int* row_lora = nullptr; };
 // speculative verify (llama_verify_rows): the head of all S <= 16 rows is the multi-row exact lm_head (bz_speculative.hip), which streams the matrix once per
 // 8 rows and leaves per-row argmax partials in m->sp_pval / m->sp_pidx; logits [S][vocab] device
 struct SpecHeadOut { float* logits; };
@@ -1994,6 +2020,15 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
   const int exact = prefill_exact(m, S, rc.row_pos != nullptr);
   const bool attn_exact = exact != 0 || act == BZ_F32;       // f32 models: the oracle's double-precision sums cost little next to the f32 cache reads
   BZ_TRACE("prefill: S=%d position=%d rows=%s exact=%d window=%d", S, pos0, rc.row_pos ? "decode-batch" : "prompt", exact, c.sliding_window);
+  // LoRA: after the GEMM of a group in the table's mask, the rows-form shrink over the rows the GEMM read and the expand over the rows it wrote
+  auto lora_rows = [&](int layer, int group, float* y, int n, int s0) -> int {
+    const BzLoraTable* T = m->lora;
+    if (!T || !T->group_on(group)) return BZ_OK;
+    const LoraGroup g = bzl_group(T, group);
+    const int* rl = rc.row_lora ? rc.row_lora + s0 : nullptr;
+    BZ_TRY(bzk_lora_shrink_rows(st, T, layer, g, act, m->pf_x16, n, rl));
+    return bzk_lora_expand_rows(st, T, layer, g, act, y, n, rl);
+  };
   for (int s0 = 0; s0 < S; s0 += CH) {
     const int n = std::min(CH, S - s0), p0 = pos0 + s0;
     // decode batch (row_pos set): one block-table row per sequence -- the kernels index rows by the row number INSIDE the chunk, so the chunk
@@ -2007,15 +2042,19 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
       const bool gq = act == BZ_F32;      // block-format projections: f32 rows, split operands
       BZ_TRY(bzk_pf_norm(st, dt, m->pf_h, prev, L.attn_norm, n, H, c.rms_eps, act, m->pf_x16));
       BZ_TRY(gq ? pf_gemm_gq(m, L.qkv, (const float*)m->pf_x16, n, m->pf_qkv) : pf_gemm(m, L.qkv.parts[0], m->pf_x16, n, m->pf_qkv, exact));
+      BZ_TRY(lora_rows(l, LG_QKV, m->pf_qkv, n, s0));
       BZ_TRY(bzk_pf_rope_kv(st, m->pf_qkv, n, nq, nkv, hd, m->cos_t, m->sin_t, c.rope_interleaved, p0, act, vw, l, slots ? slots + s0 : nullptr,
                             rc.row_pos ? rc.row_pos + s0 : nullptr));
       BZ_TRY(bzk_pf_attn(st, dt, m->pf_qkv, n, nq, nkv, hd, p0, act, vw, l, m->pf_x16, rc.row_pos ? rc.row_pos + s0 : nullptr, rc.table_stride, rc.max_len, attn_exact,
                          layer_window(c, l)));
       BZ_TRY(gq ? pf_gemm_gq(m, L.o, (const float*)m->pf_x16, n, m->pf_t) : pf_gemm(m, L.o.parts[0], m->pf_x16, n, m->pf_t, exact));
+      BZ_TRY(lora_rows(l, LG_O, m->pf_t, n, s0));
       BZ_TRY(bzk_pf_norm(st, dt, m->pf_h, m->pf_t, L.ffn_norm, n, H, c.rms_eps, act, m->pf_x16));
       BZ_TRY(gq ? pf_gemm_gq(m, L.gateup, (const float*)m->pf_x16, n, m->pf_gu) : pf_gemm(m, L.gateup.parts[0], m->pf_x16, n, m->pf_gu, exact));
+      BZ_TRY(lora_rows(l, LG_GATEUP, m->pf_gu, n, s0));
       BZ_TRY(bzk_pf_silu(st, dt, m->pf_gu, n, I, act, m->pf_x16));
       BZ_TRY(gq ? pf_gemm_gq(m, L.down, (const float*)m->pf_x16, n, m->pf_t) : pf_gemm(m, L.down.parts[0], m->pf_x16, n, m->pf_t, exact));
+      BZ_TRY(lora_rows(l, LG_DOWN, m->pf_t, n, s0));
       prev = m->pf_t;
     }
     // head.  Several rows wanted (all_logits, decode batch) and a dense lm_head in the activation dtype: final norm rows + one MFMA GEMM that
@@ -3010,7 +3049,8 @@ extern "C" int bz_decode_batch_graph_free(bz_batch_graph* g) {
   hipDeviceSynchronize();
   if (g->exec) hipGraphExecDestroy(g->exec);
   if (g->graph) hipGraphDestroy(g->graph);
-  for (void* p : {(void*)g->tok, (void*)g->next, (void*)g->pos, (void*)g->slot, (void*)g->table, (void*)g->step}) if (p) hipFree(p);
+  for (void* p : {(void*)g->tok, (void*)g->next, (void*)g->pos, (void*)g->slot, (void*)g->table, (void*)g->step, (void*)g->row_lora}) if (p) hipFree(p);
+  if (g->m && g->m->lora) for (int sl : g->host_lora) if (sl >= 0) g->m->lora->users[sl]--;
   if (g->log) hipHostFree(g->log);
   if (g->logits) bz_tensor_free(g->logits);
   if (g->dev) bz_dev_release(g->dev);
@@ -3052,11 +3092,12 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
   bz_dev_retain(m->dev); g->dev = m->dev;
   g->m = m; g->kv = kv; g->N = N; g->max_blocks = max_blocks; g->capacity = capacity; g->host_pos.assign(N, -1);
   if (hipMalloc(&g->tok, (size_t)N * 8) != hipSuccess || hipMalloc(&g->next, (size_t)N * 8) != hipSuccess || hipMalloc(&g->pos, (size_t)N * 4) != hipSuccess ||
-      hipMalloc(&g->slot, (size_t)N * 4) != hipSuccess || hipMalloc(&g->table, (size_t)N * max_blocks * 4) != hipSuccess || hipMalloc(&g->step, 64) != hipSuccess ||
+      hipMalloc(&g->slot, (size_t)N * 4) != hipSuccess || hipMalloc(&g->row_lora, (size_t)N * 4) != hipSuccess || hipMalloc(&g->table, (size_t)N * max_blocks * 4) != hipSuccess || hipMalloc(&g->step, 64) != hipSuccess ||
       hipHostMalloc(&g->log, sizeof(long long) * bz_batch_graph::LOGCAP * N, hipHostMallocDefault) != hipSuccess)
     return BZ_E_OOM;
   hipMemset(g->tok, 0, (size_t)N * 8); hipMemset(g->next, 0, (size_t)N * 8); hipMemset(g->pos, 0, (size_t)N * 4); hipMemset(g->slot, 0, (size_t)N * 4);
-  hipMemset(g->table, 0, (size_t)N * max_blocks * 4); hipMemset(g->step, 0, 64);
+  hipMemset(g->table, 0, (size_t)N * max_blocks * 4); hipMemset(g->step, 0, 64); hipMemset(g->row_lora, 0xff, (size_t)N * 4);   // every row: slot -1 (none)
+  g->host_lora.assign(N, -1);
   memset(g->log, 0xff, sizeof(long long) * bz_batch_graph::LOGCAP * N);
   const int64_t shp[2] = {N, m->cfg.vocab};
   BZ_TRY(bz_tensor_zeros(m->dev, BZ_F32, shp, 2, &g->logits));
@@ -3064,14 +3105,15 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
   auto body = [&](hipStream_t cap) -> int {
     if (er) BZ_TRY(bzk_engine_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N, er->rows));
     else BZ_TRY(bzk_batch_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N));
-    RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity;
+    RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity; rcx.row_lora = g->row_lora;
     BZ_TRY(prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, rcx));
     if (c) BZ_TRY(bzk_grammar_mask_rows(cap, c, (float*)g->logits->ptr));
     if (s) BZ_TRY(bzk_batch_sample(cap, s, (const float*)g->logits->ptr, nullptr, g->next, g->log, g->step, bz_batch_graph::LOGCAP));
     else BZ_TRY(bzk_batch_argmax(cap, (const float*)g->logits->ptr, m->cfg.vocab, g->next, g->log, g->step, bz_batch_graph::LOGCAP, N));
     if (c) BZ_TRY(bzk_grammar_advance_rows(cap, c, g->next));
     if (er)
-      BZ_TRY(bzk_engine_finish(cap, er->rows, g->next, g->pos, g->table, max_blocks, g->step, bz_batch_graph::LOGCAP, N, er->status, er->nlive, c ? bzk_grammar_cursor_states(c) : nullptr));
+      BZ_TRY(bzk_engine_finish(cap, er->rows, g->next, g->pos, g->table, max_blocks, g->step, bz_batch_graph::LOGCAP, N, er->status, er->nlive, c ? bzk_grammar_cursor_states(c) : nullptr,
+                               m->lora ? g->row_lora : nullptr));
     return BZ_OK;
   };
   BZ_TRY(capture_graph(body, &g->graph, &g->exec));
@@ -3109,11 +3151,103 @@ int bzi_batch_graph_launch(bz_batch_graph* g) {
   return BZ_OK;
 }
 bz_device* bzi_model_device(bz_model* m) { return m && m->finalized ? m->dev : nullptr; }   // nullptr: not finalized
+BzLoraTable* bzi_model_lora(bz_model* m) { return m ? m->lora : nullptr; }
+int bzi_forward_paged_lora(bz_model* m, int slot, const bz_tensor* tokens, int S, bz_paged_kv* kv, const bz_tensor* slot_mapping, const bz_tensor* block_table, int n_blocks,
+                           int seq_len_k, int start_pos, bz_tensor* logits_out, uint32_t flags) {
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  BzLoraTable* T = m->lora;
+  if (!T || T->cur == slot) return bz_forward_paged(m, tokens, S, kv, slot_mapping, block_table, n_blocks, seq_len_k, start_pos, logits_out, flags);
+  const int before = T->cur;
+  BZ_TRY(bzl_set_cur(T, m->dev->stream, slot));
+  const int rc = bz_forward_paged(m, tokens, S, kv, slot_mapping, block_table, n_blocks, seq_len_k, start_pos, logits_out, flags);
+  std::string why = rc != BZ_OK ? bz_last_error() : "";
+  const int rc2 = bzl_set_cur(T, m->dev->stream, before);
+  if (rc != BZ_OK) { bz_set_error("%s", why.c_str()); return rc; }
+  return rc2;
+}
 int bzi_prefill_reserve(bz_model* m, int rows) {
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   BZ_HIP(hipSetDevice(m->dev->id));
   return prefill_ws(m, rows);
 }
+// ---- LoRA: the model-side entry points (table, slots, current adapter; the kernels and the adapter objects are bz_lora.hip) ----
+// executor.rs:397-420 (LoraAdapterRegistry): the registry's storage -- here slots of a device-resident table the kernels read
+extern "C" int bz_lora_table_create(bz_model* m, const bz_lora_table_config* cfg) {
+  BZ_API_BEGIN
+  if (!m || !cfg) BZ_FAIL(BZ_E_INVALID, "lora table: null argument");
+  if (!m->finalized) BZ_FAIL(BZ_E_INVALID, "lora table: the model is not finalized");
+  if (m->cfg.arch != BZ_ARCH_LLAMA) BZ_FAIL(BZ_E_UNSUPPORTED, "lora table: %s models take no adapters (Llama family only)", m->cfg.arch == BZ_ARCH_MAMBA2 ? "Mamba2" : "DeepSeek-V2");
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  if (m->lora) BZ_FAIL(BZ_E_INVALID, "lora table: the model already has one");
+  const bz_model_config& c = m->cfg;
+  const int qn = c.n_heads * c.head_dim, kn = c.n_kv_heads * c.head_dim;
+  const int K[LT_N] = {c.hidden, c.hidden, c.hidden, qn, c.hidden, c.hidden, c.inter}, N[LT_N] = {qn, kn, kn, c.hidden, c.inter, c.inter, c.hidden};
+  BZ_HIP(hipSetDevice(m->dev->id));
+  BZ_HIP(hipStreamSynchronize(m->dev->stream));
+  return bzl_table_create(m->dev, cfg, c.n_layers, K, N, &m->lora);
+  BZ_API_END
+}
+// executor.rs:397-420 load_lora: an adapter becomes selectable
+extern "C" int bz_lora_attach(bz_model* m, int slot, bz_lora* a) {
+  BZ_API_BEGIN
+  if (!m || !a) BZ_FAIL(BZ_E_INVALID, "lora attach: null argument");
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  if (!m->lora) BZ_FAIL(BZ_E_INVALID, "lora attach: the model has no table (bz_lora_table_create)");
+  BZ_HIP(hipSetDevice(m->dev->id));
+  return bzl_attach(m->lora, m->dev->stream, slot, a);
+  BZ_API_END
+}
+// executor.rs:397-420 unload_lora
+extern "C" int bz_lora_detach(bz_model* m, int slot) {
+  BZ_API_BEGIN
+  if (!m) BZ_FAIL(BZ_E_INVALID, "lora detach: null argument");
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  if (!m->lora) BZ_FAIL(BZ_E_INVALID, "lora detach: the model has no table (bz_lora_table_create)");
+  BZ_HIP(hipSetDevice(m->dev->id));
+  return bzl_detach(m->lora, m->dev->stream, slot);
+  BZ_API_END
+}
+// executor_generate.rs:49-59: the request's lora_adapter is resolved before generation -- here it selects what every step reads
+extern "C" int bz_model_set_lora(bz_model* m, int slot) {
+  BZ_API_BEGIN
+  if (!m) BZ_FAIL(BZ_E_INVALID, "set_lora: null argument");
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  if (!m->lora) { if (slot == -1) return BZ_OK; BZ_FAIL(BZ_E_INVALID, "set_lora: the model has no table (bz_lora_table_create)"); }
+  BZ_HIP(hipSetDevice(m->dev->id));
+  return bzl_set_cur(m->lora, m->dev->stream, slot);
+  BZ_API_END
+}
+// config/generation.rs:142-145 per request, in a batch: one slot id per row of the captured step
+extern "C" int bz_decode_batch_graph_set_adapters(bz_batch_graph* g, const int32_t* slots) {
+  BZ_API_BEGIN
+  if (!g || !slots) BZ_FAIL(BZ_E_INVALID, "batch graph set_adapters: null argument");
+  std::lock_guard<std::recursive_mutex> lock__(g->m->mu);
+  BzLoraTable* T = g->m->lora;
+  for (int i = 0; i < g->N; i++) {
+    if (slots[i] == -1) continue;
+    if (!T) BZ_FAIL(BZ_E_INVALID, "batch graph set_adapters: row %d names slot %d but the model has no table", i, slots[i]);
+    if (slots[i] < -1 || slots[i] >= T->n_slots || !T->slots[slots[i]]) BZ_FAIL(BZ_E_INVALID, "batch graph set_adapters: row %d names slot %d, which is empty or outside 0..%d", i, slots[i], T->n_slots - 1);
+  }
+  for (int i = 0; i < g->N; i++) {
+    if (g->host_lora[i] >= 0) T->users[g->host_lora[i]]--;
+    g->host_lora[i] = slots[i];
+    if (slots[i] >= 0) T->users[slots[i]]++;
+  }
+  BZ_HIP(hipMemcpyAsync(g->row_lora, g->host_lora.data(), (size_t)g->N * 4, hipMemcpyHostToDevice, g->m->dev->stream));   // host_lora stays untouched until the next call
+  return BZ_OK;
+  BZ_API_END
+}
+// op level (parity tests): the rows form as prefill_dense runs it, the decode form as llama_step runs it
+extern "C" int bz_lora_apply(bz_model* m, int layer, uint32_t targets, const bz_tensor* x, const bz_tensor* base, const int32_t* row_slots, int rows, int form, bz_tensor* y_out) {
+  BZ_API_BEGIN
+  if (!m || !x || !base || !row_slots || !y_out) BZ_FAIL(BZ_E_INVALID, "lora_apply: null argument");
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  if (!m->lora) BZ_FAIL(BZ_E_INVALID, "lora_apply: the model has no table (bz_lora_table_create)");
+  BZ_HIP(hipSetDevice(m->dev->id));
+  return bzl_apply(m->lora, m->dev->stream, m->cfg.act_dtype, layer, targets, x, base, row_slots, rows, form, y_out);
+  BZ_API_END
+}
+
 // State BEFORE the first replay: tokens[i] = the token sequence i feeds next, seq_lens[i] = its length INCLUDING that token (its position is
 // seq_lens[i] - 1), block_table = [N, max_blocks] rows (every block a sequence will reach before the next set_block_table call).
 extern "C" int bz_decode_batch_graph_seed(bz_batch_graph* g, const int64_t* tokens, const int32_t* seq_lens, const int32_t* block_table) {
@@ -3635,6 +3769,8 @@ extern "C" int bz_speculative_create(bz_model* target, bz_model* draft, const bz
     if (mm->cfg.arch != BZ_ARCH_LLAMA)
       BZ_FAIL(BZ_E_UNSUPPORTED, "speculative: the %s model is %s; only Llama-family models are built (Mamba2 needs state rollback, DeepSeek-V2 a latent-cache verify)",
               mm == target ? "target" : "draft", mm->cfg.arch == BZ_ARCH_MAMBA2 ? "Mamba2" : "DeepSeek-V2");
+  for (const bz_model* mm : {target, draft})
+    if (mm->lora) BZ_FAIL(BZ_E_UNSUPPORTED, "speculative: the %s model has a LoRA table; the multi-row verify does not apply adapters", mm == target ? "target" : "draft");
   if (target->dev != draft->dev) BZ_FAIL(BZ_E_INVALID, "speculative: target and draft must live on the same device handle");
   if (target->cfg.vocab != draft->cfg.vocab) BZ_FAIL(BZ_E_INVALID, "speculative: vocabularies differ (target %d, draft %d)", target->cfg.vocab, draft->cfg.vocab);
   int k = sc ? sc->num_speculative_tokens : 0;

@@ -383,6 +383,7 @@ struct bz_batch_graph {
   hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
   int N = 0, max_blocks = 0, capacity = 0;
   long long* tok = nullptr; long long* next = nullptr; int* pos = nullptr; int* slot = nullptr; int* table = nullptr; int* step = nullptr;
+  int* row_lora = nullptr; std::vector<int> host_lora;   // LoRA slot id per row (-1: none): device copy the captured step reads, host copy behind it
   bz_tensor* logits = nullptr;        // [N, vocab] of the last replay
   long long* log = nullptr;           // pinned host [LOGCAP][N]
   std::vector<int> host_pos;          // host copy of the positions (limit checks, cache bookkeeping)
@@ -397,12 +398,17 @@ struct BzEngineRows { EngRow* rows; int* status; int* nlive; };
 enum { ENG_IDLE = 0, ENG_TOKEN = 1, ENG_FINISHED = 2 };   // status word: low 2 bits; a finished row's reason (0 length, 1 stop) sits in bits 2..
 int bzk_engine_advance(hipStream_t s, long long* tok, const long long* next, int* pos, int* slot, const int* table, int stride, int bs, int N, const EngRow* rows);
 int bzk_engine_finish(hipStream_t s, EngRow* rows, const long long* next, int* pos, int* table, int stride, const int* step, int logcap, int N, int* status,
-                      int* nlive, uint32_t* gstate /*nullable: the grammar cursor's states*/);
+                      int* nlive, uint32_t* gstate /*nullable: the grammar cursor's states*/, int* row_lora /*nullable: a row that ends gets LoRA slot -1*/);
 // what the engine needs of bz_host.hip: the capture with the row life cycle in it, a launch under the model's lock, the model's device, the prompt workspace
 int bzk_kv_copy_slots(hipStream_t s, bz_paged_kv* kv, const int* d_triples, int n, int max_j);
 int bzi_engine_capture(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_grammar_cursor* c, const BzEngineRows* er, bz_batch_graph** out);
 int bzi_batch_graph_launch(bz_batch_graph* g);
 bz_device* bzi_model_device(bz_model* m);
+struct BzLoraTable;
+BzLoraTable* bzi_model_lora(bz_model* m);   // nullptr: no table
+// bz_forward_paged with the model's current LoRA slot set to `slot` for this call alone (one critical section of the model's lock; the scalar is restored)
+int bzi_forward_paged_lora(bz_model* m, int slot, const bz_tensor* tokens, int S, bz_paged_kv* kv, const bz_tensor* slot_mapping, const bz_tensor* block_table, int n_blocks,
+                           int seq_len_k, int start_pos, bz_tensor* logits_out, uint32_t flags);
 int bzi_prefill_reserve(bz_model* m, int rows);
 // non-synchronising row writes for the engine: `stage` is pinned host memory the caller keeps untouched until the stream has passed the copies
 size_t bzk_batch_sampler_row_bytes();
@@ -423,6 +429,48 @@ int bzk_spec_row_partials(hipStream_t s, const float* logits, int R, long long V
 int bzk_spec_argmax_final(hipStream_t s, const float* pval, const int* pidx, int nb, int R, long long* argmax);
 // record [R + 1] = {n_accept, tokens[0 .. n_accept], -1 ...}; next_slot (nullable) <- tokens[n_accept]
 int bzk_spec_accept(hipStream_t s, const long long* argmax, const long long* draft, int R, long long* record, long long* next_slot);
+
+// LoRA (bz_lora.hip).  Targets in the order of the BZ_LORA_* bits; the fused linears of a layer are the groups {q,k,v} {o} {gate,up} {down}.
+enum { LT_Q = 0, LT_K, LT_V, LT_O, LT_GATE, LT_UP, LT_DOWN, LT_N };
+enum { LG_QKV = 0, LG_O, LG_GATEUP, LG_DOWN, LG_N };
+struct LoraEnt { const void* A; const void* B; int r; int dt; float s; int pad; };   // one adapted linear of one slot: A [r][K], B [N][r] in dt; r == 0: none
+struct LoraSeg { int target, n_off, N; };
+struct LoraGroup { int nseg; LoraSeg seg[3]; int K, N; };                             // launch argument: the linears that share x, stacked along N
+struct LoraPair { int dt = BZ_F16; int r = 0, K = 0, N = 0; void* A = nullptr; void* B = nullptr; };
+struct bz_lora {
+  bz_device* dev = nullptr;
+  int rank = 0; float alpha = 0.f; int use_rslora = 0; float scale = 0.f;
+  std::unordered_map<std::string, LoraPair> pairs;   // key: "model.layers.L.self_attn.q_proj"
+  int attached = 0;                                   // slots (of any model) that hold it
+};
+struct BzLoraTable {
+  bz_device* dev = nullptr;
+  int n_slots = 0, max_rank = 0, n_layers = 0, t_rows = 0; unsigned mask = 0;
+  int K[LT_N] = {0}, N[LT_N] = {0};
+  LoraEnt* d_ents = nullptr;         // [n_slots][n_layers][LT_N]
+  int* d_cur = nullptr;              // the model's current slot (-1: none)
+  float* d_t = nullptr;              // shrink output [t_rows][3][max_rank]
+  float* out[LG_N] = {nullptr, nullptr, nullptr, nullptr};   // decode form: the f32 row each group's consumer reads
+  void* x16 = nullptr; float* ybuf = nullptr; int* d_slots = nullptr; int op_rows = 0;   // op-level entry (bz_lora_apply) workspace, grown on demand
+  std::vector<bz_lora*> slots;       // attached adapters (retained)
+  std::vector<std::vector<LoraEnt>> host_ents;   // what each slot's device entries hold (source of the stream-ordered copies)
+  std::vector<int> users;            // per slot: batch-graph rows and admitted engine requests that name it
+  int cur = -1;
+  bool group_on(int g) const { static const unsigned gm[LG_N] = {7u, 8u, 48u, 64u}; return (mask & gm[g]) != 0; }
+};
+int bzl_table_create(bz_device* dev, const bz_lora_table_config* cfg, int n_layers, const int* K, const int* N, BzLoraTable** out);
+void bzl_table_free(BzLoraTable* T);
+int bzl_attach(BzLoraTable* T, hipStream_t st, int slot, bz_lora* a);
+int bzl_detach(BzLoraTable* T, hipStream_t st, int slot);
+int bzl_set_cur(BzLoraTable* T, hipStream_t st, int slot);
+LoraGroup bzl_group(const BzLoraTable* T, int g);
+// row_slot: device slot id per row (nullptr: every row reads the current-slot scalar)
+int bzk_lora_shrink_rows(hipStream_t s, const BzLoraTable* T, int layer, const LoraGroup& g, int act, const void* x16, int rows, const int* row_slot);
+int bzk_lora_expand_rows(hipStream_t s, const BzLoraTable* T, int layer, const LoraGroup& g, int act, float* y, int rows, const int* row_slot);
+int bzk_lora_shrink_dec(hipStream_t s, const BzLoraTable* T, int layer, const LoraGroup& g, const Pro& pro, const int* row_slot = nullptr);
+int bzk_lora_expand_dec(hipStream_t s, const BzLoraTable* T, int layer, const LoraGroup& g, int act, VSrc b, float* out, const int* row_slot = nullptr);
+int bzl_apply(BzLoraTable* T, hipStream_t st, int act, int layer, unsigned targets, const bz_tensor* x, const bz_tensor* base, const int32_t* row_slots, int rows, int form,
+              bz_tensor* y_out);
 
 #if defined(__HIPCC__)
 // ---------------------------------------------------------------------------------------------------------

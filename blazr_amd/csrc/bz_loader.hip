@@ -878,6 +878,130 @@ extern "C" int bz_safetensors_describe(const char* path, char* json_out, size_t 
   BZ_API_END
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// PEFT LoRA adapters (engine/lora.rs:138-257 load_lora_adapter, 270-306 strip_lora_suffix / read_adapter_config)
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+struct LoraFile {
+  StLoader st;
+  std::string st_path;
+  int rank = 0; float alpha = 0.f; bool rslora = false;
+  std::map<std::string, std::pair<const StTensor*, const StTensor*>> pairs;   // layer key -> (lora_A, lora_B)
+};
+// engine/lora.rs:270-281
+bool strip_lora_suffix(const std::string& name, const char* part, std::string* key) {
+  const std::string suf = std::string(".") + part + ".weight";
+  if (!ends_with(name, suf.c_str())) return false;
+  std::string k = name.substr(0, name.size() - suf.size());
+  if (!k.compare(0, 11, "base_model.")) k = k.substr(11);
+  *key = k;
+  return true;
+}
+int lora_parse(const std::string& path, LoraFile* f) {
+  // engine/lora.rs:144-156
+  if (is_file(path)) f->st_path = path;
+  else if (is_file(path + "/adapter_model.safetensors")) f->st_path = path + "/adapter_model.safetensors";
+  else BZ_FAIL(BZ_E_NOTFOUND, "No adapter_model.safetensors found in %s", path.c_str());
+  // engine/lora.rs:159-164, 285-306: r and lora_alpha when the config is there and parses; what PEFT can say beyond a plain adapter is refused, not ignored
+  const std::string cfg_path = (is_file(path) ? dirname_of(path) : path) + "/adapter_config.json";
+  std::string text; JVal j;
+  long long cfg_rank = 0; bool has_alpha = false; double cfg_alpha = 0;
+  if (is_file(cfg_path) && read_text(cfg_path, &text) && json_parse(text.data(), text.size(), &j) && j.t == JVal::OBJ) {
+    double d;
+    if (j.num("r", &d) && d >= 0 && d == (double)(long long)d) cfg_rank = (long long)d;
+    has_alpha = j.num("lora_alpha", &cfg_alpha);
+    f->rslora = j.boolean("use_rslora", false);
+    if (j.boolean("use_dora", false)) BZ_FAIL(BZ_E_UNSUPPORTED, "'%s': use_dora adapters are not supported (the magnitude vectors are not applied)", cfg_path.c_str());
+    const JVal* b = j.get("bias");
+    if (b && b->t == JVal::STR && b->s != "none") BZ_FAIL(BZ_E_UNSUPPORTED, "'%s': bias = \"%s\" is not supported (only \"none\": adapter bias tensors are not applied)", cfg_path.c_str(), b->s.c_str());
+    const JVal* ms = j.get("modules_to_save");
+    if (ms && ms->t == JVal::ARR && !ms->a.empty()) BZ_FAIL(BZ_E_UNSUPPORTED, "'%s': modules_to_save is not empty (fully replaced modules are not supported)", cfg_path.c_str());
+  }
+  if (f->st.add_file(f->st_path) != BZ_OK) {
+    const std::string why = bz_last_error();
+    BZ_FAIL(BZ_E_INVALID, "Failed to open adapter safetensors '%s': %s", f->st_path.c_str(), why.c_str());
+  }
+  // engine/lora.rs:175-196
+  std::map<std::string, const StTensor*> a_keys, b_keys;
+  for (auto& kv : f->st.tensors) {
+    std::string key;
+    if (strip_lora_suffix(kv.first, "lora_A", &key)) a_keys[key] = &kv.second;
+    else if (strip_lora_suffix(kv.first, "lora_B", &key)) b_keys[key] = &kv.second;
+  }
+  if (a_keys.empty())
+    BZ_FAIL(BZ_E_INVALID, "No lora_A weights found in '%s'. Expected tensor names like 'base_model.model.<layer>.lora_A.weight'.", f->st_path.c_str());
+  // engine/lora.rs:198-235: matched pairs; an A without its B is skipped
+  long long detected = 0;
+  for (auto& kv : a_keys) {
+    auto it = b_keys.find(kv.first);
+    if (it == b_keys.end()) continue;
+    const StTensor* A = kv.second; const StTensor* B = it->second;
+    if (kv.first.find("lm_head") != std::string::npos || kv.first.find("embed_tokens") != std::string::npos)
+      BZ_FAIL(BZ_E_UNSUPPORTED, "'%s': an adapter on '%s' is not supported (lm_head / embed_tokens are not adapted)", f->st_path.c_str(), kv.first.c_str());
+    if (A->shape.size() != 2 || B->shape.size() != 2) BZ_FAIL(BZ_E_INVALID, "'%s': '%s': lora_A and lora_B must be 2-D", f->st_path.c_str(), kv.first.c_str());
+    if (A->shape[0] != B->shape[1])
+      BZ_FAIL(BZ_E_UNSUPPORTED, "'%s': '%s': lora_A has rank %lld but lora_B has rank %lld", f->st_path.c_str(), kv.first.c_str(), (long long)A->shape[0], (long long)B->shape[1]);
+    const int dt = st_dtype(A->dtype);
+    if (A->dtype != B->dtype || (dt != BZ_F16 && dt != BZ_BF16 && dt != BZ_F32))
+      BZ_FAIL(BZ_E_UNSUPPORTED, "'%s': '%s': dtypes %s / %s (one of F16, BF16, F32 for both)", f->st_path.c_str(), kv.first.c_str(), A->dtype.c_str(), B->dtype.c_str());
+    if (!detected) detected = A->shape[0];
+    f->pairs[kv.first] = std::make_pair(A, B);
+  }
+  if (f->pairs.empty()) BZ_FAIL(BZ_E_INVALID, "No complete lora_A + lora_B pairs found in '%s'", f->st_path.c_str());
+  // engine/lora.rs:237-241: the config's rank wins; alpha defaults to the rank
+  const long long rank = cfg_rank > 0 ? cfg_rank : detected;
+  if (rank <= 0) BZ_FAIL(BZ_E_INVALID, "Could not determine LoRA rank from adapter file");
+  if (rank > 128) BZ_FAIL(BZ_E_UNSUPPORTED, "'%s': rank %lld (at most 128 is supported)", f->st_path.c_str(), rank);
+  f->rank = (int)rank;
+  f->alpha = has_alpha ? (float)cfg_alpha : (float)rank;
+  return BZ_OK;
+}
+}  // namespace
+
+// engine/lora.rs:138-257, host only: what bz_lora_load would build
+extern "C" int bz_lora_describe(const char* path, char* json_out, size_t cap, size_t* needed) {
+  BZ_API_BEGIN
+  if (!path) BZ_FAIL(BZ_E_INVALID, "lora_describe: null argument");
+  LoraFile f;
+  BZ_TRY(lora_parse(path, &f));
+  const float scaling = f.rslora ? div_rn(f.alpha, sqrt_rn((float)f.rank)) : div_rn(f.alpha, (float)f.rank);   // bz_lora_create's
+  char num[64];
+  std::string s = "{\"rank\": " + std::to_string(f.rank);
+  snprintf(num, sizeof num, "%.9g", (double)f.alpha); s += std::string(", \"alpha\": ") + num;
+  s += std::string(", \"use_rslora\": ") + (f.rslora ? "true" : "false");
+  snprintf(num, sizeof num, "%.9g", (double)scaling); s += std::string(", \"scaling\": ") + num + ", \"pairs\": {";
+  bool first = true;
+  for (auto& kv : f.pairs) {
+    if (!first) s += ", ";
+    first = false;
+    s += "\"" + json_escape(kv.first) + "\": {\"dtype\": \"" + json_escape(kv.second.first->dtype) + "\", \"rank\": " + std::to_string(kv.second.first->shape[0]) +
+         ", \"in\": " + std::to_string(kv.second.first->shape[1]) + ", \"out\": " + std::to_string(kv.second.second->shape[0]) + "}";
+  }
+  s += "}}";
+  if (needed) *needed = s.size() + 1;
+  if (json_out && cap) { const size_t n = std::min(cap - 1, s.size()); memcpy(json_out, s.data(), n); json_out[n] = 0; }
+  return BZ_OK;
+  BZ_API_END
+}
+
+// engine/lora.rs:138-257: the adapter on the device, through bz_lora_create / bz_lora_add
+extern "C" int bz_lora_load(bz_device* dev, const char* path, bz_lora** out) {
+  BZ_API_BEGIN
+  if (!dev || !path || !out) BZ_FAIL(BZ_E_INVALID, "lora_load: null argument");
+  LoraFile f;
+  BZ_TRY(lora_parse(path, &f));
+  bz_lora* a = nullptr;
+  BZ_TRY(bz_lora_create(dev, f.rank, f.alpha, f.rslora ? 1 : 0, &a));
+  for (auto& kv : f.pairs) {
+    const StTensor* A = kv.second.first; const StTensor* B = kv.second.second;
+    const int rc = bz_lora_add(a, kv.first.c_str(), st_dtype(A->dtype), A->data, A->shape.data(), B->data, B->shape.data());
+    if (rc != BZ_OK) { const std::string why = bz_last_error(); bz_lora_free(a); bz_set_error("%s", why.c_str()); return rc; }
+  }
+  *out = a;
+  return BZ_OK;
+  BZ_API_END
+}
+
 // loaders.rs load_model: detect the source, read the config, move every tensor through bz_model_add_*, finalize
 extern "C" int bz_load_model(bz_device* dev, const char* path, bz_model** out, bz_model_config* cfg_out) {
   BZ_API_BEGIN

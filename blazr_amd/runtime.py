@@ -13,7 +13,9 @@ Names and argument meaning follow the reference so that parity tests read like t
 All compute happens in libblazr_hip.so on the GPU; numpy arrays are only the host view of inputs/outputs.
 """
 import ctypes as C
+import json
 import os
+import warnings
 
 import numpy as np
 
@@ -189,6 +191,59 @@ def unpack_awq_zeros(qzeros, N):
     return ((qz[:, :, None] >> _AWQ_SHIFTS[None, None, :]) & 0xF).reshape(qz.shape[0], N).astype(np.float32)
 
 
+class LoraAdapter:
+    """engine/lora.rs LoraAdapter on the device: rank, alpha and one (lora_A [r, in], lora_B [out, r]) pair per adapted linear, at their stored dtype
+    (float16 / float32 arrays, uint16 arrays = bf16 bits)."""
+
+    def __init__(self, dev, h):
+        self.dev, self.h = dev, h
+
+    @classmethod
+    def from_arrays(cls, dev, rank, alpha, pairs, use_rslora=False):
+        """pairs: {"model.layers.3.self_attn.q_proj": (A, B)}"""
+        h = C.c_void_p()
+        L.check(L.lib().bz_lora_create(dev.h, int(rank), float(alpha), int(bool(use_rslora)), C.byref(h)))
+        self = cls(dev, h)
+        for key, (A, B) in pairs.items():
+            a, b = np.ascontiguousarray(A), np.ascontiguousarray(B)
+            if a.dtype != b.dtype or a.ndim != 2 or b.ndim != 2:
+                raise ValueError("lora pair %s: A and B must be 2-D arrays of one dtype" % key)
+            dt = L.BF16 if a.dtype == np.uint16 else _NP2BZ[a.dtype]
+            L.check(L.lib().bz_lora_add(h, key.encode(), dt, _ptr(a), (C.c_int64 * 2)(*a.shape), _ptr(b), (C.c_int64 * 2)(*b.shape)))
+        return self
+
+    @classmethod
+    def load(cls, dev, path):
+        """load_lora_adapter (engine/lora.rs:138-257): a PEFT directory or its adapter_model.safetensors"""
+        h = C.c_void_p()
+        L.check(L.lib().bz_lora_load(dev.h, str(path).encode(), C.byref(h)))
+        return cls(dev, h)
+
+    def __del__(self):
+        try:
+            if self.h and L.alive:
+                L.lib().bz_lora_free(self.h)     # refused while a slot holds it: the model that holds it frees its table first
+        except Exception:
+            pass
+
+
+def lora_describe(path):
+    """bz_lora_describe: the loader's rules on the host alone -> dict(rank, alpha, use_rslora, scaling, pairs)"""
+    need = C.c_size_t(0)
+    L.check(L.lib().bz_lora_describe(str(path).encode(), None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value)
+    L.check(L.lib().bz_lora_describe(str(path).encode(), buf, need.value, None))
+    return json.loads(buf.value.decode())
+
+
+def _lora_mask(targets):
+    if isinstance(targets, int):
+        return targets
+    if isinstance(targets, str):
+        targets = [t for t in targets.split(",") if t]
+    return sum(L.LORA_TARGETS[t.strip().replace("_proj", "")] for t in set(targets))
+
+
 class LoadedModel:
     """boostr::model::LoadedModel<R> behind the C-ABI."""
 
@@ -201,6 +256,8 @@ class LoadedModel:
         self.h = h
         self.finalized = False
         self._shapes = {}
+        self._loras = {}          # name -> (slot, LoraAdapter): LoraAdapterRegistry (executor.rs:397-420)
+        self._lora_slots = 0
 
     def __del__(self):
         try:
@@ -208,6 +265,54 @@ class LoadedModel:
                 L.lib().bz_model_free(self.h)
         except Exception:
             pass
+
+    # --- LoRA: Executor::load_lora / unload_lora / list_loras (executor.rs:397-420), GenerationConfig.lora_adapter ------------------
+    def enable_lora(self, n_slots=8, max_rank=64, targets=("q", "v")):
+        """Once, after finalize and before any graph capture / engine that should apply adapters.  targets: names out of q, k, v, o, gate, up, down."""
+        cfg = L.LoraTableConfig()
+        cfg.n_slots, cfg.max_rank, cfg.targets = int(n_slots), int(max_rank), _lora_mask(targets)
+        L.check(L.lib().bz_lora_table_create(self.h, C.byref(cfg)))
+        self._lora_slots = int(n_slots)
+
+    def load_lora(self, source, name):
+        """source: a PEFT directory / adapter_model.safetensors, or a LoraAdapter.  An insert under an existing name replaces it.  Returns the slot."""
+        adapter = source if isinstance(source, LoraAdapter) else LoraAdapter.load(self.dev, source)
+        if name in self._loras:
+            self.unload_lora(name)
+        used = {slot for slot, _ in self._loras.values()}
+        free = [i for i in range(self._lora_slots) if i not in used]
+        if not free:
+            raise L.BlazrHipError(L.E_INVALID, "load_lora: all %d slots are in use" % self._lora_slots)
+        L.check(L.lib().bz_lora_attach(self.h, free[0], adapter.h))
+        self._loras[name] = (free[0], adapter)
+        return free[0]
+
+    def unload_lora(self, name):
+        if name not in self._loras:
+            return False
+        L.check(L.lib().bz_lora_detach(self.h, self._loras[name][0]))
+        del self._loras[name]
+        return True
+
+    def list_loras(self):
+        return sorted(self._loras)
+
+    def lora_slot(self, name):
+        """slot of a registered name; None -> -1"""
+        return -1 if name is None else self._loras[name][0]
+
+    def set_lora(self, name):
+        """the adapter every following single-sequence step runs under (None: the base model); a decode graph captured earlier follows"""
+        L.check(L.lib().bz_model_set_lora(self.h, self.lora_slot(name)))
+
+    def lora_apply(self, layer, targets, x, base, row_slots, form=0):
+        """op level: the shrink + expand kernels on rows of one fused group (bz_lora_apply)"""
+        x, base = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(base, np.float32)
+        rows = x.shape[0]
+        tx, tb, ty = self.dev.tensor(x), self.dev.tensor(base), self.dev.zeros(base.shape)
+        sl = np.ascontiguousarray(row_slots, dtype=np.int32)
+        L.check(L.lib().bz_lora_apply(self.h, int(layer), _lora_mask(targets), tx.h, tb.h, _ptr(sl), rows, int(form), ty.h))
+        return ty.to_numpy()
 
     # --- VarMap::insert / insert_decomposed_quant ---------------------------------------------------------
     def add_dense(self, name, array):
@@ -594,6 +699,7 @@ def load_model(dev, path):
     L.check(L.lib().bz_load_model(dev.h, os.fsencode(path), C.byref(h), C.byref(c)))
     m = LoadedModel.__new__(LoadedModel)
     m.dev, m.cfg, m.c, m.h, m.finalized, m._shapes = dev, {}, c, h, True, {}
+    m._loras, m._lora_slots = {}, 0
     return m
 
 
@@ -973,6 +1079,13 @@ class BatchDecodeGraph:
         bt = self._table(block_tables)
         L.check(L.lib().bz_decode_batch_graph_set_block_table(self.h, _ptr(bt)))
 
+    def set_adapters(self, names):
+        """one registered adapter name (or None) per row; the next replay reads them"""
+        sl = np.ascontiguousarray([self.model.lora_slot(nm) for nm in names], dtype=np.int32)
+        if len(sl) != self.n:
+            raise ValueError("set_adapters: %d names for %d rows" % (len(sl), self.n))
+        L.check(L.lib().bz_decode_batch_graph_set_adapters(self.h, _ptr(sl)))
+
     def replay(self):
         L.check(L.lib().bz_decode_batch_graph_replay(self.h))
 
@@ -1075,10 +1188,12 @@ class BatchEngine:
         except Exception:
             pass
 
-    def submit(self, prompt, max_tokens, stop=(), grammar_state=None, **sampling):
+    def submit(self, prompt, max_tokens, stop=(), grammar_state=None, lora=None, **sampling):
+        """lora: a name registered with model.load_lora (GenerationConfig.lora_adapter per request); None: the base model"""
         p = np.ascontiguousarray(prompt, dtype=np.int64).reshape(-1)
         stop = [int(t) for t in stop]
-        rq = L.Request(max_tokens=int(max_tokens), n_stop=len(stop), grammar_state=L.GRAMMAR_ROW_FREE if grammar_state is None else int(grammar_state))
+        rq = L.Request(max_tokens=int(max_tokens), n_stop=len(stop), grammar_state=L.GRAMMAR_ROW_FREE if grammar_state is None else int(grammar_state),
+                       lora_slot=self.model.lora_slot(lora) + 1)
         for i, t in enumerate(stop[:L.ENGINE_MAX_STOP]):
             rq.stop_ids[i] = t
         kw = dict(temperature=0.0, top_k=0, top_p=1.0, min_p=0.0, repeat_penalty=1.0, frequency_penalty=0.0, presence_penalty=0.0, repeat_last_n=64, seed=0)
@@ -1208,9 +1323,15 @@ class Executor:
     def generate(self, prompt_tokens, max_tokens, temperature=0.0, repeat_penalty=1.0, repeat_last_n=64, frequency_penalty=0.0,
                  presence_penalty=0.0, eos_id=-1, use_graph=False, paged=False, block_size=16, seed=0, top_k=0, top_p=1.0, min_p=0.0,
                  dry_multiplier=0.0, dry_base=2, dry_allowed_length=0, typical_p=0.0, dynatemp_range=0.0, dynatemp_exponent=1.0, mirostat_mode=0,
-                 mirostat_tau=5.0, mirostat_eta=0.1, logit_bias=None, grammar=None, vocab_bytes=None):
+                 mirostat_tau=5.0, mirostat_eta=0.1, logit_bias=None, grammar=None, vocab_bytes=None, lora_adapter=None):
         """grammar: a GrammarDfa (used from its current state, left in its final state) with vocab_bytes = the bytes of every token of the model's vocabulary
-        (gen_config.grammar, executor_generate.rs:96-121)."""
+        (gen_config.grammar, executor_generate.rs:96-121).  lora_adapter: a name registered with load_lora; an unknown name generates without an adapter
+        and warns (executor_generate.rs:54-57).  The choice is the request's: on a model with a table, None runs the base model whatever set_lora chose before."""
+        if lora_adapter is not None and lora_adapter not in self.model._loras:
+            warnings.warn("Requested LoRA adapter '%s' not found in registry -- generating without it" % lora_adapter)
+            lora_adapter = None
+        if lora_adapter is not None or self.model._lora_slots:
+            self.model.set_lora(lora_adapter)
         g = L.GenConfig()
         g.max_tokens, g.temperature, g.repeat_penalty, g.repeat_last_n = max_tokens, temperature, repeat_penalty, repeat_last_n
         g.frequency_penalty, g.presence_penalty = frequency_penalty, presence_penalty

@@ -508,6 +508,10 @@ int bz_sched_prefix_flush(bz_sched* s, int* dropped_out /*nullable*/);
  *   cancel: a waiting request leaves the queue; an admitted one's row is made idle by a stream-ordered write and its row and blocks are released; tokens of it that
  *     replays in flight still produce are dropped.  One event with finish_reason 2 (token -1) is queued.
  *   poll: events in order; a stop id is delivered as the request's last token (as bz_generate delivers eos_id).
+ *   LoRA (config/generation.rs:142-145 lora_adapter, per request): lora_slot names a slot of the model's table (bz_lora_table_create before bz_engine_create).
+ *     Submit refuses an empty or out-of-range slot (BZ_E_INVALID naming it).  The request's prompt chunks run under that slot, its row's slot id is written with
+ *     the other row writes when it goes live and reset to -1 when the row goes idle; bz_lora_detach is refused from submit until the request's last record is
+ *     read.  Cached KV rows depend on the adapter: a request with lora_slot != 0 neither looks up nor publishes prefix blocks.
  * The engine borrows the model and the cursor (free the engine first) and owns pool, sampler and graph. */
 typedef struct {
   int32_t n_rows;          /* 2..512 */
@@ -524,7 +528,8 @@ typedef struct {
   int32_t max_tokens;
   int32_t n_stop; int64_t stop_ids[8];
   uint32_t grammar_state;  /* BZ_GRAMMAR_ROW_FREE: unconstrained */
-  int32_t reserved[3];
+  int32_t lora_slot;       /* 0: none, k: slot k - 1 of the model's LoRA table (took the first reserved word, so a zeroed request behaves as before) */
+  int32_t reserved[2];
   bz_row_sampling sampling;
 } bz_request;
 typedef struct { int64_t id; int64_t token; int32_t index; int32_t finish_reason; /* -1 running, 0 length, 1 stop, 2 cancelled */ int64_t replay; } bz_engine_event;
@@ -592,6 +597,63 @@ int bz_speculative_free(bz_speculative* s);
  * together, so gaps inside an iteration are 0 and the gap between iterations carries the whole iteration. */
 int bz_generate_speculative(bz_speculative* s, const int64_t* prompt, int n_prompt, const bz_gen_config* gc, int64_t* out_tokens, bz_gen_stats* stats,
                             bz_spec_stats* spec_stats);
+
+/* ---- LoRA adapters (config/generation.rs:142-145 GenerationConfig.lora_adapter; engine/lora.rs:138-257 the PEFT loader; executor.rs:397-420 and
+ * server/lora.rs the registry) --------------------------------------------------------------------------------------------------------------
+ * The reference loads and registers adapters and then only logs the request's choice (executor_generate.rs:49-59); here the arithmetic runs.  For an adapted
+ * linear with base output b (bias included) and input row x (what the base linear sees, unpermuted), R = rounding to the activation dtype,
+ * s = alpha / r in f32 (alpha / sqrt(r) with use_rslora):
+ *     t_j = R(sum_k A[j,k] x_k)   u_n = R(sum_j B[n,j] t_j)   v_n = R(s u_n)   y_n = R(R(b_n) + v_n)
+ * every sum exact (double over exact products) and rounded once to f32 before R; A [r,K] and B [N,r] are used at their stored values (f16 / bf16 / f32).
+ * A row without an adapter gets y = R(b): what its consumer's own rounding gives without a table.  New symbols only: BZ_ABI_VERSION is unchanged.
+ *
+ * bz_lora_table_create: once, after bz_model_finalize and before any graph capture / engine create that should see it (a second call: BZ_E_INVALID;
+ * Mamba2 / DeepSeek-V2: BZ_E_UNSUPPORTED).  The launches a step takes depend on `targets` alone, never on what is attached, so a captured graph stays
+ * valid across attach / detach / set: a target un-fuses exactly the launch that hides its input or output (o: attention and o_proj as two launches; gate /
+ * up / down: the split MLP; q / k / v: nothing, two launches more per layer).  Both kernels find the adapter through a device-resident table
+ * slot -> {layer, target: A, B, r, s} and a device-resident slot id per row (-1: none). */
+#define BZ_LORA_Q 1
+#define BZ_LORA_K 2
+#define BZ_LORA_V 4
+#define BZ_LORA_O 8
+#define BZ_LORA_GATE 16
+#define BZ_LORA_UP 32
+#define BZ_LORA_DOWN 64
+#define BZ_LORA_ALL 127
+typedef struct { int32_t n_slots; /* 1..64 */ int32_t max_rank; /* 1..128 */ uint32_t targets; /* BZ_LORA_* bits */ int32_t reserved[5]; } bz_lora_table_config;
+typedef struct bz_lora bz_lora;
+int bz_lora_table_create(bz_model* m, const bz_lora_table_config* cfg);
+/* An adapter on the device (engine/lora.rs:138-257 LoraAdapter): rank, alpha, then one pair per adapted linear.  key = the module path with the PEFT prefix
+ * stripped ("model.layers.3.self_attn.q_proj"); A host [rank, K], B host [N, rank], both of `dtype` (BZ_F16 / BZ_BF16 / BZ_F32).  bz_lora_free of an attached
+ * adapter: BZ_E_INVALID. */
+int bz_lora_create(bz_device* dev, int rank, float alpha, int use_rslora, bz_lora** out);
+int bz_lora_add(bz_lora* a, const char* key, int dtype, const void* A, const int64_t* a_shape, const void* B, const int64_t* b_shape);
+int bz_lora_free(bz_lora* a);
+/* engine/lora.rs:138-257 rule for rule: `path` = a directory holding adapter_model.safetensors, or the file; optional adapter_config.json beside it gives r,
+ * lora_alpha (and use_rslora); the config's rank wins over the first dimension of a lora_A; no or unparseable config: alpha = rank; the "base_model." prefix is
+ * stripped, the suffix is ".lora_{A,B}.weight"; an A without a B is skipped; no lora_A at all, or no complete pair, is an error in the reference's words.
+ * Beyond the reference, BZ_E_UNSUPPORTED naming the cause: use_dora, bias other than "none", a non-empty modules_to_save, a pair on lm_head / embed_tokens,
+ * a pair whose two ranks disagree.  bz_lora_describe is the host-only parse (no device): JSON {"rank", "alpha", "use_rslora", "scaling", "pairs": {key: {"dtype",
+ * "rank", "in", "out"}}}, buffer protocol of bz_safetensors_describe. */
+int bz_lora_load(bz_device* dev, const char* path, bz_lora** out);
+int bz_lora_describe(const char* path, char* json_out, size_t cap, size_t* needed);
+/* Registry slots (executor.rs:397-420 LoraAdapterRegistry keeps name -> adapter; the names live in the Python layer).  attach: shapes against the model's
+ * linears, targets within the table's mask, rank <= max_rank -- each error names the tensor and the figure; the slot is written by a stream-ordered copy and
+ * the adapter is retained until detach.  detach waits for the model's stream; BZ_E_INVALID while the slot is the model's current one or a batch graph row /
+ * admitted engine request uses it. */
+int bz_lora_attach(bz_model* m, int slot, bz_lora* a);
+int bz_lora_detach(bz_model* m, int slot);
+/* The single-sequence "current adapter" (executor_generate.rs:49-59 resolves GenerationConfig.lora_adapter per request): a stream-ordered write of a device
+ * scalar that every Llama-family step reads -- bz_forward_kv, bz_forward_paged, bz_generate*, the pieces API, captured decode graphs (a graph captured
+ * earlier follows on its next replay), prompts.  slot = -1: none. */
+int bz_model_set_lora(bz_model* m, int slot);
+/* per-row slots (host, N entries, -1 = none) of a batched decode graph: stream-ordered, the next replay reads them */
+int bz_decode_batch_graph_set_adapters(bz_batch_graph* g, const int32_t* slots);
+/* Op level: the two kernels on rows of one fused group of layer `layer` -- targets = BZ_LORA_Q|K|V (N = the three widths stacked), BZ_LORA_O, BZ_LORA_GATE|UP or
+ * BZ_LORA_DOWN.  x F32 [rows, K] (values of the activation dtype), base F32 [rows, N], row_slots host [rows], y_out F32 [rows, N].  form 0: the rows form
+ * (x converted to the activation dtype's rows, y updated in place, as the batched path runs it); form 1: the decode form (rows == 1: x through the plain
+ * prologue, base read as a VSrc, a fresh output row). */
+int bz_lora_apply(bz_model* m, int layer, uint32_t targets, const bz_tensor* x, const bz_tensor* base, const int32_t* row_slots, int rows, int form, bz_tensor* y_out);
 
 /* ---- measurement (methodology of /root/reference/src/cli/bench.rs:24-33,299-306) ----------------------- */
 typedef struct { char name[48]; int32_t launches; double total_ms; double algo_bytes; } bz_kernel_time;

@@ -7,12 +7,16 @@
 //          [--repeat-penalty R] [--seed S] [--graphs] [--paged-attention] [--device D] [--stats]
 //          [--grammar FILE --vocab-bytes FILE [--grammar-regular]]
 //          [--draft <checkpoint> [--spec-tokens k] [--spec-adaptive]]
+//          [--lora <PEFT dir | adapter_model.safetensors>]... [--lora-targets q,v,...]
 //   bz-run <model> --requests FILE --rows N [--pool-blocks B] [--prefill-chunk C] [--depth D] [--prefix-cache] [sampling options, --eos]
 // --requests: continuous batching (BatchEngine::run, engine/batch_engine.rs:91-169; RequestScheduler::submit, engine/request_scheduler.rs:105-205) over N rows.  The file
 // has one request per line, `max_tokens;comma-separated prompt ids`; all are submitted, the engine is stepped until idle, and one line of ids per request is
 // printed in submission order; the engine's statistics go to stderr.  --pool-blocks: the paged pool (default: every row can hold a full-length request);
 // the sampling options apply to every request (request i draws with seed + i), --eos is its stop id.  --prefix-cache: requests share the cached full blocks of
 // earlier prompts (a request admitted in the same step as its donor does not); hits, cached tokens and evictions go to stderr.
+// --lora (repeatable): PEFT adapters (Executor::load_lora, executor.rs:397-420; GenerationConfig.lora_adapter, config/generation.rs:142-145) in slots 0, 1, ... of a
+// table over --lora-targets (names out of q,k,v,o,gate,up,down; default: the union of what the given adapters hold).  Single-sequence modes generate under the
+// first adapter; with --requests, request i uses adapter i mod (n + 1) with 0 = none, so one file exercises a mixed batch.  Not with --draft.
 // --draft: speculative decoding (inference.speculative, config/inference.rs:197-208; generate_text.rs:61-136) with that checkpoint as the draft model: greedy only,
 // the same ids as without it; iterations / accepted / rejected go to stderr (generate_text.rs:130-135).
 // --grammar: a GBNF file (gen_config.grammar, executor_generate.rs:96-121), compiled with the reference's semantics or, with --grammar-regular, as the regular subset of
@@ -38,6 +42,44 @@ static bool read_file(const std::string& path, std::string& out) {
 
 static int fail(const char* what) { fprintf(stderr, "bz-run: %s: %s\n", what, bz_last_error()); return 1; }
 
+// the LoRA table of `m` and one slot per path; targets: "" = the union of the modules the adapters hold (read from bz_lora_describe's pair keys)
+static const char* const kLoraNames[7] = {"q", "k", "v", "o", "gate", "up", "down"};
+static int setup_lora(bz_device* dev, bz_model* m, const std::vector<std::string>& paths, const std::string& targets, std::vector<bz_lora*>& out) {
+  if (paths.empty()) return 0;
+  uint32_t mask = 0;
+  if (!targets.empty()) {
+    size_t at = 0;
+    while (at <= targets.size()) {
+      size_t c = targets.find(',', at);
+      if (c == std::string::npos) c = targets.size();
+      const std::string t = targets.substr(at, c - at);
+      bool ok = t.empty();
+      for (int i = 0; i < 7; i++) if (t == kLoraNames[i] || t == std::string(kLoraNames[i]) + "_proj") { mask |= 1u << i; ok = true; }
+      if (!ok) { fprintf(stderr, "bz-run: --lora-targets: unknown target '%s' (q,k,v,o,gate,up,down)\n", t.c_str()); return 2; }
+      at = c + 1;
+    }
+  } else {
+    for (const std::string& p : paths) {
+      size_t need = 0;
+      if (bz_lora_describe(p.c_str(), nullptr, 0, &need) != BZ_OK) return fail("lora");
+      std::string js(need, '\0');
+      if (bz_lora_describe(p.c_str(), &js[0], need, nullptr) != BZ_OK) return fail("lora");
+      for (int i = 0; i < 7; i++) if (js.find(std::string(".") + kLoraNames[i] + "_proj\"") != std::string::npos) mask |= 1u << i;
+    }
+  }
+  bz_lora_table_config tc;
+  memset(&tc, 0, sizeof tc);
+  tc.n_slots = (int)paths.size(); tc.max_rank = 128; tc.targets = mask;
+  if (bz_lora_table_create(m, &tc) != BZ_OK) return fail("lora table");
+  for (size_t i = 0; i < paths.size(); i++) {
+    bz_lora* a = nullptr;
+    if (bz_lora_load(dev, paths[i].c_str(), &a) != BZ_OK) return fail("lora load");
+    if (bz_lora_attach(m, (int)i, a) != BZ_OK) return fail("lora attach");
+    out.push_back(a);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) { fprintf(stderr, "usage: bz-run <model path> --prompt id,id,... [--max-tokens N] [--graphs] [--paged-attention] ...\n"); return 2; }
   std::string model = argv[1];
@@ -50,6 +92,7 @@ int main(int argc, char** argv) {
   std::string grammar_path, vocab_path; bool grammar_regular = false;
   std::string draft_path; bz_spec_config sc;
   std::string requests_path; int rows = 0, pool_blocks = 0, prefill_chunk = 0, depth = 2; bool prefix_cache = false;
+  std::vector<std::string> lora_paths; std::string lora_targets; std::vector<bz_lora*> loras;
   memset(&sc, 0, sizeof sc);
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
@@ -79,8 +122,12 @@ int main(int argc, char** argv) {
     else if (a == "--prefill-chunk") prefill_chunk = atoi(next("--prefill-chunk"));
     else if (a == "--depth") depth = atoi(next("--depth"));
     else if (a == "--prefix-cache") prefix_cache = true;
+    else if (a == "--lora") lora_paths.push_back(next("--lora"));
+    else if (a == "--lora-targets") lora_targets = next("--lora-targets");
     else { fprintf(stderr, "bz-run: unknown option %s\n", a.c_str()); return 2; }
   }
+  if (lora_paths.size() > 64) { fprintf(stderr, "bz-run: at most 64 --lora adapters\n"); return 2; }
+  if (!lora_paths.empty() && !draft_path.empty()) { fprintf(stderr, "bz-run: --lora and --draft do not go together\n"); return 2; }
   if (!requests_path.empty()) {
     if (rows < 2) { fprintf(stderr, "bz-run: --requests needs --rows N (2..512)\n"); return 2; }
     if (!draft_path.empty() || !grammar_path.empty() || !prompt.empty()) { fprintf(stderr, "bz-run: --requests goes without --prompt, --draft and --grammar\n"); return 2; }
@@ -117,12 +164,14 @@ int main(int argc, char** argv) {
     const bool greedy = gc.temperature == 0.0f && gc.repeat_penalty == 1.0f && gc.frequency_penalty == 0.0f && gc.presence_penalty == 0.0f;
     ec.use_sampler = greedy ? 0 : 1;
     ec.prefix_cache = prefix_cache ? 1 : 0;
+    if (int rc = setup_lora(dev, m, lora_paths, lora_targets, loras)) return rc;     // before the engine captures its step
     bz_engine* e = nullptr;
     if (bz_engine_create(m, &ec, nullptr, &e) != BZ_OK) return fail("engine");
     for (size_t i = 0; i < reqs.size(); i++) {
       bz_request rq;
       memset(&rq, 0, sizeof rq);
       rq.max_tokens = reqs[i].max_tokens; rq.grammar_state = BZ_GRAMMAR_ROW_FREE;
+      rq.lora_slot = (int32_t)(i % (loras.size() + 1));                        // 0 = none, k = adapter k - 1
       if (gc.eos_id >= 0) { rq.n_stop = 1; rq.stop_ids[0] = gc.eos_id; }
       rq.sampling.temperature = gc.temperature; rq.sampling.top_k = gc.top_k; rq.sampling.top_p = gc.top_p; rq.sampling.min_p = gc.min_p;
       rq.sampling.repeat_penalty = gc.repeat_penalty; rq.sampling.frequency_penalty = gc.frequency_penalty; rq.sampling.presence_penalty = gc.presence_penalty;
@@ -159,6 +208,7 @@ int main(int argc, char** argv) {
     }
     bz_engine_free(e);
     bz_model_free(m);
+    for (bz_lora* a : loras) bz_lora_free(a);
     bz_device_close(dev);
     return 0;
   }
@@ -187,6 +237,8 @@ int main(int argc, char** argv) {
   if (bz_device_open(device_id, &dev) != BZ_OK) return fail("device");                    // CudaDevice::new + CudaClient::new (run.rs:70-81)
   bz_model* m = nullptr; bz_model_config cfg;
   if (bz_load_model(dev, model.c_str(), &m, &cfg) != BZ_OK) return fail("load");          // detect_model_source + load_model (run.rs:88-118)
+  if (int rc = setup_lora(dev, m, lora_paths, lora_targets, loras)) return rc;
+  if (!loras.empty() && bz_model_set_lora(m, 0) != BZ_OK) return fail("set lora");          // single-sequence modes: the first adapter
   std::vector<int64_t> out((size_t)(gc.max_tokens > 0 ? gc.max_tokens : 1));
   bz_gen_stats st;
   if (!draft_path.empty()) {
@@ -208,6 +260,7 @@ int main(int argc, char** argv) {
             st.n_generated > 1 ? (st.n_generated - 1) / (st.decode_ms / 1e3) : 0.0, st.finish_reason ? "eos" : "length");
   bz_grammar_free(grammar);
   bz_model_free(m);
+  for (bz_lora* a : loras) bz_lora_free(a);
   bz_device_close(dev);
   return 0;
 }
