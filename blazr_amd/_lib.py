@@ -139,12 +139,31 @@ class EnginePrefixStats(C.Structure):
 
 class EngineConfig(C.Structure):
     _fields_ = [("n_rows", C.c_int32), ("num_blocks", C.c_int32), ("block_size", C.c_int32), ("max_seq_len", C.c_int32), ("prefill_chunk", C.c_int32),
-                ("depth", C.c_int32), ("use_sampler", C.c_int32), ("prefix_cache", C.c_int32), ("reserved", C.c_int32 * 8)]
+                ("depth", C.c_int32), ("use_sampler", C.c_int32), ("prefix_cache", C.c_int32), ("logprobs", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
 class Request(C.Structure):
     _fields_ = [("max_tokens", C.c_int32), ("n_stop", C.c_int32), ("stop_ids", C.c_int64 * 8), ("grammar_state", C.c_uint32), ("lora_slot", C.c_int32), ("reserved", C.c_int32 * 2),
                 ("sampling", RowSampling)]
+
+
+LOGIT_BIAS_MAX, TOP_LOGPROBS_MAX = 512, 20
+BS_BIAS, BS_LOGPROBS = 1, 2
+
+
+class LogprobsRecord(C.Structure):
+    _fields_ = [("token", C.c_int64), ("logprob", C.c_float), ("lse", C.c_float), ("n_top", C.c_int32), ("top_ids", C.c_uint32 * TOP_LOGPROBS_MAX),
+                ("top_logprobs", C.c_float * TOP_LOGPROBS_MAX)]
+
+
+class RequestExtras(C.Structure):
+    _fields_ = [("logprobs", C.c_int32), ("top_logprobs", C.c_int32), ("n_logit_bias", C.c_int32), ("logit_bias_ids", C.c_void_p), ("logit_bias_vals", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class EngineLogprobs(C.Structure):
+    _fields_ = [("id", C.c_int64), ("index", C.c_int32), ("token", C.c_int64), ("logprob", C.c_float), ("n_top", C.c_int32),
+                ("top_ids", C.c_uint32 * TOP_LOGPROBS_MAX), ("top_logprobs", C.c_float * TOP_LOGPROBS_MAX)]
 
 
 LORA_TARGETS = {"q": 1, "k": 2, "v": 4, "o": 8, "gate": 16, "up": 32, "down": 64}
@@ -233,6 +252,12 @@ SYMBOLS = {
     "bz_batch_sampler_set_row": (C.c_int, [P, C.c_int, C.POINTER(RowSampling), P, C.c_int, C.c_int64]),
     "bz_batch_sampler_sample": (C.c_int, [P, P, P]),
     "bz_decode_batch_graph_capture_sampled": (C.c_int, [P, P, C.c_int, C.c_int, P, C.POINTER(P)]),
+    "bz_logit_bias_dedupe": (C.c_int, [C.c_int64, P, P, C.c_int, P, P, C.POINTER(C.c_int)]),
+    "bz_batch_sampler_enable": (C.c_int, [P, C.c_uint32]),
+    "bz_batch_sampler_set_row_bias": (C.c_int, [P, C.c_int, P, P, C.c_int]),
+    "bz_batch_sampler_set_row_logprobs": (C.c_int, [P, C.c_int, C.c_int]),
+    "bz_batch_sampler_read_logprobs": (C.c_int, [P, C.POINTER(LogprobsRecord)]),
+    "bz_decode_batch_graph_read_logprobs": (C.c_int, [P, C.c_int64, C.POINTER(LogprobsRecord)]),
     "bz_generate": (C.c_int, [P, P, C.c_int, C.POINTER(GenConfig), P, C.POINTER(GenStats)]),
     "bz_profile_step": (C.c_int, [P, P, C.c_int64, C.c_int, C.c_int, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),
     "bz_profile_step_ssm": (C.c_int, [P, P, C.c_int64, C.c_int, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),
@@ -319,6 +344,8 @@ SYMBOLS = {
     "bz_engine_prefix_flush": (C.c_int, [P, C.POINTER(C.c_int)]),
     "bz_engine_create": (C.c_int, [P, C.POINTER(EngineConfig), P, C.POINTER(P)]),
     "bz_engine_submit": (C.c_int, [P, P, C.c_int, C.POINTER(Request), C.POINTER(C.c_int64)]),
+    "bz_engine_submit_ex": (C.c_int, [P, P, C.c_int, C.POINTER(Request), C.POINTER(RequestExtras), C.POINTER(C.c_int64)]),
+    "bz_engine_poll_logprobs": (C.c_int, [P, C.POINTER(EngineLogprobs), C.c_int, C.POINTER(C.c_int)]),
     "bz_engine_cancel": (C.c_int, [P, C.c_int64]),
     "bz_engine_step": (C.c_int, [P, C.POINTER(C.c_int)]),
     "bz_engine_poll": (C.c_int, [P, C.POINTER(EngineEvent), C.c_int, C.POINTER(C.c_int)]),

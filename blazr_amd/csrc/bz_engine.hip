@@ -9,6 +9,7 @@
 //                      row's own park block (it attends to what it has just written: finite logits, no slot shared with any other row).
 //   k_engine_finish    the step's last launch (after the pick and the grammar advance).  Live row: left -= 1; ends on a stop id (reason 1), else on
 //                      left == 0 (reason 0).  A row that ends becomes idle here: live = 0, pos = 0, table[row][0] = its park block, its grammar state FREE.
+//                      its bias list empty and its logprobs off (the record of this step is written before, by k_lp_record).
 //                      One status word per row and the number of rows still live go to pinned rings beside the token log.  One workgroup, N <= 512.
 //   k_kv_copy_slots    the prefix cache's copy-on-write: the first j slots of a cached block into a request's own block, every layer, K and V, every KV head;
 //                      one launch for all copies of a step, the (source, destination, j) triples read from device memory.
@@ -41,7 +42,7 @@ __global__ void k_engine_advance(long long* tok, const long long* next, int* pos
   }
 }
 __global__ __launch_bounds__(512) void k_engine_finish(EngRow* rows, const long long* next, int* pos, int* table, int stride, const int* step, int logcap, int N,
-                                                       int* status, int* nlive, uint32_t* gstate, int* row_lora) {
+                                                       int* status, int* nlive, uint32_t* gstate, int* row_lora, int* bias_cnt, int* lp_top_n) {
   const int i = threadIdx.x;
   const int st = *step - 1;                      // the pick has counted this replay already
   const int at = ((st % logcap) + logcap) % logcap;
@@ -63,6 +64,8 @@ __global__ __launch_bounds__(512) void k_engine_finish(EngRow* rows, const long 
         table[(size_t)i * stride] = r.park_block;
         if (gstate) gstate[i] = BZ_GRAMMAR_ROW_FREE;
         if (row_lora) row_lora[i] = -1;
+        if (bias_cnt) bias_cnt[i] = 0;
+        if (lp_top_n) lp_top_n[i] = -1;
         word = ENG_FINISHED | (reason << 2);
       } else { word = ENG_TOKEN; still = 1; }
     }
@@ -107,9 +110,9 @@ int bzk_engine_advance(hipStream_t s, long long* tok, const long long* next, int
   return BZ_OK;
 }
 int bzk_engine_finish(hipStream_t s, EngRow* rows, const long long* next, int* pos, int* table, int stride, const int* step, int logcap, int N, int* status,
-                      int* nlive, uint32_t* gstate, int* row_lora) {
+                      int* nlive, uint32_t* gstate, int* row_lora, int* bias_cnt, int* lp_top_n) {
   if (N > 512) BZ_FAIL(BZ_E_INVALID, "engine finish: N = %d above the 512 rows one workgroup serves", N);
-  hipLaunchKernelGGL(k_engine_finish, dim3(1), dim3(512), 0, s, rows, next, pos, table, stride, step, logcap, N, status, nlive, gstate, row_lora);
+  hipLaunchKernelGGL(k_engine_finish, dim3(1), dim3(512), 0, s, rows, next, pos, table, stride, step, logcap, N, status, nlive, gstate, row_lora, bias_cnt, lp_top_n);
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
@@ -118,7 +121,10 @@ int bzk_engine_finish(hipStream_t s, EngRow* rows, const long long* next, int* p
 // host
 // ---------------------------------------------------------------------------------------------------------
 namespace {
-struct EngReq { int64_t id = -1; std::vector<int64_t> prompt; bz_request rq{}; int row = -1; bool live = false; int produced = 0; long long first_replay = -1; int shared = 0; };
+struct EngReq {
+  int64_t id = -1; std::vector<int64_t> prompt; bz_request rq{}; int row = -1; bool live = false; int produced = 0; long long first_replay = -1; int shared = 0;
+  int top_n = -1; std::vector<uint32_t> bias_ids; std::vector<float> bias_vals;   // bz_request_extras: logprobs (-1: not asked) and the deduplicated bias list
+};
 // pinned staging for the stream-ordered writes: a slot is reused only after the stream has passed the copies that read it
 struct Stage { char* host = nullptr; hipEvent_t ev = nullptr; bool pending = false; };
 struct RowMisc { long long next; int pos, lora; EngRow er; uint32_t gram[2]; };   // lora: the row's LoRA slot id (-1: none)
@@ -129,13 +135,14 @@ struct bz_engine {
   EngRow* d_rows = nullptr; int* status = nullptr; int* nlive = nullptr;
   int max_blocks = 0, max_chunk = 0;
   long long* d_ptok = nullptr; int* d_pslot = nullptr; int* d_ptable = nullptr; int* d_copy = nullptr; bz_tensor* plogits = nullptr;
-  std::vector<Stage> stages; size_t off_misc = 0, off_bs = 0, off_ptok = 0, off_pslot = 0, off_copy = 0, stage_bytes = 0; int stage_next = 0;
+  std::vector<Stage> stages; size_t off_misc = 0, off_bs = 0, off_ptok = 0, off_pslot = 0, off_copy = 0, off_lp = 0, stage_bytes = 0; int stage_next = 0;
   std::vector<hipEvent_t> rev;               // one event per replay in flight (ring)
   long long read = 0;                        // records harvested; g->replays = enqueued
   std::map<int64_t, EngReq> reqs;            // waiting and admitted
   std::vector<int64_t> row_req;              // host view: the request a row serves, or -1
   std::vector<bz_sched_action> acts;
   std::deque<bz_engine_event> events;
+  std::deque<bz_engine_logprobs> lp_events;  // one per token event of a request that asked for logprobs
   long long prompt_tokens = 0, generated = 0; double admit_ms = 0;
   long long skipped = 0, copy_launches = 0, copied_blocks = 0;   // prefix cache
   static const int EVRING = 128;
@@ -193,6 +200,8 @@ extern "C" int bz_engine_create(bz_model* m, const bz_engine_config* cfg, bz_gra
     BZ_FAIL(BZ_E_INVALID, "engine create: max_seq_len = %d out of range (2 .. the model's %d)", cfg->max_seq_len, mc.max_seq_len);
   if (cfg->num_blocks <= cfg->n_rows) BZ_FAIL(BZ_E_INVALID, "engine create: num_blocks = %d leaves nothing beside the %d park blocks", cfg->num_blocks, cfg->n_rows);
   if (cfg->prefix_cache != 0 && cfg->prefix_cache != 1) BZ_FAIL(BZ_E_INVALID, "engine create: prefix_cache = %d (0 = off, 1 = on)", cfg->prefix_cache);
+  if (cfg->logprobs != 0 && cfg->logprobs != 1) BZ_FAIL(BZ_E_INVALID, "engine create: logprobs = %d (0 = off, 1 = on)", cfg->logprobs);
+  if (cfg->logprobs && !cfg->use_sampler) BZ_FAIL(BZ_E_INVALID, "engine create: logprobs = 1 needs use_sampler = 1 (got use_sampler = %d): bias and logprobs live in the batched sampler", cfg->use_sampler);
   const int N = cfg->n_rows;
   bz_device* dev = bzi_model_device(m);
   if (!dev) BZ_FAIL(BZ_E_INVALID, "engine create: model not finalized");
@@ -211,6 +220,7 @@ extern "C" int bz_engine_create(bz_model* m, const bz_engine_config* cfg, bz_gra
   const int kvdt = mc.act_dtype;
   if ((rc = bz_paged_kv_create(dev, mc.n_layers, cfg->num_blocks, cfg->block_size, mc.n_kv_heads, mc.head_dim, kvdt, &e->kv)) != BZ_OK) return fail(rc);
   if (cfg->use_sampler && (rc = bz_batch_sampler_create(dev, N, mc.vocab, &e->sampler)) != BZ_OK) return fail(rc);
+  if (cfg->logprobs && (rc = bz_batch_sampler_enable(e->sampler, BZ_BS_BIAS | BZ_BS_LOGPROBS)) != BZ_OK) return fail(rc);
   // the prompt workspace before the capture, for the largest chunk as well: a later reallocation would synchronise
   if ((rc = bzi_prefill_reserve(m, std::max(N, e->max_chunk))) != BZ_OK) return fail(rc);
   const size_t ring = (size_t)bz_batch_graph::LOGCAP;
@@ -222,14 +232,15 @@ extern "C" int bz_engine_create(bz_model* m, const bz_engine_config* cfg, bz_gra
   memset(e->status, 0, ring * N * 4); memset(e->nlive, 0, ring * 4);
   const int64_t shp[2] = {1, mc.vocab};
   if ((rc = bz_tensor_zeros(dev, BZ_F32, shp, 2, &e->plogits)) != BZ_OK) return fail(rc);
-  // staging slots: [table row][RowMisc][sampler row][prompt chunk tokens][prompt chunk slots][copy triples]
+  // staging slots: [table row][RowMisc][sampler row][prompt chunk tokens][prompt chunk slots][copy triples][top_n, bias list (logprobs = 1)]
   auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
   e->off_misc = up((size_t)e->max_blocks * 4);
   e->off_bs = e->off_misc + up(sizeof(RowMisc));
   e->off_ptok = e->off_bs + up(bzk_batch_sampler_row_bytes());
   e->off_pslot = e->off_ptok + up((size_t)e->max_chunk * 8);
   e->off_copy = e->off_pslot + up((size_t)e->max_chunk * 4);
-  e->stage_bytes = e->off_copy + up((size_t)N * 12);
+  e->off_lp = e->off_copy + up((size_t)N * 12);
+  e->stage_bytes = e->off_lp + (cfg->logprobs ? up(bzk_lp_stage_bytes()) : 0);
   e->stages.resize(std::min(64, std::max(8, 2 * N)));
   for (Stage& s : e->stages)
     if (hipHostMalloc((void**)&s.host, e->stage_bytes, hipHostMallocDefault) != hipSuccess || hipEventCreateWithFlags(&s.ev, hipEventDisableTiming) != hipSuccess) {
@@ -254,9 +265,16 @@ extern "C" int bz_engine_create(bz_model* m, const bz_engine_config* cfg, bz_gra
   BZ_API_END
 }
 
-extern "C" int bz_engine_submit(bz_engine* e, const int64_t* prompt, int n_prompt, const bz_request* rq, int64_t* id_out) {
+extern "C" int bz_engine_submit(bz_engine* e, const int64_t* prompt, int n_prompt, const bz_request* rq, int64_t* id_out) { return bz_engine_submit_ex(e, prompt, n_prompt, rq, nullptr, id_out); }
+extern "C" int bz_engine_submit_ex(bz_engine* e, const int64_t* prompt, int n_prompt, const bz_request* rq, const bz_request_extras* ex, int64_t* id_out) {
   BZ_API_BEGIN
   if (!e || !prompt || !rq || !id_out) BZ_FAIL(BZ_E_INVALID, "engine submit: null argument");
+  std::vector<uint32_t> bias_ids; std::vector<float> bias_vals;
+  if (ex) {
+    if (!e->cfg.logprobs) BZ_FAIL(BZ_E_INVALID, "engine submit: request extras on an engine created with logprobs = %d (bz_engine_config.logprobs = 1 enables bias and logprobs)", e->cfg.logprobs);
+    if (ex->top_logprobs < 0 || ex->top_logprobs > BZ_TOP_LOGPROBS_MAX) BZ_FAIL(BZ_E_INVALID, "engine submit: top_logprobs = %d out of range (0 .. %d)", ex->top_logprobs, BZ_TOP_LOGPROBS_MAX);
+    BZ_TRY(bzk_lp_check_bias(e->mc.vocab, ex->logit_bias_ids, ex->logit_bias_vals, ex->n_logit_bias, bias_ids, bias_vals, "engine submit"));
+  }
   if (n_prompt < 1 || rq->max_tokens < 1) BZ_FAIL(BZ_E_INVALID, "engine submit: n_prompt = %d and max_tokens = %d must both be at least 1", n_prompt, rq->max_tokens);
   if ((long long)n_prompt + rq->max_tokens > e->cfg.max_seq_len)
     BZ_FAIL(BZ_E_INVALID, "engine submit: n_prompt + max_tokens = %lld exceeds max_seq_len = %d", (long long)n_prompt + rq->max_tokens, e->cfg.max_seq_len);
@@ -286,6 +304,7 @@ extern "C" int bz_engine_submit(bz_engine* e, const int64_t* prompt, int n_promp
   else BZ_TRY(bz_sched_submit(e->sched, n_prompt, rq->max_tokens, &id));  // (names the figure when the request could never fit the pool)
   EngReq& r = e->reqs[id];
   r.id = id; r.prompt.assign(prompt, prompt + n_prompt); r.rq = *rq;
+  if (ex) { r.top_n = ex->logprobs ? ex->top_logprobs : -1; r.bias_ids.swap(bias_ids); r.bias_vals.swap(bias_vals); }
   if (rq->lora_slot != 0) T->users[rq->lora_slot - 1]++;
   *id_out = id;
   return BZ_OK;
@@ -307,6 +326,7 @@ static int eng_idle_row(bz_engine* e, int row) {
   BZ_HIP(hipMemcpyAsync(e->g->pos + row, &mi->pos, 4, hipMemcpyHostToDevice, st));
   BZ_HIP(hipMemcpyAsync(e->g->table + (size_t)row * e->max_blocks, tb, 4, hipMemcpyHostToDevice, st));
   if (e->cursor) BZ_TRY(bzk_grammar_cursor_stage_row(st, e->cursor, row, BZ_GRAMMAR_ROW_FREE, mi->gram));
+  if (e->cfg.logprobs) BZ_TRY(bzk_lp_stage_row(st, e->sampler, row, -1, nullptr, nullptr, 0, s->host + e->off_lp));
   return eng_stage_done(e, s);
 }
 
@@ -344,6 +364,14 @@ static int eng_harvest(bz_engine* e) {
     if (!q.live || q.first_replay > r) continue;            // a token of the row's previous (cancelled) request
     const bool fin = (w & 3) == ENG_FINISHED;
     e->events.push_back(bz_engine_event{q.id, lg[row], q.produced, fin ? (w >> 2) : -1, r});
+    if (q.top_n >= 0) {                                     // the record k_lp_record wrote in the same replay
+      const bz_logprobs_record& rec = bzk_lp_ring(e->sampler)[at + row];
+      bz_engine_logprobs lp;
+      memset(&lp, 0, sizeof(lp));
+      lp.id = q.id; lp.index = q.produced; lp.token = rec.token; lp.logprob = rec.logprob; lp.n_top = rec.n_top;
+      for (int k = 0; k < rec.n_top && k < BZ_TOP_LOGPROBS_MAX; k++) { lp.top_ids[k] = rec.top_ids[k]; lp.top_logprobs[k] = rec.top_logprobs[k]; }
+      e->lp_events.push_back(lp);
+    }
     q.produced++; e->generated++;
     if (fin) {
       const int64_t id = q.id;
@@ -400,6 +428,7 @@ static int eng_go_live(bz_engine* e, EngReq& q, const int32_t* blocks, int nb) {
   BZ_HIP(hipMemcpyAsync(e->g->pos + row, &mi->pos, 4, hipMemcpyHostToDevice, st));
   if (e->sampler) BZ_TRY(bzk_batch_sampler_stage_row(st, e->sampler, row, &q.rq.sampling, q.prompt.data(), n, 0, s->host + e->off_bs));
   if (e->cursor) BZ_TRY(bzk_grammar_cursor_stage_row(st, e->cursor, row, q.rq.grammar_state, mi->gram));
+  if (e->cfg.logprobs) BZ_TRY(bzk_lp_stage_row(st, e->sampler, row, q.top_n, q.bias_ids.data(), q.bias_vals.data(), (int)q.bias_ids.size(), s->host + e->off_lp));
   BZ_HIP(hipMemcpyAsync(e->d_rows + row, &mi->er, sizeof(EngRow), hipMemcpyHostToDevice, st));
   BZ_TRY(eng_stage_done(e, s));
   q.live = true; q.first_replay = e->g->replays;
@@ -478,6 +507,16 @@ extern "C" int bz_engine_poll(bz_engine* e, bz_engine_event* out, int max_events
   if (!e || !n_out || (max_events > 0 && !out) || max_events < 0) BZ_FAIL(BZ_E_INVALID, "engine poll: bad argument");
   int n = 0;
   while (n < max_events && !e->events.empty()) { out[n++] = e->events.front(); e->events.pop_front(); }
+  *n_out = n;
+  return BZ_OK;
+  BZ_API_END
+}
+
+extern "C" int bz_engine_poll_logprobs(bz_engine* e, bz_engine_logprobs* out, int max_records, int* n_out) {
+  BZ_API_BEGIN
+  if (!e || !n_out || (max_records > 0 && !out) || max_records < 0) BZ_FAIL(BZ_E_INVALID, "engine poll_logprobs: bad argument");
+  int n = 0;
+  while (n < max_records && !e->lp_events.empty()) { out[n++] = e->lp_events.front(); e->lp_events.pop_front(); }
   *n_out = n;
   return BZ_OK;
   BZ_API_END

@@ -3090,7 +3090,7 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
   BZ_TRY(prefill_ws(m, N));                      // workspace before the capture (allocation synchronises)
   Owned<bz_batch_graph, bz_decode_batch_graph_free> g(new bz_batch_graph());
   bz_dev_retain(m->dev); g->dev = m->dev;
-  g->m = m; g->kv = kv; g->N = N; g->max_blocks = max_blocks; g->capacity = capacity; g->host_pos.assign(N, -1);
+  g->m = m; g->kv = kv; g->sampler = s; g->N = N; g->max_blocks = max_blocks; g->capacity = capacity; g->host_pos.assign(N, -1);
   if (hipMalloc(&g->tok, (size_t)N * 8) != hipSuccess || hipMalloc(&g->next, (size_t)N * 8) != hipSuccess || hipMalloc(&g->pos, (size_t)N * 4) != hipSuccess ||
       hipMalloc(&g->slot, (size_t)N * 4) != hipSuccess || hipMalloc(&g->row_lora, (size_t)N * 4) != hipSuccess || hipMalloc(&g->table, (size_t)N * max_blocks * 4) != hipSuccess || hipMalloc(&g->step, 64) != hipSuccess ||
       hipHostMalloc(&g->log, sizeof(long long) * bz_batch_graph::LOGCAP * N, hipHostMallocDefault) != hipSuccess)
@@ -3107,13 +3107,20 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
     else BZ_TRY(bzk_batch_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N));
     RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity; rcx.row_lora = g->row_lora;
     BZ_TRY(prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, rcx));
+    // a sampler with bz_batch_sampler_enable (sampling.rs:414-431): logprobs on the raw rows, mask, bias, pick, records; without it none of the three launches anything
+    if (s) BZ_TRY(bzk_lp_pre(cap, s, (const float*)g->logits->ptr));
     if (c) BZ_TRY(bzk_grammar_mask_rows(cap, c, (float*)g->logits->ptr));
+    if (s) BZ_TRY(bzk_lp_bias(cap, s, (float*)g->logits->ptr));
     if (s) BZ_TRY(bzk_batch_sample(cap, s, (const float*)g->logits->ptr, nullptr, g->next, g->log, g->step, bz_batch_graph::LOGCAP));
     else BZ_TRY(bzk_batch_argmax(cap, (const float*)g->logits->ptr, m->cfg.vocab, g->next, g->log, g->step, bz_batch_graph::LOGCAP, N));
+    if (s) BZ_TRY(bzk_lp_post(cap, s, (const float*)g->logits->ptr, g->next, g->step));
     if (c) BZ_TRY(bzk_grammar_advance_rows(cap, c, g->next));
-    if (er)
+    if (er) {
+      int* bias_cnt = nullptr; int* lp_top_n = nullptr;
+      bzk_lp_row_ptrs(s, &bias_cnt, &lp_top_n);
       BZ_TRY(bzk_engine_finish(cap, er->rows, g->next, g->pos, g->table, max_blocks, g->step, bz_batch_graph::LOGCAP, N, er->status, er->nlive, c ? bzk_grammar_cursor_states(c) : nullptr,
-                               m->lora ? g->row_lora : nullptr));
+                               m->lora ? g->row_lora : nullptr, bias_cnt, lp_top_n));
+    }
     return BZ_OK;
   };
   BZ_TRY(capture_graph(body, &g->graph, &g->exec));

@@ -353,6 +353,23 @@ int bzk_sample_free(void* ws);
 // token log [logcap][N] and step counter -- the last launch writes them as bzk_batch_argmax does
 int bzk_batch_sample(hipStream_t s, bz_batch_sampler* bs, const float* logits, long long* tokens_out, long long* next, long long* log, int* step, int logcap);
 int bzk_batch_sampler_dims(const bz_batch_sampler* bs, int* N, long long* V);
+// per-row logit bias and logprobs (bz_logprobs.hip): state that hangs off the sampler handle (null until bz_batch_sampler_enable) and the three places of a step --
+// pre on the raw logits (before the grammar mask), bias after the mask, post after the pick (tokens [N] device; step nullable: the graph's counter, already
+// advanced by the pick).  Each launches nothing on a sampler without the flag.
+struct BzLpState;
+BzLpState*& bzk_batch_sampler_lp(bz_batch_sampler* bs);
+bz_device* bzk_batch_sampler_dev(const bz_batch_sampler* bs);
+bool bzk_batch_sampler_used(const bz_batch_sampler* bs);        // has sampled or been captured
+void bzk_lp_free(BzLpState* lp);
+unsigned bzk_lp_flags(bz_batch_sampler* bs);
+const bz_logprobs_record* bzk_lp_ring(bz_batch_sampler* bs);   // pinned [LOGCAP][N]; nullptr without BZ_BS_LOGPROBS
+void bzk_lp_row_ptrs(bz_batch_sampler* bs /*nullable*/, int** b_cnt, int** top_n);   // device [N] each, nullptr without the flag (k_engine_finish clears a row that ends)
+int bzk_lp_pre(hipStream_t s, bz_batch_sampler* bs, const float* logits);
+int bzk_lp_bias(hipStream_t s, bz_batch_sampler* bs, float* logits);
+int bzk_lp_post(hipStream_t s, bz_batch_sampler* bs, const float* logits, const long long* tokens, const int* step);
+int bzk_lp_check_bias(long long V, const uint32_t* ids, const float* vals, int n, std::vector<uint32_t>& ids_out, std::vector<float>& vals_out, const char* who);
+size_t bzk_lp_stage_bytes();
+int bzk_lp_stage_row(hipStream_t st, bz_batch_sampler* bs, int row, int top_n, const uint32_t* ids, const float* vals, int cnt, void* stage);
 // per-row grammar cursor (bz_grammar.hip): the two launches a captured step takes, on the stream it is captured on
 int bzk_grammar_cursor_dims(const bz_grammar_cursor* c, int* N, long long* V, bz_device** dev);
 int bzk_grammar_mask_rows(hipStream_t s, bz_grammar_cursor* c, float* logits /*[N,V]*/);
@@ -380,6 +397,7 @@ int bzk_batch_argmax(hipStream_t s, const float* logits, int V, long long* next,
 // The batched decode graph (bz_host.hip); the request engine (bz_engine.hip) drives one through its buffers.
 struct bz_batch_graph {
   bz_model* m = nullptr; bz_device* dev = nullptr; bz_paged_kv* kv = nullptr;
+  bz_batch_sampler* sampler = nullptr;   // borrowed (nullptr: argmax); its logprobs ring is read through the graph
   hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
   int N = 0, max_blocks = 0, capacity = 0;
   long long* tok = nullptr; long long* next = nullptr; int* pos = nullptr; int* slot = nullptr; int* table = nullptr; int* step = nullptr;
@@ -398,7 +416,8 @@ struct BzEngineRows { EngRow* rows; int* status; int* nlive; };
 enum { ENG_IDLE = 0, ENG_TOKEN = 1, ENG_FINISHED = 2 };   // status word: low 2 bits; a finished row's reason (0 length, 1 stop) sits in bits 2..
 int bzk_engine_advance(hipStream_t s, long long* tok, const long long* next, int* pos, int* slot, const int* table, int stride, int bs, int N, const EngRow* rows);
 int bzk_engine_finish(hipStream_t s, EngRow* rows, const long long* next, int* pos, int* table, int stride, const int* step, int logcap, int N, int* status,
-                      int* nlive, uint32_t* gstate /*nullable: the grammar cursor's states*/, int* row_lora /*nullable: a row that ends gets LoRA slot -1*/);
+                      int* nlive, uint32_t* gstate /*nullable: the grammar cursor's states*/, int* row_lora /*nullable: a row that ends gets LoRA slot -1*/,
+                      int* bias_cnt = nullptr /*nullable: a row that ends gets an empty bias list*/, int* lp_top_n = nullptr /*nullable: ... and logprobs off*/);
 // what the engine needs of bz_host.hip: the capture with the row life cycle in it, a launch under the model's lock, the model's device, the prompt workspace
 int bzk_kv_copy_slots(hipStream_t s, bz_paged_kv* kv, const int* d_triples, int n, int max_j);
 int bzi_engine_capture(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_grammar_cursor* c, const BzEngineRows* er, bz_batch_graph** out);

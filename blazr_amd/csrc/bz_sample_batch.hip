@@ -384,12 +384,18 @@ __global__ __launch_bounds__(256) void k_bs_select(BsArgs a, int L, int phase) {
 struct bz_batch_sampler {
   bz_device* dev = nullptr;
   BsArgs a{};
+  BzLpState* lp = nullptr;   // per-row logit bias / logprobs (bz_logprobs.hip), after bz_batch_sampler_enable
+  bool used = false;         // has sampled or been captured: too late to enable
 };
+BzLpState*& bzk_batch_sampler_lp(bz_batch_sampler* s) { return s->lp; }
+bz_device* bzk_batch_sampler_dev(const bz_batch_sampler* s) { return s->dev; }
+bool bzk_batch_sampler_used(const bz_batch_sampler* s) { return s->used; }
 
 int bzk_batch_sampler_dims(const bz_batch_sampler* s, int* N, long long* V) { *N = s->a.N; *V = s->a.V; return BZ_OK; }
 
 // the 21 launches; next / log / step (nullable) are the batch graph's feedback buffer, pinned token log [logcap][N] and step counter
 int bzk_batch_sample(hipStream_t st, bz_batch_sampler* s, const float* logits, long long* tokens_out, long long* next, long long* log, int* step, int logcap) {
+  s->used = true;
   BsArgs a = s->a;
   a.logits = logits; a.tokens_out = tokens_out; a.next = next; a.log = log; a.step = step; a.logcap = logcap > 0 ? logcap : 1;
   const dim3 rows(a.N), grid(NB, a.N), blk(256);
@@ -417,6 +423,7 @@ extern "C" int bz_batch_sampler_free(bz_batch_sampler* s) {
   BsArgs& a = s->a;
   for (void* p : {(void*)a.rows, (void*)a.scr, (void*)a.l2, (void*)a.pmax, (void*)a.psum, (void*)a.amv, (void*)a.ami, (void*)a.pen_id, (void*)a.pen_cnt,
                   (void*)a.h1c, (void*)a.h1m, (void*)a.hc, (void*)a.hm, (void*)a.hrep}) if (p) hipFree(p);
+  bzk_lp_free(s->lp);
   if (s->dev) bz_dev_release(s->dev);
   delete s;
   return BZ_OK;
@@ -505,6 +512,11 @@ extern "C" int bz_batch_sampler_sample(bz_batch_sampler* s, const bz_tensor* log
   if (tokens_out->dtype != BZ_I64 || tokens_out->nbytes != N * 8) BZ_FAIL(BZ_E_INVALID, "batch sampler sample: tokens_out must be I64 [%zu] (got dtype %d, %zu bytes)", N, tokens_out->dtype, tokens_out->nbytes);
   std::lock_guard<std::mutex> dlock__(s->dev->mu);
   BZ_HIP(hipSetDevice(s->dev->id));
-  return bzk_batch_sample(s->dev->stream, s, (const float*)logits->ptr, (long long*)tokens_out->ptr, nullptr, nullptr, nullptr, 0);
+  // with bz_batch_sampler_enable: logprobs phase A on the raw rows, the bias in place, the pick, the records (nothing is launched for a flag that is off)
+  hipStream_t st = s->dev->stream;
+  BZ_TRY(bzk_lp_pre(st, s, (const float*)logits->ptr));
+  BZ_TRY(bzk_lp_bias(st, s, (float*)logits->ptr));
+  BZ_TRY(bzk_batch_sample(st, s, (const float*)logits->ptr, (long long*)tokens_out->ptr, nullptr, nullptr, nullptr, 0));
+  return bzk_lp_post(st, s, (const float*)logits->ptr, (const long long*)tokens_out->ptr, nullptr);
   BZ_API_END
 }

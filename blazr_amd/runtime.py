@@ -1007,6 +1007,21 @@ class GrammarCursor:
         L.check(L.lib().bz_grammar_cursor_advance(self.h, tokens.h))
 
 
+def _bias_arrays(logit_bias):
+    items = list(logit_bias.items()) if isinstance(logit_bias, dict) else list(logit_bias or ())
+    return (np.ascontiguousarray([int(i) for i, _ in items], dtype=np.uint32), np.ascontiguousarray([float(v) for _, v in items], dtype=np.float32))
+
+
+def _logprobs_record(r):
+    if r.n_top < 0:
+        return None
+    d = dict(token=int(r.token), logprob=float(np.float32(r.logprob)), top_ids=[int(t) for t in r.top_ids[:r.n_top]],
+             top_logprobs=[float(np.float32(v)) for v in r.top_logprobs[:r.n_top]])
+    if hasattr(r, "lse"):
+        d["lse"] = float(np.float32(r.lse))
+    return d
+
+
 class BatchSampler:
     """Per-sequence sampling for a decode batch (batch_decode.rs:149-168: logits_to_token_on_device once per sequence with its own gen_config) as one
     device-side call: every row keeps its parameters, the ring of its last tokens (the penalty window of sampling.rs:169-191) and its draw index on the device."""
@@ -1032,10 +1047,30 @@ class BatchSampler:
         L.check(L.lib().bz_batch_sampler_set_row(self.h, int(row), C.byref(p), _ptr(hist) if len(hist) else None, len(hist), int(draw_index)))
 
     def sample(self, logits, out=None):
-        """logits F32 [n, vocab] (device tensor) -> I64 [n] device tensor; enqueued on the device stream."""
+        """logits F32 [n, vocab] (device tensor) -> I64 [n] device tensor; enqueued on the device stream.  With enable(bias=True) the rows' biases are added
+        to `logits` in place."""
         out = self.dev.zeros((self.n,), L.I64) if out is None else out
         L.check(L.lib().bz_batch_sampler_sample(self.h, logits.h, out.h))
         return out
+
+    def enable(self, bias=False, logprobs=False):
+        """Per-row logit bias and / or logprobs (GenerationConfig.logit_bias, logprobs, top_logprobs per sequence), once, before the first sample or capture."""
+        L.check(L.lib().bz_batch_sampler_enable(self.h, (L.BS_BIAS if bias else 0) | (L.BS_LOGPROBS if logprobs else 0)))
+
+    def set_row_bias(self, row, logit_bias=None):
+        """logit_bias: {id: bias} or a sequence of (id, bias) pairs (the last entry of an id wins, ids beyond the vocabulary are dropped); None / empty clears the row."""
+        ids, vals = _bias_arrays(logit_bias)
+        L.check(L.lib().bz_batch_sampler_set_row_bias(self.h, int(row), _ptr(ids) if len(ids) else None, _ptr(vals) if len(vals) else None, len(ids)))
+
+    def set_row_logprobs(self, row, top_n):
+        """top_n: -1 (or None) = off, 0..20 = the picked token's logprob plus that many alternatives."""
+        L.check(L.lib().bz_batch_sampler_set_row_logprobs(self.h, int(row), -1 if top_n is None else int(top_n)))
+
+    def read_logprobs(self):
+        """The records of the last sample() call, one dict per row (None for a row with logprobs off); waits for the stream."""
+        recs = (L.LogprobsRecord * self.n)()
+        L.check(L.lib().bz_batch_sampler_read_logprobs(self.h, recs))
+        return [_logprobs_record(r) for r in recs]
 
 
 class BatchDecodeGraph:
@@ -1093,6 +1128,12 @@ class BatchDecodeGraph:
         out = np.empty(self.n, dtype=np.int64)
         L.check(L.lib().bz_decode_batch_graph_read_tokens(self.h, int(step), _ptr(out)))
         return out
+
+    def read_logprobs(self, step):
+        """The records of replay `step` (sampler.enable(logprobs=True) before the capture), one dict per row, None for a row with logprobs off."""
+        recs = (L.LogprobsRecord * self.n)()
+        L.check(L.lib().bz_decode_batch_graph_read_logprobs(self.h, int(step), recs))
+        return [_logprobs_record(r) for r in recs]
 
     def read_logits(self):
         t = C.c_void_p()
@@ -1171,15 +1212,19 @@ class BatchEngine:
     come and go while the captured step keeps running; the caller drives with step().  sampler=True: every request samples with its own parameters
     (the keyword arguments of BatchSampler.set_row); grammar: a GrammarCursor of n_rows rows, borrowed (its rows are handed out by the engine)."""
 
-    def __init__(self, model, n_rows, num_blocks, block_size=16, max_seq_len=None, prefill_chunk=0, depth=2, sampler=True, grammar=None, prefix_cache=False):
+    def __init__(self, model, n_rows, num_blocks, block_size=16, max_seq_len=None, prefill_chunk=0, depth=2, sampler=True, grammar=None, prefix_cache=False,
+                 logprobs=False):
+        """logprobs=True (needs sampler=True): requests may ask for logprobs / top_logprobs and carry a logit_bias; the records arrive in `logprobs`."""
         cfg = L.EngineConfig(n_rows=int(n_rows), num_blocks=int(num_blocks), block_size=int(block_size),
                              max_seq_len=int(max_seq_len if max_seq_len is not None else model.c.max_seq_len), prefill_chunk=int(prefill_chunk), depth=int(depth),
-                             use_sampler=1 if sampler else 0, prefix_cache=int(prefix_cache))
+                             use_sampler=1 if sampler else 0, prefix_cache=int(prefix_cache), logprobs=int(bool(logprobs)))
         h = C.c_void_p()
         L.check(L.lib().bz_engine_create(model.h, C.byref(cfg), grammar.h if grammar is not None else None, C.byref(h)))
         self.h, self.model, self.grammar, self.n_rows = h, model, grammar, int(n_rows)
         self._events = (L.EngineEvent * 256)()
+        self._lp = (L.EngineLogprobs * 256)()
         self.results = {}
+        self.logprobs = {}    # id -> the per-token records of a request that asked for logprobs (filled by run_until_idle / collect_logprobs)
 
     def __del__(self):
         try:
@@ -1188,8 +1233,9 @@ class BatchEngine:
         except Exception:
             pass
 
-    def submit(self, prompt, max_tokens, stop=(), grammar_state=None, lora=None, **sampling):
-        """lora: a name registered with model.load_lora (GenerationConfig.lora_adapter per request); None: the base model"""
+    def submit(self, prompt, max_tokens, stop=(), grammar_state=None, lora=None, logprobs=False, top_logprobs=0, logit_bias=None, **sampling):
+        """lora: a name registered with model.load_lora (GenerationConfig.lora_adapter per request); None: the base model.
+        logprobs / top_logprobs / logit_bias (GenerationConfig.logprobs, top_logprobs 0..20, logit_bias {id: bias}): on an engine with logprobs=True."""
         p = np.ascontiguousarray(prompt, dtype=np.int64).reshape(-1)
         stop = [int(t) for t in stop]
         rq = L.Request(max_tokens=int(max_tokens), n_stop=len(stop), grammar_state=L.GRAMMAR_ROW_FREE if grammar_state is None else int(grammar_state),
@@ -1200,7 +1246,13 @@ class BatchEngine:
         kw.update(sampling)
         rq.sampling = L.RowSampling(**kw)
         rid = C.c_int64()
-        L.check(L.lib().bz_engine_submit(self.h, _ptr(p), len(p), C.byref(rq), C.byref(rid)))
+        if logprobs or top_logprobs or logit_bias is not None:
+            ids, vals = _bias_arrays(logit_bias)
+            ex = L.RequestExtras(logprobs=int(bool(logprobs)), top_logprobs=int(top_logprobs), n_logit_bias=len(ids),
+                                 logit_bias_ids=ids.ctypes.data if len(ids) else None, logit_bias_vals=vals.ctypes.data if len(vals) else None)
+            L.check(L.lib().bz_engine_submit_ex(self.h, _ptr(p), len(p), C.byref(rq), C.byref(ex), C.byref(rid)))
+        else:
+            L.check(L.lib().bz_engine_submit(self.h, _ptr(p), len(p), C.byref(rq), C.byref(rid)))
         return rid.value
 
     def cancel(self, rid):
@@ -1221,6 +1273,25 @@ class BatchEngine:
             out += [(e.id, e.token, e.index, e.finish_reason, e.replay) for e in self._events[:n.value]]
             if n.value < len(self._events):
                 return out
+
+    def poll_logprobs(self):
+        """[{id, index, token, logprob, top_ids, top_logprobs}] since the last call: one per token event of a request that asked for logprobs, in event order."""
+        out = []
+        while True:
+            n = C.c_int()
+            L.check(L.lib().bz_engine_poll_logprobs(self.h, self._lp, len(self._lp), C.byref(n)))
+            for r in self._lp[:n.value]:
+                d = _logprobs_record(r) or dict(token=int(r.token), logprob=float("nan"), top_ids=[], top_logprobs=[])
+                d.update(id=int(r.id), index=int(r.index))
+                out.append(d)
+            if n.value < len(self._lp):
+                return out
+
+    def collect_logprobs(self):
+        """Fold poll_logprobs() into self.logprobs {id: [records]}; returns it."""
+        for d in self.poll_logprobs():
+            self.logprobs.setdefault(d["id"], []).append(d)
+        return self.logprobs
 
     def stats(self):
         s = L.EngineStats()
@@ -1264,6 +1335,7 @@ class BatchEngine:
         while busy:
             busy = self.step()
             self.collect(self.poll(), res)
+        self.collect_logprobs()
         return {k: (v[0], v[1]) for k, v in res.items()}
 
 

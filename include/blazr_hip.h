@@ -288,6 +288,32 @@ int bz_batch_sampler_sample(bz_batch_sampler* s, const bz_tensor* logits, bz_ten
  * N or V differ from the graph's.  seed / replay / read_tokens / set_block_table / logits / free work unchanged; bz_batch_sampler_set_row between replays
  * reconfigures a row without a recapture.  The graph borrows the sampler: free the graph first. */
 int bz_decode_batch_graph_capture_sampled(bz_model* m, bz_paged_kv* kv, int N, int max_blocks, bz_batch_sampler* s, bz_batch_graph** out);
+/* Per-row logit bias and logprobs on the device (config/generation.rs:65-74 logit_bias / logprobs / top_logprobs per sequence of a batch; the reference's batched
+ * path reports none: batch_engine.rs:305,429).  Opt-in per sampler: bz_batch_sampler_enable(flags) once, before the first sample or capture, allocates the
+ * state; a sampler without it launches exactly what it launched before.  Order in a step (sampling.rs:414-431): logprobs phase A on the raw logits -> grammar
+ * mask -> bias -> penalties / temperature / pick -> logprobs phase C.  New symbols only: BZ_ABI_VERSION is unchanged.
+ *   bias (BZ_BS_BIAS): per row at most BZ_LOGIT_BIAS_MAX unique in-range (id, bias) entries.  set_row_bias dedupes on the host as bz_apply_logit_bias does (the
+ *     last entry of an id wins, ids >= V are dropped: bz_logit_bias_dedupe is that step on its own, host only, outputs of n entries each); a non-finite bias, or
+ *     more than BZ_LOGIT_BIAS_MAX entries after that, is BZ_E_INVALID naming the figure.  One launch adds the biases to the logits IN PLACE (the logits tensor of
+ *     bz_batch_sampler_sample / the graph's logits show the biased rows) and keeps the raw values of those entries; -inf + bias stays -inf.
+ *   logprobs (BZ_BS_LOGPROBS): per row top_n = -1 (off, the default) or 0..BZ_TOP_LOGPROBS_MAX.  On the row x as the lm_head wrote it (sampling.rs:197-256), with
+ *     M = max x, e_i = the specified exp of x_i - M, q_i = floor(e_i * 2^40) as a 64-bit integer, S = sum q_i (exact in any order), lse = (float)log(S * 2^-40) + M:
+ *     logprob of id i = x_i - lse in f32; top = the first min(top_n, V, 20) ids in (x descending, id ascending) order (NaN logits are never listed).
+ *     One record per row and step: token, its logprob (from the RAW logit, whatever mask and bias did), lse, n_top (-1: the row has logprobs off, nothing else
+ *     in the record is written), the top ids and their logprobs.
+ *   set_row_bias / set_row_logprobs are stream-ordered and take effect at the next sample or replay without a recapture; BZ_E_INVALID on a sampler that did not
+ *     enable the flag.  read_logprobs: the N records of the last bz_batch_sampler_sample call (waits for the stream).  bz_decode_batch_graph_read_logprobs: the
+ *     N records of replay `step`, the companion of read_tokens (a pinned ring beside the token log, same range of steps). */
+#define BZ_LOGIT_BIAS_MAX 512
+#define BZ_TOP_LOGPROBS_MAX 20
+enum { BZ_BS_BIAS = 1, BZ_BS_LOGPROBS = 2 };
+typedef struct { int64_t token; float logprob; float lse; int32_t n_top; uint32_t top_ids[BZ_TOP_LOGPROBS_MAX]; float top_logprobs[BZ_TOP_LOGPROBS_MAX]; } bz_logprobs_record;
+int bz_logit_bias_dedupe(int64_t V, const uint32_t* ids, const float* vals, int n, uint32_t* ids_out, float* vals_out, int* n_out);
+int bz_batch_sampler_enable(bz_batch_sampler* s, uint32_t flags);
+int bz_batch_sampler_set_row_bias(bz_batch_sampler* s, int row, const uint32_t* ids, const float* vals, int n);
+int bz_batch_sampler_set_row_logprobs(bz_batch_sampler* s, int row, int top_n);
+int bz_batch_sampler_read_logprobs(bz_batch_sampler* s, bz_logprobs_record* out /*[N]*/);
+int bz_decode_batch_graph_read_logprobs(bz_batch_graph* g, int64_t step, bz_logprobs_record* out /*[N]*/);
 
 /* ---- host decode loop (Executor::generate contiguous branch, executor_generate.rs:341-410) ---------------- */
 typedef struct {
@@ -522,7 +548,8 @@ typedef struct {
   int32_t depth;           /* replays in flight before the oldest record is read, 1..64 */
   int32_t use_sampler;     /* 1: the batched sampler picks (per-request parameters); 0: greedy argmax */
   int32_t prefix_cache;    /* 1: the prefix cache (shared prompt blocks, copy-on-write); 0: off (took the first reserved word) */
-  int32_t reserved[8];
+  int32_t logprobs;        /* 1: the engine's sampler is created with BZ_BS_BIAS | BZ_BS_LOGPROBS (needs use_sampler = 1); 0: off (took a reserved word) */
+  int32_t reserved[7];
 } bz_engine_config;
 typedef struct {
   int32_t max_tokens;
@@ -538,6 +565,15 @@ typedef struct { int64_t replays; int32_t free_blocks, total_blocks, park_blocks
 typedef struct bz_engine bz_engine;
 int bz_engine_create(bz_model* m, const bz_engine_config* cfg, bz_grammar_cursor* cursor /*nullable, borrowed*/, bz_engine** out);
 int bz_engine_submit(bz_engine* e, const int64_t* prompt, int n_prompt, const bz_request* rq, int64_t* id_out);
+/* Per-request logit bias and logprobs (config/generation.rs:65-74), on an engine created with logprobs = 1 (else a non-NULL `ex` is BZ_E_INVALID).
+ * bz_engine_submit is bz_engine_submit_ex with ex = NULL.  logprobs != 0: every token of the request gets a record with top_logprobs (0..20) alternatives;
+ * logit_bias_*: n_logit_bias entries, checked and deduplicated as bz_batch_sampler_set_row_bias does.  The row's bias list and top_n are written with the other
+ * row writes when the request goes live and cleared on the device when the row goes idle.  poll_logprobs: one entry per token event of a request that asked,
+ * in event order (same id / index / token), harvested from the ring with the token record of the same replay; a cancelled request's entries are dropped. */
+typedef struct { int32_t logprobs; int32_t top_logprobs; int32_t n_logit_bias; const uint32_t* logit_bias_ids; const float* logit_bias_vals; int32_t reserved[4]; } bz_request_extras;
+typedef struct { int64_t id; int32_t index; int64_t token; float logprob; int32_t n_top; uint32_t top_ids[BZ_TOP_LOGPROBS_MAX]; float top_logprobs[BZ_TOP_LOGPROBS_MAX]; } bz_engine_logprobs;
+int bz_engine_submit_ex(bz_engine* e, const int64_t* prompt, int n_prompt, const bz_request* rq, const bz_request_extras* ex /*nullable*/, int64_t* id_out);
+int bz_engine_poll_logprobs(bz_engine* e, bz_engine_logprobs* out, int max_records, int* n_out);
 int bz_engine_cancel(bz_engine* e, int64_t id);
 int bz_engine_step(bz_engine* e, int* busy_out);
 int bz_engine_poll(bz_engine* e, bz_engine_event* out, int max_events, int* n_out);

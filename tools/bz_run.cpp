@@ -81,7 +81,8 @@ static int setup_lora(bz_device* dev, bz_model* m, const std::vector<std::string
 }
 
 int main(int argc, char** argv) {
-  if (argc < 2) { fprintf(stderr, "usage: bz-run <model path> --prompt id,id,... [--max-tokens N] [--graphs] [--paged-attention] ...\n"); return 2; }
+  if (argc < 2) { fprintf(stderr, "usage: bz-run <model path> --prompt id,id,... [--max-tokens N] [--graphs] [--paged-attention] ...\n"
+                            "       bz-run <model path> --requests FILE --rows N [--logprobs K] [--logit-bias id:val,...] ...\n"); return 2; }
   std::string model = argv[1];
   std::vector<int64_t> prompt;
   bz_gen_config gc;
@@ -93,6 +94,7 @@ int main(int argc, char** argv) {
   std::string draft_path; bz_spec_config sc;
   std::string requests_path; int rows = 0, pool_blocks = 0, prefill_chunk = 0, depth = 2; bool prefix_cache = false;
   std::vector<std::string> lora_paths; std::string lora_targets; std::vector<bz_lora*> loras;
+  int logprobs = -1; std::vector<uint32_t> bias_ids; std::vector<float> bias_vals;   // --requests: every request asks for K alternatives / carries this bias
   memset(&sc, 0, sizeof sc);
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
@@ -122,6 +124,19 @@ int main(int argc, char** argv) {
     else if (a == "--prefill-chunk") prefill_chunk = atoi(next("--prefill-chunk"));
     else if (a == "--depth") depth = atoi(next("--depth"));
     else if (a == "--prefix-cache") prefix_cache = true;
+    else if (a == "--logprobs") logprobs = atoi(next("--logprobs"));
+    else if (a == "--logit-bias") {
+      const char* q = next("--logit-bias"); char* end;
+      while (*q) {
+        const unsigned long id = strtoul(q, &end, 10);
+        if (end == q || *end != ':') { fprintf(stderr, "bz-run: --logit-bias takes id:val,id:val,...\n"); return 2; }
+        q = end + 1;
+        const float v = strtof(q, &end);
+        if (end == q) { fprintf(stderr, "bz-run: --logit-bias takes id:val,id:val,...\n"); return 2; }
+        bias_ids.push_back((uint32_t)id); bias_vals.push_back(v);
+        q = *end == ',' ? end + 1 : end;
+      }
+    }
     else if (a == "--lora") lora_paths.push_back(next("--lora"));
     else if (a == "--lora-targets") lora_targets = next("--lora-targets");
     else { fprintf(stderr, "bz-run: unknown option %s\n", a.c_str()); return 2; }
@@ -162,7 +177,9 @@ int main(int argc, char** argv) {
     const int per = (ec.max_seq_len + ec.block_size - 1) / ec.block_size;
     ec.num_blocks = pool_blocks > 0 ? pool_blocks : rows * per + rows;       // one park block per row on top
     const bool greedy = gc.temperature == 0.0f && gc.repeat_penalty == 1.0f && gc.frequency_penalty == 0.0f && gc.presence_penalty == 0.0f;
-    ec.use_sampler = greedy ? 0 : 1;
+    const bool extras = logprobs >= 0 || !bias_ids.empty();                  // bias and logprobs live in the batched sampler
+    ec.use_sampler = greedy && !extras ? 0 : 1;
+    ec.logprobs = extras ? 1 : 0;
     ec.prefix_cache = prefix_cache ? 1 : 0;
     if (int rc = setup_lora(dev, m, lora_paths, lora_targets, loras)) return rc;     // before the engine captures its step
     bz_engine* e = nullptr;
@@ -177,7 +194,11 @@ int main(int argc, char** argv) {
       rq.sampling.repeat_penalty = gc.repeat_penalty; rq.sampling.frequency_penalty = gc.frequency_penalty; rq.sampling.presence_penalty = gc.presence_penalty;
       rq.sampling.repeat_last_n = gc.repeat_last_n; rq.sampling.seed = gc.seed + i;
       int64_t id = -1;
-      if (bz_engine_submit(e, reqs[i].prompt.data(), (int)reqs[i].prompt.size(), &rq, &id) != BZ_OK) return fail("submit");
+      bz_request_extras ex;
+      memset(&ex, 0, sizeof ex);
+      ex.logprobs = logprobs >= 0; ex.top_logprobs = logprobs >= 0 ? logprobs : 0;
+      ex.n_logit_bias = (int32_t)bias_ids.size(); ex.logit_bias_ids = bias_ids.data(); ex.logit_bias_vals = bias_vals.data();
+      if (bz_engine_submit_ex(e, reqs[i].prompt.data(), (int)reqs[i].prompt.size(), &rq, extras ? &ex : nullptr, &id) != BZ_OK) return fail("submit");
       if (id != (int64_t)i) { fprintf(stderr, "bz-run: request %zu got id %lld\n", i, (long long)id); return 1; }
     }
     int busy = 1;
@@ -189,6 +210,17 @@ int main(int argc, char** argv) {
         if (bz_engine_poll(e, ev, 256, &n) != BZ_OK) return fail("poll");
         for (int k = 0; k < n; k++) if (ev[k].token >= 0) reqs[(size_t)ev[k].id].out.push_back(ev[k].token);
       } while (n == 256);
+      if (logprobs >= 0) {
+        static bz_engine_logprobs lp[64];
+        do {
+          if (bz_engine_poll_logprobs(e, lp, 64, &n) != BZ_OK) return fail("poll logprobs");
+          for (int k = 0; k < n; k++) {
+            fprintf(stderr, "logprobs: request %lld token %d = %lld %.6f", (long long)lp[k].id, lp[k].index, (long long)lp[k].token, (double)lp[k].logprob);
+            for (int j = 0; j < lp[k].n_top; j++) fprintf(stderr, "%s%u:%.6f", j ? "," : " top ", lp[k].top_ids[j], (double)lp[k].top_logprobs[j]);
+            fprintf(stderr, "\n");
+          }
+        } while (n == 64);
+      }
     }
     for (const Req& r : reqs) {
       for (size_t k = 0; k < r.out.size(); k++) printf(k ? ",%lld" : "%lld", (long long)r.out[k]);
