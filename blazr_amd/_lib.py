@@ -178,6 +178,10 @@ class EngineEvent(C.Structure):
     _fields_ = [("id", C.c_int64), ("token", C.c_int64), ("index", C.c_int32), ("finish_reason", C.c_int32), ("replay", C.c_int64)]
 
 
+class RowsAttnPlan(C.Structure):
+    _fields_ = [("kernel", C.c_int), ("scalar_limit", C.c_int), ("grid_slices", C.c_int), ("rows_per_pass", C.c_int), ("ws_bytes", C.c_size_t)]
+
+
 class EngineStats(C.Structure):
     _fields_ = [("replays", C.c_int64), ("free_blocks", C.c_int32), ("total_blocks", C.c_int32), ("park_blocks", C.c_int32), ("live_rows", C.c_int32),
                 ("admitted", C.c_int32), ("waiting", C.c_int32), ("unread", C.c_int32), ("prompt_tokens", C.c_int64), ("generated_tokens", C.c_int64),
@@ -224,6 +228,7 @@ SYMBOLS = {
     "bz_paged_kv_seq_len": (C.c_int, [P]),
     "bz_paged_kv_copy_slots": (C.c_int, [P, C.c_int, C.c_int, C.c_int]),
     "bz_paged_kv_read_block": (C.c_int, [P, C.c_int, C.c_int, C.c_int, P, C.c_size_t]),
+    "bz_paged_kv_write_block": (C.c_int, [P, C.c_int, C.c_int, C.c_int, P, C.c_size_t]),
     "bz_forward_kv": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.c_uint32]),
     "bz_forward_paged": (C.c_int, [P, P, C.c_int, P, P, P, C.c_int, C.c_int, C.c_int, P, C.c_uint32]),
     "bz_forward_embed": (C.c_int, [P, P, C.c_int, P]),
@@ -300,6 +305,9 @@ SYMBOLS = {
     "bz_silu_mul": (C.c_int, [P, P, P, C.c_int64, C.c_int, P]),
     "bz_attn_decode": (C.c_int, [P, P, P, C.c_int, C.c_int, P]),
     "bz_paged_attn_decode": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P]),
+    "bz_paged_attn_decode_rows": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P]),
+    "bz_rows_attn_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P]),
+    "bz_rows_attn_slice_len": (C.c_int, [C.c_int]),
     "bz_kv_insert": (C.c_int, [P, P, C.c_int, C.c_int, P, P]),
     "bz_rope_caches": (C.c_int, [P, P, P]),
     "bz_grammar_compile": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(P)]),

@@ -315,6 +315,7 @@ struct bz_model {
   // batched-prefill workspace (bz_prefill.hip), allocated on first use for `pf_rows` prompt rows
   int pf_rows = 0; float* pf_h = nullptr; float* pf_t = nullptr; float* pf_qkv = nullptr; float* pf_gu = nullptr; void* pf_x16 = nullptr;
   int* row_pos = nullptr; int row_pos_n = 0;   // device copy of a decode batch's per-row positions
+  float* rows_ws = nullptr; size_t rows_ws_bytes = 0;   // split-KV partials of a decode batch beyond the scalar attention's limit (bz_rows_attn.hip)
   long long* pf_acc = nullptr;   // int4 multi-row GEMM scratch: 8 rows x widest N, fixed point, kept zero between launches
   // block-format (GGUF) weights on the batched prompt path: per fused linear the power-of-two scale (device float) and, while the budget lasts, the matrix
   // as three f16 pieces per weight [N][3 K] (6 bytes per weight: sized for 288 GB of HBM -- a 7B Q4_K_M model keeps 43 GB of them next to its 4.3 GB of blocks)
@@ -1400,6 +1401,21 @@ extern "C" int bz_paged_kv_read_block(const bz_paged_kv* kv, int layer, int bloc
   BZ_API_END
 }
 
+// test and debug accessor, the mirror of bz_paged_kv_read_block (the paged pool has no insert op; tests inject caches through it)
+extern "C" int bz_paged_kv_write_block(bz_paged_kv* kv, int layer, int block, int which, const void* host, size_t nbytes) {
+  BZ_API_BEGIN
+  if (!kv || !host) BZ_FAIL(BZ_E_INVALID, "kv write_block: null argument");
+  const size_t bytes = (size_t)kv->n_kv * kv->block_size * kv->hd * bz_dtype_size(kv->dtype);
+  if (layer < 0 || layer >= kv->layers || block < 0 || block >= kv->num_blocks || (which != 0 && which != 1) || nbytes != bytes)
+    BZ_FAIL(BZ_E_INVALID, "kv write_block: layer %d / block %d / which %d / %zu bytes (a block holds %zu)", layer, block, which, nbytes, bytes);
+  BZ_HIP(hipSetDevice(kv->dev->id));
+  char* base = (char*)(which ? kv->v : kv->k) + ((size_t)layer * kv->num_blocks + block) * bytes;
+  BZ_HIP(hipMemcpyAsync(base, host, bytes, hipMemcpyHostToDevice, kv->dev->stream));
+  BZ_HIP(hipStreamSynchronize(kv->dev->stream));
+  return BZ_OK;
+  BZ_API_END
+}
+
 extern "C" int bz_paged_kv_set_seq_len(bz_paged_kv* kv, int n) { if (!kv || n < 0) BZ_FAIL(BZ_E_INVALID, "bad argument"); kv->seq_len = n; return BZ_OK; }
 extern "C" int bz_paged_kv_seq_len(const bz_paged_kv* kv) { return kv ? kv->seq_len : -1; }
 
@@ -2005,7 +2021,30 @@ static int prefill_exact(const bz_model* m, int n, bool decode_batch) {
 // tokens [S] at positions pos0 .. pos0+S-1; `slots` (paged only): device i32 [S].  Logits of the last row (or all rows) -> logits_out.
 // per-row context of a decode batch: row r is its own sequence (position row_pos[r], block-table row r); nullptr row_pos = one prompt
 // row_lora: device LoRA slot id per row (-1: none); nullptr = every row under the model's current-slot scalar (prompts, the engine's prompt chunks)
-struct RowsCtx { const int* row_pos = nullptr; int table_stride = 0; int max_len = 0; const int* row_lora = nullptr; };
+// split_min: BZ_ROWS_SPLIT_MIN as rows_attn_prepare read it for this call (a captured graph keeps what its capture saw)
+struct RowsCtx { const int* row_pos = nullptr; int table_stride = 0; int max_len = 0; const int* row_lora = nullptr; int split_min = 1 << 30; };
+// What the attention of a decode batch launches, layer by layer, at a decision length of `declen` positions (the longest live row of an eager step, the
+// capacity of a graph): the scalar kernel while a row's scores fit its LDS, the split-KV pair beyond (bz_rows_attn.hip).  Refuses, naming the limit, where
+// neither applies, and grows the pair's workspace -- allocation synchronises, so this runs before any capture begins.
+static int rows_attn_prepare(bz_model* m, const bz_paged_kv* kv, int N, int declen, const char* who, int* split_min) {
+  const bz_model_config& c = m->cfg;
+  *split_min = bzk_rows_split_min();
+  size_t need = 0;
+  for (int l = 0; l < c.n_layers; l++) {
+    BzRowsPlan p;
+    BZ_TRY(bzk_rows_attn_plan(c.n_heads, c.n_kv_heads, c.head_dim, kv->dtype, kv->block_size, layer_window(c, l), std::min(N, 512), declen, *split_min, &p));
+    if (p.kernel < 0)
+      BZ_FAIL(BZ_E_UNSUPPORTED, "%s: batched decode attention holds %d positions at %d / %d heads of %d (scores in LDS) and %d are asked; the split-KV pair beyond that limit "
+              "takes head_dim 64 / 128, f16 / bf16 caches and blocks of at least 4 slots", who, p.scalar_limit, c.n_heads, c.n_kv_heads, c.head_dim,
+              layer_window(c, l) > 0 ? std::min(declen, layer_window(c, l)) : declen);
+    if (p.kernel == 1) need = std::max(need, p.ws_bytes);
+  }
+  if (need > m->rows_ws_bytes) {
+    BZ_HIP(hipStreamSynchronize(m->dev->stream));
+    void* p; BZ_TRY(dev_alloc(m, &p, need)); m->rows_ws = (float*)p; m->rows_ws_bytes = need;     // (an earlier, smaller one stays owned until the model is freed)
+  }
+  return BZ_OK;
+}
 // speculative verify (llama_verify_rows): the head of all S <= 16 rows is the multi-row exact lm_head (bz_speculative.hip), which streams the matrix once per
 // 8 rows and leaves per-row argmax partials in m->sp_pval / m->sp_pidx; logits [S][vocab] device
 struct SpecHeadOut { float* logits; };
@@ -2045,6 +2084,12 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
       BZ_TRY(lora_rows(l, LG_QKV, m->pf_qkv, n, s0));
       BZ_TRY(bzk_pf_rope_kv(st, m->pf_qkv, n, nq, nkv, hd, m->cos_t, m->sin_t, c.rope_interleaved, p0, act, vw, l, slots ? slots + s0 : nullptr,
                             rc.row_pos ? rc.row_pos + s0 : nullptr));
+      BzRowsPlan rp{};                    // decode batch: the split-KV pair where the scalar kernel cannot hold a row's scores (or from BZ_ROWS_SPLIT_MIN on)
+      if (rc.row_pos && view.paged) BZ_TRY(bzk_rows_attn_plan(nq, nkv, hd, view.dtype, view.bs, layer_window(c, l), std::min(S, CH), rc.max_len, rc.split_min, &rp));
+      if (rp.kernel == 1) {
+        if (rp.ws_bytes > m->rows_ws_bytes) BZ_FAIL(BZ_E_INVALID, "rows attention: workspace of %zu bytes not prepared (%zu)", rp.ws_bytes, m->rows_ws_bytes);
+        BZ_TRY(bzk_rows_attn(st, dt, m->pf_qkv, n, nq, nkv, hd, vw, l, m->pf_x16, rc.row_pos + s0, rc.table_stride, layer_window(c, l), rp, m->rows_ws));
+      } else
       BZ_TRY(bzk_pf_attn(st, dt, m->pf_qkv, n, nq, nkv, hd, p0, act, vw, l, m->pf_x16, rc.row_pos ? rc.row_pos + s0 : nullptr, rc.table_stride, rc.max_len, attn_exact,
                          layer_window(c, l)));
       BZ_TRY(gq ? pf_gemm_gq(m, L.o, (const float*)m->pf_x16, n, m->pf_t) : pf_gemm(m, L.o.parts[0], m->pf_x16, n, m->pf_t, exact));
@@ -2360,6 +2405,7 @@ extern "C" int bz_forward_paged_batch(bz_model* m, const bz_tensor* tokens, int 
     BZ_HIP(hipMemcpyAsync(m->row_pos, pos.data(), (size_t)N * 4, hipMemcpyHostToDevice, m->dev->stream));
     BZ_HIP(hipStreamSynchronize(m->dev->stream));       // `pos` is a stack-lifetime host buffer
     RowsCtx rc; rc.row_pos = m->row_pos; rc.table_stride = max_blocks; rc.max_len = maxlen;
+    BZ_TRY(rows_attn_prepare(m, kv, N, maxlen, "forward_paged_batch", &rc.split_min));
     BZ_TRY(prefill_dense(m, (const long long*)tokens->ptr, N, view_of(kv, (const int*)block_table->ptr, nullptr), 0, (const int*)slot_mapping->ptr, true, logits_out, rc));
     if (kv->seq_len < maxlen) kv->seq_len = maxlen;
     return BZ_OK;
@@ -3084,6 +3130,9 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
   }
   const int capacity = std::min(max_blocks * kv->block_size, m->cfg.max_seq_len);
   const LinearDev& LH = m->lm_head.parts[0];
+  int rows_split_min = 1 << 30;
+  BZ_HIP(hipSetDevice(m->dev->id));
+  BZ_TRY(rows_attn_prepare(m, kv, N, capacity, "batch graph capture", &rows_split_min));     // refusal and workspace before the capture
   if (!prefill_eligible(m, std::max(N, prefill_min_rows()), capacity, true) || LH.wdt != m->cfg.act_dtype || LH.K % 64)
     BZ_FAIL(BZ_E_UNSUPPORTED, "batch graph capture: the model does not take the weight-sharing multi-row step (int4 without act-order or dense 16-bit weights, 16-bit lm_head)");
   BZ_HIP(hipSetDevice(m->dev->id));
@@ -3105,7 +3154,7 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
   auto body = [&](hipStream_t cap) -> int {
     if (er) BZ_TRY(bzk_engine_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N, er->rows));
     else BZ_TRY(bzk_batch_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N));
-    RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity; rcx.row_lora = g->row_lora;
+    RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity; rcx.row_lora = g->row_lora; rcx.split_min = rows_split_min;
     BZ_TRY(prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, rcx));
     // a sampler with bz_batch_sampler_enable (sampling.rs:414-431): logprobs on the raw rows, mask, bias, pick, records; without it none of the three launches anything
     if (s) BZ_TRY(bzk_lp_pre(cap, s, (const float*)g->logits->ptr));
@@ -4227,6 +4276,67 @@ extern "C" int bz_kv_insert(bz_model* m, bz_kv* kv, int layer, int position, con
   BZ_TRY(bzk_kv_insert(st, view_of(kv), layer, (const float*)k->ptr, (const float*)v->ptr, m->pos_tmp, kv->n_kv, kv->hd));
   BZ_HIP(hipStreamSynchronize(st));
   if (position + 1 > kv->seq_len) kv->seq_len = position + 1;
+  return BZ_OK;
+  BZ_API_END
+}
+
+// ---- batched decode attention at long contexts (bz_rows_attn.hip; process_decode_batch, engine/batch_decode.rs:35-150) ----
+extern "C" int bz_rows_attn_slice_len(int len) { return bzk_rows_slice_len(len); }
+extern "C" int bz_rows_attn_plan(int n_heads, int n_kv_heads, int head_dim, int kv_dtype, int window, int N, int capacity, bz_rows_attn_plan_t* out) {
+  BZ_API_BEGIN
+  if (!out || n_heads <= 0 || n_kv_heads <= 0 || head_dim <= 0 || N <= 0 || capacity <= 0 || window < 0) BZ_FAIL(BZ_E_INVALID, "rows_attn_plan: bad argument");
+  BzRowsPlan p;
+  BZ_TRY(bzk_rows_attn_plan(n_heads, n_kv_heads, head_dim, kv_dtype, 16, window, std::min(N, 512), capacity, bzk_rows_split_min(), &p));
+  out->kernel = p.kernel; out->scalar_limit = p.scalar_limit; out->grid_slices = p.grid_slices; out->rows_per_pass = p.rows_per_pass; out->ws_bytes = p.ws_bytes;
+  if (p.kernel < 0)
+    BZ_FAIL(BZ_E_UNSUPPORTED, "rows_attn_plan: batched decode attention holds %d positions at %d / %d heads of %d (scores in LDS) and %d are asked; the split-KV pair beyond that "
+            "limit takes head_dim 64 / 128 and f16 / bf16 caches", p.scalar_limit, n_heads, n_kv_heads, head_dim, window > 0 ? std::min(capacity, window) : capacity);
+  return BZ_OK;
+  BZ_API_END
+}
+// The attention the batched step would launch for these rows, alone: q F32 [N, n_heads, hd] (roped and rounded), block_table I32 [N, max_blocks], seq_lens host
+// i32 [N]; out F32 [N, n_heads, hd] = the 16-bit rows the o_proj GEMM would read.  The op-level twin of bz_paged_attn_decode.
+extern "C" int bz_paged_attn_decode_rows(bz_model* m, const bz_tensor* q, bz_paged_kv* kv, int layer, const bz_tensor* block_table, int max_blocks, const int32_t* seq_lens, int N,
+                                         bz_tensor* out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || !kv || !q || !out || !block_table || !seq_lens || N <= 0 || N > 512 || max_blocks <= 0) BZ_FAIL(BZ_E_INVALID, "paged_attn_decode_rows: bad argument (1 <= N <= 512)");
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  const bz_model_config& c = m->cfg;
+  if (c.arch != BZ_ARCH_LLAMA) BZ_FAIL(BZ_E_UNSUPPORTED, "paged_attn_decode_rows: llama family only");
+  BZ_TRY(check_cache(m, kv, "paged_attn_decode_rows"));
+  if (c.act_dtype != BZ_F16 && c.act_dtype != BZ_BF16) BZ_FAIL(BZ_E_UNSUPPORTED, "paged_attn_decode_rows: 16-bit activations only");
+  const int nq = c.n_heads, nkv = c.n_kv_heads, hd = c.head_dim;
+  const size_t need = (size_t)N * nq * hd * 4;
+  if (q->dtype != BZ_F32 || out->dtype != BZ_F32 || q->nbytes < need || out->nbytes < need) BZ_FAIL(BZ_E_INVALID, "paged_attn_decode_rows: q / out must be F32 [N, n_heads, head_dim]");
+  if (block_table->dtype != BZ_I32 || block_table->nbytes < (size_t)N * max_blocks * 4) BZ_FAIL(BZ_E_INVALID, "paged_attn_decode_rows: block_table must be I32 [N, max_blocks]");
+  if (layer < 0 || layer >= c.n_layers) BZ_FAIL(BZ_E_INVALID, "paged_attn_decode_rows: bad layer");
+  int maxlen = 0;
+  std::vector<int> pos(N);
+  for (int i = 0; i < N; i++) {
+    if (seq_lens[i] <= 0 || seq_lens[i] > c.max_seq_len || (seq_lens[i] + kv->block_size - 1) / kv->block_size > max_blocks)
+      BZ_FAIL(BZ_E_INVALID, "paged_attn_decode_rows: sequence %d has length %d (max_seq_len %d, %d blocks of %d)", i, seq_lens[i], c.max_seq_len, max_blocks, kv->block_size);
+    maxlen = std::max(maxlen, seq_lens[i]);
+    pos[i] = seq_lens[i] - 1;
+  }
+  BZ_HIP(hipSetDevice(m->dev->id));
+  hipStream_t st = m->dev->stream;
+  BZ_TRY(prefill_ws(m, N));
+  int split_min = 1 << 30;
+  BZ_TRY(rows_attn_prepare(m, kv, N, maxlen, "paged_attn_decode_rows", &split_min));
+  if (!m->row_pos || m->row_pos_n < N) {
+    BZ_HIP(hipStreamSynchronize(st));
+    void* p; BZ_TRY(dev_alloc(m, &p, (size_t)N * 4)); m->row_pos = (int*)p; m->row_pos_n = N;
+  }
+  BZ_HIP(hipMemcpyAsync(m->row_pos, pos.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
+  BZ_HIP(hipMemcpy2DAsync(m->pf_qkv, (size_t)(nq + 2 * nkv) * hd * 4, q->ptr, (size_t)nq * hd * 4, (size_t)nq * hd * 4, N, hipMemcpyDeviceToDevice, st));
+  const KvView vw = view_of(kv, (const int*)block_table->ptr, nullptr);
+  const int W = layer_window(c, layer);
+  BzRowsPlan rp;
+  BZ_TRY(bzk_rows_attn_plan(nq, nkv, hd, kv->dtype, kv->block_size, W, N, maxlen, split_min, &rp));
+  if (rp.kernel == 1) BZ_TRY(bzk_rows_attn(st, c.act_dtype, m->pf_qkv, N, nq, nkv, hd, vw, layer, m->pf_x16, m->row_pos, max_blocks, W, rp, m->rows_ws));
+  else BZ_TRY(bzk_pf_attn(st, c.act_dtype, m->pf_qkv, N, nq, nkv, hd, 0, c.act_dtype, vw, layer, m->pf_x16, m->row_pos, max_blocks, maxlen, false, W));
+  BZ_TRY(bzk_rows16_to_f32(st, c.act_dtype, m->pf_x16, (size_t)N * nq * hd, (float*)out->ptr));
+  BZ_HIP(hipStreamSynchronize(st));       // (`pos` is a stack-lifetime host buffer)
   return BZ_OK;
   BZ_API_END
 }

@@ -344,6 +344,17 @@ int bzk_pf_gnorm(hipStream_t s, int dt, const float* v, const float* vss, const 
 int bzk_pf_silu(hipStream_t s, int dt, const float* gu, int S, int I, int act, void* a16);
 size_t bzk_pf_attn_smem(int nq, int nkv, int hd, int len, bool exact = false);
 bool bzk_pf_attn_mfma_ok(int hd, int rep);
+// decode batches beyond the scalar kernel's LDS limit (bz_rows_attn.hip): split-KV over the rows' block tables + merge
+// kernel: 0 = the scalar k_pf_attn, 1 = the split pair, -1 = neither applies (beyond the limit, shape the pair is not built for)
+struct BzRowsPlan { int kernel; int scalar_limit; int grid_slices; int rows_per_pass; size_t ws_bytes; };
+int bzk_rows_slice_len(int len);
+int bzk_rows_split_min();                // BZ_ROWS_SPLIT_MIN, read per call (default: out of reach)
+bool bzk_rows_attn_ok(int nq, int nkv, int hd, int kv_dtype);
+int bzk_rows_scalar_limit(int nq, int nkv, int hd);
+int bzk_rows_attn_plan(int nq, int nkv, int hd, int kv_dtype, int block_size, int window, int N, int capacity, int split_min, BzRowsPlan* out);
+int bzk_rows_attn(hipStream_t s, int dt, const float* qkv, int n, int nq, int nkv, int hd, const KvView& kv, int layer, void* out16, const int* row_pos, int table_stride,
+                  int window, const BzRowsPlan& plan, float* ws);
+int bzk_rows16_to_f32(hipStream_t s, int dt, const void* x16, size_t n, float* y);
 
 // non-greedy sampling (bz_sample.hip)
 int bzk_sample(hipStream_t s, void** ws, const float* logits, long long V, const long long* ids, const int* cnts, int n, float rp, float fp, float pp,

@@ -561,6 +561,24 @@ class LoadedModel:
         L.check(L.lib().bz_forward_paged_batch(self.h, t.h, n, cache.h, sm.h, btt.h, nb, sl.ctypes.data_as(C.c_void_p), out.h))
         return out
 
+    def paged_attn_decode_rows(self, q, cache, layer, block_tables, seq_lens):
+        """bz_paged_attn_decode_rows: the attention the batched decode step would launch for these rows, alone (batch_decode.rs:35-150).  q [N, n_heads, head_dim]
+        roped and rounded, block_tables [N][<= max_blocks] (ragged ok, padded with 0; a 2-D array is taken as it is), seq_lens [N] -> f32 array [N, n_heads, hd]"""
+        qa = np.ascontiguousarray(q, dtype=np.float32)
+        n = qa.shape[0]
+        if isinstance(block_tables, np.ndarray) and block_tables.ndim == 2:
+            bt = np.ascontiguousarray(block_tables, dtype=np.int32)
+        else:
+            bt = np.zeros((n, max(len(b) for b in block_tables)), dtype=np.int32)
+            for i, b in enumerate(block_tables):
+                bt[i, :len(b)] = b
+        sl = np.ascontiguousarray(seq_lens, dtype=np.int32)
+        if bt.shape[0] != n or len(sl) != n:
+            raise ValueError("paged_attn_decode_rows: %d rows, %d block tables, %d lengths" % (n, bt.shape[0], len(sl)))
+        tq, tb, out = self.dev.tensor(qa), self.dev.tensor(bt), self.dev.zeros(qa.shape, L.F32)
+        L.check(L.lib().bz_paged_attn_decode_rows(self.h, tq.h, cache.h, int(layer), tb.h, int(bt.shape[1]), sl.ctypes.data_as(C.c_void_p), n, out.h))
+        return out.to_numpy().reshape(qa.shape)
+
     def forward_embed(self, tokens):
         t, S = self._tokens(tokens)
         out = self.dev.zeros((S, self.c.hidden), L.F32)
@@ -802,6 +820,29 @@ class LayeredPagedKvCache:
         out = np.empty((n_kv_heads, self.block_size, head_dim), dtype=np.float32 if dtype == L.F32 else np.uint16)
         L.check(L.lib().bz_paged_kv_read_block(self.h, int(layer), int(block), int(which), _ptr(out), out.nbytes))
         return out
+
+    def write_block(self, layer, block, which, data):
+        """The mirror of read_block: `data` [kv_head][block_size][head_dim] as stored (float32 for an f32 pool, raw 16-bit patterns as uint16 otherwise)."""
+        a = np.ascontiguousarray(data)
+        L.check(L.lib().bz_paged_kv_write_block(self.h, int(layer), int(block), int(which), _ptr(a), a.nbytes))
+
+
+def rows_attn_slice_len(n):
+    """bz_rows_attn_slice_len: positions per split-KV slice for a decode-batch row of n keys (host only; the rule the device applies)"""
+    return int(L.lib().bz_rows_attn_slice_len(int(n)))
+
+
+def rows_attn_plan(n_heads, n_kv_heads, head_dim, kv_dtype, window, n, capacity):
+    """bz_rows_attn_plan (host only): what a decode batch of n rows launches per layer at a decision length of `capacity` positions.  Returns a dict with
+    kernel (0 scalar, 1 split pair, -1 refused), scalar_limit, grid_slices, rows_per_pass, ws_bytes and, for a refused plan, the library's message."""
+    p = L.RowsAttnPlan()
+    rc = L.lib().bz_rows_attn_plan(int(n_heads), int(n_kv_heads), int(head_dim), int(kv_dtype), int(window), int(n), int(capacity), C.byref(p))
+    d = dict(kernel=p.kernel, scalar_limit=p.scalar_limit, grid_slices=p.grid_slices, rows_per_pass=p.rows_per_pass, ws_bytes=int(p.ws_bytes), code=rc, error=None)
+    if rc == L.E_UNSUPPORTED and p.kernel == -1:
+        d["error"] = L.lib().bz_last_error().decode()
+        return d
+    L.check(rc)
+    return d
 
 
 def penalty_window(recent_tokens, repeat_last_n):

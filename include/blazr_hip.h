@@ -179,6 +179,9 @@ int bz_paged_kv_copy_slots(bz_paged_kv* kv, int src, int dst, int n_slots);
 /* TEST AND DEBUG ACCESSOR, not part of the serving path: one block of one layer as stored ([kv_head][block_size][hd] in the pool's dtype), raw bytes to the
  * host; which: 0 = K, 1 = V.  Waits for the stream.  (The paged pool had no read-back; the copy kernel's tests need one.) */
 int bz_paged_kv_read_block(const bz_paged_kv* kv, int layer, int block, int which, void* host, size_t nbytes);
+/* TEST AND DEBUG ACCESSOR, the mirror of bz_paged_kv_read_block: raw bytes of one block of one layer from the host into the pool; waits for the stream.
+ * (The paged pool has no insert op; tests of the batched decode attention inject caches through it -- engine/batch_decode.rs:35-150.) */
+int bz_paged_kv_write_block(bz_paged_kv* kv, int layer, int block, int which, const void* host, size_t nbytes);
 int bz_paged_kv_seq_len(const bz_paged_kv* kv);
 
 /* LayeredSsmState::new(layers, batch, mamba_config, dtype, device) (executor_generate.rs:131-133): recurrent state
@@ -738,6 +741,22 @@ int bz_silu_mul(bz_device* dev, const bz_tensor* gate, const bz_tensor* up, int6
 int bz_attn_decode(bz_model* m, const bz_tensor* q, bz_kv* kv, int layer, int len, bz_tensor* out);
 int bz_paged_attn_decode(bz_model* m, const bz_tensor* q, bz_paged_kv* kv, int layer, const bz_tensor* block_table, int len,
                          bz_tensor* out);
+/* Batched decode attention (process_decode_batch, engine/batch_decode.rs:35-150).  A decode batch's attention keeps a row's scores in LDS up to scalar_limit
+ * positions (38 888 / 18 416 / 8 180 / 3 062 at n_heads / n_kv_heads = 1 / 2 / 4 / 8); beyond, or from BZ_ROWS_SPLIT_MIN positions on, it runs as split-KV
+ * over the rows' block tables + merge (head_dim 64 / 128, f16 / bf16 caches).
+ * bz_rows_attn_plan: HOST ONLY, needs no device -- what a batch of N rows launches per layer at a decision length of `capacity` positions (the longest live row
+ * of an eager step, the capacity of a graph) under a window of `window` keys (0: none).  kernel: 0 scalar, 1 split pair, -1 refused (then the call returns
+ * BZ_E_UNSUPPORTED and the message names the limit).  ws_bytes = rows_per_pass * n_heads * grid_slices * (head_dim + 4) * 4, rows_per_pass = min(N, 512,
+ * 128 MiB / (n_heads * grid_slices * (head_dim + 4) * 4)): a larger batch passes over its rows in sub-chunks.  BZ_ROWS_SPLIT_MIN is read, as the step reads it.
+ * bz_rows_attn_slice_len: HOST ONLY -- positions per slice for a row of `len` keys (inside its window), the rule the device applies: 128, doubled until at
+ * most 64 slices cover the row. */
+typedef struct bz_rows_attn_plan_t { int kernel; int scalar_limit; int grid_slices; int rows_per_pass; size_t ws_bytes; } bz_rows_attn_plan_t;
+int bz_rows_attn_plan(int n_heads, int n_kv_heads, int head_dim, int kv_dtype, int window, int N, int capacity, bz_rows_attn_plan_t* out);
+int bz_rows_attn_slice_len(int len);
+/* op-level twin of bz_paged_attn_decode for a decode batch (engine/batch_decode.rs:35-150): runs the attention the batched step would launch for these rows and
+ * returns its 16-bit rows as F32.  q F32 [N, n_heads, hd] roped and rounded, block_table I32 [N, max_blocks], seq_lens HOST i32 [N], out F32 [N, n_heads, hd]. */
+int bz_paged_attn_decode_rows(bz_model* m, const bz_tensor* q, bz_paged_kv* kv, int layer, const bz_tensor* block_table, int max_blocks,
+                              const int32_t* seq_lens, int N, bz_tensor* out);
 /* kv_insert kernel (cuda_graphs.rs:5): write k,v F32 [n_kv_heads, head_dim] at `position` (contiguous) */
 int bz_kv_insert(bz_model* m, bz_kv* kv, int layer, int position, const bz_tensor* k, const bz_tensor* v);
 /* ConvOps (engine/executor.rs:71) -- Mamba2 layer `layer`: depthwise causal conv1d STEP (+ bias, SiLU) over the raw in_proj row zx = [z | x B C | dt]
