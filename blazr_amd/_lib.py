@@ -276,6 +276,7 @@ SYMBOLS = {
     "bz_tune_mlp": (C.c_int, [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "bz_probe_hbm_read": (C.c_int, [P, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
     "bz_expf_spec": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "bz_fp8_e4m3_spec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bz_conv1d_step": (C.c_int, [P, C.c_int, P, P, P]),
     "bz_ssm_step": (C.c_int, [P, C.c_int, P, P, P]),
     "bz_ssm_state_read": (C.c_int, [P, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),

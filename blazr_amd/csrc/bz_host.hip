@@ -4187,6 +4187,16 @@ extern "C" int bz_moe_grouped_gemv(bz_model* m, int layer, int which, const bz_t
   BZ_API_END
 }
 
+extern "C" int bz_fp8_e4m3_spec(const float* x, int n, int exp, uint8_t* bytes_out, float* values_out) {
+  BZ_API_BEGIN
+  if (!x || !bytes_out || n < 0 || exp < -5 || exp > 7) BZ_FAIL(BZ_E_INVALID, "fp8_e4m3_spec: bad argument (exponent in [-5, 7])");
+  for (int i = 0; i < n; i++) {
+    bytes_out[i] = (uint8_t)bz_fp8_quant(x[i], exp);
+    if (values_out) values_out[i] = bz_fp8_dequant(bytes_out[i], exp);
+  }
+  return BZ_OK;
+  BZ_API_END
+}
 extern "C" int bz_expf_spec(const float* x, int n, float* y) {
   BZ_API_BEGIN
   if (!x || !y || n < 0) BZ_FAIL(BZ_E_INVALID, "bad argument");

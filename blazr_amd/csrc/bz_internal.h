@@ -137,6 +137,36 @@ struct KvView {
 
 size_t bz_dtype_size(int dtype);
 
+// OCP E4M3 (e4m3fn, not fnuz) in software, host and device: the quantiser an FP8 KV pool would store with (no pool uses it yet -- DESIGN section 4 "E4M3
+// quantiser") and its scalar decode.  stored byte = e4m3(x 2^-exp), value read = e4m3 2^exp.  x 2^-exp is exact, the clamp to +-448 happens in f32 (no conversion
+// instruction's overflow mode takes part), rounding is to nearest even with subnormals (units of 2^-9), NaN -> 0x7F.
+__host__ __device__ __forceinline__ float bz_pow2f(int e) { const unsigned b = (unsigned)(127 + e) << 23; float f; __builtin_memcpy(&f, &b, 4); return f; }   // -126 <= e <= 127
+__host__ __device__ __forceinline__ unsigned bz_fp8_quant(float x, int exp) {
+  if (x != x) return 0x7Fu;
+  float y = x * bz_pow2f(-exp);
+  y = y > 448.f ? 448.f : (y < -448.f ? -448.f : y);
+  unsigned u; __builtin_memcpy(&u, &y, 4);
+  const unsigned sign = (u >> 24) & 0x80u;
+  u &= 0x7fffffffu;
+  if (u < 0x3C800000u) {                      // below 2^-6: a multiple of 2^-9 -- one f32 add at 2^14, where an ulp is 2^-9, rounds to nearest even
+    float a; __builtin_memcpy(&a, &u, 4);
+    a += 16384.f;
+    unsigned r; __builtin_memcpy(&r, &a, 4);
+    return sign | (r - 0x46800000u);          // 0 .. 8 (8 = the smallest normal number's code)
+  }
+  u += 0x7FFFFu + ((u >> 20) & 1u);           // three mantissa bits stay
+  return sign | ((u >> 20) - (120u << 3));    // exponent bias 127 -> 7; at most 0x7E after the clamp
+}
+__host__ __device__ __forceinline__ float bz_fp8_dequant(unsigned b, int exp) {
+  const unsigned m = b & 0x7Fu;
+  float f;
+  if (m == 0x7Fu) { const unsigned n = 0x7FC00000u; __builtin_memcpy(&f, &n, 4); return f; }
+  if (m < 8u) f = (float)m * 0.001953125f;    // subnormal: m 2^-9
+  else { const unsigned u = (m + (120u << 3)) << 20; __builtin_memcpy(&f, &u, 4); }
+  f *= bz_pow2f(exp);
+  return (b & 0x80u) ? -f : f;
+}
+
 // per-launch timing records (bz_profile_step)
 struct BzTimingRec { const char* label; double bytes; hipEvent_t e0, e1; };
 struct BzTimingSink { std::vector<BzTimingRec> recs; };

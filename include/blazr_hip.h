@@ -783,6 +783,12 @@ int bz_moe_grouped_gemv(bz_model* m, int layer, int which, const bz_tensor* sel,
  * compiles, so a CPU-only test can pin it bit for bit against an independent restatement.  boostr's own exp (ActivationOps / softmax behind
  * executor.rs:67-80) is not visible; any faithful expf is "the" exp, and a specified one makes both sides of a parity test compute the same bits. */
 int bz_expf_spec(const float* x, int n, float* y);
+/* The E4M3 quantiser an FP8 KV pool would store with (OCP e4m3fn; groundwork, no pool uses it yet -- DESIGN.md section 4 "E4M3 quantiser"), evaluated on the HOST
+ * for n values: bytes_out[i] = e4m3(x[i] * 2^-exp) -- multiply by 2^-exp (exact), clamp to +-448 in f32, round to nearest even with subnormals, NaN -> 0x7F --
+ * and values_out[i] (nullable) = that byte read back, times 2^exp.  exp in [-5, 7]: inside it every value read back is a normal f16 below 65 504, exact in f16 and
+ * in bf16.  Public for the reason bz_expf_spec is: it is the function body device code would compile, so a CPU-only test pins it bit for bit against an
+ * independent restatement.  Beyond the reference.  New symbol only: BZ_ABI_VERSION is unchanged. */
+int bz_fp8_e4m3_spec(const float* x, int n, int exp, uint8_t* bytes_out, float* values_out);
 /* rope_caches() -> (cos, sin) F32 [max_pos, head_dim/2] copied to host */
 int bz_rope_caches(bz_model* m, float* cos_host, float* sin_host);
 
