@@ -214,6 +214,7 @@ SYMBOLS = {
     "bz_model_add_awq": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64, P, P, P, C.c_int]),
     "bz_model_add_gptq": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64, P, P, P, P, P, C.c_int]),
     "bz_model_add_gguf": (C.c_int, [P, C.c_char_p, C.c_int, C.c_int64, C.c_int64, P]),
+    "bz_model_add_fp8": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64, P, P, C.c_int64, P]),
     "bz_model_finalize": (C.c_int, [P]),
     "bz_model_get_config": (C.c_int, [P, C.POINTER(ModelConfig)]),
     "bz_model_weight_bytes": (C.c_int, [P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

@@ -381,10 +381,12 @@ __device__ __forceinline__ float block_sum256(float v, float* red) {
 // prologue: build the activation slice x[k0, k0+KR) as f32 in LDS
 // ---------------------------------------------------------------------------------------------------------
 // Simple form (loads inside): used by the ROWS kernels, whose slice is all of K.
-// pos(i): LDS position of slice element i (identity, or the ROWS swizzle).
-template <bool SWZ>
+// pos(i): LDS position of slice element i (0: identity, 1: the ROWS swizzle, 2: the FP8 rows' padding -- four floats after every sixteen, so that sixteen
+// lanes reading sixteen consecutive elements each as float4 hit sixty-four different banks).
+template <int SWZ>
 __device__ __forceinline__ int xs_pos(int i) {
-  if (!SWZ) return i;
+  if (SWZ == 0) return i;
+  if (SWZ == 2) return i + ((i >> 4) << 2);
   return (i & ~511) + ((i & 4) << 6) + ((i & 511) >> 3 << 2) + (i & 3);
 }
 
@@ -402,7 +404,7 @@ __device__ __forceinline__ float src_cvt(typename SrcRaw<FIX>::T r, int act) {
 }
 
 // NORM pass 1: v = R(h + prev) for the whole row -> sum of squares; slice elements [k0, k0+KR) are parked in xs
-template <bool SWZ, bool FIX, bool PREV>
+template <int SWZ, bool FIX, bool PREV>
 __device__ __forceinline__ double norm_pass1(const Pro& p, int k0, int KR, float* xs, bool writer) {
   const int tid = threadIdx.x;
   double ss = 0.0;
@@ -439,7 +441,7 @@ __device__ __forceinline__ double norm_pass1(const Pro& p, int k0, int KR, float
   return ss;
 }
 
-template <bool SWZ, bool FIX, bool SILU>
+template <int SWZ, bool FIX, bool SILU>
 __device__ __forceinline__ void plain_fill(const Pro& p, int k0, int KR, float* xs) {
   const int tid = threadIdx.x;
   for (int base = 0; base < KR; base += 2048) {
@@ -461,7 +463,7 @@ __device__ __forceinline__ void plain_fill(const Pro& p, int k0, int KR, float* 
 }
 
 // Simple form (loads inside): used by the ROWS kernels (no act-order permutation there).  Slice [k0, k0+KR), KR > 0.
-template <bool SWZ>
+template <int SWZ>
 __device__ void build_x_simple(const Pro& p, int k0, int KR, float* xs, float* red, bool writer) {
   const int tid = threadIdx.x;
   if (KR <= 0) { __syncthreads(); return; }

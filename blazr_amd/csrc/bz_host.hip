@@ -238,7 +238,7 @@ extern "C" int bz_tensor_to_host_pipelined(const bz_tensor* t, uint64_t ev, void
 // model
 // ---------------------------------------------------------------------------------------------------------
 struct RawTensor {
-  int kind = 0;  // 0 dense, 1 awq, 2 gptq, 3 gguf
+  int kind = 0;  // 0 dense, 1 awq, 2 gptq, 3 gguf, 4 fp8 (d0 = e4m3 bytes [N][K], d1 = f32 scales [N])
   int dtype = BZ_F32;
   std::vector<int64_t> shape;
   int64_t N = 0, K = 0; int gs = 0; int ggml_type = 0;
@@ -529,6 +529,31 @@ extern "C" int bz_model_add_gguf(bz_model* m, const char* name, int ggml_type, i
   BZ_API_END
 }
 
+// FP8 (OCP E4M3) weights with a per-tensor or per-output-channel scale: W[n][k] = s[n] e4m3(q[n][k]).  The scales are kept as one f32 per row (a per-tensor
+// scale is broadcast here); a NaN code is refused here, so no kernel has to decode one.
+extern "C" int bz_model_add_fp8(bz_model* m, const char* name, int64_t N, int64_t K, const uint8_t* weight, const float* scale, int64_t n_scale, const float* bias) {
+  BZ_API_BEGIN
+  BZ_TRY(check_add(m, name));
+  if (!weight || !scale) BZ_FAIL(BZ_E_INVALID, "add_fp8 '%s': null data", name);
+  if (N <= 0 || K <= 0 || N % 64 || K % 64) BZ_FAIL(BZ_E_UNSUPPORTED, "add_fp8 '%s': N=%lld and K=%lld must be positive multiples of 64", name, (long long)N, (long long)K);
+  if ((uint64_t)N * (uint64_t)K >= (1ull << 32)) BZ_FAIL(BZ_E_UNSUPPORTED, "add_fp8 '%s': 2^32 weights or more", name);
+  if (n_scale != 1 && n_scale != N) BZ_FAIL(BZ_E_INVALID, "add_fp8 '%s': %lld scales (one per tensor or one per output row, N=%lld)", name, (long long)n_scale, (long long)N);
+  for (int64_t i = 0; i < n_scale; i++) if (!std::isfinite(scale[i])) BZ_FAIL(BZ_E_INVALID, "add_fp8 '%s': scale[%lld] is not finite", name, (long long)i);
+  if (bias) for (int64_t i = 0; i < N; i++) if (!std::isfinite(bias[i])) BZ_FAIL(BZ_E_INVALID, "add_fp8 '%s': bias[%lld] is not finite", name, (long long)i);
+  const size_t n = (size_t)N * (size_t)K;
+  for (size_t i = 0; i < n; i++)
+    if ((weight[i] & 0x7Fu) == 0x7Fu) BZ_FAIL(BZ_E_INVALID, "add_fp8 '%s': weight[%zu] = 0x%02X is an E4M3 NaN code", name, i, (unsigned)weight[i]);
+  RawTensor r; r.kind = 4; r.N = N; r.K = K; r.shape = {N, K}; r.bytes = n + (size_t)N * 4;
+  std::vector<float> sc((size_t)N);
+  for (int64_t i = 0; i < N; i++) sc[(size_t)i] = scale[n_scale == 1 ? 0 : i];
+  BZ_TRY(upload(m->dev, &r.d0, weight, n));
+  BZ_TRY(upload(m->dev, &r.d1, sc.data(), (size_t)N * 4));
+  if (bias) { void* b; BZ_TRY(upload(m->dev, &b, bias, (size_t)N * 4)); r.d_bias = (float*)b; }
+  m->raw[name] = r;
+  return BZ_OK;
+  BZ_API_END
+}
+
 // --- finalize helpers ---------------------------------------------------------------------------------------
 static int choose_gw(int N, int K, int target) {
   const int G = K / 128, nst = (N + 255) / 256;
@@ -627,6 +652,49 @@ static int build_rows(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev*
   return BZ_OK;
 }
 
+// FP8 tensors concatenated along N: bytes, scales (one [N] array) and biases (zero where a part has none); the split-K form's row-block counters
+static int f8_split_env() { const char* e = getenv("BZ_F8_SPLITK"); return e ? atoi(e) : -1; }   // 0: never split; n > 1: n slices wherever a row has n chunks (tests, tuning); read per finalize
+static int f8_choose_sk(int N, int K) {
+  const int env = f8_split_env();
+  if (env == 0) return 1;
+  if (env > 1) return (K + 255) / 256 >= env ? env : 1;
+  return bzk_f8_choose_sk(N, K);
+}
+static int build_f8(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L) {
+  const int K = (int)rs[0]->K;
+  int N = 0;
+  bool any_bias = false;
+  for (auto* r : rs) { N += (int)r->N; any_bias |= r->d_bias != nullptr; if (r->K != K) BZ_FAIL(BZ_E_UNSUPPORTED, "fused fp8 parts differ in K"); }
+  if ((uint64_t)N * (uint64_t)K >= (1ull << 32)) BZ_FAIL(BZ_E_UNSUPPORTED, "fused fp8 linear of 2^32 weights or more");
+  void *w, *sc, *cnt, *b = nullptr;
+  hipStream_t st = m->dev->stream;
+  if (rs.size() == 1) {
+    w = rs[0]->d0; rs[0]->d0 = nullptr; m->owned.push_back(w);      // take ownership, no copy
+    sc = rs[0]->d1; rs[0]->d1 = nullptr; m->owned.push_back(sc);
+  } else {
+    BZ_TRY(dev_alloc(m, &w, (size_t)N * K));
+    BZ_TRY(dev_alloc(m, &sc, (size_t)N * 4));
+    size_t o = 0;
+    for (auto* r : rs) {
+      BZ_HIP(hipMemcpyAsync((char*)w + o * K, r->d0, (size_t)r->N * K, hipMemcpyDeviceToDevice, st));
+      BZ_HIP(hipMemcpyAsync((float*)sc + o, r->d1, (size_t)r->N * 4, hipMemcpyDeviceToDevice, st));
+      o += (size_t)r->N;
+    }
+  }
+  if (any_bias) {
+    BZ_TRY(dev_alloc(m, &b, (size_t)N * 4));
+    BZ_HIP(hipMemsetAsync(b, 0, (size_t)N * 4, st));
+    size_t o = 0;
+    for (auto* r : rs) { if (r->d_bias) BZ_HIP(hipMemcpyAsync((float*)b + o, r->d_bias, (size_t)r->N * 4, hipMemcpyDeviceToDevice, st)); o += (size_t)r->N; }
+  }
+  BZ_TRY(dev_alloc(m, &cnt, (size_t)(N / 16) * 4));
+  BZ_HIP(hipMemsetAsync(cnt, 0, (size_t)(N / 16) * 4, st));
+  BZ_HIP(hipStreamSynchronize(st));
+  L->kind = LK_F8; L->N = N; L->K = K; L->wdt = BZ_U8; L->w = w; L->scales = sc; L->zeros = cnt; L->bias = (float*)b;
+  L->bytes = (size_t)N * K + (size_t)N * 4; L->algo_bytes = L->bytes;      // one byte per weight plus the scales
+  return BZ_OK;
+}
+
 // dense linear whose consumer reads plain f32 (lm_head logits, Mamba2 in_proj): no split-K
 static void force_direct(FusedLinear* F) {
   bool rows = true;
@@ -708,7 +776,7 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
     if (a->kind == 2 && !same_perm(a, b)) return false;
     if (a->kind == 0 && a->dtype != b->dtype) return false;
     if (a->kind == 3 && a->ggml_type != b->ggml_type) return false;
-    return true;
+    return true;   // (fp8 parts always share a launch: bytes and per-row scales concatenate)
   };
   std::vector<std::vector<RawTensor*>> groups;
   for (auto* r : rs) {
@@ -721,6 +789,7 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
     if (g[0]->kind == 1 || g[0]->kind == 2) BZ_TRY(build_q4g(m, g, &L));
     else if (g[0]->kind == 0) { if (g[0]->shape.size() != 2) BZ_FAIL(BZ_E_INVALID, "finalize: linear weight must be 2-D"); BZ_TRY(build_rows(m, g, &L)); }
     else if (g[0]->kind == 3) BZ_TRY(build_gq(m, g, &L));
+    else if (g[0]->kind == 4) BZ_TRY(build_f8(m, g, &L));
     else BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: tensor kind %d", g[0]->kind);
     F->parts.push_back(L); F->n_off.push_back(noff);
     // per-name views for the op-level API
@@ -735,6 +804,10 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
       } else if (L.kind == LK_ROWS) {
         V.sk = 1;
         V.w = (char*)L.w + (size_t)sub * L.K * bz_dtype_size(L.wdt);
+      } else if (L.kind == LK_F8) {
+        V.w = (char*)L.w + (size_t)sub * L.K; V.scales = (float*)L.scales + sub; V.zeros = (unsigned*)L.zeros + sub / 16;
+        V.bias = L.bias ? L.bias + sub : nullptr;
+        V.sk = f8_choose_sk(V.N, V.K);
       } else {
         const size_t t0 = (size_t)sub / 64, K = (size_t)L.K;
         if (L.kind == LK_Q80) { V.w = (char*)L.w + t0 * 64 * K; V.scales = (char*)L.scales + t0 * (K / 32) * 64 * 2; }
@@ -756,7 +829,8 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
   }
   static const bool no_sk = getenv("BZ_NO_ROWS_SPLITK") != nullptr;
   for (auto& p : F->parts) if (p.kind == LK_ROWS && !no_sk) p.sk = bzk_rows_choose_sk(p.N, p.K);
-  auto is_fix = [](const LinearDev& p) { return p.kind != LK_ROWS || p.sk > 1; };
+  for (auto& p : F->parts) if (p.kind == LK_F8) p.sk = f8_choose_sk(p.N, p.K);
+  auto is_fix = [](const LinearDev& p) { return (p.kind != LK_ROWS && p.kind != LK_F8) || p.sk > 1; };
   F->fix_out = is_fix(F->parts[0]);
   for (auto& p : F->parts) if (is_fix(p) != F->fix_out) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: mixed fixed-point/direct parts in one fused linear");
   for (auto* r : rs) { raw_free(*r); r->consumed = true; }
@@ -845,6 +919,10 @@ extern "C" int bz_model_finalize(bz_model* m) {
   if (!m) BZ_FAIL(BZ_E_INVALID, "null model");
   if (m->finalized) BZ_FAIL(BZ_E_INVALID, "model already finalized");
   BZ_HIP(hipSetDevice(m->dev->id));
+  if (m->cfg.act_dtype == BZ_F32)   // (x e4m3(q) is exact in f32 for 16-bit activations only)
+    for (auto& kv : m->raw) if (kv.second.kind == 4) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: fp8 tensor '%s': fp8 weights need f16 or bf16 activations", kv.first.c_str());
+  if (m->cfg.arch != BZ_ARCH_LLAMA)
+    for (auto& kv : m->raw) if (kv.second.kind == 4) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: fp8 tensor '%s': fp8 weights are built for the Llama family only", kv.first.c_str());
   if (m->cfg.arch == BZ_ARCH_MAMBA2) return finalize_mamba2(m);
   if (m->cfg.arch == BZ_ARCH_DEEPSEEK2) return finalize_dsv2(m);
   const bz_model_config& c = m->cfg;
@@ -911,6 +989,8 @@ extern "C" int bz_model_finalize(bz_model* m) {
     } else if (!tied) {
       BZ_TRY(build_fused(m, {"lm_head"}, &m->lm_head));
       force_direct(&m->lm_head);
+      // an fp8 lm_head takes the path of an int4 one: fixed-point output, converted after the launch (the split form, at least two slices)
+      for (auto& p : m->lm_head.parts) if (p.kind == LK_F8) { p.sk = std::max(p.sk, 2); m->lm_head.fix_out = true; }
       if (m->lm_head.N != V || m->lm_head.K != H) BZ_FAIL(BZ_E_INVALID, "finalize: lm_head shape does not match the config");
     }
   }
@@ -1898,7 +1978,8 @@ static bool prefill_eligible(const bz_model* m, int S, int total_len, bool decod
     for (const FusedLinear* F : {&L.qkv, &L.o, &L.gateup, &L.down}) {
       if (F->parts.size() != 1) return false;
       const LinearDev& P = F->parts[0];
-      const bool dense_ok = P.kind == LK_ROWS && P.wdt == c.act_dtype, q4_ok = bzk_gemm_q4g_rows_ok(P);
+      // (fp8 weights expand to the activation dtype exactly: an fp8 model takes the routes of a dense 16-bit one)
+      const bool dense_ok = (P.kind == LK_ROWS && P.wdt == c.act_dtype) || bzk_gemm_f8w_ok(P, c.act_dtype), q4_ok = bzk_gemm_q4g_rows_ok(P);
       if (!dense_ok && !q4_ok) return false;
       any_dense = any_dense || dense_ok;
     }
@@ -1947,6 +2028,7 @@ static int pf_gemm(bz_model* m, const LinearDev& P, const void* x16, int n, floa
   hipStream_t st = step_stream(m);
   const int act = m->cfg.act_dtype;
   if (P.kind == LK_ROWS) return bzk_gemm_nt(st, act, x16, P.w, P.bias, n, P.N, P.K, act, y, m->pf_ws, m->pf_ws_bytes);
+  if (P.kind == LK_F8) return bzk_gemm_f8w(st, P, act, x16, n, act, y, m->pf_ws, m->pf_ws_bytes);
   if (exact == 2 && bzk_gemm_q4g_i8_ok(P, act)) {
     size_t po; const size_t need = bzk_pf_quant_i8_bytes(n, P.K, &po);
     if (m->pf_xq_bytes < need) { BZ_HIP(hipStreamSynchronize(st)); void* p; BZ_TRY(dev_alloc(m, &p, need)); m->pf_xq = p; m->pf_xq_bytes = need; }
@@ -2293,8 +2375,10 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
   BZ_TRY(find_linear(m, name, &L));
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   const bool q4 = L.kind == LK_Q4G;   // int4 group-quantised weights x f16 activations (the AWQ / GPTQ prefill GEMM), S >= 9
-  if (q4 ? !bzk_gemm_q4g_mfma_ok(L, BZ_F16, S) : (L.kind != LK_ROWS || (L.wdt != BZ_F16 && L.wdt != BZ_BF16)))
-    BZ_FAIL(BZ_E_UNSUPPORTED, "prefill_matmul: '%s' is neither a dense f16 / bf16 weight nor an int4 weight without act-order (S >= 9)", name);
+  const bool f8 = L.kind == LK_F8;    // fp8 weights x the model's 16-bit activations (the W8A16 GEMM)
+  const int f8dt = m->cfg.act_dtype == BZ_F16 ? BZ_F16 : BZ_BF16;
+  if (f8 ? !bzk_gemm_f8w_ok(L, f8dt) : q4 ? !bzk_gemm_q4g_mfma_ok(L, BZ_F16, S) : (L.kind != LK_ROWS || (L.wdt != BZ_F16 && L.wdt != BZ_BF16)))
+    BZ_FAIL(BZ_E_UNSUPPORTED, "prefill_matmul: '%s' is neither a dense f16 / bf16 weight, an fp8 weight nor an int4 weight without act-order (S >= 9)", name);
   if (!x || !y || x->dtype != BZ_F32 || y->dtype != BZ_F32 || S <= 0 || x->nbytes < (size_t)S * L.K * 4 || y->nbytes < (size_t)S * L.N * 4)
     BZ_FAIL(BZ_E_INVALID, "prefill_matmul: x must be F32 [S,%d], y F32 [S,%d]", L.K, L.N);
   BZ_HIP(hipSetDevice(m->dev->id));
@@ -2303,9 +2387,9 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
   const size_t ws_bytes = (size_t)48 << 20;      // split-K partials, as the prefill paths pass them
   BZ_HIP(hipMalloc(&x16, (size_t)S * L.K * 2));
   if (hipMalloc(&ws, ws_bytes) != hipSuccess) { hipFree(x16); BZ_FAIL(BZ_E_OOM, "prefill_matmul: workspace"); }
-  const int xdt = q4 ? BZ_F16 : L.wdt;
+  const int xdt = f8 ? f8dt : q4 ? BZ_F16 : L.wdt;
   int rc = bzk_pf_cvt16(st, xdt, (const float*)x->ptr, (size_t)S * L.K, x16);
-  if (rc == BZ_OK) rc = q4 ? bzk_gemm_q4g_mfma(st, L, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes)
+  if (rc == BZ_OK) rc = f8 ? bzk_gemm_f8w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : q4 ? bzk_gemm_q4g_mfma(st, L, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes)
                            : bzk_gemm_nt(st, L.wdt, x16, L.w, L.bias, S, L.N, L.K, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes);
   hipStreamSynchronize(st);
   hipFree(x16); hipFree(ws);
@@ -3987,12 +4071,13 @@ extern "C" int bz_quant_matmul(bz_model* m, const char* name, const bz_tensor* x
   hipStream_t st = m->dev->stream;
   // op-level results are NOT rounded to the activation dtype: the caller sees the f32 accumulator
   long long* acc = nullptr;
-  if (L.kind != LK_ROWS) BZ_HIP(hipMalloc(&acc, (size_t)L.N * 8));
+  const bool direct = L.kind == LK_ROWS || (L.kind == LK_F8 && L.sk <= 1);   // (an fp8 linear's split form goes through the accumulator like the int4 kinds)
+  if (!direct) BZ_HIP(hipMalloc(&acc, (size_t)L.N * 8));
   int rc = BZ_OK;
   for (int s = 0; s < S && rc == BZ_OK; s++) {
     Pro p{}; p.mode = PRO_PLAIN; p.src = VSrc{(const float*)x->ptr + (size_t)s * L.K, 0}; p.act = BZ_F32; p.perm = L.perm;
     GemvOut o{};
-    if (L.kind == LK_ROWS) { o.direct = (float*)y->ptr + (size_t)s * L.N; rc = bzk_gemv(st, L, p, o, BZ_F32); }
+    if (direct) { o.direct = (float*)y->ptr + (size_t)s * L.N; rc = bzk_gemv(st, L, p, o, BZ_F32); }
     else {
       rc = bzk_zero64(st, acc, L.N);
       o.acc = acc;
@@ -4015,7 +4100,8 @@ extern "C" int bz_dequant(bz_model* m, const char* name, float* host) {
   const size_t n = (size_t)L.N * L.K;
   float* d;
   BZ_HIP(hipMalloc(&d, n * 4));
-  int rc = L.kind == LK_Q4G ? bzk_dequant_q4g(m->dev->stream, L, d) : (L.kind == LK_ROWS ? bzk_dequant_rows(m->dev->stream, L, d) : bzk_dequant_gq(m->dev->stream, L, d));
+  int rc = L.kind == LK_Q4G ? bzk_dequant_q4g(m->dev->stream, L, d) : L.kind == LK_ROWS ? bzk_dequant_rows(m->dev->stream, L, d)
+         : L.kind == LK_F8 ? bzk_dequant_f8(m->dev->stream, L, d) : bzk_dequant_gq(m->dev->stream, L, d);
   std::vector<float> tmp;
   if (rc == BZ_OK) rc = hipStreamSynchronize(m->dev->stream) == hipSuccess ? BZ_OK : BZ_E_HIP;  // the stream is non-blocking
   if (rc == BZ_OK) {

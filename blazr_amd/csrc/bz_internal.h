@@ -53,21 +53,21 @@ struct Pro {
   int f32_sums;        // dense k_gemv_rows2: f32 FMA chains instead of the exact (double) sums -- the DeepSeek-V2 path sets it (k_gemv_rows2's EX)
 };
 
-enum { LK_NONE = 0, LK_Q4G = 1, LK_ROWS = 2, LK_Q4K = 3, LK_Q6K = 4, LK_Q80 = 5, LK_Q5K = 6, LK_Q40 = 7, LK_Q41 = 8, LK_Q50 = 9, LK_Q51 = 10 };
+enum { LK_NONE = 0, LK_Q4G = 1, LK_ROWS = 2, LK_Q4K = 3, LK_Q6K = 4, LK_Q80 = 5, LK_Q5K = 6, LK_Q40 = 7, LK_Q41 = 8, LK_Q50 = 9, LK_Q51 = 10, LK_F8 = 11 };
 
 // Device-resident linear layer in kernel layout.
 struct LinearDev {
   int kind = LK_NONE;
   int N = 0, K = 0, gs = 0;
   int wdt = BZ_F16;         // ROWS: weight dtype
-  void* w = nullptr;        // Q4G: [N/64][K/32][64 lanes][16 B]; ROWS: [N][K]; GGUF kinds: see k_gemv_gq (zeros = Q6_K highs, hdr = headers, scales = f16 d)
-  void* scales = nullptr;   // Q4G: f16 [N/64][G][64]
-  void* zeros = nullptr;    // Q4G: u8  [N/64][G][64]  (AWQ z, GPTQ z+1)
+  void* w = nullptr;        // Q4G: [N/64][K/32][64 lanes][16 B]; ROWS: [N][K]; F8: [N][K] e4m3 bytes; GGUF kinds: see k_gemv_gq (zeros = Q6_K highs, hdr = headers, scales = f16 d)
+  void* scales = nullptr;   // Q4G: f16 [N/64][G][64]; F8: f32 [N]
+  void* zeros = nullptr;    // Q4G: u8  [N/64][G][64]  (AWQ z, GPTQ z+1); F8: u32 [N/16] row-block arrival counters of the split-K form (zero between launches)
   void* hdr = nullptr;      // K-quants: per-superblock headers
   int* perm = nullptr;      // GPTQ act-order
   float* bias = nullptr;
   int gw = 1;               // groups (of gs) per workgroup (split-K granularity)
-  int sk = 1;               // ROWS: split-K count (> 1 => fixed-point accumulator output)
+  int sk = 1;               // ROWS / F8: split-K count (> 1 => fixed-point accumulator output)
   int npf = 2;              // groups of weight loads kept in flight per wave (2 or 4)
   size_t bytes = 0;         // resident bytes
   size_t algo_bytes = 0;    // minimal on-disk bytes (SURVEY 8d accounting)
@@ -221,6 +221,12 @@ bool bzk_gemm_q4g_mfma_ok(const LinearDev& L, int xdt, int rows);   // int4 weig
 int bzk_gemm_q4g_mfma(hipStream_t s, const LinearDev& L, const void* x16, int S, int act, float* y, float* ws = nullptr, size_t ws_bytes = 0);   // ws: split-K partials (short prompts)
 int bzk_gemm_q4g_rows(hipStream_t s, const LinearDev& L, int xdt, const void* x16, int rows, int act, long long* acc, float* y);
 int bzk_rows_choose_sk(int N, int K);
+// FP8 (E4M3) weights, one f32 scale per row (bz_fp8.hip): decode GEMV (direct, or split-K with the finish in the launch), W8A16 MFMA GEMM, read-back
+int bzk_f8_choose_sk(int N, int K);
+int bzk_gemv_f8(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act);
+bool bzk_gemm_f8w_ok(const LinearDev& L, int xdt);
+int bzk_gemm_f8w(hipStream_t s, const LinearDev& L, int dt, const void* x16, int S, int act, float* y, float* ws = nullptr, size_t ws_bytes = 0);
+int bzk_dequant_f8(hipStream_t s, const LinearDev& L, float* out);
 bool bzk_mlp_gq_fusable(const LinearDev& gu, const LinearDev& dn, int H, int I, int act);   // GGUF Q4_K gate/up + Q4_K / Q6_K down, f32 activations
 int bzk_mlp_gq(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, int I, const Pro& pro, long long* acc, long long* zero_buf, int zero_n);
 // dense 16-bit form (k_mlp_dense): down_proj additionally stored slab-major [I / 32][H][32] (bzk_repack_down_slabs at finalize)

@@ -2568,6 +2568,7 @@ int bzk_gq_split3(hipStream_t s, const LinearDev& L, const float* wscale, void* 
 int bzk_argmax_partials(hipStream_t s, const float* v, long long n, float* pval, int* pidx, int nb);
 
 int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act) {
+  if (L.kind == LK_F8) return bzk_gemv_f8(s, L, pro, out, act);   // bz_fp8.hip
   if (L.kind == LK_Q4G && act == BZ_F16 && bzk_gemv_slim_ok(L, pro)) {
     if (!out.acc) BZ_FAIL(BZ_E_INVALID, "int4 gemv needs a fixed-point accumulator");
     const int nks = L.K / 256, ntg = (L.N / 64 + 7) / 8;

@@ -299,8 +299,29 @@ int hf_config_to_pod(const JVal& j, bz_model_config* c, QuantInfo* q) {
   if (const JVal* qc = j.get("quantization_config")) {   // detect_arch.rs:79-90,118-131
     std::string m = qc->str("quant_method"); std::transform(m.begin(), m.end(), m.begin(), ::tolower);
     if (m == "awq") q->method = 1; else if (m == "gptq") q->method = 2;
+    else if (m == "fp8") {
+      // per-tensor / per-channel E4M3 weights (run weight-only: activation_scheme and the input scales are read and ignored); block-scaled FP8 is not built
+      const JVal* wb = qc->get("weight_block_size");
+      if (wb && wb->t != JVal::NUL) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: quantization_config.weight_block_size (block-scaled FP8) is not implemented");
+      q->method = 3;
+    } else if (m == "compressed-tensors") {
+      const std::string fmt = qc->str("format");
+      if (fmt != "float-quantized") BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: compressed-tensors format '%s' is not implemented (float-quantized is)", fmt.c_str());
+      const JVal* groups = qc->get("config_groups");
+      if (!groups || groups->t != JVal::OBJ || groups->o.empty()) BZ_FAIL(BZ_E_INVALID, "config.json: compressed-tensors quantization_config without config_groups");
+      for (auto& g : groups->o) {
+        const JVal* w = g.second.get("weights");
+        if (!w || w->t != JVal::OBJ) BZ_FAIL(BZ_E_INVALID, "config.json: config_groups.%s has no weights entry", g.first.c_str());
+        const std::string ty = w->str("type"), strategy = w->str("strategy", "tensor");
+        if (w->i64("num_bits", 0) != 8 || ty != "float")
+          BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights: num_bits %lld type '%s' is not implemented (8-bit float is)", g.first.c_str(), w->i64("num_bits", 0), ty.c_str());
+        if (strategy != "tensor" && strategy != "channel")
+          BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights.strategy '%s' is not implemented (tensor and channel are)", g.first.c_str(), strategy.c_str());
+      }
+      q->method = 3;
+    }
     q->group_size = (int)qc->i64("group_size", 128);
-    if (q->method && qc->i64("bits", 4) != 4) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: %lld-bit %s is not implemented (4-bit only)", qc->i64("bits", 4), m.c_str());
+    if ((q->method == 1 || q->method == 2) && qc->i64("bits", 4) != 4) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: %lld-bit %s is not implemented (4-bit only)", qc->i64("bits", 4), m.c_str());
   }
   c->vocab = (int)j.i64("vocab_size", 0);
   c->hidden = (int)j.i64("hidden_size", 0);
@@ -400,6 +421,10 @@ void detect_quant(const std::string& dir, const StLoader& st, QuantInfo* q) {
   bool has_qw = false, has_gidx = false;
   for (auto& kv : st.tensors) { if (ends_with(kv.first, ".qweight")) has_qw = true; if (ends_with(kv.first, ".g_idx")) has_gidx = true; }
   if (has_gidx) q->method = 2; else if (has_qw) q->method = 1;    // regular.rs:42-49: GPTQ is probed first
+  else {
+    for (auto& kv : st.tensors)      // an E4M3 weight with its scale beside it
+      if (kv.second.dtype == "F8_E4M3" && ends_with(kv.first, ".weight") && st.find(kv.first + "_scale")) { q->method = 3; break; }
+  }
 }
 
 // boostr::model::detection::detect_architecture_from_names, as pinned by the reference's tests (loader/safetensors/detect_arch.rs:200-315):
@@ -478,12 +503,25 @@ int load_safetensors(bz_device* dev, const std::string& path, bz_model** out, bz
   if (!cfg_path.empty() && ends_with(cfg_path, ".json") && read_text(cfg_path, &text) && json_parse(text.data(), text.size(), &j)) BZ_TRY(hf_config_to_pod(j, &c, &q));
   else BZ_TRY(detect_from_tensors(st, &c));
   detect_quant(dir, st, &q);
-  if (q.method) c.act_dtype = BZ_F16;   // awq.rs:69-71 / gptq.rs: AWQ and GPTQ models always run in f16
+  if (q.method == 1 || q.method == 2) c.act_dtype = BZ_F16;   // awq.rs:69-71 / gptq.rs: AWQ and GPTQ models always run in f16 (FP8 checkpoints keep their torch_dtype)
   if (!c.tie_embeddings && c.arch != BZ_ARCH_MAMBA2 && !st.find("lm_head.weight") && !st.find("lm_head.qweight")) c.tie_embeddings = 1;
+  for (auto& kv : st.tensors)      // DeepSeek-style block-scaled FP8 ships inverse scales per 128 x 128 block
+    if (ends_with(kv.first, ".weight_scale_inv")) BZ_FAIL(BZ_E_UNSUPPORTED, "tensor '%s': .weight_scale_inv (block-scaled FP8) is not implemented", kv.first.c_str());
   bz_model* m = nullptr;
   BZ_TRY(bz_model_create(dev, &c, &m));
   int rc = BZ_OK;
   std::vector<uint16_t> tmp16; std::vector<float> f32a, f32b;
+  // a small f32 vector from an F32 / F16 / BF16 tensor (FP8 scales and biases)
+  auto to_f32 = [](const StTensor* t, size_t n, std::vector<float>* out) {
+    const size_t es = t->dtype == "F32" ? 4 : (t->dtype == "F16" || t->dtype == "BF16") ? 2 : 0;
+    if (!es || t->bytes != n * es) return false;
+    out->resize(n);
+    for (size_t i = 0; i < n; i++) {
+      if (es == 4) memcpy(&(*out)[i], t->data + i * 4, 4);
+      else { uint16_t h; memcpy(&h, t->data + i * 2, 2); if (t->dtype == "F16") (*out)[i] = f16_to_f32(h); else { const uint32_t u = (uint32_t)h << 16; memcpy(&(*out)[i], &u, 4); } }
+    }
+    return true;
+  };
   for (auto& kv : st.tensors) {
     const std::string& name = kv.first; const StTensor& t = kv.second;
     if (rc != BZ_OK) break;
@@ -530,11 +568,32 @@ int load_safetensors(bz_device* dev, const std::string& path, bz_model** out, bz
       continue;
     }
     if (ends_with(name, ".bias") && st.find(name.substr(0, name.size() - 5) + ".qweight")) continue;   // gptq.rs:158-166: handled with its layer
+    // FP8 (E4M3) linears: <linear>.weight F8_E4M3 [N,K] + <linear>.weight_scale ([] / [1] / [N] / [N,1]) + optional <linear>.bias; run weight-only, so the
+    // activation scales (<linear>.input_scale) are read past
+    if (ends_with(name, ".weight_scale") && st.find(name.substr(0, name.size() - 6)) && st.find(name.substr(0, name.size() - 6))->dtype == "F8_E4M3") continue;
+    if (ends_with(name, ".input_scale") && st.find(name.substr(0, name.size() - 12) + ".weight_scale")) continue;
+    if (ends_with(name, ".bias") && st.find(name.substr(0, name.size() - 5) + ".weight") && st.find(name.substr(0, name.size() - 5) + ".weight")->dtype == "F8_E4M3") continue;
+    if (t.dtype == "F8_E4M3") {
+      if (!ends_with(name, ".weight") || t.shape.size() != 2) { rc = BZ_E_UNSUPPORTED; bz_set_error("tensor '%s': F8_E4M3 is read for 2-D <linear>.weight tensors only", name.c_str()); break; }
+      const std::string base = name.substr(0, name.size() - 7);
+      const StTensor* sc = st.find(base + ".weight_scale"); const StTensor* bi = st.find(base + ".bias");
+      const int64_t N = t.shape[0], K = t.shape[1];
+      if (!sc) { rc = BZ_E_INVALID; bz_set_error("fp8 layer '%s': no .weight_scale beside the F8_E4M3 weight", base.c_str()); break; }
+      size_t ns = 0;
+      const bool shape_ok = sc->shape.size() <= 2 && shape_elems(sc->shape, &ns) && (ns == 1 || (ns == (size_t)N && sc->shape[0] == N));
+      if (!shape_ok || !to_f32(sc, ns, &f32a))
+        { rc = BZ_E_INVALID; bz_set_error("fp8 layer '%s': weight_scale must be F32 / F16 / BF16 of shape [], [1], [%lld] or [%lld,1]", base.c_str(), (long long)N, (long long)N); break; }
+      if (bi && (bi->shape.size() != 1 || bi->shape[0] != N || !to_f32(bi, (size_t)N, &f32b)))
+        { rc = BZ_E_INVALID; bz_set_error("fp8 layer '%s': bias must be F32 / F16 / BF16 [%lld]", base.c_str(), (long long)N); break; }
+      if (N <= 0 || K <= 0 || t.bytes != (size_t)N * (size_t)K) { rc = BZ_E_INVALID; bz_set_error("fp8 layer '%s': weight bytes do not match its shape", base.c_str()); break; }
+      rc = bz_model_add_fp8(m, name.c_str(), N, K, t.data, f32a.data(), (int64_t)ns, bi ? f32b.data() : nullptr);
+      continue;
+    }
     const int dt = st_dtype(t.dtype);
     if (dt != BZ_F32 && dt != BZ_F16 && dt != BZ_BF16) { rc = BZ_E_UNSUPPORTED; bz_set_error("tensor '%s': dtype %s is not supported", name.c_str(), t.dtype.c_str()); break; }
     if (t.shape.empty() || t.shape.size() > 3) { rc = BZ_E_UNSUPPORTED; bz_set_error("tensor '%s': rank %zu is not supported", name.c_str(), t.shape.size()); break; }
     const void* data = t.data; int use_dt = dt;
-    if (q.method && dt == BZ_BF16) {     // awq.rs:93-103: BF16 tensors of an AWQ / GPTQ checkpoint are cast to F16
+    if ((q.method == 1 || q.method == 2) && dt == BZ_BF16) {     // awq.rs:93-103: BF16 tensors of an AWQ / GPTQ checkpoint are cast to F16
       const size_t ne = t.bytes / 2;
       tmp16.resize(ne);
       for (size_t i = 0; i < ne; i++) tmp16[i] = bf16_to_f16_bits(((const uint16_t*)t.data)[i]);
@@ -827,7 +886,7 @@ extern "C" int bz_config_from_hf_json(const char* json_text, bz_model_config* cf
   if (!json_parse(json_text, strlen(json_text), &j)) BZ_FAIL(BZ_E_INVALID, "config.json: JSON syntax error");
   QuantInfo q;
   BZ_TRY(hf_config_to_pod(j, cfg, &q));
-  if (q.method) cfg->act_dtype = BZ_F16;
+  if (q.method == 1 || q.method == 2) cfg->act_dtype = BZ_F16;
   if (qinfo) { qinfo->quant_method = q.method; qinfo->group_size = q.group_size; qinfo->torch_dtype = q.has_dtype ? q.torch_dtype : -1; }
   return BZ_OK;
   BZ_API_END

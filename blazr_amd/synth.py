@@ -48,6 +48,15 @@ PRESETS = {
     "tiny-q4km": dict(arch="llama", hidden=256, n_layers=8, n_heads=4, n_kv_heads=2, head_dim=64, inter=512, vocab=1024,
                       rms_eps=1e-5, rope_theta=10000.0, act_dtype="f32", quant="q4_k_m", max_seq_len=256,
                       tie_embeddings=False, rope_interleaved=1),
+    # FP8 (E4M3) weight checkpoints (the *-FP8 / *-FP8-dynamic releases): one byte per weight, a scale per output channel, 16-bit head and embeddings
+    "llama3.1-8b-fp8": dict(arch="llama", hidden=4096, n_layers=32, n_heads=32, n_kv_heads=8, head_dim=128, inter=14336,
+                            vocab=128256, rms_eps=1e-5, rope_theta=500000.0, act_dtype="bf16", quant="fp8", fp8_strategy="channel",
+                            max_seq_len=2048, tie_embeddings=False),
+    "tiny-fp8": dict(arch="llama", hidden=256, n_layers=2, n_heads=4, n_kv_heads=2, head_dim=64, inter=512, vocab=1024,
+                     rms_eps=1e-5, rope_theta=10000.0, act_dtype="bf16", quant="fp8", fp8_strategy="channel", max_seq_len=256,
+                     tie_embeddings=True,
+                     rope_scaling=dict(type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                                       original_max_position_embeddings=64)),
     "tiny-q8_0": dict(arch="llama", hidden=256, n_layers=2, n_heads=4, n_kv_heads=2, head_dim=64, inter=512, vocab=1024,
                       rms_eps=1e-5, rope_theta=10000.0, act_dtype="f32", quant="q8_0", max_seq_len=256,
                       tie_embeddings=False, rope_interleaved=1),
@@ -149,6 +158,48 @@ def dense_linear(name, N, K, dtype, std=0.02, seed=BASE_SEED):
     return dict(kind="dense", N=N, K=K, weight=_store(_normal(_rng(name, seed), (N, K), std), dtype))
 
 
+def e4m3_table():
+    """f32 value of every OCP E4M3 (e4m3fn) code; the two NaN codes 0x7F / 0xFF read NaN."""
+    c = np.arange(256)
+    e, f = (c >> 3) & 15, (c & 7).astype(np.float64)
+    v = np.where(e == 0, f * 2.0 ** -9, (1.0 + f / 8.0) * 2.0 ** (e.astype(np.float64) - 7.0))
+    v = np.where((c & 0x7F) == 0x7F, np.nan, v)
+    return np.where(c & 0x80, -v, v).astype(np.float32)
+
+
+FINITE_E4M3 = np.array([c for c in range(256) if (c & 0x7F) != 0x7F], dtype=np.uint8)
+
+
+def e4m3_encode(x):
+    """f32 array -> E4M3 codes: clamp to +-448, round to nearest, ties to the even code (codes ascend with the magnitude)."""
+    pos = e4m3_table()[:127].astype(np.float64)
+    a = np.minimum(np.abs(np.asarray(x, dtype=np.float64)), 448.0)
+    hi = np.clip(np.searchsorted(pos, a, side="left"), 1, 126)
+    lo = hi - 1
+    dl, dh = a - pos[lo], pos[hi] - a
+    code = np.where((dl < dh) | ((dl == dh) & (lo % 2 == 0)), lo, hi).astype(np.uint8)
+    return code | (np.signbit(np.asarray(x, dtype=np.float32)).astype(np.uint8) << 7)
+
+
+def fp8_linear(name, N, K, strategy, bias=False, std=0.02, seed=BASE_SEED):
+    """E4M3 weight bytes [N, K] with one scale per output channel (`channel`) or per tensor (`tensor`): W = scale . e4m3(weight).
+    Like the int4 fixtures the codes are drawn directly (uniform over the 254 finite codes: an 8B model in seconds, where quantising
+    normal weights takes minutes); the scales put the weights' standard deviation near `std` and are bf16-representable (8 significant
+    bits), so scale . e4m3 has at most 12 and is exact in f32."""
+    if strategy not in ("channel", "tensor"):
+        raise ValueError(strategy)
+    r = _rng(name, seed)
+    q = r.integers(0, 256, size=(N, K), dtype=np.uint8)
+    q[(q & 0x7F) == 0x7F] ^= 1                                   # the two NaN codes -> +-448
+    rms = float(np.sqrt(np.mean(np.square(e4m3_table()[FINITE_E4M3].astype(np.float64)))))
+    n_scale = N if strategy == "channel" else 1
+    scale = _repr((r.uniform(0.7, 1.4, size=n_scale) * (std / rms)).astype(np.float32), "bf16")
+    d = dict(kind="fp8", N=N, K=K, strategy=strategy, weight=q, scale=scale, bias=None)
+    if bias:
+        d["bias"] = _repr(r.standard_normal(N, dtype=np.float32) * 0.01, "bf16")
+    return d
+
+
 def gguf_blocks(name, ggml_type, N, K, seed=BASE_SEED):
     """Random but well-conditioned ggml blocks: rows of K weights, N rows -> uint8 [N, row_bytes]."""
     r = _rng(name, seed)
@@ -194,6 +245,8 @@ def _linear(cfg, name, N, K, layer=None, role=None, seed=BASE_SEED):
     if q == "q4_k_m":
         six = role in ("v", "down") and q4km_uses_q6k(layer, cfg["n_layers"])
         return gguf_blocks(name, GGML_Q6_K if six else GGML_Q4_K, N, K, seed)
+    if q == "fp8":
+        return fp8_linear(name, N, K, cfg.get("fp8_strategy", "channel"), bias=cfg.get("bias", False), seed=seed)
     return dense_linear(name, N, K, cfg["act_dtype"], seed=seed)
 
 
@@ -272,6 +325,9 @@ def algorithmic_bytes_per_token(cfg):
     elif q == "q8_0":
         wb = lin // 32 * 34
         head = V * H // 32 * 34
+    elif q == "fp8":
+        wb = lin + L * ((nq + 2 * nkv) * hd + 2 * H + 2 * I) * 4      # one byte per weight + an f32 scale per output row
+        head = V * H * act_b
     elif q == "q4_k_m":
         six = sum(q4km_uses_q6k(i, L) for i in range(L))
         per_q6 = H * nkv * hd + H * I

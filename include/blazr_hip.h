@@ -129,6 +129,13 @@ int bz_model_add_gptq(bz_model* m, const char* name, int64_t N, int64_t K, const
                       const uint32_t* qzeros, const int32_t* g_idx, const float* bias, int group_size);
 /* VarMap::from_gguf (gguf.rs:33): raw ggml blocks of one tensor, N rows of K weights */
 int bz_model_add_gguf(bz_model* m, const char* name, int ggml_type, int64_t N, int64_t K, const void* raw_blocks);
+/* FP8 (OCP E4M3, e4m3fn) weights of the *-FP8 / *-FP8-dynamic SafeTensors releases, run weight-only (W8A16): W[n][k] = scale[n] e4m3(weight[n][k]), one scale
+ * per tensor (n_scale 1, broadcast) or per output row (n_scale N), optional f32 bias.  y = R(f32(scale[n] sum_k x[k] e4m3(weight[n][k])) + bias[n]): the sum
+ * exact, the scale applied once to the finished sum.  N % 64 or K % 64: BZ_E_UNSUPPORTED; n_scale other than 1 or N, a non-finite scale, a NaN code (0x7F /
+ * 0xFF) in the weights: BZ_E_INVALID, each naming the tensor.  Llama family only (Mamba2 / DeepSeek-V2: BZ_E_UNSUPPORTED at bz_model_finalize).  Beyond the
+ * reference.  New symbol only: BZ_ABI_VERSION is unchanged. */
+int bz_model_add_fp8(bz_model* m, const char* name, int64_t N, int64_t K, const uint8_t* weight /*[N][K] e4m3*/, const float* scale, int64_t n_scale /*1 or N*/,
+                     const float* bias /*nullable [N]*/);
 /* LoadedModel::load(&config.model, &mut vb) (awq.rs:133-136): validates names/shapes, repacks weights into the
  * kernels' HBM layout, builds RoPE tables and workspaces.  Host copies passed to add_* may be freed afterwards. */
 int bz_model_finalize(bz_model* m);
@@ -147,7 +154,7 @@ enum { BZ_LAYER_TRANSFORMER = 0, BZ_LAYER_MAMBA2 = 1, BZ_LAYER_MAMBA3 = 2, BZ_LA
 typedef struct { int32_t format; /* 0 HuggingFace ("model." prefix), 1 Oxidizr */ int32_t num_layers, tie_word_embeddings; uint8_t layer_types[512]; } bz_detected_arch;
 /* boostr::model::detection::detect_architecture_from_names as the reference's tests pin it (loader/safetensors/detect_arch.rs:200-315) */
 int bz_detect_architecture_from_names(const char* const* names, int n, bz_detected_arch* out);
-typedef struct { int32_t quant_method; /* 0 none, 1 awq, 2 gptq */ int32_t group_size; int32_t torch_dtype; /* BZ_* or -1 */ } bz_quant_info;
+typedef struct { int32_t quant_method; /* 0 none, 1 awq, 2 gptq, 3 fp8 */ int32_t group_size; int32_t torch_dtype; /* BZ_* or -1 */ } bz_quant_info;
 /* HuggingFaceConfig::from_json(..).to_universal() + detect_dtype_from_config (loader/safetensors/config.rs:14-70,83-95): HF config.json text ->
  * config POD; quantization_config (detect_arch.rs:79-90,118-131,146-196) -> quant info.  AWQ / GPTQ force f16 (awq.rs:69-71). */
 int bz_config_from_hf_json(const char* json_text, bz_model_config* cfg, bz_quant_info* quant);
