@@ -182,6 +182,28 @@ class RowsAttnPlan(C.Structure):
     _fields_ = [("kernel", C.c_int), ("scalar_limit", C.c_int), ("grid_slices", C.c_int), ("rows_per_pass", C.c_int), ("ws_bytes", C.c_size_t)]
 
 
+class PromptTraits(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ("arch", "act_dtype", "hidden", "inter", "n_layers", "n_heads", "n_kv_heads", "head_dim", "rep", "sliding_window",
+                                        "sliding_window_pattern", "shapes_ok", "proj_16", "any_dense", "exact_cap", "gq_all", "gq_max_k")] +
+                [("gq_max_n3k", C.c_ulonglong)] +
+                [(n, C.c_int) for n in ("head_rows", "head_gemm", "spec_head", "mla_q_lora_rank", "mla_kv_lora_rank", "mla_rope_dim", "mla_nope_dim", "mla_v_dim",
+                                        "ds_dims_ok", "ds_weights_act", "ssm_scan_ok", "ssm_groups_ok", "ssm_proj_ok")])
+
+
+class PromptSwitches(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("prefill_min", "no_mfma_prefill", "no_gguf_prefill", "exact", "exact_max", "exact_i8_max")]
+
+
+class PromptPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("route", "exact", "attn", "head", "chunk")]
+
+
+PLAN_PROMPT, PLAN_DECODE_BATCH, PLAN_VERIFY = 0, 1, 2
+ROUTE_STEPS, ROUTE_ROWS, ROUTE_DSV2, ROUTE_MAMBA = 0, 1, 2, 3
+PF_ATTN_NONE, PF_ATTN_MFMA, PF_ATTN_SCALAR, PF_ATTN_SCALAR_EXACT, PF_ATTN_ROWS = 0, 1, 2, 3, 4
+HEAD_STEP, HEAD_GEMM, HEAD_GEMV_ROWS, HEAD_SPEC = 0, 1, 2, 3
+
+
 class EngineStats(C.Structure):
     _fields_ = [("replays", C.c_int64), ("free_blocks", C.c_int32), ("total_blocks", C.c_int32), ("park_blocks", C.c_int32), ("live_rows", C.c_int32),
                 ("admitted", C.c_int32), ("waiting", C.c_int32), ("unread", C.c_int32), ("prompt_tokens", C.c_int64), ("generated_tokens", C.c_int64),
@@ -310,6 +332,8 @@ SYMBOLS = {
     "bz_paged_attn_decode_rows": (C.c_int, [P, P, P, C.c_int, P, C.c_int, P, C.c_int, P]),
     "bz_rows_attn_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P]),
     "bz_rows_attn_slice_len": (C.c_int, [C.c_int]),
+    "bz_model_prompt_traits": (C.c_int, [P, C.POINTER(PromptTraits)]),
+    "bz_prompt_plan": (C.c_int, [C.POINTER(PromptTraits), C.POINTER(PromptSwitches), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PromptPlan)]),
     "bz_kv_insert": (C.c_int, [P, P, C.c_int, C.c_int, P, P]),
     "bz_rope_caches": (C.c_int, [P, P, P]),
     "bz_grammar_compile": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(P)]),

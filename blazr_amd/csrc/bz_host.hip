@@ -299,6 +299,7 @@ struct bz_model {
   bz_device* dev = nullptr;
   bz_model_config cfg;
   bool finalized = false;
+  bz_prompt_traits_t traits{};   // what the route decision (bz_route.hip) reads of the model, filled at finalize: no linear changes its format afterwards
   std::unordered_map<std::string, RawTensor> raw;
   std::vector<LayerDev> layers;
   void* embed = nullptr; int embed_dt = BZ_F16;
@@ -911,6 +912,68 @@ static float mla_softmax_scale(const bz_model_config& c) {
   return 1.0f / sqrtf((float)(c.mla_nope_dim + c.mla_rope_dim)) * ms * ms;     // HF DeepseekV2Attention: softmax_scale * mscale * mscale
 }
 
+// The facts the route decision (bz_route.hip: bz_prompt_plan) reads of a model, collected once: every finalize ends here.  Nothing changes a linear's kind,
+// dtype, perm, bias, N, K or fix_out afterwards (LoRA adapters live in their own table, the GGUF split cache in gq_pf).
+static void fill_prompt_traits(bz_model* m) {
+  const bz_model_config& c = m->cfg;
+  bz_prompt_traits_t& t = m->traits;
+  t = bz_prompt_traits_t{};
+  const int act = c.act_dtype;
+  t.arch = c.arch; t.act_dtype = act; t.hidden = c.hidden; t.inter = c.inter; t.n_layers = c.n_layers; t.n_heads = c.n_heads; t.n_kv_heads = c.n_kv_heads;
+  t.head_dim = c.head_dim; t.rep = c.n_kv_heads > 0 ? c.n_heads / c.n_kv_heads : 0;
+  t.sliding_window = c.sliding_window; t.sliding_window_pattern = c.sliding_window_pattern;
+  const bool act16 = act == BZ_F16 || act == BZ_BF16;
+  auto dense_act = [&](const FusedLinear& F) { return F.parts.size() == 1 && F.parts[0].kind == LK_ROWS && F.parts[0].wdt == act; };
+  const FusedLinear& LH = m->lm_head;
+  t.head_rows = LH.parts.size() == 1 && LH.parts[0].kind == LK_ROWS && !LH.fix_out;
+  t.head_gemm = !LH.parts.empty() && LH.parts[0].wdt == act && LH.parts[0].K % 64 == 0;
+  t.spec_head = LH.parts.size() == 1 && !LH.fix_out && bzk_spec_head_ok(LH.parts[0], act, c.hidden);
+  if (c.arch == BZ_ARCH_LLAMA) {
+    t.shapes_ok = !(c.hidden % 64 || (c.n_heads * c.head_dim) % 64 || c.inter % 64 || c.head_dim % 8 || 256 % (c.head_dim / 8)) &&
+                  (t.rep == 1 || t.rep == 2 || t.rep == 4 || t.rep == 8);
+    t.proj_16 = act16; t.gq_all = 1; t.exact_cap = 2;
+    for (const LayerDev& L : m->layers)
+      for (const FusedLinear* F : {&L.qkv, &L.o, &L.gateup, &L.down}) {
+        // 16-bit activations: dense in the activation dtype or fp8 (fp8 weights expand to it exactly: the MFMA GEMM), or int4 without act-order (the
+        // multi-row dot4 GEMM; exact_cap: what the exact rows can use of it)
+        const bool one = F->parts.size() == 1;
+        const bool dense_ok = one && ((F->parts[0].kind == LK_ROWS && F->parts[0].wdt == act) || bzk_gemm_f8w_ok(F->parts[0], act));
+        const bool q4_ok = one && bzk_gemm_q4g_rows_ok(F->parts[0]);
+        if (!dense_ok && !q4_ok) t.proj_16 = 0;
+        if (dense_ok) t.any_dense = 1;
+        t.exact_cap = !q4_ok ? 0 : std::min(t.exact_cap, bzk_gemm_q4g_i8_ok(F->parts[0], BZ_F16) ? 2 : 1);
+        // f32 activations (GGUF models): every part a block format, no bias, one K per fused linear
+        unsigned long long ntot = 0;
+        if (F->parts.empty()) t.gq_all = 0;
+        for (const LinearDev& P : F->parts) { if (!bzk_gq_split_ok(P) || P.bias || P.K != F->parts[0].K) t.gq_all = 0; ntot += (unsigned long long)P.N; }
+        if (!F->parts.empty()) { t.gq_max_k = std::max(t.gq_max_k, F->parts[0].K); t.gq_max_n3k = std::max(t.gq_max_n3k, ntot * 3ull * (unsigned long long)F->parts[0].K); }
+      }
+  } else if (c.arch == BZ_ARCH_DEEPSEEK2) {
+    t.mla_q_lora_rank = c.mla_q_lora_rank; t.mla_kv_lora_rank = c.mla_kv_lora_rank; t.mla_rope_dim = c.mla_rope_dim; t.mla_nope_dim = c.mla_nope_dim; t.mla_v_dim = c.mla_v_dim;
+    t.ds_dims_ok = !(c.hidden % 64 || (c.n_heads * c.mla_v_dim) % 64 || (c.moe_n_experts > 0 && c.moe_inter % 64));
+    t.ds_weights_act = 1;
+    for (const DsLayerDev& L : m->dlayers) {
+      if (!dense_act(L.qkva) || !dense_act(L.o) || L.kv_b_dt != act) t.ds_weights_act = 0;
+      if (L.is_moe) { if (L.e_dt != act) t.ds_weights_act = 0; continue; }
+      if (!dense_act(L.gateup) || !dense_act(L.down)) t.ds_weights_act = 0;
+      if (c.inter % 64) t.ds_dims_ok = 0;
+    }
+  } else if (c.arch == BZ_ARCH_MAMBA2) {
+    t.ssm_scan_ok = bzk_ssm_scan_ok(c.ssm_head_dim, c.ssm_d_state, c.ssm_n_groups, c.ssm_conv_kernel);
+    t.ssm_groups_ok = c.ssm_n_groups > 0 && c.ssm_d_inner % c.ssm_n_groups == 0 && c.ssm_n_heads % c.ssm_n_groups == 0;
+    t.ssm_proj_ok = 1;
+    for (const MambaLayerDev& L : m->mlayers)
+      for (const FusedLinear* F : {&L.in_proj, &L.out_proj}) if (!dense_act(*F) || F->parts[0].K % 64) t.ssm_proj_ok = 0;
+  }
+}
+extern "C" int bz_model_prompt_traits(const bz_model* m, bz_prompt_traits_t* out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || !out) BZ_FAIL(BZ_E_INVALID, "prompt_traits: model not finalized / null argument");
+  *out = m->traits;
+  return BZ_OK;
+  BZ_API_END
+}
+
 static int finalize_mamba2(bz_model* m);
 static int finalize_dsv2(bz_model* m);
 
@@ -1032,6 +1095,7 @@ extern "C" int bz_model_finalize(bz_model* m) {
       for (auto& L : F->parts) { m->resident += L.bytes; m->per_token += L.algo_bytes; }
   for (auto& L : m->lm_head.parts) { m->resident += L.bytes; m->per_token += L.algo_bytes; }
   BZ_HIP(hipDeviceSynchronize());   // null-stream memsets above vs. the non-blocking compute stream
+  fill_prompt_traits(m);
   m->finalized = true;
   return BZ_OK;
   BZ_API_END
@@ -1229,6 +1293,7 @@ static int finalize_dsv2(bz_model* m) {
   for (auto& L : m->lm_head.parts) { m->resident += L.bytes; per_token += L.algo_bytes; }
   m->per_token = per_token + (size_t)H * bz_dtype_size(m->embed_dt) + (size_t)H * act_b;
   BZ_HIP(hipDeviceSynchronize());
+  fill_prompt_traits(m);
   m->finalized = true;
   return BZ_OK;
 }
@@ -1312,6 +1377,7 @@ static int finalize_mamba2(bz_model* m) {
   }
   for (auto& L : m->lm_head.parts) { m->resident += L.bytes; m->per_token += L.algo_bytes; }
   BZ_HIP(hipDeviceSynchronize());
+  fill_prompt_traits(m);
   m->finalized = true;
   return BZ_OK;
 }
@@ -1942,56 +2008,6 @@ static int emit_logits(bz_model* m, bz_tensor* logits_out, int row) {
 // batched prefill on the matrix cores (dense f16 / bf16 Llama-family models): SURVEY.md 8 row K4
 // ---------------------------------------------------------------------------------------------------------
 static int find_linear(bz_model* m, const char* name, LinearDev* out);
-static int prefill_min_rows() {
-  static const int v = getenv("BZ_NO_MFMA_PREFILL") ? (1 << 30) : (getenv("BZ_PREFILL_MIN") ? atoi(getenv("BZ_PREFILL_MIN")) : 8);
-  return v;
-}
-static int prefill_exact(const bz_model* m, int n, bool decode_batch);
-static bool prefill_eligible(const bz_model* m, int S, int total_len, bool decode_batch = false) {
-  const bz_model_config& c = m->cfg;
-  static const bool no_gq = getenv("BZ_NO_GGUF_PREFILL") != nullptr;
-  if (c.arch != BZ_ARCH_LLAMA || S < prefill_min_rows() || (c.act_dtype != BZ_F16 && c.act_dtype != BZ_BF16 && (c.act_dtype != BZ_F32 || no_gq))) return false;
-  if (c.hidden % 64 || (c.n_heads * c.head_dim) % 64 || c.inter % 64 || c.head_dim % 8 || 256 % (c.head_dim / 8)) return false;
-  const int rep = c.n_heads / c.n_kv_heads;
-  if (rep != 1 && rep != 2 && rep != 4 && rep != 8) return false;
-  // the scalar attention kernel keeps the scores of the whole context in LDS: where prefill_dense would pick it (exact rows, f32 activations, no MFMA
-  // form) and the context does not fit, the prompt runs on the decode step, token by token, whose attention has no context limit
-  const bool attn_exact = !decode_batch && (prefill_exact(m, S, false) != 0 || c.act_dtype == BZ_F32);
-  const bool attn_mfma = !decode_batch && c.act_dtype != BZ_F32 && !attn_exact && bzk_pf_attn_mfma_ok(c.head_dim, rep);
-  if (!attn_mfma && (!decode_batch || !bzk_pf_attn_mfma_ok(c.head_dim, rep)) &&
-      bzk_pf_attn_smem(c.n_heads, c.n_kv_heads, c.head_dim, window_keys(c, total_len), attn_exact) > 160 * 1024) return false;   // (a row's scores: its window)
-  // every projection either dense in the activation dtype (MFMA GEMM) or int4 without act-order (multi-row dot4 GEMM)
-  if (c.act_dtype == BZ_F32) {
-    // f32 activations (GGUF models): every projection in a block format, no bias, same K in all parts of a fused linear; the head stays the decode GEMV
-    for (const LayerDev& L : m->layers)
-      for (const FusedLinear* F : {&L.qkv, &L.o, &L.gateup, &L.down}) {
-        if (F->parts.empty()) return false;
-        unsigned long long ntot = 0;
-        for (const LinearDev& P : F->parts) { if (!bzk_gq_split_ok(P) || P.bias || P.K != F->parts[0].K) return false; ntot += (unsigned long long)P.N; }
-        // the split operands go through ONE 16-bit GEMM over 3 K whose element offsets are 32-bit (bzk_gemm_nt)
-        if (ntot * 3ull * (unsigned long long)F->parts[0].K >= (1ull << 32) || (unsigned long long)std::min(S, 2048) * 3ull * (unsigned long long)F->parts[0].K >= (1ull << 32)) return false;
-      }
-    return true;
-  }
-  bool any_dense = false;
-  for (const LayerDev& L : m->layers)
-    for (const FusedLinear* F : {&L.qkv, &L.o, &L.gateup, &L.down}) {
-      if (F->parts.size() != 1) return false;
-      const LinearDev& P = F->parts[0];
-      // (fp8 weights expand to the activation dtype exactly: an fp8 model takes the routes of a dense 16-bit one)
-      const bool dense_ok = (P.kind == LK_ROWS && P.wdt == c.act_dtype) || bzk_gemm_f8w_ok(P, c.act_dtype), q4_ok = bzk_gemm_q4g_rows_ok(P);
-      if (!dense_ok && !q4_ok) return false;
-      any_dense = any_dense || dense_ok;
-    }
-  // dense 16-bit models: the decode GEMVs carry exact sums (piece_dot_d), the MFMA GEMMs f32 ones -- prompts of up to BZ_EXACT_PREFILL_MAX (16) rows stay on the
-  // decode kernels, token by token, so that their rows are the oracle's bits like the int4 models' exact rows (bz_host.hip prefill_exact; BZ_EXACT_PREFILL=0: never)
-  if (any_dense && !decode_batch) {
-    static const int env = getenv("BZ_EXACT_PREFILL") ? atoi(getenv("BZ_EXACT_PREFILL")) : -1;
-    static const int max_rows = getenv("BZ_EXACT_PREFILL_MAX") ? atoi(getenv("BZ_EXACT_PREFILL_MAX")) : 16;
-    if (env != 0 && (env > 0 || S <= max_rows)) return false;
-  }
-  return m->lm_head.parts.size() == 1 && m->lm_head.parts[0].kind == LK_ROWS && !m->lm_head.fix_out;
-}
 // split-K partials of the prefill GEMMs (bzk_gemm_nt / bzk_gemm_q4g_mfma)
 static int ensure_pf_ws(bz_model* m) {
   if (m->pf_ws) return BZ_OK;
@@ -2077,29 +2093,6 @@ static int pf_gemm_gq(bz_model* m, const FusedLinear& F, const float* xf, int n,
   return bzk_gemm_nt(st, BZ_F16, m->pf_x3, w3, nullptr, n, N, 3 * K, BZ_F32, y, m->pf_ws, m->pf_ws_bytes, m->pf_rscale);
 }
 
-// EXACT prompt rows (f16 int4 models): the multi-row form of the decode kernels' integer arithmetic for every projection, the exact scalar attention and
-// the decode lm_head -- a prompt row is then the same bits as the decode step would produce for it (and as the oracle's: tests/test_gpu_exact_prefill.py).
-// One pass over the weights serves 8 rows and costs ~3.9 ms at the 8B AWQ shape (13 launches per layer), the MFMA path has a floor of ~4.6 ms: up to
-// BZ_EXACT_PREFILL_MAX rows (default 16: two passes) exactness is nearly free (32 rows: 15.8 vs 4.8 ms); longer prompts take the matrix cores, whose f32 accumulation order differs from the exact sums: ~1e-6 per GEMM, which the f16 roundings
-// of a deep model amplify to the f16 noise floor (profiles/r03_prefill_parity_depth.txt).  BZ_EXACT_PREFILL=1 forces the exact rows for every prompt length.
-// returns 0 (MFMA f16 path), 1 (exact rows) or 2 (exact integer-MFMA GEMMs: BZ_EXACT_PREFILL=2 for every prompt, or prompts of up to BZ_EXACT_I8_MAX rows)
-static int prefill_exact(const bz_model* m, int n, bool decode_batch) {
-  static const int env = getenv("BZ_EXACT_PREFILL") ? atoi(getenv("BZ_EXACT_PREFILL")) : -1;     // -1: by prompt length
-  static const int max_rows = getenv("BZ_EXACT_PREFILL_MAX") ? atoi(getenv("BZ_EXACT_PREFILL_MAX")) : 16;
-  static const int max_i8 = getenv("BZ_EXACT_I8_MAX") ? atoi(getenv("BZ_EXACT_I8_MAX")) : 0;
-  if (env == 0 || decode_batch || m->cfg.act_dtype != BZ_F16) return 0;
-  int mode = 0;
-  if (env == 1) mode = 1; else if (env >= 2) mode = n <= 16 ? 1 : 2;
-  else if (n <= max_rows) mode = 1; else if (n <= max_i8) mode = 2;
-  if (!mode) return 0;
-  for (const LayerDev& L : m->layers)
-    for (const FusedLinear* F : {&L.qkv, &L.o, &L.gateup, &L.down}) {
-      if (F->parts.size() != 1 || !bzk_gemm_q4g_rows_ok(F->parts[0])) return 0;
-      if (mode == 2 && !bzk_gemm_q4g_i8_ok(F->parts[0], BZ_F16)) mode = 1;
-    }
-  return mode;
-}
-
 // tokens [S] at positions pos0 .. pos0+S-1; `slots` (paged only): device i32 [S].  Logits of the last row (or all rows) -> logits_out.
 // per-row context of a decode batch: row r is its own sequence (position row_pos[r], block-table row r); nullptr row_pos = one prompt
 // row_lora: device LoRA slot id per row (-1: none); nullptr = every row under the model's current-slot scalar (prompts, the engine's prompt chunks)
@@ -2127,19 +2120,55 @@ static int rows_attn_prepare(bz_model* m, const bz_paged_kv* kv, int N, int decl
   }
   return BZ_OK;
 }
-// speculative verify (llama_verify_rows): the head of all S <= 16 rows is the multi-row exact lm_head (bz_speculative.hip), which streams the matrix once per
-// 8 rows and leaves per-row argmax partials in m->sp_pval / m->sp_pidx; logits [S][vocab] device
-struct SpecHeadOut { float* logits; };
+// The tail of a prompt chunk, shared by the three prompt functions: the logits of chunk rows s0 .. s0 + n - 1 of S (residual stream h, deferred residual prev),
+// every row (`all`) or the last of the prompt, by the plan's head.  GEMM: several rows wanted -- final norm rows + one MFMA GEMM that streams the lm_head once;
+// otherwise the decode lm_head GEMV per row (final norm fused as its prologue), or the decode step's head on the row (STEP: quantised lm_head).  SPEC (the
+// speculative verify, S <= 16): the multi-row exact lm_head (bz_speculative.hip), which streams the matrix once per 8 rows and leaves per-row argmax partials in
+// m->sp_pval / m->sp_pidx; its logits go to spec_rows [S][vocab] (device).
+static int prompt_head(bz_model* m, hipStream_t st, float* h, const float* prev, int n, int s0, int S, bool all, bz_tensor* logits_out, const bz_prompt_plan_t& plan,
+                       float* spec_rows = nullptr) {
+  const bz_model_config& c = m->cfg;
+  const int H = c.hidden, act = c.act_dtype;
+  const LinearDev& LH = m->lm_head.parts[0];
+  if (plan.head == BZ_HEAD_SPEC) {
+    for (int r0 = 0; r0 < n; r0 += 8) {
+      SpecHeadRows hr{h + (size_t)r0 * H, prev ? prev + (size_t)r0 * H : nullptr, H, m->final_norm, c.rms_eps, H, act};
+      BZ_TRY(bzk_spec_head(st, LH, hr, std::min(8, n - r0), spec_rows + (size_t)(s0 + r0) * c.vocab, m->sp_pval + (size_t)(s0 + r0) * m->sp_nb,
+                           m->sp_pidx + (size_t)(s0 + r0) * m->sp_nb, m->sp_nb));
+    }
+    return BZ_OK;
+  }
+  if (plan.head == BZ_HEAD_GEMM && all && n > 1 && logits_out->nbytes >= (size_t)(s0 + n) * c.vocab * 4) {
+    BZ_TRY(bzk_pf_norm(st, act, h, prev, m->final_norm, n, H, c.rms_eps, act, m->pf_x16));
+    return bzk_gemm_nt(st, act, m->pf_x16, LH.w, LH.bias, n, c.vocab, H, act, (float*)logits_out->ptr + (size_t)s0 * c.vocab, m->pf_ws, m->pf_ws_bytes);
+  }
+  for (int r = 0; r < n; r++) {
+    const int srow = s0 + r;
+    if (!all && srow != S - 1) continue;
+    if (plan.head == BZ_HEAD_STEP) {
+      StepIO hio{};
+      hio.do_embed = false; hio.do_head = true; hio.layer_start = 0; hio.layer_end = 0;
+      hio.hidden_in = h + (size_t)r * H; hio.prev_in = prev + (size_t)r * H;
+      BZ_TRY(llama_step(m, hio));
+    } else {
+      Pro ph{}; ph.mode = PRO_NORM; ph.src = VSrc{prev + (size_t)r * H, 0}; ph.h_in = h + (size_t)r * H; ph.h_out = nullptr; ph.norm_w = m->final_norm;
+      ph.eps = c.rms_eps; ph.H = H; ph.act = act;
+      GemvOut o{};
+      o.direct = m->logits; o.amax_val = m->pval; o.amax_idx = m->pidx;
+      BZ_TRY(bzk_gemv(st, LH, ph, o, act));
+    }
+    BZ_TRY(emit_logits(m, logits_out, all ? srow : 0));
+  }
+  return BZ_OK;
+}
 
 static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvView& view, int pos0, const int* slots, bool all, bz_tensor* logits_out,
-                         const RowsCtx& rc = RowsCtx(), const SpecHeadOut* sh = nullptr) {
+                         const bz_prompt_plan_t& plan, const RowsCtx& rc = RowsCtx(), float* spec_rows = nullptr) {
   const bz_model_config& c = m->cfg;
   hipStream_t st = step_stream(m);     // (a batched decode graph records this function on its capture stream)
   const int H = c.hidden, I = c.inter, nq = c.n_heads, nkv = c.n_kv_heads, hd = c.head_dim, act = c.act_dtype, dt = c.act_dtype;
-  const int CH = rc.row_pos ? 512 : 2048;      // prompts: 2048-row chunks (larger GEMMs: 8B AWQ 2048-token prompt 105 -> 90 ms)
+  const int CH = plan.chunk, exact = plan.exact;
   BZ_TRY(prefill_ws(m, std::min(S, CH)));
-  const int exact = prefill_exact(m, S, rc.row_pos != nullptr);
-  const bool attn_exact = exact != 0 || act == BZ_F32;       // f32 models: the oracle's double-precision sums cost little next to the f32 cache reads
   BZ_TRACE("prefill: S=%d position=%d rows=%s exact=%d window=%d", S, pos0, rc.row_pos ? "decode-batch" : "prompt", exact, c.sliding_window);
   // LoRA: after the GEMM of a group in the table's mask, the rows-form shrink over the rows the GEMM read and the expand over the rows it wrote
   auto lora_rows = [&](int layer, int group, float* y, int n, int s0) -> int {
@@ -2172,7 +2201,7 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
         if (rp.ws_bytes > m->rows_ws_bytes) BZ_FAIL(BZ_E_INVALID, "rows attention: workspace of %zu bytes not prepared (%zu)", rp.ws_bytes, m->rows_ws_bytes);
         BZ_TRY(bzk_rows_attn(st, dt, m->pf_qkv, n, nq, nkv, hd, vw, l, m->pf_x16, rc.row_pos + s0, rc.table_stride, layer_window(c, l), rp, m->rows_ws));
       } else
-      BZ_TRY(bzk_pf_attn(st, dt, m->pf_qkv, n, nq, nkv, hd, p0, act, vw, l, m->pf_x16, rc.row_pos ? rc.row_pos + s0 : nullptr, rc.table_stride, rc.max_len, attn_exact,
+      BZ_TRY(bzk_pf_attn(st, dt, m->pf_qkv, n, nq, nkv, hd, p0, act, vw, l, m->pf_x16, rc.row_pos ? rc.row_pos + s0 : nullptr, rc.table_stride, rc.max_len, plan.attn,
                          layer_window(c, l)));
       BZ_TRY(gq ? pf_gemm_gq(m, L.o, (const float*)m->pf_x16, n, m->pf_t) : pf_gemm(m, L.o.parts[0], m->pf_x16, n, m->pf_t, exact));
       BZ_TRY(lora_rows(l, LG_O, m->pf_t, n, s0));
@@ -2184,40 +2213,7 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
       BZ_TRY(lora_rows(l, LG_DOWN, m->pf_t, n, s0));
       prev = m->pf_t;
     }
-    // head.  Several rows wanted (all_logits, decode batch) and a dense lm_head in the activation dtype: final norm rows + one MFMA GEMM that
-    // streams the lm_head once; otherwise the decode lm_head GEMV per row (final norm fused as its prologue)
-    const LinearDev& LH = m->lm_head.parts[0];
-    if (sh) {
-      for (int r0 = 0; r0 < n; r0 += 8) {
-        SpecHeadRows hr{m->pf_h + (size_t)r0 * H, prev ? prev + (size_t)r0 * H : nullptr, H, m->final_norm, c.rms_eps, H, act};
-        BZ_TRY(bzk_spec_head(st, LH, hr, std::min(8, n - r0), sh->logits + (size_t)(s0 + r0) * c.vocab, m->sp_pval + (size_t)(s0 + r0) * m->sp_nb,
-                             m->sp_pidx + (size_t)(s0 + r0) * m->sp_nb, m->sp_nb));
-      }
-      continue;
-    }
-    if (all && n > 1 && !exact && act != BZ_F32 && LH.wdt == act && LH.K % 64 == 0 && logits_out->nbytes >= (size_t)(s0 + n) * c.vocab * 4) {
-      BZ_TRY(bzk_pf_norm(st, dt, m->pf_h, prev, m->final_norm, n, H, c.rms_eps, act, m->pf_x16));
-      BZ_TRY(bzk_gemm_nt(st, act, m->pf_x16, LH.w, LH.bias, n, c.vocab, H, act, (float*)logits_out->ptr + (size_t)s0 * c.vocab, m->pf_ws, m->pf_ws_bytes));
-      continue;
-    }
-    for (int r = 0; r < n; r++) {
-      const int srow = s0 + r;
-      if (!all && srow != S - 1) continue;
-      if (m->lm_head.fix_out || m->lm_head.parts.size() != 1) {   // quantised lm_head (GGUF output.weight): the decode step's head on this row
-        StepIO hio{};
-        hio.do_embed = false; hio.do_head = true; hio.layer_start = 0; hio.layer_end = 0;
-        hio.hidden_in = m->pf_h + (size_t)r * H; hio.prev_in = prev + (size_t)r * H;
-        BZ_TRY(llama_step(m, hio));
-        BZ_TRY(emit_logits(m, logits_out, all ? srow : 0));
-        continue;
-      }
-      Pro ph{}; ph.mode = PRO_NORM; ph.src = VSrc{prev + (size_t)r * H, 0}; ph.h_in = m->pf_h + (size_t)r * H; ph.h_out = nullptr; ph.norm_w = m->final_norm;
-      ph.eps = c.rms_eps; ph.H = H; ph.act = act;
-      GemvOut o{};
-      o.direct = m->logits; o.amax_val = m->pval; o.amax_idx = m->pidx;
-      BZ_TRY(bzk_gemv(st, m->lm_head.parts[0], ph, o, act));
-      BZ_TRY(emit_logits(m, logits_out, all ? srow : 0));
-    }
+    BZ_TRY(prompt_head(m, st, m->pf_h, prev, n, s0, S, all, logits_out, plan, spec_rows));
   }
   return BZ_OK;
 }
@@ -2228,26 +2224,6 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
 // cache that a row-wise kernel filled first, and the routed experts become per-expert GEMMs over gathered token rows
 // (docs/architecture.md:108-119: softmax -> top-k -> weighted sum + shared experts).  Same rounding points as the decode step, token for token.
 // ---------------------------------------------------------------------------------------------------------
-static bool dsv2_prefill_eligible(const bz_model* m, int S, int total_len, const KvView& view) {
-  const bz_model_config& c = m->cfg;
-  if (c.arch != BZ_ARCH_DEEPSEEK2 || S < prefill_min_rows() || (c.act_dtype != BZ_F16 && c.act_dtype != BZ_BF16) || c.mla_q_lora_rank > 0) return false;
-  {   // short prompts stay on the decode kernels (exact sums), as for the other families (prefill_eligible)
-    static const int env = getenv("BZ_EXACT_PREFILL") ? atoi(getenv("BZ_EXACT_PREFILL")) : -1;
-    static const int max_rows = getenv("BZ_EXACT_PREFILL_MAX") ? atoi(getenv("BZ_EXACT_PREFILL_MAX")) : 16;
-    if (env != 0 && (env > 0 || S <= max_rows)) return false;
-  }
-  if (c.hidden % 64 || (c.n_heads * c.mla_v_dim) % 64 || (c.moe_n_experts > 0 && c.moe_inter % 64) || view.dtype != c.act_dtype) return false;
-  for (const DsLayerDev& L : m->dlayers) {
-    for (const FusedLinear* F : {&L.qkva, &L.o}) if (F->parts.size() != 1 || F->parts[0].kind != LK_ROWS || F->parts[0].wdt != c.act_dtype) return false;
-    if (L.kv_b_dt != c.act_dtype) return false;
-    if (!L.is_moe) { for (const FusedLinear* F : {&L.gateup, &L.down}) if (F->parts.size() != 1 || F->parts[0].kind != LK_ROWS || F->parts[0].wdt != c.act_dtype || c.inter % 64) return false; }
-    else if (L.e_dt != c.act_dtype) return false;
-  }
-  MlaArgs probe{}; probe.rank = c.mla_kv_lora_rank; probe.rope = c.mla_rope_dim; probe.nope = c.mla_nope_dim; probe.vdim = c.mla_v_dim;
-  extern size_t bzk_mla_smem(const MlaArgs&, int);
-  if (bzk_mla_smem(probe, total_len) > 160 * 1024) return false;
-  return m->lm_head.parts.size() == 1 && m->lm_head.parts[0].kind == LK_ROWS && !m->lm_head.fix_out;
-}
 static int dsv2_prefill_ws(bz_model* m, int rows) {
   if (m->dpf_rows >= rows) return BZ_OK;
   const bz_model_config& c = m->cfg;
@@ -2281,7 +2257,7 @@ static int dsv2_prefill_ws(bz_model* m, int rows) {
 __global__ void k_acc_rows(float* acc, const float* y, size_t n, int first) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) acc[i] = first ? y[i] : acc[i] + y[i];
 }
-static int dsv2_prefill(bz_model* m, const long long* d_tok, int S, const KvView& view, int pos0, bool all, bz_tensor* logits_out) {
+static int dsv2_prefill(bz_model* m, const long long* d_tok, int S, const KvView& view, int pos0, bool all, bz_tensor* logits_out, const bz_prompt_plan_t& plan) {
   // (a chunk whose batched rows round to the decode step's bits is told apart by this line: test_gpu_dsv2_prefill.py, "no-shared")
   BZ_TRACE("dsv2_prefill: S=%d position=%d", S, pos0);
   const bz_model_config& c = m->cfg;
@@ -2290,7 +2266,7 @@ static int dsv2_prefill(bz_model* m, const long long* d_tok, int S, const KvView
   const int E = c.moe_n_experts, TK = c.moe_top_k, NS = c.moe_n_shared, MI = c.moe_inter;
   const int NQ = NH * (DN + DR), QN = NQ + R + DR;
   const size_t es = bz_dtype_size(dt);
-  const int CH = 512;
+  const int CH = plan.chunk;
   BZ_TRY(dsv2_prefill_ws(m, std::min(S, CH)));
   BZ_TRY(ensure_pf_ws(m));
   std::vector<int> hcnt(std::max(E, 1));
@@ -2348,22 +2324,7 @@ static int dsv2_prefill(bz_model* m, const long long* d_tok, int S, const KvView
       }
       prev = m->pf_t;
     }
-    const LinearDev& LH = m->lm_head.parts[0];
-    if (all && n > 1 && LH.wdt == act && LH.K % 64 == 0 && logits_out->nbytes >= (size_t)(s0 + n) * c.vocab * 4) {
-      BZ_TRY(bzk_pf_norm(st, dt, m->pf_h, prev, m->final_norm, n, H, c.rms_eps, act, m->pf_x16));
-      BZ_TRY(bzk_gemm_nt(st, act, m->pf_x16, LH.w, LH.bias, n, c.vocab, H, act, (float*)logits_out->ptr + (size_t)s0 * c.vocab, m->pf_ws, m->pf_ws_bytes));
-      continue;
-    }
-    for (int r = 0; r < n; r++) {
-      const int srow = s0 + r;
-      if (!all && srow != S - 1) continue;
-      Pro ph{}; ph.mode = PRO_NORM; ph.src = VSrc{prev + (size_t)r * H, 0}; ph.h_in = m->pf_h + (size_t)r * H; ph.h_out = nullptr; ph.norm_w = m->final_norm;
-      ph.eps = c.rms_eps; ph.H = H; ph.act = act;
-      GemvOut o{};
-      o.direct = m->logits; o.amax_val = m->pval; o.amax_idx = m->pidx;
-      BZ_TRY(bzk_gemv(st, m->lm_head.parts[0], ph, o, act));
-      BZ_TRY(emit_logits(m, logits_out, all ? srow : 0));
-    }
+    BZ_TRY(prompt_head(m, st, m->pf_h, prev, n, s0, S, all, logits_out, plan));
   }
   return BZ_OK;
 }
@@ -2401,15 +2362,17 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
 // (`slots`: a paged cache's slot of every row, else null), logits of every row (`all`) or of the last one.  The caller sets its cache's seq_len.
 static int forward_core(bz_model* m, const bz_tensor* tokens, int S, const KvView& view, const int* slots, int position, bool all, bz_tensor* logits_out) {
   const long long* d_tok = (const long long*)tokens->ptr;
-  if (prefill_eligible(m, S, position + S)) {
+  bz_prompt_plan_t plan;
+  BZ_TRY(bz_prompt_plan(&m->traits, nullptr, BZ_PLAN_PROMPT, S, position + S, view.dtype, &plan));
+  if (plan.route == BZ_ROUTE_ROWS) {
     // prompt-sized inputs of dense 16-bit models: batched prefill, GEMMs on the matrix cores
     BZ_TRY(check_logits_out(m, logits_out, all ? S : 1));
-    return prefill_dense(m, d_tok, S, view, position, slots, all, logits_out);
+    return prefill_dense(m, d_tok, S, view, position, slots, all, logits_out, plan);
   }
-  if (dsv2_prefill_eligible(m, S, position + S, view)) {
+  if (plan.route == BZ_ROUTE_DSV2) {
     // (paged: the rows' slots follow from the block table: slot = block_table[p / bs] * bs + p % bs, batch_decode.rs:81-88)
     BZ_TRY(check_logits_out(m, logits_out, all ? S : 1));
-    return dsv2_prefill(m, d_tok, S, view, position, all, logits_out);
+    return dsv2_prefill(m, d_tok, S, view, position, all, logits_out, plan);
   }
   for (int s = 0; s < S; s++) {
     StepIO io{};
@@ -2477,7 +2440,9 @@ extern "C" int bz_forward_paged_batch(bz_model* m, const bz_tensor* tokens, int 
     maxlen = std::max(maxlen, seq_lens[i]);
   }
   static const bool no_share = getenv("BZ_NO_BATCH_SHARING") != nullptr;
-  if (!no_share && N >= 2 && prefill_eligible(m, std::max(N, prefill_min_rows()), maxlen, true)) {
+  bz_prompt_plan_t plan;
+  BZ_TRY(bz_prompt_plan(&m->traits, nullptr, BZ_PLAN_DECODE_BATCH, N, maxlen, kv->dtype, &plan));
+  if (!no_share && N >= 2 && plan.route == BZ_ROUTE_ROWS) {
     // weight-sharing path: the N rows go through the multi-row pipeline (int4: one pass over the weights per 8 sequences; dense: MFMA GEMM),
     // each row with its own position, slot and block-table row
     std::vector<int> pos(N);
@@ -2490,7 +2455,7 @@ extern "C" int bz_forward_paged_batch(bz_model* m, const bz_tensor* tokens, int 
     BZ_HIP(hipStreamSynchronize(m->dev->stream));       // `pos` is a stack-lifetime host buffer
     RowsCtx rc; rc.row_pos = m->row_pos; rc.table_stride = max_blocks; rc.max_len = maxlen;
     BZ_TRY(rows_attn_prepare(m, kv, N, maxlen, "forward_paged_batch", &rc.split_min));
-    BZ_TRY(prefill_dense(m, (const long long*)tokens->ptr, N, view_of(kv, (const int*)block_table->ptr, nullptr), 0, (const int*)slot_mapping->ptr, true, logits_out, rc));
+    BZ_TRY(prefill_dense(m, (const long long*)tokens->ptr, N, view_of(kv, (const int*)block_table->ptr, nullptr), 0, (const int*)slot_mapping->ptr, true, logits_out, plan, rc));
     if (kv->seq_len < maxlen) kv->seq_len = maxlen;
     return BZ_OK;
   }
@@ -2515,34 +2480,16 @@ static int check_ssm(bz_model* m, bz_ssm_state* st) {
   return BZ_OK;
 }
 
-// Mamba2 batched prefill (prompts of >= prefill_min_rows() tokens, dense 16-bit in_proj / out_proj in the activation dtype): rows through the
+// Mamba2 batched prefill (prompts of >= BZ_PREFILL_MIN tokens, dense 16-bit in_proj / out_proj in the activation dtype): rows through the
 // MFMA GEMMs, conv as a map over (token, channel), the recurrence as an in-kernel scan per head (bz_prefill.hip).  Same rounding points as
 // mamba_step, token for token.
-static bool mamba_prefill_eligible(const bz_model* m, int S) {
-  static const bool off = getenv("BZ_NO_MFMA_PREFILL") != nullptr;
-  const bz_model_config& c = m->cfg;
-  if (off || c.arch != BZ_ARCH_MAMBA2 || S < prefill_min_rows()) return false;
-  if (c.act_dtype != BZ_F16 && c.act_dtype != BZ_BF16) return false;
-  {   // short prompts stay on the step kernels (exact sums: the oracle's bits), as for the dense Llama models (prefill_eligible)
-    static const int env = getenv("BZ_EXACT_PREFILL") ? atoi(getenv("BZ_EXACT_PREFILL")) : -1;
-    static const int max_rows = getenv("BZ_EXACT_PREFILL_MAX") ? atoi(getenv("BZ_EXACT_PREFILL_MAX")) : 16;
-    if (env != 0 && (env > 0 || S <= max_rows)) return false;
-  }
-  if (!bzk_ssm_scan_ok(c.ssm_head_dim, c.ssm_d_state, c.ssm_n_groups, c.ssm_conv_kernel) || c.ssm_d_inner % c.ssm_n_groups || c.ssm_n_heads % c.ssm_n_groups) return false;
-  for (const MambaLayerDev& L : m->mlayers)
-    for (const FusedLinear* F : {&L.in_proj, &L.out_proj}) {
-      if (F->parts.size() != 1) return false;
-      const LinearDev& P = F->parts[0];
-      if (P.kind != LK_ROWS || P.wdt != c.act_dtype || P.K % 64) return false;
-    }
-  return m->lm_head.parts.size() == 1 && m->lm_head.parts[0].kind == LK_ROWS && !m->lm_head.fix_out;
-}
-static int mamba_prefill(bz_model* m, const long long* d_tok, int S, bz_ssm_state* state, bool all, bz_tensor* logits_out) {
+static int mamba_prefill(bz_model* m, const long long* d_tok, int S, bz_ssm_state* state, bool all, bz_tensor* logits_out, const bz_prompt_plan_t& plan) {
+  BZ_TRACE("mamba_prefill: S=%d", S);
   const bz_model_config& c = m->cfg;
   hipStream_t st = m->dev->stream;
   const int D = c.hidden, DI = c.ssm_d_inner, NH = c.ssm_n_heads, NS = c.ssm_d_state, G = c.ssm_n_groups, KC = c.ssm_conv_kernel, act = c.act_dtype, dt = c.act_dtype;
   const int conv_dim = DI + 2 * G * NS, ld = DI + conv_dim + NH;
-  const int CH = 512;
+  const int CH = plan.chunk;
   const int rows = std::min(S, CH);
   BZ_TRY(ensure_pf_ws(m));
   if (m->mpf_rows < rows) {
@@ -2576,16 +2523,7 @@ static int mamba_prefill(bz_model* m, const long long* d_tok, int S, bz_ssm_stat
       BZ_TRY(bzk_gemm_nt(st, act, m->mpf_x16, Pout.w, Pout.bias, n, Pout.N, Pout.K, act, m->mpf_t, m->pf_ws, m->pf_ws_bytes));
       prev = m->mpf_t;
     }
-    for (int r = 0; r < n; r++) {
-      const int srow = s0 + r;
-      if (!all && srow != S - 1) continue;
-      Pro ph{}; ph.mode = PRO_NORM; ph.src = VSrc{prev + (size_t)r * D, 0}; ph.h_in = m->mpf_h + (size_t)r * D; ph.h_out = nullptr; ph.norm_w = m->final_norm;
-      ph.eps = c.rms_eps; ph.H = D; ph.act = act;
-      GemvOut o{};
-      o.direct = m->logits; o.amax_val = m->pval; o.amax_idx = m->pidx;
-      BZ_TRY(bzk_gemv(st, m->lm_head.parts[0], ph, o, act));
-      BZ_TRY(emit_logits(m, logits_out, all ? srow : 0));
-    }
+    BZ_TRY(prompt_head(m, st, m->mpf_h, prev, n, s0, S, all, logits_out, plan));
   }
   return BZ_OK;
 }
@@ -2596,10 +2534,12 @@ extern "C" int bz_forward_ssm(bz_model* m, const bz_tensor* tokens, int S, bz_ss
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   BZ_TRY(check_ssm(m, st));
   const bool all = flags & BZ_FWD_ALL_LOGITS;
-  if (mamba_prefill_eligible(m, S)) {
+  bz_prompt_plan_t plan;
+  BZ_TRY(bz_prompt_plan(&m->traits, nullptr, BZ_PLAN_PROMPT, S, S, st->dtype, &plan));
+  if (plan.route == BZ_ROUTE_MAMBA) {
     BZ_TRY(check_logits_out(m, logits_out, all ? S : 1));
     BZ_HIP(hipSetDevice(m->dev->id));
-    return mamba_prefill(m, (const long long*)tokens->ptr, S, st, all, logits_out);
+    return mamba_prefill(m, (const long long*)tokens->ptr, S, st, all, logits_out, plan);
   }
   for (int s = 0; s < S; s++) {
     StepIO io{};
@@ -3213,11 +3153,12 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
     if (cdev != m->dev) BZ_FAIL(BZ_E_INVALID, "grammar batch graph capture: the grammar cursor lives on another device handle");
   }
   const int capacity = std::min(max_blocks * kv->block_size, m->cfg.max_seq_len);
-  const LinearDev& LH = m->lm_head.parts[0];
   int rows_split_min = 1 << 30;
   BZ_HIP(hipSetDevice(m->dev->id));
   BZ_TRY(rows_attn_prepare(m, kv, N, capacity, "batch graph capture", &rows_split_min));     // refusal and workspace before the capture
-  if (!prefill_eligible(m, std::max(N, prefill_min_rows()), capacity, true) || LH.wdt != m->cfg.act_dtype || LH.K % 64)
+  bz_prompt_plan_t plan;
+  BZ_TRY(bz_prompt_plan(&m->traits, nullptr, BZ_PLAN_DECODE_BATCH, N, capacity, kv->dtype, &plan));
+  if (plan.route != BZ_ROUTE_ROWS || !m->traits.head_gemm)
     BZ_FAIL(BZ_E_UNSUPPORTED, "batch graph capture: the model does not take the weight-sharing multi-row step (int4 without act-order or dense 16-bit weights, 16-bit lm_head)");
   BZ_HIP(hipSetDevice(m->dev->id));
   BZ_TRY(prefill_ws(m, N));                      // workspace before the capture (allocation synchronises)
@@ -3239,7 +3180,7 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
     if (er) BZ_TRY(bzk_engine_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N, er->rows));
     else BZ_TRY(bzk_batch_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N));
     RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity; rcx.row_lora = g->row_lora; rcx.split_min = rows_split_min;
-    BZ_TRY(prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, rcx));
+    BZ_TRY(prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, plan, rcx));
     // a sampler with bz_batch_sampler_enable (sampling.rs:414-431): logprobs on the raw rows, mask, bias, pick, records; without it none of the three launches anything
     if (s) BZ_TRY(bzk_lp_pre(cap, s, (const float*)g->logits->ptr));
     if (c) BZ_TRY(bzk_grammar_mask_rows(cap, c, (float*)g->logits->ptr));
@@ -3790,13 +3731,10 @@ int GenLoop::loop(bz_model* m, const int64_t* prompt, int n_prompt, const bz_gen
 // speculative decoding (reference: engine/generate_text.rs:41-44,61-136, engine/speculative.rs:99-125, config/inference.rs:197-208):
 // a draft model proposes k tokens, the target verifies [t, d1 .. dk] in ONE pass whose rows are the decode step's bits, acceptance is decided on the device
 // ---------------------------------------------------------------------------------------------------------
-static bool spec_head_eligible(const bz_model* m) {
-  return m->lm_head.parts.size() == 1 && !m->lm_head.fix_out && bzk_spec_head_ok(m->lm_head.parts[0], m->cfg.act_dtype, m->cfg.hidden);
-}
 static int ensure_spec_ws(bz_model* m) {
   if (m->sp_record) return BZ_OK;
   void* p;
-  m->sp_nb = spec_head_eligible(m) ? bzk_spec_head_blocks(m->lm_head.parts[0]) : 64;
+  m->sp_nb = m->traits.spec_head ? bzk_spec_head_blocks(m->lm_head.parts[0]) : 64;
   BZ_TRY(dev_alloc(m, &p, (size_t)16 * m->cfg.vocab * 4)); m->sp_logits = (float*)p;
   BZ_TRY(dev_alloc(m, &p, (size_t)16 * m->sp_nb * 4)); m->sp_pval = (float*)p;
   BZ_TRY(dev_alloc(m, &p, (size_t)16 * m->sp_nb * 4)); m->sp_pidx = (int*)p;
@@ -3804,18 +3742,6 @@ static int ensure_spec_ws(bz_model* m) {
   BZ_TRY(dev_alloc(m, &p, 17 * 8)); m->sp_record = (long long*)p;
   return BZ_OK;
 }
-// the multi-row exact rows apply: f16 int4 model whose every projection has the multi-row form (prefill_exact == 1), the shapes the row kernels take (as
-// prefill_eligible), the exact attention's scores of position + R keys in LDS, and a head the multi-row lm_head takes
-static bool verify_fast_ok(const bz_model* m, int R, int position) {
-  const bz_model_config& c = m->cfg;
-  if (c.arch != BZ_ARCH_LLAMA || c.act_dtype != BZ_F16 || R > 16 || prefill_exact(m, R, false) != 1) return false;
-  if (c.hidden % 64 || (c.n_heads * c.head_dim) % 64 || c.inter % 64 || c.head_dim % 8 || 256 % (c.head_dim / 8)) return false;
-  const int rep = c.n_heads / c.n_kv_heads;
-  if (rep != 1 && rep != 2 && rep != 4 && rep != 8) return false;
-  if (bzk_pf_attn_smem(c.n_heads, c.n_kv_heads, c.head_dim, window_keys(c, position + R), true) > 160 * 1024) return false;
-  return spec_head_eligible(m);
-}
-
 // rows d_tok[0 .. R) at positions position .. position + R - 1 (1 <= R <= 16): logits [R][vocab] (device), m->sp_argmax [R], then the accept kernel over
 // (argmax, draft = d_tok + 1) -> m->sp_record; next_slot (nullable) receives the correction / bonus token.  Nothing is synchronised here; the caller
 // reads the record and sets kv->seq_len = position + n_accept + 1 (rows past it hold rejected tokens: no kernel reads them, the next forward overwrites them).
@@ -3825,11 +3751,12 @@ static int llama_verify_rows(bz_model* m, const long long* d_tok, int R, bz_kv* 
   hipStream_t st = m->dev->stream;
   BZ_TRY(ensure_spec_ws(m));
   BZ_TRY(kv_grow(kv, position + R));
-  const bool fast = verify_fast_ok(m, R, position);
+  bz_prompt_plan_t plan;
+  BZ_TRY(bz_prompt_plan(&m->traits, nullptr, BZ_PLAN_VERIFY, R, position + R, kv->dtype, &plan));
+  const bool fast = plan.route == BZ_ROUTE_ROWS;
   BZ_TRACE("verify: R=%d position=%d path=%d", R, position, (int)fast);
   if (fast) {
-    SpecHeadOut sh{logits};
-    BZ_TRY(prefill_dense(m, d_tok, R, view_of(kv), position, nullptr, true, nullptr, RowsCtx(), &sh));
+    BZ_TRY(prefill_dense(m, d_tok, R, view_of(kv), position, nullptr, true, nullptr, plan, RowsCtx(), logits));
     BZ_TRY(bzk_spec_argmax_final(st, m->sp_pval, m->sp_pidx, m->sp_nb, R, m->sp_argmax));
   } else {
     for (int r = 0; r < R; r++) {
@@ -4430,7 +4357,7 @@ extern "C" int bz_paged_attn_decode_rows(bz_model* m, const bz_tensor* q, bz_pag
   BzRowsPlan rp;
   BZ_TRY(bzk_rows_attn_plan(nq, nkv, hd, kv->dtype, kv->block_size, W, N, maxlen, split_min, &rp));
   if (rp.kernel == 1) BZ_TRY(bzk_rows_attn(st, c.act_dtype, m->pf_qkv, N, nq, nkv, hd, vw, layer, m->pf_x16, m->row_pos, max_blocks, W, rp, m->rows_ws));
-  else BZ_TRY(bzk_pf_attn(st, c.act_dtype, m->pf_qkv, N, nq, nkv, hd, 0, c.act_dtype, vw, layer, m->pf_x16, m->row_pos, max_blocks, maxlen, false, W));
+  else BZ_TRY(bzk_pf_attn(st, c.act_dtype, m->pf_qkv, N, nq, nkv, hd, 0, c.act_dtype, vw, layer, m->pf_x16, m->row_pos, max_blocks, maxlen, BZ_PF_ATTN_SCALAR, W));     // (plain sums in every dtype; the batched step runs an f32 cache's exact ones)
   BZ_TRY(bzk_rows16_to_f32(st, c.act_dtype, m->pf_x16, (size_t)N * nq * hd, (float*)out->ptr));
   BZ_HIP(hipStreamSynchronize(st));       // (`pos` is a stack-lifetime host buffer)
   return BZ_OK;

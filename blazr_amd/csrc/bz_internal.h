@@ -350,6 +350,7 @@ struct MoeGemvArgs {
 };
 int bzk_moe_gemv(hipStream_t s, const MoeGemvArgs& g, int wdt, int n_slots, const Pro& pro, int act, bool split, double bytes);
 int bzk_mla_attn(hipStream_t s, const MlaArgs& a, int max_len);
+size_t bzk_mla_smem(const MlaArgs& a, int max_len);   // LDS of the single-pass kernel at a context of max_len positions (160 KiB: its limit)
 int bzk_moe_router(hipStream_t s, const Pro& pro, const void* wr, int wdt, int E, int top_k, int n_shared, float routed_scale, int norm_topk,
                    float* xn_out, int* sel, float* wsel, float* lg_glob, unsigned* counter);
 int bzk_moe_combine(hipStream_t s, long long* acc, const float* wsel, int top_k, int has_shared, int H, int act, float* out, long long* zero_buf = nullptr, int zero_n = 0);
@@ -366,7 +367,7 @@ int bzk_pf_norm(hipStream_t s, int dt, float* hbuf, const float* prev, const flo
 int bzk_pf_rope_kv(hipStream_t s, float* qkv, int S, int nq, int nkv, int hd, const float* cos_t, const float* sin_t, int interleaved, int pos0, int act,
                    const KvView& kv, int layer, const int* slots, const int* row_pos = nullptr);
 int bzk_pf_attn(hipStream_t s, int dt, const float* qkv, int S, int nq, int nkv, int hd, int pos0, int act, const KvView& kv, int layer, void* out16,
-                const int* row_pos = nullptr, int table_stride = 0, int max_len = 0, bool exact = false, int window = 0);   // window: see AttnArgs (every row its own lo)
+                const int* row_pos, int table_stride, int max_len, int form, int window);   // form: BZ_PF_ATTN_* of the plan (bz_route.hip); window: see AttnArgs (every row its own lo)
 // Mamba2 batched prefill (bz_prefill.hip): conv over the prompt rows (+ carried conv state), in-kernel scan over the tokens, gated RMSNorm rows
 struct BzSsmScan {
   const float* xbc; int conv_dim; const float* zx; int ld; int dt_off; const float* dt_bias; const float* A_log; const float* D; void* state;
@@ -391,6 +392,8 @@ int bzk_rows_attn_plan(int nq, int nkv, int hd, int kv_dtype, int block_size, in
 int bzk_rows_attn(hipStream_t s, int dt, const float* qkv, int n, int nq, int nkv, int hd, const KvView& kv, int layer, void* out16, const int* row_pos, int table_stride,
                   int window, const BzRowsPlan& plan, float* ws);
 int bzk_rows16_to_f32(hipStream_t s, int dt, const void* x16, size_t n, float* y);
+// which path a prompt takes (bz_route.hip): the process's switches; bz_prompt_plan itself is public
+const bz_prompt_switches_t* bzk_prompt_switches();
 
 // non-greedy sampling (bz_sample.hip)
 int bzk_sample(hipStream_t s, void** ws, const float* logits, long long V, const long long* ids, const int* cnts, int n, float rp, float fp, float pp,

@@ -1407,11 +1407,15 @@ size_t bzk_pf_attn_smem(int nq, int nkv, int hd, int len, bool exact) {
   return (size_t)(8 * REP + RPP * REP * hd) * (exact ? 8 : 4) + (size_t)REP * len * 4 + 64;
 }
 int bzk_pf_attn(hipStream_t s, int dt, const float* qkv, int S, int nq, int nkv, int hd, int pos0, int act, const KvView& kv, int layer, void* out16,
-                const int* row_pos, int table_stride, int max_len, bool exact, int window) {
+                const int* row_pos, int table_stride, int max_len, int form, int window) {
+  // form: the plan's (bz_route.hip) -- launched as named or refused, never replaced.  MFMA: one prompt, 16-bit; SCALAR / SCALAR_EXACT: the scalar kernel,
+  // plain or exact sums; ROWS: a decode batch's rows on the scalar kernel (f32 caches: exact sums, as their prompts)
   const int REP = nq / nkv;
-  if (hd % 8 || hd > 256 || (256 % (hd / 8)) || (REP != 1 && REP != 2 && REP != 4 && REP != 8) || kv.dtype != dt)
+  if (hd % 8 || hd > 256 || (256 % (hd / 8)) || (REP != 1 && REP != 2 && REP != 4 && REP != 8) || kv.dtype != dt ||
+      (form == BZ_PF_ATTN_MFMA ? row_pos || dt == BZ_F32 || !bzk_pf_attn_mfma_ok(hd, REP) : form == BZ_PF_ATTN_ROWS ? !row_pos : form != BZ_PF_ATTN_SCALAR && form != BZ_PF_ATTN_SCALAR_EXACT))
     BZ_FAIL(BZ_E_UNSUPPORTED, "prefill attention: head_dim %d / group size %d / cache dtype unsupported", hd, REP);
-  if (!row_pos && dt != BZ_F32 && !exact && bzk_pf_attn_mfma_ok(hd, REP)) {
+  const bool exact = form == BZ_PF_ATTN_SCALAR_EXACT || (form == BZ_PF_ATTN_ROWS && dt == BZ_F32);
+  if (form == BZ_PF_ATTN_MFMA) {
     const float scale_m = div_rn(1.0f, sqrt_rn((float)hd));
     const int HW = REP < 4 ? REP : 4, QT = 4 / HW;
     const dim3 grid((S + 32 * QT - 1) / (32 * QT), nkv, REP / HW);

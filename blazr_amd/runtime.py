@@ -850,6 +850,21 @@ def rows_attn_plan(n_heads, n_kv_heads, head_dim, kv_dtype, window, n, capacity)
     return d
 
 
+def prompt_traits(model):
+    """bz_model_prompt_traits: what the route decision reads of a loaded model (a LoadedModel or a raw handle), as an L.PromptTraits"""
+    t = L.PromptTraits()
+    L.check(L.lib().bz_model_prompt_traits(getattr(model, "h", model), C.byref(t)))
+    return t
+
+
+def prompt_plan(traits, kind, rows, total_len, kv_dtype=L.F16, switches=None):
+    """bz_prompt_plan (host only): the path `rows` rows ending at a context of `total_len` positions take.  switches: an L.PromptSwitches, or None for this
+    process's environment.  Returns a dict of route, exact, attn, head, chunk (L.ROUTE_*, L.PF_ATTN_*, L.HEAD_*)."""
+    p = L.PromptPlan()
+    L.check(L.lib().bz_prompt_plan(C.byref(traits), C.byref(switches) if switches is not None else None, int(kind), int(rows), int(total_len), int(kv_dtype), C.byref(p)))
+    return dict(route=p.route, exact=p.exact, attn=p.attn, head=p.head, chunk=p.chunk)
+
+
 def penalty_window(recent_tokens, repeat_last_n):
     """sampling.rs:169-191: unique ids + counts over the last `repeat_last_n` tokens."""
     w = recent_tokens[-repeat_last_n:] if 0 < repeat_last_n < len(recent_tokens) else recent_tokens

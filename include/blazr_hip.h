@@ -760,6 +760,57 @@ int bz_paged_attn_decode(bz_model* m, const bz_tensor* q, bz_paged_kv* kv, int l
 typedef struct bz_rows_attn_plan_t { int kernel; int scalar_limit; int grid_slices; int rows_per_pass; size_t ws_bytes; } bz_rows_attn_plan_t;
 int bz_rows_attn_plan(int n_heads, int n_kv_heads, int head_dim, int kv_dtype, int window, int N, int capacity, bz_rows_attn_plan_t* out);
 int bz_rows_attn_slice_len(int len);
+/* Which path a prompt, a decode batch or a speculative verify takes (DESIGN.md "Which path a prompt takes").
+ * bz_prompt_traits_t: what the decision reads of a model, fixed at bz_model_finalize (nothing changes a linear's format afterwards); bz_model_prompt_traits
+ * copies it out.  Flags are 0 / 1.  bz_prompt_switches_t: the six environment switches the decision depends on, read once per process.
+ * bz_prompt_plan: HOST ONLY, needs no device -- the decision itself, a pure function of (traits, switches, kind, rows, total_len, kv_dtype).  sw == NULL: this
+ * process's switches.  rows: prompt rows / sequences of a decode batch / verify rows; total_len: position + rows (decode batch: the longest sequence, or the
+ * capacity of a graph); kv_dtype: the cache's element type.  BZ_NO_PF_ATTN_MFMA is read where the attention launcher reads it.
+ * New symbols only: BZ_ABI_VERSION is unchanged. */
+typedef struct bz_prompt_traits_t {
+  int arch, act_dtype;
+  int hidden, inter, n_layers, n_heads, n_kv_heads, head_dim, rep;   /* rep = n_heads / n_kv_heads */
+  int sliding_window, sliding_window_pattern;                         /* with n_layers: whether every layer has the window */
+  /* Llama family */
+  int shapes_ok;      /* hidden, n_heads head_dim, inter multiples of 64; head_dim % 8 == 0, 256 % (head_dim / 8) == 0; rep 1 / 2 / 4 / 8 */
+  int proj_16;        /* 16-bit activations and every projection one part: dense in the activation dtype, fp8, or int4 without act-order */
+  int any_dense;      /* ... and one of them dense or fp8 */
+  int exact_cap;      /* 0: some projection lacks the multi-row int4 form; 1: all have it; 2: all have the integer-MFMA form too */
+  int gq_all;         /* every part of every projection a block format without bias, one K per fused linear */
+  int gq_max_k;       /* largest K of a fused linear */
+  unsigned long long gq_max_n3k;   /* largest N_total * 3 * K of a fused linear (32-bit element offsets of the split GEMM) */
+  /* lm_head */
+  int head_rows;      /* one dense part with direct f32 output */
+  int head_gemm;      /* weight dtype == activation dtype and K % 64 == 0 */
+  int spec_head;      /* the multi-row exact lm_head of the speculative verify takes it */
+  /* DeepSeek-V2 */
+  int mla_q_lora_rank, mla_kv_lora_rank, mla_rope_dim, mla_nope_dim, mla_v_dim;
+  int ds_dims_ok;     /* hidden, n_heads v_dim, moe_inter (MoE models) and inter (models with a dense layer) multiples of 64 */
+  int ds_weights_act; /* every projection one dense part in the activation dtype, kv_b_proj and the experts too */
+  /* Mamba2 */
+  int ssm_scan_ok;    /* the in-kernel scan takes head_dim / d_state / n_groups / conv kernel */
+  int ssm_groups_ok;  /* d_inner and n_heads divisible by n_groups */
+  int ssm_proj_ok;    /* in_proj / out_proj one dense part in the activation dtype, K % 64 == 0 */
+} bz_prompt_traits_t;
+typedef struct bz_prompt_switches_t {
+  int prefill_min;       /* BZ_PREFILL_MIN, default 8 */
+  int no_mfma_prefill;   /* BZ_NO_MFMA_PREFILL set */
+  int no_gguf_prefill;   /* BZ_NO_GGUF_PREFILL set */
+  int exact;             /* BZ_EXACT_PREFILL, default -1: by prompt length */
+  int exact_max;         /* BZ_EXACT_PREFILL_MAX, default 16 */
+  int exact_i8_max;      /* BZ_EXACT_I8_MAX, default 0 */
+} bz_prompt_switches_t;
+enum { BZ_PLAN_PROMPT = 0, BZ_PLAN_DECODE_BATCH = 1, BZ_PLAN_VERIFY = 2 };
+enum { BZ_ROUTE_STEPS = 0, BZ_ROUTE_ROWS = 1, BZ_ROUTE_DSV2 = 2, BZ_ROUTE_MAMBA = 3 };
+enum { BZ_PF_ATTN_NONE = 0, BZ_PF_ATTN_MFMA = 1, BZ_PF_ATTN_SCALAR = 2, BZ_PF_ATTN_SCALAR_EXACT = 3, BZ_PF_ATTN_ROWS = 4 };
+enum { BZ_HEAD_STEP = 0, BZ_HEAD_GEMM = 1, BZ_HEAD_GEMV_ROWS = 2, BZ_HEAD_SPEC = 3 };
+/* route STEPS: token by token on the decode step (exact 0, attn NONE, head STEP, chunk 0).  exact: 0 MFMA GEMMs, 1 the multi-row exact rows, 2 the exact
+ * integer-MFMA GEMMs.  attn ROWS: a decode batch -- scalar or split-KV per layer, by bz_rows_attn_plan.  head GEMM: one MFMA GEMM over a chunk where all its
+ * rows are wanted, else as GEMV_ROWS (final norm + lm_head GEMV per wanted row); STEP: the decode step's head per wanted row (quantised lm_head).
+ * chunk: rows per pass, 2048 or 512. */
+typedef struct bz_prompt_plan_t { int route, exact, attn, head, chunk; } bz_prompt_plan_t;
+int bz_model_prompt_traits(const bz_model* m, bz_prompt_traits_t* out);
+int bz_prompt_plan(const bz_prompt_traits_t* t, const bz_prompt_switches_t* sw, int kind, int rows, int total_len, int kv_dtype, bz_prompt_plan_t* out);
 /* op-level twin of bz_paged_attn_decode for a decode batch (engine/batch_decode.rs:35-150): runs the attention the batched step would launch for these rows and
  * returns its 16-bit rows as F32.  q F32 [N, n_heads, hd] roped and rounded, block_table I32 [N, max_blocks], seq_lens HOST i32 [N], out F32 [N, n_heads, hd]. */
 int bz_paged_attn_decode_rows(bz_model* m, const bz_tensor* q, bz_paged_kv* kv, int layer, const bz_tensor* block_table, int max_blocks,
