@@ -156,6 +156,27 @@ class LogprobsRecord(C.Structure):
                 ("top_logprobs", C.c_float * TOP_LOGPROBS_MAX)]
 
 
+class ScoreConfig(C.Structure):
+    _fields_ = [("top_n", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+class ScoreRow(C.Structure):
+    _fields_ = [("target", C.c_int64), ("logit", C.c_float), ("logprob", C.c_float), ("lse", C.c_float), ("rank", C.c_int32), ("n_top", C.c_int32),
+                ("top_ids", C.c_uint32 * TOP_LOGPROBS_MAX), ("top_logprobs", C.c_float * TOP_LOGPROBS_MAX)]
+
+
+class ScoreTotal(C.Structure):
+    _fields_ = [("sum_logprob", C.c_double), ("n_scored", C.c_int64)]
+
+
+POOL_NONE, POOL_MEAN, POOL_CLS, POOL_LAST = 0, 1, 2, 3
+POOLINGS = {"none": POOL_NONE, "mean": POOL_MEAN, "cls": POOL_CLS, "last": POOL_LAST}
+
+
+class EmbedConfig(C.Structure):
+    _fields_ = [("pooling", C.c_int32), ("normalize", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
 class RequestExtras(C.Structure):
     _fields_ = [("logprobs", C.c_int32), ("top_logprobs", C.c_int32), ("n_logit_bias", C.c_int32), ("logit_bias_ids", C.c_void_p), ("logit_bias_vals", C.c_void_p),
                 ("reserved", C.c_int32 * 4)]
@@ -286,6 +307,16 @@ SYMBOLS = {
     "bz_batch_sampler_set_row_logprobs": (C.c_int, [P, C.c_int, C.c_int]),
     "bz_batch_sampler_read_logprobs": (C.c_int, [P, C.POINTER(LogprobsRecord)]),
     "bz_decode_batch_graph_read_logprobs": (C.c_int, [P, C.c_int64, C.POINTER(LogprobsRecord)]),
+    "bz_score_kv": (C.c_int, [P, P, C.c_int, P, C.c_int, P, C.POINTER(ScoreConfig), C.POINTER(ScoreRow), C.POINTER(ScoreTotal)]),
+    "bz_score_paged": (C.c_int, [P, P, C.c_int, P, P, P, C.c_int, C.c_int, C.c_int, P, C.POINTER(ScoreConfig), C.POINTER(ScoreRow), C.POINTER(ScoreTotal)]),
+    "bz_score_ssm": (C.c_int, [P, P, C.c_int, P, P, C.POINTER(ScoreConfig), C.POINTER(ScoreRow), C.POINTER(ScoreTotal)]),
+    "bz_embed_kv": (C.c_int, [P, P, C.c_int, P, C.c_int, C.POINTER(EmbedConfig), P]),
+    "bz_embed_paged": (C.c_int, [P, P, C.c_int, P, P, P, C.c_int, C.c_int, C.c_int, C.POINTER(EmbedConfig), P]),
+    "bz_embed_ssm": (C.c_int, [P, P, C.c_int, P, C.POINTER(EmbedConfig), P]),
+    "bz_score_rows": (C.c_int, [P, P, C.c_int64, C.c_int64, P, C.POINTER(ScoreConfig), C.POINTER(ScoreRow)]),
+    "bz_pool_rows": (C.c_int, [P, P, C.c_int64, C.c_int64, C.POINTER(EmbedConfig), P]),
+    "bz_score_row_spec": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int, C.POINTER(ScoreRow)]),
+    "bz_pool_spec": (C.c_int, [P, C.c_int64, C.c_int64, C.POINTER(EmbedConfig), P]),
     "bz_generate": (C.c_int, [P, P, C.c_int, C.POINTER(GenConfig), P, C.POINTER(GenStats)]),
     "bz_profile_step": (C.c_int, [P, P, C.c_int64, C.c_int, C.c_int, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),
     "bz_profile_step_ssm": (C.c_int, [P, P, C.c_int64, C.c_int, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),

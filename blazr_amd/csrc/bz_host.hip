@@ -340,6 +340,7 @@ struct bz_model {
   float* sp_logits = nullptr; float* sp_pval = nullptr; int* sp_pidx = nullptr; int sp_nb = 0;
   long long* sp_argmax = nullptr; long long* sp_record = nullptr;
   size_t resident = 0, per_token = 0;
+  BzSinkWs* sink_ws = nullptr;   // buffers of score / embed calls (bz_score.hip), made by the first such call
   BzLoraTable* lora = nullptr;   // bz_lora_table_create: the adapter slots, the current-slot scalar and the f32 rows the adapted linears' consumers read (bz_lora.hip)
 };
 
@@ -418,6 +419,7 @@ extern "C" int bz_model_free(bz_model* m) {
   hipStreamSynchronize(m->dev->stream);
   for (auto& kv : m->raw) raw_free(kv.second);
   for (void* p : m->owned) hipFree(p);
+  bzk_sink_free(m->sink_ws);
   bzl_table_free(m->lora);
   bz_dev_release(m->dev);
   delete m;
@@ -1706,6 +1708,20 @@ static int step_tail(bz_model* m, const StepIO& io, RingState& rs, VSrc prev, co
   return BZ_OK;
 }
 
+// hidden_out / prev_out of a step that has no pieces API of its own (Mamba2, DeepSeek-V2): the residual row and the deferred residual the head would have read --
+// what an embed call's final norm reads on the token-by-token route.  Nothing without hidden_out.
+static int step_rows_out(bz_model* m, const StepIO& io, VSrc prev, const float* h) {
+  if (!io.hidden_out) return BZ_OK;
+  hipStream_t st = step_stream(m);
+  const int H = m->cfg.hidden;
+  BZ_HIP(hipMemcpyAsync(io.hidden_out, h, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
+  if (io.prev_out && prev.p) {
+    if (prev.fix) BZ_TRY(bzk_fix_to_f32(st, (const long long*)prev.p, H, m->cfg.act_dtype, io.prev_out));
+    else BZ_HIP(hipMemcpyAsync(io.prev_out, prev.p, (size_t)H * 4, hipMemcpyDeviceToDevice, st));
+  }
+  return BZ_OK;
+}
+
 // LoRA in the decode step: after the base launch of a group whose linears are in the table's mask, the group's shrink (x from `px`: the prologue the base
 // launch ran, over state it has left in place) and expand (b from the base launch's VSrc); the consumer then reads the table's f32 row.  The expand takes no
 // ring slot: the accumulator it reads is zeroed by the launch that would have zeroed it anyway.
@@ -1864,6 +1880,7 @@ static int mamba_step(bz_model* m, const StepIO& io) {
     BZ_TRY(run_fused(m, L.out_proj, pg, rs, &ov, &shf));
     prev = ov;
   }
+  BZ_TRY(step_rows_out(m, io, prev, m->hbuf[cur]));
   return step_tail(m, io, rs, prev, m->hbuf[cur]);
 }
 
@@ -1962,6 +1979,7 @@ static int dsv2_step(bz_model* m, const StepIO& io) {
       prev = VSrc{m->moe_out, 0};
     }
   }
+  BZ_TRY(step_rows_out(m, io, prev, m->hbuf[cur]));
   return step_tail(m, io, rs, prev, m->hbuf[cur]);
 }
 
@@ -2000,6 +2018,60 @@ static int emit_logits(bz_model* m, bz_tensor* logits_out, int row) {
   const size_t vb = (size_t)m->cfg.vocab * 4;
   BZ_TRY(check_logits_out(m, logits_out, (size_t)row + 1));
   BZ_HIP(hipMemcpyAsync((char*)logits_out->ptr + (size_t)row * vb, m->logits, vb, hipMemcpyDeviceToDevice, m->dev->stream));
+  return BZ_OK;
+}
+
+// What becomes of the rows of a prompt: the one thing that travels from a forward call down to the tail of a chunk (prompt_head) and to the row of a token-by-token
+// step.  LAST / ALL: the logits of the last row / of every row into the caller's tensor -- what the forward calls have always done, launch for launch.  SCORE: the
+// head ALL would run for the chunk, with the same arguments, into the library's workspace, and the scoring kernels on it (bz_score.hip) -- a record is the record of
+// the ALL row by construction.  HIDDEN: no head; the final norm's rows (the rows a GEMM head reads) as F32 into the pooling kernels.
+enum { SINK_LAST = 0, SINK_ALL = 1, SINK_SCORE = 2, SINK_HIDDEN = 3 };
+struct RowSink {
+  int kind = SINK_LAST;
+  bz_tensor* logits_out = nullptr;                                                        // LAST: F32 [1, vocab]; ALL: F32 [S, vocab]
+  const int64_t* targets = nullptr; const bz_score_config* scfg = nullptr; bz_score_row* rows_out = nullptr; bz_score_total* total = nullptr;   // SCORE (host)
+  const bz_embed_config* ecfg = nullptr; bz_tensor* out = nullptr;                        // HIDDEN
+  bool every_row() const { return kind != SINK_LAST; }
+  bool has_logits() const { return kind == SINK_LAST || kind == SINK_ALL; }
+  static RowSink logits(bool all, bz_tensor* t) { RowSink s; s.kind = all ? SINK_ALL : SINK_LAST; s.logits_out = t; return s; }
+  static RowSink score(const int64_t* targets, const bz_score_config* cfg, bz_score_row* rows_out, bz_score_total* total) {
+    RowSink s; s.kind = SINK_SCORE; s.targets = targets; s.scfg = cfg; s.rows_out = rows_out; s.total = total; return s;
+  }
+  static RowSink hidden(const bz_embed_config* cfg, bz_tensor* out) { RowSink s; s.kind = SINK_HIDDEN; s.ecfg = cfg; s.out = out; return s; }
+};
+// the sink's own arguments, refused before anything is enqueued (LAST / ALL: checked where they always were)
+static int sink_check(const bz_model* m, const RowSink& sink, int S, const char* who) {
+  if (sink.kind == SINK_SCORE) return bzk_check_score_cfg(sink.scfg, sink.targets, S, m->cfg.vocab, sink.rows_out, who);
+  if (sink.kind == SINK_HIDDEN) return bzk_check_embed_cfg(sink.ecfg, sink.out, S, m->cfg.hidden, who);
+  return BZ_OK;
+}
+// rows: the rows of a chunk on a batched route (min(S, chunk)), 0 on the token-by-token route; gemm_head: those chunks take the GEMM head
+static int sink_begin(bz_model* m, const RowSink& sink, int S, int rows, bool gemm_head) {
+  if (sink.kind == SINK_SCORE) return bzk_score_begin(m->dev->stream, &m->sink_ws, S, m->cfg.vocab, gemm_head && rows > 1 ? rows : 0, sink.targets, sink.scfg->top_n);
+  if (sink.kind == SINK_HIDDEN) return bzk_pool_begin(m->dev->stream, &m->sink_ws, S, m->cfg.hidden, std::max(rows, 1), sink.ecfg);
+  return BZ_OK;
+}
+static int sink_end(bz_model* m, const RowSink& sink) {
+  if (sink.kind == SINK_SCORE) return bzk_score_end(m->dev->stream, m->sink_ws, sink.rows_out, sink.total);
+  if (sink.kind == SINK_HIDDEN) return bzk_pool_end(m->dev->stream, m->sink_ws, (float*)sink.out->ptr);
+  return BZ_OK;
+}
+// a token-by-token step of row s: what the step is asked for, and what becomes of what it left
+static void sink_step_io(bz_model* m, const RowSink& sink, StepIO& io, int s, int S) {
+  io.do_head = sink.kind != SINK_HIDDEN && (sink.every_row() || s == S - 1);
+  if (sink.kind == SINK_HIDDEN) bzk_pool_step_rows(m->sink_ws, &io.hidden_out, &io.prev_out);
+}
+static int sink_step_row(bz_model* m, const RowSink& sink, const StepIO& io, int s) {
+  const bz_model_config& c = m->cfg;
+  hipStream_t st = m->dev->stream;
+  if (sink.kind == SINK_SCORE) return bzk_score_chunk(st, m->sink_ws, m->logits, 1, s);
+  if (sink.kind == SINK_HIDDEN) {
+    // the norm the GEMM head's rows go through (bzk_pf_norm), on the step's residual row and deferred residual, stored as f32
+    float* row = bzk_pool_rows_ws(m->sink_ws);
+    BZ_TRY(bzk_pf_norm(st, BZ_F32, io.hidden_out, io.prev_out, m->final_norm, 1, c.hidden, c.rms_eps, c.act_dtype, row));
+    return bzk_pool_chunk(st, m->sink_ws, row, 1, s, (float*)sink.out->ptr);
+  }
+  if (io.do_head) BZ_TRY(emit_logits(m, sink.logits_out, sink.kind == SINK_ALL ? s : 0));
   return BZ_OK;
 }
 
@@ -2125,11 +2197,20 @@ static int rows_attn_prepare(bz_model* m, const bz_paged_kv* kv, int N, int decl
 // otherwise the decode lm_head GEMV per row (final norm fused as its prologue), or the decode step's head on the row (STEP: quantised lm_head).  SPEC (the
 // speculative verify, S <= 16): the multi-row exact lm_head (bz_speculative.hip), which streams the matrix once per 8 rows and leaves per-row argmax partials in
 // m->sp_pval / m->sp_pidx; its logits go to spec_rows [S][vocab] (device).
-static int prompt_head(bz_model* m, hipStream_t st, float* h, const float* prev, int n, int s0, int S, bool all, bz_tensor* logits_out, const bz_prompt_plan_t& plan,
+// The sink (RowSink above) says what becomes of the rows: SCORE runs what ALL runs, into the library's workspace (GEMM) or the model's logits row (per-row heads),
+// and the scoring kernels behind it; HIDDEN runs the GEMM head's norm with f32 storage and no head at all.
+static int prompt_head(bz_model* m, hipStream_t st, float* h, const float* prev, int n, int s0, int S, const RowSink& sink, const bz_prompt_plan_t& plan,
                        float* spec_rows = nullptr) {
   const bz_model_config& c = m->cfg;
   const int H = c.hidden, act = c.act_dtype;
   const LinearDev& LH = m->lm_head.parts[0];
+  const bool all = sink.every_row(), score = sink.kind == SINK_SCORE;
+  bz_tensor* const logits_out = sink.logits_out;
+  if (sink.kind == SINK_HIDDEN) {
+    float* rows = bzk_pool_rows_ws(m->sink_ws);
+    BZ_TRY(bzk_pf_norm(st, BZ_F32, h, prev, m->final_norm, n, H, c.rms_eps, act, rows));
+    return bzk_pool_chunk(st, m->sink_ws, rows, n, s0, (float*)sink.out->ptr);
+  }
   if (plan.head == BZ_HEAD_SPEC) {
     for (int r0 = 0; r0 < n; r0 += 8) {
       SpecHeadRows hr{h + (size_t)r0 * H, prev ? prev + (size_t)r0 * H : nullptr, H, m->final_norm, c.rms_eps, H, act};
@@ -2138,9 +2219,11 @@ static int prompt_head(bz_model* m, hipStream_t st, float* h, const float* prev,
     }
     return BZ_OK;
   }
-  if (plan.head == BZ_HEAD_GEMM && all && n > 1 && logits_out->nbytes >= (size_t)(s0 + n) * c.vocab * 4) {
+  if (plan.head == BZ_HEAD_GEMM && all && n > 1 && (score || logits_out->nbytes >= (size_t)(s0 + n) * c.vocab * 4)) {
+    float* dst = score ? bzk_score_logits_ws(m->sink_ws) : (float*)logits_out->ptr + (size_t)s0 * c.vocab;
     BZ_TRY(bzk_pf_norm(st, act, h, prev, m->final_norm, n, H, c.rms_eps, act, m->pf_x16));
-    return bzk_gemm_nt(st, act, m->pf_x16, LH.w, LH.bias, n, c.vocab, H, act, (float*)logits_out->ptr + (size_t)s0 * c.vocab, m->pf_ws, m->pf_ws_bytes);
+    BZ_TRY(bzk_gemm_nt(st, act, m->pf_x16, LH.w, LH.bias, n, c.vocab, H, act, dst, m->pf_ws, m->pf_ws_bytes));
+    return score ? bzk_score_chunk(st, m->sink_ws, dst, n, s0) : BZ_OK;
   }
   for (int r = 0; r < n; r++) {
     const int srow = s0 + r;
@@ -2157,12 +2240,13 @@ static int prompt_head(bz_model* m, hipStream_t st, float* h, const float* prev,
       o.direct = m->logits; o.amax_val = m->pval; o.amax_idx = m->pidx;
       BZ_TRY(bzk_gemv(st, LH, ph, o, act));
     }
-    BZ_TRY(emit_logits(m, logits_out, all ? srow : 0));
+    if (score) BZ_TRY(bzk_score_chunk(st, m->sink_ws, m->logits, 1, srow));
+    else BZ_TRY(emit_logits(m, logits_out, all ? srow : 0));
   }
   return BZ_OK;
 }
 
-static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvView& view, int pos0, const int* slots, bool all, bz_tensor* logits_out,
+static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvView& view, int pos0, const int* slots, const RowSink& sink,
                          const bz_prompt_plan_t& plan, const RowsCtx& rc = RowsCtx(), float* spec_rows = nullptr) {
   const bz_model_config& c = m->cfg;
   hipStream_t st = step_stream(m);     // (a batched decode graph records this function on its capture stream)
@@ -2213,7 +2297,7 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
       BZ_TRY(lora_rows(l, LG_DOWN, m->pf_t, n, s0));
       prev = m->pf_t;
     }
-    BZ_TRY(prompt_head(m, st, m->pf_h, prev, n, s0, S, all, logits_out, plan, spec_rows));
+    BZ_TRY(prompt_head(m, st, m->pf_h, prev, n, s0, S, sink, plan, spec_rows));
   }
   return BZ_OK;
 }
@@ -2257,7 +2341,7 @@ static int dsv2_prefill_ws(bz_model* m, int rows) {
 __global__ void k_acc_rows(float* acc, const float* y, size_t n, int first) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) acc[i] = first ? y[i] : acc[i] + y[i];
 }
-static int dsv2_prefill(bz_model* m, const long long* d_tok, int S, const KvView& view, int pos0, bool all, bz_tensor* logits_out, const bz_prompt_plan_t& plan) {
+static int dsv2_prefill(bz_model* m, const long long* d_tok, int S, const KvView& view, int pos0, const RowSink& sink, const bz_prompt_plan_t& plan) {
   // (a chunk whose batched rows round to the decode step's bits is told apart by this line: test_gpu_dsv2_prefill.py, "no-shared")
   BZ_TRACE("dsv2_prefill: S=%d position=%d", S, pos0);
   const bz_model_config& c = m->cfg;
@@ -2324,7 +2408,7 @@ static int dsv2_prefill(bz_model* m, const long long* d_tok, int S, const KvView
       }
       prev = m->pf_t;
     }
-    BZ_TRY(prompt_head(m, st, m->pf_h, prev, n, s0, S, all, logits_out, plan));
+    BZ_TRY(prompt_head(m, st, m->pf_h, prev, n, s0, S, sink, plan));
   }
   return BZ_OK;
 }
@@ -2358,50 +2442,69 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
   BZ_API_END
 }
 
-// What bz_forward_kv and bz_forward_paged share once their arguments are checked: S tokens at positions position .. position + S - 1 over `view`
-// (`slots`: a paged cache's slot of every row, else null), logits of every row (`all`) or of the last one.  The caller sets its cache's seq_len.
-static int forward_core(bz_model* m, const bz_tensor* tokens, int S, const KvView& view, const int* slots, int position, bool all, bz_tensor* logits_out) {
+// What the kv / paged forward, score and embed calls share once their arguments are checked: S tokens at positions position .. position + S - 1 over `view`
+// (`slots`: a paged cache's slot of every row, else null), the rows to `sink`.  The caller sets its cache's seq_len.
+static int forward_core(bz_model* m, const bz_tensor* tokens, int S, const KvView& view, const int* slots, int position, const RowSink& sink) {
   const long long* d_tok = (const long long*)tokens->ptr;
   bz_prompt_plan_t plan;
   BZ_TRY(bz_prompt_plan(&m->traits, nullptr, BZ_PLAN_PROMPT, S, position + S, view.dtype, &plan));
+  const bool rows_route = plan.route == BZ_ROUTE_ROWS || plan.route == BZ_ROUTE_DSV2;
+  BZ_TRY(sink_begin(m, sink, S, rows_route ? std::min(S, plan.chunk) : 0, plan.head == BZ_HEAD_GEMM));
   if (plan.route == BZ_ROUTE_ROWS) {
     // prompt-sized inputs of dense 16-bit models: batched prefill, GEMMs on the matrix cores
-    BZ_TRY(check_logits_out(m, logits_out, all ? S : 1));
-    return prefill_dense(m, d_tok, S, view, position, slots, all, logits_out, plan);
+    if (sink.has_logits()) BZ_TRY(check_logits_out(m, sink.logits_out, sink.every_row() ? S : 1));
+    BZ_TRY(prefill_dense(m, d_tok, S, view, position, slots, sink, plan));
+    return sink_end(m, sink);
   }
   if (plan.route == BZ_ROUTE_DSV2) {
     // (paged: the rows' slots follow from the block table: slot = block_table[p / bs] * bs + p % bs, batch_decode.rs:81-88)
-    BZ_TRY(check_logits_out(m, logits_out, all ? S : 1));
-    return dsv2_prefill(m, d_tok, S, view, position, all, logits_out, plan);
+    if (sink.has_logits()) BZ_TRY(check_logits_out(m, sink.logits_out, sink.every_row() ? S : 1));
+    BZ_TRY(dsv2_prefill(m, d_tok, S, view, position, sink, plan));
+    return sink_end(m, sink);
   }
   for (int s = 0; s < S; s++) {
     StepIO io{};
     io.kv = view; io.kv.slot = slots ? slots + s : nullptr; io.d_tok = d_tok + s;
-    io.do_head = all || s == S - 1;
+    sink_step_io(m, sink, io, s, S);
     BZ_TRY(step_at(m, position + s, io, model_step));
-    if (io.do_head) BZ_TRY(emit_logits(m, logits_out, all ? s : 0));
+    BZ_TRY(sink_step_row(m, sink, io, s));
   }
-  return BZ_OK;
+  return sink_end(m, sink);
 }
 
-extern "C" int bz_forward_kv(bz_model* m, const bz_tensor* tokens, int S, bz_kv* kv, int position, bz_tensor* logits_out, uint32_t flags) {
-  BZ_API_BEGIN
+// bz_forward_kv / bz_score_kv / bz_embed_kv: one argument list, one set of refusals, one cache bookkeeping; `who` names the call in the sink's own refusals
+static int forward_kv_sink(bz_model* m, const bz_tensor* tokens, int S, bz_kv* kv, int position, const RowSink& sink, const char* who) {
   BZ_TRY(check_fwd(m, tokens, S));
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   BZ_TRACE("forward_kv: S=%d position=%d", S, position);
   if (m->cfg.arch == BZ_ARCH_MAMBA2) BZ_FAIL(BZ_E_INVALID, "forward_kv: model has no KV cache (use bz_forward_ssm)");
   BZ_TRY(check_cache(m, kv, "forward_kv"));
   if (position < 0 || position + S > m->cfg.max_seq_len) BZ_FAIL(BZ_E_INVALID, "forward_kv: position %d + S %d exceeds max_seq_len %d", position, S, m->cfg.max_seq_len);
+  BZ_TRY(sink_check(m, sink, S, who));
   BZ_TRY(kv_grow(kv, position + S));
-  BZ_TRY(forward_core(m, tokens, S, view_of(kv), nullptr, position, flags & BZ_FWD_ALL_LOGITS, logits_out));
+  BZ_TRY(forward_core(m, tokens, S, view_of(kv), nullptr, position, sink));
   kv->seq_len = position + S;
   return BZ_OK;
+}
+extern "C" int bz_forward_kv(bz_model* m, const bz_tensor* tokens, int S, bz_kv* kv, int position, bz_tensor* logits_out, uint32_t flags) {
+  BZ_API_BEGIN
+  return forward_kv_sink(m, tokens, S, kv, position, RowSink::logits(flags & BZ_FWD_ALL_LOGITS, logits_out), "forward_kv");
+  BZ_API_END
+}
+extern "C" int bz_score_kv(bz_model* m, const bz_tensor* tokens, int S, bz_kv* kv, int position, const int64_t* targets, const bz_score_config* cfg, bz_score_row* rows_out,
+                           bz_score_total* total) {
+  BZ_API_BEGIN
+  return forward_kv_sink(m, tokens, S, kv, position, RowSink::score(targets, cfg, rows_out, total), "score_kv");
+  BZ_API_END
+}
+extern "C" int bz_embed_kv(bz_model* m, const bz_tensor* tokens, int S, bz_kv* kv, int position, const bz_embed_config* cfg, bz_tensor* out) {
+  BZ_API_BEGIN
+  return forward_kv_sink(m, tokens, S, kv, position, RowSink::hidden(cfg, out), "embed_kv");
   BZ_API_END
 }
 
-extern "C" int bz_forward_paged(bz_model* m, const bz_tensor* tokens, int S, bz_paged_kv* kv, const bz_tensor* slot_mapping,
-                                const bz_tensor* block_table, int n_table, int seq_len_k, int start_pos, bz_tensor* logits_out, uint32_t flags) {
-  BZ_API_BEGIN
+static int forward_paged_sink(bz_model* m, const bz_tensor* tokens, int S, bz_paged_kv* kv, const bz_tensor* slot_mapping, const bz_tensor* block_table, int n_table,
+                              int seq_len_k, int start_pos, const RowSink& sink, const char* who) {
   BZ_TRY(check_fwd(m, tokens, S));
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   if (m->cfg.arch == BZ_ARCH_MAMBA2) BZ_FAIL(BZ_E_UNSUPPORTED, "forward_paged: Mamba2 has no KV cache");   // MLA: the latent cache pages like any other (one 'head' of rank + rope values)
@@ -2411,9 +2514,27 @@ extern "C" int bz_forward_paged(bz_model* m, const bz_tensor* tokens, int S, bz_
   if (start_pos < 0 || start_pos + S != seq_len_k) BZ_FAIL(BZ_E_INVALID, "forward_paged: start_pos + S must equal seq_len_k");
   if ((seq_len_k + kv->block_size - 1) / kv->block_size > n_table) BZ_FAIL(BZ_E_INVALID, "forward_paged: block_table too short for seq_len_k");
   if (seq_len_k > m->cfg.max_seq_len) BZ_FAIL(BZ_E_INVALID, "forward_paged: seq_len_k exceeds max_seq_len");
-  BZ_TRY(forward_core(m, tokens, S, view_of(kv, (const int*)block_table->ptr, nullptr), (const int*)slot_mapping->ptr, start_pos, flags & BZ_FWD_ALL_LOGITS, logits_out));
+  BZ_TRY(sink_check(m, sink, S, who));
+  BZ_TRY(forward_core(m, tokens, S, view_of(kv, (const int*)block_table->ptr, nullptr), (const int*)slot_mapping->ptr, start_pos, sink));
   kv->seq_len = seq_len_k;
   return BZ_OK;
+}
+extern "C" int bz_forward_paged(bz_model* m, const bz_tensor* tokens, int S, bz_paged_kv* kv, const bz_tensor* slot_mapping,
+                                const bz_tensor* block_table, int n_table, int seq_len_k, int start_pos, bz_tensor* logits_out, uint32_t flags) {
+  BZ_API_BEGIN
+  return forward_paged_sink(m, tokens, S, kv, slot_mapping, block_table, n_table, seq_len_k, start_pos, RowSink::logits(flags & BZ_FWD_ALL_LOGITS, logits_out), "forward_paged");
+  BZ_API_END
+}
+extern "C" int bz_score_paged(bz_model* m, const bz_tensor* tokens, int S, bz_paged_kv* kv, const bz_tensor* slot_mapping, const bz_tensor* block_table, int n_table,
+                              int seq_len_k, int start_pos, const int64_t* targets, const bz_score_config* cfg, bz_score_row* rows_out, bz_score_total* total) {
+  BZ_API_BEGIN
+  return forward_paged_sink(m, tokens, S, kv, slot_mapping, block_table, n_table, seq_len_k, start_pos, RowSink::score(targets, cfg, rows_out, total), "score_paged");
+  BZ_API_END
+}
+extern "C" int bz_embed_paged(bz_model* m, const bz_tensor* tokens, int S, bz_paged_kv* kv, const bz_tensor* slot_mapping, const bz_tensor* block_table, int n_table,
+                              int seq_len_k, int start_pos, const bz_embed_config* cfg, bz_tensor* out) {
+  BZ_API_BEGIN
+  return forward_paged_sink(m, tokens, S, kv, slot_mapping, block_table, n_table, seq_len_k, start_pos, RowSink::hidden(cfg, out), "embed_paged");
   BZ_API_END
 }
 
@@ -2455,7 +2576,7 @@ extern "C" int bz_forward_paged_batch(bz_model* m, const bz_tensor* tokens, int 
     BZ_HIP(hipStreamSynchronize(m->dev->stream));       // `pos` is a stack-lifetime host buffer
     RowsCtx rc; rc.row_pos = m->row_pos; rc.table_stride = max_blocks; rc.max_len = maxlen;
     BZ_TRY(rows_attn_prepare(m, kv, N, maxlen, "forward_paged_batch", &rc.split_min));
-    BZ_TRY(prefill_dense(m, (const long long*)tokens->ptr, N, view_of(kv, (const int*)block_table->ptr, nullptr), 0, (const int*)slot_mapping->ptr, true, logits_out, plan, rc));
+    BZ_TRY(prefill_dense(m, (const long long*)tokens->ptr, N, view_of(kv, (const int*)block_table->ptr, nullptr), 0, (const int*)slot_mapping->ptr, RowSink::logits(true, logits_out), plan, rc));
     if (kv->seq_len < maxlen) kv->seq_len = maxlen;
     return BZ_OK;
   }
@@ -2483,7 +2604,7 @@ static int check_ssm(bz_model* m, bz_ssm_state* st) {
 // Mamba2 batched prefill (prompts of >= BZ_PREFILL_MIN tokens, dense 16-bit in_proj / out_proj in the activation dtype): rows through the
 // MFMA GEMMs, conv as a map over (token, channel), the recurrence as an in-kernel scan per head (bz_prefill.hip).  Same rounding points as
 // mamba_step, token for token.
-static int mamba_prefill(bz_model* m, const long long* d_tok, int S, bz_ssm_state* state, bool all, bz_tensor* logits_out, const bz_prompt_plan_t& plan) {
+static int mamba_prefill(bz_model* m, const long long* d_tok, int S, bz_ssm_state* state, const RowSink& sink, const bz_prompt_plan_t& plan) {
   BZ_TRACE("mamba_prefill: S=%d", S);
   const bz_model_config& c = m->cfg;
   hipStream_t st = m->dev->stream;
@@ -2523,32 +2644,48 @@ static int mamba_prefill(bz_model* m, const long long* d_tok, int S, bz_ssm_stat
       BZ_TRY(bzk_gemm_nt(st, act, m->mpf_x16, Pout.w, Pout.bias, n, Pout.N, Pout.K, act, m->mpf_t, m->pf_ws, m->pf_ws_bytes));
       prev = m->mpf_t;
     }
-    BZ_TRY(prompt_head(m, st, m->mpf_h, prev, n, s0, S, all, logits_out, plan));
+    BZ_TRY(prompt_head(m, st, m->mpf_h, prev, n, s0, S, sink, plan));
   }
   return BZ_OK;
 }
 
-extern "C" int bz_forward_ssm(bz_model* m, const bz_tensor* tokens, int S, bz_ssm_state* st, bz_tensor* logits_out, uint32_t flags) {
-  BZ_API_BEGIN
+static int forward_ssm_sink(bz_model* m, const bz_tensor* tokens, int S, bz_ssm_state* st, const RowSink& sink, const char* who) {
   BZ_TRY(check_fwd(m, tokens, S));
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   BZ_TRY(check_ssm(m, st));
-  const bool all = flags & BZ_FWD_ALL_LOGITS;
+  BZ_TRY(sink_check(m, sink, S, who));
   bz_prompt_plan_t plan;
   BZ_TRY(bz_prompt_plan(&m->traits, nullptr, BZ_PLAN_PROMPT, S, S, st->dtype, &plan));
+  BZ_TRY(sink_begin(m, sink, S, plan.route == BZ_ROUTE_MAMBA ? std::min(S, plan.chunk) : 0, plan.head == BZ_HEAD_GEMM));
   if (plan.route == BZ_ROUTE_MAMBA) {
-    BZ_TRY(check_logits_out(m, logits_out, all ? S : 1));
+    if (sink.has_logits()) BZ_TRY(check_logits_out(m, sink.logits_out, sink.every_row() ? S : 1));
     BZ_HIP(hipSetDevice(m->dev->id));
-    return mamba_prefill(m, (const long long*)tokens->ptr, S, st, all, logits_out, plan);
+    BZ_TRY(mamba_prefill(m, (const long long*)tokens->ptr, S, st, sink, plan));
+    return sink_end(m, sink);
   }
   for (int s = 0; s < S; s++) {
     StepIO io{};
     io.ssm = st; io.d_tok = (const long long*)tokens->ptr + s;
-    io.do_head = all || s == S - 1;
+    sink_step_io(m, sink, io, s, S);
     BZ_TRY(mamba_step(m, io));
-    if (io.do_head) BZ_TRY(emit_logits(m, logits_out, all ? s : 0));
+    BZ_TRY(sink_step_row(m, sink, io, s));
   }
-  return BZ_OK;
+  return sink_end(m, sink);
+}
+extern "C" int bz_forward_ssm(bz_model* m, const bz_tensor* tokens, int S, bz_ssm_state* st, bz_tensor* logits_out, uint32_t flags) {
+  BZ_API_BEGIN
+  return forward_ssm_sink(m, tokens, S, st, RowSink::logits(flags & BZ_FWD_ALL_LOGITS, logits_out), "forward_ssm");
+  BZ_API_END
+}
+extern "C" int bz_score_ssm(bz_model* m, const bz_tensor* tokens, int S, bz_ssm_state* st, const int64_t* targets, const bz_score_config* cfg, bz_score_row* rows_out,
+                            bz_score_total* total) {
+  BZ_API_BEGIN
+  return forward_ssm_sink(m, tokens, S, st, RowSink::score(targets, cfg, rows_out, total), "score_ssm");
+  BZ_API_END
+}
+extern "C" int bz_embed_ssm(bz_model* m, const bz_tensor* tokens, int S, bz_ssm_state* st, const bz_embed_config* cfg, bz_tensor* out) {
+  BZ_API_BEGIN
+  return forward_ssm_sink(m, tokens, S, st, RowSink::hidden(cfg, out), "embed_ssm");
   BZ_API_END
 }
 
@@ -3180,7 +3317,7 @@ static int batch_graph_capture(bz_model* m, bz_paged_kv* kv, int N, int max_bloc
     if (er) BZ_TRY(bzk_engine_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N, er->rows));
     else BZ_TRY(bzk_batch_advance(cap, g->tok, g->next, g->pos, g->slot, g->table, max_blocks, kv->block_size, N));
     RowsCtx rcx; rcx.row_pos = g->pos; rcx.table_stride = max_blocks; rcx.max_len = capacity; rcx.row_lora = g->row_lora; rcx.split_min = rows_split_min;
-    BZ_TRY(prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, true, g->logits, plan, rcx));
+    BZ_TRY(prefill_dense(m, g->tok, N, view_of(kv, g->table, nullptr), 0, g->slot, RowSink::logits(true, g->logits), plan, rcx));
     // a sampler with bz_batch_sampler_enable (sampling.rs:414-431): logprobs on the raw rows, mask, bias, pick, records; without it none of the three launches anything
     if (s) BZ_TRY(bzk_lp_pre(cap, s, (const float*)g->logits->ptr));
     if (c) BZ_TRY(bzk_grammar_mask_rows(cap, c, (float*)g->logits->ptr));
@@ -3756,7 +3893,7 @@ static int llama_verify_rows(bz_model* m, const long long* d_tok, int R, bz_kv* 
   const bool fast = plan.route == BZ_ROUTE_ROWS;
   BZ_TRACE("verify: R=%d position=%d path=%d", R, position, (int)fast);
   if (fast) {
-    BZ_TRY(prefill_dense(m, d_tok, R, view_of(kv), position, nullptr, true, nullptr, plan, RowsCtx(), logits));
+    BZ_TRY(prefill_dense(m, d_tok, R, view_of(kv), position, nullptr, RowSink::logits(true, nullptr), plan, RowsCtx(), logits));
     BZ_TRY(bzk_spec_argmax_final(st, m->sp_pval, m->sp_pidx, m->sp_nb, R, m->sp_argmax));
   } else {
     for (int r = 0; r < R; r++) {

@@ -420,6 +420,24 @@ int bzk_lp_post(hipStream_t s, bz_batch_sampler* bs, const float* logits, const 
 int bzk_lp_check_bias(long long V, const uint32_t* ids, const float* vals, int n, std::vector<uint32_t>& ids_out, std::vector<float>& vals_out, const char* who);
 size_t bzk_lp_stage_bytes();
 int bzk_lp_stage_row(hipStream_t st, bz_batch_sampler* bs, int row, int top_n, const uint32_t* ids, const float* vals, int cnt, void* stage);
+// the sink of a score / embed call (bz_score.hip): library-owned buffers that hang off the model (null until the first such call, freed with it).  A call is
+// begin (checks made by the caller; grows the buffers -- after a stream synchronise -- and stages the call's parameters), one `chunk` per prompt chunk or per row in
+// row order, and end (the one wait of the call).
+struct BzSinkWs;
+void bzk_sink_free(BzSinkWs* w);
+// logits_rows: rows of the F32 [logits_rows][V] workspace a GEMM head writes (0: every head of the call is per-row and scores the model's logits row)
+int bzk_score_begin(hipStream_t st, BzSinkWs** w, int S, long long V, int logits_rows, const int64_t* targets_host, int top_n);
+float* bzk_score_logits_ws(BzSinkWs* w);
+int bzk_score_chunk(hipStream_t st, BzSinkWs* w, const float* logits /*[n][V]*/, int n, int s0);
+int bzk_score_end(hipStream_t st, BzSinkWs* w, bz_score_row* rows_out, bz_score_total* total);
+// rows: rows of the F32 [rows][H] workspace the final norm writes; two more rows follow it (bzk_pool_step_rows: hidden / prev of a token-by-token step)
+int bzk_pool_begin(hipStream_t st, BzSinkWs** w, int S, int H, int rows, const bz_embed_config* cfg);
+float* bzk_pool_rows_ws(BzSinkWs* w);
+void bzk_pool_step_rows(BzSinkWs* w, float** hidden, float** prev);
+int bzk_pool_chunk(hipStream_t st, BzSinkWs* w, const float* rows /*[n][H]*/, int n, int s0, float* out);
+int bzk_pool_end(hipStream_t st, BzSinkWs* w, float* out);
+int bzk_check_score_cfg(const bz_score_config* cfg, const int64_t* targets, int S, long long V, const void* rows_out, const char* who);
+int bzk_check_embed_cfg(const bz_embed_config* cfg, const bz_tensor* out, int S, int H, const char* who);
 // per-row grammar cursor (bz_grammar.hip): the two launches a captured step takes, on the stream it is captured on
 int bzk_grammar_cursor_dims(const bz_grammar_cursor* c, int* N, long long* V, bz_device** dev);
 int bzk_grammar_mask_rows(hipStream_t s, bz_grammar_cursor* c, float* logits /*[N,V]*/);

@@ -25,8 +25,7 @@
 #include <vector>
 
 #include "bz_internal.h"
-
-typedef unsigned long long u64;
+#include "bz_lp_dev.h"
 
 namespace {
 constexpr int NB = 128;                         // blocks per row of the streaming passes
@@ -40,39 +39,6 @@ struct LpArgs {
   int* top_n; float* pmax; u64* S; u64* cand;                   // [N], [N][NB], [N], [N][NB][TOPN]
   bz_logprobs_record* ring; int ringcap;                        // pinned host [ringcap][N]
 };
-
-// larger = earlier in (x descending, id ascending); 0 = no entry (a NaN logit maps there: never listed)
-__device__ __forceinline__ u64 lp_composite(float x, long long i) {
-  if (x != x) return 0;
-  unsigned b = x == 0.0f ? 0u : __float_as_uint(x);             // -0 orders as +0: equal logits tie on the id alone
-  b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ((u64)b << 32) | (u64)(0xFFFFFFFFu - (unsigned)i);
-}
-__device__ __forceinline__ float lp_logit_of(u64 c) {
-  const unsigned k = (unsigned)(c >> 32);
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-__device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a > b ? a : b; }
-// every thread of the 256 gets the block's maximum (two barriers; red: 4 words of LDS)
-__device__ __forceinline__ u64 block_max_u64(u64 v, u64* red) {
-  for (int k = 32; k >= 1; k >>= 1) {
-    const unsigned lo = __shfl_xor((unsigned)v, k, 64), hi = __shfl_xor((unsigned)(v >> 32), k, 64);
-    v = umax64(v, ((u64)hi << 32) | lo);
-  }
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const u64 t = umax64(umax64(red[0], red[1]), umax64(red[2], red[3]));
-  __syncthreads();
-  return t;
-}
-__device__ __forceinline__ float block_max_f(float v, float* red) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float t = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  return t;
-}
 
 __global__ __launch_bounds__(256) void k_lp_max(LpArgs a, const float* logits) {
   __shared__ float redf[4];

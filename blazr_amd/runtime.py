@@ -584,6 +584,60 @@ class LoadedModel:
         L.check(L.lib().bz_paged_attn_decode_rows(self.h, tq.h, cache.h, int(layer), tb.h, int(bt.shape[1]), sl.ctypes.data_as(C.c_void_p), n, out.h))
         return out.to_numpy().reshape(qa.shape)
 
+    # --- scoring and embeddings (bz_score_* / bz_embed_*: a forward call whose rows go to a sink inside the library) ---------------------------------
+    def _score(self, call, S, tokens, targets, top_logprobs):
+        if targets is None:                                       # each token given its predecessors: row i reads the likelihood of token i + 1
+            tk = tokens.to_numpy().reshape(-1) if isinstance(tokens, Tensor) else np.asarray(tokens, dtype=np.int64).reshape(-1)
+            targets = np.concatenate([tk[1:], [-1]])
+        tg = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
+        if len(tg) != S:
+            raise ValueError("score: %d targets for %d tokens" % (len(tg), S))
+        cfg = L.ScoreConfig(top_n=int(top_logprobs))
+        rows, tot = (L.ScoreRow * S)(), L.ScoreTotal()
+        L.check(call(_ptr(tg), C.byref(cfg), rows, C.byref(tot)))
+        return score_result(rows, tot)
+
+    def score(self, tokens, cache, position=0, targets=None, top_logprobs=0):
+        """Log-likelihoods of given tokens from one prompt pass (echo + logprobs, perplexity, loglikelihood requests).  targets[i] is the token read from row i
+        (-1: nothing); by default each token given its predecessors.  `cache`: a LayeredKvCache (at `position`: a continuation is a second call at
+        position = len(context) on the same cache) or a LayeredSsmState.  -> dict(rows = SCORE_ROW array [S], sum_logprob, n_scored, perplexity = exp(-sum / n))."""
+        t, S = self._tokens(tokens)
+        if isinstance(cache, LayeredSsmState):
+            return self._score(lambda tg, cfg, rows, tot: L.lib().bz_score_ssm(self.h, t.h, S, cache.h, tg, cfg, rows, tot), S, tokens, targets, top_logprobs)
+        return self._score(lambda tg, cfg, rows, tot: L.lib().bz_score_kv(self.h, t.h, S, cache.h, int(position), tg, cfg, rows, tot), S, tokens, targets, top_logprobs)
+
+    def score_paged(self, tokens, cache, slot_mapping, block_table, seq_len_k, start_pos, targets=None, top_logprobs=0):
+        t, S = self._tokens(tokens)
+        sm = slot_mapping if isinstance(slot_mapping, Tensor) else self.dev.tensor(np.asarray(slot_mapping, dtype=np.int32))
+        bt = block_table if isinstance(block_table, Tensor) else self.dev.tensor(np.asarray(block_table, dtype=np.int32).reshape(-1))
+        return self._score(lambda tg, cfg, rows, tot: L.lib().bz_score_paged(self.h, t.h, S, cache.h, sm.h, bt.h, int(np.prod(bt.shape)), seq_len_k, start_pos, tg, cfg,
+                                                                             rows, tot), S, tokens, targets, top_logprobs)
+
+    def _embed_out(self, S, pooling, normalize):
+        if pooling not in L.POOLINGS:
+            raise ValueError("embed: pooling %r (one of %s)" % (pooling, ", ".join(sorted(L.POOLINGS))))
+        cfg = L.EmbedConfig(pooling=L.POOLINGS[pooling], normalize=int(bool(normalize)))
+        return cfg, self.dev.zeros((S, self.c.hidden) if pooling == "none" else (self.c.hidden,), L.F32)
+
+    def embed(self, tokens, cache, position=0, pooling="mean", normalize=False):
+        """Contextual embedding of a prompt (/v1/embeddings): the rows the lm_head would read -- every layer and the final norm -- pooled ("mean", "cls", "last";
+        "none": the rows themselves) and optionally L2-normalised.  -> f32 array [hidden] ([S, hidden] for "none").  `cache` as in score()."""
+        t, S = self._tokens(tokens)
+        cfg, out = self._embed_out(S, pooling, normalize)
+        if isinstance(cache, LayeredSsmState):
+            L.check(L.lib().bz_embed_ssm(self.h, t.h, S, cache.h, C.byref(cfg), out.h))
+        else:
+            L.check(L.lib().bz_embed_kv(self.h, t.h, S, cache.h, int(position), C.byref(cfg), out.h))
+        return out.to_numpy().reshape(out.shape)
+
+    def embed_paged(self, tokens, cache, slot_mapping, block_table, seq_len_k, start_pos, pooling="mean", normalize=False):
+        t, S = self._tokens(tokens)
+        sm = slot_mapping if isinstance(slot_mapping, Tensor) else self.dev.tensor(np.asarray(slot_mapping, dtype=np.int32))
+        bt = block_table if isinstance(block_table, Tensor) else self.dev.tensor(np.asarray(block_table, dtype=np.int32).reshape(-1))
+        cfg, out = self._embed_out(S, pooling, normalize)
+        L.check(L.lib().bz_embed_paged(self.h, t.h, S, cache.h, sm.h, bt.h, int(np.prod(bt.shape)), seq_len_k, start_pos, C.byref(cfg), out.h))
+        return out.to_numpy().reshape(out.shape)
+
     def forward_embed(self, tokens):
         t, S = self._tokens(tokens)
         out = self.dev.zeros((S, self.c.hidden), L.F32)
@@ -889,6 +943,92 @@ def logits_to_token(dev, logits, ids, cnts, repeat_penalty=1.0, frequency_penalt
     L.check(L.lib().bz_logits_to_token(dev.h, logits.h, rows, vocab, tid.h if n else None, tcn.h if n else None, n, repeat_penalty,
                                        frequency_penalty, presence_penalty, temperature, top_k, top_p, min_p, seed, out.h))
     return out
+
+
+# bz_score_row as a numpy record (same layout: 192 bytes)
+SCORE_ROW = np.dtype([("target", np.int64), ("logit", np.float32), ("logprob", np.float32), ("lse", np.float32), ("rank", np.int32), ("n_top", np.int32),
+                      ("top_ids", np.uint32, (L.TOP_LOGPROBS_MAX,)), ("top_logprobs", np.float32, (L.TOP_LOGPROBS_MAX,))], align=True)
+
+
+def score_result(rows, total=None):
+    """ctypes ScoreRow array (+ ScoreTotal) -> dict(rows, sum_logprob, n_scored, perplexity); without a total it is added here as the library adds it"""
+    r = np.frombuffer(bytes(rows), dtype=SCORE_ROW).copy()
+    if total is None:
+        lp = r["logprob"][(r["n_top"] >= 0) & np.isfinite(r["logprob"])]
+        ssum, n = float(np.cumsum(lp.astype(np.float64))[-1]) if len(lp) else 0.0, len(lp)
+    else:
+        ssum, n = float(total.sum_logprob), int(total.n_scored)
+    return dict(rows=r, sum_logprob=ssum, n_scored=n, perplexity=float(np.exp(-ssum / n)) if n else float("nan"))
+
+
+def score_rows(dev, logits, targets, top_logprobs=0):
+    """bz_score_rows (op level): logits F32 [R, V] (device tensor or array), targets [R] (-1: not scored) -> as LoadedModel.score"""
+    lg = logits if isinstance(logits, Tensor) else dev.tensor(np.ascontiguousarray(logits, dtype=np.float32))
+    R, V = lg.shape
+    tg = dev.tensor(np.ascontiguousarray(targets, dtype=np.int64).reshape(-1))
+    if tg.shape[0] != R:
+        raise ValueError("score_rows: %d targets for %d rows" % (tg.shape[0], R))
+    cfg, rows = L.ScoreConfig(top_n=int(top_logprobs)), (L.ScoreRow * R)()
+    L.check(L.lib().bz_score_rows(dev.h, lg.h, R, V, tg.h, C.byref(cfg), rows))
+    return score_result(rows)
+
+
+def score_row_spec(x, target, top_logprobs=0):
+    """bz_score_row_spec: the definition of one row's record, evaluated on the host -> one SCORE_ROW record"""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    row = (L.ScoreRow * 1)()
+    L.check(L.lib().bz_score_row_spec(_ptr(x), len(x), int(target), int(top_logprobs), row))
+    return np.frombuffer(bytes(row), dtype=SCORE_ROW).copy()[0]
+
+
+def _embed_cfg(pooling, normalize):
+    if pooling not in L.POOLINGS:
+        raise ValueError("pooling %r (one of %s)" % (pooling, ", ".join(sorted(L.POOLINGS))))
+    return L.EmbedConfig(pooling=L.POOLINGS[pooling], normalize=int(bool(normalize)))
+
+
+def pool_rows(dev, hidden, pooling="mean", normalize=False):
+    """bz_pool_rows (op level): hidden F32 [S, H] (device tensor or array) -> f32 array [H] ([S, H] for "none")"""
+    hd = hidden if isinstance(hidden, Tensor) else dev.tensor(np.ascontiguousarray(hidden, dtype=np.float32))
+    S, H = hd.shape
+    cfg = _embed_cfg(pooling, normalize)
+    out = dev.zeros((S, H) if pooling == "none" else (H,), L.F32)
+    L.check(L.lib().bz_pool_rows(dev.h, hd.h, S, H, C.byref(cfg), out.h))
+    return out.to_numpy().reshape(out.shape)
+
+
+def pool_spec(hidden, pooling="mean", normalize=False):
+    """bz_pool_spec: the definition of pooling, evaluated on the host"""
+    hd = np.ascontiguousarray(hidden, dtype=np.float32)
+    S, H = hd.shape
+    cfg = _embed_cfg(pooling, normalize)
+    out = np.zeros((S, H) if pooling == "none" else (H,), dtype=np.float32)
+    L.check(L.lib().bz_pool_spec(_ptr(hd), S, H, C.byref(cfg), _ptr(out)))
+    return out
+
+
+def cosine_similarity(a, b):
+    """rerank.rs:206-224: f32 running sums in element order, dot / (sqrt(|a|^2) * sqrt(|b|^2)) if that exceeds 1e-12, else 0.0 (also for unequal or zero lengths)"""
+    a, b = np.asarray(a, dtype=np.float32).reshape(-1), np.asarray(b, dtype=np.float32).reshape(-1)
+    if len(a) != len(b) or len(a) == 0:
+        return 0.0
+    dot, na, nb = np.float32(0), np.float32(0), np.float32(0)
+    for x, y in zip(a, b):
+        dot = np.float32(dot + np.float32(x * y)); na = np.float32(na + np.float32(x * x)); nb = np.float32(nb + np.float32(y * y))
+    denom = np.float32(np.sqrt(na) * np.sqrt(nb))
+    return float(np.float32(dot / denom)) if denom > 1e-12 else 0.0
+
+
+def rerank(model, cache, query, docs, top_n=None):
+    """/rerank (rerank.rs:206): mean-pooled embeddings of the query and of every document (each from position 0 of `cache`, which is reset between them), cosine
+    similarity, highest first, ties in document order -> list of dict(index, relevance_score), at most top_n"""
+    def emb(tokens):
+        cache.reset()
+        return model.embed(tokens, cache, 0, pooling="mean")
+    q = emb(query)
+    scored = [dict(index=i, relevance_score=cosine_similarity(q, emb(d))) for i, d in enumerate(docs)]
+    scored.sort(key=lambda e: -e["relevance_score"])              # stable
+    return scored[:top_n] if top_n is not None else scored
 
 
 def spec_accept(dev, logits, draft):

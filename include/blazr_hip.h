@@ -325,6 +325,55 @@ int bz_batch_sampler_set_row_logprobs(bz_batch_sampler* s, int row, int top_n);
 int bz_batch_sampler_read_logprobs(bz_batch_sampler* s, bz_logprobs_record* out /*[N]*/);
 int bz_decode_batch_graph_read_logprobs(bz_batch_graph* g, int64_t step, bz_logprobs_record* out /*[N]*/);
 
+/* ---- prompt scoring and pooled embeddings (beyond the reference's surface; new symbols only, BZ_ABI_VERSION unchanged) ------------------------------------
+ * A prompt pass gives more than the next token.  Both calls below are a forward call (same cache writes, same seq_len bookkeeping, same LoRA handling, the same
+ * prompt plan asked the same way) whose rows go to a SINK inside the library instead of a caller-owned [S, vocab] tensor.
+ *
+ * SCORE (echo + logprobs, perplexity, the loglikelihood requests of evaluation harnesses): targets[i] (host, [S]) is the token whose likelihood is read from row i
+ *   -- the caller passes the tokens shifted by one, and -1 where nothing is wanted; a continuation is scored by a second call at position = len(context) on the
+ *   same cache.  The call runs the head BZ_FWD_ALL_LOGITS would run for each chunk, with the same arguments, into a library-owned F32 [min(S, chunk), vocab]
+ *   workspace (allocated on first use, grown when a later call needs more, owned by the model and freed with it: 1.05 GB for a full 2 048-row chunk at a 128 256
+ *   vocabulary -- against S * vocab * 4 bytes in the caller's hands for ALL_LOGITS plus the copy to the host), so every record is the record of the ALL_LOGITS row
+ *   by construction.  Per row x, the arithmetic of the batched sampler's logprobs above (sampling.rs:197-256): M = max x, q_i = floor(exp_spec(x_i - M) * 2^40),
+ *   S = sum q_i (integer: order-free), lse = (float)log(S * 2^-40) + M, every logprob the f32 subtraction x - lse, top = the first min(top_n, V, 20) ids by (logit
+ *   descending, id ascending).  Beyond it: the target's raw logit and its RANK = #{x_j > x_t} + #{x_j == x_t, j < t} (0-based; -0 ties with +0; a NaN logit is
+ *   never counted; -1 when the target's own logit is NaN).  A row with target -1 is not scored: rank = -1, n_top = -1, logprob = lse = logit = 0.
+ *   total (nullable): sum of the logprobs and their count, added on the host in row order over the scored rows whose logprob is finite.
+ * EMBED (/v1/embeddings and /rerank: Executor::get_embeddings, engine/executor_embed.rs:33-55, whose comment asks for a forward_hidden that runs all layers and the
+ *   final norm; pooling server/pooling.rs:4-47; cosine server/rerank.rs:139-171,206): the row of position s is the final RMSNorm of the residual stream plus the
+ *   deferred residual, rounded to the activation dtype -- the row the lm_head reads -- delivered as F32 on every route; the head is not run.  pooling NONE copies
+ *   the rows ([S, hidden]); CLS is row 0 of the call; LAST row S - 1; MEAN adds (double)x[s][j] in row order and returns (float)(sum / S).  ASSUMPTION: the
+ *   reference's mean is an f32 running sum whose order its backend decides; a fixed-order double sum makes the result a pure function of the rows (the reference's
+ *   own test vectors come out identical either way).  normalize: on the pooled vector (each row for NONE) norm = sqrt(sum (double)v_j^2), v_j = (float)((double)v_j
+ *   / norm) when norm > 1e-12, else unchanged (pooling.rs:40-47).
+ * BZ_E_INVALID naming the figure, before anything is enqueued: a target >= vocab or < -1, top_n outside 0..20, an unknown pooling, an `out` that is too small, and
+ * whatever the forward call of the same name refuses (cache / architecture mismatch, positions).  Not built: packed multi-sequence (varlen) prompt batches, scoring
+ * or embedding inside the request engine, a bidirectional (non-causal) mask for encoder-style embedding models. */
+typedef struct { int32_t top_n; /* 0..20 */ int32_t reserved[7]; } bz_score_config;
+typedef struct { int64_t target; float logit, logprob, lse; int32_t rank, n_top;
+                 uint32_t top_ids[BZ_TOP_LOGPROBS_MAX]; float top_logprobs[BZ_TOP_LOGPROBS_MAX]; } bz_score_row;
+typedef struct { double sum_logprob; int64_t n_scored; } bz_score_total;   /* host, added in row order over rows with a finite logprob */
+enum { BZ_POOL_NONE = 0, BZ_POOL_MEAN = 1, BZ_POOL_CLS = 2, BZ_POOL_LAST = 3 };
+typedef struct { int32_t pooling, normalize; int32_t reserved[6]; } bz_embed_config;
+int bz_score_kv(bz_model* m, const bz_tensor* tokens, int S, bz_kv* kv, int position, const int64_t* targets /*host [S]*/, const bz_score_config* cfg,
+                bz_score_row* rows_out /*host [S]*/, bz_score_total* total /*nullable*/);
+int bz_score_paged(bz_model* m, const bz_tensor* tokens, int S, bz_paged_kv* kv, const bz_tensor* slot_mapping, const bz_tensor* block_table, int n_table,
+                   int seq_len_k, int start_pos, const int64_t* targets, const bz_score_config* cfg, bz_score_row* rows_out, bz_score_total* total);
+int bz_score_ssm(bz_model* m, const bz_tensor* tokens, int S, bz_ssm_state* state, const int64_t* targets, const bz_score_config* cfg, bz_score_row* rows_out,
+                 bz_score_total* total);
+int bz_embed_kv(bz_model* m, const bz_tensor* tokens, int S, bz_kv* kv, int position, const bz_embed_config* cfg, bz_tensor* out /*F32 [hidden], or [S,hidden] for NONE*/);
+int bz_embed_paged(bz_model* m, const bz_tensor* tokens, int S, bz_paged_kv* kv, const bz_tensor* slot_mapping, const bz_tensor* block_table, int n_table,
+                   int seq_len_k, int start_pos, const bz_embed_config* cfg, bz_tensor* out);
+int bz_embed_ssm(bz_model* m, const bz_tensor* tokens, int S, bz_ssm_state* state, const bz_embed_config* cfg, bz_tensor* out);
+/* op level, as bz_spec_accept is: the records of logits F32 [R,V] rows (any R) against targets I64 [R] on the device; rows_out on the host (waits for the stream) */
+int bz_score_rows(bz_device* dev, const bz_tensor* logits, int64_t R, int64_t V, const bz_tensor* targets, const bz_score_config* cfg, bz_score_row* rows_out);
+/* op level: hidden F32 [S,H] rows -> out F32 [H] ([S,H] for NONE); waits for the stream (the column sums are the call's own) */
+int bz_pool_rows(bz_device* dev, const bz_tensor* hidden, int64_t S, int64_t H, const bz_embed_config* cfg, bz_tensor* out);
+/* The two definitions evaluated on the HOST, public for the reason bz_expf_spec is: a CPU-only test pins them against an independent restatement, and the device
+ * tests compare the kernels with them.  They run the expressions the kernels run (composite key, integer term, sequential double sums). */
+int bz_score_row_spec(const float* x, int64_t V, int64_t target, int top_n, bz_score_row* row_out);
+int bz_pool_spec(const float* hidden, int64_t S, int64_t H, const bz_embed_config* cfg, float* out);
+
 /* ---- host decode loop (Executor::generate contiguous branch, executor_generate.rs:341-410) ---------------- */
 typedef struct {
   int32_t max_tokens;

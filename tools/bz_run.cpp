@@ -8,6 +8,8 @@
 //          [--grammar FILE --vocab-bytes FILE [--grammar-regular]]
 //          [--draft <checkpoint> [--spec-tokens k] [--spec-adaptive]]
 //          [--lora <PEFT dir | adapter_model.safetensors>]... [--lora-targets q,v,...]
+//   bz-run <model> --prompt 1,2,3 --score [--top-logprobs K]
+//   bz-run <model> --prompt 1,2,3 --embed mean|cls|last|none [--normalize]
 //   bz-run <model> --requests FILE --rows N [--pool-blocks B] [--prefill-chunk C] [--depth D] [--prefix-cache] [sampling options, --eos]
 // --requests: continuous batching (BatchEngine::run, engine/batch_engine.rs:91-169; RequestScheduler::submit, engine/request_scheduler.rs:105-205) over N rows.  The file
 // has one request per line, `max_tokens;comma-separated prompt ids`; all are submitted, the engine is stepped until idle, and one line of ids per request is
@@ -21,7 +23,12 @@
 // the same ids as without it; iterations / accepted / rejected go to stderr (generate_text.rs:130-135).
 // --grammar: a GBNF file (gen_config.grammar, executor_generate.rs:96-121), compiled with the reference's semantics or, with --grammar-regular, as the regular subset of
 // GBNF; with --graphs (Llama family, no penalty) the captured step carries the DFA state on the device.  --vocab-bytes: the bytes of every token, which blazr takes from its tokenizer (executor_generate.rs:104-113): u32 V, u32 offsets[V+1], then the bytes.
+// --score: one prompt pass, the log-likelihood of every prompt token given its predecessors (bz_score_kv / bz_score_ssm; echo + logprobs, perplexity): one line per
+// position from the second on -- `position token logprob rank`, then with --top-logprobs K the K likeliest ids as id:logprob -- then `total <sum> tokens <n> perplexity <p>`.
+// --embed: the prompt's contextual embedding (bz_embed_kv / bz_embed_ssm; /v1/embeddings: engine/executor_embed.rs:33-55, server/pooling.rs:4-47), pooled as named
+// and L2-normalised with --normalize: the vector on one line, comma separated (`none`: one line per position).
 // prints the generated ids, comma separated, on stdout.
+#include <cmath>
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -94,6 +101,7 @@ int main(int argc, char** argv) {
   std::string draft_path; bz_spec_config sc;
   std::string requests_path; int rows = 0, pool_blocks = 0, prefill_chunk = 0, depth = 2; bool prefix_cache = false;
   std::vector<std::string> lora_paths; std::string lora_targets; std::vector<bz_lora*> loras;
+  bool score = false; int top_logprobs = 0; std::string embed; bool normalize = false;
   int logprobs = -1; std::vector<uint32_t> bias_ids; std::vector<float> bias_vals;   // --requests: every request asks for K alternatives / carries this bias
   memset(&sc, 0, sizeof sc);
   for (int i = 2; i < argc; i++) {
@@ -125,6 +133,10 @@ int main(int argc, char** argv) {
     else if (a == "--depth") depth = atoi(next("--depth"));
     else if (a == "--prefix-cache") prefix_cache = true;
     else if (a == "--logprobs") logprobs = atoi(next("--logprobs"));
+    else if (a == "--score") score = true;
+    else if (a == "--top-logprobs") top_logprobs = atoi(next("--top-logprobs"));
+    else if (a == "--embed") embed = next("--embed");
+    else if (a == "--normalize") normalize = true;
     else if (a == "--logit-bias") {
       const char* q = next("--logit-bias"); char* end;
       while (*q) {
@@ -271,6 +283,60 @@ int main(int argc, char** argv) {
   if (bz_load_model(dev, model.c_str(), &m, &cfg) != BZ_OK) return fail("load");          // detect_model_source + load_model (run.rs:88-118)
   if (int rc = setup_lora(dev, m, lora_paths, lora_targets, loras)) return rc;
   if (!loras.empty() && bz_model_set_lora(m, 0) != BZ_OK) return fail("set lora");          // single-sequence modes: the first adapter
+  if (score || !embed.empty()) {
+    if (score && !embed.empty()) { fprintf(stderr, "bz-run: --score and --embed do not go together\n"); return 2; }
+    static const char* const kPool[4] = {"none", "mean", "cls", "last"};      // BZ_POOL_*
+    bz_embed_config ecfg;
+    memset(&ecfg, 0, sizeof ecfg);
+    ecfg.pooling = -1; ecfg.normalize = normalize ? 1 : 0;
+    for (int i = 0; i < 4; i++) if (embed == kPool[i]) ecfg.pooling = i;
+    if (!score && ecfg.pooling < 0) { fprintf(stderr, "bz-run: --embed takes mean, cls, last or none\n"); return 2; }
+    if (bz_model_get_config(m, &cfg) != BZ_OK) return fail("config");            // the cache's shape as the library keeps it (MLA: one latent 'head')
+    const int S = (int)prompt.size();
+    const int64_t shp[1] = {S};
+    bz_tensor* tok = nullptr;
+    if (bz_tensor_from_host(dev, BZ_I64, shp, 1, prompt.data(), &tok) != BZ_OK) return fail("tokens");
+    bz_kv* kv = nullptr; bz_ssm_state* ssm = nullptr;
+    const bool is_ssm = cfg.arch == BZ_ARCH_MAMBA2;
+    if (is_ssm ? bz_ssm_state_create(m, 1, cfg.act_dtype, &ssm) != BZ_OK
+               : bz_kv_create(dev, cfg.n_layers, 1, cfg.n_kv_heads, S, cfg.max_seq_len, cfg.head_dim, cfg.act_dtype, &kv) != BZ_OK) return fail("cache");
+    if (score) {
+      std::vector<int64_t> targets(prompt.begin() + 1, prompt.end());
+      targets.push_back(-1);
+      std::vector<bz_score_row> rows((size_t)S);
+      bz_score_config scfg; bz_score_total tot;
+      memset(&scfg, 0, sizeof scfg);
+      scfg.top_n = top_logprobs;
+      if ((is_ssm ? bz_score_ssm(m, tok, S, ssm, targets.data(), &scfg, rows.data(), &tot) : bz_score_kv(m, tok, S, kv, 0, targets.data(), &scfg, rows.data(), &tot)) != BZ_OK)
+        return fail("score");
+      for (int i = 0; i + 1 < S; i++) {
+        printf("%d %lld %.6f %d", i + 1, (long long)rows[i].target, (double)rows[i].logprob, rows[i].rank);
+        for (int j = 0; j < rows[i].n_top; j++) printf(" %u:%.6f", rows[i].top_ids[j], (double)rows[i].top_logprobs[j]);
+        printf("\n");
+      }
+      printf("total %.6f tokens %lld perplexity %.6f\n", tot.sum_logprob, (long long)tot.n_scored, tot.n_scored ? exp(-tot.sum_logprob / (double)tot.n_scored) : 0.0);
+    } else {
+      const int nvec = ecfg.pooling == BZ_POOL_NONE ? S : 1;
+      const int64_t oshp[2] = {nvec, cfg.hidden};
+      bz_tensor* out = nullptr;
+      if (bz_tensor_zeros(dev, BZ_F32, oshp, 2, &out) != BZ_OK) return fail("out");
+      if ((is_ssm ? bz_embed_ssm(m, tok, S, ssm, &ecfg, out) : bz_embed_kv(m, tok, S, kv, 0, &ecfg, out)) != BZ_OK) return fail("embed");
+      std::vector<float> v((size_t)nvec * cfg.hidden);
+      if (bz_tensor_to_host(out, v.data(), v.size() * 4) != BZ_OK) return fail("read");
+      for (int r = 0; r < nvec; r++) {
+        for (int j = 0; j < cfg.hidden; j++) printf(j ? ",%.9g" : "%.9g", (double)v[(size_t)r * cfg.hidden + j]);
+        printf("\n");
+      }
+      bz_tensor_free(out);
+    }
+    bz_tensor_free(tok);
+    if (kv) bz_kv_free(kv);
+    if (ssm) bz_ssm_state_free(ssm);
+    bz_model_free(m);
+    for (bz_lora* a : loras) bz_lora_free(a);
+    bz_device_close(dev);
+    return 0;
+  }
   std::vector<int64_t> out((size_t)(gc.max_tokens > 0 ? gc.max_tokens : 1));
   bz_gen_stats st;
   if (!draft_path.empty()) {
