@@ -333,6 +333,7 @@ SYMBOLS = {
     "bz_fp8_e4m3_spec": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bz_conv1d_step": (C.c_int, [P, C.c_int, P, P, P]),
     "bz_ssm_step": (C.c_int, [P, C.c_int, P, P, P]),
+    "bz_ssm_scan_rows": (C.c_int, [P, C.c_int, P, P, C.c_int, P, P, P]),
     "bz_ssm_state_read": (C.c_int, [P, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     "bz_moe_route": (C.c_int, [P, C.c_int, P, P, P, P]),
     "bz_moe_grouped_gemv": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int, P, P]),

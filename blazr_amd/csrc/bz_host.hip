@@ -2603,7 +2603,7 @@ static int check_ssm(bz_model* m, bz_ssm_state* st) {
 
 // Mamba2 batched prefill (prompts of >= BZ_PREFILL_MIN tokens, dense 16-bit in_proj / out_proj in the activation dtype): rows through the
 // MFMA GEMMs, conv as a map over (token, channel), the recurrence as an in-kernel scan per head (bz_prefill.hip).  Same rounding points as
-// mamba_step, token for token.
+// mamba_step, token for token, and the same exactly rounded sums between them (tests/test_gpu_mamba2_scan.py: the oracle's bits).
 static int mamba_prefill(bz_model* m, const long long* d_tok, int S, bz_ssm_state* state, const RowSink& sink, const bz_prompt_plan_t& plan) {
   BZ_TRACE("mamba_prefill: S=%d", S);
   const bz_model_config& c = m->cfg;
@@ -4238,6 +4238,59 @@ extern "C" int bz_ssm_step(bz_model* m, int layer, bz_ssm_state* state, const bz
   BZ_TRY(bzk_conv_shift(st, shf, a.act));
   BZ_HIP(hipStreamSynchronize(st));
   return BZ_OK;
+  BZ_API_END
+}
+
+// The prompt route's kernels between the two GEMMs of one layer (mamba_prefill: bzk_pf_conv, bzk_ssm_scan, bzk_pf_gnorm) on caller-provided in_proj rows, so that
+// conv, scan and gated norm can be compared with the oracle's token-by-token step without the MFMA GEMMs in between.  Scratch (vss, the 16-bit norm rows) is the call's own.
+extern "C" int bz_ssm_scan_rows(bz_model* m, int layer, bz_ssm_state* state, const bz_tensor* zx_rows, int S, bz_tensor* xbc_out, bz_tensor* y_out, bz_tensor* yn_out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || m->cfg.arch != BZ_ARCH_MAMBA2) BZ_FAIL(BZ_E_INVALID, "ssm_scan_rows: not a finalized Mamba2 model");
+  std::lock_guard<std::recursive_mutex> lk(m->mu);
+  BZ_TRY(check_ssm(m, state));
+  const bz_model_config& c = m->cfg;
+  if (layer < 0 || layer >= c.n_layers) BZ_FAIL(BZ_E_INVALID, "ssm_scan_rows: layer %d out of range", layer);
+  if (S < 1 || S > 65535) BZ_FAIL(BZ_E_INVALID, "ssm_scan_rows: S = %d rows (1 .. 65535: the conv map's grid has a row per token)", S);
+  const int DI = c.ssm_d_inner, NH = c.ssm_n_heads, HD = c.ssm_head_dim, NS = c.ssm_d_state, G = c.ssm_n_groups, KC = c.ssm_conv_kernel, act = c.act_dtype;
+  const int conv_dim = DI + 2 * G * NS, d_in = DI + conv_dim + NH, pieces = bzk_ssm_scan_pieces(HD);
+  if (!bzk_ssm_scan_ok(HD, NS, G, KC)) BZ_FAIL(BZ_E_UNSUPPORTED, "ssm_scan_rows: the scan does not take head_dim %d, d_state %d, n_groups %d, conv_kernel %d", HD, NS, G, KC);
+  if (!zx_rows || zx_rows->dtype != BZ_F32 || zx_rows->nbytes != (size_t)S * d_in * 4) BZ_FAIL(BZ_E_INVALID, "ssm_scan_rows: zx_rows must be F32 [%d, %d] ([z | x B C | dt] rows)", S, d_in);
+  if (!xbc_out || xbc_out->dtype != BZ_F32 || xbc_out->nbytes != (size_t)S * conv_dim * 4) BZ_FAIL(BZ_E_INVALID, "ssm_scan_rows: xbc_out must be F32 [%d, %d]", S, conv_dim);
+  if (!y_out || y_out->dtype != BZ_F32 || y_out->nbytes != (size_t)S * DI * 4) BZ_FAIL(BZ_E_INVALID, "ssm_scan_rows: y_out must be F32 [%d, %d]", S, DI);
+  if (yn_out && act == BZ_F32) BZ_FAIL(BZ_E_UNSUPPORTED, "ssm_scan_rows: the gated-norm rows are 16-bit (the prompt route never runs an f32 model): no yn_out");
+  if (yn_out && (yn_out->dtype != BZ_F32 || yn_out->nbytes != (size_t)S * DI * 4)) BZ_FAIL(BZ_E_INVALID, "ssm_scan_rows: yn_out must be F32 [%d, %d]", S, DI);
+  BZ_HIP(hipSetDevice(m->dev->id));
+  hipStream_t st = m->dev->stream;
+  const MambaLayerDev& L = m->mlayers[layer];
+  float* vss = nullptr; void* x16 = nullptr;
+  const size_t nyn = (size_t)S * DI;
+  std::vector<uint16_t> raw(yn_out ? nyn : 0);     // (host buffers first: nothing below throws with device memory held)
+  std::vector<float> out(yn_out ? nyn : 0);
+  BZ_HIP(hipMalloc((void**)&vss, (size_t)S * NH * pieces * 4));
+  if (yn_out && hipMalloc(&x16, nyn * 2) != hipSuccess) { hipFree(vss); BZ_FAIL(BZ_E_OOM, "ssm_scan_rows: hipMalloc failed"); }
+  const float* zx = (const float*)zx_rows->ptr;
+  int rc = bzk_pf_conv(st, zx, d_in, DI, conv_dim, KC, L.conv_w, L.conv_b, state->conv + (size_t)layer * conv_dim * (KC - 1), S, act, (float*)xbc_out->ptr);
+  if (rc == BZ_OK) {
+    BzSsmScan sc{};
+    sc.xbc = (const float*)xbc_out->ptr; sc.conv_dim = conv_dim; sc.zx = zx; sc.ld = d_in; sc.dt_off = DI + conv_dim; sc.dt_bias = L.dt_bias; sc.A_log = L.A_log; sc.D = L.D;
+    sc.state = (char*)state->ssm + (size_t)layer * NH * HD * NS * bz_dtype_size(state->dtype);
+    sc.n_heads = NH; sc.head_dim = HD; sc.d_state = NS; sc.n_groups = G; sc.d_inner = DI; sc.act = act; sc.S = S; sc.y = (float*)y_out->ptr; sc.vss = vss;
+    rc = bzk_ssm_scan(st, sc, state->dtype);
+  }
+  if (rc == BZ_OK && yn_out) rc = bzk_pf_gnorm(st, act, (const float*)y_out->ptr, vss, L.gnorm, S, DI, G, NH * pieces, c.rms_eps, act, x16);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == BZ_OK) { bz_set_error("ssm_scan_rows: the launches failed: %s", hipGetErrorString(hipGetLastError())); rc = BZ_E_HIP; }
+  if (rc == BZ_OK && yn_out) {     // the 16-bit rows, expanded on the host
+    if (hipMemcpy(raw.data(), x16, nyn * 2, hipMemcpyDeviceToHost) != hipSuccess) rc = BZ_E_HIP;
+    for (size_t i = 0; i < nyn; i++) {
+      if (act == BZ_BF16) { const uint32_t u = (uint32_t)raw[i] << 16; memcpy(&out[i], &u, 4); }
+      else out[i] = __half2float(__ushort_as_half(raw[i]));
+    }
+    if (rc == BZ_OK && hipMemcpy(yn_out->ptr, out.data(), nyn * 4, hipMemcpyHostToDevice) != hipSuccess) rc = BZ_E_HIP;
+    if (rc != BZ_OK) bz_set_error("ssm_scan_rows: copying the gated-norm rows failed");
+  }
+  hipFree(vss);
+  if (x16) hipFree(x16);
+  return rc;
   BZ_API_END
 }
 

@@ -1034,13 +1034,14 @@ __global__ void k_pf_conv(const float* __restrict__ zx, int ld, int x_off, int c
                           const float* __restrict__ cs, int S, int act, float* __restrict__ out) {
   const int ch = blockIdx.x * 256 + threadIdx.x, t = blockIdx.y;
   if (ch >= conv_dim) return;
-  float a = 0.f;
+  double ad = 0.0;     // the window's dot product exactly rounded (products exact in double, one rounding to f32), as the step kernel and the oracle have it
   for (int j = 0; j < kc - 1; j++) {
     const int tau = t - (kc - 1) + j;
     const float v = tau >= 0 ? zx[(size_t)tau * ld + x_off + ch] : cs[(size_t)ch * (kc - 1) + (tau + kc - 1)];
-    a += v * w[(size_t)ch * kc + j];
+    ad = fma((double)v, (double)w[(size_t)ch * kc + j], ad);
   }
-  a += zx[(size_t)t * ld + x_off + ch] * w[(size_t)ch * kc + kc - 1];
+  ad = fma((double)zx[(size_t)t * ld + x_off + ch], (double)w[(size_t)ch * kc + kc - 1], ad);
+  float a = (float)ad;
   a = pf_round(a + b[ch], act);
   out[(size_t)t * conv_dim + ch] = pf_round(pf_silu(a), act);
 }
@@ -1091,17 +1092,18 @@ template <int ACT> __device__ __forceinline__ float rnd(float x) {
 
 // The recurrence is sequential in t (the state is rounded at every token, as the decode step stores it), so the kernel is bound by the instructions one
 // CU issues per token.  What keeps that count low: rounding is compile-time (ACT); a head's rows are split over ceil(head_dim / 16) workgroups; B / C
-// come out of LDS as 16-byte reads; per token only the state update, the C dot and its 16-lane reduction run (dt * x comes staged from LDS) -- the
+// come out of LDS as 16-byte reads (as doubles: the sums are exactly rounded, see below); per token only the state update, the C dot and its 16-lane reduction run (dt * x comes staged from LDS) -- the
 // gate / SiLU / y epilogue runs once per CHUNK with lane q of a row serving token q (it used to run per token on one lane in 16); the next chunk's
 // rows are requested before the current chunk's arithmetic, and a chunk's stores are issued one chunk late, ahead of that request.
 // grid = (n_heads, ceil(head_dim / 16)); 256 threads = 16 rows (p) x 16 state parts (q); NQ = d_state / 16 state values per thread in registers;
 // tokens in chunks of 8.  vss rows are [S][n_heads][gridDim.y] (k_pf_gnorm adds the pieces)
 template <int SDT, int ACT, int NQ>
 __global__ __launch_bounds__(256) void k_ssm_scan(SsmScanArgs a) {
-  constexpr int TC = 8, PARTS = 16, NS = NQ * PARTS, NP = NQ == 8 ? 12 : NQ, NTH = 256, NWV = 4;   // NP: part stride in LDS (16-byte aligned for NQ >= 4)
+  constexpr int TC = 8, PARTS = 16, NS = NQ * PARTS, NP = NQ == 8 ? 10 : NQ == 4 ? 6 : NQ, NTH = 256, NWV = 4;   // NP: part stride in LDS, in doubles (16-byte aligned and bank-conflict free for NQ >= 4)
   constexpr int NBC = (TC * NS + NTH - 1) / NTH;     // B and C elements per thread per chunk
-  __shared__ __attribute__((aligned(16))) float sB[TC][PARTS * NP], sC[TC][PARTS * NP];
-  __shared__ float sdA[TC], sdtx[TC][16], sred[TC][NWV];
+  __shared__ __attribute__((aligned(16))) double sB[TC][PARTS * NP], sC[TC][PARTS * NP];     // staged as doubles: converted once per chunk, not once per row
+  __shared__ double sdA[TC], sdtx[TC][16];
+  __shared__ float sred[TC][NWV];
   const int hd = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int HD = a.head_dim;
   const int g = hd / (a.n_heads / a.n_groups);
@@ -1142,13 +1144,13 @@ __global__ __launch_bounds__(256) void k_ssm_scan(SsmScanArgs a) {
 #pragma unroll
     for (int k = 0; k < NBC; k++) {
       const int i = k * NTH + tid, tt = i / NS, n = i % NS;
-      if (i < TC * NS) { sB[tt][(n / NQ) * NP + n % NQ] = bv[k]; sC[tt][(n / NQ) * NP + n % NQ] = cv[k]; }
+      if (i < TC * NS) { sB[tt][(n / NQ) * NP + n % NQ] = (double)bv[k]; sC[tt][(n / NQ) * NP + n % NQ] = (double)cv[k]; }
     }
     const float xc = xn, zc = zn;
     {
       const float dt = rnd<ACT>(pf_softplus(rnd<ACT>(dtraw + dtb)));     // token tq
-      if (q < TC) sdtx[q][pl] = dt * xc;
-      if (tid < TC) sdA[tid] = bz_expf(dt * Aneg);
+      if (q < TC) sdtx[q][pl] = (double)__fmul_rn(dt, xc);
+      if (tid < TC) sdA[tid] = (double)bz_expf(dt * Aneg);
     }
     __syncthreads();
     flush();
@@ -1158,26 +1160,32 @@ __global__ __launch_bounds__(256) void k_ssm_scan(SsmScanArgs a) {
     for (int tt = 0; tt < TC; tt++) {
       accs[tt] = 0.f;
       if (tt < nt) {
-        const float dA = sdA[tt], dtx = sdtx[tt][pl];
-        float Bq[NQ], Cq[NQ];
-        if constexpr (NQ % 4 == 0) {
+        const double dAd = sdA[tt], dtxd = sdtx[tt][pl];
+        double Bq[NQ], Cq[NQ];
+        if constexpr (NQ % 2 == 0) {
 #pragma unroll
-          for (int n = 0; n < NQ; n += 4) {
-            const float4 b4 = *(const float4*)&sB[tt][q * NP + n], c4 = *(const float4*)&sC[tt][q * NP + n];
-            Bq[n] = b4.x; Bq[n + 1] = b4.y; Bq[n + 2] = b4.z; Bq[n + 3] = b4.w; Cq[n] = c4.x; Cq[n + 1] = c4.y; Cq[n + 2] = c4.z; Cq[n + 3] = c4.w;
+          for (int n = 0; n < NQ; n += 2) {
+            const double2 b2 = *(const double2*)&sB[tt][q * NP + n], c2 = *(const double2*)&sC[tt][q * NP + n];
+            Bq[n] = b2.x; Bq[n + 1] = b2.y; Cq[n] = c2.x; Cq[n + 1] = c2.y;
           }
         } else {
 #pragma unroll
           for (int n = 0; n < NQ; n++) { Bq[n] = sB[tt][q * NP + n]; Cq[n] = sC[tt][q * NP + n]; }
         }
-        float acc = 0.f;
+        // exactly rounded sums, as k_ssm_step and the oracle have them (products exact in double, one rounding to f32).  An f32 chain here rounds to the other
+        // 16-bit neighbour about once in 2^13 (f16) updates, the carried state keeps that interval while later tokens cancel the element, and small elements
+        // end many of their own intervals away from the step path's (tests/test_gpu_mamba2_scan.py measured up to 21)
+        double acc = 0.0;
 #pragma unroll
         for (int n = 0; n < NQ; n++) {
-          const float hn = rnd<ACT>(h[n] * dA + dtx * Bq[n]);
-          acc += hn * Cq[n];                   // (the step kernel multiplies the activation-rounded value and stores the state-dtype one)
+          float hs = (float)fma((double)h[n], dAd, dtxd * Bq[n]);
+          asm volatile("" : "+v"(hs));     // the f32 value materialised: double -> f32 -> bf16 must stay two roundings (the compiler folds them into one otherwise)
+          const float hn = rnd<ACT>(hs);
+          acc = fma((double)hn, Cq[n], acc);     // (the step kernel multiplies the activation-rounded value and stores the state-dtype one)
           h[n] = ACT == SDT ? hn : st_round<SDT>(hn);
         }
-        accs[tt] = grp_reduce<PARTS, OpAdd>(acc);
+        acc += dpp_get<DPP_XOR1>(acc); acc += dpp_get<DPP_XOR2>(acc); acc += dpp_get<DPP_HMIRROR>(acc); acc += dpp_get<DPP_MIRROR>(acc);     // the 16 parts of a row
+        accs[tt] = (float)acc;
       }
     }
     // epilogue, once per chunk: lane q < nt of row p finishes token t0 + q
@@ -1186,12 +1194,12 @@ __global__ __launch_bounds__(256) void k_ssm_scan(SsmScanArgs a) {
     for (int tt = 1; tt < TC; tt++) am = tq == tt ? accs[tt] : am;
     float y = 0.f;
     if (on && q < nt) {
-      const float y0 = rnd<ACT>(am + Dh * xc);
-      y = rnd<ACT>(y0 * rnd<ACT>(pf_silu(zc)));
+      const float y0 = rnd<ACT>(__fadd_rn(am, __fmul_rn(Dh, xc)));     // (no contraction: the product keeps its own f32 rounding, as in the step kernel)
+      y = rnd<ACT>(__fmul_rn(y0, rnd<ACT>(pf_silu(zc))));
     }
     yprev = y;
     // per-token sums of squares over this workgroup's rows: the wave's 4 rows by two lane exchanges, the 4 waves through LDS (fixed tree)
-    float sq = y * y;
+    float sq = __fmul_rn(y, y);
     sq += __shfl_xor(sq, 16, 64);
     sq += __shfl_xor(sq, 32, 64);
     if (lane < TC) sred[lane][wave] = sq;

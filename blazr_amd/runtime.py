@@ -702,6 +702,19 @@ class LoadedModel:
         L.check(L.lib().bz_ssm_step(self.h, layer, state.h, zt.h, out.h))
         return out.to_numpy()
 
+    def ssm_scan_rows(self, layer, state, zx_rows, norm=True):
+        """the prompt route's conv, scan and gated norm of Mamba2 layer `layer` on the in_proj rows zx_rows [S, d_in]; returns (xbc [S, conv_dim], gated y
+        [S, d_inner], yn [S, d_inner] or None when norm is False); conv window and SSM state advance by S tokens"""
+        c = self.mamba_config()
+        zx = np.ascontiguousarray(zx_rows, dtype=np.float32)
+        S = zx.shape[0]
+        zt = self.dev.tensor(zx)
+        xbc = self.dev.zeros((S, c["d_inner"] + 2 * c["n_groups"] * c["d_state"]), L.F32)
+        y = self.dev.zeros((S, c["d_inner"]), L.F32)
+        yn = self.dev.zeros((S, c["d_inner"]), L.F32) if norm else None
+        L.check(L.lib().bz_ssm_scan_rows(self.h, layer, state.h, zt.h, S, xbc.h, y.h, None if yn is None else yn.h))
+        return xbc.to_numpy(), y.to_numpy(), None if yn is None else yn.to_numpy()
+
     def moe_route(self, layer, hidden):
         """router of DeepSeek MoE layer `layer` on the residual-stream row (norm inside): (sel int32 [top_k + n_shared], w float32 [...], xn float32 [H])"""
         n = self.c.moe_top_k + self.c.moe_n_shared

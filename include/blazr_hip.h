@@ -874,6 +874,12 @@ int bz_conv1d_step(bz_model* m, int layer, bz_ssm_state* state, const bz_tensor*
  * y_out [d_inner] F32 (before the gated RMSNorm); `state` (conv window + SSM state [n_heads, head_dim, d_state]) advances by one token
  * (forward_with_ssm_state, engine/executor_generate.rs:137,148). */
 int bz_ssm_step(bz_model* m, int layer, bz_ssm_state* state, const bz_tensor* zx, bz_tensor* y_out);
+/* The kernels the batched Mamba2 prompt route runs between the two GEMMs of layer `layer` (conv over the rows, the in-kernel scan over the tokens, the gated
+ * RMSNorm), on S caller-provided in_proj rows: zx_rows F32 [S, 2 d_inner + 2 n_groups d_state + n_heads], each row [z | x B C | dt] already rounded to the
+ * activation dtype.  xbc_out F32 [S, d_inner + 2 n_groups d_state] (conv + SiLU), y_out F32 [S, d_inner] (the gated y), yn_out F32 [S, d_inner] (the norm's
+ * 16-bit rows, expanded; may be NULL; refused for an f32 model, whose prompts never take this route).  `state` advances by S tokens.  Any S >= 1: the
+ * 8-token minimum belongs to the route, not to the kernels.  BZ_E_UNSUPPORTED for a state shape the scan does not take. */
+int bz_ssm_scan_rows(bz_model* m, int layer, bz_ssm_state* state, const bz_tensor* zx_rows, int S, bz_tensor* xbc_out, bz_tensor* y_out, bz_tensor* yn_out);
 /* One layer of a LayeredSsmState copied to the host as F32 (which = 0: SSM state [n_heads * head_dim * d_state], 1: conv window [conv_dim * (k-1)]);
  * n = the expected element count.  Test / debugging aid for the two entry points above (the state layouts are docs/architecture.md:52-54). */
 int bz_ssm_state_read(const bz_ssm_state* state, int layer, int which, float* host, size_t n);

@@ -5,14 +5,18 @@ The recurrence lives in the absent boostr crate; the oracle restates the public 
 oracle/orc_mamba2.c).  Bars as in test_gpu_llama.py: relative L2 of the logits, greedy ids bit-exact on fair prefixes.
 """
 import ctypes as C
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 from blazr_amd import _lib as L
 from blazr_amd import runtime, synth
+from mamba2_carry_probe import carry, read_state as _read_state
 from oracle import orc_py
-from test_gpu_llama import _check_logits, _fair_prefix
+from test_gpu_llama import REL, TINY, _check_logits, _fair_prefix
 
 pytestmark = pytest.mark.gpu
 
@@ -189,3 +193,119 @@ def test_batched_prefill_crosses_the_row_chunk(device):
         _check_logits(lm.forward_with_ssm_state([tok], st).to_numpy(), lo, cfg["act_dtype"])
         tok = int(lo[0].argmax())
     orc_py.lib().orc_ssm_state_free(ost)
+
+
+# ---- the batched prompt path at its chunk edges, and the state it leaves ---------------------------------------------------------------------------
+def _orc_state(cfg, ost):
+    """the oracle's state as two float32 views: ssm [L, n_heads * head_dim * d_state], conv [L, conv_dim * (k - 1)]"""
+    conv_dim = cfg["d_inner"] + 2 * cfg["n_groups"] * cfg["d_state"]
+    n_ssm, n_win = cfg["n_heads"] * cfg["head_dim"] * cfg["d_state"], conv_dim * (cfg["conv_kernel"] - 1)
+    view = lambda p, n: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), (cfg["n_layers"], n))
+    return view(ost.contents.ssm, n_ssm), view(ost.contents.conv, n_win)
+
+
+_TINY = {}
+
+
+def _tiny(device):
+    if not _TINY:
+        model = synth.make_mamba2("tiny-mamba2")
+        _TINY["pair"] = (model, runtime.LoadedModel.from_synth(device, model), orc_py.OrcMamba2(model))
+    return _TINY["pair"]
+
+
+@pytest.mark.parametrize("r", [8, 18])
+def test_chunk_carry_is_an_identity(device, r, tmp_path):
+    """512 + r tokens in one call == a call of 512 and a call of r on the same state, bit for bit: both sides launch the same GEMMs on the same row counts (the
+    workspace chunk is 512 rows), so nothing but a defect in what is carried from chunk to chunk can differ.  (Other splits are not comparable exactly: the GEMM
+    chooses its K split from the row count.)  By default a prompt of up to 16 rows stays on the decode kernels (BZ_EXACT_PREFILL_MAX), so the call of 8 rows takes
+    the batched route -- what the long call's last chunk runs -- only with BZ_EXACT_PREFILL=0: that case runs in a process of its own (the switches are read once)."""
+    if r > 16:
+        model, lm, _ = _tiny(device)
+        d = carry(lm, model["config"]["vocab"], r)
+    else:
+        out = tmp_path / "carry.npz"
+        env = dict(os.environ, BZ_EXACT_PREFILL="0")
+        run = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "mamba2_carry_probe.py"), str(r), str(out)],
+                             env=env, capture_output=True, text=True, timeout=120)
+        assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-2000:])
+        d = np.load(out)
+    names = sorted(k[2:] for k in d.keys() if k.startswith("a_"))
+    assert len(names) == 1 + 2 * 3
+    for k in names:
+        assert np.array_equal(d["a_" + k], d["b_" + k]), k
+
+
+def _edge_reference(device):
+    """the oracle over one 520-token prompt, stopped at 512, 513 and 520 tokens: the last row's logits and a copy of the state at each stop (computed once)"""
+    if "edges" not in _TINY:
+        model, _, om = _tiny(device)
+        cfg = model["config"]
+        p = synth.prompt_tokens(520, cfg["vocab"], seed=91)
+        ost = om.new_state()
+        stops, lo = {}, 0
+        for S in (512, 513, 520):
+            logits = om.forward(p[lo:S], ost)
+            stops[S] = (logits, tuple(a.copy() for a in _orc_state(cfg, ost)))
+            lo = S
+        orc_py.lib().orc_ssm_state_free(ost)
+        _TINY["edges"] = (p, stops)
+    return _TINY["edges"]
+
+
+@pytest.mark.parametrize("S", [512, 513, 520])
+def test_batched_prefill_at_the_row_chunk_edges(device, S):
+    """exactly one workspace chunk, a final chunk of ONE row (in_proj GEMM, conv, scan, gated norm and out_proj with n = 1) and one of 8: the last row's logits against
+    the oracle, then four decode steps from the state the prompt left"""
+    model, lm, om = _tiny(device)
+    cfg = model["config"]
+    p, stops = _edge_reference(device)
+    want, (ssm, conv) = stops[S]
+    st, ost = runtime.LayeredSsmState(lm), om.new_state()
+    _check_logits(lm.forward_with_ssm_state(p[:S], st).to_numpy(), want, cfg["act_dtype"])
+    for dst, src in zip(_orc_state(cfg, ost), (ssm, conv)):
+        dst[...] = src
+    tok = int(want[-1].argmax())
+    for _ in range(4):
+        lo = om.forward([tok], ost)
+        _check_logits(lm.forward_with_ssm_state([tok], st).to_numpy(), lo, cfg["act_dtype"])
+        tok = int(lo[0].argmax())
+    orc_py.lib().orc_ssm_state_free(ost)
+
+
+def _interval(v, act):
+    """one rounding interval of the activation dtype at |v| (floor: the smallest normal)"""
+    e = np.floor(np.log2(np.maximum(np.abs(np.asarray(v, dtype=np.float64)), 1e-300)))
+    return np.exp2(np.maximum(e, -14.0) - 10.0) if act == "f16" else np.exp2(np.maximum(e, -126.0) - 7.0)
+
+
+@pytest.mark.parametrize("over", [dict(), dict(d_state=16), dict(conv_kernel=2), dict(n_groups=4, d_state=64), dict(act_dtype="f16"), dict(head_dim=32, n_heads=16)],
+                         ids=["base", "state16", "conv2", "groups4", "f16", "headdim32"])
+@pytest.mark.parametrize("S", [8, 21])
+def test_state_after_a_batched_prompt_matches_the_oracle(device, over, S):
+    """every layer's SSM state and conv window after a batched prompt, against the oracle's: per layer a relative L2 within the bar of the logits these states produce
+    (REL * TINY), and layer 0's window -- the rounded in_proj output and nothing else -- within one rounding interval, at most 1 % of its elements not the same bits.
+    (With the default switches the 8-token prompts stay on the decode kernels, token by token; the 21-token ones take the batched route.)  Measured: DESIGN 5."""
+    model = synth.make_mamba2("tiny-mamba2", **over)
+    cfg = model["config"]
+    act = cfg["act_dtype"]
+    lm, om = runtime.LoadedModel.from_synth(device, model), orc_py.OrcMamba2(model)
+    p = synth.prompt_tokens(S, cfg["vocab"], seed=23 + S)
+    st, ost = runtime.LayeredSsmState(lm), om.new_state()
+    lm.forward_with_ssm_state(p, st)
+    om.forward(p, ost)
+    want = [a.copy() for a in _orc_state(cfg, ost)]
+    orc_py.lib().orc_ssm_state_free(ost)
+    rel = lambda g, w: float(np.linalg.norm(g.astype(np.float64) - w) / max(np.linalg.norm(w.astype(np.float64)), 1e-30))
+    bad = []
+    for l, (ssm, win) in enumerate(_read_state(lm, st)):
+        e_ssm, e_win = rel(ssm, want[0][l]), rel(win, want[1][l])
+        print("S=%d layer %d: ssm rel L2 %.2e (%d of %d differ), window rel L2 %.2e (%d of %d differ)"
+              % (S, l, e_ssm, int((ssm != want[0][l]).sum()), ssm.size, e_win, int((win != want[1][l]).sum()), win.size))
+        if max(e_ssm, e_win) > REL[act] * TINY:
+            bad.append((l, e_ssm, e_win))
+        if l == 0:
+            dist = np.abs(win.astype(np.float64) - want[1][0]) / _interval(want[1][0], act)
+            print("S=%d layer 0 window: max %.3g intervals" % (S, float(dist.max())))
+            assert dist.max() <= 1.0 and (win != want[1][0]).mean() <= 0.01, (float(dist.max()), float((win != want[1][0]).mean()))
+    assert not bad, bad
