@@ -4138,6 +4138,19 @@ extern "C" int bz_quant_matmul(bz_model* m, const char* name, const bz_tensor* x
   const bool direct = L.kind == LK_ROWS || (L.kind == LK_F8 && L.sk <= 1);   // (an fp8 linear's split form goes through the accumulator like the int4 kinds)
   if (!direct) BZ_HIP(hipMalloc(&acc, (size_t)L.N * 8));
   int rc = BZ_OK;
+  // int4: the accumulator's unit per row.  The kernels' sums are exact up to one rounding per workgroup to the accumulator's grid; at the f32 grid (2^-32, +-2^31)
+  // that rounding is several f32 ulps of a result below 2^-8.  A row whose sums cannot leave the fine grid's range (2^-44, +-2^19) takes that one:
+  // |sum| <= K max|x| 16 max(scale), with a factor 2 to spare.
+  std::vector<float> xh; float smax = 0.f;
+  if (L.kind == LK_Q4G) {
+    const size_t ns = (size_t)L.N * (L.K / L.gs);
+    std::vector<__half> sh(ns);
+    xh.resize((size_t)S * L.K);
+    BZ_HIP(hipStreamSynchronize(st));
+    BZ_HIP(hipMemcpy(sh.data(), L.scales, ns * 2, hipMemcpyDeviceToHost));
+    BZ_HIP(hipMemcpy(xh.data(), x->ptr, xh.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < ns; i++) smax = std::max(smax, std::fabs(__half2float(sh[i])));
+  }
   for (int s = 0; s < S && rc == BZ_OK; s++) {
     Pro p{}; p.mode = PRO_PLAIN; p.src = VSrc{(const float*)x->ptr + (size_t)s * L.K, 0}; p.act = BZ_F32; p.perm = L.perm;
     GemvOut o{};
@@ -4145,8 +4158,19 @@ extern "C" int bz_quant_matmul(bz_model* m, const char* name, const bz_tensor* x
     else {
       rc = bzk_zero64(st, acc, L.N);
       o.acc = acc;
-      if (rc == BZ_OK) rc = bzk_gemv(st, L, p, o, BZ_F32);
-      if (rc == BZ_OK) rc = bzk_fix_to_f32(st, acc, L.N, BZ_F32, (float*)y->ptr + (size_t)s * L.N);
+      // an int4 linear's bias joins the sum after its rounding to f32, here where the accumulator is read back (f32 results have no room for bzk_fix_bias's in-place form)
+      LinearDev Ls = L;
+      const float* rb = nullptr;
+      int grid = BZ_F32;
+      if (L.kind == LK_Q4G) {
+        rb = L.bias; Ls.bias = nullptr;
+        float xm = 0.f;
+        for (int k = 0; k < L.K; k++) xm = std::max(xm, std::fabs(xh[(size_t)s * L.K + k]));
+        if ((double)L.K * xm * 16.0 * smax < 262144.0) grid = BZ_F16;   // (the plain prologue rounds nothing: `act` only selects the unit here)
+      }
+      p.act = grid;
+      if (rc == BZ_OK) rc = bzk_gemv(st, Ls, p, o, grid);
+      if (rc == BZ_OK) rc = bzk_fix_to_f32(st, acc, L.N, BZ_F32, (float*)y->ptr + (size_t)s * L.N, rb, grid);
     }
   }
   hipStreamSynchronize(st);

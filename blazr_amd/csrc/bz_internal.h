@@ -258,7 +258,8 @@ int bzk_argmax_partials(hipStream_t s, const float* v, long long n, float* pval,
 int bzk_embed(hipStream_t s, const void* table, int tdt, int gg, const long long* tok, int H, int act, float* h_out, const int* pos = nullptr,
               const float* cos_t = nullptr, const float* sin_t = nullptr, int half = 0, float* rope_cur = nullptr);   // rope_cur: stage [cos|sin] of *pos
 int bzk_rope_row(hipStream_t s, const int* pos, const float* cos_t, const float* sin_t, int half, float* rope_cur);
-int bzk_fix_to_f32(hipStream_t s, const long long* acc, int n, int act, float* out);
+int bzk_fix_to_f32(hipStream_t s, const long long* acc, int n, int act, float* out, const float* bias = nullptr, int grid = -1);   // bias: added in f32 to the rounded sum; grid >= 0: the accumulator's units are that dtype's
+int bzk_fix_bias(hipStream_t s, long long* acc, const float* bias, int n, int act);   // acc <- R(fix2f(acc) + bias) in place, behind the producer (no-op without a bias)
 int bzk_zero64(hipStream_t s, long long* p, int n);
 
 struct AttnArgs {

@@ -224,7 +224,7 @@ __device__ __forceinline__ void mlp_q4g_tail(const double* part, const float* __
 template <int FIX, int GPW, int TPW, int NW, int ACT>   // NW waves per block; GPW k-groups per wave (gate/up), TPW output tiles per wave (down)
 __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ Wgu, const __half* __restrict__ Sgu, const unsigned char* __restrict__ Zgu,
                                                  const float* __restrict__ bgu, const uint4* __restrict__ Wd, const __half* __restrict__ Sd,
-                                                 const unsigned char* __restrict__ Zd, const float* __restrict__ bd, int H, int I, Pro pro,
+                                                 const unsigned char* __restrict__ Zd, int H, int I, Pro pro,
                                                  long long* acc, long long* zero_buf, int zero_n) {
   static_assert(GPW == 2, "a wave owns two 128-k groups of gate / up");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -368,7 +368,6 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
     double y = 0.0;
     q4g_consume_n<2>(D[q], 0, 0, apl, apar, sd[q], zd[q], y);
     const int n = (tbeg + q) * 64 + lane;
-    if (bd != nullptr && sl == 0) y += (double)bd[n];
     atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, ACT));
     __builtin_amdgcn_sched_barrier(0);   // tile q's atomic is issued before tile q + 1 is waited for
   }
@@ -388,17 +387,17 @@ int bzk_mlp_q4g(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, 
   const double bytes = (double)gu.algo_bytes + (double)dn.algo_bytes;
 #define LAUNCH_MLP(FIX, GP, TP, W_) BZ_LAUNCH("mlp_q4g<norm+gate/up+silu+down>", bytes, (k_mlp_q4g<FIX, GP, TP, W_, BZ_F16>), dim3(I / 64), dim3(W_ * 64), smem, s, \
     (const uint4*)gu.w, (const __half*)gu.scales, (const unsigned char*)gu.zeros, gu.bias, (const uint4*)dn.w, (const __half*)dn.scales,            \
-    (const unsigned char*)dn.zeros, dn.bias, H, I, pro, acc, zero_buf, zero_n)
+    (const unsigned char*)dn.zeros, H, I, pro, acc, zero_buf, zero_n)
   if (H == 4096) { if (pro.src.fix) LAUNCH_MLP(1, 2, 4, 16); else LAUNCH_MLP(0, 2, 4, 16); }
   else { if (pro.src.fix) LAUNCH_MLP(1, 2, 4, 8); else LAUNCH_MLP(0, 2, 4, 8); }
 #undef LAUNCH_MLP
   BZ_HIP(hipGetLastError());
-  return BZ_OK;
+  return bzk_fix_bias(s, acc, dn.bias, H, pro.act);   // down_proj's bias: behind the complete sum
 }
 
 template <int MODE, int FIX, int MAXJ, int NPF>
 __global__ __launch_bounds__(256) void k_gemv_q4g(const uint4* __restrict__ W, const __half* __restrict__ S,
-                                                  const unsigned char* __restrict__ Z, const float* __restrict__ bias, int N, int K,
+                                                  const unsigned char* __restrict__ Z, int N, int K,
                                                   int GW, int nst, Pro pro, long long* acc, long long* zero_buf, int zero_n) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int KR = GW * 128;
@@ -477,8 +476,7 @@ __global__ __launch_bounds__(256) void k_gemv_q4g(const uint4* __restrict__ W, c
     }
   }
   const int n = nt * 64 + lane;
-  if (bias != nullptr && ks == 0) y += (double)bias[n];
-  atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, pro.act));
+  atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, pro.act));   // the bare sum: a bias is added behind the launch (bzk_fix_bias)
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -497,7 +495,7 @@ __global__ __launch_bounds__(256) void k_gemv_q4g(const uint4* __restrict__ W, c
 // everything else (the prologue's dependent loads, norm, planes: done at ~2.8 us) hides under it.
 template <int FIX, int NJ, int ACT>     // NJ = H / 2048
 __global__ __launch_bounds__(768) void k_gemv_q4g_slim(const uint4* __restrict__ W, const __half* __restrict__ S, const unsigned char* __restrict__ Z,
-                                                      const float* __restrict__ bias, int N, int H, Pro pro, long long* acc, long long* zero_buf, int zero_n) {
+                                                      int N, int H, Pro pro, long long* acc, long long* zero_buf, int zero_n) {
   __shared__ uint4 xpl[8 * XQ_NP];
   __shared__ int4 gpar[4];
   __shared__ double red[4];
@@ -508,7 +506,7 @@ __global__ __launch_bounds__(768) void k_gemv_q4g_slim(const uint4* __restrict__
   const int NKS = H >> 8, G = H >> 7;
   const int ksl = blockIdx.x % NKS, tg = blockIdx.x / NKS;
   asm volatile("" :: "s"(zero_buf), "s"(zero_n), "s"(acc), "s"(pro.h_in), "s"(pro.src.p), "s"(pro.norm_w), "s"(pro.h_out), "s"(pro.H),
-               "s"(H), "s"(N), "s"(W), "s"(S), "s"(Z), "s"(bias));   // one scalar-load batch for all arguments
+               "s"(H), "s"(N), "s"(W), "s"(S), "s"(Z));   // one scalar-load batch for all arguments
   if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
   if (prolog) {
     // (1p) the row: octet j * 256 + pt of thread pt
@@ -607,7 +605,6 @@ __global__ __launch_bounds__(768) void k_gemv_q4g_slim(const uint4* __restrict__
       else q4g_consume_at<4, 4>(Q, 4, 2, xpl, gpar, sq[1], zq[1], y);
     }
     const int n = tq * 64 + lane;
-    if (bias != nullptr && ksl == 0) y += (double)bias[n];
     atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, ACT));
   }
 }
@@ -622,7 +619,7 @@ __global__ __launch_bounds__(768) void k_gemv_q4g_slim(const uint4* __restrict__
 // ---------------------------------------------------------------------------------------------------------
 template <int XDT>
 __global__ __launch_bounds__(512) void k_gemm_q4g_rows(const uint4* __restrict__ W, const __half* __restrict__ S, const unsigned char* __restrict__ Z,
-                                                      const float* __restrict__ bias, int N, int K, const unsigned short* __restrict__ X, int rows,
+                                                      int N, int K, const unsigned short* __restrict__ X, int rows,
                                                       long long* __restrict__ acc) {
   __shared__ __attribute__((aligned(16))) float xs[8 * 256];
   __shared__ uint4 xpl[8 * 8 * XQ_NP];
@@ -662,11 +659,10 @@ __global__ __launch_bounds__(512) void k_gemm_q4g_rows(const uint4* __restrict__
   __syncthreads();
   if (!q_on) return;
   const int n = tq * 64 + lane;
-  const double bv = (bias != nullptr && ksl == 0) ? (double)bias[n] : 0.0;
 #pragma unroll
   for (int r = 0; r < 8; r++) {
     if (r < rows) {
-      double y = bv;
+      double y = 0.0;
       q4g_consume(Q[0], r * 2, xpl, gpar, sq[0], zq[0], y);
       q4g_consume(Q[1], r * 2 + 1, xpl, gpar, sq[1], zq[1], y);
       atomicAdd((unsigned long long*)(acc + (size_t)r * N + n), (unsigned long long)d2fix(y, XDT));
@@ -674,9 +670,13 @@ __global__ __launch_bounds__(512) void k_gemm_q4g_rows(const uint4* __restrict__
   }
 }
 
-// out[i] = R(fix2f(acc[i])), acc[i] = 0  (the accumulator is ready for the next GEMM)
-__global__ void k_fix_rows_finish(long long* acc, size_t n, int act, float* out) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) { out[i] = round_act(fix2f(acc[i], act), act); acc[i] = 0; }
+// out[i] = R(fix2f(acc[i]) + bias[i % N]), acc[i] = 0  (the accumulator is ready for the next GEMM): the sum rounded to f32 once, then the bias in f32 -- the oracle's order
+__global__ void k_fix_rows_finish(long long* acc, size_t n, int act, float* out, const float* __restrict__ bias, int N) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    float v = fix2f(acc[i], act);
+    if (bias) v = __fadd_rn(v, bias[i % (size_t)N]);
+    out[i] = round_act(v, act); acc[i] = 0;
+  }
 }
 
 bool bzk_gemm_q4g_rows_ok(const LinearDev& L) { return L.kind == LK_Q4G && !L.perm && L.K % 256 == 0 && L.N % 64 == 0; }
@@ -690,10 +690,11 @@ int bzk_gemm_q4g_rows(hipStream_t s, const LinearDev& L, int xdt, const void* x1
     const unsigned short* xp = (const unsigned short*)x16 + (size_t)r0 * L.K;
     const double bytes = (double)L.algo_bytes;
     if (xdt == BZ_F16) BZ_LAUNCH("gemm_q4g_rows", bytes, k_gemm_q4g_rows<BZ_F16>, dim3(nks * ntg), dim3(512), 0, s, (const uint4*)L.w, (const __half*)L.scales,
-                                 (const unsigned char*)L.zeros, L.bias, L.N, L.K, xp, nr, acc);
+                                 (const unsigned char*)L.zeros, L.N, L.K, xp, nr, acc);
     else BZ_LAUNCH("gemm_q4g_rows", bytes, k_gemm_q4g_rows<BZ_BF16>, dim3(nks * ntg), dim3(512), 0, s, (const uint4*)L.w, (const __half*)L.scales,
-                   (const unsigned char*)L.zeros, L.bias, L.N, L.K, xp, nr, acc);
-    hipLaunchKernelGGL(k_fix_rows_finish, dim3(std::min<size_t>(1024, ((size_t)nr * L.N + 255) / 256)), dim3(256), 0, s, acc, (size_t)nr * L.N, act, y + (size_t)r0 * L.N);
+                   (const unsigned char*)L.zeros, L.N, L.K, xp, nr, acc);
+    hipLaunchKernelGGL(k_fix_rows_finish, dim3(std::min<size_t>(1024, ((size_t)nr * L.N + 255) / 256)), dim3(256), 0, s, acc, (size_t)nr * L.N, act, y + (size_t)r0 * L.N,
+                       (const float*)L.bias, L.N);
   }
   BZ_HIP(hipGetLastError());
   return BZ_OK;
@@ -2573,13 +2574,13 @@ int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& o
     if (!out.acc) BZ_FAIL(BZ_E_INVALID, "int4 gemv needs a fixed-point accumulator");
     const int nks = L.K / 256, ntg = (L.N / 64 + 7) / 8;
 #define LAUNCH_SLIM(FIX, NJ) BZ_LAUNCH("gemv_q4g<norm>", L.algo_bytes, (k_gemv_q4g_slim<FIX, NJ, BZ_F16>), dim3(nks * ntg), dim3(768), 0, s, (const uint4*)L.w, \
-    (const __half*)L.scales, (const unsigned char*)L.zeros, L.bias, L.N, L.K, pro, out.acc, out.zero_buf, out.zero_n)
+    (const __half*)L.scales, (const unsigned char*)L.zeros, L.N, L.K, pro, out.acc, out.zero_buf, out.zero_n)
 #define LAUNCH_SLIM_NJ(FIX) do { if (L.K == 2048) LAUNCH_SLIM(FIX, 1); else if (L.K == 4096) LAUNCH_SLIM(FIX, 2); else LAUNCH_SLIM(FIX, 4); } while (0)
     if (pro.src.fix) LAUNCH_SLIM_NJ(1); else LAUNCH_SLIM_NJ(0);
 #undef LAUNCH_SLIM_NJ
 #undef LAUNCH_SLIM
     BZ_HIP(hipGetLastError());
-    return BZ_OK;
+    return bzk_fix_bias(s, out.acc, L.bias, L.N, act);
   }
   if (L.kind == LK_Q4G) {
     if (!out.acc) BZ_FAIL(BZ_E_INVALID, "q4g gemv needs a fixed-point accumulator");
@@ -2591,7 +2592,7 @@ int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& o
     if (GW > 16) BZ_FAIL(BZ_E_INVALID, "q4g gemv: %d groups per workgroup (max 16)", GW);
 #define LAUNCH_Q4G(MODE, FIX, MJ, NPF) BZ_LAUNCH(MODE == PRO_NORM ? "gemv_q4g<norm>" : (MODE == PRO_SILU ? "gemv_q4g<silu>" : "gemv_q4g<plain>"), \
     L.algo_bytes, (k_gemv_q4g<MODE, FIX, MJ, NPF>), dim3(grid), dim3(256), smem, s, (const uint4*)L.w,                      \
-    (const __half*)L.scales, (const unsigned char*)L.zeros, L.bias, L.N, L.K, GW, nst, pro, out.acc, out.zero_buf, out.zero_n)
+    (const __half*)L.scales, (const unsigned char*)L.zeros, L.N, L.K, GW, nst, pro, out.acc, out.zero_buf, out.zero_n)
 #define LAUNCH_Q4G_N(MODE, FIX, MJ) do { if (GW == 1) LAUNCH_Q4G(MODE, FIX, MJ, 1); else if (L.npf >= 4 && GW >= 4) LAUNCH_Q4G(MODE, FIX, MJ, 4); \
                                           else LAUNCH_Q4G(MODE, FIX, MJ, 2); } while (0)
 #define LAUNCH_Q4G_F(MODE, MJ) do { if (pro.src.fix) LAUNCH_Q4G_N(MODE, 1, MJ); else LAUNCH_Q4G_N(MODE, 0, MJ); } while (0)
@@ -2606,7 +2607,7 @@ int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& o
 #undef LAUNCH_Q4G_F
 #undef LAUNCH_Q4G
     BZ_HIP(hipGetLastError());
-    return BZ_OK;
+    return bzk_fix_bias(s, out.acc, L.bias, L.N, act);
   }
   if (L.kind == LK_ROWS && bzk_rows2_ok(L, pro, out)) {
     const long long U = (long long)((L.N + 3) / 4) * ((L.K + 511) / 512);
@@ -2867,11 +2868,34 @@ int bzk_rope_row(hipStream_t s, const int* pos, const float* cos_t, const float*
   return BZ_OK;
 }
 
-__global__ void k_fix_to_f32(const long long* acc, int n, int act, float* out) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = round_act(fix2f(acc[i], act), act);
+// out[i] = R(fix2f(acc[i]) + bias[i]): the sum rounded to f32 once, then the bias in f32 (the oracle's order); bias == nullptr: none
+// (grid: the activation dtype whose fixed-point unit the accumulator was written in, where that is not `act`'s)
+__global__ void k_fix_to_f32(const long long* acc, const float* __restrict__ bias, int n, int grid, int act, float* out) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    float v = fix2f(acc[i], grid);
+    if (bias) v = __fadd_rn(v, bias[i]);
+    out[i] = round_act(v, act);
+  }
 }
-int bzk_fix_to_f32(hipStream_t s, const long long* acc, int n, int act, float* out) {
-  hipLaunchKernelGGL(k_fix_to_f32, dim3((n + 255) / 256), dim3(256), 0, s, acc, n, act, out);
+int bzk_fix_to_f32(hipStream_t s, const long long* acc, int n, int act, float* out, const float* bias, int grid) {
+  hipLaunchKernelGGL(k_fix_to_f32, dim3((n + 255) / 256), dim3(256), 0, s, acc, bias, n, grid < 0 ? act : grid, act, out);
+  BZ_HIP(hipGetLastError());
+  return BZ_OK;
+}
+// The bias of a linear whose sum lives in a fixed-point accumulator.  The oracle adds a bias AFTER the sum's one rounding to f32, y = R(RN32(sum) + bias), so it
+// cannot go into the exact sum (RN32(sum + bias) is another number wherever RN32(sum)'s own error decides a 16-bit rounding).  Every reader of an accumulator
+// computes R(fix2f(acc)); this pass, launched behind the producer, replaces the complete sum by the finished activation y on the same grid, which the readers
+// then reproduce: R(fix2f(d2fix(y))) == y wherever y is a multiple of the grid unit -- every f16 value (multiples of 2^-24 on a 2^-44 grid), bf16 values from
+// 2^-33 up (2^-40 grid; below, off by less than one grid unit).  f32 activations have no rounding to hide the grid behind: their one caller (bz_quant_matmul)
+// adds the bias in bzk_fix_to_f32 instead.  A model without biases never launches this.
+__global__ void k_fix_bias(long long* acc, const float* __restrict__ bias, int n, int act) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    acc[i] = d2fix((double)round_act(__fadd_rn(fix2f(acc[i], act), bias[i]), act), act);
+}
+int bzk_fix_bias(hipStream_t s, long long* acc, const float* bias, int n, int act) {
+  if (!bias) return BZ_OK;
+  if (act == BZ_F32) BZ_FAIL(BZ_E_UNSUPPORTED, "a biased linear into a fixed-point accumulator needs 16-bit activations (f32: add the bias where the sum is read back)");
+  BZ_LAUNCH("fix_bias<f32 after the sum>", (double)n * 4, k_fix_bias, dim3((n + 255) / 256), dim3(256), 0, s, acc, bias, n, act);
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
@@ -3096,7 +3120,7 @@ __global__ __launch_bounds__(256) void k_attn_decode(AttnArgs a) {
 // ---------------------------------------------------------------------------------------------------------
 template <int KVDT, int FUSE, int TPW, int NW, int PAGED, int HD = 128, int WIN = 0>   // WIN: sliding window (see below); NW waves per block: each owns 256/NW positions of a chunk; HD = 128 or 64 (64: not fused)
 __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __restrict__ W, const __half* __restrict__ S,
-                                               const unsigned char* __restrict__ Z, const float* __restrict__ bias, int CS, long long* acc) {
+                                               const unsigned char* __restrict__ Z, int CS, long long* acc) {
   // Mapping: a chunk is 256 positions in row groups of RPL = 512 / HD whole rows (one wave-wide 16-byte load: 1 KiB contiguous in the contiguous cache; 4 rows of
   // 128 elements, 8 rows of 64), dealt ROUND-ROBIN to the waves: load i of wave w is row group i NW + w, lane l holds piece (l % NPC) = elements 8 piece .. +7 of
   // row RPL (i NW + w) + l / NPC (NPC = HD / 8 pieces per row).  A context of c positions is ceil(c / RPL) groups spread over all NW waves -- ceil(c / (RPL NW))
@@ -3118,7 +3142,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
   constexpr int half = HD / 2, NPC = HD / 8, RPL = 64 / NPC, PW = 256 / NW, NL = PW / RPL, OW = NW > 8 ? 8 : NW, NTH = NW * 64;   // OW waves carry o_proj tiles
   asm volatile("" :: "s"(a.zero_buf), "s"(a.zero_n), "s"(a.kv.k), "s"(a.kv.v), "s"(a.kv.cap), "s"(a.kv.layer_stride), "s"(a.layer), "s"(a.act),
                "s"(a.interleaved), "s"(a.rope_cur), "s"(a.qkv.p), "s"(a.qkv.fix), "s"(a.nq), "s"(a.nkv), "s"(a.q_only), "s"(a.pos), "s"(W), "s"(S),
-               "s"(Z), "s"(bias), "s"(CS), "s"(acc), "s"(a.out), "s"(a.kv.bs), "s"(a.kv.n_kv));   // one scalar-load batch for all arguments
+               "s"(Z), "s"(CS), "s"(acc), "s"(a.out), "s"(a.kv.bs), "s"(a.kv.n_kv));   // one scalar-load batch for all arguments
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned* q2 = (unsigned*)smem;             // [64] packed q pairs
   unsigned* k2 = q2 + 64;                     // [64] packed new key
@@ -3365,10 +3389,7 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
       for (int e = 0; e < 8; e++) d += (double)__fmul_rn(w8[e], of8[e]);
       d = grp_sum_d<NPC>(d);
       const int n = nd0 + t * RPL + rsub;
-      if (piece == 0) {
-        if (bias != nullptr && hq == 0) d += (double)bias[n];
-        atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(d, a.act));
-      }
+      if (piece == 0) atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(d, a.act));
     }
     return;
   }
@@ -3390,7 +3411,6 @@ __global__ __launch_bounds__(NW * 64) void k_attn2(AttnArgs a, const uint4* __re
     double y = 0.0;
     q4g_consume(Wb[t], 0, xpl, gpar, sc[t], zp[t], y);
     const int n = (t0 + t) * 64 + lane;
-    if (bias != nullptr && hq == 0) y += (double)bias[n];
     if (wave < OW) atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, a.act));
   }
 }
@@ -3650,7 +3670,7 @@ int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long lo
     const int DL = attn_dense_oproj_loads(a, L);
     if (DL <= 0) BZ_FAIL(BZ_E_INVALID, "attn+o_proj fusion (dense) does not apply to this shape");
 #define LAUNCH_AD_(DT, T, PG, HDV, WN) BZ_LAUNCH("attn+o_proj<dense>", L.algo_bytes, (k_attn2<DT, 2, T, 8, PG, HDV, WN>), dim3(a.nq * 8), dim3(512), attn2_smem(8), s, a, \
-    (const uint4*)L.w, (const __half*)nullptr, (const unsigned char*)nullptr, L.bias, 8, acc)
+    (const uint4*)L.w, (const __half*)nullptr, (const unsigned char*)nullptr, 8, acc)
 #define LAUNCH_AD(DT, T, PG, HDV) do { if (a.window > 0) LAUNCH_AD_(DT, T, PG, HDV, 1); else LAUNCH_AD_(DT, T, PG, HDV, 0); } while (0)
 #define LAUNCH_AD_P(DT, T, HDV) do { if (a.kv.paged) LAUNCH_AD(DT, T, 1, HDV); else LAUNCH_AD(DT, T, 0, HDV); } while (0)
 #define LAUNCH_AD_T(DT, HDV) do { if (DL == 1) LAUNCH_AD_P(DT, 1, HDV); else if (DL == 2) LAUNCH_AD_P(DT, 2, HDV); else LAUNCH_AD_P(DT, 4, HDV); } while (0)
@@ -3662,14 +3682,14 @@ int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long lo
 #undef LAUNCH_AD
 #undef LAUNCH_AD_
     BZ_HIP(hipGetLastError());
-    return BZ_OK;
+    return bzk_fix_bias(s, acc, L.bias, L.N, a.act);
   }
   int NW;
   const int CS = attn_oproj_plan(a, L, NW);
   if (CS <= 0) BZ_FAIL(BZ_E_INVALID, "attn+o_proj fusion does not apply to this shape");
   const int TPW = (L.N / 64) / (CS * (NW > 8 ? 8 : NW));
 #define LAUNCH_AO_(DT, T, W_, PG, WN) BZ_LAUNCH("attn+o_proj", L.algo_bytes, (k_attn2<DT, 1, T, W_, PG, 128, WN>), dim3(a.nq * CS), dim3(W_ * 64), attn2_smem(W_), s, a, \
-    (const uint4*)L.w, (const __half*)L.scales, (const unsigned char*)L.zeros, L.bias, CS, acc)
+    (const uint4*)L.w, (const __half*)L.scales, (const unsigned char*)L.zeros, CS, acc)
 #define LAUNCH_AO(DT, T, W_, PG) do { if (a.window > 0) LAUNCH_AO_(DT, T, W_, PG, 1); else LAUNCH_AO_(DT, T, W_, PG, 0); } while (0)
 #define LAUNCH_AO_W(DT, T, PG) do { if (NW == 8) LAUNCH_AO(DT, T, 8, PG); else LAUNCH_AO(DT, T, 4, PG); } while (0)
 #define LAUNCH_AO_P(DT, T) do { if (a.kv.paged) LAUNCH_AO_W(DT, T, 1); else LAUNCH_AO_W(DT, T, 0); } while (0)
@@ -3683,7 +3703,7 @@ int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long lo
 #undef LAUNCH_AO
 #undef LAUNCH_AO_
   BZ_HIP(hipGetLastError());
-  return BZ_OK;
+  return bzk_fix_bias(s, acc, L.bias, L.N, a.act);   // o_proj's bias: behind the complete sum over the heads
 }
 
 
@@ -3715,8 +3735,10 @@ __global__ __launch_bounds__(REP == 8 ? 512 : 256) void k_attn_split(AttnArgs a,
   constexpr int HD = 128, half = 64, NW = REP == 8 ? 8 : 4, NTH = NW * 64, PW = 128 / NW, NL = PW / 4;
   __shared__ __attribute__((aligned(16))) unsigned q2[REP][64];
   __shared__ __attribute__((aligned(16))) unsigned k2[64], v2[64];
-  __shared__ float wred[REP][NW], lred[REP][NW];
-  __shared__ __attribute__((aligned(16))) float pout[NW][REP][128];
+  constexpr int HB = REP < 4 ? REP : 4;     // heads per P.V pass: the waves' double partials of 4 heads are 16 / 32 KiB of LDS
+  __shared__ float wred[REP][NW];
+  __shared__ double lred[HB][NW];
+  __shared__ __attribute__((aligned(16))) double pout[NW][HB][128];
   asm volatile("" :: "s"(a.kv.k), "s"(a.kv.v), "s"(a.kv.cap), "s"(a.kv.layer_stride), "s"(a.layer), "s"(a.act), "s"(a.interleaved), "s"(a.rope_cur),
                "s"(a.qkv.p), "s"(a.qkv.fix), "s"(a.nq), "s"(a.nkv), "s"(a.pos), "s"(nsplit), "s"(ws), "s"(a.kv.bs), "s"(a.kv.n_kv),
                "s"(a.zero_buf), "s"(a.zero_n));
@@ -3780,9 +3802,13 @@ __global__ __launch_bounds__(REP == 8 ? 512 : 256) void k_attn_split(AttnArgs a,
   uint4 qq[REP];
 #pragma unroll
   for (int h = 0; h < REP; h++) qq[h] = ((const uint4*)q2[h])[piece];
-  float Mrun[REP], Lrun[REP], Orun[REP];    // threads < 128 own output dim tid of every head
+  // Inside a slice the sums are the oracle's (orc_attn_decode), as in k_attn2: score = f32(sum q k) * scale with the sum in double over exact products,
+  // p = exp(score - slice max), sum p and sum p v in double, each rounded to f32 once where the partial is written.  A context that one slice covers
+  // (up to 128 positions) therefore leaves the merge nothing to rescale and has the oracle's bits; across slices the merge still rescales f32 partials.
+  float Mrun[REP];                          // threads < 128 own output dim tid of every head
+  double Lrun[REP], Orun[REP];
 #pragma unroll
-  for (int h = 0; h < REP; h++) { Mrun[h] = -INFINITY; Lrun[h] = 0.f; Orun[h] = 0.f; }
+  for (int h = 0; h < REP; h++) { Mrun[h] = -INFINITY; Lrun[h] = 0.0; Orun[h] = 0.0; }
   for (int c0 = p0; c0 < p1; c0 += 128) {
     if (c0 > p0) __syncthreads();           // the previous chunk's pout / wred / lred reads are done
     const bool won = c0 + wave * PW < p1;   // wave-uniform
@@ -3803,12 +3829,17 @@ __global__ __launch_bounds__(REP == 8 ? 512 : 256) void k_attn_split(AttnArgs a,
         const int p = c0 + wave * PW + 4 * r + rsub;
         uint4 kk = kr[r];
         if (p == pos) { kk = ((const uint4*)k2)[piece]; vr[r] = ((const uint4*)v2)[piece]; }
+        float kf[8];
+        unpack2<KVDT>(kk.x, kf[0], kf[1]); unpack2<KVDT>(kk.y, kf[2], kf[3]); unpack2<KVDT>(kk.z, kf[4], kf[5]); unpack2<KVDT>(kk.w, kf[6], kf[7]);
 #pragma unroll
         for (int h = 0; h < REP; h++) {
-          float d = dot2acc<KVDT>(kk.x, qq[h].x, 0.f);
-          d = dot2acc<KVDT>(kk.y, qq[h].y, d); d = dot2acc<KVDT>(kk.z, qq[h].z, d); d = dot2acc<KVDT>(kk.w, qq[h].w, d);
-          d = grp_reduce<16, OpAdd>(d);
-          sc_[h][r] = (p < p1) ? d * scale : -INFINITY;
+          float qf[8];
+          unpack2<KVDT>(qq[h].x, qf[0], qf[1]); unpack2<KVDT>(qq[h].y, qf[2], qf[3]); unpack2<KVDT>(qq[h].z, qf[4], qf[5]); unpack2<KVDT>(qq[h].w, qf[6], qf[7]);
+          double d = 0.0;
+#pragma unroll
+          for (int e = 0; e < 8; e++) d = fma((double)kf[e], (double)qf[e], d);
+          d = grp_sum_d<16>(d);
+          sc_[h][r] = (p < p1) ? (float)d * scale : -INFINITY;
           mloc[h] = fmaxf(mloc[h], sc_[h][r]);
         }
       }
@@ -3827,63 +3858,60 @@ __global__ __launch_bounds__(REP == 8 ? 512 : 256) void k_attn_split(AttnArgs a,
 #pragma unroll
       for (int w = 1; w < NW; w++) Mc[h] = fmaxf(Mc[h], wred[h][w]);
     }
-    if (won) {
-      float accv[REP][8], lsum[REP];
 #pragma unroll
-      for (int h = 0; h < REP; h++) {
-        lsum[h] = 0.f;
+    for (int hb = 0; hb < REP; hb += HB) {
+      if (hb > 0) __syncthreads();          // the previous pass's pout / lred reads are done
+      if (won) {
 #pragma unroll
-        for (int q = 0; q < 8; q++) accv[h][q] = 0.f;
-      }
+        for (int hh = 0; hh < HB; hh++) {
+          const int h = hb + hh;
+          double lsum = 0.0, accv[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-      for (int r = 0; r < NL; r++) {
-        float v[8];
-        unpack2<KVDT>(vr[r].x, v[0], v[1]); unpack2<KVDT>(vr[r].y, v[2], v[3]);
-        unpack2<KVDT>(vr[r].z, v[4], v[5]); unpack2<KVDT>(vr[r].w, v[6], v[7]);
+          for (int r = 0; r < NL; r++) {
+            float v[8];
+            unpack2<KVDT>(vr[r].x, v[0], v[1]); unpack2<KVDT>(vr[r].y, v[2], v[3]);
+            unpack2<KVDT>(vr[r].z, v[4], v[5]); unpack2<KVDT>(vr[r].w, v[6], v[7]);
+            const double ed = (double)((sc_[h][r] == -INFINITY) ? 0.f : bz_expf(sc_[h][r] - Mc[h]));
+            lsum += ed;
 #pragma unroll
-        for (int h = 0; h < REP; h++) {
-          const float e = (sc_[h][r] == -INFINITY) ? 0.f : bz_expf(sc_[h][r] - Mc[h]);
-          lsum[h] += e;
+            for (int q = 0; q < 8; q++) accv[q] = fma(ed, (double)v[q], accv[q]);
+          }
+          lsum = xrow32_d(xrow16_d(lsum));
 #pragma unroll
-          for (int q = 0; q < 8; q++) accv[h][q] = fmaf(e, v[q], accv[h][q]);
+          for (int q = 0; q < 8; q++) accv[q] = xrow32_d(xrow16_d(accv[q]));
+          if (lane < 16) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) pout[wave][hh][piece * 8 + q] = accv[q];
+          }
+          if (lane == 0) lred[hh][wave] = lsum;
         }
-      }
-#pragma unroll
-      for (int h = 0; h < REP; h++) {
-        lsum[h] = xrow32<OpAdd>(xrow16<OpAdd>(lsum[h]));
-#pragma unroll
-        for (int q = 0; q < 8; q++) accv[h][q] = xrow32<OpAdd>(xrow16<OpAdd>(accv[h][q]));
+      } else {
         if (lane < 16) {
-          *(float4*)(&pout[wave][h][piece * 8]) = make_float4(accv[h][0], accv[h][1], accv[h][2], accv[h][3]);
-          *(float4*)(&pout[wave][h][piece * 8 + 4]) = make_float4(accv[h][4], accv[h][5], accv[h][6], accv[h][7]);
-        }
-        if (lane == 0) lred[h][wave] = lsum[h];
-      }
-    } else {
-      if (lane < 16) {
 #pragma unroll
-        for (int h = 0; h < REP; h++) {
-          *(float4*)(&pout[wave][h][piece * 8]) = make_float4(0.f, 0.f, 0.f, 0.f);
-          *(float4*)(&pout[wave][h][piece * 8 + 4]) = make_float4(0.f, 0.f, 0.f, 0.f);
+          for (int hh = 0; hh < HB; hh++) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) pout[wave][hh][piece * 8 + q] = 0.0;
+          }
+        }
+        if (lane == 0) {
+#pragma unroll
+          for (int hh = 0; hh < HB; hh++) lred[hh][wave] = 0.0;
         }
       }
-      if (lane == 0) {
+      __syncthreads();
+      if (tid < 128) {
 #pragma unroll
-        for (int h = 0; h < REP; h++) lred[h][wave] = 0.f;
-      }
-    }
-    __syncthreads();
-    if (tid < 128) {
+        for (int hh = 0; hh < HB; hh++) {
+          const int h = hb + hh;
+          double oc = 0.0, Lc = 0.0;
 #pragma unroll
-      for (int h = 0; h < REP; h++) {
-        float oc = 0.f, Lc = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; w++) { oc += pout[w][h][tid]; Lc += lred[h][w]; }
-        const float Mn = fmaxf(Mrun[h], Mc[h]);
-        const float fa = (Mrun[h] == -INFINITY) ? 0.f : bz_expf(Mrun[h] - Mn), fb = bz_expf(Mc[h] - Mn);
-        Orun[h] = Orun[h] * fa + oc * fb;
-        Lrun[h] = Lrun[h] * fa + Lc * fb;
-        Mrun[h] = Mn;
+          for (int w = 0; w < NW; w++) { oc += pout[w][hh][tid]; Lc += lred[hh][w]; }
+          const float Mn = fmaxf(Mrun[h], Mc[h]);
+          const float fa = (Mrun[h] == -INFINITY) ? 0.f : bz_expf(Mrun[h] - Mn), fb = bz_expf(Mc[h] - Mn);   // one chunk: 0 and exactly 1
+          Orun[h] = Orun[h] * (double)fa + oc * (double)fb;
+          Lrun[h] = Lrun[h] * (double)fa + Lc * (double)fb;
+          Mrun[h] = Mn;
+        }
       }
     }
   }
@@ -3891,8 +3919,8 @@ __global__ __launch_bounds__(REP == 8 ? 512 : 256) void k_attn_split(AttnArgs a,
 #pragma unroll
     for (int h = 0; h < REP; h++) {
       float* dst = ws + ((size_t)(kvh * REP + h) * nsplit + s) * ATT_PSTRIDE;
-      dst[4 + tid] = Orun[h];
-      if (tid == 0) { dst[0] = Mrun[h]; dst[1] = Lrun[h]; }
+      dst[4 + tid] = (float)Orun[h];
+      if (tid == 0) { dst[0] = Mrun[h]; dst[1] = (float)Lrun[h]; }
     }
   }
 }
@@ -3925,7 +3953,7 @@ __device__ __forceinline__ void att_merge_512(const float* __restrict__ ws, int 
   for (int s = ph; s < ns; s += 4) o += wS[s] * base[(size_t)s * ATT_PSTRIDE + 4 + d];
   osum[ph][d] = o;
   __syncthreads();
-  if (tid < 128) outh[tid] = round_act(((osum[0][tid] + osum[1][tid]) + (osum[2][tid] + osum[3][tid])) / L, act);
+  if (tid < 128) outh[tid] = round_act(div_rn((osum[0][tid] + osum[1][tid]) + (osum[2][tid] + osum[3][tid]), L), act);   // one live slice: O / L themselves
 }
 
 template <int WIN>
@@ -3942,13 +3970,13 @@ __global__ __launch_bounds__(512) void k_attn_merge(AttnArgs a, const float* __r
 template <int TPW, int WIN = 0>
 __global__ __launch_bounds__(512) void k_attn_merge_oproj(AttnArgs a, const float* __restrict__ ws, int nsplit, const uint4* __restrict__ W,
                                                           const __half* __restrict__ S, const unsigned char* __restrict__ Z,
-                                                          const float* __restrict__ bias, int CS, long long* acc) {
+                                                          int CS, long long* acc) {
   constexpr int HD = 128;
   __shared__ float wS[128], red[16], osum[4][128];
   __shared__ __attribute__((aligned(16))) float outh[128];
   __shared__ uint4 xpl[4 * XQ_NP];
   __shared__ int4 gpar[2];
-  asm volatile("" :: "s"(a.pos), "s"(a.act), "s"(a.nq), "s"(ws), "s"(nsplit), "s"(W), "s"(S), "s"(Z), "s"(bias), "s"(CS), "s"(acc),
+  asm volatile("" :: "s"(a.pos), "s"(a.act), "s"(a.nq), "s"(ws), "s"(nsplit), "s"(W), "s"(S), "s"(Z), "s"(CS), "s"(acc),
                "s"(a.zero_buf), "s"(a.zero_n));
   const int hq = blockIdx.x / CS, cs = blockIdx.x % CS;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -3984,7 +4012,6 @@ __global__ __launch_bounds__(512) void k_attn_merge_oproj(AttnArgs a, const floa
     double y = 0.0;
     q4g_consume(Wb[t], 0, xpl, gpar, sc[t], zp[t], y);
     const int n = (t0 + t) * 64 + lane;
-    if (bias != nullptr && hq == 0) y += (double)bias[n];
     atomicAdd((unsigned long long*)(acc + n), (unsigned long long)d2fix(y, a.act));
   }
 }
@@ -4031,13 +4058,13 @@ int bzk_attn_merge_oproj(hipStream_t s, const AttnArgs& a, const float* ws, int 
   if (CS <= 0 || NW != 8) BZ_FAIL(BZ_E_INVALID, "attn merge + o_proj fusion does not apply to this shape");
   const int TPW = (L.N / 64) / (CS * 8);
 #define LAUNCH_MO_(T, WN) BZ_LAUNCH("attn_merge+o_proj", L.algo_bytes, (k_attn_merge_oproj<T, WN>), dim3(a.nq * CS), dim3(512), 0, s, a, ws, nsplit, \
-    (const uint4*)L.w, (const __half*)L.scales, (const unsigned char*)L.zeros, L.bias, CS, acc)
+    (const uint4*)L.w, (const __half*)L.scales, (const unsigned char*)L.zeros, CS, acc)
 #define LAUNCH_MO(T) do { if (a.window > 0) LAUNCH_MO_(T, 1); else LAUNCH_MO_(T, 0); } while (0)
   if (TPW == 1) LAUNCH_MO(1); else LAUNCH_MO(2);
 #undef LAUNCH_MO
 #undef LAUNCH_MO_
   BZ_HIP(hipGetLastError());
-  return BZ_OK;
+  return bzk_fix_bias(s, acc, L.bias, L.N, a.act);
 }
 
 int bzk_attn_decode(hipStream_t s, const AttnArgs& a) {
@@ -4050,7 +4077,7 @@ int bzk_attn_decode(hipStream_t s, const AttnArgs& a) {
   if ((a.hd == 128 || (a.hd == 64 && a.rope_cur != nullptr && !no_a64)) && a.kv.dtype != BZ_F32) {
     // the 8-wave lane = (row, 8-element piece) kernel: head_dim 128, and 64 (Llama-3.2-1B) with 8 rows per wave-wide load
 #define LAUNCH_A2_(DT, PG, HDV, WN) BZ_LAUNCH("attn_decode", 0.0, (k_attn2<DT, 0, 1, 8, PG, HDV, WN>), dim3(a.nq), dim3(512), attn2_smem(8), s, a, (const uint4*)nullptr, \
-    (const __half*)nullptr, (const unsigned char*)nullptr, (const float*)nullptr, 1, (long long*)nullptr)
+    (const __half*)nullptr, (const unsigned char*)nullptr, 1, (long long*)nullptr)
 #define LAUNCH_A2(DT, PG, HDV) do { if (a.window > 0) LAUNCH_A2_(DT, PG, HDV, 1); else LAUNCH_A2_(DT, PG, HDV, 0); } while (0)
 #define LAUNCH_A2_P(DT, HDV) do { if (a.kv.paged) LAUNCH_A2(DT, 1, HDV); else LAUNCH_A2(DT, 0, HDV); } while (0)
 #define LAUNCH_A2_H(DT) do { if (a.hd == 128) LAUNCH_A2_P(DT, 128); else LAUNCH_A2_P(DT, 64); } while (0)

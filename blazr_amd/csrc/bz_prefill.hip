@@ -1000,11 +1000,11 @@ __global__ __launch_bounds__(WPB * 64) void k_gemm_q4g_i8(const uint4* __restric
 #pragma unroll
   for (int T = 0; T < 2; T++) {
     const int n = tile * 64 + 32 * T + c;
-    const double bv = bias ? (double)bias[n] : 0.0;
+    const float bv = bias ? bias[n] : 0.f;
 #pragma unroll
     for (int i = 0; i < 16; i++) {
       const int m = r0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-      if (m < S) Y[(size_t)m * N + n] = pf_round((float)(tot[T][i] + bv), act);
+      if (m < S) Y[(size_t)m * N + n] = pf_round(__fadd_rn((float)tot[T][i], bv), act);     // the exact sum rounded to f32 once, then the bias in f32 (the oracle's order)
     }
   }
 }

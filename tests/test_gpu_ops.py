@@ -104,9 +104,33 @@ def test_quant_matmul_vs_oracle(fix, short, request):
     x[2, ::7] = 0.0
     want = orc_py.OrcLinear(spec).forward(x)
     got = lm.quant_matmul(_names(0)[short], x)
-    # int8x3 activation split is 24-bit fixed point (f32-exact products); f32 accumulation order differs from the oracle
+    # the sums are exact (eight signed-nibble planes of the activation codes, integer group sums, doubles across groups); what is left is the op's accumulator grid:
+    # f32 results take the 2^-32 fixed point, one rounding per workgroup, where the model's f16 steps take 2^-44
     tol = 2e-6 * np.abs(want).max() + 1e-7
     assert np.abs(got - want).max() <= tol, (np.abs(got - want).max(), tol)
+
+
+@pytest.mark.parametrize("width,short", [("h2048", "o"), ("h2048", "down"), ("h4096", "k")])
+def test_quant_matmul_bias_after_the_rounded_sum(device, width, short):
+    """a biased GPTQ linear at real width, f16-exact inputs: |got - (RN32(exact sum) + bias)| <= 1 f32 ulp of the result (the bias is added in f32 to the
+    sum's one rounding; the op's 2^-32 accumulator units leave no room for equality -- tests/test_gpu_linear_bias.py holds the f16 steps to that)"""
+    import bias_cases as bc
+    model = bc.make_model(width)
+    spec = model["layers"][0][short]
+    spec["bias"] = (np.random.default_rng(8).standard_normal(spec["N"]).astype(np.float32) * 0.01).astype(np.float16).astype(np.float32)
+    lm = runtime.LoadedModel.from_synth(device, model)
+    x = np.random.default_rng(5).standard_normal((3, spec["K"])).astype(np.float16).astype(np.float32)
+    x[1] *= 8.0           # (a power of two: still f16 values)
+    x[2, ::7] = 0.0
+    got = lm.quant_matmul(_names(0)[short], x)
+    worst = 0.0
+    for r in range(3):
+        want = bc.rn32(bc.exact_sums(dict(spec, bias=None), x[r])) + spec["bias"]
+        assert np.array_equal(want, orc_py.OrcLinear(spec).forward(x[r])[0])
+        ulps = np.abs(got[r].astype(np.float64) - want.astype(np.float64)) / np.spacing(np.abs(want)).astype(np.float64)
+        print("%s %s row %d: max |got - want| = %.3g f32 ulps of the result, %d of %d elements off" % (width, short, r, ulps.max(), int((ulps > 0).sum()), ulps.size))
+        worst = max(worst, float(ulps.max()))
+    assert worst <= 1.0, worst
 
 
 def test_quant_matmul_edge_inputs(tiny_awq):
