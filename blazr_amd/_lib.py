@@ -225,6 +225,39 @@ PF_ATTN_NONE, PF_ATTN_MFMA, PF_ATTN_SCALAR, PF_ATTN_SCALAR_EXACT, PF_ATTN_ROWS =
 HEAD_STEP, HEAD_GEMM, HEAD_GEMV_ROWS, HEAD_SPEC = 0, 1, 2, 3
 
 
+# which kernels a decode step launches (bz_layer_plan)
+class LinearTraits(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("kind", "N", "K", "wdt", "gw", "sk", "npf", "act_order", "bias")]
+
+
+class FusedTraits(C.Structure):
+    _fields_ = [("n_parts", C.c_int), ("fix_out", C.c_int), ("parts", LinearTraits * 3)]
+
+
+class LayerTraits(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ("arch", "act_dtype", "hidden", "inter", "n_heads", "n_kv_heads", "head_dim", "window", "lora_o", "lora_mlp", "down_slabs")] +
+                [(n, FusedTraits) for n in ("qkv", "o", "gateup", "down")] + [("mla_x_ok", C.c_int * 3)] +
+                [(n, C.c_int) for n in ("is_moe", "e_dt", "router_dt", "moe_inter", "moe_n_experts", "moe_slots", "ssm_d_inner", "ssm_n_groups")])
+
+
+class StepSwitches(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("no_slim_qkv", "no_gq_slim", "no_gq_mix", "no_rows2", "no_attn_fusion", "no_attn_split", "no_attn_f32", "no_attn2_hd64",
+                                       "no_mlp_fusion", "gguf_mlp_fusion", "dsv2_f32_sums", "no_moe_route_fusion")]
+
+
+class LayerPlan(C.Structure):
+    _fields_ = [("qkv_mix", C.c_int), ("qkv", C.c_int * 3), ("attn_short", C.c_int), ("attn_long", C.c_int), ("attn_kernel", C.c_int), ("o", C.c_int * 3),
+                ("mlp", C.c_int), ("gateup_mix", C.c_int), ("gateup", C.c_int * 3), ("down", C.c_int * 3),
+                ("mla_exact", C.c_int), ("moe_route_fused", C.c_int), ("moe_rows2", C.c_int)]
+
+
+(LIN_NONE, LIN_Q4G, LIN_ROWS, LIN_Q4K, LIN_Q6K, LIN_Q80, LIN_Q5K, LIN_Q40, LIN_Q41, LIN_Q50, LIN_Q51, LIN_F8) = range(12)
+(GEMV_NONE, GEMV_F8, GEMV_Q4G_SLIM, GEMV_Q4G, GEMV_ROWS2, GEMV_ROWS, GEMV_GQ_SLIM, GEMV_GQ, GEMV_UNSUPPORTED) = range(9)
+ATTN_PLAIN, ATTN_FUSED_Q4G, ATTN_FUSED_DENSE, ATTN_FUSED_Q4K, ATTN_SPLIT, ATTN_SPLIT_FUSED = range(6)
+ATTN_K_DECODE, ATTN_K_ATTN2, ATTN_K_ATTN2F, ATTN_K_UNSUPPORTED = range(4)
+MLP_SPLIT, MLP_Q4G, MLP_DENSE, MLP_GQ = range(4)
+
+
 class EngineStats(C.Structure):
     _fields_ = [("replays", C.c_int64), ("free_blocks", C.c_int32), ("total_blocks", C.c_int32), ("park_blocks", C.c_int32), ("live_rows", C.c_int32),
                 ("admitted", C.c_int32), ("waiting", C.c_int32), ("unread", C.c_int32), ("prompt_tokens", C.c_int64), ("generated_tokens", C.c_int64),
@@ -366,6 +399,10 @@ SYMBOLS = {
     "bz_rows_attn_slice_len": (C.c_int, [C.c_int]),
     "bz_model_prompt_traits": (C.c_int, [P, C.POINTER(PromptTraits)]),
     "bz_prompt_plan": (C.c_int, [C.POINTER(PromptTraits), C.POINTER(PromptSwitches), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PromptPlan)]),
+    "bz_model_layer_traits": (C.c_int, [P, C.c_int, C.POINTER(LayerTraits)]),
+    "bz_model_layer_plan": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(LayerPlan)]),
+    "bz_layer_plan": (C.c_int, [C.POINTER(LayerTraits), C.POINTER(StepSwitches), C.c_int, C.POINTER(LayerPlan)]),
+    "bz_step_attn_form": (C.c_int, [C.POINTER(LayerPlan), C.c_int, C.c_int, C.c_int]),
     "bz_kv_insert": (C.c_int, [P, P, C.c_int, C.c_int, P, P]),
     "bz_rope_caches": (C.c_int, [P, P, P]),
     "bz_grammar_compile": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(P)]),

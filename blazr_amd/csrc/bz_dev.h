@@ -75,7 +75,7 @@ __device__ __forceinline__ float silu_f(float x) { return div_rn(x, 1.0f + bz_ex
 //   sum_k (q_k - z) x_k = c * [ 256 * sum_{p<6} 16^p (D_p + (8 - z) S_p) + (D_6 + (8 - z) S_6) + 16 (D_7 + (8 - z) S_7) ],  D_p = sum_k (q_k - 8) n_p,k
 //   -- all of it exact integer arithmetic.
 // ---------------------------------------------------------------------------------------------------------
-#define XQ_NP 8   // planes stored per chunk
+// (XQ_NP, the planes stored per chunk: bz_internal.h -- the host's LDS sizes need it)
 #define XQ_NM 6   // main planes (always multiplied)
 struct OpOr { __device__ __forceinline__ static int f(int a, int b) { return a | b; } };
 __device__ __forceinline__ int xq_pack_low(int s6, int s7, int flag) { return (s6 & 0xFFF) | ((s7 & 0xFFF) << 12) | (flag ? (1 << 24) : 0); }

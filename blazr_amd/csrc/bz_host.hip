@@ -300,6 +300,11 @@ struct bz_model {
   bz_model_config cfg;
   bool finalized = false;
   bz_prompt_traits_t traits{};   // what the route decision (bz_route.hip) reads of the model, filled at finalize: no linear changes its format afterwards
+  // which kernels a decode step launches (bz_step_plan.hip): per layer what the decision reads, and the plan for each cache dtype the step accepts
+  // ([layer][BZ_F32 / BZ_F16 / BZ_BF16]); made at finalize and again by bz_lora_table_create, the only other place where an input changes
+  std::vector<bz_layer_traits_t> ltraits;
+  std::vector<bz_layer_plan_t> plans;
+  const bz_layer_plan_t& plan(int layer, int kv_dtype) const { return plans[(size_t)layer * 3 + kv_dtype]; }
   std::unordered_map<std::string, RawTensor> raw;
   std::vector<LayerDev> layers;
   void* embed = nullptr; int embed_dt = BZ_F16;
@@ -976,6 +981,72 @@ extern "C" int bz_model_prompt_traits(const bz_model* m, bz_prompt_traits_t* out
   BZ_API_END
 }
 
+// sliding window of layer l (0: full attention): every layer, or -- sliding_window_pattern n > 1 -- every layer but each n-th (l % n == n - 1)
+static int layer_window(const bz_model_config& c, int l) {
+  if (c.sliding_window <= 0) return 0;
+  const int n = c.sliding_window_pattern;
+  return (n > 1 && l % n == n - 1) ? 0 : c.sliding_window;
+}
+
+// What the step plan (bz_step_plan.hip: bz_layer_plan) reads of layer l.  Fixed once the model is finalized, but for the two LoRA flags: the launches depend
+// on the table's mask alone (never on what is attached), so a captured graph stays valid across attach / detach / set.
+static bz_fused_traits_t fused_traits(const FusedLinear& F) {
+  bz_fused_traits_t t{};
+  t.n_parts = (int)F.parts.size(); t.fix_out = F.fix_out;
+  for (int i = 0; i < t.n_parts && i < 3; i++) t.parts[i] = lin_traits(F.parts[i]);
+  return t;
+}
+static bz_layer_traits_t layer_traits(const bz_model* m, int l) {
+  const bz_model_config& c = m->cfg;
+  bz_layer_traits_t t{};
+  t.arch = c.arch; t.act_dtype = c.act_dtype; t.hidden = c.hidden; t.inter = c.inter; t.n_heads = c.n_heads; t.n_kv_heads = c.n_kv_heads; t.head_dim = c.head_dim;
+  if (c.arch == BZ_ARCH_LLAMA) {
+    const LayerDev& L = m->layers[l];
+    t.window = layer_window(c, l);
+    t.lora_o = m->lora && m->lora->group_on(LG_O); t.lora_mlp = m->lora && (m->lora->group_on(LG_GATEUP) || m->lora->group_on(LG_DOWN));
+    t.down_slabs = L.down_slabs != nullptr;
+    t.qkv = fused_traits(L.qkv); t.o = fused_traits(L.o); t.gateup = fused_traits(L.gateup); t.down = fused_traits(L.down);
+  } else if (c.arch == BZ_ARCH_DEEPSEEK2) {
+    const DsLayerDev& L = m->dlayers[l];
+    t.qkv = fused_traits(L.qkva); t.o = fused_traits(L.o);
+    MlaArgs probe{}; probe.rank = c.mla_kv_lora_rank; probe.rope = c.mla_rope_dim; probe.nope = c.mla_nope_dim; probe.vdim = c.mla_v_dim; probe.wdt = L.kv_b_dt; probe.nsplit = m->mla_nsplit;
+    for (int dt : {BZ_F32, BZ_F16, BZ_BF16}) { probe.kv.dtype = dt; t.mla_x_ok[dt] = bzk_mla_x_ok(probe, c.max_seq_len); }
+    t.is_moe = L.is_moe;
+    if (L.is_moe) { t.e_dt = L.e_dt; t.router_dt = L.router_dt; t.moe_inter = c.moe_inter; t.moe_n_experts = c.moe_n_experts; t.moe_slots = c.moe_top_k + c.moe_n_shared; }
+    else { t.gateup = fused_traits(L.gateup); t.down = fused_traits(L.down); }
+  } else {
+    const MambaLayerDev& L = m->mlayers[l];
+    t.qkv = fused_traits(L.in_proj); t.o = fused_traits(L.out_proj);
+    t.ssm_d_inner = c.ssm_d_inner; t.ssm_n_groups = c.ssm_n_groups;
+  }
+  return t;
+}
+// every finalize ends here, and bz_lora_table_create
+static int fill_step_plans(bz_model* m) {
+  const int n = m->cfg.n_layers;
+  m->ltraits.resize(n); m->plans.resize((size_t)n * 3);
+  for (int l = 0; l < n; l++) {
+    m->ltraits[l] = layer_traits(m, l);
+    for (int dt : {BZ_F32, BZ_F16, BZ_BF16}) BZ_TRY(bz_layer_plan(&m->ltraits[l], nullptr, dt, &m->plans[(size_t)l * 3 + dt]));
+  }
+  return BZ_OK;
+}
+extern "C" int bz_model_layer_traits(const bz_model* m, int layer, bz_layer_traits_t* out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || !out || layer < 0 || layer >= m->cfg.n_layers) BZ_FAIL(BZ_E_INVALID, "layer_traits: model not finalized / bad argument");
+  *out = m->ltraits[layer];
+  return BZ_OK;
+  BZ_API_END
+}
+extern "C" int bz_model_layer_plan(const bz_model* m, int layer, int kv_dtype, bz_layer_plan_t* out) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized || !out || layer < 0 || layer >= m->cfg.n_layers || (kv_dtype != BZ_F32 && kv_dtype != BZ_F16 && kv_dtype != BZ_BF16))
+    BZ_FAIL(BZ_E_INVALID, "layer_plan: model not finalized / bad argument");
+  *out = m->plan(layer, kv_dtype);
+  return BZ_OK;
+  BZ_API_END
+}
+
 static int finalize_mamba2(bz_model* m);
 static int finalize_dsv2(bz_model* m);
 
@@ -1012,13 +1083,15 @@ extern "C" int bz_model_finalize(bz_model* m) {
     if (Ld.gateup.N != 2 * I || Ld.gateup.K != H) BZ_FAIL(BZ_E_INVALID, "layer %d: gate/up shapes do not match the config", l);
     if (Ld.down.N != H || Ld.down.K != I) BZ_FAIL(BZ_E_INVALID, "layer %d: down_proj shape does not match the config", l);
     // dense 16-bit MLP of the Llama-3.2-1B class: a slab-major copy of down_proj for the fused MLP launch (the row-major one stays for prefill / fallbacks)
-    if (Ld.gateup.parts.size() == 1 && Ld.down.parts.size() == 1 && Ld.down.parts[0].kind == LK_ROWS) {
-      char dummy = 0;
-      if (bzk_mlp_dense_fusable(Ld.gateup.parts[0], Ld.down.parts[0], &dummy, H, I, c.act_dtype)) {
-        BZ_TRY(dev_alloc(m, &Ld.down_slabs, (size_t)H * I * 2));
-        BZ_TRY(bzk_repack_down_slabs(m->dev->stream, Ld.down.parts[0].w, H, I, Ld.down_slabs));
-        m->resident += (size_t)H * I * 2;
-      }
+    // -- made where the layer's plan takes that launch once the copy exists (the MLP's form does not depend on the cache dtype)
+    bz_layer_traits_t with_slabs = layer_traits(m, l);
+    with_slabs.down_slabs = 1;
+    bz_layer_plan_t lp;
+    BZ_TRY(bz_layer_plan(&with_slabs, nullptr, c.act_dtype, &lp));
+    if (lp.mlp == BZ_MLP_DENSE) {
+      BZ_TRY(dev_alloc(m, &Ld.down_slabs, (size_t)H * I * 2));
+      BZ_TRY(bzk_repack_down_slabs(m->dev->stream, Ld.down.parts[0].w, H, I, Ld.down_slabs));
+      m->resident += (size_t)H * I * 2;
     }
   }
   BZ_HIP(hipStreamSynchronize(m->dev->stream));
@@ -1098,6 +1171,7 @@ extern "C" int bz_model_finalize(bz_model* m) {
   for (auto& L : m->lm_head.parts) { m->resident += L.bytes; m->per_token += L.algo_bytes; }
   BZ_HIP(hipDeviceSynchronize());   // null-stream memsets above vs. the non-blocking compute stream
   fill_prompt_traits(m);
+  BZ_TRY(fill_step_plans(m));
   m->finalized = true;
   return BZ_OK;
   BZ_API_END
@@ -1296,6 +1370,7 @@ static int finalize_dsv2(bz_model* m) {
   m->per_token = per_token + (size_t)H * bz_dtype_size(m->embed_dt) + (size_t)H * act_b;
   BZ_HIP(hipDeviceSynchronize());
   fill_prompt_traits(m);
+  BZ_TRY(fill_step_plans(m));
   m->finalized = true;
   return BZ_OK;
 }
@@ -1380,6 +1455,7 @@ static int finalize_mamba2(bz_model* m) {
   for (auto& L : m->lm_head.parts) { m->resident += L.bytes; m->per_token += L.algo_bytes; }
   BZ_HIP(hipDeviceSynchronize());
   fill_prompt_traits(m);
+  BZ_TRY(fill_step_plans(m));
   m->finalized = true;
   return BZ_OK;
 }
@@ -1580,18 +1656,6 @@ static hipStream_t step_stream(const bz_model* m) { return tl_capture_stream ? t
 // contexts beyond this many positions take the split-KV attention path (two launches; the fused single launch wins below it)
 static int att_split_min() { const char* e = getenv("BZ_SPLIT_MIN"); return e ? atoi(e) : 512; }   // read per call: tests move it
 static int att_positions_for(int len) { return len > att_split_min() ? len : 0; }
-// sliding window of layer l (0: full attention): every layer, or -- sliding_window_pattern n > 1 -- every layer but each n-th (l % n == n - 1)
-static int layer_window(const bz_model_config& c, int l) {
-  if (c.sliding_window <= 0) return 0;
-  const int n = c.sliding_window_pattern;
-  return (n > 1 && l % n == n - 1) ? 0 : c.sliding_window;
-}
-// the most keys any layer's query reads at a context of `len` positions
-static int window_keys(const bz_model_config& c, int len) {
-  bool all = c.sliding_window > 0;
-  for (int l = 0; all && l < c.n_layers; l++) all = layer_window(c, l) > 0;
-  return all ? std::min(len, c.sliding_window) : len;
-}
 
 struct StepIO {
   KvView kv;
@@ -1632,13 +1696,12 @@ struct RingState {
   }
 };
 
-// Launch every part of a fused linear.  Returns the VSrc describing its output.
-static int run_fused(bz_model* m, const FusedLinear& F, Pro pro, RingState& rs, VSrc* out, const ConvShift* shift = nullptr) {
+// Launch every part of a fused linear (mix: the layer plan's qkv_mix / gateup_mix -- its two parts in one launch).  Returns the VSrc describing its output.
+static int run_fused(bz_model* m, const FusedLinear& F, Pro pro, RingState& rs, VSrc* out, bool mix = false, const ConvShift* shift = nullptr) {
   hipStream_t st = step_stream(m);
   const int act = m->cfg.act_dtype;
   float* direct = m->dring[rs.ri];
-  static const bool no_mix = getenv("BZ_NO_GQ_MIX") != nullptr;
-  if (!no_mix && F.parts.size() == 2 && F.fix_out && F.n_off[1] == F.parts[0].N && bzk_gq_mix_ok(F.parts[0], F.parts[1], pro)) {
+  if (mix) {
     // GGUF Q4_K_M q/k/v: the Q4_K part (q, k) and the Q6_K part (v) in one launch
     const RingSlot r = rs.take(F.N);
     GemvOut o{};
@@ -1740,8 +1803,6 @@ static int llama_step(bz_model* m, const StepIO& io) {
   const bz_model_config& c = m->cfg;
   hipStream_t st = step_stream(m);
   const int H = c.hidden, I = c.inter, act = c.act_dtype;
-  // the launches depend on the table's mask alone (never on what is attached): a captured graph stays valid across attach / detach / set
-  const bool lora_o = m->lora && m->lora->group_on(LG_O), lora_mlp = m->lora && (m->lora->group_on(LG_GATEUP) || m->lora->group_on(LG_DOWN));
   const int lend = io.layer_end < 0 ? c.n_layers : io.layer_end;
   int cur = 0;
   RingState rs(m);
@@ -1755,10 +1816,11 @@ static int llama_step(bz_model* m, const StepIO& io) {
   }
   for (int l = io.layer_start; l < lend; l++) {
     const LayerDev& Ld = m->layers[l];
+    const bz_layer_plan_t& P = m->plan(l, io.kv.dtype);     // (the caches hold F32 / F16 / BF16: refused otherwise where they are made)
     Pro pn{}; pn.mode = PRO_NORM; pn.src = prev; pn.h_in = m->hbuf[cur]; pn.h_out = m->hbuf[cur ^ 1]; pn.norm_w = Ld.attn_norm;
     pn.eps = c.rms_eps; pn.H = H; pn.act = act;
     VSrc qkv;
-    BZ_TRY(run_fused(m, Ld.qkv, pn, rs, &qkv));
+    BZ_TRY(run_fused(m, Ld.qkv, pn, rs, &qkv, P.qkv_mix));
     cur ^= 1;
     // the adapter's x is the norm of the residual row the base launch has just written (h', no deferred residual left to add)
     Pro pxn = pn; pxn.src = VSrc{nullptr, 0}; pxn.h_in = m->hbuf[cur]; pxn.h_out = nullptr; pxn.perm = nullptr;
@@ -1768,21 +1830,11 @@ static int llama_step(bz_model* m, const StepIO& io) {
     aa.qkv = qkv; aa.cos_t = m->cos_t; aa.sin_t = m->sin_t; aa.interleaved = c.rope_interleaved; aa.pos = io.d_pos; aa.rope_cur = m->rope_cur;
     aa.nq = c.n_heads; aa.nkv = c.n_kv_heads; aa.hd = c.head_dim; aa.act = act; aa.kv = io.kv; aa.layer = l; aa.out = m->attn_out;
     aa.zero_buf = nullptr; aa.zero_n = 0; aa.q_only = 0; aa.window = layer_window(c, l);
-    // a windowed layer reads min(len, W) keys: the choice of path is made on that many positions, so a long context with a window that fits the single-pass
-    // kernel goes back to it (att_positions: position + 1 in eager steps, the capacity in a graph -- both sides of W give the same choice)
-    const int att_positions = aa.window > 0 ? att_positions_for(std::min(io.att_positions, aa.window)) : io.att_positions;
+    // the one decision taken per call, short or long: a windowed layer makes it on min(len, W) positions (bz_step_plan.hip)
+    const int att_positions = bzk_att_positions(io.att_positions, aa.window, att_split_min());
     VSrc ov;
-    static const bool no_fuse = getenv("BZ_NO_ATTN_FUSION") != nullptr;
-    // (the f32-cache form has no split-KV partner: beyond the single-launch contexts it stays unfused)
-    const bool fuse_shape = !no_fuse && !lora_o && Ld.o.parts.size() == 1 && Ld.o.fix_out;   // an o_proj adapter reads the attention output: two launches
-    const bool fuse_cap = fuse_shape && bzk_attn_oproj_slices(aa, Ld.o.parts[0]) > 0;
-    static const bool no_split = getenv("BZ_NO_ATTN_SPLIT") != nullptr;
-    const bool split_wanted = !no_split && att_positions > 0 && m->att_ws && bzk_attn_split_ok(aa);
-    const bool merge_fused = fuse_shape && Ld.o.parts[0].kind == LK_Q4G && bzk_attn_merge_oproj_ok(aa, Ld.o.parts[0]);
-    // long contexts: split-KV attention merged with the o_proj where that form exists (int4); otherwise attention (split or not) and a separate o_proj launch --
-    // the fused single-launch kernel reads the context once per column slice, which only pays while the context is short
-    const bool fuse_o = (fuse_cap && att_positions == 0) || (split_wanted && merge_fused);
-    const bool split = split_wanted && (!fuse_o || merge_fused);
+    const int attn = att_positions == 0 ? P.attn_short : P.attn_long;
+    const bool split = attn == BZ_ATTN_SPLIT || attn == BZ_ATTN_SPLIT_FUSED, fuse_o = attn != BZ_ATTN_PLAIN && attn != BZ_ATTN_SPLIT;
     int nsplit = 0;
     if (split) {
       // long context: split-KV partials (all query heads of a group share the K/V rows), then merge (+ o_proj); the grid covers
@@ -1808,26 +1860,18 @@ static int llama_step(bz_model* m, const StepIO& io) {
     Pro pf{}; pf.mode = PRO_NORM; pf.src = ov; pf.h_in = m->hbuf[cur]; pf.h_out = m->hbuf[cur ^ 1]; pf.norm_w = Ld.ffn_norm;
     pf.eps = c.rms_eps; pf.H = H; pf.act = act;
     VSrc dn;
-    static const bool no_mlp_fuse = getenv("BZ_NO_MLP_FUSION") != nullptr;
     // norm + gate/up + SiLU*up + down in one launch (same ring protocol as one GEMV launch), where one of its three forms takes the layer
-    enum { MLP_SPLIT, MLP_Q4G, MLP_DENSE, MLP_GQ } mlp = MLP_SPLIT;
-    if (!no_mlp_fuse && !lora_mlp && Ld.gateup.parts.size() == 1 && Ld.down.parts.size() == 1) {   // a gate / up / down adapter takes the split MLP
-      const LinearDev& GU = Ld.gateup.parts[0]; const LinearDev& DN = Ld.down.parts[0];
-      if (act == BZ_F16 && bzk_mlp_fusable(GU, DN, H, I)) mlp = MLP_Q4G;
-      else if (bzk_mlp_dense_fusable(GU, DN, Ld.down_slabs, H, I, act)) mlp = MLP_DENSE;   // the dense 16-bit form of the same fusion (slab-major down_proj copy)
-      else if (bzk_mlp_gq_fusable(GU, DN, H, I, act)) mlp = MLP_GQ;   // the GGUF form of the same fusion (Q4_K gate / up, Q4_K or Q6_K down, f32 activations)
-    }
-    if (mlp != MLP_SPLIT) {
+    if (P.mlp != BZ_MLP_SPLIT) {
       const LinearDev& GU = Ld.gateup.parts[0]; const LinearDev& DN = Ld.down.parts[0];
       const RingSlot r = rs.take(H);
-      if (mlp == MLP_Q4G) BZ_TRY(bzk_mlp_q4g(st, GU, DN, H, I, pf, r.acc, r.zero_buf, r.zero_n));
-      else if (mlp == MLP_DENSE) BZ_TRY(bzk_mlp_dense(st, GU, DN, Ld.down_slabs, H, I, pf, r.acc, r.zero_buf, r.zero_n));
+      if (P.mlp == BZ_MLP_Q4G) BZ_TRY(bzk_mlp_q4g(st, GU, DN, H, I, pf, r.acc, r.zero_buf, r.zero_n));
+      else if (P.mlp == BZ_MLP_DENSE) BZ_TRY(bzk_mlp_dense(st, GU, DN, Ld.down_slabs, H, I, pf, r.acc, r.zero_buf, r.zero_n));
       else BZ_TRY(bzk_mlp_gq(st, GU, DN, H, I, pf, r.acc, r.zero_buf, r.zero_n));
       dn = VSrc{r.acc, 1};
       cur ^= 1;
     } else {
       VSrc gu;
-      BZ_TRY(run_fused(m, Ld.gateup, pf, rs, &gu));
+      BZ_TRY(run_fused(m, Ld.gateup, pf, rs, &gu, P.gateup_mix));
       cur ^= 1;
       Pro pxf = pf; pxf.src = VSrc{nullptr, 0}; pxf.h_in = m->hbuf[cur]; pxf.h_out = nullptr; pxf.perm = nullptr;
       BZ_TRY(lora_after(m, l, LG_GATEUP, pxf, &gu));
@@ -1864,7 +1908,7 @@ static int mamba_step(bz_model* m, const StepIO& io) {
     const MambaLayerDev& L = m->mlayers[l];
     Pro pn{}; pn.mode = PRO_NORM; pn.src = prev; pn.h_in = m->hbuf[cur]; pn.h_out = m->hbuf[cur ^ 1]; pn.norm_w = L.norm; pn.eps = c.rms_eps; pn.H = D; pn.act = act;
     VSrc zx;
-    BZ_TRY(run_fused(m, L.in_proj, pn, rs, &zx));
+    BZ_TRY(run_fused(m, L.in_proj, pn, rs, &zx, m->plan(l, BZ_F32).qkv_mix));     // (no cache: a Mamba2 plan is the same under every cache dtype)
     cur ^= 1;
     // conv1d step + SiLU + SSM recurrence + gate in one launch (reads the projection from the ring: f32 or fixed point)
     SsmArgs sa{};
@@ -1877,7 +1921,7 @@ static int mamba_step(bz_model* m, const StepIO& io) {
     VSrc ov;
     // side duty of this launch: the B / C channels' conv state moves on by this step's projection (every head's SSM step has read the old one)
     ConvShift shf{sa.conv_state, zx, DI, DI, 2 * G * NS, KC};
-    BZ_TRY(run_fused(m, L.out_proj, pg, rs, &ov, &shf));
+    BZ_TRY(run_fused(m, L.out_proj, pg, rs, &ov, false, &shf));
     prev = ov;
   }
   BZ_TRY(step_rows_out(m, io, prev, m->hbuf[cur]));
@@ -1898,9 +1942,10 @@ static int dsv2_step(bz_model* m, const StepIO& io) {
   BZ_TRY(bzk_embed(st, m->embed, m->embed_dt, m->embed_ggml, io.d_tok, H, act, m->hbuf[cur]));
   for (int l = 0; l < c.n_layers; l++) {
     const DsLayerDev& L = m->dlayers[l];
+    const bz_layer_plan_t& P = m->plan(l, io.kv.dtype);
     Pro pn{}; pn.mode = PRO_NORM; pn.src = prev; pn.h_in = m->hbuf[cur]; pn.h_out = m->hbuf[cur ^ 1]; pn.norm_w = L.attn_norm; pn.eps = c.rms_eps; pn.H = H; pn.act = act; pn.f32_sums = 0;
     VSrc qkva;
-    BZ_TRY(run_fused(m, L.qkva, pn, rs, &qkva));
+    BZ_TRY(run_fused(m, L.qkva, pn, rs, &qkva, P.qkv_mix));
     cur ^= 1;
     MlaArgs ma{};
     if (c.mla_q_lora_rank > 0) {
@@ -1917,8 +1962,7 @@ static int dsv2_step(bz_model* m, const StepIO& io) {
     ma.scale = mla_softmax_scale(c);
     ma.ws = m->mla_ws; ma.nsplit = m->mla_nsplit;
     // exact decode (16-bit models): every sum as the oracle defines it, one maximum over the whole context (BZ_DSV2_F32_SUMS=1: the f32 kernels)
-    static const bool f32_mla = getenv("BZ_DSV2_F32_SUMS") != nullptr;
-    if (!f32_mla && (act == BZ_F16 || act == BZ_BF16) && bzk_mla_x_ok(ma, c.max_seq_len)) BZ_TRY(bzk_mla_attn_x(st, ma, c.max_seq_len, m->mla_wsd, m->mla_scw, m->mla_mxw));
+    if (P.mla_exact) BZ_TRY(bzk_mla_attn_x(st, ma, c.max_seq_len, m->mla_wsd, m->mla_scw, m->mla_mxw));
     else BZ_TRY(bzk_mla_attn(st, ma, c.max_seq_len));
     Pro pp{}; pp.mode = PRO_PLAIN; pp.src = VSrc{m->attn_out, 0}; pp.act = act; pp.H = 0; pp.f32_sums = 0;
     VSrc ov;
@@ -1926,7 +1970,7 @@ static int dsv2_step(bz_model* m, const StepIO& io) {
     Pro pf{}; pf.mode = PRO_NORM; pf.src = ov; pf.h_in = m->hbuf[cur]; pf.h_out = m->hbuf[cur ^ 1]; pf.norm_w = L.ffn_norm; pf.eps = c.rms_eps; pf.H = H; pf.act = act; pf.f32_sums = 0;
     if (!L.is_moe) {
       VSrc gu, dn;
-      BZ_TRY(run_fused(m, L.gateup, pf, rs, &gu));
+      BZ_TRY(run_fused(m, L.gateup, pf, rs, &gu, P.gateup_mix));
       cur ^= 1;
       Pro ps{}; ps.mode = PRO_SILU; ps.src = gu; ps.H = c.inter; ps.act = act; ps.f32_sums = 0;
       BZ_TRY(run_fused(m, L.down, ps, rs, &dn));
@@ -1934,8 +1978,7 @@ static int dsv2_step(bz_model* m, const StepIO& io) {
     } else {
       const int slots = TK + NS;
       const size_t es = bz_dtype_size(L.e_dt);
-      static const bool no_fr = getenv("BZ_NO_MOE_ROUTE_FUSION") != nullptr;
-      if (!no_fr && bzk_moe_rows2_ok(L.e_dt, H) && bzk_moe_rows2_ok(L.e_dt, MI) && bzk_moe_rows2_ok(L.router_dt, H) && E <= 1024 && slots <= 128) {
+      if (P.moe_route_fused) {
         // router logits = one more fixed-point GEMV of the ring (norm prologue: writes h'); the top-k runs in the prologue of the gate / up launch, which
         // repeats the norm for its own x (the same inputs: h and the o_proj accumulator, both still in place)
         LinearDev RL; RL.kind = LK_ROWS; RL.N = E; RL.K = H; RL.wdt = L.router_dt; RL.w = L.router; RL.sk = 2; RL.owned = false; RL.algo_bytes = (size_t)E * H * bz_dtype_size(L.router_dt);
@@ -1963,7 +2006,7 @@ static int dsv2_step(bz_model* m, const StepIO& io) {
       cur ^= 1;
       // gate / up of the selected + shared experts in ONE launch, down in one more.  Balanced role kernel (fixed-point accumulators both times) when the
       // expert weights are 16-bit; else the 16-row workgroup form with a direct f32 gate / up
-      const bool r2 = bzk_moe_rows2_ok(L.e_dt, H) && bzk_moe_rows2_ok(L.e_dt, MI);
+      const bool r2 = P.moe_rows2;
       MoeGemvArgs g1{};
       g1.w = L.e_gu; g1.expert_stride = (long long)2 * MI * H; g1.sel = m->moe_sel; g1.N = 2 * MI; g1.K = H; g1.src_stride = 0;
       g1.out = m->moe_gu; g1.out_stride = 2 * MI;
@@ -3402,7 +3445,8 @@ extern "C" int bz_lora_table_create(bz_model* m, const bz_lora_table_config* cfg
   const int K[LT_N] = {c.hidden, c.hidden, c.hidden, qn, c.hidden, c.hidden, c.inter}, N[LT_N] = {qn, kn, kn, c.hidden, c.inter, c.inter, c.hidden};
   BZ_HIP(hipSetDevice(m->dev->id));
   BZ_HIP(hipStreamSynchronize(m->dev->stream));
-  return bzl_table_create(m->dev, cfg, c.n_layers, K, N, &m->lora);
+  BZ_TRY(bzl_table_create(m->dev, cfg, c.n_layers, K, N, &m->lora));
+  return fill_step_plans(m);     // the table's mask decides whether attention + o_proj and the MLP stay fused
   BZ_API_END
 }
 // executor.rs:397-420 load_lora: an adapter becomes selectable
@@ -4393,7 +4437,7 @@ extern "C" int bz_moe_grouped_gemv(bz_model* m, int layer, int which, const bz_t
   std::lock_guard<std::recursive_mutex> lk(m->mu);
   hipStream_t st = m->dev->stream;
   const size_t es = bz_dtype_size(L->e_dt);
-  const bool r2 = bzk_moe_rows2_ok(L->e_dt, K);
+  const bool r2 = bzk_moe_rows2_ok(L->e_dt, K, *bzk_step_switches());
   long long* acc = nullptr;
   BZ_HIP(hipMalloc((void**)&acc, (size_t)n_slots * N * 8));
   hipError_t e0 = hipMemsetAsync(acc, 0, (size_t)n_slots * N * 8, st);

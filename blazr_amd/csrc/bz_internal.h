@@ -53,7 +53,9 @@ struct Pro {
   int f32_sums;        // dense k_gemv_rows2: f32 FMA chains instead of the exact (double) sums -- the DeepSeek-V2 path sets it (k_gemv_rows2's EX)
 };
 
-enum { LK_NONE = 0, LK_Q4G = 1, LK_ROWS = 2, LK_Q4K = 3, LK_Q6K = 4, LK_Q80 = 5, LK_Q5K = 6, LK_Q40 = 7, LK_Q41 = 8, LK_Q50 = 9, LK_Q51 = 10, LK_F8 = 11 };
+// (the public BZ_LIN_* values: bz_linear_traits_t carries a kind as it is)
+enum { LK_NONE = BZ_LIN_NONE, LK_Q4G = BZ_LIN_Q4G, LK_ROWS = BZ_LIN_ROWS, LK_Q4K = BZ_LIN_Q4K, LK_Q6K = BZ_LIN_Q6K, LK_Q80 = BZ_LIN_Q80, LK_Q5K = BZ_LIN_Q5K, LK_Q40 = BZ_LIN_Q40,
+       LK_Q41 = BZ_LIN_Q41, LK_Q50 = BZ_LIN_Q50, LK_Q51 = BZ_LIN_Q51, LK_F8 = BZ_LIN_F8 };
 
 // Device-resident linear layer in kernel layout.
 struct LinearDev {
@@ -202,7 +204,6 @@ struct RouteArgs { const long long* lg; int E, top_k, n_shared; float routed_sca
 
 // second (Q6_K) tile range of a mixed-format slim GGUF launch: tiles [nt4, ...) read these arrays with the tile index restarting at 0
 struct GqMix { const uint4* Wq6; const uint2* Wh6; const uint4* Hd6; const __half* Dd6; int nt4; };
-bool bzk_gq_mix_ok(const LinearDev& A, const LinearDev& B, const Pro& pro);
 int bzk_gemv_gq_mix(hipStream_t s, const LinearDev& A, const LinearDev& B, const Pro& pro, const struct GemvOut& out);
 
 struct GemvOut {
@@ -227,13 +228,10 @@ int bzk_gemv_f8(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut
 bool bzk_gemm_f8w_ok(const LinearDev& L, int xdt);
 int bzk_gemm_f8w(hipStream_t s, const LinearDev& L, int dt, const void* x16, int S, int act, float* y, float* ws = nullptr, size_t ws_bytes = 0);
 int bzk_dequant_f8(hipStream_t s, const LinearDev& L, float* out);
-bool bzk_mlp_gq_fusable(const LinearDev& gu, const LinearDev& dn, int H, int I, int act);   // GGUF Q4_K gate/up + Q4_K / Q6_K down, f32 activations
 int bzk_mlp_gq(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, int I, const Pro& pro, long long* acc, long long* zero_buf, int zero_n);
 // dense 16-bit form (k_mlp_dense): down_proj additionally stored slab-major [I / 32][H][32] (bzk_repack_down_slabs at finalize)
 int bzk_repack_down_slabs(hipStream_t s, const void* w, int H, int I, void* out);
-bool bzk_mlp_dense_fusable(const LinearDev& gu, const LinearDev& dn, const void* down_slabs, int H, int I, int act);
 int bzk_mlp_dense(hipStream_t s, const LinearDev& gu, const LinearDev& dn, const void* down_slabs, int H, int I, const Pro& pro, long long* acc, long long* zero_buf, int zero_n);
-bool bzk_mlp_fusable(const LinearDev& gu, const LinearDev& dn, int H, int I);
 int bzk_mlp_q4g(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, int I, const Pro& pro, long long* acc, long long* zero_buf, int zero_n);   // number of workgroups the ROWS kernel uses (argmax partial count)
 int bzk_repack_awq(hipStream_t s, const uint32_t* d_qweight, const float* d_scales, const float* d_zeros, int N, int K, int gs,
                    void* w_out, void* s_out, void* z_out);
@@ -278,19 +276,49 @@ struct AttnArgs {
 // first key a query sees under a window of W keys (W <= 0: none), len = the query's position + 1
 __host__ __device__ __forceinline__ int att_lo(int len, int W) { return W > 0 && len > W ? len - W : 0; }
 int bzk_attn_decode(hipStream_t s, const AttnArgs& a);
-int bzk_attn_oproj_slices(const AttnArgs& a, const LinearDev& L);   // 0: fused form not applicable
 int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long long* acc);
 // long-context path: split-KV partials + merge (see bz_kernels.hip); ws holds bzk_attn_split_ws_bytes(nq) bytes
 int bzk_attn_split_slices(int positions);
-int bzk_attn_split_ok(const AttnArgs& a);
 size_t bzk_attn_split_ws_bytes(int nq);
 int bzk_attn_split(hipStream_t s, const AttnArgs& a, int nsplit, float* ws);
 int bzk_attn_merge(hipStream_t s, const AttnArgs& a, const float* ws, int nsplit);
-int bzk_attn_merge_oproj_ok(const AttnArgs& a, const LinearDev& L);
 int bzk_attn_merge_oproj(hipStream_t s, const AttnArgs& a, const float* ws, int nsplit, const LinearDev& L, long long* acc);
 int bzk_kv_insert(hipStream_t s, const KvView& kv, int layer, const float* k, const float* v, const int* pos, int nkv, int hd);
 int bzk_kv_read(hipStream_t s, const KvView& kv, int layer, int kvh, int which, int len, float* out);
 
+
+// ---------------------------------------------------------------------------------------------------------
+// which kernels a decode step launches (bz_step_plan.hip): the process's switches, every "does form X apply" predicate -- one definition each, which the plan
+// and the launchers' refusals both call -- and the form of one GEMV launch.  They read plain structs: a flag where the device structs hold a pointer.
+// ---------------------------------------------------------------------------------------------------------
+#define XQ_NP 8   // activation planes stored per 32-k chunk (bz_dev.h)
+struct GemvPro { int mode, H, perm, src_fix, aux; };                  // of a Pro
+struct AttnShape { int nq, nkv, hd, kv_dtype, rope_cur, q_only; };     // of an AttnArgs
+enum { OUT_ACC = 0, OUT_DIRECT = 1, OUT_AMAX = 2 };                    // of a GemvOut: fixed-point accumulator, direct f32 store, direct store with argmax partials
+inline bz_linear_traits_t lin_traits(const LinearDev& L) { return bz_linear_traits_t{L.kind, L.N, L.K, L.wdt, L.gw, L.sk, L.npf, L.perm != nullptr, L.bias != nullptr}; }
+inline GemvPro gemv_pro(const Pro& p) { return GemvPro{p.mode, p.H, p.perm != nullptr, p.src.fix, p.aux}; }
+inline AttnShape attn_shape(const AttnArgs& a) { return AttnShape{a.nq, a.nkv, a.hd, a.kv.dtype, a.rope_cur != nullptr, a.q_only}; }
+inline int out_kind(const GemvOut& o) { return o.amax_val ? OUT_AMAX : o.acc ? OUT_ACC : OUT_DIRECT; }
+const bz_step_switches_t* bzk_step_switches();
+size_t bzk_mlp_smem(int H);   // LDS of k_mlp_q4g
+bool bzk_gemv_slim_ok(const bz_linear_traits_t& L, const GemvPro& p, const bz_step_switches_t& sw);
+bool bzk_gq_slim_ok(const bz_linear_traits_t& L, const GemvPro& p, const bz_step_switches_t& sw);
+bool bzk_gq_mix_ok(const bz_linear_traits_t& A, const bz_linear_traits_t& B, const GemvPro& p, const bz_step_switches_t& sw);
+bool bzk_rows2_enabled(const bz_step_switches_t& sw);
+bool bzk_rows2_ok(const bz_linear_traits_t& L, const GemvPro& p, int out, const bz_step_switches_t& sw);
+bool bzk_moe_rows2_ok(int wdt, int K, const bz_step_switches_t& sw);   // the balanced role kernel takes the grouped expert GEMVs (16-bit weights)
+bool bzk_mlp_fusable(const bz_linear_traits_t& gu, const bz_linear_traits_t& dn, int H, int I);   // (+ f16 activations: checked by the callers)
+bool bzk_mlp_dense_fusable(const bz_linear_traits_t& gu, const bz_linear_traits_t& dn, bool down_slabs, int H, int I, int act, const bz_step_switches_t& sw);
+bool bzk_mlp_gq_fusable(const bz_linear_traits_t& gu, const bz_linear_traits_t& dn, int H, int I, int act, const bz_step_switches_t& sw);   // GGUF Q4_K gate/up + Q4_K / Q6_K down, f32 activations
+int bzk_attn_oproj_plan(const AttnShape& a, const bz_linear_traits_t& L, int& NW);   // int4 o_proj: column slices (0: not applicable) and waves
+int bzk_attn2f_oproj_slices(const AttnShape& a, const bz_linear_traits_t& L, const bz_step_switches_t& sw);
+int bzk_attn_dense_oproj_loads(const AttnShape& a, const bz_linear_traits_t& L, const bz_step_switches_t& sw);
+int bzk_attn_oproj_form(const AttnShape& a, const bz_linear_traits_t& L, const bz_step_switches_t& sw);   // BZ_ATTN_FUSED_*, or BZ_ATTN_PLAIN: fused form not applicable
+int bzk_attn_split_ok(const AttnShape& a);
+int bzk_attn_merge_oproj_ok(const AttnShape& a, const bz_linear_traits_t& L);
+int bzk_attn_kernel(const AttnShape& a, const bz_step_switches_t& sw);   // BZ_ATTN_K_*: the kernel behind bzk_attn_decode
+int bzk_att_positions(int positions, int window, int split_min);   // the positions a layer's attention path is sized for (0: the plan's short form)
+int bzk_gemv_form(const bz_linear_traits_t& L, const GemvPro& p, int out, int act, const bz_step_switches_t& sw);   // BZ_GEMV_*: the kernel behind bzk_gemv
 
 // final argmax over partials (or full logits) -> token; optionally advance position and publish token
 struct FinalArgs {
@@ -355,7 +383,6 @@ size_t bzk_mla_smem(const MlaArgs& a, int max_len);   // LDS of the single-pass 
 int bzk_moe_router(hipStream_t s, const Pro& pro, const void* wr, int wdt, int E, int top_k, int n_shared, float routed_scale, int norm_topk,
                    float* xn_out, int* sel, float* wsel, float* lg_glob, unsigned* counter);
 int bzk_moe_combine(hipStream_t s, long long* acc, const float* wsel, int top_k, int has_shared, int H, int act, float* out, long long* zero_buf = nullptr, int zero_n = 0);
-bool bzk_moe_rows2_ok(int wdt, int K);   // the balanced role kernel takes the grouped expert GEMVs (16-bit weights)
 
 // batched prefill for dense 16-bit models (bz_prefill.hip): MFMA GEMM + row-wise norm / RoPE + KV append / causal attention / SiLU*up
 int bzk_gemm_nt(hipStream_t s, int dt, const void* x16, const void* w, const float* bias, int S, int N, int K, int act, float* y, float* ws = nullptr, size_t ws_bytes = 0,

@@ -374,16 +374,9 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_q4g(const uint4* __restrict__ W
 #undef MLP_GU_PARAMS
 }
 
-static size_t mlp_smem(int H) { return (size_t)(H >> 5) * XQ_NP * 16 + (size_t)(H >> 7) * 32 + 16 * 128 * 8 + 2 * XQ_NP * 16 + 32 + 16 * 8 + 64; }   // planes, gpar, part, apl, apar, dred, counters
-
-bool bzk_mlp_fusable(const LinearDev& gu, const LinearDev& dn, int H, int I) {
-  return gu.kind == LK_Q4G && dn.kind == LK_Q4G && !gu.perm && !dn.perm && gu.N == 2 * I && gu.K == H && dn.N == H && dn.K == I &&
-         (H == 2048 || H == 4096) && I % 128 == 0 && mlp_smem(H) <= 64 * 1024;   // (+ f16 activations: checked by the launcher)
-}
-
 int bzk_mlp_q4g(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, int I, const Pro& pro, long long* acc, long long* zero_buf, int zero_n) {
-  if (!bzk_mlp_fusable(gu, dn, H, I) || pro.act != BZ_F16) BZ_FAIL(BZ_E_INVALID, "fused MLP does not apply to this shape / activation dtype");
-  const size_t smem = mlp_smem(H);
+  if (!bzk_mlp_fusable(lin_traits(gu), lin_traits(dn), H, I) || pro.act != BZ_F16) BZ_FAIL(BZ_E_INVALID, "fused MLP does not apply to this shape / activation dtype");
+  const size_t smem = bzk_mlp_smem(H);
   const double bytes = (double)gu.algo_bytes + (double)dn.algo_bytes;
 #define LAUNCH_MLP(FIX, GP, TP, W_) BZ_LAUNCH("mlp_q4g<norm+gate/up+silu+down>", bytes, (k_mlp_q4g<FIX, GP, TP, W_, BZ_F16>), dim3(I / 64), dim3(W_ * 64), smem, s, \
     (const uint4*)gu.w, (const __half*)gu.scales, (const unsigned char*)gu.zeros, gu.bias, (const uint4*)dn.w, (const __half*)dn.scales,            \
@@ -698,12 +691,6 @@ int bzk_gemm_q4g_rows(hipStream_t s, const LinearDev& L, int xdt, const void* x1
   }
   BZ_HIP(hipGetLastError());
   return BZ_OK;
-}
-
-bool bzk_gemv_slim_ok(const LinearDev& L, const Pro& pro) {
-  static const bool off = getenv("BZ_NO_SLIM_QKV") != nullptr;
-  return !off && L.kind == LK_Q4G && !L.perm && pro.mode == PRO_NORM && pro.perm == nullptr && L.K == pro.H && (L.K == 2048 || L.K == 4096 || L.K == 8192) && L.N % 64 == 0 &&
-         L.N <= 16384;
 }
 
 // =========================================================================================================
@@ -1503,16 +1490,8 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_gq(const uint4* __restrict__ Wg
   }
 }
 static size_t mlp_gq_smem(int H) { return (size_t)H * 3 + (size_t)(H >> 5) * 32 + 16 * 128 * 4 + 64 * 4 + 48 * 4 + 64 + 16 * 4 + 16 + 64; }
-bool bzk_mlp_gq_fusable(const LinearDev& gu, const LinearDev& dn, int H, int I, int act) {
-  // opt-in: measured on the Mistral-7B Q4_K_M shape the fused launch takes 31.0 us against ~19 + ~11 us for the two slim launches (535.6 vs 549.0 tok/s, same
-  // box): the block formats cost ~2.5 VALU operations per weight (AND-unpack + three-plane V_DOT4 + a per-32-k epilogue of scale / min arithmetic), ~19 us
-  // of issue per CU when 224 workgroups carry all of it -- the fused form serialises that behind its stream, the slim launches spread it over 256 CUs
-  static const bool on = getenv("BZ_GGUF_MLP_FUSION") != nullptr && getenv("BZ_NO_MLP_FUSION") == nullptr;
-  return on && act == BZ_F32 && gu.kind == LK_Q4K && (dn.kind == LK_Q4K || dn.kind == LK_Q6K) && !gu.perm && !dn.perm && gu.N == 2 * I && gu.K == H && dn.N == H && dn.K == I &&
-         (H == 2048 || H == 4096) && I % 256 == 0 && I % 64 == 0;
-}
 int bzk_mlp_gq(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, int I, const Pro& pro, long long* acc, long long* zero_buf, int zero_n) {
-  if (!bzk_mlp_gq_fusable(gu, dn, H, I, pro.act)) BZ_FAIL(BZ_E_INVALID, "fused GGUF MLP does not apply to this shape");
+  if (!bzk_mlp_gq_fusable(lin_traits(gu), lin_traits(dn), H, I, pro.act, *bzk_step_switches())) BZ_FAIL(BZ_E_INVALID, "fused GGUF MLP does not apply to this shape");
   const size_t smem = mlp_gq_smem(H);
   const double bytes = (double)gu.algo_bytes + (double)dn.algo_bytes;
 #define LAUNCH_MGQ(FD, FIX, NW_, TP) BZ_LAUNCH("mlp_gguf<norm+gate/up+silu+down>", bytes, (k_mlp_gq<FD, FIX, NW_, TP>), dim3(I / 64), dim3(NW_ * 64), smem, s, (const uint4*)gu.w, \
@@ -1526,22 +1505,9 @@ int bzk_mlp_gq(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, i
   return BZ_OK;
 }
 
-bool bzk_gq_slim_ok(const LinearDev& L, const Pro& pro) {
-  static const bool off = getenv("BZ_NO_GQ_SLIM") != nullptr;
-  const bool kind_ok = L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K || L.kind == LK_Q40 || L.kind == LK_Q41 || L.kind == LK_Q50 || L.kind == LK_Q51;
-  if (off || !kind_ok || pro.perm != nullptr || L.N % 64 || L.K % 256) return false;
-  if (pro.mode == PRO_NORM) return L.K == pro.H && (L.K == 2048 || L.K == 4096 || L.K == 8192);
-  if (pro.mode == PRO_SILU) return L.K == pro.H;
-  return false;
-}
-
-
-// Q4_K tiles followed by Q6_K tiles (one K, one prologue) in ONE slim launch: the Q4_K_M rule stores q / k as Q4_K and v as Q6_K, which made q/k/v two launches
-bool bzk_gq_mix_ok(const LinearDev& A, const LinearDev& B, const Pro& pro) {
-  return A.kind == LK_Q4K && B.kind == LK_Q6K && A.K == B.K && !A.bias && !B.bias && pro.mode == PRO_NORM && bzk_gq_slim_ok(A, pro) && bzk_gq_slim_ok(B, pro);
-}
+// Q4_K tiles followed by Q6_K tiles (one K, one prologue) in ONE slim launch (bzk_gq_mix_ok)
 int bzk_gemv_gq_mix(hipStream_t s, const LinearDev& A, const LinearDev& B, const Pro& pro, const GemvOut& out) {
-  if (!bzk_gq_mix_ok(A, B, pro) || !out.acc) BZ_FAIL(BZ_E_INVALID, "mixed Q4_K / Q6_K slim launch does not apply");
+  if (!bzk_gq_mix_ok(lin_traits(A), lin_traits(B), gemv_pro(pro), *bzk_step_switches()) || !out.acc) BZ_FAIL(BZ_E_INVALID, "mixed Q4_K / Q6_K slim launch does not apply");
   const int N = A.N + B.N, K = A.K, nsb = K / 256, ntg = (N / 64 + 7) / 8;
   const GqMix mix{(const uint4*)B.w, (const uint2*)B.zeros, (const uint4*)B.hdr, (const __half*)B.scales, A.N / 64};
   const double bytes = (double)A.algo_bytes + (double)B.algo_bytes;
@@ -2234,13 +2200,9 @@ __global__ __launch_bounds__(768) void k_mlp_dense(const void* __restrict__ Wgu,
   }
 }
 
-bool bzk_mlp_dense_fusable(const LinearDev& gu, const LinearDev& dn, const void* down_slabs, int H, int I, int act) {
-  static const bool off = getenv("BZ_NO_MLP_FUSION") != nullptr;
-  return !off && down_slabs != nullptr && gu.kind == LK_ROWS && dn.kind == LK_ROWS && gu.wdt == dn.wdt && (gu.wdt == BZ_F16 || gu.wdt == BZ_BF16) && gu.N == 2 * I &&
-         gu.K == H && dn.N == H && dn.K == I && H % 512 == 0 && H >= 1024 && H <= 2048 && I % 32 == 0 && I / 32 >= 128 && gu.sk > 1 && dn.sk > 1 && (act == BZ_F16 || act == BZ_BF16 || act == BZ_F32);
-}
 int bzk_mlp_dense(hipStream_t s, const LinearDev& gu, const LinearDev& dn, const void* down_slabs, int H, int I, const Pro& pro, long long* acc, long long* zero_buf, int zero_n) {
-  if (!bzk_mlp_dense_fusable(gu, dn, down_slabs, H, I, pro.act) || pro.mode != PRO_NORM || pro.H != H) BZ_FAIL(BZ_E_INVALID, "dense fused MLP does not apply to this shape");
+  if (!bzk_mlp_dense_fusable(lin_traits(gu), lin_traits(dn), down_slabs != nullptr, H, I, pro.act, *bzk_step_switches()) || pro.mode != PRO_NORM || pro.H != H)
+    BZ_FAIL(BZ_E_INVALID, "dense fused MLP does not apply to this shape");
   const size_t smem = (size_t)H * 4 + 32 * 4 + 4 * 8 + 64;
   const double bytes = (double)gu.algo_bytes + (double)dn.algo_bytes;
 #define LAUNCH_MD(DT, FX) BZ_LAUNCH("mlp_dense<norm+gate/up+silu+down>", bytes, (k_mlp_dense<DT, FX>), dim3(I / 32), dim3(768), smem, s, gu.w, gu.bias, down_slabs, dn.bias, H, I, pro, \
@@ -2273,26 +2235,16 @@ static int rows_per_wg_for(int N) {
   while (r < 256 && (N + r - 1) / r > 1024) r <<= 1;
   return r;
 }
-static bool rows2_enabled() { static const bool off = getenv("BZ_NO_ROWS2") != nullptr; return !off; }
 // split count for a dense [N,K] GEMV: enough (16-row x K-slice) workgroups to fill the chip when N alone is too small
 int bzk_rows_choose_sk(int N, int K) {
   const int rbs = (N + 15) / 16, KC = (K + 511) / 512;
-  if (rows2_enabled() && K % 8 == 0 && K <= 131072) {   // fixed-point output whatever the shape: k_gemv_rows2 balances any [N, K] over the chip
+  if (bzk_rows2_enabled(*bzk_step_switches()) && K % 8 == 0 && K <= 131072) {   // fixed-point output whatever the shape: k_gemv_rows2 balances any [N, K] over the chip
     if (rbs >= 512 || KC < 8) return 2;                // (the value only matters to the fallback kernel)
   } else if (rbs >= 512 || KC < 8) return 1;
   int sk = std::min((512 + rbs - 1) / rbs, KC / 4);   // a slice keeps >= 4 chunks (2048 k): below that the prologue dominates
   const int kcs = (KC + sk - 1) / sk;
   sk = (KC + kcs - 1) / kcs;
   return sk;
-}
-// the balanced role kernel (k_gemv_rows2) takes every fixed-point-output dense GEMV with 16-bit weights
-static bool bzk_rows2_ok(const LinearDev& L, const Pro& pro, const GemvOut& out) {
-  if (!rows2_enabled() || L.kind != LK_ROWS || L.sk <= 1 || !out.acc || out.amax_val) return false;
-  if (L.wdt != BZ_F16 && L.wdt != BZ_BF16) return false;
-  if (L.K % 8 || L.K > 131072 || pro.perm) return false;
-  if (pro.mode == PRO_NORM) return pro.H == L.K && pro.H % 8 == 0;
-  if (pro.mode == PRO_GATED2) return !pro.src.fix && (pro.aux <= 8) && pro.H == L.K && (pro.H / (pro.aux > 0 ? pro.aux : 1)) % 4 == 0;
-  return pro.mode == PRO_PLAIN || pro.mode == PRO_SILU;
 }
 int bzk_gemv_rows_blocks(const LinearDev& L) { int r = rows_per_wg_for(L.N); return (L.N + r - 1) / r; }
 
@@ -2568,132 +2520,141 @@ int bzk_gq_split3(hipStream_t s, const LinearDev& L, const float* wscale, void* 
 // partial argmax over a plain f32 vector (quantised lm_head path): nb blocks -> pval/pidx
 int bzk_argmax_partials(hipStream_t s, const float* v, long long n, float* pval, int* pidx, int nb);
 
-int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act) {
-  if (L.kind == LK_F8) return bzk_gemv_f8(s, L, pro, out, act);   // bz_fp8.hip
-  if (L.kind == LK_Q4G && act == BZ_F16 && bzk_gemv_slim_ok(L, pro)) {
-    if (!out.acc) BZ_FAIL(BZ_E_INVALID, "int4 gemv needs a fixed-point accumulator");
-    const int nks = L.K / 256, ntg = (L.N / 64 + 7) / 8;
+// the launchers of bzk_gemv, one per BZ_GEMV_* form (bzk_gemv_form, bz_step_plan.hip)
+static int gemv_q4g_slim(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act) {
+  if (!out.acc) BZ_FAIL(BZ_E_INVALID, "int4 gemv needs a fixed-point accumulator");
+  const int nks = L.K / 256, ntg = (L.N / 64 + 7) / 8;
 #define LAUNCH_SLIM(FIX, NJ) BZ_LAUNCH("gemv_q4g<norm>", L.algo_bytes, (k_gemv_q4g_slim<FIX, NJ, BZ_F16>), dim3(nks * ntg), dim3(768), 0, s, (const uint4*)L.w, \
-    (const __half*)L.scales, (const unsigned char*)L.zeros, L.N, L.K, pro, out.acc, out.zero_buf, out.zero_n)
+  (const __half*)L.scales, (const unsigned char*)L.zeros, L.N, L.K, pro, out.acc, out.zero_buf, out.zero_n)
 #define LAUNCH_SLIM_NJ(FIX) do { if (L.K == 2048) LAUNCH_SLIM(FIX, 1); else if (L.K == 4096) LAUNCH_SLIM(FIX, 2); else LAUNCH_SLIM(FIX, 4); } while (0)
-    if (pro.src.fix) LAUNCH_SLIM_NJ(1); else LAUNCH_SLIM_NJ(0);
+  if (pro.src.fix) LAUNCH_SLIM_NJ(1); else LAUNCH_SLIM_NJ(0);
 #undef LAUNCH_SLIM_NJ
 #undef LAUNCH_SLIM
-    BZ_HIP(hipGetLastError());
-    return bzk_fix_bias(s, out.acc, L.bias, L.N, act);
-  }
-  if (L.kind == LK_Q4G) {
-    if (!out.acc) BZ_FAIL(BZ_E_INVALID, "q4g gemv needs a fixed-point accumulator");
-    const int G = L.K / 128, GW = L.gw;
-    const int nst = (L.N + 255) / 256;
-    const int grid = nst * (G / GW);
-    const size_t smem = q4g_smem(GW);
-    const int maxj = pro.mode == PRO_NORM ? (pro.H + 1023) / 1024 : 1;
-    if (GW > 16) BZ_FAIL(BZ_E_INVALID, "q4g gemv: %d groups per workgroup (max 16)", GW);
+  BZ_HIP(hipGetLastError());
+  return bzk_fix_bias(s, out.acc, L.bias, L.N, act);
+}
+static int gemv_q4g(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act) {
+  if (!out.acc) BZ_FAIL(BZ_E_INVALID, "q4g gemv needs a fixed-point accumulator");
+  const int G = L.K / 128, GW = L.gw;
+  const int nst = (L.N + 255) / 256;
+  const int grid = nst * (G / GW);
+  const size_t smem = q4g_smem(GW);
+  const int maxj = pro.mode == PRO_NORM ? (pro.H + 1023) / 1024 : 1;
+  if (GW > 16) BZ_FAIL(BZ_E_INVALID, "q4g gemv: %d groups per workgroup (max 16)", GW);
 #define LAUNCH_Q4G(MODE, FIX, MJ, NPF) BZ_LAUNCH(MODE == PRO_NORM ? "gemv_q4g<norm>" : (MODE == PRO_SILU ? "gemv_q4g<silu>" : "gemv_q4g<plain>"), \
-    L.algo_bytes, (k_gemv_q4g<MODE, FIX, MJ, NPF>), dim3(grid), dim3(256), smem, s, (const uint4*)L.w,                      \
-    (const __half*)L.scales, (const unsigned char*)L.zeros, L.N, L.K, GW, nst, pro, out.acc, out.zero_buf, out.zero_n)
+  L.algo_bytes, (k_gemv_q4g<MODE, FIX, MJ, NPF>), dim3(grid), dim3(256), smem, s, (const uint4*)L.w,                      \
+  (const __half*)L.scales, (const unsigned char*)L.zeros, L.N, L.K, GW, nst, pro, out.acc, out.zero_buf, out.zero_n)
 #define LAUNCH_Q4G_N(MODE, FIX, MJ) do { if (GW == 1) LAUNCH_Q4G(MODE, FIX, MJ, 1); else if (L.npf >= 4 && GW >= 4) LAUNCH_Q4G(MODE, FIX, MJ, 4); \
-                                          else LAUNCH_Q4G(MODE, FIX, MJ, 2); } while (0)
+                                        else LAUNCH_Q4G(MODE, FIX, MJ, 2); } while (0)
 #define LAUNCH_Q4G_F(MODE, MJ) do { if (pro.src.fix) LAUNCH_Q4G_N(MODE, 1, MJ); else LAUNCH_Q4G_N(MODE, 0, MJ); } while (0)
-    if (pro.mode == PRO_PLAIN) LAUNCH_Q4G_F(PRO_PLAIN, 1);
-    else if (pro.mode == PRO_SILU) LAUNCH_Q4G_F(PRO_SILU, 1);
-    else if (maxj <= 1) LAUNCH_Q4G_F(PRO_NORM, 1);
-    else if (maxj <= 2) LAUNCH_Q4G_F(PRO_NORM, 2);
-    else if (maxj <= 4) LAUNCH_Q4G_F(PRO_NORM, 4);
-    else if (maxj <= 8) LAUNCH_Q4G_F(PRO_NORM, 8);
-    else BZ_FAIL(BZ_E_UNSUPPORTED, "hidden size %d too large for the fused norm prologue", pro.H);
+  if (pro.mode == PRO_PLAIN) LAUNCH_Q4G_F(PRO_PLAIN, 1);
+  else if (pro.mode == PRO_SILU) LAUNCH_Q4G_F(PRO_SILU, 1);
+  else if (maxj <= 1) LAUNCH_Q4G_F(PRO_NORM, 1);
+  else if (maxj <= 2) LAUNCH_Q4G_F(PRO_NORM, 2);
+  else if (maxj <= 4) LAUNCH_Q4G_F(PRO_NORM, 4);
+  else if (maxj <= 8) LAUNCH_Q4G_F(PRO_NORM, 8);
+  else BZ_FAIL(BZ_E_UNSUPPORTED, "hidden size %d too large for the fused norm prologue", pro.H);
 #undef LAUNCH_Q4G_N
 #undef LAUNCH_Q4G_F
 #undef LAUNCH_Q4G
-    BZ_HIP(hipGetLastError());
-    return bzk_fix_bias(s, out.acc, L.bias, L.N, act);
-  }
-  if (L.kind == LK_ROWS && bzk_rows2_ok(L, pro, out)) {
-    const long long U = (long long)((L.N + 3) / 4) * ((L.K + 511) / 512);
-    const int KC = (L.K + 511) / 512;
-    const int nb = (int)std::max<long long>(std::min<long long>(256, U), KC);   // one workgroup per CU; a range lies in <= 2 chunks when nb >= K / 512
-    const char* lbl = pro.mode == PRO_NORM ? "gemv_rows2<norm>" : pro.mode == PRO_GATED2 ? "gemv_rows2<gated>" : pro.mode == PRO_SILU ? "gemv_rows2<silu>" : "gemv_rows2";
+  BZ_HIP(hipGetLastError());
+  return bzk_fix_bias(s, out.acc, L.bias, L.N, act);
+}
+static int gemv_rows2(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out) {
+  const long long U = (long long)((L.N + 3) / 4) * ((L.K + 511) / 512);
+  const int KC = (L.K + 511) / 512;
+  const int nb = (int)std::max<long long>(std::min<long long>(256, U), KC);   // one workgroup per CU; a range lies in <= 2 chunks when nb >= K / 512
+  const char* lbl = pro.mode == PRO_NORM ? "gemv_rows2<norm>" : pro.mode == PRO_GATED2 ? "gemv_rows2<gated>" : pro.mode == PRO_SILU ? "gemv_rows2<silu>" : "gemv_rows2";
 #define LAUNCH_R2(DT, MODE, FIX) do { if (pro.f32_sums) LAUNCH_R2X(DT, MODE, FIX, false); else LAUNCH_R2X(DT, MODE, FIX, true); } while (0)
 #define LAUNCH_R2X(DT, MODE, FIX, EX_) BZ_LAUNCH(lbl, L.algo_bytes, (k_gemv_rows2<DT, MODE, FIX, 0, EX_>), dim3(nb), dim3(768), 0, s, (const void*)L.w, L.bias, L.N, L.K, pro, \
-    out.acc, out.zero_buf, out.zero_n, out.shift, MoeSlots{nullptr, 0, 1, 0, 0, 1}, RouteArgs{})
+  out.acc, out.zero_buf, out.zero_n, out.shift, MoeSlots{nullptr, 0, 1, 0, 0, 1}, RouteArgs{})
 #define LAUNCH_R2_F(DT, MODE) do { if (pro.src.fix) LAUNCH_R2(DT, MODE, true); else LAUNCH_R2(DT, MODE, false); } while (0)
 #define LAUNCH_R2_M(DT) do { if (pro.mode == PRO_NORM) LAUNCH_R2_F(DT, PRO_NORM); else if (pro.mode == PRO_SILU) LAUNCH_R2_F(DT, PRO_SILU); \
-    else if (pro.mode == PRO_GATED2) LAUNCH_R2(DT, PRO_GATED2, false); else LAUNCH_R2_F(DT, PRO_PLAIN); } while (0)
-    if (L.wdt == BZ_F16) LAUNCH_R2_M(BZ_F16); else LAUNCH_R2_M(BZ_BF16);
+  else if (pro.mode == PRO_GATED2) LAUNCH_R2(DT, PRO_GATED2, false); else LAUNCH_R2_F(DT, PRO_PLAIN); } while (0)
+  if (L.wdt == BZ_F16) LAUNCH_R2_M(BZ_F16); else LAUNCH_R2_M(BZ_BF16);
 #undef LAUNCH_R2_M
 #undef LAUNCH_R2_F
 #undef LAUNCH_R2
 #undef LAUNCH_R2X
-    BZ_HIP(hipGetLastError());
-    return BZ_OK;
-  }
-  if (L.kind == LK_ROWS) {
-    const int SK = L.sk > 1 ? L.sk : 1;
-    if (out.shift.cs) { hipLaunchKernelGGL(k_conv_shift, dim3((out.shift.n + 255) / 256), dim3(256), 0, s, out.shift, act); BZ_HIP(hipGetLastError()); }   // (k_gemv_rows2 does it in-launch)
-    if (SK == 1 && !out.direct) BZ_FAIL(BZ_E_INVALID, "rows gemv needs a direct output");
-    if (SK > 1 && (!out.acc || out.amax_val)) BZ_FAIL(BZ_E_INVALID, "split-K rows gemv needs a fixed-point accumulator");
-    const int rpw = SK > 1 ? 16 : rows_per_wg_for(L.N);
-    const int grid = ((L.N + rpw - 1) / rpw) * SK;
-    const int KP = (L.K + 511) & ~511;
-    const size_t smem = (size_t)KP * 4 + 64;
-    if (smem > 160 * 1024) BZ_FAIL(BZ_E_UNSUPPORTED, "K=%d too large for the rows GEMV", L.K);
-    const char* lbl = out.amax_val ? "gemv_rows<lm_head+argmax>" : pro.mode == PRO_NORM ? "gemv_rows<norm>" : (pro.mode == PRO_GATED || pro.mode == PRO_GATED2) ? "gemv_rows<gated>"
-                      : pro.mode == PRO_SILU ? "gemv_rows<silu>" : "gemv_rows";
+  BZ_HIP(hipGetLastError());
+  return BZ_OK;
+}
+static int gemv_rows(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act) {
+  const int SK = L.sk > 1 ? L.sk : 1;
+  if (out.shift.cs) { hipLaunchKernelGGL(k_conv_shift, dim3((out.shift.n + 255) / 256), dim3(256), 0, s, out.shift, act); BZ_HIP(hipGetLastError()); }   // (k_gemv_rows2 does it in-launch)
+  if (SK == 1 && !out.direct) BZ_FAIL(BZ_E_INVALID, "rows gemv needs a direct output");
+  if (SK > 1 && (!out.acc || out.amax_val)) BZ_FAIL(BZ_E_INVALID, "split-K rows gemv needs a fixed-point accumulator");
+  const int rpw = SK > 1 ? 16 : rows_per_wg_for(L.N);
+  const int grid = ((L.N + rpw - 1) / rpw) * SK;
+  const int KP = (L.K + 511) & ~511;
+  const size_t smem = (size_t)KP * 4 + 64;
+  if (smem > 160 * 1024) BZ_FAIL(BZ_E_UNSUPPORTED, "K=%d too large for the rows GEMV", L.K);
+  const char* lbl = out.amax_val ? "gemv_rows<lm_head+argmax>" : pro.mode == PRO_NORM ? "gemv_rows<norm>" : (pro.mode == PRO_GATED || pro.mode == PRO_GATED2) ? "gemv_rows<gated>"
+                    : pro.mode == PRO_SILU ? "gemv_rows<silu>" : "gemv_rows";
 #define LAUNCH_ROWS1(DT, SP) BZ_LAUNCH(lbl, L.algo_bytes, (k_gemv_rows<DT, SP>), dim3(grid), \
-    dim3(256), smem, s, (const void*)L.w, L.bias, L.N, L.K, rpw, pro, out.direct, act, out.amax_val, out.amax_idx, out.zero_buf, out.zero_n, SK, out.acc)
+  dim3(256), smem, s, (const void*)L.w, L.bias, L.N, L.K, rpw, pro, out.direct, act, out.amax_val, out.amax_idx, out.zero_buf, out.zero_n, SK, out.acc)
 #define LAUNCH_ROWS(DT) do { if (SK > 1) LAUNCH_ROWS1(DT, true); else LAUNCH_ROWS1(DT, false); } while (0)
-    if (L.wdt == BZ_F16) LAUNCH_ROWS(BZ_F16); else if (L.wdt == BZ_BF16) LAUNCH_ROWS(BZ_BF16); else LAUNCH_ROWS(BZ_F32);
+  if (L.wdt == BZ_F16) LAUNCH_ROWS(BZ_F16); else if (L.wdt == BZ_BF16) LAUNCH_ROWS(BZ_BF16); else LAUNCH_ROWS(BZ_F32);
 #undef LAUNCH_ROWS
 #undef LAUNCH_ROWS1
-    BZ_HIP(hipGetLastError());
-    return BZ_OK;
-  }
-  if (bzk_gq_slim_ok(L, pro)) {
-    if (!out.acc) BZ_FAIL(BZ_E_INVALID, "block-quant gemv needs a fixed-point accumulator");
-    const int nsb = L.K / 256, ntg = (L.N / 64 + 7) / 8;
-    const char* label = L.kind == LK_Q4K ? "gemv_q4_K<slim>" : L.kind == LK_Q5K ? "gemv_q5_K<slim>" : L.kind == LK_Q6K ? "gemv_q6_K<slim>"
-                      : L.kind == LK_Q40 ? "gemv_q4_0<slim>" : L.kind == LK_Q41 ? "gemv_q4_1<slim>" : L.kind == LK_Q50 ? "gemv_q5_0<slim>" : "gemv_q5_1<slim>";
+  BZ_HIP(hipGetLastError());
+  return BZ_OK;
+}
+static int gemv_gq_slim(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out) {
+  if (!out.acc) BZ_FAIL(BZ_E_INVALID, "block-quant gemv needs a fixed-point accumulator");
+  const int nsb = L.K / 256, ntg = (L.N / 64 + 7) / 8;
+  const char* label = L.kind == LK_Q4K ? "gemv_q4_K<slim>" : L.kind == LK_Q5K ? "gemv_q5_K<slim>" : L.kind == LK_Q6K ? "gemv_q6_K<slim>"
+                    : L.kind == LK_Q40 ? "gemv_q4_0<slim>" : L.kind == LK_Q41 ? "gemv_q4_1<slim>" : L.kind == LK_Q50 ? "gemv_q5_0<slim>" : "gemv_q5_1<slim>";
 #define LAUNCH_GQS(FMT, MODE, FIX, NJ) BZ_LAUNCH(label, L.algo_bytes, (k_gemv_gq_slim<FMT, MODE, FIX, NJ>), dim3(nsb * ntg), dim3(512), 0, s, (const uint4*)L.w, \
-    (const uint2*)L.zeros, (const uint4*)L.hdr, (const __half*)L.scales, L.bias, L.N, L.K, pro, out.acc, out.zero_buf, out.zero_n, GqMix{})
+  (const uint2*)L.zeros, (const uint4*)L.hdr, (const __half*)L.scales, L.bias, L.N, L.K, pro, out.acc, out.zero_buf, out.zero_n, GqMix{})
 #define LAUNCH_GQS_NJ(FMT, FIX) do { if (pro.mode == PRO_SILU) LAUNCH_GQS(FMT, PRO_SILU, FIX, 1); else if (L.K == 2048) LAUNCH_GQS(FMT, PRO_NORM, FIX, 1); \
-    else if (L.K == 4096) LAUNCH_GQS(FMT, PRO_NORM, FIX, 2); else LAUNCH_GQS(FMT, PRO_NORM, FIX, 4); } while (0)
+  else if (L.K == 4096) LAUNCH_GQS(FMT, PRO_NORM, FIX, 2); else LAUNCH_GQS(FMT, PRO_NORM, FIX, 4); } while (0)
 #define LAUNCH_GQS_F(FMT) do { if (pro.src.fix) LAUNCH_GQS_NJ(FMT, 1); else LAUNCH_GQS_NJ(FMT, 0); } while (0)
-    if (L.kind == LK_Q4K) LAUNCH_GQS_F(GQ_Q4K); else if (L.kind == LK_Q5K) LAUNCH_GQS_F(GQ_Q5K); else if (L.kind == LK_Q6K) LAUNCH_GQS_F(GQ_Q6K);
-    else if (L.kind == LK_Q40) LAUNCH_GQS_F(GQ_Q40); else if (L.kind == LK_Q41) LAUNCH_GQS_F(GQ_Q41); else if (L.kind == LK_Q50) LAUNCH_GQS_F(GQ_Q50);
-    else LAUNCH_GQS_F(GQ_Q51);
+  if (L.kind == LK_Q4K) LAUNCH_GQS_F(GQ_Q4K); else if (L.kind == LK_Q5K) LAUNCH_GQS_F(GQ_Q5K); else if (L.kind == LK_Q6K) LAUNCH_GQS_F(GQ_Q6K);
+  else if (L.kind == LK_Q40) LAUNCH_GQS_F(GQ_Q40); else if (L.kind == LK_Q41) LAUNCH_GQS_F(GQ_Q41); else if (L.kind == LK_Q50) LAUNCH_GQS_F(GQ_Q50);
+  else LAUNCH_GQS_F(GQ_Q51);
 #undef LAUNCH_GQS_F
 #undef LAUNCH_GQS_NJ
 #undef LAUNCH_GQS
-    BZ_HIP(hipGetLastError());
-    return BZ_OK;
-  }
-  if (L.kind == LK_Q80 || L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K || L.kind == LK_Q40 || L.kind == LK_Q41 || L.kind == LK_Q50 || L.kind == LK_Q51) {
-    if (!out.acc) BZ_FAIL(BZ_E_INVALID, "block-quant gemv needs a fixed-point accumulator");
-    const int SB = L.K / 256, SBW = L.gw;
-    if (SBW <= 0 || SB % SBW || SBW > 8) BZ_FAIL(BZ_E_INVALID, "block-quant gemv: bad k-slice %d of %d superblocks", SBW, SB);
-    const int nst = (L.N + 255) / 256;
-    const int grid = nst * (SB / SBW);
-    const size_t smem = gq_smem(SBW);
-    const int maxj = pro.mode == PRO_NORM ? (pro.H + 1023) / 1024 : 1;
-    const char* label = L.kind == LK_Q80 ? "gemv_q8_0" : L.kind == LK_Q4K ? "gemv_q4_K" : L.kind == LK_Q5K ? "gemv_q5_K" : L.kind == LK_Q6K ? "gemv_q6_K"
-                      : L.kind == LK_Q40 ? "gemv_q4_0" : L.kind == LK_Q41 ? "gemv_q4_1" : L.kind == LK_Q50 ? "gemv_q5_0" : "gemv_q5_1";
+  BZ_HIP(hipGetLastError());
+  return BZ_OK;
+}
+static int gemv_gq(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out) {
+  if (!out.acc) BZ_FAIL(BZ_E_INVALID, "block-quant gemv needs a fixed-point accumulator");
+  const int SB = L.K / 256, SBW = L.gw;
+  if (SBW <= 0 || SB % SBW || SBW > 8) BZ_FAIL(BZ_E_INVALID, "block-quant gemv: bad k-slice %d of %d superblocks", SBW, SB);
+  const int nst = (L.N + 255) / 256;
+  const int grid = nst * (SB / SBW);
+  const size_t smem = gq_smem(SBW);
+  const int maxj = pro.mode == PRO_NORM ? (pro.H + 1023) / 1024 : 1;
+  const char* label = L.kind == LK_Q80 ? "gemv_q8_0" : L.kind == LK_Q4K ? "gemv_q4_K" : L.kind == LK_Q5K ? "gemv_q5_K" : L.kind == LK_Q6K ? "gemv_q6_K"
+                    : L.kind == LK_Q40 ? "gemv_q4_0" : L.kind == LK_Q41 ? "gemv_q4_1" : L.kind == LK_Q50 ? "gemv_q5_0" : "gemv_q5_1";
 #define LAUNCH_GQ(FMT, MODE, FIX, MJ) BZ_LAUNCH(label, L.algo_bytes, (k_gemv_gq<FMT, MODE, FIX, MJ>), dim3(grid), dim3(256), smem, s, (const uint4*)L.w, \
-    (const uint2*)L.zeros, (const uint4*)L.hdr, (const __half*)L.scales, L.bias, L.N, L.K, SBW, nst, pro, out.acc, out.zero_buf, out.zero_n)
+  (const uint2*)L.zeros, (const uint4*)L.hdr, (const __half*)L.scales, L.bias, L.N, L.K, SBW, nst, pro, out.acc, out.zero_buf, out.zero_n)
 #define LAUNCH_GQ_F(FMT, MODE, MJ) do { if (pro.src.fix) LAUNCH_GQ(FMT, MODE, 1, MJ); else LAUNCH_GQ(FMT, MODE, 0, MJ); } while (0)
 #define LAUNCH_GQ_M(FMT) do { if (pro.mode == PRO_PLAIN) LAUNCH_GQ_F(FMT, PRO_PLAIN, 1); else if (pro.mode == PRO_SILU) LAUNCH_GQ_F(FMT, PRO_SILU, 1); \
-    else if (maxj <= 1) LAUNCH_GQ_F(FMT, PRO_NORM, 1); else if (maxj <= 2) LAUNCH_GQ_F(FMT, PRO_NORM, 2); else if (maxj <= 4) LAUNCH_GQ_F(FMT, PRO_NORM, 4); \
-    else if (maxj <= 8) LAUNCH_GQ_F(FMT, PRO_NORM, 8); else BZ_FAIL(BZ_E_UNSUPPORTED, "hidden size %d too large for the fused norm prologue", pro.H); } while (0)
-    if (L.kind == LK_Q80) LAUNCH_GQ_M(GQ_Q80); else if (L.kind == LK_Q4K) LAUNCH_GQ_M(GQ_Q4K); else if (L.kind == LK_Q5K) LAUNCH_GQ_M(GQ_Q5K);
-    else if (L.kind == LK_Q6K) LAUNCH_GQ_M(GQ_Q6K); else if (L.kind == LK_Q40) LAUNCH_GQ_M(GQ_Q40); else if (L.kind == LK_Q41) LAUNCH_GQ_M(GQ_Q41);
-    else if (L.kind == LK_Q50) LAUNCH_GQ_M(GQ_Q50); else LAUNCH_GQ_M(GQ_Q51);
+  else if (maxj <= 1) LAUNCH_GQ_F(FMT, PRO_NORM, 1); else if (maxj <= 2) LAUNCH_GQ_F(FMT, PRO_NORM, 2); else if (maxj <= 4) LAUNCH_GQ_F(FMT, PRO_NORM, 4); \
+  else if (maxj <= 8) LAUNCH_GQ_F(FMT, PRO_NORM, 8); else BZ_FAIL(BZ_E_UNSUPPORTED, "hidden size %d too large for the fused norm prologue", pro.H); } while (0)
+  if (L.kind == LK_Q80) LAUNCH_GQ_M(GQ_Q80); else if (L.kind == LK_Q4K) LAUNCH_GQ_M(GQ_Q4K); else if (L.kind == LK_Q5K) LAUNCH_GQ_M(GQ_Q5K);
+  else if (L.kind == LK_Q6K) LAUNCH_GQ_M(GQ_Q6K); else if (L.kind == LK_Q40) LAUNCH_GQ_M(GQ_Q40); else if (L.kind == LK_Q41) LAUNCH_GQ_M(GQ_Q41);
+  else if (L.kind == LK_Q50) LAUNCH_GQ_M(GQ_Q50); else LAUNCH_GQ_M(GQ_Q51);
 #undef LAUNCH_GQ_M
 #undef LAUNCH_GQ_F
 #undef LAUNCH_GQ
-    BZ_HIP(hipGetLastError());
-    return BZ_OK;
+  BZ_HIP(hipGetLastError());
+  return BZ_OK;
+}
+int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act) {
+  switch (bzk_gemv_form(lin_traits(L), gemv_pro(pro), out_kind(out), act, *bzk_step_switches())) {
+    case BZ_GEMV_F8: return bzk_gemv_f8(s, L, pro, out, act);   // bz_fp8.hip
+    case BZ_GEMV_Q4G_SLIM: return gemv_q4g_slim(s, L, pro, out, act);
+    case BZ_GEMV_Q4G: return gemv_q4g(s, L, pro, out, act);
+    case BZ_GEMV_ROWS2: return gemv_rows2(s, L, pro, out);
+    case BZ_GEMV_ROWS: return gemv_rows(s, L, pro, out, act);
+    case BZ_GEMV_GQ_SLIM: return gemv_gq_slim(s, L, pro, out);
+    case BZ_GEMV_GQ: return gemv_gq(s, L, pro, out);
+    default: BZ_FAIL(BZ_E_UNSUPPORTED, "gemv: linear kind %d not implemented", L.kind);
   }
-  BZ_FAIL(BZ_E_UNSUPPORTED, "gemv: linear kind %d not implemented", L.kind);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -3619,46 +3580,15 @@ __global__ __launch_bounds__(512) void k_attn2f(AttnArgs a, const uint4* __restr
 
 static size_t attn2_smem(int nw) { return (size_t)(64 * 3 + 2 * nw + 128 + 4 * XQ_NP * 4 + 8) * 4 + (size_t)(nw * 128 + nw) * 8; }
 
-// picks the column-slice count so that nq * CS ~ 256 workgroups, and the wave count (8 waves halve the per-wave attention chain);
-// returns 0 when the fused form does not apply
-static int attn_oproj_plan(const AttnArgs& a, const LinearDev& L, int& NW) {
-  NW = 0;
-  if (a.hd != 128 || L.kind != LK_Q4G || L.perm != nullptr || L.K != a.nq * 128 || a.q_only) return 0;
-  const int NT = L.N / 64;
-  for (int nw = 8; nw >= 4; nw >>= 1) {
-    const int ow = nw > 8 ? 8 : nw;
-    for (int cs = 8; cs >= 1; cs >>= 1)
-      if (NT % (cs * ow) == 0 && NT / (cs * ow) <= 2 && a.nq * cs <= 1024) { NW = nw; return cs; }
-  }
-  return 0;
-}
-// the f32-cache form (GGUF models): Q4_K o_proj, one tile per wave, CS = N / 512 column slices; single-launch contexts only (no split-KV path for the f32 cache)
-static int attn2f_oproj_slices(const AttnArgs& a, const LinearDev& L) {
-  static const bool off = getenv("BZ_NO_ATTN_F32") != nullptr;
-  if (off || a.hd != 128 || a.kv.dtype != BZ_F32 || a.rope_cur == nullptr || a.q_only || L.kind != LK_Q4K || L.K != a.nq * 128 || L.N % 512 || L.K % 256) return 0;
-  const int cs = L.N / 512;
-  return a.nq * cs <= 2048 ? cs : 0;
-}
-// dense 16-bit o_proj in the cache dtype (Llama-3.2-1B: head_dim 64, N 2048): 8 column slices, RPL rows per wave-wide load, 1..4 loads per wave
-static int attn_dense_oproj_loads(const AttnArgs& a, const LinearDev& L) {
-  static const bool off = getenv("BZ_NO_ATTN2_HD64") != nullptr;
-  if (off || L.kind != LK_ROWS || L.wdt != a.kv.dtype || (a.kv.dtype != BZ_F16 && a.kv.dtype != BZ_BF16) || (a.hd != 64 && a.hd != 128) || a.q_only || a.rope_cur == nullptr) return 0;
-  if (L.K != a.nq * a.hd || a.nq * 8 > 2048) return 0;
-  const int rpl = 512 / a.hd, per_wave = L.N / 64;          // 8 slices x 8 waves
-  if (L.N % 64 || per_wave % rpl) return 0;
-  const int loads = per_wave / rpl;
-  return (loads == 1 || loads == 2 || loads == 4) ? loads : 0;
-}
-int bzk_attn_oproj_slices(const AttnArgs& a, const LinearDev& L) {
-  if (a.kv.dtype == BZ_F32) return attn2f_oproj_slices(a, L);
-  if (L.kind == LK_ROWS) return attn_dense_oproj_loads(a, L) > 0 ? 8 : 0;
-  int nw; return attn_oproj_plan(a, L, nw);
-}
-
+// attention + o_proj in one launch, in the form bzk_attn_oproj_form (bz_step_plan.hip) names for the shape
 int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long long* acc) {
-  if (a.kv.dtype == BZ_F32) {
-    const int CS = attn2f_oproj_slices(a, L);
-    if (CS <= 0) BZ_FAIL(BZ_E_INVALID, "attn+o_proj fusion (f32 cache) does not apply to this shape");
+  const AttnShape sh = attn_shape(a);
+  const bz_linear_traits_t lt = lin_traits(L);
+  const bz_step_switches_t& sw = *bzk_step_switches();
+  const int form = bzk_attn_oproj_form(sh, lt, sw);
+  if (form == BZ_ATTN_PLAIN) BZ_FAIL(BZ_E_INVALID, "attn+o_proj fusion does not apply to this shape");
+  if (form == BZ_ATTN_FUSED_Q4K) {
+    const int CS = bzk_attn2f_oproj_slices(sh, lt, sw);
 #define LAUNCH_AF(PG, WN) BZ_LAUNCH("attn+o_proj<q4_K>", L.algo_bytes, (k_attn2f<PG, 1, WN>), dim3(a.nq * CS), dim3(512), 0, s, a, (const uint4*)L.w, (const uint4*)L.hdr, L.bias, CS, acc)
     if (a.window > 0) { if (a.kv.paged) LAUNCH_AF(1, 1); else LAUNCH_AF(0, 1); }
     else { if (a.kv.paged) LAUNCH_AF(1, 0); else LAUNCH_AF(0, 0); }
@@ -3666,9 +3596,8 @@ int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long lo
     BZ_HIP(hipGetLastError());
     return BZ_OK;
   }
-  if (L.kind == LK_ROWS) {
-    const int DL = attn_dense_oproj_loads(a, L);
-    if (DL <= 0) BZ_FAIL(BZ_E_INVALID, "attn+o_proj fusion (dense) does not apply to this shape");
+  if (form == BZ_ATTN_FUSED_DENSE) {
+    const int DL = bzk_attn_dense_oproj_loads(sh, lt, sw);
 #define LAUNCH_AD_(DT, T, PG, HDV, WN) BZ_LAUNCH("attn+o_proj<dense>", L.algo_bytes, (k_attn2<DT, 2, T, 8, PG, HDV, WN>), dim3(a.nq * 8), dim3(512), attn2_smem(8), s, a, \
     (const uint4*)L.w, (const __half*)nullptr, (const unsigned char*)nullptr, 8, acc)
 #define LAUNCH_AD(DT, T, PG, HDV) do { if (a.window > 0) LAUNCH_AD_(DT, T, PG, HDV, 1); else LAUNCH_AD_(DT, T, PG, HDV, 0); } while (0)
@@ -3685,8 +3614,7 @@ int bzk_attn_oproj(hipStream_t s, const AttnArgs& a, const LinearDev& L, long lo
     return bzk_fix_bias(s, acc, L.bias, L.N, a.act);
   }
   int NW;
-  const int CS = attn_oproj_plan(a, L, NW);
-  if (CS <= 0) BZ_FAIL(BZ_E_INVALID, "attn+o_proj fusion does not apply to this shape");
+  const int CS = bzk_attn_oproj_plan(sh, lt, NW);
   const int TPW = (L.N / 64) / (CS * (NW > 8 ? 8 : NW));
 #define LAUNCH_AO_(DT, T, W_, PG, WN) BZ_LAUNCH("attn+o_proj", L.algo_bytes, (k_attn2<DT, 1, T, W_, PG, 128, WN>), dim3(a.nq * CS), dim3(W_ * 64), attn2_smem(W_), s, a, \
     (const uint4*)L.w, (const __half*)L.scales, (const unsigned char*)L.zeros, CS, acc)
@@ -4022,15 +3950,10 @@ int bzk_attn_split_slices(int positions) {
   // up to 128 * 128 positions every context uses 128-position slices; beyond, the slice length doubles and the count stays <= ATT_MAX_SPLITS
   return std::min((std::max(positions, 1) + 127) / 128, ATT_MAX_SPLITS);
 }
-int bzk_attn_split_ok(const AttnArgs& a) {
-  const int rep = a.nkv > 0 ? a.nq / a.nkv : 0;
-  return a.hd == 128 && (a.kv.dtype == BZ_F16 || a.kv.dtype == BZ_BF16) && !a.q_only && a.nq % a.nkv == 0 && (rep == 1 || rep == 2 || rep == 4 || rep == 8) &&
-         a.rope_cur != nullptr;
-}
 size_t bzk_attn_split_ws_bytes(int nq) { return (size_t)nq * 128 * ATT_PSTRIDE * 4; }
 
 int bzk_attn_split(hipStream_t s, const AttnArgs& a, int nsplit, float* ws) {
-  if (!bzk_attn_split_ok(a) || nsplit < 1 || nsplit > ATT_MAX_SPLITS) BZ_FAIL(BZ_E_INVALID, "split attention does not apply to this shape");
+  if (!bzk_attn_split_ok(attn_shape(a)) || nsplit < 1 || nsplit > ATT_MAX_SPLITS) BZ_FAIL(BZ_E_INVALID, "split attention does not apply to this shape");
   const int rep = a.nq / a.nkv;
 #define LAUNCH_SP_(DT, PG, R, WN) BZ_LAUNCH("attn_split", 0.0, (k_attn_split<DT, PG, R, WN>), dim3(a.nkv * nsplit), dim3(R == 8 ? 512 : 256), 0, s, a, nsplit, ws)
 #define LAUNCH_SP(DT, PG, R) do { if (a.window > 0) LAUNCH_SP_(DT, PG, R, 1); else LAUNCH_SP_(DT, PG, R, 0); } while (0)
@@ -4051,11 +3974,10 @@ int bzk_attn_merge(hipStream_t s, const AttnArgs& a, const float* ws, int nsplit
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
-int bzk_attn_merge_oproj_ok(const AttnArgs& a, const LinearDev& L) { int nw; return attn_oproj_plan(a, L, nw) > 0 && nw == 8; }
 int bzk_attn_merge_oproj(hipStream_t s, const AttnArgs& a, const float* ws, int nsplit, const LinearDev& L, long long* acc) {
   int NW;
-  const int CS = attn_oproj_plan(a, L, NW);
-  if (CS <= 0 || NW != 8) BZ_FAIL(BZ_E_INVALID, "attn merge + o_proj fusion does not apply to this shape");
+  const int CS = bzk_attn_oproj_plan(attn_shape(a), lin_traits(L), NW);
+  if (!bzk_attn_merge_oproj_ok(attn_shape(a), lin_traits(L))) BZ_FAIL(BZ_E_INVALID, "attn merge + o_proj fusion does not apply to this shape");
   const int TPW = (L.N / 64) / (CS * 8);
 #define LAUNCH_MO_(T, WN) BZ_LAUNCH("attn_merge+o_proj", L.algo_bytes, (k_attn_merge_oproj<T, WN>), dim3(a.nq * CS), dim3(512), 0, s, a, ws, nsplit, \
     (const uint4*)L.w, (const __half*)L.scales, (const unsigned char*)L.zeros, CS, acc)
@@ -4073,8 +3995,8 @@ int bzk_attn_decode(hipStream_t s, const AttnArgs& a) {
 #define LAUNCH_ATT(HD, DT) do { if (a.window > 0) LAUNCH_ATT_(HD, DT, 1); else LAUNCH_ATT_(HD, DT, 0); } while (0)
 #define LAUNCH_ATT_DT(HD) do { if (a.kv.dtype == BZ_F16) LAUNCH_ATT(HD, BZ_F16); else if (a.kv.dtype == BZ_BF16) LAUNCH_ATT(HD, BZ_BF16); \
                                else LAUNCH_ATT(HD, BZ_F32); } while (0)
-  static const bool no_a64 = getenv("BZ_NO_ATTN2_HD64") != nullptr;
-  if ((a.hd == 128 || (a.hd == 64 && a.rope_cur != nullptr && !no_a64)) && a.kv.dtype != BZ_F32) {
+  const int kernel = bzk_attn_kernel(attn_shape(a), *bzk_step_switches());
+  if (kernel == BZ_ATTN_K_ATTN2) {
     // the 8-wave lane = (row, 8-element piece) kernel: head_dim 128, and 64 (Llama-3.2-1B) with 8 rows per wave-wide load
 #define LAUNCH_A2_(DT, PG, HDV, WN) BZ_LAUNCH("attn_decode", 0.0, (k_attn2<DT, 0, 1, 8, PG, HDV, WN>), dim3(a.nq), dim3(512), attn2_smem(8), s, a, (const uint4*)nullptr, \
     (const __half*)nullptr, (const unsigned char*)nullptr, 1, (long long*)nullptr)
@@ -4087,14 +4009,14 @@ int bzk_attn_decode(hipStream_t s, const AttnArgs& a) {
 #undef LAUNCH_A2
 #undef LAUNCH_A2_
   }
-  else if (a.hd == 128 && a.kv.dtype == BZ_F32 && a.rope_cur != nullptr && getenv("BZ_NO_ATTN_F32") == nullptr) {
+  else if (kernel == BZ_ATTN_K_ATTN2F) {
 #define LAUNCH_A2F(PG, WN) BZ_LAUNCH("attn_decode", 0.0, (k_attn2f<PG, 0, WN>), dim3(a.nq), dim3(512), 0, s, a, (const uint4*)nullptr, (const uint4*)nullptr, (const float*)nullptr, 1, (long long*)nullptr)
     if (a.window > 0) { if (a.kv.paged) LAUNCH_A2F(1, 1); else LAUNCH_A2F(0, 1); }
     else { if (a.kv.paged) LAUNCH_A2F(1, 0); else LAUNCH_A2F(0, 0); }
 #undef LAUNCH_A2F
   }
-  else if (a.hd == 64) LAUNCH_ATT_DT(64);
-  else if (a.hd == 128) LAUNCH_ATT_DT(128);
+  else if (kernel == BZ_ATTN_K_DECODE && a.hd == 64) LAUNCH_ATT_DT(64);
+  else if (kernel == BZ_ATTN_K_DECODE) LAUNCH_ATT_DT(128);
   else BZ_FAIL(BZ_E_UNSUPPORTED, "head_dim %d unsupported (64 and 128 are built)", a.hd);
 #undef LAUNCH_ATT_DT
 #undef LAUNCH_ATT
@@ -5534,10 +5456,8 @@ int bzk_moe_router(hipStream_t s, const Pro& pro, const void* wr, int wdt, int E
   return BZ_OK;
 }
 
-bool bzk_moe_rows2_ok(int wdt, int K) { return rows2_enabled() && (wdt == BZ_F16 || wdt == BZ_BF16) && K % 8 == 0 && K <= 131072; }
-
 int bzk_moe_gemv(hipStream_t s, const MoeGemvArgs& g, int wdt, int n_slots, const Pro& pro, int act, bool split, double bytes) {
-  if (split && g.acc && bzk_moe_rows2_ok(wdt, g.K) && (pro.mode == PRO_PLAIN || pro.mode == PRO_SILU || (pro.mode == PRO_NORM && g.route.lg))) {
+  if (split && g.acc && bzk_moe_rows2_ok(wdt, g.K, *bzk_step_switches()) &&(pro.mode == PRO_PLAIN || pro.mode == PRO_SILU || (pro.mode == PRO_NORM && g.route.lg))) {
     // the balanced role kernel over all slots at once (fixed-point accumulators: slot s -> acc[min(s, acc_slots - 1)])
     const int KC = (g.K + 511) / 512;
     const long long U = (long long)((g.N + 3) / 4) * KC * n_slots;

@@ -673,6 +673,18 @@ class LoadedModel:
         return [dict(name=buf[i].name.decode(), launches=buf[i].launches, total_ms=buf[i].total_ms, algo_bytes=buf[i].algo_bytes)
                 for i in range(n.value)]
 
+    def layer_traits(self, layer):
+        """bz_model_layer_traits: what the step plan reads of one layer, as an L.LayerTraits"""
+        t = L.LayerTraits()
+        L.check(L.lib().bz_model_layer_traits(self.h, int(layer), C.byref(t)))
+        return t
+
+    def layer_plan(self, layer, kv_dtype):
+        """bz_model_layer_plan: the plan the decode step dispatches on for `layer` over a cache of kv_dtype (see layer_plan below)"""
+        p = L.LayerPlan()
+        L.check(L.lib().bz_model_layer_plan(self.h, int(layer), int(kv_dtype), C.byref(p)))
+        return _plan_dict(p)
+
     # --- op-level ----------------------------------------------------------------------------------------------
     def quant_matmul(self, name, x):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -930,6 +942,18 @@ def prompt_plan(traits, kind, rows, total_len, kv_dtype=L.F16, switches=None):
     p = L.PromptPlan()
     L.check(L.lib().bz_prompt_plan(C.byref(traits), C.byref(switches) if switches is not None else None, int(kind), int(rows), int(total_len), int(kv_dtype), C.byref(p)))
     return dict(route=p.route, exact=p.exact, attn=p.attn, head=p.head, chunk=p.chunk)
+
+
+def _plan_dict(p):
+    return {n: (list(getattr(p, n)) if n in ("qkv", "o", "gateup", "down") else getattr(p, n)) for n, _ in L.LayerPlan._fields_}
+
+
+def layer_plan(traits, kv_dtype=L.F16, switches=None):
+    """bz_layer_plan (host only): the kernels one layer of a decode step launches over a cache of kv_dtype.  switches: an L.StepSwitches, or None for this
+    process's environment.  Returns a dict of the L.LayerPlan fields (L.GEMV_*, L.ATTN_*, L.ATTN_K_*, L.MLP_*; per-part forms as lists of three)."""
+    p = L.LayerPlan()
+    L.check(L.lib().bz_layer_plan(C.byref(traits), C.byref(switches) if switches is not None else None, int(kv_dtype), C.byref(p)))
+    return _plan_dict(p)
 
 
 def penalty_window(recent_tokens, repeat_last_n):

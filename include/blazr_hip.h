@@ -860,6 +860,61 @@ enum { BZ_HEAD_STEP = 0, BZ_HEAD_GEMM = 1, BZ_HEAD_GEMV_ROWS = 2, BZ_HEAD_SPEC =
 typedef struct bz_prompt_plan_t { int route, exact, attn, head, chunk; } bz_prompt_plan_t;
 int bz_model_prompt_traits(const bz_model* m, bz_prompt_traits_t* out);
 int bz_prompt_plan(const bz_prompt_traits_t* t, const bz_prompt_switches_t* sw, int kind, int rows, int total_len, int kv_dtype, bz_prompt_plan_t* out);
+/* Which kernels a decode step launches (DESIGN.md "Which kernels a decode step launches").  As above: bz_layer_traits_t is what the decision reads of one
+ * layer, fixed at bz_model_finalize but for the two LoRA flags, which bz_lora_table_create sets from the table's mask; bz_step_switches_t the twelve environment
+ * switches, read once per process; bz_layer_plan: HOST ONLY, needs no device -- the decision itself, a pure function of (traits, switches, kv_dtype).  The model
+ * keeps one plan per layer and cache dtype (F32 / F16 / BF16); the step dispatches on it and decides one thing per call: the short or the long attention form,
+ * from the context and BZ_SPLIT_MIN.  A fused linear is described by its parts (at most three).  Flags are 0 / 1.  New symbols only: BZ_ABI_VERSION is unchanged. */
+enum { BZ_LIN_NONE = 0, BZ_LIN_Q4G = 1, BZ_LIN_ROWS = 2, BZ_LIN_Q4K = 3, BZ_LIN_Q6K = 4, BZ_LIN_Q80 = 5, BZ_LIN_Q5K = 6, BZ_LIN_Q40 = 7, BZ_LIN_Q41 = 8, BZ_LIN_Q50 = 9,
+       BZ_LIN_Q51 = 10, BZ_LIN_F8 = 11 };
+typedef struct bz_linear_traits_t {
+  int kind, N, K;        /* BZ_LIN_* */
+  int wdt;               /* ROWS: the weights' dtype */
+  int gw, sk, npf;       /* k-groups per workgroup, split-K count, weight loads in flight: the layout choices of finalize */
+  int act_order, bias;   /* GPTQ act-order permutation / bias present */
+} bz_linear_traits_t;
+typedef struct bz_fused_traits_t { int n_parts, fix_out; bz_linear_traits_t parts[3]; } bz_fused_traits_t;
+typedef struct bz_layer_traits_t {
+  int arch, act_dtype, hidden, inter, n_heads, n_kv_heads, head_dim;
+  int window;                /* this layer's sliding window (0: full attention) */
+  int lora_o, lora_mlp;      /* the LoRA table's mask covers o_proj / one of gate, up, down */
+  int down_slabs;            /* the slab-major copy of a dense down_proj exists (k_mlp_dense reads it) */
+  bz_fused_traits_t qkv, o, gateup, down;   /* DeepSeek-V2: [q ; kv_a], o_proj, a dense layer's gate/up and down; Mamba2: in_proj and out_proj in qkv and o */
+  /* DeepSeek-V2 */
+  int mla_x_ok[3];           /* per cache dtype: the exact decode MLA kernels take the shape and the model's longest context */
+  int is_moe, e_dt, router_dt, moe_inter, moe_n_experts, moe_slots;   /* moe_slots = top_k + n_shared */
+  /* Mamba2 */
+  int ssm_d_inner, ssm_n_groups;
+} bz_layer_traits_t;
+typedef struct bz_step_switches_t {
+  int no_slim_qkv, no_gq_slim, no_gq_mix, no_rows2;                          /* BZ_NO_SLIM_QKV, BZ_NO_GQ_SLIM, BZ_NO_GQ_MIX, BZ_NO_ROWS2 set */
+  int no_attn_fusion, no_attn_split, no_attn_f32, no_attn2_hd64;             /* BZ_NO_ATTN_FUSION, BZ_NO_ATTN_SPLIT, BZ_NO_ATTN_F32, BZ_NO_ATTN2_HD64 set */
+  int no_mlp_fusion, gguf_mlp_fusion, dsv2_f32_sums, no_moe_route_fusion;    /* BZ_NO_MLP_FUSION, BZ_GGUF_MLP_FUSION, BZ_DSV2_F32_SUMS, BZ_NO_MOE_ROUTE_FUSION set */
+} bz_step_switches_t;
+/* the kernel one GEMV launch takes (NONE: no such part) */
+enum { BZ_GEMV_NONE = 0, BZ_GEMV_F8 = 1, BZ_GEMV_Q4G_SLIM = 2, BZ_GEMV_Q4G = 3, BZ_GEMV_ROWS2 = 4, BZ_GEMV_ROWS = 5, BZ_GEMV_GQ_SLIM = 6, BZ_GEMV_GQ = 7, BZ_GEMV_UNSUPPORTED = 8 };
+/* attention and o_proj: PLAIN = attention, then the o_proj GEMV(s); FUSED_*: one launch (int4 / dense 16-bit / Q4_K o_proj over an f32 cache); SPLIT: split-KV
+ * partials + merge + o_proj GEMV; SPLIT_FUSED: split-KV partials + merge with the int4 o_proj */
+enum { BZ_ATTN_PLAIN = 0, BZ_ATTN_FUSED_Q4G = 1, BZ_ATTN_FUSED_DENSE = 2, BZ_ATTN_FUSED_Q4K = 3, BZ_ATTN_SPLIT = 4, BZ_ATTN_SPLIT_FUSED = 5 };
+/* the kernel behind a plain attention launch: k_attn_decode (one thread per position), k_attn2 (8 waves, 16-bit cache), k_attn2f (f32 cache) */
+enum { BZ_ATTN_K_DECODE = 0, BZ_ATTN_K_ATTN2 = 1, BZ_ATTN_K_ATTN2F = 2, BZ_ATTN_K_UNSUPPORTED = 3 };
+enum { BZ_MLP_SPLIT = 0, BZ_MLP_Q4G = 1, BZ_MLP_DENSE = 2, BZ_MLP_GQ = 3 };
+/* qkv_mix (gateup_mix): a Q4_K part and a Q6_K part -- q/k and v of a Q4_K_M file -- in one slim launch; else qkv[i] per part.  attn_short: the form of a step of at most BZ_SPLIT_MIN keys (of its window, for a
+ * windowed layer); attn_long: beyond.  attn_kernel, o[i]: what PLAIN and SPLIT launch.  mlp: a fused form, or SPLIT with gateup[i] and down[i] (filled for every
+ * plan: what BZ_MLP_SPLIT would launch).  mla_exact / moe_route_fused / moe_rows2: DeepSeek-V2 -- the exact MLA kernels (else the f32 ones), router logits as
+ * a ring GEMV with the top-k inside the gate/up launch (else the router launch), the balanced role kernel for the experts behind the router launch. */
+typedef struct bz_layer_plan_t {
+  int qkv_mix, qkv[3];
+  int attn_short, attn_long, attn_kernel, o[3];
+  int mlp, gateup_mix, gateup[3], down[3];
+  int mla_exact, moe_route_fused, moe_rows2;
+} bz_layer_plan_t;
+int bz_model_layer_traits(const bz_model* m, int layer, bz_layer_traits_t* out);
+int bz_model_layer_plan(const bz_model* m, int layer, int kv_dtype, bz_layer_plan_t* out);
+int bz_layer_plan(const bz_layer_traits_t* t, const bz_step_switches_t* sw, int kv_dtype, bz_layer_plan_t* out);
+/* HOST ONLY: the attention form (BZ_ATTN_*) of a step that sees `keys` positions (an eager step: position + 1; a graph: its capacity) on a layer with the given
+ * window under BZ_SPLIT_MIN = split_min -- plan->attn_short up to split_min keys, or a window of at most that many, plan->attn_long beyond.  -1: null plan. */
+int bz_step_attn_form(const bz_layer_plan_t* plan, int window, int keys, int split_min);
 /* op-level twin of bz_paged_attn_decode for a decode batch (engine/batch_decode.rs:35-150): runs the attention the batched step would launch for these rows and
  * returns its 16-bit rows as F32.  q F32 [N, n_heads, hd] roped and rounded, block_table I32 [N, max_blocks], seq_lens HOST i32 [N], out F32 [N, n_heads, hd]. */
 int bz_paged_attn_decode_rows(bz_model* m, const bz_tensor* q, bz_paged_kv* kv, int layer, const bz_tensor* block_table, int max_blocks,

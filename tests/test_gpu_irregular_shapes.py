@@ -6,25 +6,13 @@ Every other Llama-family fixture of the suite has hidden 256 / 2048 / 4096 / 819
 or superblocks along K and 6 / 12 / 20 / 22 column tiles along N, ragged vocabularies (1001 / 1003 / 1027 rows through the row GEMV, the fused argmax,
 the MFMA prompt GEMM and the batched-decode head), and the head_dims that are not built (refused at bz_model_finalize).
 
-What each case launched in one decode step at position 8: the kernel names bz_profile_step reported on an MI355X, which `test_kernels_each_case_reached`
-prints (with launch counts, under `-s`).  The test asserts the entries the reasoning above depends on: no fused attention + o_proj / MLP launch on the
-shapes those kernels are not built for, the slim SILU GEMV on q4km-g3's down projection.
-
-| case          | launched (name x launches in the step; 2 layers)                                                                          |
-|---------------|---------------------------------------------------------------------------------------------------------------------------|
-| bf16-g3-hd64  | embed x1, gemv_rows2<norm> x4 (q/k/v, gate/up), attn_decode x2, gemv_rows2 x2 (o_proj), gemv_rows2<silu> x2 (down), gemv_rows<lm_head+argmax> x1, argmax_final x1 |
-| bf16-g3-hd128 | embed x1, gemv_rows2<norm> x4, attn_decode x2, gemv_rows2 x2, gemv_rows2<silu> x2, gemv_rows<lm_head+argmax> x1, argmax_final x1 |
-| bf16-g2-w768  | embed x1, gemv_rows2<norm> x4, attn_decode x2, gemv_rows2 x2, gemv_rows2<silu> x2, gemv_rows<lm_head+argmax> x1, argmax_final x1 |
-| awq-g3        | embed x1, gemv_q4g<norm> x4 (q/k/v, gate/up), attn_decode x2, gemv_q4g<plain> x2 (o_proj), gemv_q4g<silu> x2 (down), gemv_rows<lm_head+argmax> x1, argmax_final x1 |
-| awq-g4-w768   | embed x1, gemv_q4g<norm> x4, attn_decode x2, gemv_q4g<plain> x2, gemv_q4g<silu> x2, gemv_rows<lm_head+argmax> x1, argmax_final x1 |
-| awq-g7        | embed x1, gemv_q4g<norm> x4, attn_decode x2, gemv_q4g<plain> x2, gemv_q4g<silu> x2, gemv_rows<lm_head+argmax> x1, argmax_final x1 |
-| gptq-g6       | embed x1, gemv_q4g<norm> x10 (act-order: q, k, v, gate, up each a launch of its own), attn_decode x2, gemv_q4g<plain> x2, gemv_q4g<silu> x2, gemv_rows<lm_head+argmax> x1, argmax_final x1 |
-| q4km-g3       | embed x1, gemv_q4_K x6 (per layer: q/k/v -- q/k in layer 1 --, o_proj, gate/up), gemv_q6_K x2 (v of layer 1, lm_head), attn_decode x2, gemv_q4_K<slim> x1 (down of layer 0), gemv_q6_K<slim> x1 (down of layer 1), argmax_final x1 |
-| q8_0-g7       | embed x1, gemv_q8_0 x9 (four projections per layer and the lm_head), attn_decode x2, argmax_final x1                       |
-
-No case launched `attn+o_proj*`, `attn_merge+o_proj`, `mlp_*` or the mixed `gemv_q4_K+q6_K<slim>`: hidden 384 / 768 / 896 is outside what those kernels are
-built for (the names in brackets say which projection a name belongs to, from the order of the launches in llama_step).  With BZ_SPLIT_MIN=4 at position 269
-the rep-3 cases still reported `attn_decode`, and bf16-g2-w768 reported `attn_split` + `attn_merge` in its place (test_long_context_token_by_token).
+What each case launched in one decode step at position 8, and at position 269 under BZ_SPLIT_MIN=4: profiles/step_census.json holds the kernel names and
+launch counts bz_profile_step reported on an MI355X (scripts/step_census.py takes the record), tests/test_step_plan.py holds the layer plan to them without a
+device (awq-g3, bf16-g3-hd64, bf16-g2-w768, gptq-g6, q4km-g3 and q8_0-g7 by name), and tests/test_gpu_step_plan.py holds a loaded model's step to its plan.
+`test_kernels_each_case_reached` prints the names (with launch counts, under `-s`) and asserts the entries the reasoning above depends on: no fused
+attention + o_proj / MLP launch on the shapes those kernels are not built for (hidden 384 / 768 / 896), the slim SILU GEMV on q4km-g3's down projection.  With
+BZ_SPLIT_MIN=4 at position 269 the rep-3 cases still report `attn_decode`, and bf16-g2-w768 reports `attn_split` + `attn_merge` in its place
+(test_long_context_token_by_token).
 
 Tolerances are the suite's own: logits at 2 x REL[act] (test_gpu_llama.py TINY: the rule for narrow fixtures), op-level bounds as in tests/test_gpu_ops.py /
 test_gpu_llama.py, ids bit-exact on the oracle's fair prefix.
