@@ -219,6 +219,10 @@ class PromptPlan(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("route", "exact", "attn", "head", "chunk")]
 
 
+class PackedPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("packed", "rows", "n_seq", "max_len")] + [("plan", PromptPlan)]
+
+
 PLAN_PROMPT, PLAN_DECODE_BATCH, PLAN_VERIFY = 0, 1, 2
 ROUTE_STEPS, ROUTE_ROWS, ROUTE_DSV2, ROUTE_MAMBA = 0, 1, 2, 3
 PF_ATTN_NONE, PF_ATTN_MFMA, PF_ATTN_SCALAR, PF_ATTN_SCALAR_EXACT, PF_ATTN_ROWS = 0, 1, 2, 3, 4
@@ -346,6 +350,9 @@ SYMBOLS = {
     "bz_embed_kv": (C.c_int, [P, P, C.c_int, P, C.c_int, C.POINTER(EmbedConfig), P]),
     "bz_embed_paged": (C.c_int, [P, P, C.c_int, P, P, P, C.c_int, C.c_int, C.c_int, C.POINTER(EmbedConfig), P]),
     "bz_embed_ssm": (C.c_int, [P, P, C.c_int, P, C.POINTER(EmbedConfig), P]),
+    "bz_embed_batch": (C.c_int, [P, P, P, C.c_int, P, C.POINTER(EmbedConfig), P]),
+    "bz_score_batch": (C.c_int, [P, P, P, C.c_int, P, P, C.POINTER(ScoreConfig), C.POINTER(ScoreRow), C.POINTER(ScoreTotal)]),
+    "bz_attn_packed": (C.c_int, [P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P]),
     "bz_score_rows": (C.c_int, [P, P, C.c_int64, C.c_int64, P, C.POINTER(ScoreConfig), C.POINTER(ScoreRow)]),
     "bz_pool_rows": (C.c_int, [P, P, C.c_int64, C.c_int64, C.POINTER(EmbedConfig), P]),
     "bz_score_row_spec": (C.c_int, [P, C.c_int64, C.c_int64, C.c_int, C.POINTER(ScoreRow)]),
@@ -399,6 +406,9 @@ SYMBOLS = {
     "bz_rows_attn_slice_len": (C.c_int, [C.c_int]),
     "bz_model_prompt_traits": (C.c_int, [P, C.POINTER(PromptTraits)]),
     "bz_prompt_plan": (C.c_int, [C.POINTER(PromptTraits), C.POINTER(PromptSwitches), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PromptPlan)]),
+    "bz_packed_plan": (C.c_int, [C.POINTER(PromptTraits), C.POINTER(PromptSwitches), P, C.c_int, C.c_int, C.POINTER(PackedPlan)]),
+    "bz_packed_targets_spec": (C.c_int, [P, P, C.c_int, P]),
+    "bz_packed_totals_spec": (C.c_int, [P, P, C.c_int, C.POINTER(ScoreTotal)]),
     "bz_model_layer_traits": (C.c_int, [P, C.c_int, C.POINTER(LayerTraits)]),
     "bz_model_layer_plan": (C.c_int, [P, C.c_int, C.c_int, C.POINTER(LayerPlan)]),
     "bz_layer_plan": (C.c_int, [C.POINTER(LayerTraits), C.POINTER(StepSwitches), C.c_int, C.POINTER(LayerPlan)]),

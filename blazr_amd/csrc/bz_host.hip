@@ -346,6 +346,7 @@ struct bz_model {
   long long* sp_argmax = nullptr; long long* sp_record = nullptr;
   size_t resident = 0, per_token = 0;
   BzSinkWs* sink_ws = nullptr;   // buffers of score / embed calls (bz_score.hip), made by the first such call
+  int* pk_seg = nullptr; size_t pk_seg_elems = 0;   // packed prompt batches: [T] segment starts of the rows, then [n_seq + 1] first rows of the inputs (its own hipMalloc, not in `owned`)
   BzLoraTable* lora = nullptr;   // bz_lora_table_create: the adapter slots, the current-slot scalar and the f32 rows the adapted linears' consumers read (bz_lora.hip)
 };
 
@@ -424,6 +425,7 @@ extern "C" int bz_model_free(bz_model* m) {
   hipStreamSynchronize(m->dev->stream);
   for (auto& kv : m->raw) raw_free(kv.second);
   for (void* p : m->owned) hipFree(p);
+  if (m->pk_seg) hipFree(m->pk_seg);
   bzk_sink_free(m->sink_ws);
   bzl_table_free(m->lora);
   bz_dev_release(m->dev);
@@ -2212,7 +2214,9 @@ static int pf_gemm_gq(bz_model* m, const FusedLinear& F, const float* xf, int n,
 // per-row context of a decode batch: row r is its own sequence (position row_pos[r], block-table row r); nullptr row_pos = one prompt
 // row_lora: device LoRA slot id per row (-1: none); nullptr = every row under the model's current-slot scalar (prompts, the engine's prompt chunks)
 // split_min: BZ_ROWS_SPLIT_MIN as rows_attn_prepare read it for this call (a captured graph keeps what its capture saw)
-struct RowsCtx { const int* row_pos = nullptr; int table_stride = 0; int max_len = 0; const int* row_lora = nullptr; int split_min = 1 << 30; };
+// seg_lo: a packed prompt batch (row_pos == nullptr, contiguous cache, pos0 = 0) -- device i32 [S], the packed row at which each row's input starts; max_len is then
+// the longest input
+struct RowsCtx { const int* row_pos = nullptr; int table_stride = 0; int max_len = 0; const int* row_lora = nullptr; int split_min = 1 << 30; const int* seg_lo = nullptr; };
 // What the attention of a decode batch launches, layer by layer, at a decision length of `declen` positions (the longest live row of an eager step, the
 // capacity of a graph): the scalar kernel while a row's scores fit its LDS, the split-KV pair beyond (bz_rows_attn.hip).  Refuses, naming the limit, where
 // neither applies, and grows the pair's workspace -- allocation synchronises, so this runs before any capture begins.
@@ -2320,6 +2324,8 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
       BZ_TRY(bzk_pf_norm(st, dt, m->pf_h, prev, L.attn_norm, n, H, c.rms_eps, act, m->pf_x16));
       BZ_TRY(gq ? pf_gemm_gq(m, L.qkv, (const float*)m->pf_x16, n, m->pf_qkv) : pf_gemm(m, L.qkv.parts[0], m->pf_x16, n, m->pf_qkv, exact));
       BZ_TRY(lora_rows(l, LG_QKV, m->pf_qkv, n, s0));
+      if (rc.seg_lo) BZ_TRY(bzk_pf_rope_kv_seg(st, m->pf_qkv, n, nq, nkv, hd, m->cos_t, m->sin_t, c.rope_interleaved, p0, act, vw, l, rc.seg_lo));
+      else
       BZ_TRY(bzk_pf_rope_kv(st, m->pf_qkv, n, nq, nkv, hd, m->cos_t, m->sin_t, c.rope_interleaved, p0, act, vw, l, slots ? slots + s0 : nullptr,
                             rc.row_pos ? rc.row_pos + s0 : nullptr));
       BzRowsPlan rp{};                    // decode batch: the split-KV pair where the scalar kernel cannot hold a row's scores (or from BZ_ROWS_SPLIT_MIN on)
@@ -2329,7 +2335,7 @@ static int prefill_dense(bz_model* m, const long long* d_tok, int S, const KvVie
         BZ_TRY(bzk_rows_attn(st, dt, m->pf_qkv, n, nq, nkv, hd, vw, l, m->pf_x16, rc.row_pos + s0, rc.table_stride, layer_window(c, l), rp, m->rows_ws));
       } else
       BZ_TRY(bzk_pf_attn(st, dt, m->pf_qkv, n, nq, nkv, hd, p0, act, vw, l, m->pf_x16, rc.row_pos ? rc.row_pos + s0 : nullptr, rc.table_stride, rc.max_len, plan.attn,
-                         layer_window(c, l)));
+                         layer_window(c, l), rc.seg_lo));
       BZ_TRY(gq ? pf_gemm_gq(m, L.o, (const float*)m->pf_x16, n, m->pf_t) : pf_gemm(m, L.o.parts[0], m->pf_x16, n, m->pf_t, exact));
       BZ_TRY(lora_rows(l, LG_O, m->pf_t, n, s0));
       BZ_TRY(bzk_pf_norm(st, dt, m->pf_h, m->pf_t, L.ffn_norm, n, H, c.rms_eps, act, m->pf_x16));
@@ -2543,6 +2549,109 @@ extern "C" int bz_score_kv(bz_model* m, const bz_tensor* tokens, int S, bz_kv* k
 extern "C" int bz_embed_kv(bz_model* m, const bz_tensor* tokens, int S, bz_kv* kv, int position, const bz_embed_config* cfg, bz_tensor* out) {
   BZ_API_BEGIN
   return forward_kv_sink(m, tokens, S, kv, position, RowSink::hidden(cfg, out), "embed_kv");
+  BZ_API_END
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Packed prompt batches: n_seq inputs laid end to end in `tokens`, one prompt pass for all of them (server/embeddings.rs:180 and server/rerank.rs:144 are the
+// per-text loops this serves).  Packed row i is stored at row i of the scratch cache and rotated by its position inside its own input; the attention keeps a
+// query to its own input's keys (bz_prefill.hip, the SEG forms); GEMMs, norms, SiLU and the score sink are row-wise; pooling is per input (k_pool_seg).
+// Where bz_packed_plan says packed = 0 the single-input path runs once per input -- reset cache, then what bz_embed_kv / bz_score_kv run -- into the same layout.
+// ---------------------------------------------------------------------------------------------------------
+struct PackedCall { std::vector<int> off; int T = 0, max_len = 0; bz_packed_plan_t pp{}; };
+static int packed_check(bz_model* m, const bz_tensor* tokens, const int32_t* seq_lens, int n_seq, bz_kv* kv, const char* who, PackedCall* pc) {
+  if (!m || !m->finalized) BZ_FAIL(BZ_E_INVALID, "%s: model not finalized", who);
+  BZ_TRY(bzk_packed_lens(seq_lens, n_seq, who, nullptr, &pc->off, &pc->max_len));
+  pc->T = pc->off[(size_t)n_seq];
+  BZ_TRY(check_fwd(m, tokens, pc->T));
+  if (m->cfg.arch == BZ_ARCH_MAMBA2) BZ_FAIL(BZ_E_INVALID, "%s: model has no KV cache (loop bz_embed_ssm / bz_score_ssm over the inputs)", who);
+  BZ_TRY(check_cache(m, kv, who));
+  if (pc->T > kv->max_len) BZ_FAIL(BZ_E_INVALID, "%s: %d packed rows, the scratch cache holds %d", who, pc->T, kv->max_len);
+  if (pc->max_len > m->cfg.max_seq_len) BZ_FAIL(BZ_E_INVALID, "%s: an input of %d tokens exceeds max_seq_len %d", who, pc->max_len, m->cfg.max_seq_len);
+  return bz_packed_plan(&m->traits, nullptr, seq_lens, n_seq, kv->dtype, &pc->pp);
+}
+// the packed pass itself: the segment starts go to the device, the rows through prefill_dense
+static int packed_run(bz_model* m, const bz_tensor* tokens, bz_kv* kv, const PackedCall& pc, int n_seq, const RowSink& sink) {
+  const int T = pc.T;
+  hipStream_t st = m->dev->stream;
+  BZ_TRY(kv_grow(kv, T));
+  const size_t need = (size_t)T + (size_t)n_seq + 1;
+  if (need > m->pk_seg_elems) {      // sized once for the scratch cache (n_seq <= T <= its capacity); a smaller one from an earlier cache is replaced, not kept
+    const size_t cap = 2 * (size_t)kv->max_len + 1;
+    BZ_HIP(hipStreamSynchronize(st));
+    if (m->pk_seg) { hipFree(m->pk_seg); m->pk_seg = nullptr; m->pk_seg_elems = 0; }
+    if (hipMalloc((void**)&m->pk_seg, cap * 4) != hipSuccess) { m->pk_seg = nullptr; (void)hipGetLastError(); BZ_FAIL(BZ_E_OOM, "packed batch: out of device memory (%zu bytes of segment starts)", cap * 4); }
+    m->pk_seg_elems = cap;
+  }
+  std::vector<int> host(need);
+  for (int i = 0; i < n_seq; i++) for (int r = pc.off[i]; r < pc.off[i + 1]; r++) host[r] = pc.off[i];
+  for (int i = 0; i <= n_seq; i++) host[(size_t)T + i] = pc.off[i];
+  BZ_HIP(hipStreamSynchronize(st));      // an earlier call's kernels are done with the buffer
+  BZ_HIP(hipMemcpy(m->pk_seg, host.data(), need * 4, hipMemcpyHostToDevice));
+  const bz_prompt_plan_t& plan = pc.pp.plan;
+  const int rows = std::min(T, plan.chunk);
+  if (sink.kind == SINK_HIDDEN) BZ_TRY(bzk_pool_begin_seg(st, &m->sink_ws, T, m->cfg.hidden, rows, sink.ecfg, pc.off.data(), m->pk_seg + T, n_seq));
+  else BZ_TRY(sink_begin(m, sink, T, rows, plan.head == BZ_HEAD_GEMM));
+  RowsCtx rc; rc.seg_lo = m->pk_seg; rc.max_len = pc.max_len;
+  BZ_TRY(prefill_dense(m, (const long long*)tokens->ptr, T, view_of(kv), 0, nullptr, sink, plan, rc));
+  return sink_end(m, sink);
+}
+extern "C" int bz_embed_batch(bz_model* m, const bz_tensor* tokens, const int32_t* seq_lens, int n_seq, bz_kv* scratch, const bz_embed_config* cfg, bz_tensor* out) {
+  BZ_API_BEGIN
+  PackedCall pc;
+  BZ_TRY(packed_check(m, tokens, seq_lens, n_seq, scratch, "embed_batch", &pc));
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  const int H = m->cfg.hidden;
+  BZ_TRY(bzk_check_embed_cfg(cfg, out, 1, H, "embed_batch"));
+  const bool none = cfg->pooling == BZ_POOL_NONE;
+  const size_t need = (size_t)(none ? pc.T : n_seq) * H * 4;
+  if (out->nbytes < need) BZ_FAIL(BZ_E_INVALID, "embed_batch: out must be F32 with at least %zu bytes (%s, hidden %d), has %zu", need, none ? "[T, hidden]" : "[n_seq, hidden]", H, out->nbytes);
+  BZ_TRACE("embed_batch: n_seq=%d rows=%d packed=%d", n_seq, pc.T, pc.pp.packed);
+  int rc = BZ_OK;
+  if (pc.pp.packed) rc = packed_run(m, tokens, scratch, pc, n_seq, RowSink::hidden(cfg, out));
+  else
+    for (int i = 0; i < n_seq && rc == BZ_OK; i++) {
+      const int n = seq_lens[i];
+      bz_tensor tk = *tokens; tk.owned = false; tk.ptr = (char*)tokens->ptr + (size_t)pc.off[i] * 8; tk.nbytes = (size_t)n * 8;
+      bz_tensor o = *out; o.owned = false; o.ptr = (char*)out->ptr + (size_t)(none ? pc.off[i] : i) * H * 4; o.nbytes = (size_t)(none ? n : 1) * H * 4;
+      scratch->seq_len = 0;
+      rc = forward_kv_sink(m, &tk, n, scratch, 0, RowSink::hidden(cfg, &o), "embed_batch");
+    }
+  scratch->seq_len = 0;
+  return rc;
+  BZ_API_END
+}
+extern "C" int bz_score_batch(bz_model* m, const bz_tensor* tokens, const int32_t* seq_lens, int n_seq, bz_kv* scratch, const int64_t* targets, const bz_score_config* cfg,
+                              bz_score_row* rows_out, bz_score_total* totals) {
+  BZ_API_BEGIN
+  PackedCall pc;
+  BZ_TRY(packed_check(m, tokens, seq_lens, n_seq, scratch, "score_batch", &pc));
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  const int T = pc.T;
+  std::vector<int64_t> dflt;
+  if (!targets) {      // every row's target is the next token of its own input; an input's last row is not scored
+    dflt.resize((size_t)T);
+    BZ_HIP(hipStreamSynchronize(m->dev->stream));
+    BZ_HIP(hipMemcpy(dflt.data(), tokens->ptr, (size_t)T * 8, hipMemcpyDeviceToHost));
+    std::vector<int64_t> tk(dflt);
+    BZ_TRY(bz_packed_targets_spec(tk.data(), seq_lens, n_seq, dflt.data()));
+    targets = dflt.data();
+  }
+  BZ_TRY(bzk_check_score_cfg(cfg, targets, T, m->cfg.vocab, rows_out, "score_batch"));
+  BZ_TRACE("score_batch: n_seq=%d rows=%d packed=%d", n_seq, T, pc.pp.packed);
+  int rc = BZ_OK;
+  if (pc.pp.packed) {
+    rc = packed_run(m, tokens, scratch, pc, n_seq, RowSink::score(targets, cfg, rows_out, nullptr));
+    if (rc == BZ_OK && totals) rc = bz_packed_totals_spec(rows_out, seq_lens, n_seq, totals);      // per input, added in row order as bzk_score_end adds a single call's
+  } else
+    for (int i = 0; i < n_seq && rc == BZ_OK; i++) {
+      const int n = seq_lens[i];
+      bz_tensor tk = *tokens; tk.owned = false; tk.ptr = (char*)tokens->ptr + (size_t)pc.off[i] * 8; tk.nbytes = (size_t)n * 8;
+      scratch->seq_len = 0;
+      rc = forward_kv_sink(m, &tk, n, scratch, 0, RowSink::score(targets + pc.off[i], cfg, rows_out + pc.off[i], totals ? totals + i : nullptr), "score_batch");
+    }
+  scratch->seq_len = 0;
+  return rc;
   BZ_API_END
 }
 

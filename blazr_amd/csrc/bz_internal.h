@@ -395,7 +395,10 @@ int bzk_pf_norm(hipStream_t s, int dt, float* hbuf, const float* prev, const flo
 int bzk_pf_rope_kv(hipStream_t s, float* qkv, int S, int nq, int nkv, int hd, const float* cos_t, const float* sin_t, int interleaved, int pos0, int act,
                    const KvView& kv, int layer, const int* slots, const int* row_pos = nullptr);
 int bzk_pf_attn(hipStream_t s, int dt, const float* qkv, int S, int nq, int nkv, int hd, int pos0, int act, const KvView& kv, int layer, void* out16,
-                const int* row_pos, int table_stride, int max_len, int form, int window);   // form: BZ_PF_ATTN_* of the plan (bz_route.hip); window: see AttnArgs (every row its own lo)
+                const int* row_pos, int table_stride, int max_len, int form, int window,    // form: BZ_PF_ATTN_* of the plan (bz_route.hip); window: see AttnArgs (every row its own lo)
+                const int* seg_lo = nullptr);   // packed prompt batch: device i32 over the whole batch, the packed row at which each row's input starts (positions = packed rows)
+int bzk_pf_rope_kv_seg(hipStream_t s, float* qkv, int S, int nq, int nkv, int hd, const float* cos_t, const float* sin_t, int interleaved, int pos0, int act,
+                       const KvView& kv, int layer, const int* seg_lo);
 // Mamba2 batched prefill (bz_prefill.hip): conv over the prompt rows (+ carried conv state), in-kernel scan over the tokens, gated RMSNorm rows
 struct BzSsmScan {
   const float* xbc; int conv_dim; const float* zx; int ld; int dt_off; const float* dt_bias; const float* A_log; const float* D; void* state;
@@ -460,6 +463,10 @@ int bzk_score_chunk(hipStream_t st, BzSinkWs* w, const float* logits /*[n][V]*/,
 int bzk_score_end(hipStream_t st, BzSinkWs* w, bz_score_row* rows_out, bz_score_total* total);
 // rows: rows of the F32 [rows][H] workspace the final norm writes; two more rows follow it (bzk_pool_step_rows: hidden / prev of a token-by-token step)
 int bzk_pool_begin(hipStream_t st, BzSinkWs** w, int S, int H, int rows, const bz_embed_config* cfg);
+// a packed batch: seg_off [n_seq + 1] = the inputs' first packed rows, on the host (copied) and on the device (read by the chunks' kernels); out is [n_seq, H]
+int bzk_pool_begin_seg(hipStream_t st, BzSinkWs** w, int S, int H, int rows, const bz_embed_config* cfg, const int* seg_off_host, const int* seg_off_dev, int n_seq);
+// the lengths of a packed batch, checked (BZ_E_INVALID naming the figure): seg_lo [T] = the packed row at which each row's input starts, seg_off [n_seq + 1], the longest
+int bzk_packed_lens(const int32_t* seq_lens, int n_seq, const char* who, std::vector<int>* seg_lo, std::vector<int>* seg_off, int* max_len);
 float* bzk_pool_rows_ws(BzSinkWs* w);
 void bzk_pool_step_rows(BzSinkWs* w, float** hidden, float** prev);
 int bzk_pool_chunk(hipStream_t st, BzSinkWs* w, const float* rows /*[n][H]*/, int n, int s0, float* out);

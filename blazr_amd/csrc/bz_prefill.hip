@@ -224,6 +224,36 @@ __global__ __launch_bounds__(64) void k_pf_rope_kv(float* qkv, int nq, int nkv, 
     }
   }
 }
+// The same for a packed prompt batch (contiguous cache): the row is stored at its packed index pos = pos0 + s and rotated by its position inside its own input,
+// pos - seg_lo[pos] (seg_lo: device i32 over the whole packed batch, the packed row at which the row's input starts).  A kernel of its own: k_pf_rope_kv and
+// its launches are what they were.
+__global__ __launch_bounds__(64) void k_pf_rope_kv_seg(float* qkv, int nq, int nkv, int hd, const float* cos_t, const float* sin_t, int interleaved, int pos0, int act,
+                                                       KvView kv, int layer, const int* seg_lo) {
+  const int s = blockIdx.x, j = blockIdx.y, pos = pos0 + s, rpos = pos - seg_lo[pos];
+  float* v = qkv + (size_t)s * (nq + 2 * nkv) * hd + (size_t)j * hd;
+  const int half = hd / 2;
+  if (j < nq + nkv) {
+    const float* cr = cos_t + (size_t)rpos * half; const float* sr = sin_t + (size_t)rpos * half;
+    for (int i = threadIdx.x; i < half; i += 64) {
+      const int a = interleaved ? 2 * i : i, b = interleaved ? 2 * i + 1 : i + half;
+      const float x0 = v[a], x1 = v[b];
+      v[a] = pf_round(rope_lo(x0, x1, cr[i], sr[i]), act);
+      v[b] = pf_round(rope_hi(x0, x1, cr[i], sr[i]), act);
+    }
+  }
+  __syncthreads();
+  if (j >= nq) {
+    const int kvh = (j - nq) % nkv;
+    const size_t off = (size_t)layer * kv.layer_stride + ((size_t)kvh * kv.cap + pos) * kv.hd;
+    void* base = j >= nq + nkv ? kv.v : kv.k;
+    for (int i = threadIdx.x; i < hd; i += 64) {
+      const float x = v[i];
+      if (kv.dtype == BZ_F16) ((__half*)base)[off + i] = f16_cvt(x);
+      else if (kv.dtype == BZ_BF16) ((unsigned short*)base)[off + i] = to16<BZ_BF16>(x);
+      else ((float*)base)[off + i] = x;
+    }
+  }
+}
 
 __device__ __forceinline__ float kv_at(const KvView& kv, const void* base, int layer, int kvh, int p, int i) {
   size_t off;
@@ -255,13 +285,18 @@ __device__ __forceinline__ void ld_row8(const void* base, size_t off, float (&o)
 // sums are order-independent to ~1e-16, so a prompt row's attention output is the same bits as the decode step's.  (Non-exact form: f32 FMAs.)
 // WIN: sliding window of `window` keys -- the row walks keys [lo, len), lo = att_lo(len, window), and its score buffer holds len - lo <= window entries, so
 // what limits a prompt is the window, not the context.
-template <int DT, int KVDT, int REP, bool EXACT, bool WIN = false>
+// SEG (packed prompt batch: row_pos == nullptr, positions are packed rows): the row walks keys [lo, len) with lo = max(seg_lo[len - 1], the window's lo) -- its own
+// input's rows and nothing else -- and the score buffer holds the longest input.  Keys go to the threads from lo on, so a row's sums are those of a call that
+// holds its input alone.
+template <int DT, int KVDT, int REP, bool EXACT, bool WIN = false, bool SEG = false>
 __global__ __launch_bounds__(256) void k_pf_attn(const float* qkv, int nq, int nkv, int hd, int pos0, int act, KvView kv, int layer, float scale, void* out16,
-                                                const int* row_pos, int table_stride, int window) {
+                                                const int* row_pos, int table_stride, int window, const int* seg_lo) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   typedef typename std::conditional<EXACT, double, float>::type acc_t;
   const int s = blockIdx.x, kvh = blockIdx.y, len = (row_pos ? row_pos[s] : pos0 + s) + 1;
-  const int lo = WIN ? att_lo(len, window) : 0, wl = len - lo;   // sc is indexed from lo: [REP][wl]
+  int lo_ = WIN ? att_lo(len, window) : 0;
+  if constexpr (SEG) lo_ = max(lo_, seg_lo[len - 1]);
+  const int lo = lo_, wl = len - lo;                             // sc is indexed from lo: [REP][wl]
   const int* btab = kv.block_table + (row_pos ? (size_t)s * table_stride : 0);   // decode batch: one block-table row per sequence
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int PR = hd >> 3, RPP = 256 / PR;              // lanes per row, rows per pass
@@ -374,9 +409,13 @@ template <int DT> __device__ __forceinline__ uint4 pack8(const float* v) {
 // WIN: sliding window of `window` keys.  A query at position q sees keys (q - window, q]: the key tiles start at the 64-key tile that holds the window of the
 // workgroup's first query (tiles wholly below it are never loaded), a wave skips the tiles wholly below its own first query's window, and inside a tile the keys
 // below a query's window are masked like the keys above its position.
-template <int DT, int HD, int REP, bool PAGED, bool WIN = false>
+// SEG: a packed prompt batch -- positions are packed rows, and query q sees keys [seg_lo[q], q] only (seg_lo: device i32 over the whole packed batch, the packed row
+// at which q's input starts).  seg_lo is non-decreasing in q exactly as the window's lower bound is, so the tile structure is the window form's with
+// lo(q) = max(seg_lo[q], window lo) in the window's place; so is the fully-masked-tile case (a wave whose first query ends a long input and whose later queries open
+// a new one).
+template <int DT, int HD, int REP, bool PAGED, bool WIN = false, bool SEG = false>
 __global__ __launch_bounds__(256) void k_pf_attn_mfma(const float* __restrict__ qkv, int S, int nq, int nkv, int pos0, int act, KvView kv, int layer, float scale,
-                                                      unsigned short* __restrict__ out16, int window) {
+                                                      unsigned short* __restrict__ out16, int window, const int* __restrict__ seg_lo) {
   constexpr int HW = REP < 4 ? REP : 4, QT = 4 / HW, PR = HD / 8, PK = HD * 2 + 16, PV = 64 * 2 + 8, NC = HD / 16, NDB = HD / 32, KPT = PR / 4;
   __shared__ __attribute__((aligned(16))) unsigned char Ks[64 * PK];
   __shared__ __attribute__((aligned(16))) unsigned char Vt[HD * PV];
@@ -386,8 +425,16 @@ __global__ __launch_bounds__(256) void k_pf_attn_mfma(const float* __restrict__ 
   const int q0 = (wgt * QT + qt) * 32, qrow = min(q0 + r, S - 1), qpos = pos0 + q0 + r;
   const int kmax = pos0 + min(S, (wgt + 1) * 32 * QT);        // this workgroup's keys: [0, kmax)
   const int my_last = pos0 + min(q0 + 31, S - 1);             // last position any query of this wave attends to
-  const int kt_lo = WIN ? (att_lo(pos0 + wgt * QT * 32 + 1, window) & ~63) : 0;   // first key tile of the workgroup
-  const int my_lo = WIN ? att_lo(pos0 + q0 + 1, window) : 0;   // first key any query of this wave attends to
+  int kt_lo_ = WIN ? (att_lo(pos0 + wgt * QT * 32 + 1, window) & ~63) : 0;   // first key tile of the workgroup
+  int my_lo_ = WIN ? att_lo(pos0 + q0 + 1, window) : 0;        // first key any query of this wave attends to
+  int qlo = 0;                                                 // SEG: first key THIS query attends to (both masks)
+  if constexpr (SEG) {                                         // (a wave past the last row reads the last row's entry: its results are dropped)
+    const int last = pos0 + S - 1;
+    kt_lo_ = max(att_lo(pos0 + wgt * QT * 32 + 1, WIN ? window : 0), seg_lo[pos0 + wgt * QT * 32]) & ~63;
+    my_lo_ = max(my_lo_, seg_lo[min(pos0 + q0, last)]);
+    qlo = max(att_lo(qpos + 1, WIN ? window : 0), seg_lo[min(qpos, last)]);
+  }
+  const int kt_lo = kt_lo_, my_lo = my_lo_;
   uint4 qf[NC];
   {
     const float* qp = qkv + (size_t)qrow * (nq + 2 * nkv) * HD + (size_t)head * HD + 8 * h;
@@ -432,7 +479,7 @@ __global__ __launch_bounds__(256) void k_pf_attn_mfma(const float* __restrict__ 
     }
     __syncthreads();
     { const int ktn = kt0 + 64 < kmax ? kt0 + 64 : kt0; PFA_GLOAD(ktn) }                  // lands under this tile's arithmetic (last tile: a redundant reload, never a branch around the loads -- under one, hipcc kept the prefetch registers in scratch)
-    if (kt0 <= my_last && (!WIN || kt0 + 63 >= my_lo)) {      // wave-uniform: later (WIN: and earlier) tiles are fully masked for this wave
+    if (kt0 <= my_last && (!(WIN || SEG) || kt0 + 63 >= my_lo)) {      // wave-uniform: later (WIN / SEG: and earlier) tiles are fully masked for this wave
       f32x16 st[2];
 #pragma unroll
       for (int kb = 0; kb < 2; kb++) {
@@ -450,7 +497,7 @@ __global__ __launch_bounds__(256) void k_pf_attn_mfma(const float* __restrict__ 
 #pragma unroll
         for (int i = 0; i < 16; i++) {
           const int kp = kt0 + 32 * kb + (i & 3) + 8 * (i >> 2) + 4 * h;
-          const float v = (kp > qpos || (WIN && kp < att_lo(qpos + 1, window))) ? -INFINITY : st[kb][i] * scale;
+          const float v = (kp > qpos || (SEG ? kp < qlo : (WIN && kp < att_lo(qpos + 1, window)))) ? -INFINITY : st[kb][i] * scale;
           st[kb][i] = v; mx = fmaxf(mx, v);
         }
       mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -459,7 +506,7 @@ __global__ __launch_bounds__(256) void k_pf_attn_mfma(const float* __restrict__ 
       // makes alpha and every p of that tile 0 (l and o stay 0), and the next tile with a visible key resets m (alpha = exp(-1e30 - mn) = 0).  Every query sees its
       // own key in a tile the wave processes, so l > 0 at the end.
       const float mn_ = fmaxf(m, mx);
-      const float mn = (WIN && mn_ == -INFINITY) ? -1e30f : mn_;
+      const float mn = ((WIN || SEG) && mn_ == -INFINITY) ? -1e30f : mn_;
       const float alpha = bz_expf(m - mn);
       float ps = 0.f;
 #pragma unroll
@@ -1406,6 +1453,14 @@ int bzk_pf_rope_kv(hipStream_t s, float* qkv, int S, int nq, int nkv, int hd, co
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }
+// packed prompt batch: rows pos0 .. pos0 + S - 1 of the packed batch into rows of the same index of a contiguous cache, each rotated by its position in its own input
+int bzk_pf_rope_kv_seg(hipStream_t s, float* qkv, int S, int nq, int nkv, int hd, const float* cos_t, const float* sin_t, int interleaved, int pos0, int act,
+                       const KvView& kv, int layer, const int* seg_lo) {
+  if (kv.paged || !seg_lo) BZ_FAIL(BZ_E_INVALID, "packed prompt rows: a contiguous cache and the rows' segment starts are needed");
+  hipLaunchKernelGGL(k_pf_rope_kv_seg, dim3(S, nq + 2 * nkv), dim3(64), 0, s, qkv, nq, nkv, hd, cos_t, sin_t, interleaved, pos0, act, kv, layer, seg_lo);
+  BZ_HIP(hipGetLastError());
+  return BZ_OK;
+}
 bool bzk_pf_attn_mfma_ok(int hd, int rep) {     // prompts: the MFMA flash kernel (any context length)
   static const bool off = getenv("BZ_NO_PF_ATTN_MFMA") != nullptr;
   return !off && (hd == 64 || hd == 128) && (rep == 1 || rep == 2 || rep == 4 || rep == 8);
@@ -1415,21 +1470,25 @@ size_t bzk_pf_attn_smem(int nq, int nkv, int hd, int len, bool exact) {
   return (size_t)(8 * REP + RPP * REP * hd) * (exact ? 8 : 4) + (size_t)REP * len * 4 + 64;
 }
 int bzk_pf_attn(hipStream_t s, int dt, const float* qkv, int S, int nq, int nkv, int hd, int pos0, int act, const KvView& kv, int layer, void* out16,
-                const int* row_pos, int table_stride, int max_len, int form, int window) {
+                const int* row_pos, int table_stride, int max_len, int form, int window, const int* seg_lo) {
+  // seg_lo (packed prompt batch; else nullptr): pos0 is the chunk's first packed row, max_len the longest input, the cache contiguous with row = packed row.
   // form: the plan's (bz_route.hip) -- launched as named or refused, never replaced.  MFMA: one prompt, 16-bit; SCALAR / SCALAR_EXACT: the scalar kernel,
   // plain or exact sums; ROWS: a decode batch's rows on the scalar kernel (f32 caches: exact sums, as their prompts)
   const int REP = nq / nkv;
   if (hd % 8 || hd > 256 || (256 % (hd / 8)) || (REP != 1 && REP != 2 && REP != 4 && REP != 8) || kv.dtype != dt ||
       (form == BZ_PF_ATTN_MFMA ? row_pos || dt == BZ_F32 || !bzk_pf_attn_mfma_ok(hd, REP) : form == BZ_PF_ATTN_ROWS ? !row_pos : form != BZ_PF_ATTN_SCALAR && form != BZ_PF_ATTN_SCALAR_EXACT))
     BZ_FAIL(BZ_E_UNSUPPORTED, "prefill attention: head_dim %d / group size %d / cache dtype unsupported", hd, REP);
+  if (seg_lo && (row_pos || kv.paged || form == BZ_PF_ATTN_ROWS)) BZ_FAIL(BZ_E_INVALID, "prefill attention: a packed batch takes a contiguous cache and a prompt form");
   const bool exact = form == BZ_PF_ATTN_SCALAR_EXACT || (form == BZ_PF_ATTN_ROWS && dt == BZ_F32);
   if (form == BZ_PF_ATTN_MFMA) {
     const float scale_m = div_rn(1.0f, sqrt_rn((float)hd));
     const int HW = REP < 4 ? REP : 4, QT = 4 / HW;
     const dim3 grid((S + 32 * QT - 1) / (32 * QT), nkv, REP / HW);
     const double flops = 4.0 * nq * hd * ((double)S * pos0 + 0.5 * (double)S * S);
-#define LAUNCH_PFM_(DT, HD, R, PG, WN) BZ_LAUNCH("pf_attn_mfma", flops, (k_pf_attn_mfma<DT, HD, R, PG, WN>), grid, dim3(256), 0, s, qkv, S, nq, nkv, pos0, act, kv, layer, scale_m, (unsigned short*)out16, window)
-#define LAUNCH_PFM(DT, HD, R) do { if (window > 0) { if (kv.paged) LAUNCH_PFM_(DT, HD, R, true, true); else LAUNCH_PFM_(DT, HD, R, false, true); } \
+#define LAUNCH_PFM_(DT, HD, R, PG, WN) BZ_LAUNCH("pf_attn_mfma", flops, (k_pf_attn_mfma<DT, HD, R, PG, WN>), grid, dim3(256), 0, s, qkv, S, nq, nkv, pos0, act, kv, layer, scale_m, (unsigned short*)out16, window, (const int*)nullptr)
+#define LAUNCH_PFM_SEG(DT, HD, R, WN) BZ_LAUNCH("pf_attn_mfma_seg", flops, (k_pf_attn_mfma<DT, HD, R, false, WN, true>), grid, dim3(256), 0, s, qkv, S, nq, nkv, pos0, act, kv, layer, scale_m, (unsigned short*)out16, window, seg_lo)
+#define LAUNCH_PFM(DT, HD, R) do { if (seg_lo) { if (window > 0) LAUNCH_PFM_SEG(DT, HD, R, true); else LAUNCH_PFM_SEG(DT, HD, R, false); } \
+                                   else if (window > 0) { if (kv.paged) LAUNCH_PFM_(DT, HD, R, true, true); else LAUNCH_PFM_(DT, HD, R, false, true); } \
                                    else { if (kv.paged) LAUNCH_PFM_(DT, HD, R, true, false); else LAUNCH_PFM_(DT, HD, R, false, false); } } while (0)
 #define LAUNCH_PFM_R(DT, HD) do { if (REP == 1) LAUNCH_PFM(DT, HD, 1); else if (REP == 2) LAUNCH_PFM(DT, HD, 2); else if (REP == 4) LAUNCH_PFM(DT, HD, 4); else LAUNCH_PFM(DT, HD, 8); } while (0)
 #define LAUNCH_PFM_H(DT) do { if (hd == 64) LAUNCH_PFM_R(DT, 64); else LAUNCH_PFM_R(DT, 128); } while (0)
@@ -1437,19 +1496,21 @@ int bzk_pf_attn(hipStream_t s, int dt, const float* qkv, int S, int nq, int nkv,
 #undef LAUNCH_PFM_H
 #undef LAUNCH_PFM_R
 #undef LAUNCH_PFM
+#undef LAUNCH_PFM_SEG
 #undef LAUNCH_PFM_
     BZ_HIP(hipGetLastError());
     return BZ_OK;
   }
-  const int ctx_full = row_pos ? max_len : pos0 + S, ctx = window > 0 ? std::min(ctx_full, window) : ctx_full;   // a row's score buffer: its window
+  const int ctx_full = (row_pos || seg_lo) ? max_len : pos0 + S, ctx = window > 0 ? std::min(ctx_full, window) : ctx_full;   // a row's score buffer: its window
   const size_t smem = bzk_pf_attn_smem(nq, nkv, hd, ctx, exact);
   if (smem > 160 * 1024) BZ_FAIL(BZ_E_UNSUPPORTED, "prefill attention: context %d too long for this kernel", ctx);
   const float scale = div_rn(1.0f, sqrt_rn((float)hd));
-#define LAUNCH_PFA_(DT, R, EX, WN) do { \
+#define LAUNCH_PFA_(DT, R, EX, WN, SG) do { \
     static bool attr_done = false; \
-    if (!attr_done) { BZ_HIP(hipFuncSetAttribute((const void*)k_pf_attn<DT, DT, R, EX, WN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_done = true; } \
-    hipLaunchKernelGGL((k_pf_attn<DT, DT, R, EX, WN>), dim3(S, nkv), dim3(256), smem, s, qkv, nq, nkv, hd, pos0, act, kv, layer, scale, out16, row_pos, table_stride, window); } while (0)
-#define LAUNCH_PFA(DT, R, EX) do { if (window > 0) LAUNCH_PFA_(DT, R, EX, true); else LAUNCH_PFA_(DT, R, EX, false); } while (0)
+    if (!attr_done) { BZ_HIP(hipFuncSetAttribute((const void*)k_pf_attn<DT, DT, R, EX, WN, SG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_done = true; } \
+    hipLaunchKernelGGL((k_pf_attn<DT, DT, R, EX, WN, SG>), dim3(S, nkv), dim3(256), smem, s, qkv, nq, nkv, hd, pos0, act, kv, layer, scale, out16, row_pos, table_stride, window, seg_lo); } while (0)
+#define LAUNCH_PFA(DT, R, EX) do { if (seg_lo) { if (window > 0) LAUNCH_PFA_(DT, R, EX, true, true); else LAUNCH_PFA_(DT, R, EX, false, true); } \
+                                   else if (window > 0) LAUNCH_PFA_(DT, R, EX, true, false); else LAUNCH_PFA_(DT, R, EX, false, false); } while (0)
 #define LAUNCH_PFA_R(DT, EX) do { if (REP == 1) LAUNCH_PFA(DT, 1, EX); else if (REP == 2) LAUNCH_PFA(DT, 2, EX); else if (REP == 4) LAUNCH_PFA(DT, 4, EX); else LAUNCH_PFA(DT, 8, EX); } while (0)
   if (exact) { if (dt == BZ_F16) LAUNCH_PFA_R(BZ_F16, true); else if (dt == BZ_F32) LAUNCH_PFA_R(BZ_F32, true); else LAUNCH_PFA_R(BZ_BF16, true); }
   else { if (dt == BZ_F16) LAUNCH_PFA_R(BZ_F16, false); else if (dt == BZ_F32) LAUNCH_PFA_R(BZ_F32, false); else LAUNCH_PFA_R(BZ_BF16, false); }
@@ -1501,4 +1562,72 @@ int bzk_pf_split3(hipStream_t s, const float* x, int S, int K, void* xs, float* 
   hipLaunchKernelGGL(k_pf_split3, dim3(S), dim3(256), 0, s, x, K, (unsigned short*)xs, rscale, wscale);
   BZ_HIP(hipGetLastError());
   return BZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// op level: the attention of a packed prompt batch on its own (tests/test_gpu_packed_attn.py), as bz_pool_rows is for the pooling kernels
+// ---------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+// rows of rotated [q | k | v] F32 -> K / V rows of a contiguous one-layer cache [nkv][T][hd], rounded to `dt`        grid = (T, 2 nkv), 64 threads
+__global__ __launch_bounds__(64) void k_pk_stage(const float* qkv, int T, int nq, int nkv, int hd, int dt, void* kc, void* vc) {
+  const int s = blockIdx.x, j = blockIdx.y, kvh = j % nkv;
+  const float* src = qkv + (size_t)s * (nq + 2 * nkv) * hd + (size_t)(nq + j) * hd;
+  void* base = j >= nkv ? vc : kc;
+  const size_t off = ((size_t)kvh * T + s) * hd;
+  for (int i = threadIdx.x; i < hd; i += 64) {
+    const float x = src[i];
+    if (dt == BZ_F16) ((__half*)base)[off + i] = f16_cvt(x);
+    else if (dt == BZ_BF16) ((unsigned short*)base)[off + i] = to16<BZ_BF16>(x);
+    else ((float*)base)[off + i] = x;
+  }
+}
+__global__ void k_pk_widen(const void* x, int dt, size_t n, float* y) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    y[i] = dt == BZ_F32 ? ((const float*)x)[i] : dt == BZ_F16 ? from16<BZ_F16>(((const unsigned short*)x)[i]) : from16<BZ_BF16>(((const unsigned short*)x)[i]);
+}
+}  // namespace
+
+extern "C" int bz_attn_packed(bz_device* dev, const bz_tensor* qkv, const int32_t* seq_lens, int n_seq, int nq, int nkv, int hd, int dt, int form, int window,
+                              bz_tensor* out) {
+  BZ_API_BEGIN
+  if (!dev) BZ_FAIL(BZ_E_INVALID, "attn_packed: null device");
+  std::vector<int> seg_lo;
+  int max_len = 0;
+  BZ_TRY(bzk_packed_lens(seq_lens, n_seq, "attn_packed", &seg_lo, nullptr, &max_len));
+  const int T = (int)seg_lo.size();
+  if (nq <= 0 || nkv <= 0 || nq % nkv || hd <= 0) BZ_FAIL(BZ_E_INVALID, "attn_packed: %d query heads over %d kv heads of %d", nq, nkv, hd);
+  if (dt != BZ_F16 && dt != BZ_BF16 && dt != BZ_F32) BZ_FAIL(BZ_E_INVALID, "attn_packed: dt = %d (F16, BF16 or F32)", dt);
+  if (form != BZ_PF_ATTN_MFMA && form != BZ_PF_ATTN_SCALAR && form != BZ_PF_ATTN_SCALAR_EXACT) BZ_FAIL(BZ_E_INVALID, "attn_packed: form = %d (MFMA, SCALAR or SCALAR_EXACT)", form);
+  if (window < 0) BZ_FAIL(BZ_E_INVALID, "attn_packed: window = %d (0: none)", window);
+  const size_t qw = (size_t)(nq + 2 * nkv) * hd, ow = (size_t)nq * hd;
+  if (!qkv || qkv->dtype != BZ_F32 || qkv->nbytes < (size_t)T * qw * 4) BZ_FAIL(BZ_E_INVALID, "attn_packed: qkv must be F32 [%d, %zu]", T, qw);
+  if (!out || out->dtype != BZ_F32 || out->nbytes < (size_t)T * ow * 4) BZ_FAIL(BZ_E_INVALID, "attn_packed: out must be F32 [%d, %zu]", T, ow);
+  std::lock_guard<std::mutex> dlock__(dev->mu);
+  BZ_HIP(hipSetDevice(dev->id));
+  hipStream_t st = dev->stream;
+  const size_t es = dt == BZ_F32 ? 4 : 2, cb = (size_t)nkv * T * hd * es;
+  void *kc = nullptr, *vc = nullptr, *o16 = nullptr; int* dlo = nullptr;
+  auto cleanup = [&] { hipStreamSynchronize(st); for (void* p : {kc, vc, o16, (void*)dlo}) if (p) hipFree(p); };
+  if (hipMalloc(&kc, cb) != hipSuccess || hipMalloc(&vc, cb) != hipSuccess || hipMalloc(&o16, (size_t)T * ow * es) != hipSuccess || hipMalloc((void**)&dlo, (size_t)T * 4) != hipSuccess) {
+    (void)hipGetLastError(); cleanup(); BZ_FAIL(BZ_E_OOM, "attn_packed: out of device memory");
+  }
+  int rc = BZ_OK;
+  if (hipMemcpy(dlo, seg_lo.data(), (size_t)T * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); cleanup(); BZ_FAIL(BZ_E_HIP, "attn_packed: copy of the segment starts failed"); }
+  KvView kv{};
+  kv.k = kc; kv.v = vc; kv.dtype = dt; kv.hd = hd; kv.n_kv = nkv; kv.paged = 0; kv.layer_stride = (long long)nkv * T * hd; kv.cap = T; kv.bs = 1;
+  hipLaunchKernelGGL(k_pk_stage, dim3(T, 2 * nkv), dim3(64), 0, st, (const float*)qkv->ptr, T, nq, nkv, hd, dt, kc, vc);
+  // the model's chunking: rows in chunks of 2048, later chunks read earlier chunks' keys from the cache
+  for (int s0 = 0; s0 < T && rc == BZ_OK; s0 += 2048) {
+    const int n = std::min(2048, T - s0);
+    // (one input: no segment starts -- the plain prompt launch, as a single bz_embed_kv / bz_score_kv call runs it)
+    rc = bzk_pf_attn(st, dt, (const float*)qkv->ptr + (size_t)s0 * qw, n, nq, nkv, hd, s0, dt, kv, 0, (char*)o16 + (size_t)s0 * ow * es, nullptr, 0, max_len, form, window,
+                     n_seq == 1 ? nullptr : dlo);
+  }
+  if (rc == BZ_OK) {
+    hipLaunchKernelGGL(k_pk_widen, dim3(512), dim3(256), 0, st, (const void*)o16, dt, (size_t)T * ow, (float*)out->ptr);
+    if (hipGetLastError() != hipSuccess) { bz_set_error("attn_packed: launch failed"); rc = BZ_E_HIP; }
+  }
+  cleanup();
+  return rc;
+  BZ_API_END
 }

@@ -3,7 +3,9 @@
 // tests/prompt_plan_ref.py can restate it and tests/test_prompt_plan.py can sweep it without a device.  The callers in bz_host.hip dispatch on the plan and
 // hand it to the prompt functions; bzk_pf_attn launches the attention form it names and refuses one whose preconditions do not hold.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <vector>
 
 #include "bz_internal.h"
 
@@ -112,6 +114,73 @@ extern "C" int bz_prompt_plan(const bz_prompt_traits_t* t, const bz_prompt_switc
   else if (kind != BZ_PLAN_PROMPT) return BZ_OK;     // decode batches and the verify are built for the Llama family
   else if (t->arch == BZ_ARCH_DEEPSEEK2) plan_dsv2(*t, *sw, rows, total_len, kv_dtype, min_rows, out);
   else if (t->arch == BZ_ARCH_MAMBA2) plan_mamba(*t, *sw, rows, min_rows, out);
+  return BZ_OK;
+  BZ_API_END
+}
+
+// ---- packed prompt batches: n_seq inputs laid end to end, one prompt pass for all of them -------------------------------------------------
+int bzk_packed_lens(const int32_t* seq_lens, int n_seq, const char* who, std::vector<int>* seg_lo, std::vector<int>* seg_off, int* max_len) {
+  if (!seq_lens || n_seq <= 0) BZ_FAIL(BZ_E_INVALID, "%s: n_seq = %d inputs (at least 1, with their lengths)", who, n_seq);
+  long long T = 0;
+  int ml = 0;
+  for (int i = 0; i < n_seq; i++) {
+    if (seq_lens[i] <= 0) BZ_FAIL(BZ_E_INVALID, "%s: seq_lens[%d] = %d (every input has at least one token)", who, i, seq_lens[i]);
+    T += seq_lens[i]; ml = std::max(ml, (int)seq_lens[i]);
+    if (T >= (1ll << 31)) BZ_FAIL(BZ_E_INVALID, "%s: %lld packed rows and more (below 2^31)", who, T);
+  }
+  if (seg_off) { seg_off->resize((size_t)n_seq + 1); (*seg_off)[0] = 0; for (int i = 0; i < n_seq; i++) (*seg_off)[i + 1] = (*seg_off)[i] + seq_lens[i]; }
+  if (seg_lo) {
+    seg_lo->resize((size_t)T);
+    size_t r = 0;
+    for (int i = 0; i < n_seq; i++) { const int lo = (int)r; for (int k = 0; k < seq_lens[i]; k++) (*seg_lo)[r++] = lo; }
+  }
+  if (max_len) *max_len = ml;
+  return BZ_OK;
+}
+
+// One packed pass exactly when the prompt plan of T = sum(seq_lens) rows answers ROWS at a context of the LONGEST input: a query reads its own input's keys and
+// nothing else, so the longest input is what the scalar attention's score buffer has to hold.  Everything else (odd GQA groups, DeepSeek-V2, Mamba2, T below the
+// row floor, models whose plan is STEPS) takes the single-input path once per input inside the library: packed = 0, and `plan` is the plan of the longest input.
+extern "C" int bz_packed_plan(const bz_prompt_traits_t* t, const bz_prompt_switches_t* sw, const int32_t* seq_lens, int n_seq, int kv_dtype, bz_packed_plan_t* out) {
+  BZ_API_BEGIN
+  if (!t || !out) BZ_FAIL(BZ_E_INVALID, "packed_plan: bad argument");
+  std::vector<int> off;
+  int max_len = 0;
+  BZ_TRY(bzk_packed_lens(seq_lens, n_seq, "packed_plan", nullptr, &off, &max_len));
+  const int T = off[(size_t)n_seq];
+  bz_prompt_plan_t p;
+  BZ_TRY(bz_prompt_plan(t, sw, BZ_PLAN_PROMPT, T, max_len, kv_dtype, &p));
+  out->packed = p.route == BZ_ROUTE_ROWS ? 1 : 0;
+  out->rows = T; out->n_seq = n_seq; out->max_len = max_len;
+  if (!out->packed) BZ_TRY(bz_prompt_plan(t, sw, BZ_PLAN_PROMPT, max_len, max_len, kv_dtype, &p));
+  out->plan = p;
+  return BZ_OK;
+  BZ_API_END
+}
+
+// the two host-side definitions of bz_score_batch, public as bz_score_row_spec is: a CPU-only test holds them to an independent restatement
+extern "C" int bz_packed_targets_spec(const int64_t* tokens, const int32_t* seq_lens, int n_seq, int64_t* targets_out) {
+  BZ_API_BEGIN
+  std::vector<int> off;
+  BZ_TRY(bzk_packed_lens(seq_lens, n_seq, "packed_targets_spec", nullptr, &off, nullptr));
+  if (!tokens || !targets_out) BZ_FAIL(BZ_E_INVALID, "packed_targets_spec: null tokens / targets_out");
+  for (int i = 0; i < n_seq; i++) {      // every row reads the next token of its own input; an input's last row is not scored
+    for (int r = off[i]; r + 1 < off[i + 1]; r++) targets_out[r] = tokens[r + 1];
+    targets_out[(size_t)off[i + 1] - 1] = -1;
+  }
+  return BZ_OK;
+  BZ_API_END
+}
+extern "C" int bz_packed_totals_spec(const bz_score_row* rows, const int32_t* seq_lens, int n_seq, bz_score_total* totals_out) {
+  BZ_API_BEGIN
+  std::vector<int> off;
+  BZ_TRY(bzk_packed_lens(seq_lens, n_seq, "packed_totals_spec", nullptr, &off, nullptr));
+  if (!rows || !totals_out) BZ_FAIL(BZ_E_INVALID, "packed_totals_spec: null rows / totals_out");
+  for (int i = 0; i < n_seq; i++) {      // per input, in row order, over the scored rows whose logprob is finite -- as a single call's total
+    totals_out[i].sum_logprob = 0.0; totals_out[i].n_scored = 0;
+    for (int r = off[i]; r < off[i + 1]; r++)
+      if (rows[r].n_top >= 0 && std::isfinite(rows[r].logprob)) { totals_out[i].sum_logprob += (double)rows[r].logprob; totals_out[i].n_scored++; }
+  }
   return BZ_OK;
   BZ_API_END
 }

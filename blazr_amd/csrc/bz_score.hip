@@ -28,6 +28,7 @@
 // that (the reference's own test vectors come out identical either way).  normalize: norm = sqrt(sum_j (double)v_j^2) (any order: the squares are exact in double),
 // v_j = (float)((double)v_j / norm) if norm > 1e-12, else unchanged (pooling.rs:40-47).
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -176,6 +177,24 @@ __global__ __launch_bounds__(256) void k_pool_mean_finish(const double* dsum, in
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j < H) out[j] = (float)(dsum[j] / (double)S);
 }
+// Packed prompt batch: the rows of a chunk (packed rows s0 .. s0 + n - 1) belong to inputs seg0 .. seg0 + gridDim.y - 1, input i owning packed rows off[i] ..
+// off[i + 1] - 1.  Thread (column j, input i) walks the input's rows INSIDE this chunk in row order: MEAN carries the column's double sum (from dsum[i][j] when the
+// input began in an earlier chunk; to dsum when it goes on in a later one) and stores (float)(sum / len) with the input's last row -- bz_pool_spec of the input's
+// rows, bit for bit; CLS / LAST copy the input's first / last row when the chunk holds it.       grid = (ceil(H / 256), inputs in the chunk)
+__global__ __launch_bounds__(256) void k_pool_seg(const float* __restrict__ rows, int s0, int n, int H, const int* __restrict__ off, int seg0, int pooling, double* dsum,
+                                                  float* __restrict__ out) {
+  const int j = blockIdx.x * 256 + threadIdx.x, i = seg0 + blockIdx.y;
+  if (j >= H) return;
+  const int beg = off[i], end = off[i + 1], a = max(beg, s0), b = min(end, s0 + n);
+  if (a >= b) return;
+  const float* x = rows + (size_t)(a - s0) * H + j;
+  if (pooling == BZ_POOL_CLS) { if (a == beg) out[(size_t)i * H + j] = x[0]; return; }
+  if (pooling == BZ_POOL_LAST) { if (b == end) out[(size_t)i * H + j] = x[(size_t)(b - 1 - a) * H]; return; }
+  double acc = a == beg ? 0.0 : dsum[(size_t)i * H + j];
+  for (int r = 0; r < b - a; r++) acc += (double)x[(size_t)r * H];
+  if (b == end) out[(size_t)i * H + j] = (float)(acc / (double)(end - beg));
+  else dsum[(size_t)i * H + j] = acc;
+}
 // one block per vector
 __global__ __launch_bounds__(256) void k_pool_normalize(float* v, int H) {
   float* x = v + (size_t)blockIdx.x * H;
@@ -199,8 +218,10 @@ struct BzSinkWs {
   float* pmax = nullptr; u64* S = nullptr; unsigned* rank = nullptr; u64* cand = nullptr;   // one sub-batch
   const long long* tg_use = nullptr; int cS = 0; long long cV = 0; int ctop = 0;           // the call in flight
   // pooling
-  float* hid = nullptr; size_t hid_elems = 0; double* dsum = nullptr; int dsum_h = 0;
+  float* hid = nullptr; size_t hid_elems = 0; double* dsum = nullptr; size_t dsum_elems = 0;   // column sums: H doubles (a single prompt), n_seq * H (MEAN over a packed batch)
   int pS = 0, pH = 0, prows = 0; bz_embed_config pcfg{};
+  // pooling per input of a packed batch (n_seq > 0): inputs' first packed rows, [n_seq + 1], on the host and on the device (the caller's; it outlives the call)
+  int n_seq = 0; std::vector<int> seg_off; const int* seg_off_dev = nullptr;
 };
 
 void bzk_sink_free(BzSinkWs* w) {
@@ -309,12 +330,24 @@ int bzk_pool_begin(hipStream_t st, BzSinkWs** wp, int S, int H, int rows, const 
   if (!*wp) *wp = new BzSinkWs();
   BzSinkWs* w = *wp;
   const size_t hid_need = (size_t)(rows + 2) * H;
-  if (hid_need > w->hid_elems || H > w->dsum_h) {
+  if (hid_need > w->hid_elems || (size_t)H > w->dsum_elems) {
     BZ_HIP(hipStreamSynchronize(st));
     if (hid_need > w->hid_elems) { w->hid_elems = 0; BZ_TRY(sink_grow(&w->hid, hid_need * 4, "embed: rows workspace")); w->hid_elems = hid_need; }
-    if (H > w->dsum_h) { w->dsum_h = 0; BZ_TRY(sink_grow(&w->dsum, (size_t)H * 8, "embed: column sums")); w->dsum_h = H; }
+    if ((size_t)H > w->dsum_elems) { w->dsum_elems = 0; BZ_TRY(sink_grow(&w->dsum, (size_t)H * 8, "embed: column sums")); w->dsum_elems = (size_t)H; }
   }
-  w->pS = S; w->pH = H; w->prows = rows; w->pcfg = *cfg;
+  w->pS = S; w->pH = H; w->prows = rows; w->pcfg = *cfg; w->n_seq = 0;
+  return BZ_OK;
+}
+// a packed batch of n_seq inputs (S = off[n_seq] rows in all): the result is [n_seq, H], one pooled vector per input (NONE: all S rows)
+int bzk_pool_begin_seg(hipStream_t st, BzSinkWs** wp, int S, int H, int rows, const bz_embed_config* cfg, const int* seg_off_host, const int* seg_off_dev, int n_seq) {
+  BZ_TRY(bzk_pool_begin(st, wp, S, H, rows, cfg));
+  BzSinkWs* w = *wp;
+  const size_t need = (size_t)n_seq * H;      // only MEAN carries sums (k_pool_seg); CLS / LAST / NONE copy rows
+  if (cfg->pooling == BZ_POOL_MEAN && need > w->dsum_elems) {
+    BZ_HIP(hipStreamSynchronize(st));
+    w->dsum_elems = 0; BZ_TRY(sink_grow(&w->dsum, need * 8, "embed: column sums")); w->dsum_elems = need;
+  }
+  w->n_seq = n_seq; w->seg_off.assign(seg_off_host, seg_off_host + n_seq + 1); w->seg_off_dev = seg_off_dev;
   return BZ_OK;
 }
 float* bzk_pool_rows_ws(BzSinkWs* w) { return w->hid; }
@@ -324,6 +357,16 @@ int bzk_pool_chunk(hipStream_t st, BzSinkWs* w, const float* rows, int n, int s0
   const int S = w->pS, H = w->pH;
   if (s0 < 0 || n <= 0 || s0 + n > S) BZ_FAIL(BZ_E_INVALID, "embed: rows %d .. %d outside the call's %d", s0, s0 + n, S);
   const size_t rb = (size_t)H * 4;
+  if (w->n_seq > 0 && w->pcfg.pooling != BZ_POOL_NONE) {
+    // the inputs with a row in this chunk: the one holding s0 .. the one holding s0 + n - 1
+    const int i0 = (int)(std::upper_bound(w->seg_off.begin(), w->seg_off.end(), s0) - w->seg_off.begin()) - 1;
+    const int i1 = (int)(std::upper_bound(w->seg_off.begin(), w->seg_off.end(), s0 + n - 1) - w->seg_off.begin()) - 1;
+    for (int y0 = i0; y0 <= i1; y0 += 65535) {
+      hipLaunchKernelGGL(k_pool_seg, dim3((H + 255) / 256, std::min(65535, i1 - y0 + 1)), dim3(256), 0, st, rows, s0, n, H, w->seg_off_dev, y0, (int)w->pcfg.pooling, w->dsum, out);
+    }
+    BZ_HIP(hipGetLastError());
+    return BZ_OK;
+  }
   switch (w->pcfg.pooling) {
     case BZ_POOL_NONE: BZ_HIP(hipMemcpyAsync(out + (size_t)s0 * H, rows, (size_t)n * rb, hipMemcpyDeviceToDevice, st)); break;
     case BZ_POOL_CLS: if (s0 == 0) BZ_HIP(hipMemcpyAsync(out, rows, rb, hipMemcpyDeviceToDevice, st)); break;
@@ -336,8 +379,9 @@ int bzk_pool_chunk(hipStream_t st, BzSinkWs* w, const float* rows, int n, int s0
 }
 int bzk_pool_end(hipStream_t st, BzSinkWs* w, float* out) {
   const int S = w->pS, H = w->pH;
-  if (w->pcfg.pooling == BZ_POOL_MEAN) hipLaunchKernelGGL(k_pool_mean_finish, dim3((H + 255) / 256), dim3(256), 0, st, w->dsum, S, H, out);
-  if (w->pcfg.normalize) hipLaunchKernelGGL(k_pool_normalize, dim3(w->pcfg.pooling == BZ_POOL_NONE ? S : 1), dim3(256), 0, st, out, H);
+  if (w->pcfg.pooling == BZ_POOL_MEAN && w->n_seq == 0) hipLaunchKernelGGL(k_pool_mean_finish, dim3((H + 255) / 256), dim3(256), 0, st, w->dsum, S, H, out);
+  if (w->pcfg.normalize) hipLaunchKernelGGL(k_pool_normalize, dim3(w->pcfg.pooling == BZ_POOL_NONE ? S : std::max(w->n_seq, 1)), dim3(256), 0, st, out, H);
+  w->n_seq = 0;
   BZ_HIP(hipGetLastError());
   return BZ_OK;
 }

@@ -630,6 +630,58 @@ class LoadedModel:
             L.check(L.lib().bz_embed_kv(self.h, t.h, S, cache.h, int(position), C.byref(cfg), out.h))
         return out.to_numpy().reshape(out.shape)
 
+    # --- packed prompt batches: many inputs per pass (bz_embed_batch / bz_score_batch) ---------------------------------------------------------------
+    def _packed(self, inputs, who):
+        lens = np.asarray([len(x) for x in inputs], dtype=np.int32)
+        if len(lens) == 0 or (lens <= 0).any():
+            raise ValueError("%s: %d inputs, the shortest of %d tokens (at least one input, every input at least one token)" % (who, len(lens), int(lens.min()) if len(lens) else 0))
+        flat = np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in inputs])
+        return self.dev.tensor(flat), lens, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+
+    def embed_batch(self, inputs, cache, pooling="mean", normalize=False):
+        """embed() of many inputs in one prompt pass (/v1/embeddings with a list, /rerank): `inputs` is a list of token lists, `cache` a LayeredKvCache used as
+        scratch (it must hold sum(len) rows; left reset).  -> f32 [n_seq, hidden]; "none": a list of [len_i, hidden].  A LayeredSsmState loops the single call."""
+        if isinstance(cache, LayeredSsmState):
+            res = []
+            for x in inputs:
+                cache.reset()
+                res.append(self.embed(x, cache, pooling=pooling, normalize=normalize))
+            return res if pooling == "none" else np.stack(res)
+        t, lens, off = self._packed(inputs, "embed_batch")
+        if pooling not in L.POOLINGS:
+            raise ValueError("embed: pooling %r (one of %s)" % (pooling, ", ".join(sorted(L.POOLINGS))))
+        cfg = L.EmbedConfig(pooling=L.POOLINGS[pooling], normalize=int(bool(normalize)))
+        out = self.dev.zeros((int(off[-1]) if pooling == "none" else len(lens), self.c.hidden), L.F32)
+        L.check(L.lib().bz_embed_batch(self.h, t.h, _ptr(lens), len(lens), cache.h, C.byref(cfg), out.h))
+        a = out.to_numpy().reshape(out.shape)
+        return [a[off[i]:off[i + 1]] for i in range(len(lens))] if pooling == "none" else a
+
+    def score_batch(self, inputs, cache, targets=None, top_logprobs=0):
+        """score() of many inputs in one prompt pass: `inputs` a list of token lists, `targets` None (each token given its predecessors inside its own input) or a
+        list of per-input target lists.  -> a list of the dicts score() returns.  A LayeredSsmState loops the single call."""
+        if isinstance(cache, LayeredSsmState):
+            res = []
+            for i, x in enumerate(inputs):
+                cache.reset()
+                res.append(self.score(x, cache, targets=None if targets is None else targets[i], top_logprobs=top_logprobs))
+            return res
+        t, lens, off = self._packed(inputs, "score_batch")
+        T, n = int(off[-1]), len(lens)
+        tg = None
+        if targets is not None:
+            tg = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in targets]), dtype=np.int64)
+            if len(targets) != n or any(len(x) != k for x, k in zip(targets, lens)):
+                raise ValueError("score_batch: targets must hold one list per input, of the input's length")
+        cfg = L.ScoreConfig(top_n=int(top_logprobs))
+        rows, tots = (L.ScoreRow * T)(), (L.ScoreTotal * n)()
+        L.check(L.lib().bz_score_batch(self.h, t.h, _ptr(lens), n, cache.h, _ptr(tg) if tg is not None else None, C.byref(cfg), rows, tots))
+        r = np.frombuffer(bytes(rows), dtype=SCORE_ROW).copy()
+        res = []
+        for i in range(n):
+            ssum, k = float(tots[i].sum_logprob), int(tots[i].n_scored)
+            res.append(dict(rows=r[off[i]:off[i + 1]], sum_logprob=ssum, n_scored=k, perplexity=float(np.exp(-ssum / k)) if k else float("nan")))
+        return res
+
     def embed_paged(self, tokens, cache, slot_mapping, block_table, seq_len_k, start_pos, pooling="mean", normalize=False):
         t, S = self._tokens(tokens)
         sm = slot_mapping if isinstance(slot_mapping, Tensor) else self.dev.tensor(np.asarray(slot_mapping, dtype=np.int32))
@@ -944,6 +996,47 @@ def prompt_plan(traits, kind, rows, total_len, kv_dtype=L.F16, switches=None):
     return dict(route=p.route, exact=p.exact, attn=p.attn, head=p.head, chunk=p.chunk)
 
 
+def packed_plan(traits, seq_lens, kv_dtype=L.F16, switches=None):
+    """bz_packed_plan (host only): what a packed prompt batch of these input lengths does -> dict(packed, rows, n_seq, max_len, plan = the prompt_plan dict)"""
+    sl = np.ascontiguousarray(seq_lens, dtype=np.int32).reshape(-1)
+    p = L.PackedPlan()
+    L.check(L.lib().bz_packed_plan(C.byref(traits), C.byref(switches) if switches is not None else None, _ptr(sl) if len(sl) else None, len(sl), int(kv_dtype), C.byref(p)))
+    q = p.plan
+    return dict(packed=p.packed, rows=p.rows, n_seq=p.n_seq, max_len=p.max_len, plan=dict(route=q.route, exact=q.exact, attn=q.attn, head=q.head, chunk=q.chunk))
+
+
+def packed_targets_spec(tokens, seq_lens):
+    """bz_packed_targets_spec (host only): the default targets of score_batch for packed `tokens` -> int64 [T]"""
+    tk, sl = np.ascontiguousarray(tokens, dtype=np.int64).reshape(-1), np.ascontiguousarray(seq_lens, dtype=np.int32).reshape(-1)
+    if int(sl.sum()) != len(tk):
+        raise ValueError("packed_targets_spec: %d tokens for lengths summing to %d" % (len(tk), int(sl.sum())))
+    out = np.zeros(len(tk), dtype=np.int64)
+    L.check(L.lib().bz_packed_targets_spec(_ptr(tk), _ptr(sl), len(sl), _ptr(out)))
+    return out
+
+
+def packed_totals_spec(rows, seq_lens):
+    """bz_packed_totals_spec (host only): SCORE_ROW records [T] of a packed batch -> list of (sum_logprob, n_scored) per input, as score_batch adds them"""
+    r, sl = np.ascontiguousarray(rows, dtype=SCORE_ROW), np.ascontiguousarray(seq_lens, dtype=np.int32).reshape(-1)
+    if int(sl.sum()) != len(r):
+        raise ValueError("packed_totals_spec: %d rows for lengths summing to %d" % (len(r), int(sl.sum())))
+    tots = (L.ScoreTotal * len(sl))()
+    L.check(L.lib().bz_packed_totals_spec(_ptr(r), _ptr(sl), len(sl), tots))
+    return [(float(t.sum_logprob), int(t.n_scored)) for t in tots]
+
+
+def attn_packed(dev, qkv, seq_lens, nq, nkv, hd, dt=L.F16, form=None, window=0):
+    """bz_attn_packed (op level): rotated q / k / v rows F32 [T, (nq + 2 nkv) hd] of a packed batch -> its attention output, f32 array [T, nq hd].  K / V are rounded
+    to `dt`; form: L.PF_ATTN_MFMA (default) / _SCALAR / _SCALAR_EXACT."""
+    x = qkv if isinstance(qkv, Tensor) else dev.tensor(np.ascontiguousarray(qkv, dtype=np.float32))
+    sl = np.ascontiguousarray(seq_lens, dtype=np.int32).reshape(-1)
+    T = int(sl.sum()) if len(sl) else 0
+    out = dev.zeros((max(T, 1), nq * hd), L.F32)
+    L.check(L.lib().bz_attn_packed(dev.h, x.h, _ptr(sl) if len(sl) else None, len(sl), int(nq), int(nkv), int(hd), int(dt), int(L.PF_ATTN_MFMA if form is None else form),
+                                   int(window), out.h))
+    return out.to_numpy().reshape(out.shape)
+
+
 def _plan_dict(p):
     return {n: (list(getattr(p, n)) if n in ("qkv", "o", "gateup", "down") else getattr(p, n)) for n, _ in L.LayerPlan._fields_}
 
@@ -1056,14 +1149,20 @@ def cosine_similarity(a, b):
     return float(np.float32(dot / denom)) if denom > 1e-12 else 0.0
 
 
-def rerank(model, cache, query, docs, top_n=None):
+def rerank(model, cache, query, docs, top_n=None, batched=False):
     """/rerank (rerank.rs:206): mean-pooled embeddings of the query and of every document (each from position 0 of `cache`, which is reset between them), cosine
-    similarity, highest first, ties in document order -> list of dict(index, relevance_score), at most top_n"""
+    similarity, highest first, ties in document order -> list of dict(index, relevance_score), at most top_n.  batched: the query and all documents in ONE
+    embed_batch pass (`cache` must hold all their tokens); the default stays the loop of single calls."""
     def emb(tokens):
         cache.reset()
         return model.embed(tokens, cache, 0, pooling="mean")
-    q = emb(query)
-    scored = [dict(index=i, relevance_score=cosine_similarity(q, emb(d))) for i, d in enumerate(docs)]
+    if batched:
+        e = model.embed_batch([query] + list(docs), cache, pooling="mean")
+        q, embs = e[0], e[1:]
+    else:
+        q = emb(query)
+        embs = (emb(d) for d in docs)
+    scored = [dict(index=i, relevance_score=cosine_similarity(q, v)) for i, v in enumerate(embs)]
     scored.sort(key=lambda e: -e["relevance_score"])              # stable
     return scored[:top_n] if top_n is not None else scored
 

@@ -347,8 +347,8 @@ int bz_decode_batch_graph_read_logprobs(bz_batch_graph* g, int64_t step, bz_logp
  *   own test vectors come out identical either way).  normalize: on the pooled vector (each row for NONE) norm = sqrt(sum (double)v_j^2), v_j = (float)((double)v_j
  *   / norm) when norm > 1e-12, else unchanged (pooling.rs:40-47).
  * BZ_E_INVALID naming the figure, before anything is enqueued: a target >= vocab or < -1, top_n outside 0..20, an unknown pooling, an `out` that is too small, and
- * whatever the forward call of the same name refuses (cache / architecture mismatch, positions).  Not built: packed multi-sequence (varlen) prompt batches, scoring
- * or embedding inside the request engine, a bidirectional (non-causal) mask for encoder-style embedding models. */
+ * whatever the forward call of the same name refuses (cache / architecture mismatch, positions).  Many short inputs in one pass: the packed batches below.  Not built:
+ * scoring or embedding inside the request engine, a bidirectional (non-causal) mask for encoder-style embedding models. */
 typedef struct { int32_t top_n; /* 0..20 */ int32_t reserved[7]; } bz_score_config;
 typedef struct { int64_t target; float logit, logprob, lse; int32_t rank, n_top;
                  uint32_t top_ids[BZ_TOP_LOGPROBS_MAX]; float top_logprobs[BZ_TOP_LOGPROBS_MAX]; } bz_score_row;
@@ -365,6 +365,28 @@ int bz_embed_kv(bz_model* m, const bz_tensor* tokens, int S, bz_kv* kv, int posi
 int bz_embed_paged(bz_model* m, const bz_tensor* tokens, int S, bz_paged_kv* kv, const bz_tensor* slot_mapping, const bz_tensor* block_table, int n_table,
                    int seq_len_k, int start_pos, const bz_embed_config* cfg, bz_tensor* out);
 int bz_embed_ssm(bz_model* m, const bz_tensor* tokens, int S, bz_ssm_state* state, const bz_embed_config* cfg, bz_tensor* out);
+/* Packed prompt batches: n_seq inputs in ONE prompt pass (the per-text loops of server/embeddings.rs:180 and server/rerank.rs:144; the continuations of a
+ * loglikelihood request).  tokens I64 [T] holds the inputs end to end, seq_lens (host) their lengths, T = sum(seq_lens).  Packed row i is stored at row i of
+ * `scratch`, a contiguous cache that can hold T rows (it grows up to its max_len; its content afterwards is unspecified and it is left reset), and rotated by its
+ * position inside its own input; the attention keeps a query to its own input's keys (DESIGN.md section 4 "Packed prompt batches").  Where bz_packed_plan answers
+ * packed = 0 (GQA groups other than 1 / 2 / 4 / 8, head_dim the MFMA kernel does not take on a 16-bit model whose longest input does not fit the scalar kernel,
+ * DeepSeek-V2, models whose plan is STEPS, T below the row floor) the single-input call runs once per input inside the library -- reset, then what bz_embed_kv /
+ * bz_score_kv run -- into the same layout: the single calls' bits.  Mamba2 models are refused (loop the _ssm calls).
+ * bz_embed_batch: out F32 [n_seq, hidden], input i's pooled vector at row i -- bit for bit bz_pool_spec of the input's rows; NONE: all T rows, [T, hidden];
+ *   normalize per pooled vector (per row for NONE).
+ * bz_score_batch: rows_out [T]; targets host [T], NULL = the next token inside the row's input and -1 (not scored) on each input's last row; totals (nullable)
+ *   [n_seq], per input, added on the host in row order.
+ * BZ_E_INVALID naming the figure, before anything is enqueued: n_seq <= 0, a length <= 0, T over the scratch cache's capacity, T >= 2^31, an input longer than
+ * max_seq_len, and what the single calls refuse.  New symbols only: BZ_ABI_VERSION is unchanged. */
+int bz_embed_batch(bz_model* m, const bz_tensor* tokens /*I64 [T], packed*/, const int32_t* seq_lens /*host [n_seq]*/, int n_seq, bz_kv* scratch,
+                   const bz_embed_config* cfg, bz_tensor* out /*F32 [n_seq, hidden]; NONE: [T, hidden]*/);
+int bz_score_batch(bz_model* m, const bz_tensor* tokens, const int32_t* seq_lens, int n_seq, bz_kv* scratch, const int64_t* targets /*host [T], nullable*/,
+                   const bz_score_config* cfg, bz_score_row* rows_out /*host [T]*/, bz_score_total* totals /*host [n_seq], nullable*/);
+/* op level, as bz_pool_rows is: rotated q / k / v rows F32 [T, (nq + 2 nkv) hd] of a packed batch -> its attention output F32 [T, nq hd].  K / V are staged,
+ * rounded to `dt` (BZ_F16 / BZ_BF16 / BZ_F32), into a cache of the call's own; the rows go through the kernels in the model's chunks of 2048.
+ * form = BZ_PF_ATTN_MFMA | BZ_PF_ATTN_SCALAR | BZ_PF_ATTN_SCALAR_EXACT (below); window >= 0 (0: none).  n_seq = 1 runs the plain prompt launch of a single call
+ * (no segment mask): the yardstick the packed forms are measured against.  Waits for the stream. */
+int bz_attn_packed(bz_device* dev, const bz_tensor* qkv, const int32_t* seq_lens, int n_seq, int nq, int nkv, int hd, int dt, int form, int window, bz_tensor* out);
 /* op level, as bz_spec_accept is: the records of logits F32 [R,V] rows (any R) against targets I64 [R] on the device; rows_out on the host (waits for the stream) */
 int bz_score_rows(bz_device* dev, const bz_tensor* logits, int64_t R, int64_t V, const bz_tensor* targets, const bz_score_config* cfg, bz_score_row* rows_out);
 /* op level: hidden F32 [S,H] rows -> out F32 [H] ([S,H] for NONE); waits for the stream (the column sums are the call's own) */
@@ -860,6 +882,16 @@ enum { BZ_HEAD_STEP = 0, BZ_HEAD_GEMM = 1, BZ_HEAD_GEMV_ROWS = 2, BZ_HEAD_SPEC =
 typedef struct bz_prompt_plan_t { int route, exact, attn, head, chunk; } bz_prompt_plan_t;
 int bz_model_prompt_traits(const bz_model* m, bz_prompt_traits_t* out);
 int bz_prompt_plan(const bz_prompt_traits_t* t, const bz_prompt_switches_t* sw, int kind, int rows, int total_len, int kv_dtype, bz_prompt_plan_t* out);
+/* HOST ONLY: what a packed prompt batch of these lengths does.  packed = 1 exactly when bz_prompt_plan(BZ_PLAN_PROMPT, rows = T, total_len = max_len) answers
+ * BZ_ROUTE_ROWS -- a query reads at most its own input, so the longest input is the context (and what bounds the scalar attention's LDS); `plan` is that plan.
+ * packed = 0: the single-input path once per input; `plan` is then the plan of the longest input alone.  BZ_E_INVALID naming the figure for n_seq <= 0, a
+ * length <= 0 and T >= 2^31. */
+typedef struct bz_packed_plan_t { int packed, rows, n_seq, max_len; bz_prompt_plan_t plan; } bz_packed_plan_t;
+int bz_packed_plan(const bz_prompt_traits_t* t, const bz_prompt_switches_t* sw, const int32_t* seq_lens, int n_seq, int kv_dtype, bz_packed_plan_t* out);
+/* HOST ONLY: the two definitions bz_score_batch applies on the host, public for the reason bz_score_row_spec is.  targets: row r reads the next token of its own
+ * input, an input's last row -1.  totals: per input, the sum of the logprobs and their count in row order over the scored rows whose logprob is finite. */
+int bz_packed_targets_spec(const int64_t* tokens /*[T]*/, const int32_t* seq_lens, int n_seq, int64_t* targets_out /*[T]*/);
+int bz_packed_totals_spec(const bz_score_row* rows /*[T]*/, const int32_t* seq_lens, int n_seq, bz_score_total* totals_out /*[n_seq]*/);
 /* Which kernels a decode step launches (DESIGN.md "Which kernels a decode step launches").  As above: bz_layer_traits_t is what the decision reads of one
  * layer, fixed at bz_model_finalize but for the two LoRA flags, which bz_lora_table_create sets from the table's mask; bz_step_switches_t the twelve environment
  * switches, read once per process; bz_layer_plan: HOST ONLY, needs no device -- the decision itself, a pure function of (traits, switches, kv_dtype).  The model

@@ -10,6 +10,7 @@
 //          [--lora <PEFT dir | adapter_model.safetensors>]... [--lora-targets q,v,...]
 //   bz-run <model> --prompt 1,2,3 --score [--top-logprobs K]
 //   bz-run <model> --prompt 1,2,3 --embed mean|cls|last|none [--normalize]
+//   bz-run <model> --prompts-file FILE --score [--top-logprobs K]  |  --embed mean|cls|last|none [--normalize]
 //   bz-run <model> --requests FILE --rows N [--pool-blocks B] [--prefill-chunk C] [--depth D] [--prefix-cache] [sampling options, --eos]
 // --requests: continuous batching (BatchEngine::run, engine/batch_engine.rs:91-169; RequestScheduler::submit, engine/request_scheduler.rs:105-205) over N rows.  The file
 // has one request per line, `max_tokens;comma-separated prompt ids`; all are submitted, the engine is stepped until idle, and one line of ids per request is
@@ -27,6 +28,8 @@
 // position from the second on -- `position token logprob rank`, then with --top-logprobs K the K likeliest ids as id:logprob -- then `total <sum> tokens <n> perplexity <p>`.
 // --embed: the prompt's contextual embedding (bz_embed_kv / bz_embed_ssm; /v1/embeddings: engine/executor_embed.rs:33-55, server/pooling.rs:4-47), pooled as named
 // and L2-normalised with --normalize: the vector on one line, comma separated (`none`: one line per position).
+// --prompts-file FILE (one comma-separated id list per line) with --score or --embed: all the inputs in ONE packed call (bz_score_batch / bz_embed_batch; the
+// per-text loops of server/embeddings.rs:180 and server/rerank.rs:144); per input what the single-prompt form prints, preceded by `# input i`.
 // prints the generated ids, comma separated, on stdout.
 #include <cmath>
 #include <algorithm>
@@ -101,7 +104,7 @@ int main(int argc, char** argv) {
   std::string draft_path; bz_spec_config sc;
   std::string requests_path; int rows = 0, pool_blocks = 0, prefill_chunk = 0, depth = 2; bool prefix_cache = false;
   std::vector<std::string> lora_paths; std::string lora_targets; std::vector<bz_lora*> loras;
-  bool score = false; int top_logprobs = 0; std::string embed; bool normalize = false;
+  bool score = false; int top_logprobs = 0; std::string embed; bool normalize = false; std::string prompts_path;
   int logprobs = -1; std::vector<uint32_t> bias_ids; std::vector<float> bias_vals;   // --requests: every request asks for K alternatives / carries this bias
   memset(&sc, 0, sizeof sc);
   for (int i = 2; i < argc; i++) {
@@ -137,6 +140,7 @@ int main(int argc, char** argv) {
     else if (a == "--top-logprobs") top_logprobs = atoi(next("--top-logprobs"));
     else if (a == "--embed") embed = next("--embed");
     else if (a == "--normalize") normalize = true;
+    else if (a == "--prompts-file") prompts_path = next("--prompts-file");
     else if (a == "--logit-bias") {
       const char* q = next("--logit-bias"); char* end;
       while (*q) {
@@ -256,7 +260,8 @@ int main(int argc, char** argv) {
     bz_device_close(dev);
     return 0;
   }
-  if (prompt.empty()) { fprintf(stderr, "bz-run: --prompt id,id,... is required\n"); return 2; }
+  if (!prompts_path.empty() && !score && embed.empty()) { fprintf(stderr, "bz-run: --prompts-file goes with --score or --embed\n"); return 2; }
+  if (prompt.empty() && prompts_path.empty()) { fprintf(stderr, "bz-run: --prompt id,id,... is required\n"); return 2; }
   if (!draft_path.empty() && !grammar_path.empty()) { fprintf(stderr, "bz-run: --draft and --grammar do not go together\n"); return 2; }
   if (grammar_path.empty() != vocab_path.empty()) { fprintf(stderr, "bz-run: --grammar and --vocab-bytes go together\n"); return 2; }
   bz_grammar* grammar = nullptr;
@@ -292,6 +297,66 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 4; i++) if (embed == kPool[i]) ecfg.pooling = i;
     if (!score && ecfg.pooling < 0) { fprintf(stderr, "bz-run: --embed takes mean, cls, last or none\n"); return 2; }
     if (bz_model_get_config(m, &cfg) != BZ_OK) return fail("config");            // the cache's shape as the library keeps it (MLA: one latent 'head')
+    auto print_score = [&](const bz_score_row* rows, int S, const bz_score_total& tot) {
+      for (int i = 0; i + 1 < S; i++) {
+        printf("%d %lld %.6f %d", i + 1, (long long)rows[i].target, (double)rows[i].logprob, rows[i].rank);
+        for (int j = 0; j < rows[i].n_top; j++) printf(" %u:%.6f", rows[i].top_ids[j], (double)rows[i].top_logprobs[j]);
+        printf("\n");
+      }
+      printf("total %.6f tokens %lld perplexity %.6f\n", tot.sum_logprob, (long long)tot.n_scored, tot.n_scored ? exp(-tot.sum_logprob / (double)tot.n_scored) : 0.0);
+    };
+    auto print_vecs = [&](const float* v, int nvec) {
+      for (int r = 0; r < nvec; r++) {
+        for (int j = 0; j < cfg.hidden; j++) printf(j ? ",%.9g" : "%.9g", (double)v[(size_t)r * cfg.hidden + j]);
+        printf("\n");
+      }
+    };
+    if (!prompts_path.empty()) {      // many inputs, one packed call
+      std::string text;
+      if (!read_file(prompts_path, text)) { fprintf(stderr, "bz-run: cannot read %s\n", prompts_path.c_str()); return 2; }
+      std::vector<int64_t> flat; std::vector<int32_t> lens;
+      {
+        std::string line;
+        size_t at = 0;
+        while (at <= text.size()) {
+          const size_t nl = text.find('\n', at);
+          line = text.substr(at, nl == std::string::npos ? std::string::npos : nl - at);
+          at = nl == std::string::npos ? text.size() + 1 : nl + 1;
+          const char* q = line.c_str(); char* end; int n = 0;
+          while (*q) { const long long id = strtoll(q, &end, 10); if (end == q) break; flat.push_back(id); n++; q = *end == ',' ? end + 1 : end; }
+          if (n) lens.push_back(n);
+        }
+      }
+      if (lens.empty()) { fprintf(stderr, "bz-run: %s holds no input\n", prompts_path.c_str()); return 2; }
+      if (cfg.arch == BZ_ARCH_MAMBA2) { fprintf(stderr, "bz-run: --prompts-file takes models with a KV cache\n"); return 2; }
+      const int T = (int)flat.size(), n_seq = (int)lens.size();
+      const int64_t shp[1] = {T};
+      bz_tensor* tok = nullptr; bz_kv* kv = nullptr;
+      if (bz_tensor_from_host(dev, BZ_I64, shp, 1, flat.data(), &tok) != BZ_OK) return fail("tokens");
+      if (bz_kv_create(dev, cfg.n_layers, 1, cfg.n_kv_heads, T, T > cfg.max_seq_len ? T : cfg.max_seq_len, cfg.head_dim, cfg.act_dtype, &kv) != BZ_OK) return fail("cache");
+      if (score) {
+        std::vector<bz_score_row> rows((size_t)T); std::vector<bz_score_total> tots((size_t)n_seq);
+        bz_score_config scfg;
+        memset(&scfg, 0, sizeof scfg);
+        scfg.top_n = top_logprobs;
+        if (bz_score_batch(m, tok, lens.data(), n_seq, kv, nullptr, &scfg, rows.data(), tots.data()) != BZ_OK) return fail("score");
+        for (int i = 0, o = 0; i < n_seq; o += lens[i], i++) { printf("# input %d\n", i); print_score(rows.data() + o, lens[i], tots[i]); }
+      } else {
+        const bool none = ecfg.pooling == BZ_POOL_NONE;
+        const int64_t oshp[2] = {none ? T : n_seq, cfg.hidden};
+        bz_tensor* out = nullptr;
+        if (bz_tensor_zeros(dev, BZ_F32, oshp, 2, &out) != BZ_OK) return fail("out");
+        if (bz_embed_batch(m, tok, lens.data(), n_seq, kv, &ecfg, out) != BZ_OK) return fail("embed");
+        std::vector<float> v((size_t)oshp[0] * cfg.hidden);
+        if (bz_tensor_to_host(out, v.data(), v.size() * 4) != BZ_OK) return fail("read");
+        for (int i = 0, o = 0; i < n_seq; o += lens[i], i++) { printf("# input %d\n", i); print_vecs(v.data() + (size_t)(none ? o : i) * cfg.hidden, none ? lens[i] : 1); }
+        bz_tensor_free(out);
+      }
+      bz_tensor_free(tok); bz_kv_free(kv); bz_model_free(m);
+      for (bz_lora* a : loras) bz_lora_free(a);
+      bz_device_close(dev);
+      return 0;
+    }
     const int S = (int)prompt.size();
     const int64_t shp[1] = {S};
     bz_tensor* tok = nullptr;
@@ -309,12 +374,7 @@ int main(int argc, char** argv) {
       scfg.top_n = top_logprobs;
       if ((is_ssm ? bz_score_ssm(m, tok, S, ssm, targets.data(), &scfg, rows.data(), &tot) : bz_score_kv(m, tok, S, kv, 0, targets.data(), &scfg, rows.data(), &tot)) != BZ_OK)
         return fail("score");
-      for (int i = 0; i + 1 < S; i++) {
-        printf("%d %lld %.6f %d", i + 1, (long long)rows[i].target, (double)rows[i].logprob, rows[i].rank);
-        for (int j = 0; j < rows[i].n_top; j++) printf(" %u:%.6f", rows[i].top_ids[j], (double)rows[i].top_logprobs[j]);
-        printf("\n");
-      }
-      printf("total %.6f tokens %lld perplexity %.6f\n", tot.sum_logprob, (long long)tot.n_scored, tot.n_scored ? exp(-tot.sum_logprob / (double)tot.n_scored) : 0.0);
+      print_score(rows.data(), S, tot);
     } else {
       const int nvec = ecfg.pooling == BZ_POOL_NONE ? S : 1;
       const int64_t oshp[2] = {nvec, cfg.hidden};
@@ -323,10 +383,7 @@ int main(int argc, char** argv) {
       if ((is_ssm ? bz_embed_ssm(m, tok, S, ssm, &ecfg, out) : bz_embed_kv(m, tok, S, kv, 0, &ecfg, out)) != BZ_OK) return fail("embed");
       std::vector<float> v((size_t)nvec * cfg.hidden);
       if (bz_tensor_to_host(out, v.data(), v.size() * 4) != BZ_OK) return fail("read");
-      for (int r = 0; r < nvec; r++) {
-        for (int j = 0; j < cfg.hidden; j++) printf(j ? ",%.9g" : "%.9g", (double)v[(size_t)r * cfg.hidden + j]);
-        printf("\n");
-      }
+      print_vecs(v.data(), nvec);
       bz_tensor_free(out);
     }
     bz_tensor_free(tok);
