@@ -255,8 +255,8 @@ class LayerPlan(C.Structure):
                 ("mla_exact", C.c_int), ("moe_route_fused", C.c_int), ("moe_rows2", C.c_int)]
 
 
-(LIN_NONE, LIN_Q4G, LIN_ROWS, LIN_Q4K, LIN_Q6K, LIN_Q80, LIN_Q5K, LIN_Q40, LIN_Q41, LIN_Q50, LIN_Q51, LIN_F8) = range(12)
-(GEMV_NONE, GEMV_F8, GEMV_Q4G_SLIM, GEMV_Q4G, GEMV_ROWS2, GEMV_ROWS, GEMV_GQ_SLIM, GEMV_GQ, GEMV_UNSUPPORTED) = range(9)
+(LIN_NONE, LIN_Q4G, LIN_ROWS, LIN_Q4K, LIN_Q6K, LIN_Q80, LIN_Q5K, LIN_Q40, LIN_Q41, LIN_Q50, LIN_Q51, LIN_F8, LIN_MX4) = range(13)
+(GEMV_NONE, GEMV_F8, GEMV_Q4G_SLIM, GEMV_Q4G, GEMV_ROWS2, GEMV_ROWS, GEMV_GQ_SLIM, GEMV_GQ, GEMV_UNSUPPORTED, GEMV_MX4) = range(10)
 ATTN_PLAIN, ATTN_FUSED_Q4G, ATTN_FUSED_DENSE, ATTN_FUSED_Q4K, ATTN_SPLIT, ATTN_SPLIT_FUSED = range(6)
 ATTN_K_DECODE, ATTN_K_ATTN2, ATTN_K_ATTN2F, ATTN_K_UNSUPPORTED = range(4)
 MLP_SPLIT, MLP_Q4G, MLP_DENSE, MLP_GQ = range(4)
@@ -295,6 +295,7 @@ SYMBOLS = {
     "bz_model_add_gptq": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64, P, P, P, P, P, C.c_int]),
     "bz_model_add_gguf": (C.c_int, [P, C.c_char_p, C.c_int, C.c_int64, C.c_int64, P]),
     "bz_model_add_fp8": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64, P, P, C.c_int64, P]),
+    "bz_model_add_mxfp4": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64, P, P, P]),
     "bz_model_finalize": (C.c_int, [P]),
     "bz_model_get_config": (C.c_int, [P, C.POINTER(ModelConfig)]),
     "bz_model_weight_bytes": (C.c_int, [P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

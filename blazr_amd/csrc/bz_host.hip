@@ -238,7 +238,7 @@ extern "C" int bz_tensor_to_host_pipelined(const bz_tensor* t, uint64_t ev, void
 // model
 // ---------------------------------------------------------------------------------------------------------
 struct RawTensor {
-  int kind = 0;  // 0 dense, 1 awq, 2 gptq, 3 gguf, 4 fp8 (d0 = e4m3 bytes [N][K], d1 = f32 scales [N])
+  int kind = 0;  // 0 dense, 1 awq, 2 gptq, 3 gguf, 4 fp8 (d0 = e4m3 bytes [N][K], d1 = f32 scales [N]), 5 mxfp4 (d0 = e2m1 codes [N][K/2], d1 = e8m0 codes [N][K/32])
   int dtype = BZ_F32;
   std::vector<int64_t> shape;
   int64_t N = 0, K = 0; int gs = 0; int ggml_type = 0;
@@ -564,6 +564,29 @@ extern "C" int bz_model_add_fp8(bz_model* m, const char* name, int64_t N, int64_
   BZ_API_END
 }
 
+// MXFP4 weights: E2M1 codes two per byte (low nibble first) with one E8M0 scale code per block of 32 along K: W[n][k] = 2^(scale[n][k / 32] - 127) e2m1(q[n][k]).
+// Scale codes that a kernel could not carry exactly are refused here: 255 is NaN, 253 and 254 put 6 . 2^(c - 127) beyond f32.
+extern "C" int bz_model_add_mxfp4(bz_model* m, const char* name, int64_t N, int64_t K, const uint8_t* weight, const uint8_t* scale, const float* bias) {
+  BZ_API_BEGIN
+  BZ_TRY(check_add(m, name));
+  if (!weight || !scale) BZ_FAIL(BZ_E_INVALID, "add_mxfp4 '%s': null data", name);
+  if (N <= 0 || K <= 0 || N % 64 || K % 64) BZ_FAIL(BZ_E_UNSUPPORTED, "add_mxfp4 '%s': N=%lld and K=%lld must be positive multiples of 64", name, (long long)N, (long long)K);
+  if ((uint64_t)N * (uint64_t)K >= (1ull << 32)) BZ_FAIL(BZ_E_UNSUPPORTED, "add_mxfp4 '%s': 2^32 weights or more", name);
+  const size_t nw = (size_t)N * (size_t)(K / 2), ns = (size_t)N * (size_t)(K / 32);
+  for (size_t i = 0; i < ns; i++) {
+    if (scale[i] == 255u) BZ_FAIL(BZ_E_INVALID, "add_mxfp4 '%s': scale[%zu] = 255 is the E8M0 NaN code", name, i);
+    if (scale[i] > 252u) BZ_FAIL(BZ_E_UNSUPPORTED, "add_mxfp4 '%s': scale[%zu] = %u: 6 . 2^(code - 127) is not a finite f32 (codes 0 .. 252 are built)", name, i, (unsigned)scale[i]);
+  }
+  if (bias) for (int64_t i = 0; i < N; i++) if (!std::isfinite(bias[i])) BZ_FAIL(BZ_E_INVALID, "add_mxfp4 '%s': bias[%lld] is not finite", name, (long long)i);
+  RawTensor r; r.kind = 5; r.N = N; r.K = K; r.shape = {N, K}; r.bytes = nw + ns;
+  BZ_TRY(upload(m->dev, &r.d0, weight, nw));
+  BZ_TRY(upload(m->dev, &r.d1, scale, ns));
+  if (bias) { void* b; BZ_TRY(upload(m->dev, &b, bias, (size_t)N * 4)); r.d_bias = (float*)b; }
+  m->raw[name] = r;
+  return BZ_OK;
+  BZ_API_END
+}
+
 // --- finalize helpers ---------------------------------------------------------------------------------------
 static int choose_gw(int N, int K, int target) {
   const int G = K / 128, nst = (N + 255) / 256;
@@ -705,6 +728,31 @@ static int build_f8(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L
   return BZ_OK;
 }
 
+// MXFP4 tensors concatenated along N and repacked into the kernels' tiles (four rows x 512 k with their scale bytes, bz_mxfp4.hip); N % 64 == 0 per part, so
+// no tile straddles two parts and a part's tiles are a contiguous range; biases as build_f8 keeps them
+static int build_mx4(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L) {
+  const int K = (int)rs[0]->K;
+  int N = 0;
+  bool any_bias = false;
+  for (auto* r : rs) { N += (int)r->N; any_bias |= r->d_bias != nullptr; if (r->K != K) BZ_FAIL(BZ_E_UNSUPPORTED, "fused mxfp4 parts differ in K"); }
+  if ((uint64_t)N * (uint64_t)K >= (1ull << 32)) BZ_FAIL(BZ_E_UNSUPPORTED, "fused mxfp4 linear of 2^32 weights or more");
+  void *w, *b = nullptr;
+  hipStream_t st = m->dev->stream;
+  BZ_TRY(dev_alloc(m, &w, bzk_mx4_bytes(N, K)));
+  size_t o = 0;
+  for (auto* r : rs) { BZ_TRY(bzk_repack_mx4(st, r->d0, r->d1, (int)r->N, K, (char*)w + bzk_mx4_bytes((int)o, K))); o += (size_t)r->N; }
+  if (any_bias) {
+    BZ_TRY(dev_alloc(m, &b, (size_t)N * 4));
+    BZ_HIP(hipMemsetAsync(b, 0, (size_t)N * 4, st));
+    o = 0;
+    for (auto* r : rs) { if (r->d_bias) BZ_HIP(hipMemcpyAsync((float*)b + o, r->d_bias, (size_t)r->N * 4, hipMemcpyDeviceToDevice, st)); o += (size_t)r->N; }
+  }
+  BZ_HIP(hipStreamSynchronize(st));
+  L->kind = LK_MX4; L->N = N; L->K = K; L->gs = 32; L->wdt = BZ_U8; L->w = w; L->bias = (float*)b; L->sk = 1;
+  L->bytes = bzk_mx4_bytes(N, K); L->algo_bytes = (size_t)N * (size_t)(K / 2 + K / 32);      // 4.25 bits per weight on disk; the tiles pad K to 512
+  return BZ_OK;
+}
+
 // dense linear whose consumer reads plain f32 (lm_head logits, Mamba2 in_proj): no split-K
 static void force_direct(FusedLinear* F) {
   bool rows = true;
@@ -800,6 +848,7 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
     else if (g[0]->kind == 0) { if (g[0]->shape.size() != 2) BZ_FAIL(BZ_E_INVALID, "finalize: linear weight must be 2-D"); BZ_TRY(build_rows(m, g, &L)); }
     else if (g[0]->kind == 3) BZ_TRY(build_gq(m, g, &L));
     else if (g[0]->kind == 4) BZ_TRY(build_f8(m, g, &L));
+    else if (g[0]->kind == 5) BZ_TRY(build_mx4(m, g, &L));
     else BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: tensor kind %d", g[0]->kind);
     F->parts.push_back(L); F->n_off.push_back(noff);
     // per-name views for the op-level API
@@ -818,6 +867,10 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
         V.w = (char*)L.w + (size_t)sub * L.K; V.scales = (float*)L.scales + sub; V.zeros = (unsigned*)L.zeros + sub / 16;
         V.bias = L.bias ? L.bias + sub : nullptr;
         V.sk = f8_choose_sk(V.N, V.K);
+      } else if (L.kind == LK_MX4) {
+        V.w = (char*)L.w + bzk_mx4_bytes(sub, L.K);
+        V.bias = L.bias ? L.bias + sub : nullptr;
+        V.bytes = bzk_mx4_bytes(V.N, V.K); V.algo_bytes = (size_t)V.N * (size_t)(V.K / 2 + V.K / 32);
       } else {
         const size_t t0 = (size_t)sub / 64, K = (size_t)L.K;
         if (L.kind == LK_Q80) { V.w = (char*)L.w + t0 * 64 * K; V.scales = (char*)L.scales + t0 * (K / 32) * 64 * 2; }
@@ -840,7 +893,7 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
   static const bool no_sk = getenv("BZ_NO_ROWS_SPLITK") != nullptr;
   for (auto& p : F->parts) if (p.kind == LK_ROWS && !no_sk) p.sk = bzk_rows_choose_sk(p.N, p.K);
   for (auto& p : F->parts) if (p.kind == LK_F8) p.sk = f8_choose_sk(p.N, p.K);
-  auto is_fix = [](const LinearDev& p) { return (p.kind != LK_ROWS && p.kind != LK_F8) || p.sk > 1; };
+  auto is_fix = [](const LinearDev& p) { return (p.kind != LK_ROWS && p.kind != LK_F8 && p.kind != LK_MX4) || p.sk > 1; };   // (an mxfp4 linear never splits K)
   F->fix_out = is_fix(F->parts[0]);
   for (auto& p : F->parts) if (is_fix(p) != F->fix_out) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: mixed fixed-point/direct parts in one fused linear");
   for (auto* r : rs) { raw_free(*r); r->consumed = true; }
@@ -946,7 +999,7 @@ static void fill_prompt_traits(bz_model* m) {
         // 16-bit activations: dense in the activation dtype or fp8 (fp8 weights expand to it exactly: the MFMA GEMM), or int4 without act-order (the
         // multi-row dot4 GEMM; exact_cap: what the exact rows can use of it)
         const bool one = F->parts.size() == 1;
-        const bool dense_ok = one && ((F->parts[0].kind == LK_ROWS && F->parts[0].wdt == act) || bzk_gemm_f8w_ok(F->parts[0], act));
+        const bool dense_ok = one && ((F->parts[0].kind == LK_ROWS && F->parts[0].wdt == act) || bzk_gemm_f8w_ok(F->parts[0], act) || bzk_gemm_mx4w_ok(F->parts[0], act));
         const bool q4_ok = one && bzk_gemm_q4g_rows_ok(F->parts[0]);
         if (!dense_ok && !q4_ok) t.proj_16 = 0;
         if (dense_ok) t.any_dense = 1;
@@ -1061,6 +1114,10 @@ extern "C" int bz_model_finalize(bz_model* m) {
     for (auto& kv : m->raw) if (kv.second.kind == 4) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: fp8 tensor '%s': fp8 weights need f16 or bf16 activations", kv.first.c_str());
   if (m->cfg.arch != BZ_ARCH_LLAMA)
     for (auto& kv : m->raw) if (kv.second.kind == 4) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: fp8 tensor '%s': fp8 weights are built for the Llama family only", kv.first.c_str());
+  if (m->cfg.act_dtype == BZ_F32)   // (likewise x e2m1(q))
+    for (auto& kv : m->raw) if (kv.second.kind == 5) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: mxfp4 tensor '%s': mxfp4 weights need f16 or bf16 activations", kv.first.c_str());
+  if (m->cfg.arch != BZ_ARCH_LLAMA)
+    for (auto& kv : m->raw) if (kv.second.kind == 5) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: mxfp4 tensor '%s': mxfp4 weights are built for the Llama family only", kv.first.c_str());
   if (m->cfg.arch == BZ_ARCH_MAMBA2) return finalize_mamba2(m);
   if (m->cfg.arch == BZ_ARCH_DEEPSEEK2) return finalize_dsv2(m);
   const bz_model_config& c = m->cfg;
@@ -1127,6 +1184,8 @@ extern "C" int bz_model_finalize(bz_model* m) {
       m->lm_head.parts.push_back(L); m->lm_head.n_off.push_back(0); m->lm_head.N = V; m->lm_head.K = H; m->lm_head.fix_out = false;
       m->named["lm_head.weight"] = L;
     } else if (!tied) {
+      // (the head reads argmax partials or the ring's fixed point; k_gemv_mx4 gives neither)
+      { auto it = m->raw.find("lm_head.weight"); if (it != m->raw.end() && it->second.kind == 5) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: mxfp4 tensor 'lm_head.weight': an mxfp4 lm_head is not built (keep it 16-bit)"); }
       BZ_TRY(build_fused(m, {"lm_head"}, &m->lm_head));
       force_direct(&m->lm_head);
       // an fp8 lm_head takes the path of an int4 one: fixed-point output, converted after the launch (the split form, at least two slices)
@@ -2162,6 +2221,7 @@ static int pf_gemm(bz_model* m, const LinearDev& P, const void* x16, int n, floa
   const int act = m->cfg.act_dtype;
   if (P.kind == LK_ROWS) return bzk_gemm_nt(st, act, x16, P.w, P.bias, n, P.N, P.K, act, y, m->pf_ws, m->pf_ws_bytes);
   if (P.kind == LK_F8) return bzk_gemm_f8w(st, P, act, x16, n, act, y, m->pf_ws, m->pf_ws_bytes);
+  if (P.kind == LK_MX4) return bzk_gemm_mx4w(st, P, act, x16, n, act, y, m->pf_ws, m->pf_ws_bytes);
   if (exact == 2 && bzk_gemm_q4g_i8_ok(P, act)) {
     size_t po; const size_t need = bzk_pf_quant_i8_bytes(n, P.K, &po);
     if (m->pf_xq_bytes < need) { BZ_HIP(hipStreamSynchronize(st)); void* p; BZ_TRY(dev_alloc(m, &p, need)); m->pf_xq = p; m->pf_xq_bytes = need; }
@@ -2470,9 +2530,10 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   const bool q4 = L.kind == LK_Q4G;   // int4 group-quantised weights x f16 activations (the AWQ / GPTQ prefill GEMM), S >= 9
   const bool f8 = L.kind == LK_F8;    // fp8 weights x the model's 16-bit activations (the W8A16 GEMM)
+  const bool mx4 = L.kind == LK_MX4;  // mxfp4 weights likewise (the W4A16 GEMM)
   const int f8dt = m->cfg.act_dtype == BZ_F16 ? BZ_F16 : BZ_BF16;
-  if (f8 ? !bzk_gemm_f8w_ok(L, f8dt) : q4 ? !bzk_gemm_q4g_mfma_ok(L, BZ_F16, S) : (L.kind != LK_ROWS || (L.wdt != BZ_F16 && L.wdt != BZ_BF16)))
-    BZ_FAIL(BZ_E_UNSUPPORTED, "prefill_matmul: '%s' is neither a dense f16 / bf16 weight, an fp8 weight nor an int4 weight without act-order (S >= 9)", name);
+  if (mx4 ? !bzk_gemm_mx4w_ok(L, f8dt) : f8 ? !bzk_gemm_f8w_ok(L, f8dt) : q4 ? !bzk_gemm_q4g_mfma_ok(L, BZ_F16, S) : (L.kind != LK_ROWS || (L.wdt != BZ_F16 && L.wdt != BZ_BF16)))
+    BZ_FAIL(BZ_E_UNSUPPORTED, "prefill_matmul: '%s' is neither a dense f16 / bf16 weight, an fp8 or mxfp4 weight nor an int4 weight without act-order (S >= 9)", name);
   if (!x || !y || x->dtype != BZ_F32 || y->dtype != BZ_F32 || S <= 0 || x->nbytes < (size_t)S * L.K * 4 || y->nbytes < (size_t)S * L.N * 4)
     BZ_FAIL(BZ_E_INVALID, "prefill_matmul: x must be F32 [S,%d], y F32 [S,%d]", L.K, L.N);
   BZ_HIP(hipSetDevice(m->dev->id));
@@ -2481,9 +2542,9 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
   const size_t ws_bytes = (size_t)48 << 20;      // split-K partials, as the prefill paths pass them
   BZ_HIP(hipMalloc(&x16, (size_t)S * L.K * 2));
   if (hipMalloc(&ws, ws_bytes) != hipSuccess) { hipFree(x16); BZ_FAIL(BZ_E_OOM, "prefill_matmul: workspace"); }
-  const int xdt = f8 ? f8dt : q4 ? BZ_F16 : L.wdt;
+  const int xdt = (f8 || mx4) ? f8dt : q4 ? BZ_F16 : L.wdt;
   int rc = bzk_pf_cvt16(st, xdt, (const float*)x->ptr, (size_t)S * L.K, x16);
-  if (rc == BZ_OK) rc = f8 ? bzk_gemm_f8w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : q4 ? bzk_gemm_q4g_mfma(st, L, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes)
+  if (rc == BZ_OK) rc = mx4 ? bzk_gemm_mx4w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : f8 ? bzk_gemm_f8w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : q4 ? bzk_gemm_q4g_mfma(st, L, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes)
                            : bzk_gemm_nt(st, L.wdt, x16, L.w, L.bias, S, L.N, L.K, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes);
   hipStreamSynchronize(st);
   hipFree(x16); hipFree(ws);
@@ -4288,7 +4349,7 @@ extern "C" int bz_quant_matmul(bz_model* m, const char* name, const bz_tensor* x
   hipStream_t st = m->dev->stream;
   // op-level results are NOT rounded to the activation dtype: the caller sees the f32 accumulator
   long long* acc = nullptr;
-  const bool direct = L.kind == LK_ROWS || (L.kind == LK_F8 && L.sk <= 1);   // (an fp8 linear's split form goes through the accumulator like the int4 kinds)
+  const bool direct = L.kind == LK_ROWS || L.kind == LK_MX4 || (L.kind == LK_F8 && L.sk <= 1);   // (an fp8 linear's split form goes through the accumulator like the int4 kinds)
   if (!direct) BZ_HIP(hipMalloc(&acc, (size_t)L.N * 8));
   int rc = BZ_OK;
   // int4: the accumulator's unit per row.  The kernels' sums are exact up to one rounding per workgroup to the accumulator's grid; at the f32 grid (2^-32, +-2^31)
@@ -4342,7 +4403,7 @@ extern "C" int bz_dequant(bz_model* m, const char* name, float* host) {
   float* d;
   BZ_HIP(hipMalloc(&d, n * 4));
   int rc = L.kind == LK_Q4G ? bzk_dequant_q4g(m->dev->stream, L, d) : L.kind == LK_ROWS ? bzk_dequant_rows(m->dev->stream, L, d)
-         : L.kind == LK_F8 ? bzk_dequant_f8(m->dev->stream, L, d) : bzk_dequant_gq(m->dev->stream, L, d);
+         : L.kind == LK_F8 ? bzk_dequant_f8(m->dev->stream, L, d) : L.kind == LK_MX4 ? bzk_dequant_mx4(m->dev->stream, L, d) : bzk_dequant_gq(m->dev->stream, L, d);
   std::vector<float> tmp;
   if (rc == BZ_OK) rc = hipStreamSynchronize(m->dev->stream) == hipSuccess ? BZ_OK : BZ_E_HIP;  // the stream is non-blocking
   if (rc == BZ_OK) {

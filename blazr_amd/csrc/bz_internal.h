@@ -55,14 +55,14 @@ struct Pro {
 
 // (the public BZ_LIN_* values: bz_linear_traits_t carries a kind as it is)
 enum { LK_NONE = BZ_LIN_NONE, LK_Q4G = BZ_LIN_Q4G, LK_ROWS = BZ_LIN_ROWS, LK_Q4K = BZ_LIN_Q4K, LK_Q6K = BZ_LIN_Q6K, LK_Q80 = BZ_LIN_Q80, LK_Q5K = BZ_LIN_Q5K, LK_Q40 = BZ_LIN_Q40,
-       LK_Q41 = BZ_LIN_Q41, LK_Q50 = BZ_LIN_Q50, LK_Q51 = BZ_LIN_Q51, LK_F8 = BZ_LIN_F8 };
+       LK_Q41 = BZ_LIN_Q41, LK_Q50 = BZ_LIN_Q50, LK_Q51 = BZ_LIN_Q51, LK_F8 = BZ_LIN_F8, LK_MX4 = BZ_LIN_MX4 };
 
 // Device-resident linear layer in kernel layout.
 struct LinearDev {
   int kind = LK_NONE;
   int N = 0, K = 0, gs = 0;
   int wdt = BZ_F16;         // ROWS: weight dtype
-  void* w = nullptr;        // Q4G: [N/64][K/32][64 lanes][16 B]; ROWS: [N][K]; F8: [N][K] e4m3 bytes; GGUF kinds: see k_gemv_gq (zeros = Q6_K highs, hdr = headers, scales = f16 d)
+  void* w = nullptr;        // Q4G: [N/64][K/32][64 lanes][16 B]; ROWS: [N][K]; F8: [N][K] e4m3 bytes; MX4: [N/4][ceil(K/512)][1088 B] tiles, scales inside (bz_mxfp4.hip); GGUF kinds: see k_gemv_gq (zeros = Q6_K highs, hdr = headers, scales = f16 d)
   void* scales = nullptr;   // Q4G: f16 [N/64][G][64]; F8: f32 [N]
   void* zeros = nullptr;    // Q4G: u8  [N/64][G][64]  (AWQ z, GPTQ z+1); F8: u32 [N/16] row-block arrival counters of the split-K form (zero between launches)
   void* hdr = nullptr;      // K-quants: per-superblock headers
@@ -228,6 +228,14 @@ int bzk_gemv_f8(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut
 bool bzk_gemm_f8w_ok(const LinearDev& L, int xdt);
 int bzk_gemm_f8w(hipStream_t s, const LinearDev& L, int dt, const void* x16, int S, int act, float* y, float* ws = nullptr, size_t ws_bytes = 0);
 int bzk_dequant_f8(hipStream_t s, const LinearDev& L, float* out);
+// MXFP4 weights (E2M1 codes, an E8M0 scale per block of 32), in tiles of four rows x 512 k that carry their scales (bz_mxfp4.hip): load-time repack, decode GEMV
+// (direct output), W4A16 MFMA GEMM, read-back
+size_t bzk_mx4_bytes(int N, int K);
+int bzk_repack_mx4(hipStream_t s, const void* q, const void* sc, int N, int K, void* out);
+int bzk_gemv_mx4(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act);
+bool bzk_gemm_mx4w_ok(const LinearDev& L, int xdt);
+int bzk_gemm_mx4w(hipStream_t s, const LinearDev& L, int dt, const void* x16, int S, int act, float* y, float* ws = nullptr, size_t ws_bytes = 0);
+int bzk_dequant_mx4(hipStream_t s, const LinearDev& L, float* out);
 int bzk_mlp_gq(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, int I, const Pro& pro, long long* acc, long long* zero_buf, int zero_n);
 // dense 16-bit form (k_mlp_dense): down_proj additionally stored slab-major [I / 32][H][32] (bzk_repack_down_slabs at finalize)
 int bzk_repack_down_slabs(hipStream_t s, const void* w, int H, int I, void* out);

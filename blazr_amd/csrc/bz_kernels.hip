@@ -2647,6 +2647,7 @@ static int gemv_gq(hipStream_t s, const LinearDev& L, const Pro& pro, const Gemv
 int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act) {
   switch (bzk_gemv_form(lin_traits(L), gemv_pro(pro), out_kind(out), act, *bzk_step_switches())) {
     case BZ_GEMV_F8: return bzk_gemv_f8(s, L, pro, out, act);   // bz_fp8.hip
+    case BZ_GEMV_MX4: return bzk_gemv_mx4(s, L, pro, out, act);   // bz_mxfp4.hip
     case BZ_GEMV_Q4G_SLIM: return gemv_q4g_slim(s, L, pro, out, act);
     case BZ_GEMV_Q4G: return gemv_q4g(s, L, pro, out, act);
     case BZ_GEMV_ROWS2: return gemv_rows2(s, L, pro, out);

@@ -319,8 +319,25 @@ int hf_config_to_pod(const JVal& j, bz_model_config* c, QuantInfo* q) {
           BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights.strategy '%s' is not implemented (tensor and channel are)", g.first.c_str(), strategy.c_str());
       }
       q->method = 3;
+    } else if (m == "quark") {
+      // Quark MXFP4 exports (the *-MXFP4 releases): E2M1 weights in groups of 32 with an E8M0 scale, one scheme for every linear off the `exclude` list; run
+      // weight-only, so global_quant_config.input_tensors is read past.  ASSUMPTION: these field names could not be checked against a published file;
+      // tests/mxfp4_cases.py writes what this branch reads.
+      const JVal* g = qc->get("global_quant_config");
+      const JVal* w = g && g->t == JVal::OBJ ? g->get("weight") : nullptr;
+      if (!w || w->t != JVal::OBJ) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: quark quantization_config without global_quant_config.weight (one weight scheme for the model is what is read)");
+      const std::string dt = w->str("dtype"), sf = w->str("scale_format");
+      if (dt != "fp4") BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: quark global_quant_config.weight.dtype '%s' is not implemented (fp4 is)", dt.c_str());
+      if (w->i64("group_size", 0) != 32) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: quark global_quant_config.weight.group_size %lld is not implemented (32, the MX block, is)", w->i64("group_size", 0));
+      if (sf != "e8m0") BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: quark global_quant_config.weight.scale_format '%s' is not implemented (e8m0 is)", sf.c_str());
+      for (const char* ov : {"layer_quant_config", "layer_type_quant_config"}) {
+        const JVal* o = qc->get(ov);
+        if (o && ((o->t == JVal::OBJ && !o->o.empty()) || (o->t == JVal::ARR && !o->a.empty())))
+          BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: quark %s (per-layer overrides of the weight scheme) is not implemented", ov);
+      }
+      q->method = 4;
     }
-    q->group_size = (int)qc->i64("group_size", 128);
+    q->group_size = q->method == 4 ? 32 : (int)qc->i64("group_size", 128);
     if ((q->method == 1 || q->method == 2) && qc->i64("bits", 4) != 4) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: %lld-bit %s is not implemented (4-bit only)", qc->i64("bits", 4), m.c_str());
   }
   c->vocab = (int)j.i64("vocab_size", 0);
@@ -588,6 +605,27 @@ int load_safetensors(bz_device* dev, const std::string& path, bz_model** out, bz
       if (N <= 0 || K <= 0 || t.bytes != (size_t)N * (size_t)K) { rc = BZ_E_INVALID; bz_set_error("fp8 layer '%s': weight bytes do not match its shape", base.c_str()); break; }
       rc = bz_model_add_fp8(m, name.c_str(), N, K, t.data, f32a.data(), (int64_t)ns, bi ? f32b.data() : nullptr);
       continue;
+    }
+    // MXFP4 (Quark) linears: <linear>.weight U8 [N, K/2] (two E2M1 codes per byte) + <linear>.weight_scale U8 [N, K/32] (E8M0) + optional <linear>.bias; the
+    // tensors on the config's `exclude` list (lm_head, embeddings, norms) are 16-bit and take the dense path below
+    if (q.method == 4) {
+      auto u8_weight = [&](const std::string& w) { const StTensor* x = st.find(w); return x && x->dtype == "U8"; };
+      if (ends_with(name, ".weight_scale") && u8_weight(name.substr(0, name.size() - 6))) continue;
+      if (ends_with(name, ".bias") && u8_weight(name.substr(0, name.size() - 5) + ".weight")) continue;
+      if (t.dtype == "U8") {
+        if (!ends_with(name, ".weight") || t.shape.size() != 2) { rc = BZ_E_UNSUPPORTED; bz_set_error("tensor '%s': U8 is read for 2-D <linear>.weight tensors (packed E2M1) and their .weight_scale only", name.c_str()); break; }
+        const std::string base = name.substr(0, name.size() - 7);
+        const StTensor* sc = st.find(base + ".weight_scale"); const StTensor* bi = st.find(base + ".bias");
+        const int64_t N = t.shape[0], K = t.shape[1] * 2;
+        if (!sc) { rc = BZ_E_INVALID; bz_set_error("mxfp4 layer '%s': no .weight_scale beside the packed weight", base.c_str()); break; }
+        if (N <= 0 || K <= 0 || K % 32 || t.bytes != (size_t)N * (size_t)(K / 2)) { rc = BZ_E_INVALID; bz_set_error("mxfp4 layer '%s': weight must be U8 [N, K/2] with K a multiple of 32, its bytes matching its shape", base.c_str()); break; }
+        if (sc->dtype != "U8" || sc->shape.size() != 2 || sc->shape[0] != N || sc->shape[1] != K / 32 || sc->bytes != (size_t)N * (size_t)(K / 32))
+          { rc = BZ_E_INVALID; bz_set_error("mxfp4 layer '%s': weight_scale must be U8 [%lld,%lld] (one E8M0 code per block of 32)", base.c_str(), (long long)N, (long long)(K / 32)); break; }
+        if (bi && (bi->shape.size() != 1 || bi->shape[0] != N || !to_f32(bi, (size_t)N, &f32b)))
+          { rc = BZ_E_INVALID; bz_set_error("mxfp4 layer '%s': bias must be F32 / F16 / BF16 [%lld]", base.c_str(), (long long)N); break; }
+        rc = bz_model_add_mxfp4(m, name.c_str(), N, K, t.data, sc->data, bi ? f32b.data() : nullptr);
+        continue;
+      }
     }
     const int dt = st_dtype(t.dtype);
     if (dt != BZ_F32 && dt != BZ_F16 && dt != BZ_BF16) { rc = BZ_E_UNSUPPORTED; bz_set_error("tensor '%s': dtype %s is not supported", name.c_str(), t.dtype.c_str()); break; }

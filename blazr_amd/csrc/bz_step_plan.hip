@@ -54,6 +54,7 @@ bool bzk_moe_rows2_ok(int wdt, int K, const bz_step_switches_t& sw) { return bzk
 // the kernel behind one bzk_gemv launch; the order of the tests is the order the launcher has always had
 int bzk_gemv_form(const bz_linear_traits_t& L, const GemvPro& p, int out, int act, const bz_step_switches_t& sw) {
   if (L.kind == LK_F8) return BZ_GEMV_F8;
+  if (L.kind == LK_MX4) return BZ_GEMV_MX4;
   if (L.kind == LK_Q4G) return act == BZ_F16 && bzk_gemv_slim_ok(L, p, sw) ? BZ_GEMV_Q4G_SLIM : BZ_GEMV_Q4G;
   if (L.kind == LK_ROWS) return bzk_rows2_ok(L, p, out, sw) ? BZ_GEMV_ROWS2 : BZ_GEMV_ROWS;
   if (bzk_gq_slim_ok(L, p, sw)) return BZ_GEMV_GQ_SLIM;

@@ -349,6 +349,11 @@ class LoadedModel:
             sc = np.ascontiguousarray(spec["scale"], dtype=np.float32).reshape(-1)  # one per tensor or one per output row
             bi = None if spec.get("bias") is None else np.ascontiguousarray(spec["bias"], dtype=np.float32)
             L.check(L.lib().bz_model_add_fp8(self.h, name, spec["N"], spec["K"], _ptr(w), _ptr(sc), sc.size, None if bi is None else _ptr(bi)))
+        elif kind == "mxfp4":
+            w = np.ascontiguousarray(spec["weight"], dtype=np.uint8)                # [N, K/2] two E2M1 codes per byte, low nibble first
+            sc = np.ascontiguousarray(spec["scale"], dtype=np.uint8)                # [N, K/32] E8M0 codes
+            bi = None if spec.get("bias") is None else np.ascontiguousarray(spec["bias"], dtype=np.float32)
+            L.check(L.lib().bz_model_add_mxfp4(self.h, name, spec["N"], spec["K"], _ptr(w), _ptr(sc), None if bi is None else _ptr(bi)))
         else:
             raise ValueError(kind)
 
@@ -828,7 +833,7 @@ def config_from_hf_json(text):
     """HF config.json text -> (bz_model_config POD, dict(quant_method, group_size, torch_dtype))"""
     c, q = L.ModelConfig(), L.QuantInfo()
     L.check(L.lib().bz_config_from_hf_json(text.encode(), C.byref(c), C.byref(q)))
-    return c, dict(quant_method={0: None, 1: "awq", 2: "gptq", 3: "fp8"}[q.quant_method], group_size=q.group_size, torch_dtype=q.torch_dtype)
+    return c, dict(quant_method={0: None, 1: "awq", 2: "gptq", 3: "fp8", 4: "mxfp4"}[q.quant_method], group_size=q.group_size, torch_dtype=q.torch_dtype)
 
 
 def config_from_gguf(path):

@@ -57,6 +57,15 @@ PRESETS = {
                      tie_embeddings=True,
                      rope_scaling=dict(type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
                                        original_max_position_embeddings=64)),
+    # MXFP4 weight checkpoints (the *-MXFP4 releases): E2M1 codes in blocks of 32 with an E8M0 scale, 4.25 bits per weight, 16-bit head and embeddings
+    "llama3.1-8b-mxfp4": dict(arch="llama", hidden=4096, n_layers=32, n_heads=32, n_kv_heads=8, head_dim=128, inter=14336,
+                              vocab=128256, rms_eps=1e-5, rope_theta=500000.0, act_dtype="bf16", quant="mxfp4",
+                              max_seq_len=2048, tie_embeddings=False),
+    "tiny-mxfp4": dict(arch="llama", hidden=256, n_layers=2, n_heads=4, n_kv_heads=2, head_dim=64, inter=512, vocab=1024,
+                       rms_eps=1e-5, rope_theta=10000.0, act_dtype="bf16", quant="mxfp4", max_seq_len=256,
+                       tie_embeddings=True,
+                       rope_scaling=dict(type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                                         original_max_position_embeddings=64)),
     "tiny-q8_0": dict(arch="llama", hidden=256, n_layers=2, n_heads=4, n_kv_heads=2, head_dim=64, inter=512, vocab=1024,
                       rms_eps=1e-5, rope_theta=10000.0, act_dtype="f32", quant="q8_0", max_seq_len=256,
                       tie_embeddings=False, rope_interleaved=1),
@@ -200,6 +209,69 @@ def fp8_linear(name, N, K, strategy, bias=False, std=0.02, seed=BASE_SEED):
     return d
 
 
+E2M1_VALUES = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], dtype=np.float32)   # codes 0..7; bit 3 of a code is the sign
+
+
+def e2m1_table():
+    """f32 value of the sixteen E2M1 codes (code 8 reads -0)."""
+    return np.concatenate([E2M1_VALUES, -E2M1_VALUES]).astype(np.float32)
+
+
+def e8m0_table():
+    """float64 value 2^(c - 127) of the E8M0 codes 0..254; code 255 reads NaN."""
+    v = np.ldexp(1.0, np.arange(256) - 127)
+    v[255] = np.nan
+    return v
+
+
+def e2m1_encode(w):
+    """f32 [N, K] (K % 32 == 0) -> (E2M1 codes uint8 [N, K], E8M0 scale codes uint8 [N, K/32]): the OCP MX quantiser.  A block's shared
+    exponent is floor(log2(max|w|)) - 2 (2 = the exponent of E2M1's largest value, 6), clamped to the scale codes this project admits
+    (0..252; an all-zero block takes code 127); w / 2^exponent is rounded to the nearest E2M1 value, ties to the even code, and
+    saturates at +-6."""
+    w = np.asarray(w, dtype=np.float32)
+    N, K = w.shape
+    blocks = w.astype(np.float64).reshape(N, K // 32, 32)
+    amax = np.abs(blocks).max(axis=2)
+    e = np.frexp(amax)[1].astype(np.int64) - 1                   # floor(log2(amax)) for amax > 0
+    code = np.where(amax > 0, np.clip(e - 2 + 127, 0, 252), 127).astype(np.int64)
+    a = np.minimum(np.abs(blocks) * np.ldexp(1.0, 127 - code)[:, :, None], 6.0)
+    pos = E2M1_VALUES.astype(np.float64)
+    hi = np.clip(np.searchsorted(pos, a, side="left"), 1, 7)
+    lo = hi - 1
+    dl, dh = a - pos[lo], pos[hi] - a
+    q = np.where((dl < dh) | ((dl == dh) & (lo % 2 == 0)), lo, hi).astype(np.uint8)
+    q |= np.signbit(blocks).astype(np.uint8) << 3
+    return q.reshape(N, K), code.astype(np.uint8)
+
+
+def mxfp4_pack(codes):
+    """E2M1 codes [N, K] -> bytes [N, K/2]: the LOW nibble of byte j is element 2 j, the high nibble element 2 j + 1."""
+    c = np.ascontiguousarray(codes, dtype=np.uint8)
+    return (c[:, 0::2] | (c[:, 1::2] << 4)).astype(np.uint8)
+
+
+def mxfp4_unpack(packed):
+    p = np.ascontiguousarray(packed, dtype=np.uint8)
+    out = np.empty((p.shape[0], p.shape[1] * 2), dtype=np.uint8)
+    out[:, 0::2] = p & 15
+    out[:, 1::2] = p >> 4
+    return out
+
+
+def mxfp4_linear(name, N, K, bias=False, seed=BASE_SEED):
+    """MXFP4 weight [N, K/2] (two E2M1 codes per byte) with E8M0 scales [N, K/32]: W = 2^(scale - 127) . e2m1(code).  As for the int4
+    and FP8 fixtures the codes are drawn directly (uniform over the sixteen codes; an 8B model in seconds); the scale codes 119..121
+    put the weights' standard deviation near 0.02."""
+    r = _rng(name, seed)
+    packed = r.integers(0, 256, size=(N, K // 2), dtype=np.uint8)
+    scale = r.integers(119, 122, size=(N, K // 32), dtype=np.uint8)
+    d = dict(kind="mxfp4", N=N, K=K, weight=packed, scale=scale, bias=None)
+    if bias:
+        d["bias"] = _repr(r.standard_normal(N, dtype=np.float32) * 0.01, "bf16")
+    return d
+
+
 def gguf_blocks(name, ggml_type, N, K, seed=BASE_SEED):
     """Random but well-conditioned ggml blocks: rows of K weights, N rows -> uint8 [N, row_bytes]."""
     r = _rng(name, seed)
@@ -247,6 +319,8 @@ def _linear(cfg, name, N, K, layer=None, role=None, seed=BASE_SEED):
         return gguf_blocks(name, GGML_Q6_K if six else GGML_Q4_K, N, K, seed)
     if q == "fp8":
         return fp8_linear(name, N, K, cfg.get("fp8_strategy", "channel"), bias=cfg.get("bias", False), seed=seed)
+    if q == "mxfp4":
+        return mxfp4_linear(name, N, K, bias=cfg.get("bias", False), seed=seed)
     return dense_linear(name, N, K, cfg["act_dtype"], seed=seed)
 
 
@@ -327,6 +401,9 @@ def algorithmic_bytes_per_token(cfg):
         head = V * H // 32 * 34
     elif q == "fp8":
         wb = lin + L * ((nq + 2 * nkv) * hd + 2 * H + 2 * I) * 4      # one byte per weight + an f32 scale per output row
+        head = V * H * act_b
+    elif q == "mxfp4":
+        wb = lin // 2 + lin // 32                                     # two codes per byte + a scale byte per block of 32
         head = V * H * act_b
     elif q == "q4_k_m":
         six = sum(q4km_uses_q6k(i, L) for i in range(L))

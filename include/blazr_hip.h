@@ -136,6 +136,15 @@ int bz_model_add_gguf(bz_model* m, const char* name, int ggml_type, int64_t N, i
  * reference.  New symbol only: BZ_ABI_VERSION is unchanged. */
 int bz_model_add_fp8(bz_model* m, const char* name, int64_t N, int64_t K, const uint8_t* weight /*[N][K] e4m3*/, const float* scale, int64_t n_scale /*1 or N*/,
                      const float* bias /*nullable [N]*/);
+/* MXFP4 (OCP microscaling FP4) weights of the *-MXFP4 SafeTensors releases (Quark), run weight-only (W4A16): weight holds E2M1 codes (0..7 = 0, 0.5, 1, 1.5, 2,
+ * 3, 4, 6; bit 3 the sign), two per byte -- the LOW nibble of byte j is element 2 j, the high nibble element 2 j + 1 -- and scale one E8M0 code per block of
+ * 32 along K: W[n][k] = 2^(scale[n][k / 32] - 127) e2m1(weight[n][k]).  y = R(f32(sum_k x[k] W[n][k]) + bias[n]), the sum exact (double over exact products,
+ * rounded to f32 once).  ASSUMPTION: the nibble order could not be checked against a published file; tests/mxfp4_cases.py (the writer) and this call define it,
+ * and mx4_pair_bits in bz_mxfp4.hip is the one place that reads it.  N % 64 or K % 64: BZ_E_UNSUPPORTED; a scale code of 255 (NaN): BZ_E_INVALID; a scale code
+ * of 253 or 254 (6 . 2^(c - 127) is not a finite f32): BZ_E_UNSUPPORTED; each naming the tensor.  Llama family and 16-bit activations only (Mamba2, DeepSeek-V2,
+ * f32 activations, an MXFP4 lm_head: BZ_E_UNSUPPORTED at bz_model_finalize).  Beyond the reference.  New symbol only: BZ_ABI_VERSION is unchanged. */
+int bz_model_add_mxfp4(bz_model* m, const char* name, int64_t N, int64_t K, const uint8_t* weight /*[N][K/2]*/, const uint8_t* scale /*[N][K/32]*/,
+                       const float* bias /*nullable [N]*/);
 /* LoadedModel::load(&config.model, &mut vb) (awq.rs:133-136): validates names/shapes, repacks weights into the
  * kernels' HBM layout, builds RoPE tables and workspaces.  Host copies passed to add_* may be freed afterwards. */
 int bz_model_finalize(bz_model* m);
@@ -154,7 +163,7 @@ enum { BZ_LAYER_TRANSFORMER = 0, BZ_LAYER_MAMBA2 = 1, BZ_LAYER_MAMBA3 = 2, BZ_LA
 typedef struct { int32_t format; /* 0 HuggingFace ("model." prefix), 1 Oxidizr */ int32_t num_layers, tie_word_embeddings; uint8_t layer_types[512]; } bz_detected_arch;
 /* boostr::model::detection::detect_architecture_from_names as the reference's tests pin it (loader/safetensors/detect_arch.rs:200-315) */
 int bz_detect_architecture_from_names(const char* const* names, int n, bz_detected_arch* out);
-typedef struct { int32_t quant_method; /* 0 none, 1 awq, 2 gptq, 3 fp8 */ int32_t group_size; int32_t torch_dtype; /* BZ_* or -1 */ } bz_quant_info;
+typedef struct { int32_t quant_method; /* 0 none, 1 awq, 2 gptq, 3 fp8, 4 mxfp4 (quark) */ int32_t group_size; int32_t torch_dtype; /* BZ_* or -1 */ } bz_quant_info;
 /* HuggingFaceConfig::from_json(..).to_universal() + detect_dtype_from_config (loader/safetensors/config.rs:14-70,83-95): HF config.json text ->
  * config POD; quantization_config (detect_arch.rs:79-90,118-131,146-196) -> quant info.  AWQ / GPTQ force f16 (awq.rs:69-71). */
 int bz_config_from_hf_json(const char* json_text, bz_model_config* cfg, bz_quant_info* quant);
@@ -844,8 +853,8 @@ typedef struct bz_prompt_traits_t {
   int sliding_window, sliding_window_pattern;                         /* with n_layers: whether every layer has the window */
   /* Llama family */
   int shapes_ok;      /* hidden, n_heads head_dim, inter multiples of 64; head_dim % 8 == 0, 256 % (head_dim / 8) == 0; rep 1 / 2 / 4 / 8 */
-  int proj_16;        /* 16-bit activations and every projection one part: dense in the activation dtype, fp8, or int4 without act-order */
-  int any_dense;      /* ... and one of them dense or fp8 */
+  int proj_16;        /* 16-bit activations and every projection one part: dense in the activation dtype, fp8, mxfp4, or int4 without act-order */
+  int any_dense;      /* ... and one of them dense, fp8 or mxfp4 */
   int exact_cap;      /* 0: some projection lacks the multi-row int4 form; 1: all have it; 2: all have the integer-MFMA form too */
   int gq_all;         /* every part of every projection a block format without bias, one K per fused linear */
   int gq_max_k;       /* largest K of a fused linear */
@@ -898,7 +907,7 @@ int bz_packed_totals_spec(const bz_score_row* rows /*[T]*/, const int32_t* seq_l
  * keeps one plan per layer and cache dtype (F32 / F16 / BF16); the step dispatches on it and decides one thing per call: the short or the long attention form,
  * from the context and BZ_SPLIT_MIN.  A fused linear is described by its parts (at most three).  Flags are 0 / 1.  New symbols only: BZ_ABI_VERSION is unchanged. */
 enum { BZ_LIN_NONE = 0, BZ_LIN_Q4G = 1, BZ_LIN_ROWS = 2, BZ_LIN_Q4K = 3, BZ_LIN_Q6K = 4, BZ_LIN_Q80 = 5, BZ_LIN_Q5K = 6, BZ_LIN_Q40 = 7, BZ_LIN_Q41 = 8, BZ_LIN_Q50 = 9,
-       BZ_LIN_Q51 = 10, BZ_LIN_F8 = 11 };
+       BZ_LIN_Q51 = 10, BZ_LIN_F8 = 11, BZ_LIN_MX4 = 12 };
 typedef struct bz_linear_traits_t {
   int kind, N, K;        /* BZ_LIN_* */
   int wdt;               /* ROWS: the weights' dtype */
@@ -924,7 +933,7 @@ typedef struct bz_step_switches_t {
   int no_mlp_fusion, gguf_mlp_fusion, dsv2_f32_sums, no_moe_route_fusion;    /* BZ_NO_MLP_FUSION, BZ_GGUF_MLP_FUSION, BZ_DSV2_F32_SUMS, BZ_NO_MOE_ROUTE_FUSION set */
 } bz_step_switches_t;
 /* the kernel one GEMV launch takes (NONE: no such part) */
-enum { BZ_GEMV_NONE = 0, BZ_GEMV_F8 = 1, BZ_GEMV_Q4G_SLIM = 2, BZ_GEMV_Q4G = 3, BZ_GEMV_ROWS2 = 4, BZ_GEMV_ROWS = 5, BZ_GEMV_GQ_SLIM = 6, BZ_GEMV_GQ = 7, BZ_GEMV_UNSUPPORTED = 8 };
+enum { BZ_GEMV_NONE = 0, BZ_GEMV_F8 = 1, BZ_GEMV_Q4G_SLIM = 2, BZ_GEMV_Q4G = 3, BZ_GEMV_ROWS2 = 4, BZ_GEMV_ROWS = 5, BZ_GEMV_GQ_SLIM = 6, BZ_GEMV_GQ = 7, BZ_GEMV_UNSUPPORTED = 8, BZ_GEMV_MX4 = 9 };
 /* attention and o_proj: PLAIN = attention, then the o_proj GEMV(s); FUSED_*: one launch (int4 / dense 16-bit / Q4_K o_proj over an f32 cache); SPLIT: split-KV
  * partials + merge + o_proj GEMV; SPLIT_FUSED: split-KV partials + merge with the int4 o_proj */
 enum { BZ_ATTN_PLAIN = 0, BZ_ATTN_FUSED_Q4G = 1, BZ_ATTN_FUSED_DENSE = 2, BZ_ATTN_FUSED_Q4K = 3, BZ_ATTN_SPLIT = 4, BZ_ATTN_SPLIT_FUSED = 5 };
