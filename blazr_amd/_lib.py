@@ -296,6 +296,8 @@ SYMBOLS = {
     "bz_model_add_gguf": (C.c_int, [P, C.c_char_p, C.c_int, C.c_int64, C.c_int64, P]),
     "bz_model_add_fp8": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64, P, P, C.c_int64, P]),
     "bz_model_add_mxfp4": (C.c_int, [P, C.c_char_p, C.c_int64, C.c_int64, P, P, P]),
+    "bz_model_set_mxfp4_activations": (C.c_int, [P, C.c_int]),
+    "bz_mxfp4_quant_rows": (C.c_int, [P, P, C.c_int, C.c_int, P, P]),
     "bz_model_finalize": (C.c_int, [P]),
     "bz_model_get_config": (C.c_int, [P, C.POINTER(ModelConfig)]),
     "bz_model_weight_bytes": (C.c_int, [P, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

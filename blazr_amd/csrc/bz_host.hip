@@ -332,6 +332,9 @@ struct bz_model {
   void* pf_x3 = nullptr; float* pf_rscale = nullptr;   // split activation rows [rows][3 xw] f16 + their row scales
   void* pf_xq = nullptr; size_t pf_xq_bytes = 0;       // int8 digit planes + row parameters of the exact integer-MFMA GEMM (bzk_pf_quant_i8)
   float* pf_ws = nullptr; size_t pf_ws_bytes = 0;   // W4A16 MFMA GEMM: split-K partials for short prompts / decode batches
+  // MXFP4 linears: has_mx4 -- the model holds one; mx4_a4 -- bz_model_set_mxfp4_activations (0: 16-bit activations, 1: FP4); the quantised rows of a
+  // prefill GEMM's input (codes [rows][K / 2], scales [rows][bzk_mx4_quant_ld(K)]), sized with the prefill workspace
+  bool has_mx4 = false; int mx4_a4 = 0; void* pf_xc4 = nullptr; void* pf_xs4 = nullptr;
   long long* ring[3] = {nullptr, nullptr, nullptr};
   float* dring[3] = {nullptr, nullptr, nullptr};   // direct-output twins of the ring (ROWS kernels)
   int ring_n = 0;
@@ -748,6 +751,7 @@ static int build_mx4(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* 
     for (auto* r : rs) { if (r->d_bias) BZ_HIP(hipMemcpyAsync((float*)b + o, r->d_bias, (size_t)r->N * 4, hipMemcpyDeviceToDevice, st)); o += (size_t)r->N; }
   }
   BZ_HIP(hipStreamSynchronize(st));
+  m->has_mx4 = true;
   L->kind = LK_MX4; L->N = N; L->K = K; L->gs = 32; L->wdt = BZ_U8; L->w = w; L->bias = (float*)b; L->sk = 1;
   L->bytes = bzk_mx4_bytes(N, K); L->algo_bytes = (size_t)N * (size_t)(K / 2 + K / 32);      // 4.25 bits per weight on disk; the tiles pad K to 512
   return BZ_OK;
@@ -2204,6 +2208,10 @@ static int prefill_ws(bz_model* m, int rows) {
   BZ_TRY(dev_alloc(m, &p, (size_t)rows * qn * 4)); m->pf_qkv = (float*)p;
   BZ_TRY(dev_alloc(m, &p, (size_t)rows * 2 * c.inter * 4)); m->pf_gu = (float*)p;
   BZ_TRY(dev_alloc(m, &p, (size_t)rows * xw * (c.act_dtype == BZ_F32 ? 4 : 2))); m->pf_x16 = p;
+  if (m->has_mx4) {      // whatever the mode is now: a later switch allocates nothing, so none happens inside a capture
+    BZ_TRY(dev_alloc(m, &p, (size_t)rows * xw / 2)); m->pf_xc4 = p;
+    BZ_TRY(dev_alloc(m, &p, (size_t)rows * bzk_mx4_quant_ld((int)xw))); m->pf_xs4 = p;
+  }
   if (c.act_dtype == BZ_F32) {
     BZ_TRY(dev_alloc(m, &p, (size_t)rows * 3 * xw * 2)); m->pf_x3 = p;
     BZ_TRY(dev_alloc(m, &p, (size_t)rows * 4)); m->pf_rscale = (float*)p;
@@ -2221,6 +2229,11 @@ static int pf_gemm(bz_model* m, const LinearDev& P, const void* x16, int n, floa
   const int act = m->cfg.act_dtype;
   if (P.kind == LK_ROWS) return bzk_gemm_nt(st, act, x16, P.w, P.bias, n, P.N, P.K, act, y, m->pf_ws, m->pf_ws_bytes);
   if (P.kind == LK_F8) return bzk_gemm_f8w(st, P, act, x16, n, act, y, m->pf_ws, m->pf_ws_bytes);
+  if (P.kind == LK_MX4 && m->mx4_a4) {   // W4A4: the rows quantised to MXFP4, then both operands on the block-scaled FP4 MFMA
+    const int ld = bzk_mx4_quant_ld(P.K);
+    BZ_TRY(bzk_mx4_quant_rows(st, act, x16, n, P.K, m->pf_xc4, m->pf_xs4, ld));
+    return bzk_gemm_mx4a4(st, P, m->pf_xc4, m->pf_xs4, ld, n, act, y, m->pf_ws, m->pf_ws_bytes);
+  }
   if (P.kind == LK_MX4) return bzk_gemm_mx4w(st, P, act, x16, n, act, y, m->pf_ws, m->pf_ws_bytes);
   if (exact == 2 && bzk_gemm_q4g_i8_ok(P, act)) {
     size_t po; const size_t need = bzk_pf_quant_i8_bytes(n, P.K, &po);
@@ -2544,10 +2557,52 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
   if (hipMalloc(&ws, ws_bytes) != hipSuccess) { hipFree(x16); BZ_FAIL(BZ_E_OOM, "prefill_matmul: workspace"); }
   const int xdt = (f8 || mx4) ? f8dt : q4 ? BZ_F16 : L.wdt;
   int rc = bzk_pf_cvt16(st, xdt, (const float*)x->ptr, (size_t)S * L.K, x16);
+  if (rc == BZ_OK && mx4 && m->mx4_a4) {      // the model's mode: FP4 activations (the codes and scales take the head of the workspace, the partials the rest)
+    const int ld = bzk_mx4_quant_ld(L.K);
+    const size_t cb = ((size_t)S * (L.K / 2) + 255) & ~(size_t)255, sb = ((size_t)S * ld + 255) & ~(size_t)255;
+    if (cb + sb >= ws_bytes) { bz_set_error("prefill_matmul: S=%d rows of FP4 activations do not fit the workspace", S); rc = BZ_E_UNSUPPORTED; }
+    if (rc == BZ_OK) rc = bzk_mx4_quant_rows(st, xdt, x16, S, L.K, ws, (char*)ws + cb, ld);
+    if (rc == BZ_OK) rc = bzk_gemm_mx4a4(st, L, ws, (char*)ws + cb, ld, S, BZ_F32, (float*)y->ptr, (float*)((char*)ws + cb + sb), ws_bytes - cb - sb);
+  } else
   if (rc == BZ_OK) rc = mx4 ? bzk_gemm_mx4w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : f8 ? bzk_gemm_f8w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : q4 ? bzk_gemm_q4g_mfma(st, L, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes)
                            : bzk_gemm_nt(st, L.wdt, x16, L.w, L.bias, S, L.N, L.K, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes);
   hipStreamSynchronize(st);
   hipFree(x16); hipFree(ws);
+  return rc;
+  BZ_API_END
+}
+
+// W4A4 for the MXFP4 linears of `m` (include/blazr_hip.h)
+extern "C" int bz_model_set_mxfp4_activations(bz_model* m, int mode) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized) BZ_FAIL(BZ_E_INVALID, "set_mxfp4_activations: the model is not finalized");
+  if (!m->has_mx4) BZ_FAIL(BZ_E_UNSUPPORTED, "set_mxfp4_activations: the model has no MXFP4 linear");
+  if (mode != 0 && mode != 1) BZ_FAIL(BZ_E_INVALID, "set_mxfp4_activations: mode %d (0: 16-bit activations, 1: FP4)", mode);
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  m->mx4_a4 = mode;
+  return BZ_OK;
+  BZ_API_END
+}
+
+// op-level: the activation quantiser of the W4A4 GEMM on rows rounded to the model's activation dtype, the result in the plain row-major layout
+extern "C" int bz_mxfp4_quant_rows(bz_model* m, const bz_tensor* x, int S, int K, bz_tensor* codes, bz_tensor* scales) {
+  BZ_API_BEGIN
+  if (!m || !m->finalized) BZ_FAIL(BZ_E_INVALID, "mxfp4_quant_rows: the model is not finalized");
+  const int dt = m->cfg.act_dtype;
+  if (dt != BZ_F16 && dt != BZ_BF16) BZ_FAIL(BZ_E_UNSUPPORTED, "mxfp4_quant_rows: f16 or bf16 activations only");
+  if (S <= 0 || K < 64 || K % 64) BZ_FAIL(BZ_E_INVALID, "mxfp4_quant_rows: S=%d, K=%d must be a positive multiple of 64", S, K);
+  if (!x || !codes || !scales || x->dtype != BZ_F32 || codes->dtype != BZ_U8 || scales->dtype != BZ_U8 || x->nbytes < (size_t)S * K * 4 || codes->nbytes < (size_t)S * (K / 2) ||
+      scales->nbytes < (size_t)S * (K / 32))
+    BZ_FAIL(BZ_E_INVALID, "mxfp4_quant_rows: x must be F32 [S,%d], codes U8 [S,%d], scales U8 [S,%d]", K, K / 2, K / 32);
+  std::lock_guard<std::recursive_mutex> lock__(m->mu);
+  BZ_HIP(hipSetDevice(m->dev->id));
+  hipStream_t st = m->dev->stream;
+  void* x16 = nullptr;
+  BZ_HIP(hipMalloc(&x16, (size_t)S * K * 2));
+  int rc = bzk_pf_cvt16(st, dt, (const float*)x->ptr, (size_t)S * K, x16);
+  if (rc == BZ_OK) rc = bzk_mx4_quant_rows(st, dt, x16, S, K, codes->ptr, scales->ptr, K / 32);
+  hipStreamSynchronize(st);
+  hipFree(x16);
   return rc;
   BZ_API_END
 }

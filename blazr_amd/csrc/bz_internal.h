@@ -236,6 +236,12 @@ int bzk_gemv_mx4(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOu
 bool bzk_gemm_mx4w_ok(const LinearDev& L, int xdt);
 int bzk_gemm_mx4w(hipStream_t s, const LinearDev& L, int dt, const void* x16, int S, int act, float* y, float* ws = nullptr, size_t ws_bytes = 0);
 int bzk_dequant_mx4(hipStream_t s, const LinearDev& L, float* out);
+// W4A4 (bz_model_set_mxfp4_activations): 16-bit rows -> E2M1 codes [S][K / 2] and E8M0 scales [S][ldsc] (ldsc = K / 32: plain; bzk_mx4_quant_ld(K): what the
+// GEMM reads), and the GEMM of those rows with an MXFP4 linear on the block-scaled FP4 MFMA
+int bzk_mx4_quant_ld(int K);
+int bzk_mx4_quant_rows(hipStream_t s, int dt, const void* x16, int S, int K, void* codes, void* scales, int ldsc);
+bool bzk_gemm_mx4a4_ok(const LinearDev& L);
+int bzk_gemm_mx4a4(hipStream_t s, const LinearDev& L, const void* codes, const void* scales, int ldsc, int S, int act, float* y, float* ws = nullptr, size_t ws_bytes = 0);
 int bzk_mlp_gq(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, int I, const Pro& pro, long long* acc, long long* zero_buf, int zero_n);
 // dense 16-bit form (k_mlp_dense): down_proj additionally stored slab-major [I / 32][H][32] (bzk_repack_down_slabs at finalize)
 int bzk_repack_down_slabs(hipStream_t s, const void* w, int H, int I, void* out);

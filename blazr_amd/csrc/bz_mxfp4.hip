@@ -17,6 +17,7 @@
 //   k_gemm_mx4w    prompt / decode-batch GEMM on the 16-bit matrix cores: code tiles staged by LDS-DMA, expanded to UNSCALED f16 / bf16 fragments in registers,
 //                  one f32 multiply-add per block applies the scale to the block's 32 x 32 partial tile
 //   k_dequant_mx4  op-level read-back of the device layout
+//   k_mx4_quant_rows, k_gemm_mx4a4   W4A4 (opt-in): activation rows quantised to MXFP4, both operands on the block-scaled FP4 matrix instruction (end of file)
 #include "bz_internal.h"
 #include "bz_dev.h"
 #include <algorithm>
@@ -423,6 +424,251 @@ int bzk_gemm_mx4w(hipStream_t s, const LinearDev& L, int dt, const void* x16, in
   if (dt == BZ_F16) { if (TM == 1) LAUNCH_MX4W(BZ_F16, 1); else LAUNCH_MX4W(BZ_F16, 2); }
   else { if (TM == 1) LAUNCH_MX4W(BZ_BF16, 1); else LAUNCH_MX4W(BZ_BF16, 2); }
 #undef LAUNCH_MX4W
+  BZ_HIP(hipGetLastError());
+  if (KS > 1) {
+    const size_t SN = (size_t)S * N;
+    hipLaunchKernelGGL(k_gemm_mx4w_reduce, dim3((unsigned)std::min<size_t>((SN + 255) / 256, 2048)), dim3(256), 0, s, (const float*)ws, KS, SN, N, L.bias, act, y);
+    BZ_HIP(hipGetLastError());
+  }
+  return BZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// W4A4: FP4 activations on the block-scaled FP4 matrix instruction (opt-in per model, bz_model_set_mxfp4_activations).
+//
+//   xq[s][k] = 2^(a[s][k / 32] - 127) e2m1(c[s][k])        y[s][n] = R_act( f32( sum_k xq[s][k] W[n][k] ) + b[n] )
+//
+// k_mx4_quant_rows: the OCP MX quantiser on rows of 16-bit activations, K % 64 == 0.  Per block of 32 the scale code is clamp(floor(log2(max |x|)) - 2 + 127,
+// 0, 252) (127 for an all-zero block); elements are rounded to the nearest E2M1 value times the scale (a power of two: exact in f32), saturating at 6,
+// ties to the even significand; the sign bit is kept (-0 stays -0).  Finite inputs only.  floor(log2) is read off the f32 exponent field E of max |x|: E >= 1
+// gives E - 127, and an f32 subnormal (E = 0, a bf16 subnormal) lies below 2^-126, where the clamp holds the code at 0 as it does for E <= 2 -- so the code is
+// clamp(E - 2, 0, 252).  One lane owns one block: 64 bytes in, 16 code bytes (low nibble = the even element, the weights' file order) and one scale byte out.
+// `ldsc` is the byte stride of a row of scales: K / 32 for the plain [S][K / 32] result, mx4_quant_ld(K) for the rows k_gemm_mx4a4 reads.
+// ---------------------------------------------------------------------------------------------------------
+template <int DT>
+__global__ __launch_bounds__(256) void k_mx4_quant_rows(const unsigned short* __restrict__ X, int S, int K, unsigned char* __restrict__ codes, unsigned char* __restrict__ scales,
+                                                        int ldsc) {
+  const int KB = K >> 5;
+  const size_t total = (size_t)S * KB;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = idx / (size_t)KB;
+    const int b = (int)(idx % (size_t)KB);
+    const uint4* src = (const uint4*)(X + row * (size_t)K + (size_t)b * 32);
+    unsigned w[16];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { const uint4 v = src[i]; w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w; }
+    auto f32_bits = [](unsigned h16) -> unsigned {
+      if constexpr (DT == BZ_BF16) return h16 << 16;
+      else return __float_as_uint((float)__builtin_bit_cast(_Float16, (unsigned short)h16));
+    };
+    unsigned fb[32], amax = 0u;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+      fb[2 * i] = f32_bits(w[i] & 0xffffu);
+      fb[2 * i + 1] = f32_bits(w[i] >> 16);
+      amax = max(amax, max(fb[2 * i] & 0x7fffffffu, fb[2 * i + 1] & 0x7fffffffu));   // (finite magnitudes order as their bit patterns)
+    }
+    const int sc = amax == 0u ? 127 : min(max((int)(amax >> 23) - 2, 0), 252);
+    // the midpoints of neighbouring E2M1 values times the scale (at most three significant bits: exact down to the f32 subnormals, which every kernel mode hipcc
+    // builds keeps); a tie goes to the neighbour whose code is even (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4; 6 and beyond saturate at
+    // code 7).  Finite magnitudes order as their bit patterns, so an element costs seven integer compares and no floating-point operation.
+    unsigned thr[7];
+    {
+      const float mid[7] = {0.25f, 0.75f, 1.25f, 1.75f, 2.5f, 3.5f, 5.0f};
+#pragma unroll
+      for (int j = 0; j < 7; j++) thr[j] = __float_as_uint(ldexpf(mid[j], sc - 127));
+    }
+    unsigned out[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < 32; i++) {
+      const unsigned a = fb[i] & 0x7fffffffu;
+      const unsigned c = (unsigned)(a > thr[0]) + (unsigned)(a >= thr[1]) + (unsigned)(a > thr[2]) + (unsigned)(a >= thr[3]) + (unsigned)(a > thr[4]) + (unsigned)(a >= thr[5]) +
+                         (unsigned)(a > thr[6]);
+      out[i >> 3] |= (c | ((fb[i] >> 28) & 8u)) << (4 * (i & 7));
+    }
+    *(uint4*)(codes + row * (size_t)(K >> 1) + (size_t)b * 16) = make_uint4(out[0], out[1], out[2], out[3]);
+    scales[row * (size_t)ldsc + b] = (unsigned char)sc;
+  }
+}
+
+// the stride of a row of scale bytes as k_gemm_mx4a4 reads them: eight bytes (four 64-k steps) per load, so a row is padded to a multiple of eight
+int bzk_mx4_quant_ld(int K) { return ((K >> 5) + 7) & ~7; }
+
+int bzk_mx4_quant_rows(hipStream_t s, int dt, const void* x16, int S, int K, void* codes, void* scales, int ldsc) {
+  if ((dt != BZ_F16 && dt != BZ_BF16) || S <= 0 || K < 64 || K % 64 || ldsc < K / 32) BZ_FAIL(BZ_E_INVALID, "mx4_quant_rows: 16-bit rows with K %% 64 == 0 (S=%d K=%d)", S, K);
+  const size_t total = (size_t)S * (K / 32);
+  const dim3 grid((unsigned)std::min<size_t>((total + 255) / 256, 4096));
+  if (dt == BZ_F16) BZ_LAUNCH("mx4_quant_rows", (double)S * K * 2.0, (k_mx4_quant_rows<BZ_F16>), grid, dim3(256), 0, s, (const unsigned short*)x16, S, K, (unsigned char*)codes, (unsigned char*)scales, ldsc);
+  else BZ_LAUNCH("mx4_quant_rows", (double)S * K * 2.0, (k_mx4_quant_rows<BZ_BF16>), grid, dim3(256), 0, s, (const unsigned short*)x16, S, K, (unsigned char*)codes, (unsigned char*)scales, ldsc);
+  BZ_HIP(hipGetLastError());
+  return BZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_gemm_mx4a4: Y[S][N] = R((XQ[S][K] . W[N][K]^T) + b[n]) with BOTH operands FP4 under E8M0 block scales, on v_mfma_scale_f32_32x32x64_f8f6f4.  Nothing is
+// converted and no scale touches the VALU: a lane (r = lane & 31, h = lane / 32) of a 64-k step hands the instruction one MX block of row r -- a 16-byte piece
+// of codes -- and the block's scale byte, once for A (activation row r, block 2 step + h, from the quantiser's row-major rows) and once for B (weight row r,
+// the same block, the piece straight from the device tiles at ((n / 4) KC + k / 512) MX4_TILE + ((n % 4) 16 + (k % 512) / 32) 16, its scale byte at
+// ... + 1024 + (n % 4) 16 + (k % 512) / 32).  The instruction multiplies element i of the A piece with element i of the B piece, whichever order it numbers a
+// piece's nibbles in: a block's dot product does not depend on the order of its 32 elements as long as both operands use the same one, and the quantiser packs
+// a block exactly as the weights' file order packs one.  What the hardware calls element 0 therefore cancels out (the identity test proves it).
+//
+// Work split: 256 threads, 2 x 2 waves, a (64 TM) x 128 tile, a wave's share 32 TM x 64: TM x 2 accumulators of 16 doubles (see "Accumulation" in the kernel),
+// TM + 2 pieces per lane and step.  The
+// grid swizzle (xcd / mtile / ntile / split-K) is k_gemm_mx4w's.  Data movement: plain 16-byte register loads, no LDS and no barrier -- a step is a quarter of
+// the W4A16 kernel's activation bytes, and the waves of a workgroup share their pieces through the vector cache.  Loads go in GROUPS of four steps (256 k), two
+// groups in flight: while one group's 4 (TM + 2) pieces feed 16 TM MFMAs the next group's are on their way.  A group's four scale bytes per operand row are
+// eight consecutive bytes (blocks 8 g .. 8 g + 7); one v_perm per row and group keeps this half's four (h, 2 + h, 4 + h, 6 + h) in one VGPR and op_sel picks
+// step u's byte, so no scale byte is extracted or shuffled per MFMA.  Split-K cuts between groups.  Steps past K in the last group are loaded from the last
+// valid step (never a branch around a load) and their MFMAs skipped.
+// ---------------------------------------------------------------------------------------------------------
+typedef int mx4_i32x8 __attribute__((ext_vector_type(8)));
+
+template <int U>
+__device__ __forceinline__ mx4_f32x16 mx4_mfma_fp4(const uint4& a, const uint4& b, mx4_f32x16 c, unsigned sa, unsigned sb) {
+  const mx4_i32x8 av = {(int)a.x, (int)a.y, (int)a.z, (int)a.w, 0, 0, 0, 0}, bv = {(int)b.x, (int)b.y, (int)b.z, (int)b.w, 0, 0, 0, 0};   // (FP4 reads four registers)
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, c, 4, 4, U, (int)sa, U, (int)sb);   // cbsz = blgp = 4: E2M1; op_sel U: byte U of the scale registers
+}
+
+template <int TM>
+__global__ __launch_bounds__(256) void k_gemm_mx4a4(const unsigned char* __restrict__ XQ, const unsigned char* __restrict__ XS, int ldsc, const unsigned char* __restrict__ W,
+                                                       const float* __restrict__ bias, int S, int N, int K, int act, float* __restrict__ Y, float* __restrict__ part, int KS,
+                                                       int mtiles, int ntiles) {
+  constexpr int BM = 64 * TM;
+  const int xcd = blockIdx.x & 7, jj0 = blockIdx.x >> 3;
+  const int mt = jj0 % mtiles, rest = jj0 / mtiles, ks = rest % KS, nt = (rest / KS) * 8 + xcd;
+  if (nt >= ntiles) return;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
+  const int m0 = mt * BM, n0 = nt * 128;
+  const int KC = (K + 511) >> 9;
+  const int nk = K >> 6, ng = (nk + 3) >> 2, g_beg = (int)((long long)ks * ng / KS), g_end = (int)((long long)(ks + 1) * ng / KS);
+  // byte offsets of this lane's rows (S K < 2^32 and N K < 2^32 on this path: every offset fits 32 bits); rows past the edge are clamped, their results dropped
+  unsigned xa[TM], xs[TM], wb[2], ws[2];
+#pragma unroll
+  for (int t = 0; t < TM; t++) {
+    const unsigned row = (unsigned)min(m0 + wm * 32 * TM + 32 * t + r, S - 1);
+    xa[t] = row * (unsigned)(K >> 1) + 16u * h;
+    xs[t] = row * (unsigned)ldsc;
+  }
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    const unsigned n = (unsigned)min(n0 + wn * 64 + 32 * j + r, N - 1);
+    const unsigned tile0 = (n >> 2) * (unsigned)KC * MX4_TILE;
+    wb[j] = tile0 + (n & 3u) * 256u + 16u * h;
+    ws[j] = tile0 + 1024u + (n & 3u) * 16u;
+  }
+  auto issue = [&](int g, uint4 (&a)[TM][4], uint4 (&b)[2][4], uint2 (&sa)[TM], uint2 (&sb)[2]) {
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const unsigned kt = (unsigned)min(4 * g + u, nk - 1);
+#pragma unroll
+      for (int t = 0; t < TM; t++) a[t][u] = *(const uint4*)(XQ + (xa[t] + kt * 32u));
+#pragma unroll
+      for (int j = 0; j < 2; j++) b[j][u] = *(const uint4*)(W + (wb[j] + (kt >> 3) * MX4_TILE + (kt & 7u) * 32u));
+    }
+#pragma unroll
+    for (int t = 0; t < TM; t++) sa[t] = *(const uint2*)(XS + (xs[t] + 8u * g));
+#pragma unroll
+    for (int j = 0; j < 2; j++) sb[j] = *(const uint2*)(W + (ws[j] + (unsigned)(g >> 1) * MX4_TILE + 8u * (g & 1)));
+  };
+  // Accumulation.  The instruction sums its 64 k -- two blocks, one per half of the wave -- and C in f32 in one pass, and what lies many binades below the
+  // largest term is lost: on rows whose blocks mix scales from 2^-30 to 2^0 a running f32 C gave up to 2.5 x the dense 16-bit GEMM's normalised error, and so
+  // did folding C into doubles every four steps (the worst elements unchanged to sixteen digits: the loss is inside the instruction).  So every MFMA
+  // is given ONE block and a zero C: a step runs twice, each time with the other half's B piece cleared (code 0 is +0: exact zeros), which leaves per result
+  // the dot product of 32 E2M1 x E2M1 products under one common scale -- at most 32 . 36 in units of a quarter of that scale, exact in f32 -- and the blocks'
+  // values are summed in double and rounded to f32 once, as k_gemv_mx4 carries its rows.
+  double acc[TM][2][16];
+#pragma unroll
+  for (int t = 0; t < TM; t++)
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+      for (int i = 0; i < 16; i++) acc[t][j][i] = 0.0;
+  const unsigned sel = 0x06040200u + 0x01010101u * (unsigned)h;      // bytes h, 2 + h, 4 + h, 6 + h of a group's eight scale bytes
+  auto consume = [&](int g, const uint4 (&a)[TM][4], const uint4 (&b)[2][4], const uint2 (&sa)[TM], const uint2 (&sb)[2]) {
+    if (g >= g_end) return;
+    unsigned pa[TM], pb[2];
+#pragma unroll
+    for (int t = 0; t < TM; t++) pa[t] = __builtin_amdgcn_perm(sa[t].y, sa[t].x, sel);
+#pragma unroll
+    for (int j = 0; j < 2; j++) pb[j] = __builtin_amdgcn_perm(sb[j].y, sb[j].x, sel);
+    auto step = [&](auto uc) {
+      constexpr int u = decltype(uc)::value;
+      if (4 * g + u < nk) {
+#pragma unroll
+        for (int half = 0; half < 2; half++) {
+          uint4 bh[2];
+#pragma unroll
+          for (int j = 0; j < 2; j++) bh[j] = h == half ? b[j][u] : make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+          for (int t = 0; t < TM; t++)
+#pragma unroll
+            for (int j = 0; j < 2; j++) {
+              mx4_f32x16 z;
+#pragma unroll
+              for (int i = 0; i < 16; i++) z[i] = 0.f;
+              const mx4_f32x16 tile = mx4_mfma_fp4<u>(a[t][u], bh[j], z, pa[t], pb[j]);
+#pragma unroll
+              for (int i = 0; i < 16; i++) acc[t][j][i] += (double)tile[i];
+            }
+        }
+      }
+    };
+    step(std::integral_constant<int, 0>()); step(std::integral_constant<int, 1>()); step(std::integral_constant<int, 2>()); step(std::integral_constant<int, 3>());
+  };
+  if (g_end > g_beg) {
+    uint4 a0[TM][4], a1[TM][4], b0[2][4], b1[2][4];
+    uint2 sa0[TM], sa1[TM], sb0[2], sb1[2];
+    issue(g_beg, a0, b0, sa0, sb0);
+    for (int g = g_beg; g < g_end; g += 2) {
+      issue(min(g + 1, g_end - 1), a1, b1, sa1, sb1); consume(g, a0, b0, sa0, sb0);
+      issue(min(g + 2, g_end - 1), a0, b0, sa0, sb0); consume(g + 1, a1, b1, sa1, sb1);
+    }
+  }
+  // C layout: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    const int n = n0 + wn * 64 + 32 * j + r;
+    if (n < N) {
+      const float bv = (!part && bias) ? bias[n] : 0.f;
+#pragma unroll
+      for (int t = 0; t < TM; t++)
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+          const int m = m0 + wm * 32 * TM + 32 * t + (i & 3) + 8 * (i >> 2) + 4 * h;
+          if (m < S) {
+            const float v = (float)acc[t][j][i];
+            if (part) part[((size_t)ks * S + m) * N + n] = v;
+            else Y[(size_t)m * N + n] = round_act(__fadd_rn(v, bv), act);
+          }
+        }
+    }
+  }
+}
+
+bool bzk_gemm_mx4a4_ok(const LinearDev& L) { return L.kind == LK_MX4 && L.K % 64 == 0 && L.K >= 64 && L.N % 64 == 0 && L.w != nullptr; }
+
+// codes [S][K / 2], scales [S][ldsc] with ldsc = bzk_mx4_quant_ld(K) (bzk_mx4_quant_rows wrote them); act: rounding of the output (BZ_F32: none); ws: split-K partials
+int bzk_gemm_mx4a4(hipStream_t s, const LinearDev& L, const void* codes, const void* scales, int ldsc, int S, int act, float* y, float* ws, size_t ws_bytes) {
+  const int N = L.N, K = L.K;
+  if (!bzk_gemm_mx4a4_ok(L)) BZ_FAIL(BZ_E_UNSUPPORTED, "gemm_mx4a4: mxfp4 weights with K %% 64 == 0 only");
+  if (S <= 0 || N <= 0 || ldsc != bzk_mx4_quant_ld(K)) BZ_FAIL(BZ_E_INVALID, "gemm_mx4a4: S=%d N=%d scale stride %d", S, N, ldsc);
+  if ((unsigned long long)S * K >= (1ull << 32) || (unsigned long long)N * K >= (1ull << 32) || bzk_mx4_bytes(N, K) >= ((size_t)1 << 32))
+    BZ_FAIL(BZ_E_UNSUPPORTED, "gemm_mx4a4: operand of 2^32 elements or more");
+  const double flops = 2.0 * S * (double)N * K;
+  const int TM = S <= 64 ? 1 : 2, BM = 64 * TM;
+  const int mtiles = (S + BM - 1) / BM, ntiles = (N + 127) / 128, ng = (K / 64 + 3) / 4;
+  const long long tiles = (long long)mtiles * ntiles;
+  int KS = 1;
+  if (ws) {
+    while (KS * 2 * tiles <= 320 && KS * 2 <= ng && KS < 16 && (size_t)KS * 2 * S * N * 4 <= ws_bytes) KS *= 2;   // (KS <= ng: no split is empty)
+  }
+  float* part = KS > 1 ? ws : nullptr;
+  const unsigned grid = 8u * (unsigned)((ntiles + 7) / 8) * (unsigned)mtiles * (unsigned)KS;
+#define LAUNCH_MX4A4(M) BZ_LAUNCH("gemm_mx4a4_mfma", flops, (k_gemm_mx4a4<M>), dim3(grid), dim3(256), 0, s, (const unsigned char*)codes, (const unsigned char*)scales, ldsc, \
+    (const unsigned char*)L.w, L.bias, S, N, K, act, y, part, KS, mtiles, ntiles)
+  if (TM == 1) LAUNCH_MX4A4(1); else LAUNCH_MX4A4(2);
+#undef LAUNCH_MX4A4
   BZ_HIP(hipGetLastError());
   if (KS > 1) {
     const size_t SN = (size_t)S * N;

@@ -752,6 +752,18 @@ class LoadedModel:
         L.check(L.lib().bz_quant_matmul(self.h, name.encode(), xt.h, S, y.h))
         return y.to_numpy()
 
+    def set_mxfp4_activations(self, mode):
+        """0: 16-bit activations (the default); 1: FP4 activations on the block-scaled FP4 MFMA wherever rows meet an MXFP4 linear in a GEMM"""
+        L.check(L.lib().bz_model_set_mxfp4_activations(self.h, int(mode)))
+
+    def mxfp4_quant_rows(self, x):
+        """op level: the W4A4 activation quantiser on x [S, K] -> (codes U8 [S, K/2], scales U8 [S, K/32])"""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        S, K = x.shape
+        tx, tc, ts = self.dev.tensor(x), self.dev.zeros((S, K // 2), L.U8), self.dev.zeros((S, K // 32), L.U8)
+        L.check(L.lib().bz_mxfp4_quant_rows(self.h, tx.h, S, K, tc.h, ts.h))
+        return tc.to_numpy(), ts.to_numpy()
+
     def linear_shape(self, name):
         return self._shapes[name]
 

@@ -145,6 +145,18 @@ int bz_model_add_fp8(bz_model* m, const char* name, int64_t N, int64_t K, const 
  * f32 activations, an MXFP4 lm_head: BZ_E_UNSUPPORTED at bz_model_finalize).  Beyond the reference.  New symbol only: BZ_ABI_VERSION is unchanged. */
 int bz_model_add_mxfp4(bz_model* m, const char* name, int64_t N, int64_t K, const uint8_t* weight /*[N][K/2]*/, const uint8_t* scale /*[N][K/32]*/,
                        const float* bias /*nullable [N]*/);
+/* W4A4 for the MXFP4 linears of a finalized model, opt-in because it changes results.  mode 0 (the default): 16-bit activations, every launch and bit as
+ * without this call.  mode 1: wherever rows of activations meet an MXFP4 linear in a GEMM -- prompts on the batched route, bz_forward_paged_batch, the batched
+ * decode graphs, the request engine, bz_prefill_matmul -- the rows are quantised to MXFP4 first (blocks of 32 along K, scale code clamp(floor(log2(max |x|)) - 2
+ * + 127, 0, 252), 127 for an all-zero block; elements to the nearest E2M1 value, ties to the even significand, saturating at 6) and the product runs on the
+ * block-scaled FP4 matrix instruction: y = R(f32(sum_k xq[k] W[n][k]) + bias[n]), accumulated in f32.  The single-stream decode GEMV, and prompts short enough to
+ * stay on the decode kernels (BZ_EXACT_PREFILL_MAX rows), keep 16-bit activations in either mode.  The quantization_config's input_tensors entry of a checkpoint is
+ * not read: only this call turns the mode on.  A graph captured earlier keeps the arithmetic it was captured with.  A model without an MXFP4 linear:
+ * BZ_E_UNSUPPORTED; a mode other than 0 or 1: BZ_E_INVALID.  Beyond the reference.  New symbols only: BZ_ABI_VERSION is unchanged. */
+int bz_model_set_mxfp4_activations(bz_model* m, int mode);
+/* op level: that quantiser on x F32 [S,K] (K % 64 == 0), rounded to the model's activation dtype (f16 / bf16) first as bz_prefill_matmul does: codes U8 [S,K/2]
+ * (the low nibble of byte j is element 2 j) and scales U8 [S,K/32], row-major.  Finite inputs only. */
+int bz_mxfp4_quant_rows(bz_model* m, const bz_tensor* x, int S, int K, bz_tensor* codes, bz_tensor* scales);
 /* LoadedModel::load(&config.model, &mut vb) (awq.rs:133-136): validates names/shapes, repacks weights into the
  * kernels' HBM layout, builds RoPE tables and workspaces.  Host copies passed to add_* may be freed afterwards. */
 int bz_model_finalize(bz_model* m);
@@ -813,7 +825,8 @@ int bz_probe_hbm_read(bz_device* dev, size_t bytes, int iters, double* gbs);
 int bz_quant_matmul(bz_model* m, const char* name, const bz_tensor* x, int S, bz_tensor* y);
 /* Prefill GEMM on the matrix cores: y[S,N] = round16(x)[S,K] . W[N,K]^T, f32 accumulate, result unrounded.  Dense f16 / bf16 weights
  * (K % 64 == 0, x rounded to the weight dtype), or int4 group-quantised weights without act-order (AWQ / GPTQ: x rounded to f16, S >= 9).  The same kernel runs inside bz_forward_kv / bz_forward_paged when a dense 16-bit Llama-family model is given S >= 8 tokens
- * (regular.rs:89-117 bf16 SafeTensors path; boostr's matmul behind LoadedModel::forward_with_kv_cache at executor_generate.rs:357). */
+ * (regular.rs:89-117 bf16 SafeTensors path; boostr's matmul behind LoadedModel::forward_with_kv_cache at executor_generate.rs:357).  An MXFP4 name follows the model's
+ * bz_model_set_mxfp4_activations mode. */
 int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor* x, int S, bz_tensor* y);
 /* DequantOps: whole weight -> F32 [N,K] on host (from the REPACKED device layout: validates the repack) */
 int bz_dequant(bz_model* m, const char* name, float* host_out);
