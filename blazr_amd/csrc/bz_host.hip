@@ -238,7 +238,8 @@ extern "C" int bz_tensor_to_host_pipelined(const bz_tensor* t, uint64_t ev, void
 // model
 // ---------------------------------------------------------------------------------------------------------
 struct RawTensor {
-  int kind = 0;  // 0 dense, 1 awq, 2 gptq, 3 gguf, 4 fp8 (d0 = e4m3 bytes [N][K], d1 = f32 scales [N]), 5 mxfp4 (d0 = e2m1 codes [N][K/2], d1 = e8m0 codes [N][K/32])
+  int kind = 0;  // 0 dense, 1 awq, 2 gptq, 3 gguf, 4 fp8 (d0 = e4m3 bytes [N][K], d1 = f32 scales [N]), 5 mxfp4 (d0 = e2m1 codes [N][K/2], d1 = e8m0 codes [N][K/32]),
+                 // 6 int8 w8a8 (d0 = int8 [N][K], d1 = f32 scales [N])
   int dtype = BZ_F32;
   std::vector<int64_t> shape;
   int64_t N = 0, K = 0; int gs = 0; int ggml_type = 0;
@@ -335,6 +336,8 @@ struct bz_model {
   // MXFP4 linears: has_mx4 -- the model holds one; mx4_a4 -- bz_model_set_mxfp4_activations (0: 16-bit activations, 1: FP4); the quantised rows of a
   // prefill GEMM's input (codes [rows][K / 2], scales [rows][bzk_mx4_quant_ld(K)]), sized with the prefill workspace
   bool has_mx4 = false; int mx4_a4 = 0; void* pf_xc4 = nullptr; void* pf_xs4 = nullptr;
+  // INT8 W8A8 linears: has_i8 -- the model holds one; the int8 codes and row scales of a prompt chunk's rows (k_i8_quant_rows -> k_gemm_i8a8), sized in prefill_ws
+  bool has_i8 = false; void* pf_xc8 = nullptr; float* pf_xs8 = nullptr;
   long long* ring[3] = {nullptr, nullptr, nullptr};
   float* dring[3] = {nullptr, nullptr, nullptr};   // direct-output twins of the ring (ROWS kernels)
   int ring_n = 0;
@@ -590,6 +593,31 @@ extern "C" int bz_model_add_mxfp4(bz_model* m, const char* name, int64_t N, int6
   BZ_API_END
 }
 
+// INT8 W8A8 weights (compressed-tensors int-quantized): W[n][k] = s[n] q[n][k], q int8 (-128 included), the activations quantised per row by the kernels
+// (bz_int8.hip).  The scales are kept as one f32 per row (a per-tensor scale is broadcast here).  K <= 131072 keeps the int32 sum of a row inside its range.
+extern "C" int bz_model_add_int8(bz_model* m, const char* name, int64_t N, int64_t K, const int8_t* weight, const float* scale, int64_t n_scale, const float* bias) {
+  BZ_API_BEGIN
+  BZ_TRY(check_add(m, name));
+  if (!weight || !scale) BZ_FAIL(BZ_E_INVALID, "add_int8 '%s': null data", name);
+  if (N <= 0 || K <= 0 || N % 64 || K % 64) BZ_FAIL(BZ_E_UNSUPPORTED, "add_int8 '%s': N=%lld and K=%lld must be positive multiples of 64", name, (long long)N, (long long)K);
+  if (K > 131072) BZ_FAIL(BZ_E_UNSUPPORTED, "add_int8 '%s': K=%lld is beyond 131072 (the int32 sum of a row could overflow)", name, (long long)K);
+  if ((uint64_t)N * (uint64_t)K >= (1ull << 32)) BZ_FAIL(BZ_E_UNSUPPORTED, "add_int8 '%s': 2^32 weights or more", name);
+  if (n_scale != 1 && n_scale != N) BZ_FAIL(BZ_E_INVALID, "add_int8 '%s': %lld scales (one per tensor or one per output row, N=%lld)", name, (long long)n_scale, (long long)N);
+  for (int64_t i = 0; i < n_scale; i++)
+    if (!std::isfinite(scale[i]) || !(scale[i] > 0.f)) BZ_FAIL(BZ_E_INVALID, "add_int8 '%s': scale[%lld] is not a finite positive number", name, (long long)i);
+  if (bias) for (int64_t i = 0; i < N; i++) if (!std::isfinite(bias[i])) BZ_FAIL(BZ_E_INVALID, "add_int8 '%s': bias[%lld] is not finite", name, (long long)i);
+  const size_t n = (size_t)N * (size_t)K;
+  RawTensor r; r.kind = 6; r.N = N; r.K = K; r.shape = {N, K}; r.bytes = n + (size_t)N * 4;
+  std::vector<float> sc((size_t)N);
+  for (int64_t i = 0; i < N; i++) sc[(size_t)i] = scale[n_scale == 1 ? 0 : i];
+  BZ_TRY(upload(m->dev, &r.d0, weight, n));
+  BZ_TRY(upload(m->dev, &r.d1, sc.data(), (size_t)N * 4));
+  if (bias) { void* b; BZ_TRY(upload(m->dev, &b, bias, (size_t)N * 4)); r.d_bias = (float*)b; }
+  m->raw[name] = r;
+  return BZ_OK;
+  BZ_API_END
+}
+
 // --- finalize helpers ---------------------------------------------------------------------------------------
 static int choose_gw(int N, int K, int target) {
   const int G = K / 128, nst = (N + 255) / 256;
@@ -696,12 +724,13 @@ static int f8_choose_sk(int N, int K) {
   if (env > 1) return (K + 255) / 256 >= env ? env : 1;
   return bzk_f8_choose_sk(N, K);
 }
-static int build_f8(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L) {
+// (one body for the two kinds whose device layout is a row-major byte per weight with an f32 scale per row: LK_F8 and LK_I8)
+static int build_byte_rows(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L, int kind, const char* what) {
   const int K = (int)rs[0]->K;
   int N = 0;
   bool any_bias = false;
-  for (auto* r : rs) { N += (int)r->N; any_bias |= r->d_bias != nullptr; if (r->K != K) BZ_FAIL(BZ_E_UNSUPPORTED, "fused fp8 parts differ in K"); }
-  if ((uint64_t)N * (uint64_t)K >= (1ull << 32)) BZ_FAIL(BZ_E_UNSUPPORTED, "fused fp8 linear of 2^32 weights or more");
+  for (auto* r : rs) { N += (int)r->N; any_bias |= r->d_bias != nullptr; if (r->K != K) BZ_FAIL(BZ_E_UNSUPPORTED, "fused %s parts differ in K", what); }
+  if ((uint64_t)N * (uint64_t)K >= (1ull << 32)) BZ_FAIL(BZ_E_UNSUPPORTED, "fused %s linear of 2^32 weights or more", what);
   void *w, *sc, *cnt, *b = nullptr;
   hipStream_t st = m->dev->stream;
   if (rs.size() == 1) {
@@ -726,10 +755,20 @@ static int build_f8(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L
   BZ_TRY(dev_alloc(m, &cnt, (size_t)(N / 16) * 4));
   BZ_HIP(hipMemsetAsync(cnt, 0, (size_t)(N / 16) * 4, st));
   BZ_HIP(hipStreamSynchronize(st));
-  L->kind = LK_F8; L->N = N; L->K = K; L->wdt = BZ_U8; L->w = w; L->scales = sc; L->zeros = cnt; L->bias = (float*)b;
+  L->kind = kind; L->N = N; L->K = K; L->wdt = BZ_U8; L->w = w; L->scales = sc; L->zeros = cnt; L->bias = (float*)b;
   L->bytes = (size_t)N * K + (size_t)N * 4; L->algo_bytes = L->bytes;      // one byte per weight plus the scales
   return BZ_OK;
 }
+static int build_f8(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L) { return build_byte_rows(m, rs, L, LK_F8, "fp8"); }
+// INT8 W8A8 tensors concatenated along N, the file's bytes as they are; the split-K form's row-block counters in `zeros`, as for FP8
+static int i8_split_env() { const char* e = getenv("BZ_I8_SPLITK"); return e ? atoi(e) : -1; }   // as BZ_F8_SPLITK: 0 never, n > 1: n slices wherever a row has n chunks; read per finalize
+static int i8_choose_sk(int N, int K) {
+  const int env = i8_split_env();
+  if (env == 0) return 1;
+  if (env > 1) return (K + 255) / 256 >= env ? env : 1;
+  return bzk_i8_choose_sk(N, K);
+}
+static int build_i8(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L) { m->has_i8 = true; return build_byte_rows(m, rs, L, LK_I8, "int8"); }
 
 // MXFP4 tensors concatenated along N and repacked into the kernels' tiles (four rows x 512 k with their scale bytes, bz_mxfp4.hip); N % 64 == 0 per part, so
 // no tile straddles two parts and a part's tiles are a contiguous range; biases as build_f8 keeps them
@@ -853,6 +892,7 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
     else if (g[0]->kind == 3) BZ_TRY(build_gq(m, g, &L));
     else if (g[0]->kind == 4) BZ_TRY(build_f8(m, g, &L));
     else if (g[0]->kind == 5) BZ_TRY(build_mx4(m, g, &L));
+    else if (g[0]->kind == 6) BZ_TRY(build_i8(m, g, &L));
     else BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: tensor kind %d", g[0]->kind);
     F->parts.push_back(L); F->n_off.push_back(noff);
     // per-name views for the op-level API
@@ -867,10 +907,10 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
       } else if (L.kind == LK_ROWS) {
         V.sk = 1;
         V.w = (char*)L.w + (size_t)sub * L.K * bz_dtype_size(L.wdt);
-      } else if (L.kind == LK_F8) {
+      } else if (L.kind == LK_F8 || L.kind == LK_I8) {
         V.w = (char*)L.w + (size_t)sub * L.K; V.scales = (float*)L.scales + sub; V.zeros = (unsigned*)L.zeros + sub / 16;
         V.bias = L.bias ? L.bias + sub : nullptr;
-        V.sk = f8_choose_sk(V.N, V.K);
+        V.sk = L.kind == LK_F8 ? f8_choose_sk(V.N, V.K) : i8_choose_sk(V.N, V.K);
       } else if (L.kind == LK_MX4) {
         V.w = (char*)L.w + bzk_mx4_bytes(sub, L.K);
         V.bias = L.bias ? L.bias + sub : nullptr;
@@ -897,7 +937,8 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
   static const bool no_sk = getenv("BZ_NO_ROWS_SPLITK") != nullptr;
   for (auto& p : F->parts) if (p.kind == LK_ROWS && !no_sk) p.sk = bzk_rows_choose_sk(p.N, p.K);
   for (auto& p : F->parts) if (p.kind == LK_F8) p.sk = f8_choose_sk(p.N, p.K);
-  auto is_fix = [](const LinearDev& p) { return (p.kind != LK_ROWS && p.kind != LK_F8 && p.kind != LK_MX4) || p.sk > 1; };   // (an mxfp4 linear never splits K)
+  for (auto& p : F->parts) if (p.kind == LK_I8) p.sk = i8_choose_sk(p.N, p.K);
+  auto is_fix = [](const LinearDev& p) { return (p.kind != LK_ROWS && p.kind != LK_F8 && p.kind != LK_MX4 && p.kind != LK_I8) || p.sk > 1; };   // (an mxfp4 linear never splits K)
   F->fix_out = is_fix(F->parts[0]);
   for (auto& p : F->parts) if (is_fix(p) != F->fix_out) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: mixed fixed-point/direct parts in one fused linear");
   for (auto* r : rs) { raw_free(*r); r->consumed = true; }
@@ -1003,7 +1044,8 @@ static void fill_prompt_traits(bz_model* m) {
         // 16-bit activations: dense in the activation dtype or fp8 (fp8 weights expand to it exactly: the MFMA GEMM), or int4 without act-order (the
         // multi-row dot4 GEMM; exact_cap: what the exact rows can use of it)
         const bool one = F->parts.size() == 1;
-        const bool dense_ok = one && ((F->parts[0].kind == LK_ROWS && F->parts[0].wdt == act) || bzk_gemm_f8w_ok(F->parts[0], act) || bzk_gemm_mx4w_ok(F->parts[0], act));
+        const bool dense_ok = one && ((F->parts[0].kind == LK_ROWS && F->parts[0].wdt == act) || bzk_gemm_f8w_ok(F->parts[0], act) || bzk_gemm_mx4w_ok(F->parts[0], act) ||
+                                     bzk_gemm_i8a8_ok(F->parts[0], act));
         const bool q4_ok = one && bzk_gemm_q4g_rows_ok(F->parts[0]);
         if (!dense_ok && !q4_ok) t.proj_16 = 0;
         if (dense_ok) t.any_dense = 1;
@@ -1122,6 +1164,10 @@ extern "C" int bz_model_finalize(bz_model* m) {
     for (auto& kv : m->raw) if (kv.second.kind == 5) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: mxfp4 tensor '%s': mxfp4 weights need f16 or bf16 activations", kv.first.c_str());
   if (m->cfg.arch != BZ_ARCH_LLAMA)
     for (auto& kv : m->raw) if (kv.second.kind == 5) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: mxfp4 tensor '%s': mxfp4 weights are built for the Llama family only", kv.first.c_str());
+  if (m->cfg.act_dtype == BZ_F32)   // (the quantiser reads rows rounded to a 16-bit dtype; the GEMM path quantises 16-bit rows)
+    for (auto& kv : m->raw) if (kv.second.kind == 6) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: int8 tensor '%s': int8 weights need f16 or bf16 activations", kv.first.c_str());
+  if (m->cfg.arch != BZ_ARCH_LLAMA)
+    for (auto& kv : m->raw) if (kv.second.kind == 6) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: int8 tensor '%s': int8 weights are built for the Llama family only", kv.first.c_str());
   if (m->cfg.arch == BZ_ARCH_MAMBA2) return finalize_mamba2(m);
   if (m->cfg.arch == BZ_ARCH_DEEPSEEK2) return finalize_dsv2(m);
   const bz_model_config& c = m->cfg;
@@ -1190,6 +1236,8 @@ extern "C" int bz_model_finalize(bz_model* m) {
     } else if (!tied) {
       // (the head reads argmax partials or the ring's fixed point; k_gemv_mx4 gives neither)
       { auto it = m->raw.find("lm_head.weight"); if (it != m->raw.end() && it->second.kind == 5) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: mxfp4 tensor 'lm_head.weight': an mxfp4 lm_head is not built (keep it 16-bit)"); }
+      // (likewise k_gemv_i8; the files keep lm_head on their `ignore` list)
+      { auto it = m->raw.find("lm_head.weight"); if (it != m->raw.end() && it->second.kind == 6) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: int8 tensor 'lm_head.weight': an int8 lm_head is not built (keep it 16-bit)"); }
       BZ_TRY(build_fused(m, {"lm_head"}, &m->lm_head));
       force_direct(&m->lm_head);
       // an fp8 lm_head takes the path of an int4 one: fixed-point output, converted after the launch (the split form, at least two slices)
@@ -2212,6 +2260,10 @@ static int prefill_ws(bz_model* m, int rows) {
     BZ_TRY(dev_alloc(m, &p, (size_t)rows * xw / 2)); m->pf_xc4 = p;
     BZ_TRY(dev_alloc(m, &p, (size_t)rows * bzk_mx4_quant_ld((int)xw))); m->pf_xs4 = p;
   }
+  if (m->has_i8) {
+    BZ_TRY(dev_alloc(m, &p, (size_t)rows * xw)); m->pf_xc8 = p;
+    BZ_TRY(dev_alloc(m, &p, (size_t)rows * 4)); m->pf_xs8 = (float*)p;
+  }
   if (c.act_dtype == BZ_F32) {
     BZ_TRY(dev_alloc(m, &p, (size_t)rows * 3 * xw * 2)); m->pf_x3 = p;
     BZ_TRY(dev_alloc(m, &p, (size_t)rows * 4)); m->pf_rscale = (float*)p;
@@ -2235,6 +2287,10 @@ static int pf_gemm(bz_model* m, const LinearDev& P, const void* x16, int n, floa
     return bzk_gemm_mx4a4(st, P, m->pf_xc4, m->pf_xs4, ld, n, act, y, m->pf_ws, m->pf_ws_bytes);
   }
   if (P.kind == LK_MX4) return bzk_gemm_mx4w(st, P, act, x16, n, act, y, m->pf_ws, m->pf_ws_bytes);
+  if (P.kind == LK_I8) {   // W8A8: the rows quantised once (a fused q/k/v or gate/up is one linear, so one input is quantised once), then both operands on the int8 MFMA
+    BZ_TRY(bzk_i8_quant_rows(st, act, x16, n, P.K, m->pf_xc8, m->pf_xs8));
+    return bzk_gemm_i8a8(st, P, m->pf_xc8, m->pf_xs8, n, act, y);
+  }
   if (exact == 2 && bzk_gemm_q4g_i8_ok(P, act)) {
     size_t po; const size_t need = bzk_pf_quant_i8_bytes(n, P.K, &po);
     if (m->pf_xq_bytes < need) { BZ_HIP(hipStreamSynchronize(st)); void* p; BZ_TRY(dev_alloc(m, &p, need)); m->pf_xq = p; m->pf_xq_bytes = need; }
@@ -2544,9 +2600,10 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
   const bool q4 = L.kind == LK_Q4G;   // int4 group-quantised weights x f16 activations (the AWQ / GPTQ prefill GEMM), S >= 9
   const bool f8 = L.kind == LK_F8;    // fp8 weights x the model's 16-bit activations (the W8A16 GEMM)
   const bool mx4 = L.kind == LK_MX4;  // mxfp4 weights likewise (the W4A16 GEMM)
+  const bool i8 = L.kind == LK_I8;    // int8 weights x the rows quantised to int8 (the W8A8 GEMM)
   const int f8dt = m->cfg.act_dtype == BZ_F16 ? BZ_F16 : BZ_BF16;
-  if (mx4 ? !bzk_gemm_mx4w_ok(L, f8dt) : f8 ? !bzk_gemm_f8w_ok(L, f8dt) : q4 ? !bzk_gemm_q4g_mfma_ok(L, BZ_F16, S) : (L.kind != LK_ROWS || (L.wdt != BZ_F16 && L.wdt != BZ_BF16)))
-    BZ_FAIL(BZ_E_UNSUPPORTED, "prefill_matmul: '%s' is neither a dense f16 / bf16 weight, an fp8 or mxfp4 weight nor an int4 weight without act-order (S >= 9)", name);
+  if (i8 ? !bzk_gemm_i8a8_ok(L, f8dt) : mx4 ? !bzk_gemm_mx4w_ok(L, f8dt) : f8 ? !bzk_gemm_f8w_ok(L, f8dt) : q4 ? !bzk_gemm_q4g_mfma_ok(L, BZ_F16, S) : (L.kind != LK_ROWS || (L.wdt != BZ_F16 && L.wdt != BZ_BF16)))
+    BZ_FAIL(BZ_E_UNSUPPORTED, "prefill_matmul: '%s' is neither a dense f16 / bf16 weight, an fp8, mxfp4 or int8 weight nor an int4 weight without act-order (S >= 9)", name);
   if (!x || !y || x->dtype != BZ_F32 || y->dtype != BZ_F32 || S <= 0 || x->nbytes < (size_t)S * L.K * 4 || y->nbytes < (size_t)S * L.N * 4)
     BZ_FAIL(BZ_E_INVALID, "prefill_matmul: x must be F32 [S,%d], y F32 [S,%d]", L.K, L.N);
   BZ_HIP(hipSetDevice(m->dev->id));
@@ -2555,7 +2612,7 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
   const size_t ws_bytes = (size_t)48 << 20;      // split-K partials, as the prefill paths pass them
   BZ_HIP(hipMalloc(&x16, (size_t)S * L.K * 2));
   if (hipMalloc(&ws, ws_bytes) != hipSuccess) { hipFree(x16); BZ_FAIL(BZ_E_OOM, "prefill_matmul: workspace"); }
-  const int xdt = (f8 || mx4) ? f8dt : q4 ? BZ_F16 : L.wdt;
+  const int xdt = (f8 || mx4 || i8) ? f8dt : q4 ? BZ_F16 : L.wdt;
   int rc = bzk_pf_cvt16(st, xdt, (const float*)x->ptr, (size_t)S * L.K, x16);
   if (rc == BZ_OK && mx4 && m->mx4_a4) {      // the model's mode: FP4 activations (the codes and scales take the head of the workspace, the partials the rest)
     const int ld = bzk_mx4_quant_ld(L.K);
@@ -2563,6 +2620,11 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
     if (cb + sb >= ws_bytes) { bz_set_error("prefill_matmul: S=%d rows of FP4 activations do not fit the workspace", S); rc = BZ_E_UNSUPPORTED; }
     if (rc == BZ_OK) rc = bzk_mx4_quant_rows(st, xdt, x16, S, L.K, ws, (char*)ws + cb, ld);
     if (rc == BZ_OK) rc = bzk_gemm_mx4a4(st, L, ws, (char*)ws + cb, ld, S, BZ_F32, (float*)y->ptr, (float*)((char*)ws + cb + sb), ws_bytes - cb - sb);
+  } else if (i8) {                             // the codes and row scales take the head of the workspace
+    const size_t cb = ((size_t)S * L.K + 255) & ~(size_t)255;
+    if (cb + (size_t)S * 4 > ws_bytes) { bz_set_error("prefill_matmul: S=%d rows of int8 activations do not fit the workspace", S); rc = BZ_E_UNSUPPORTED; }
+    if (rc == BZ_OK) rc = bzk_i8_quant_rows(st, xdt, x16, S, L.K, ws, (float*)((char*)ws + cb));
+    if (rc == BZ_OK) rc = bzk_gemm_i8a8(st, L, ws, (const float*)((char*)ws + cb), S, BZ_F32, (float*)y->ptr);
   } else
   if (rc == BZ_OK) rc = mx4 ? bzk_gemm_mx4w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : f8 ? bzk_gemm_f8w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : q4 ? bzk_gemm_q4g_mfma(st, L, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes)
                            : bzk_gemm_nt(st, L.wdt, x16, L.w, L.bias, S, L.N, L.K, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes);
@@ -4404,7 +4466,8 @@ extern "C" int bz_quant_matmul(bz_model* m, const char* name, const bz_tensor* x
   hipStream_t st = m->dev->stream;
   // op-level results are NOT rounded to the activation dtype: the caller sees the f32 accumulator
   long long* acc = nullptr;
-  const bool direct = L.kind == LK_ROWS || L.kind == LK_MX4 || (L.kind == LK_F8 && L.sk <= 1);   // (an fp8 linear's split form goes through the accumulator like the int4 kinds)
+  const bool direct = L.kind == LK_ROWS || L.kind == LK_MX4 || ((L.kind == LK_F8 || L.kind == LK_I8) && L.sk <= 1);   // (an fp8 linear's split form goes through the accumulator like the int4 kinds)
+  const bool i8_split = L.kind == LK_I8 && L.sk > 1;   // integer partials in the accumulator; the finishing workgroup stores the f32 result itself and hands the accumulator back zeroed
   if (!direct) BZ_HIP(hipMalloc(&acc, (size_t)L.N * 8));
   int rc = BZ_OK;
   // int4: the accumulator's unit per row.  The kernels' sums are exact up to one rounding per workgroup to the accumulator's grid; at the f32 grid (2^-32, +-2^31)
@@ -4427,6 +4490,7 @@ extern "C" int bz_quant_matmul(bz_model* m, const char* name, const bz_tensor* x
     else {
       rc = bzk_zero64(st, acc, L.N);
       o.acc = acc;
+      if (i8_split) o.split_f32 = (float*)y->ptr + (size_t)s * L.N;
       // an int4 linear's bias joins the sum after its rounding to f32, here where the accumulator is read back (f32 results have no room for bzk_fix_bias's in-place form)
       LinearDev Ls = L;
       const float* rb = nullptr;
@@ -4439,7 +4503,7 @@ extern "C" int bz_quant_matmul(bz_model* m, const char* name, const bz_tensor* x
       }
       p.act = grid;
       if (rc == BZ_OK) rc = bzk_gemv(st, Ls, p, o, grid);
-      if (rc == BZ_OK) rc = bzk_fix_to_f32(st, acc, L.N, BZ_F32, (float*)y->ptr + (size_t)s * L.N, rb, grid);
+      if (rc == BZ_OK && !i8_split) rc = bzk_fix_to_f32(st, acc, L.N, BZ_F32, (float*)y->ptr + (size_t)s * L.N, rb, grid);
     }
   }
   hipStreamSynchronize(st);
@@ -4458,7 +4522,7 @@ extern "C" int bz_dequant(bz_model* m, const char* name, float* host) {
   float* d;
   BZ_HIP(hipMalloc(&d, n * 4));
   int rc = L.kind == LK_Q4G ? bzk_dequant_q4g(m->dev->stream, L, d) : L.kind == LK_ROWS ? bzk_dequant_rows(m->dev->stream, L, d)
-         : L.kind == LK_F8 ? bzk_dequant_f8(m->dev->stream, L, d) : L.kind == LK_MX4 ? bzk_dequant_mx4(m->dev->stream, L, d) : bzk_dequant_gq(m->dev->stream, L, d);
+         : L.kind == LK_F8 ? bzk_dequant_f8(m->dev->stream, L, d) : L.kind == LK_I8 ? bzk_dequant_i8(m->dev->stream, L, d) : L.kind == LK_MX4 ? bzk_dequant_mx4(m->dev->stream, L, d) : bzk_dequant_gq(m->dev->stream, L, d);
   std::vector<float> tmp;
   if (rc == BZ_OK) rc = hipStreamSynchronize(m->dev->stream) == hipSuccess ? BZ_OK : BZ_E_HIP;  // the stream is non-blocking
   if (rc == BZ_OK) {

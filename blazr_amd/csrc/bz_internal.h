@@ -55,7 +55,7 @@ struct Pro {
 
 // (the public BZ_LIN_* values: bz_linear_traits_t carries a kind as it is)
 enum { LK_NONE = BZ_LIN_NONE, LK_Q4G = BZ_LIN_Q4G, LK_ROWS = BZ_LIN_ROWS, LK_Q4K = BZ_LIN_Q4K, LK_Q6K = BZ_LIN_Q6K, LK_Q80 = BZ_LIN_Q80, LK_Q5K = BZ_LIN_Q5K, LK_Q40 = BZ_LIN_Q40,
-       LK_Q41 = BZ_LIN_Q41, LK_Q50 = BZ_LIN_Q50, LK_Q51 = BZ_LIN_Q51, LK_F8 = BZ_LIN_F8, LK_MX4 = BZ_LIN_MX4 };
+       LK_Q41 = BZ_LIN_Q41, LK_Q50 = BZ_LIN_Q50, LK_Q51 = BZ_LIN_Q51, LK_F8 = BZ_LIN_F8, LK_MX4 = BZ_LIN_MX4, LK_I8 = BZ_LIN_I8 };
 
 // Device-resident linear layer in kernel layout.
 struct LinearDev {
@@ -213,6 +213,7 @@ struct GemvOut {
   int zero_n;
   float* amax_val; int* amax_idx; // ROWS argmax partials per block (nullptr: off)
   ConvShift shift;       // ROWS: optional side duty (cs == nullptr: none)
+  float* split_f32;      // I8 split-K form only: where the finishing workgroup stores the f32 result instead of the fixed-point value (it then zeroes acc); nullptr in the step
 };
 
 int bzk_gemv(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act);
@@ -228,6 +229,14 @@ int bzk_gemv_f8(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut
 bool bzk_gemm_f8w_ok(const LinearDev& L, int xdt);
 int bzk_gemm_f8w(hipStream_t s, const LinearDev& L, int dt, const void* x16, int S, int act, float* y, float* ws = nullptr, size_t ws_bytes = 0);
 int bzk_dequant_f8(hipStream_t s, const LinearDev& L, float* out);
+// INT8 W8A8: int8 weights, one f32 scale per row, activations quantised per row by the kernels (bz_int8.hip): decode GEMV with the quantiser in its prologue
+// (direct, or split-K with integer partials and the finish in the launch), the row quantiser and the int8 MFMA GEMM of the prompt path, read-back
+int bzk_i8_choose_sk(int N, int K);
+int bzk_gemv_i8(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act);
+int bzk_i8_quant_rows(hipStream_t s, int dt, const void* x16, int S, int K, void* codes, float* sx);
+bool bzk_gemm_i8a8_ok(const LinearDev& L, int xdt);
+int bzk_gemm_i8a8(hipStream_t s, const LinearDev& L, const void* codes, const float* sx, int S, int act, float* y);
+int bzk_dequant_i8(hipStream_t s, const LinearDev& L, float* out);
 // MXFP4 weights (E2M1 codes, an E8M0 scale per block of 32), in tiles of four rows x 512 k that carry their scales (bz_mxfp4.hip): load-time repack, decode GEMV
 // (direct output), W4A16 MFMA GEMM, read-back
 size_t bzk_mx4_bytes(int N, int K);

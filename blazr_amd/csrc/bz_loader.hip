@@ -306,19 +306,33 @@ int hf_config_to_pod(const JVal& j, bz_model_config* c, QuantInfo* q) {
       q->method = 3;
     } else if (m == "compressed-tensors") {
       const std::string fmt = qc->str("format");
-      if (fmt != "float-quantized") BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: compressed-tensors format '%s' is not implemented (float-quantized is)", fmt.c_str());
+      const bool i8 = fmt == "int-quantized";      // INT8 W8A8: int8 weights per channel / tensor, int8 activations per token, dynamic and symmetric
+      if (fmt != "float-quantized" && !i8)
+        BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: compressed-tensors format '%s' is not implemented (float-quantized and int-quantized are)", fmt.c_str());
       const JVal* groups = qc->get("config_groups");
       if (!groups || groups->t != JVal::OBJ || groups->o.empty()) BZ_FAIL(BZ_E_INVALID, "config.json: compressed-tensors quantization_config without config_groups");
       for (auto& g : groups->o) {
         const JVal* w = g.second.get("weights");
         if (!w || w->t != JVal::OBJ) BZ_FAIL(BZ_E_INVALID, "config.json: config_groups.%s has no weights entry", g.first.c_str());
         const std::string ty = w->str("type"), strategy = w->str("strategy", "tensor");
-        if (w->i64("num_bits", 0) != 8 || ty != "float")
-          BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights: num_bits %lld type '%s' is not implemented (8-bit float is)", g.first.c_str(), w->i64("num_bits", 0), ty.c_str());
+        if (w->i64("num_bits", 0) != 8 || ty != (i8 ? "int" : "float"))
+          BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights: num_bits %lld type '%s' is not implemented (8-bit %s is)", g.first.c_str(), w->i64("num_bits", 0), ty.c_str(),
+                  i8 ? "int" : "float");
         if (strategy != "tensor" && strategy != "channel")
           BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights.strategy '%s' is not implemented (tensor and channel are)", g.first.c_str(), strategy.c_str());
+        if (!i8) continue;
+        if (!w->boolean("symmetric", true)) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights.symmetric false (asymmetric int8 weights) is not implemented", g.first.c_str());
+        // the activations: int8 per token, dynamic, symmetric -- what the kernels' quantiser computes; a file that asks for anything else would be run wrongly
+        const JVal* a = g.second.get("input_activations");
+        if (!a || a->t != JVal::OBJ) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.input_activations is missing (weight-only int8 is not implemented)", g.first.c_str());
+        const std::string aty = a->str("type"), astr = a->str("strategy", "tensor");
+        if (a->i64("num_bits", 0) != 8 || aty != "int")
+          BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.input_activations: num_bits %lld type '%s' is not implemented (8-bit int is)", g.first.c_str(), a->i64("num_bits", 0), aty.c_str());
+        if (!a->boolean("dynamic", false)) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.input_activations.dynamic false (static activation scales) is not implemented", g.first.c_str());
+        if (!a->boolean("symmetric", true)) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.input_activations.symmetric false is not implemented", g.first.c_str());
+        if (astr != "token") BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.input_activations.strategy '%s' is not implemented (token is)", g.first.c_str(), astr.c_str());
       }
-      q->method = 3;
+      q->method = i8 ? 5 : 3;
     } else if (m == "quark") {
       // Quark MXFP4 exports (the *-MXFP4 releases): E2M1 weights in groups of 32 with an E8M0 scale, one scheme for every linear off the `exclude` list; run
       // weight-only, so global_quant_config.input_tensors is read past.  ASSUMPTION: these field names could not be checked against a published file;
@@ -441,6 +455,9 @@ void detect_quant(const std::string& dir, const StLoader& st, QuantInfo* q) {
   else {
     for (auto& kv : st.tensors)      // an E4M3 weight with its scale beside it
       if (kv.second.dtype == "F8_E4M3" && ends_with(kv.first, ".weight") && st.find(kv.first + "_scale")) { q->method = 3; break; }
+    if (!q->method)
+      for (auto& kv : st.tensors)    // likewise an I8 weight with its scale: INT8 W8A8
+        if (kv.second.dtype == "I8" && ends_with(kv.first, ".weight") && st.find(kv.first + "_scale")) { q->method = 5; break; }
   }
 }
 
@@ -605,6 +622,35 @@ int load_safetensors(bz_device* dev, const std::string& path, bz_model** out, bz
       if (N <= 0 || K <= 0 || t.bytes != (size_t)N * (size_t)K) { rc = BZ_E_INVALID; bz_set_error("fp8 layer '%s': weight bytes do not match its shape", base.c_str()); break; }
       rc = bz_model_add_fp8(m, name.c_str(), N, K, t.data, f32a.data(), (int64_t)ns, bi ? f32b.data() : nullptr);
       continue;
+    }
+    // INT8 W8A8 linears: <linear>.weight I8 [N,K] + <linear>.weight_scale ([] / [1] / [N] / [N,1]) + optional <linear>.bias; a .weight_zero_point may ride along
+    // when all of it is zero (symmetric weights)
+    {
+      auto i8_weight = [&](const std::string& w) { const StTensor* x = st.find(w); return x && x->dtype == "I8"; };
+      if (ends_with(name, ".weight_scale") && i8_weight(name.substr(0, name.size() - 6))) continue;
+      if (ends_with(name, ".bias") && i8_weight(name.substr(0, name.size() - 5) + ".weight")) continue;
+      if (ends_with(name, ".weight_zero_point") && i8_weight(name.substr(0, name.size() - 11))) {
+        for (size_t i = 0; i < t.bytes; i++)
+          if (t.data[i]) { rc = BZ_E_UNSUPPORTED; bz_set_error("tensor '%s': a nonzero weight_zero_point (asymmetric int8 weights) is not implemented", name.c_str()); break; }
+        if (rc != BZ_OK) break;
+        continue;
+      }
+      if (t.dtype == "I8") {
+        if (!ends_with(name, ".weight") || t.shape.size() != 2) { rc = BZ_E_UNSUPPORTED; bz_set_error("tensor '%s': I8 is read for 2-D <linear>.weight tensors only", name.c_str()); break; }
+        const std::string base = name.substr(0, name.size() - 7);
+        const StTensor* sc = st.find(base + ".weight_scale"); const StTensor* bi = st.find(base + ".bias");
+        const int64_t N = t.shape[0], K = t.shape[1];
+        if (!sc) { rc = BZ_E_INVALID; bz_set_error("int8 layer '%s': no .weight_scale beside the I8 weight", base.c_str()); break; }
+        size_t ns = 0;
+        const bool shape_ok = sc->shape.size() <= 2 && shape_elems(sc->shape, &ns) && (ns == 1 || (ns == (size_t)N && sc->shape[0] == N));
+        if (!shape_ok || !to_f32(sc, ns, &f32a))
+          { rc = BZ_E_INVALID; bz_set_error("int8 layer '%s': weight_scale must be F32 / F16 / BF16 of shape [], [1], [%lld] or [%lld,1]", base.c_str(), (long long)N, (long long)N); break; }
+        if (bi && (bi->shape.size() != 1 || bi->shape[0] != N || !to_f32(bi, (size_t)N, &f32b)))
+          { rc = BZ_E_INVALID; bz_set_error("int8 layer '%s': bias must be F32 / F16 / BF16 [%lld]", base.c_str(), (long long)N); break; }
+        if (N <= 0 || K <= 0 || t.bytes != (size_t)N * (size_t)K) { rc = BZ_E_INVALID; bz_set_error("int8 layer '%s': weight bytes do not match its shape", base.c_str()); break; }
+        rc = bz_model_add_int8(m, name.c_str(), N, K, (const int8_t*)t.data, f32a.data(), (int64_t)ns, bi ? f32b.data() : nullptr);
+        continue;
+      }
     }
     // MXFP4 (Quark) linears: <linear>.weight U8 [N, K/2] (two E2M1 codes per byte) + <linear>.weight_scale U8 [N, K/32] (E8M0) + optional <linear>.bias; the
     // tensors on the config's `exclude` list (lm_head, embeddings, norms) are 16-bit and take the dense path below

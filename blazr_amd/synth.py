@@ -66,6 +66,15 @@ PRESETS = {
                        tie_embeddings=True,
                        rope_scaling=dict(type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
                                          original_max_position_embeddings=64)),
+    # INT8 W8A8 checkpoints (the *-quantized.w8a8 releases): int8 weights with a scale per output channel, int8 activations per token (dynamic), 16-bit head
+    "llama3.1-8b-int8": dict(arch="llama", hidden=4096, n_layers=32, n_heads=32, n_kv_heads=8, head_dim=128, inter=14336,
+                             vocab=128256, rms_eps=1e-5, rope_theta=500000.0, act_dtype="bf16", quant="int8", int8_strategy="channel",
+                             max_seq_len=2048, tie_embeddings=False),
+    "tiny-int8": dict(arch="llama", hidden=256, n_layers=2, n_heads=4, n_kv_heads=2, head_dim=64, inter=512, vocab=1024,
+                      rms_eps=1e-5, rope_theta=10000.0, act_dtype="bf16", quant="int8", int8_strategy="channel", max_seq_len=256,
+                      tie_embeddings=True,
+                      rope_scaling=dict(type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                                        original_max_position_embeddings=64)),
     "tiny-q8_0": dict(arch="llama", hidden=256, n_layers=2, n_heads=4, n_kv_heads=2, head_dim=64, inter=512, vocab=1024,
                       rms_eps=1e-5, rope_theta=10000.0, act_dtype="f32", quant="q8_0", max_seq_len=256,
                       tie_embeddings=False, rope_interleaved=1),
@@ -272,6 +281,22 @@ def mxfp4_linear(name, N, K, bias=False, seed=BASE_SEED):
     return d
 
 
+def int8_linear(name, N, K, strategy, bias=False, std=0.02, seed=BASE_SEED):
+    """INT8 W8A8 weight [N, K] int8 with one f32 scale per output channel (`channel`) or per tensor (`tensor`): W = scale . weight.  The
+    codes are drawn directly, uniform over all 256 values (-128 included; an 8B model in seconds); the scales put the weights' standard
+    deviation near `std` and are bf16-representable, so a checkpoint may store them in any of F32 / F16 / BF16."""
+    if strategy not in ("channel", "tensor"):
+        raise ValueError(strategy)
+    r = _rng(name, seed)
+    q = r.integers(-128, 128, size=(N, K), dtype=np.int8)
+    rms = float(np.sqrt(np.mean(np.square(np.arange(-128, 128, dtype=np.float64)))))
+    scale = _repr((r.uniform(0.7, 1.4, size=N if strategy == "channel" else 1) * (std / rms)).astype(np.float32), "bf16")
+    d = dict(kind="int8", N=N, K=K, strategy=strategy, weight=q, scale=scale, bias=None)
+    if bias:
+        d["bias"] = _repr(r.standard_normal(N, dtype=np.float32) * 0.01, "bf16")
+    return d
+
+
 def gguf_blocks(name, ggml_type, N, K, seed=BASE_SEED):
     """Random but well-conditioned ggml blocks: rows of K weights, N rows -> uint8 [N, row_bytes]."""
     r = _rng(name, seed)
@@ -321,6 +346,8 @@ def _linear(cfg, name, N, K, layer=None, role=None, seed=BASE_SEED):
         return fp8_linear(name, N, K, cfg.get("fp8_strategy", "channel"), bias=cfg.get("bias", False), seed=seed)
     if q == "mxfp4":
         return mxfp4_linear(name, N, K, bias=cfg.get("bias", False), seed=seed)
+    if q == "int8":
+        return int8_linear(name, N, K, cfg.get("int8_strategy", "channel"), bias=cfg.get("bias", False), seed=seed)
     return dense_linear(name, N, K, cfg["act_dtype"], seed=seed)
 
 
@@ -399,7 +426,7 @@ def algorithmic_bytes_per_token(cfg):
     elif q == "q8_0":
         wb = lin // 32 * 34
         head = V * H // 32 * 34
-    elif q == "fp8":
+    elif q in ("fp8", "int8"):
         wb = lin + L * ((nq + 2 * nkv) * hd + 2 * H + 2 * I) * 4      # one byte per weight + an f32 scale per output row
         head = V * H * act_b
     elif q == "mxfp4":

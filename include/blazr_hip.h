@@ -145,6 +145,16 @@ int bz_model_add_fp8(bz_model* m, const char* name, int64_t N, int64_t K, const 
  * f32 activations, an MXFP4 lm_head: BZ_E_UNSUPPORTED at bz_model_finalize).  Beyond the reference.  New symbol only: BZ_ABI_VERSION is unchanged. */
 int bz_model_add_mxfp4(bz_model* m, const char* name, int64_t N, int64_t K, const uint8_t* weight /*[N][K/2]*/, const uint8_t* scale /*[N][K/32]*/,
                        const float* bias /*nullable [N]*/);
+/* INT8 W8A8 weights of the *-quantized.w8a8 SafeTensors releases (compressed-tensors "int-quantized"): int8 weights [N][K] with one scale per tensor (n_scale 1,
+ * broadcast) or per output row (n_scale N), optional f32 bias; the activations are quantised to int8 per row by the kernels, dynamically and symmetrically.  For
+ * a row x (rounded to the activation dtype): amax = max |x[k]|, sx = amax == 0 ? 1 : amax / 127, a[k] = clamp(rint(x[k] / sx), -127, 127) (f32 divisions, ties
+ * to even), acc[n] = sum_k a[k] weight[n][k] in int32 (exact), y[n] = R(f32(acc[n] (sx scale[n])) + bias[n]) with both products in double.  ASSUMPTION: the
+ * divisor 127 could not be checked against a published file (an observer may divide by 127.5); it is one constant in bz_int8.hip.  N % 64, K % 64 or
+ * K > 131072 (the int32 sum's bound): BZ_E_UNSUPPORTED; n_scale other than 1 or N, a scale that is not finite and positive: BZ_E_INVALID; each naming the
+ * tensor.  Llama family and 16-bit activations only (Mamba2, DeepSeek-V2, f32 activations, an int8 lm_head: BZ_E_UNSUPPORTED at bz_model_finalize).  Beyond
+ * the reference.  New symbol only: BZ_ABI_VERSION is unchanged. */
+int bz_model_add_int8(bz_model* m, const char* name, int64_t N, int64_t K, const int8_t* weight /*[N][K]*/, const float* scale, int64_t n_scale /*1 or N*/,
+                      const float* bias /*nullable [N]*/);
 /* W4A4 for the MXFP4 linears of a finalized model, opt-in because it changes results.  mode 0 (the default): 16-bit activations, every launch and bit as
  * without this call.  mode 1: wherever rows of activations meet an MXFP4 linear in a GEMM -- prompts on the batched route, bz_forward_paged_batch, the batched
  * decode graphs, the request engine, bz_prefill_matmul -- the rows are quantised to MXFP4 first (blocks of 32 along K, scale code clamp(floor(log2(max |x|)) - 2
@@ -175,7 +185,7 @@ enum { BZ_LAYER_TRANSFORMER = 0, BZ_LAYER_MAMBA2 = 1, BZ_LAYER_MAMBA3 = 2, BZ_LA
 typedef struct { int32_t format; /* 0 HuggingFace ("model." prefix), 1 Oxidizr */ int32_t num_layers, tie_word_embeddings; uint8_t layer_types[512]; } bz_detected_arch;
 /* boostr::model::detection::detect_architecture_from_names as the reference's tests pin it (loader/safetensors/detect_arch.rs:200-315) */
 int bz_detect_architecture_from_names(const char* const* names, int n, bz_detected_arch* out);
-typedef struct { int32_t quant_method; /* 0 none, 1 awq, 2 gptq, 3 fp8, 4 mxfp4 (quark) */ int32_t group_size; int32_t torch_dtype; /* BZ_* or -1 */ } bz_quant_info;
+typedef struct { int32_t quant_method; /* 0 none, 1 awq, 2 gptq, 3 fp8, 4 mxfp4 (quark), 5 int8 (w8a8) */ int32_t group_size; int32_t torch_dtype; /* BZ_* or -1 */ } bz_quant_info;
 /* HuggingFaceConfig::from_json(..).to_universal() + detect_dtype_from_config (loader/safetensors/config.rs:14-70,83-95): HF config.json text ->
  * config POD; quantization_config (detect_arch.rs:79-90,118-131,146-196) -> quant info.  AWQ / GPTQ force f16 (awq.rs:69-71). */
 int bz_config_from_hf_json(const char* json_text, bz_model_config* cfg, bz_quant_info* quant);
@@ -920,7 +930,7 @@ int bz_packed_totals_spec(const bz_score_row* rows /*[T]*/, const int32_t* seq_l
  * keeps one plan per layer and cache dtype (F32 / F16 / BF16); the step dispatches on it and decides one thing per call: the short or the long attention form,
  * from the context and BZ_SPLIT_MIN.  A fused linear is described by its parts (at most three).  Flags are 0 / 1.  New symbols only: BZ_ABI_VERSION is unchanged. */
 enum { BZ_LIN_NONE = 0, BZ_LIN_Q4G = 1, BZ_LIN_ROWS = 2, BZ_LIN_Q4K = 3, BZ_LIN_Q6K = 4, BZ_LIN_Q80 = 5, BZ_LIN_Q5K = 6, BZ_LIN_Q40 = 7, BZ_LIN_Q41 = 8, BZ_LIN_Q50 = 9,
-       BZ_LIN_Q51 = 10, BZ_LIN_F8 = 11, BZ_LIN_MX4 = 12 };
+       BZ_LIN_Q51 = 10, BZ_LIN_F8 = 11, BZ_LIN_MX4 = 12, BZ_LIN_I8 = 13 };
 typedef struct bz_linear_traits_t {
   int kind, N, K;        /* BZ_LIN_* */
   int wdt;               /* ROWS: the weights' dtype */
@@ -946,7 +956,7 @@ typedef struct bz_step_switches_t {
   int no_mlp_fusion, gguf_mlp_fusion, dsv2_f32_sums, no_moe_route_fusion;    /* BZ_NO_MLP_FUSION, BZ_GGUF_MLP_FUSION, BZ_DSV2_F32_SUMS, BZ_NO_MOE_ROUTE_FUSION set */
 } bz_step_switches_t;
 /* the kernel one GEMV launch takes (NONE: no such part) */
-enum { BZ_GEMV_NONE = 0, BZ_GEMV_F8 = 1, BZ_GEMV_Q4G_SLIM = 2, BZ_GEMV_Q4G = 3, BZ_GEMV_ROWS2 = 4, BZ_GEMV_ROWS = 5, BZ_GEMV_GQ_SLIM = 6, BZ_GEMV_GQ = 7, BZ_GEMV_UNSUPPORTED = 8, BZ_GEMV_MX4 = 9 };
+enum { BZ_GEMV_NONE = 0, BZ_GEMV_F8 = 1, BZ_GEMV_Q4G_SLIM = 2, BZ_GEMV_Q4G = 3, BZ_GEMV_ROWS2 = 4, BZ_GEMV_ROWS = 5, BZ_GEMV_GQ_SLIM = 6, BZ_GEMV_GQ = 7, BZ_GEMV_UNSUPPORTED = 8, BZ_GEMV_MX4 = 9, BZ_GEMV_I8 = 10 };
 /* attention and o_proj: PLAIN = attention, then the o_proj GEMV(s); FUSED_*: one launch (int4 / dense 16-bit / Q4_K o_proj over an f32 cache); SPLIT: split-KV
  * partials + merge + o_proj GEMV; SPLIT_FUSED: split-KV partials + merge with the int4 o_proj */
 enum { BZ_ATTN_PLAIN = 0, BZ_ATTN_FUSED_Q4G = 1, BZ_ATTN_FUSED_DENSE = 2, BZ_ATTN_FUSED_Q4K = 3, BZ_ATTN_SPLIT = 4, BZ_ATTN_SPLIT_FUSED = 5 };
