@@ -404,16 +404,16 @@ __device__ __forceinline__ float src_cvt(typename SrcRaw<FIX>::T r, int act) {
 }
 
 // NORM pass 1: v = R(h + prev) for the whole row -> sum of squares; slice elements [k0, k0+KR) are parked in xs
-template <int SWZ, bool FIX, bool PREV>
+template <int SWZ, bool FIX, bool PREV, int NT = 256>
 __device__ __forceinline__ double norm_pass1(const Pro& p, int k0, int KR, float* xs, bool writer) {
   const int tid = threadIdx.x;
   double ss = 0.0;
-  for (int base = 0; base < p.H; base += 4096) {
+  for (int base = 0; base < p.H; base += 16 * NT) {
     float4 hv[4];
     typename SrcRaw<FIX>::T pr[4][4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      const int i = min(base + j * 1024 + tid * 4, p.H - 4);
+      const int i = min(base + j * 4 * NT + tid * 4, p.H - 4);
       hv[j] = *(const float4*)(p.h_in + i);
       if (PREV) {
 #pragma unroll
@@ -422,7 +422,7 @@ __device__ __forceinline__ double norm_pass1(const Pro& p, int k0, int KR, float
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      const int i = base + j * 1024 + tid * 4;
+      const int i = base + j * 4 * NT + tid * 4;
       float v[4] = {hv[j].x, hv[j].y, hv[j].z, hv[j].w};
       if (PREV) {
 #pragma unroll
@@ -441,20 +441,20 @@ __device__ __forceinline__ double norm_pass1(const Pro& p, int k0, int KR, float
   return ss;
 }
 
-template <int SWZ, bool FIX, bool SILU>
+template <int SWZ, bool FIX, bool SILU, int NT = 256>
 __device__ __forceinline__ void plain_fill(const Pro& p, int k0, int KR, float* xs) {
   const int tid = threadIdx.x;
-  for (int base = 0; base < KR; base += 2048) {
+  for (int base = 0; base < KR; base += 8 * NT) {
     typename SrcRaw<FIX>::T a[8], b[8];
 #pragma unroll
     for (int e = 0; e < 8; e++) {
-      const int kk = k0 + min(base + e * 256 + tid, KR - 1);
+      const int kk = k0 + min(base + e * NT + tid, KR - 1);
       a[e] = src_raw<FIX>(p.src.p, kk);
       if (SILU) b[e] = src_raw<FIX>(p.src.p, p.H + kk);
     }
 #pragma unroll
     for (int e = 0; e < 8; e++) {
-      const int i = base + e * 256 + tid;
+      const int i = base + e * NT + tid;
       float v = src_cvt<FIX>(a[e], p.act);
       if (SILU) v = round_act(round_act(silu_f(v), p.act) * src_cvt<FIX>(b[e], p.act), p.act);
       if (i < KR) xs[xs_pos<SWZ>(i)] = v;
@@ -462,25 +462,26 @@ __device__ __forceinline__ void plain_fill(const Pro& p, int k0, int KR, float* 
   }
 }
 
-// Simple form (loads inside): used by the ROWS kernels (no act-order permutation there).  Slice [k0, k0+KR), KR > 0.
-template <int SWZ>
+// Simple form (loads inside): used by the ROWS kernels (no act-order permutation there).  Slice [k0, k0+KR), KR > 0.  NT: threads of the workgroup (the
+// gated forms are written for 256).
+template <int SWZ, int NT = 256>
 __device__ void build_x_simple(const Pro& p, int k0, int KR, float* xs, float* red, bool writer) {
   const int tid = threadIdx.x;
   if (KR <= 0) { __syncthreads(); return; }
   if (p.mode == PRO_NORM) {
     double ssd;
-    if (p.src.p == nullptr) ssd = norm_pass1<SWZ, false, false>(p, k0, KR, xs, writer);
-    else if (p.src.fix) ssd = norm_pass1<SWZ, true, true>(p, k0, KR, xs, writer);
-    else ssd = norm_pass1<SWZ, false, true>(p, k0, KR, xs, writer);
-    const float ss = (float)block_sum_d<4>(ssd);   // the rounded exact sum (also orders the xs writes of pass 1 before the reads below)
+    if (p.src.p == nullptr) ssd = norm_pass1<SWZ, false, false, NT>(p, k0, KR, xs, writer);
+    else if (p.src.fix) ssd = norm_pass1<SWZ, true, true, NT>(p, k0, KR, xs, writer);
+    else ssd = norm_pass1<SWZ, false, true, NT>(p, k0, KR, xs, writer);
+    const float ss = (float)block_sum_d<NT / 64>(ssd);   // the rounded exact sum (also orders the xs writes of pass 1 before the reads below)
     const float rs = rms_scale(ss, (float)p.H, p.eps);
-    for (int base = 0; base < KR; base += 2048) {
+    for (int base = 0; base < KR; base += 8 * NT) {
       float ww[8];
 #pragma unroll
-      for (int e = 0; e < 8; e++) ww[e] = p.norm_w[k0 + min(base + e * 256 + tid, KR - 1)];
+      for (int e = 0; e < 8; e++) ww[e] = p.norm_w[k0 + min(base + e * NT + tid, KR - 1)];
 #pragma unroll
       for (int e = 0; e < 8; e++) {
-        const int i = base + e * 256 + tid;
+        const int i = base + e * NT + tid;
         if (i < KR) xs[xs_pos<SWZ>(i)] = round_act(ww[e] * round_act(xs[xs_pos<SWZ>(i)] * rs, p.act), p.act);
       }
     }
@@ -527,9 +528,9 @@ __device__ void build_x_simple(const Pro& p, int k0, int KR, float* xs, float* r
       }
     }
   } else if (p.mode == PRO_SILU) {
-    if (p.src.fix) plain_fill<SWZ, true, true>(p, k0, KR, xs); else plain_fill<SWZ, false, true>(p, k0, KR, xs);
+    if (p.src.fix) plain_fill<SWZ, true, true, NT>(p, k0, KR, xs); else plain_fill<SWZ, false, true, NT>(p, k0, KR, xs);
   } else {
-    if (p.src.fix) plain_fill<SWZ, true, false>(p, k0, KR, xs); else plain_fill<SWZ, false, false>(p, k0, KR, xs);
+    if (p.src.fix) plain_fill<SWZ, true, false, NT>(p, k0, KR, xs); else plain_fill<SWZ, false, false, NT>(p, k0, KR, xs);
   }
   __syncthreads();
 }

@@ -333,7 +333,7 @@ struct bz_model {
   void* pf_x3 = nullptr; float* pf_rscale = nullptr;   // split activation rows [rows][3 xw] f16 + their row scales
   void* pf_xq = nullptr; size_t pf_xq_bytes = 0;       // int8 digit planes + row parameters of the exact integer-MFMA GEMM (bzk_pf_quant_i8)
   float* pf_ws = nullptr; size_t pf_ws_bytes = 0;   // W4A16 MFMA GEMM: split-K partials for short prompts / decode batches
-  // MXFP4 linears: has_mx4 -- the model holds one; mx4_a4 -- bz_model_set_mxfp4_activations (0: 16-bit activations, 1: FP4); the quantised rows of a
+  // MXFP4 linears: has_mx4 -- the model holds one; mx4_a4 -- bz_model_set_mxfp4_activations (0: 16-bit activations, 1: FP4 rows in the GEMMs, 3: and in the decode GEMV); the quantised rows of a
   // prefill GEMM's input (codes [rows][K / 2], scales [rows][bzk_mx4_quant_ld(K)]), sized with the prefill workspace
   bool has_mx4 = false; int mx4_a4 = 0; void* pf_xc4 = nullptr; void* pf_xs4 = nullptr;
   // INT8 W8A8 linears: has_i8 -- the model holds one; the int8 codes and row scales of a prompt chunk's rows (k_i8_quant_rows -> k_gemm_i8a8), sized in prefill_ws
@@ -2639,9 +2639,17 @@ extern "C" int bz_model_set_mxfp4_activations(bz_model* m, int mode) {
   BZ_API_BEGIN
   if (!m || !m->finalized) BZ_FAIL(BZ_E_INVALID, "set_mxfp4_activations: the model is not finalized");
   if (!m->has_mx4) BZ_FAIL(BZ_E_UNSUPPORTED, "set_mxfp4_activations: the model has no MXFP4 linear");
-  if (mode != 0 && mode != 1) BZ_FAIL(BZ_E_INVALID, "set_mxfp4_activations: mode %d (0: 16-bit activations, 1: FP4)", mode);
+  if (mode != 0 && mode != 1 && mode != 3)
+    BZ_FAIL(BZ_E_INVALID, "set_mxfp4_activations: mode %d (0: 16-bit activations, 1: FP4 rows in the GEMMs, 3: and the single row of a decode GEMV)", mode);
   std::lock_guard<std::recursive_mutex> lock__(m->mu);
   m->mx4_a4 = mode;
+  // bit 1 travels on the linears themselves: bzk_gemv_mx4 sees a LinearDev, not the model.  A captured step graph keeps the kernels it was captured with, so
+  // the mode is set before a capture, as bit 0 is.
+  const bool gemv = (mode & 2) != 0;
+  auto mark = [&](FusedLinear& F) { for (auto& p : F.parts) if (p.kind == LK_MX4) p.mx4_a4 = gemv; };
+  for (auto& l : m->layers) { mark(l.qkv); mark(l.o); mark(l.gateup); mark(l.down); }
+  mark(m->lm_head);
+  for (auto& kv : m->named) if (kv.second.kind == LK_MX4) kv.second.mx4_a4 = gemv;
   return BZ_OK;
   BZ_API_END
 }

@@ -71,6 +71,7 @@ struct LinearDev {
   int gw = 1;               // groups (of gs) per workgroup (split-K granularity)
   int sk = 1;               // ROWS / F8: split-K count (> 1 => fixed-point accumulator output)
   int npf = 2;              // groups of weight loads kept in flight per wave (2 or 4)
+  bool mx4_a4 = false;      // MX4: the decode GEMV quantises its row to MXFP4 (k_gemv_mx4a4); written by bz_model_set_mxfp4_activations only
   size_t bytes = 0;         // resident bytes
   size_t algo_bytes = 0;    // minimal on-disk bytes (SURVEY 8d accounting)
   bool owned = true;

@@ -18,6 +18,7 @@
 //                  one f32 multiply-add per block applies the scale to the block's 32 x 32 partial tile
 //   k_dequant_mx4  op-level read-back of the device layout
 //   k_mx4_quant_rows, k_gemm_mx4a4   W4A4 (opt-in): activation rows quantised to MXFP4, both operands on the block-scaled FP4 matrix instruction (end of file)
+//   k_gemv_mx4a4   W4A4 decode GEMV (opt-in, mode 3): the row quantised in the prologue, K split over eight waves on the 16x16x128 form of that instruction (end of file)
 #include "bz_internal.h"
 #include "bz_dev.h"
 #include <algorithm>
@@ -162,12 +163,15 @@ static int mx4_rows_per_wg(int N) {
   return r;
 }
 
+static int gemv_mx4a4(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act);
+
 int bzk_gemv_mx4(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act) {
   if (pro.mode != PRO_PLAIN && pro.mode != PRO_NORM && pro.mode != PRO_SILU) BZ_FAIL(BZ_E_UNSUPPORTED, "mxfp4 gemv: prologue mode %d is not built (plain, norm, silu are)", pro.mode);
   if (pro.perm || out.amax_val || out.shift.cs) BZ_FAIL(BZ_E_UNSUPPORTED, "mxfp4 gemv: act-order / argmax partials / conv shift are not built");
   if (L.K % 64 || L.N % 64 || !L.w) BZ_FAIL(BZ_E_INVALID, "mxfp4 gemv: N=%d K=%d must be multiples of 64", L.N, L.K);
   if (pro.mode == PRO_NORM && (pro.H != L.K || pro.H % 4)) BZ_FAIL(BZ_E_INVALID, "mxfp4 gemv: norm prologue over %d elements, K=%d", pro.H, L.K);
   if (!out.direct) BZ_FAIL(BZ_E_INVALID, "mxfp4 gemv needs a direct output");
+  if (L.mx4_a4) return gemv_mx4a4(s, L, pro, out, act);   // FP4 activations for single rows too (bit 1 of bz_model_set_mxfp4_activations): k_gemv_mx4a4, end of file
   const int KC = (L.K + 511) / 512;
   const char* lbl = pro.mode == PRO_NORM ? "gemv_mx4<norm>" : pro.mode == PRO_SILU ? "gemv_mx4<silu>" : "gemv_mx4";
   static bool attr_done = false;      // a long row's activations take more than the 64 KiB a launch gets without asking
@@ -445,6 +449,33 @@ int bzk_gemm_mx4w(hipStream_t s, const LinearDev& L, int dt, const void* x16, in
 // clamp(E - 2, 0, 252).  One lane owns one block: 64 bytes in, 16 code bytes (low nibble = the even element, the weights' file order) and one scale byte out.
 // `ldsc` is the byte stride of a row of scales: K / 32 for the plain [S][K / 32] result, mx4_quant_ld(K) for the rows k_gemm_mx4a4 reads.
 // ---------------------------------------------------------------------------------------------------------
+// One block: the f32 bit patterns of its 32 elements -> 16 code bytes as four words and the scale code (returned).  Shared by k_mx4_quant_rows and the
+// prologue of k_gemv_mx4a4, so a decode row and a prompt row holding the same values get the same codes.
+__device__ __forceinline__ int mx4_encode_block(const unsigned (&fb)[32], unsigned (&out)[4]) {
+  unsigned amax = 0u;
+#pragma unroll
+  for (int i = 0; i < 32; i++) amax = max(amax, fb[i] & 0x7fffffffu);   // (finite magnitudes order as their bit patterns)
+  const int sc = amax == 0u ? 127 : min(max((int)(amax >> 23) - 2, 0), 252);
+  // the midpoints of neighbouring E2M1 values times the scale (at most three significant bits: exact down to the f32 subnormals, which every kernel mode hipcc
+  // builds keeps); a tie goes to the neighbour whose code is even (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4; 6 and beyond saturate at
+  // code 7).  Finite magnitudes order as their bit patterns, so an element costs seven integer compares and no floating-point operation.
+  unsigned thr[7];
+  {
+    const float mid[7] = {0.25f, 0.75f, 1.25f, 1.75f, 2.5f, 3.5f, 5.0f};
+#pragma unroll
+    for (int j = 0; j < 7; j++) thr[j] = __float_as_uint(ldexpf(mid[j], sc - 127));
+  }
+  out[0] = out[1] = out[2] = out[3] = 0u;
+#pragma unroll
+  for (int i = 0; i < 32; i++) {
+    const unsigned a = fb[i] & 0x7fffffffu;
+    const unsigned c = (unsigned)(a > thr[0]) + (unsigned)(a >= thr[1]) + (unsigned)(a > thr[2]) + (unsigned)(a >= thr[3]) + (unsigned)(a > thr[4]) + (unsigned)(a >= thr[5]) +
+                       (unsigned)(a > thr[6]);
+    out[i >> 3] |= (c | ((fb[i] >> 28) & 8u)) << (4 * (i & 7));
+  }
+  return sc;
+}
+
 template <int DT>
 __global__ __launch_bounds__(256) void k_mx4_quant_rows(const unsigned short* __restrict__ X, int S, int K, unsigned char* __restrict__ codes, unsigned char* __restrict__ scales,
                                                         int ldsc) {
@@ -461,31 +492,13 @@ __global__ __launch_bounds__(256) void k_mx4_quant_rows(const unsigned short* __
       if constexpr (DT == BZ_BF16) return h16 << 16;
       else return __float_as_uint((float)__builtin_bit_cast(_Float16, (unsigned short)h16));
     };
-    unsigned fb[32], amax = 0u;
+    unsigned fb[32], out[4];
 #pragma unroll
     for (int i = 0; i < 16; i++) {
       fb[2 * i] = f32_bits(w[i] & 0xffffu);
       fb[2 * i + 1] = f32_bits(w[i] >> 16);
-      amax = max(amax, max(fb[2 * i] & 0x7fffffffu, fb[2 * i + 1] & 0x7fffffffu));   // (finite magnitudes order as their bit patterns)
     }
-    const int sc = amax == 0u ? 127 : min(max((int)(amax >> 23) - 2, 0), 252);
-    // the midpoints of neighbouring E2M1 values times the scale (at most three significant bits: exact down to the f32 subnormals, which every kernel mode hipcc
-    // builds keeps); a tie goes to the neighbour whose code is even (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4; 6 and beyond saturate at
-    // code 7).  Finite magnitudes order as their bit patterns, so an element costs seven integer compares and no floating-point operation.
-    unsigned thr[7];
-    {
-      const float mid[7] = {0.25f, 0.75f, 1.25f, 1.75f, 2.5f, 3.5f, 5.0f};
-#pragma unroll
-      for (int j = 0; j < 7; j++) thr[j] = __float_as_uint(ldexpf(mid[j], sc - 127));
-    }
-    unsigned out[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < 32; i++) {
-      const unsigned a = fb[i] & 0x7fffffffu;
-      const unsigned c = (unsigned)(a > thr[0]) + (unsigned)(a >= thr[1]) + (unsigned)(a > thr[2]) + (unsigned)(a >= thr[3]) + (unsigned)(a > thr[4]) + (unsigned)(a >= thr[5]) +
-                         (unsigned)(a > thr[6]);
-      out[i >> 3] |= (c | ((fb[i] >> 28) & 8u)) << (4 * (i & 7));
-    }
+    const int sc = mx4_encode_block(fb, out);
     *(uint4*)(codes + row * (size_t)(K >> 1) + (size_t)b * 16) = make_uint4(out[0], out[1], out[2], out[3]);
     scales[row * (size_t)ldsc + b] = (unsigned char)sc;
   }
@@ -675,5 +688,163 @@ int bzk_gemm_mx4a4(hipStream_t s, const LinearDev& L, const void* codes, const v
     hipLaunchKernelGGL(k_gemm_mx4w_reduce, dim3((unsigned)std::min<size_t>((SN + 255) / 256, 2048)), dim3(256), 0, s, (const float*)ws, KS, SN, N, L.bias, act, y);
     BZ_HIP(hipGetLastError());
   }
+  return BZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_gemv_mx4a4: the decode GEMV of the W4A4 mode (bit 1 of bz_model_set_mxfp4_activations), y[n] = R_act(f32(sum_k xq[k] W[n][k]) + b[n]) with xq the MX
+// quantisation of the row the prologue builds, on v_mfma_scale_f32_16x16x128_f8f6f4.  No weight is expanded and no scale touches the VALU.
+//
+// Prologue: 512 threads build the row in LDS as f32 exactly as k_gemv_mx4 does (build_x_simple, zero beyond K up to the tiles' 512), then one thread per block
+// quantises it with mx4_encode_block into 16 code bytes at xq + 16 b and a scale byte at xsc + b.  From there on the f32 row is dead.
+//
+// Lane map of a step (128 k, four blocks; step s of a row covers blocks 4 s .. 4 s + 3, i.e. a quarter of a 512-k tile): lane l = 16 q + r.
+//   A (weights):  row n0 + r, block 4 s + q -- the 16-byte piece at ((n / 4) KC + s / 4) MX4_TILE + (n % 4) 256 + ((4 s + q) % 16) 16, its scale byte at
+//                 ... + 1024 + (n % 4) 16 + (4 s + q) % 16, both straight from the device tiles.  The four pieces of a row are 64 consecutive bytes, so a
+//                 wave-wide 16-byte load touches 16 lines (one per row; the rows of a tile are 256 bytes apart, so no map over 16 rows touches fewer) and
+//                 the next step takes the other half of the same lines.  The 32x32x64 shape would touch 32 lines for 32 bytes each.
+//   B (the row):  column c = r, block 4 s + q.  Column c of the instruction's B holds block 4 s + c in lane group q == c and zero codes everywhere else, for
+//                 c = 0 .. 3; columns 4 .. 15 are all zero codes.  So D[row][c] is the dot product of ONE block -- what k_gemm_mx4a4 found it has to be: 32
+//                 E2M1 x E2M1 products under one common scale, exact in f32 from a zero C -- and one MFMA per step yields all four blocks' values without
+//                 the instruction ever adding two blocks of different scales.  A cleared piece also carries scale code 0, so whatever exponent the
+//                 instruction aligns its terms to, a cleared term's lies far below the live block's.
+//   D:            lane l holds column r of rows 4 q + i (register i = 0 .. 3): lanes r < 4 fold their four values into doubles after every step (the
+//                 others hold zeros and run the same adds).  The scale byte is byte 0 of its register (op_sel 0: the block a lane feeds varies with the
+//                 lane, an op_sel cannot).
+//
+// Work split: a workgroup of 8 waves owns rows_per_wg rows (16, 32 or 64: ~1000 workgroups at most, each runs the prologue) and walks them 16 at a time; the
+// ceil(K / 128) steps of a row group are cut into 8 contiguous slices, one per wave (a cut at a multiple of four blocks is one at a block pair).  A wave keeps
+// two groups of two steps in flight (4.25 KiB; 34 KiB per workgroup), the first two issued before the prologue.  The issue cursor stops at the wave's last
+// step: the tail reloads it and a wave with an empty slice (K < 1024) reloads its first, never a branch around a load; only the MFMA is skipped.  At the end of
+// a row group a wave adds its four columns (two lane exchanges in a fixed order) and leaves 16 doubles in LDS; after one barrier thread t sums the eight waves'
+// partials of row t in wave order, rounds to f32 once, adds the bias and stores.  No atomics, no workspace, the same bits whatever the scheduling.
+// ---------------------------------------------------------------------------------------------------------
+#define MX4A4_NT 512
+#define MX4A4_WAVES (MX4A4_NT / 64)
+#define MX4A4_MAXG 4                          // row groups of 16 per workgroup, at most
+typedef float mx4_f32x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(MX4A4_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_gemv_mx4a4(const unsigned char* __restrict__ W, const float* __restrict__ bias, int N, int K, int rows_per_wg, Pro pro,
+                                                         float* __restrict__ out, int act, long long* zero_buf, int zero_n) {
+  extern __shared__ __attribute__((aligned(16))) char mx4_smem3[];
+  const int KC = (K + 511) >> 9, KB = KC * 16;                                   // tiles and (padded) blocks of a row
+  float* xs = (float*)mx4_smem3;                                                 // [KC][MX4_XCHUNK] f32 row (xs_pos<2>)
+  float* red = xs + KC * MX4_XCHUNK;                                             // [16]
+  double* part = (double*)(red + 16);                                            // [MX4A4_MAXG][MX4A4_WAVES][16]
+  unsigned char* xq = (unsigned char*)(part + MX4A4_MAXG * MX4A4_WAVES * 16);    // [KB][16] codes
+  unsigned char* xsc = xq + KB * 16;                                             // [KB] scale codes
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 15, q = lane >> 4;
+  const int bid = blockIdx.x;
+  const int row0 = bid * rows_per_wg;
+  const int G = min(rows_per_wg, N - row0) >> 4;                                 // (N % 64 == 0: whole groups of 16)
+  const int nst = (K + 127) >> 7;
+  const int s_beg = wave * nst / MX4A4_WAVES, ns = (wave + 1) * nst / MX4A4_WAVES - s_beg;
+  const int total = G * ns;
+  // this lane's row of group 0: byte offsets of its tile row and of its scale row (the launcher holds the tiles below 2^32 bytes)
+  const unsigned n_l = (unsigned)(row0 + r);
+  const unsigned wrow = (n_l >> 2) * (unsigned)KC * MX4_TILE + (n_l & 3u) * 256u, srow = (n_l >> 2) * (unsigned)KC * MX4_TILE + 1024u + (n_l & 3u) * 16u;
+  const unsigned gstride = 4u * (unsigned)KC * MX4_TILE;                         // 16 rows further
+  int ig = 0, is = s_beg, ist = 0;
+  auto issue = [&](uint4 (&a)[2], unsigned (&sa)[2]) {
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      const unsigned blk = 4u * (unsigned)is + (unsigned)q, to = (unsigned)ig * gstride + (blk >> 4) * MX4_TILE;
+      a[j] = ldnt((const uint4*)(W + (wrow + to + (blk & 15u) * 16u)));
+      sa[j] = W[srow + to + (blk & 15u)];
+      if (ist + 1 < total) { ist++; if (++is == s_beg + ns) { is = s_beg; ig++; } }
+    }
+  };
+  uint4 a0[2], a1[2];
+  unsigned sa0[2], sa1[2];
+  issue(a0, sa0);
+  issue(a1, sa1);
+  __builtin_amdgcn_sched_barrier(0);
+  if (zero_buf)                                 // the ring protocol's side duty: zero the buffer the NEXT accumulate launch adds into
+    for (int i = bid * MX4A4_NT + tid; i < zero_n; i += gridDim.x * MX4A4_NT) zero_buf[i] = 0;
+  for (int i = K + tid; i < KC * 512; i += MX4A4_NT) xs[xs_pos<2>(i)] = 0.f;
+  build_x_simple<2, MX4A4_NT>(pro, 0, K, xs, red, bid == 0);
+  for (int b = tid; b < KB; b += MX4A4_NT) {
+    const float4* xp = (const float4*)(xs + (b >> 4) * MX4_XCHUNK + (b & 15) * 40);
+    unsigned fb[32], cw[4];
+#pragma unroll
+    for (int d = 0; d < 8; d++) {               // float4 d of the block: elements 4 d .. 4 d + 3 (four floats of padding after the first sixteen)
+      const float4 v = xp[d + (d >> 2)];
+      fb[4 * d] = __float_as_uint(v.x); fb[4 * d + 1] = __float_as_uint(v.y); fb[4 * d + 2] = __float_as_uint(v.z); fb[4 * d + 3] = __float_as_uint(v.w);
+    }
+    xsc[b] = (unsigned char)mx4_encode_block(fb, cw);
+    *(uint4*)(xq + b * 16) = make_uint4(cw[0], cw[1], cw[2], cw[3]);
+  }
+  __syncthreads();
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  auto store_part = [&](int g) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      double v = acc[i];
+      v += __shfl_xor(v, 1);
+      v += __shfl_xor(v, 2);
+      if (r == 0) part[(g * MX4A4_WAVES + wave) * 16 + 4 * q + i] = v;
+      acc[i] = 0.0;
+    }
+  };
+  const bool live = r == q;                     // lanes 0, 17, 34, 51: column c = q holds block 4 s + q
+  int cg = 0, cs = s_beg, cst = 0;
+  auto consume = [&](const uint4 (&a)[2], const unsigned (&sa)[2]) {
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      if (cst < total) {
+        cst++;
+        const int blk = 4 * cs + q;
+        const uint4 xb = *(const uint4*)(xq + blk * 16);
+        const unsigned xs_b = xsc[blk];
+        const mx4_i32x8 av = {(int)a[j].x, (int)a[j].y, (int)a[j].z, (int)a[j].w, 0, 0, 0, 0};
+        const mx4_i32x8 bv = {live ? (int)xb.x : 0, live ? (int)xb.y : 0, live ? (int)xb.z : 0, live ? (int)xb.w : 0, 0, 0, 0, 0};
+        const mx4_f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        const mx4_f32x4 d = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, z, 4, 4, 0, (int)sa[j], 0, live ? (int)xs_b : 0);   // cbsz = blgp = 4: E2M1
+#pragma unroll
+        for (int i = 0; i < 4; i++) acc[i] += (double)d[i];
+        if (++cs == s_beg + ns) { cs = s_beg; store_part(cg); cg++; }
+      }
+    }
+  };
+  if (ns == 0)                                  // an empty slice (K < 1024) still owes its zeros to the sum below
+    for (int g = 0; g < G; g++) store_part(g);
+  for (int st = 0; st < total; st += 4) {
+    consume(a0, sa0); issue(a0, sa0);
+    consume(a1, sa1); issue(a1, sa1);
+  }
+  __syncthreads();
+  if (tid < G * 16) {
+    const int g = tid >> 4, row = row0 + tid;
+    double v = 0.0;
+#pragma unroll
+    for (int w = 0; w < MX4A4_WAVES; w++) v += part[(g * MX4A4_WAVES + w) * 16 + (tid & 15)];
+    float f = (float)v;                         // one rounding to f32, then the bias in f32 (k_gemv_mx4's order)
+    if (bias) f += bias[row];
+    out[row] = round_act(f, act);
+  }
+}
+
+static int mx4a4_rows_per_wg(int N) {
+  int r = 16;
+  while (r < 16 * MX4A4_MAXG && (N + r - 1) / r > 1024) r <<= 1;
+  return r;
+}
+
+// the checks of bzk_gemv_mx4 have passed
+static int gemv_mx4a4(hipStream_t s, const LinearDev& L, const Pro& pro, const GemvOut& out, int act) {
+  const int KC = (L.K + 511) / 512;
+  const char* lbl = pro.mode == PRO_NORM ? "gemv_mx4a4<norm>" : pro.mode == PRO_SILU ? "gemv_mx4a4<silu>" : "gemv_mx4a4";
+  if (bzk_mx4_bytes(L.N, L.K) >= ((size_t)1 << 32)) BZ_FAIL(BZ_E_UNSUPPORTED, "mxfp4 gemv (FP4 activations): tiles of 2^32 bytes or more");
+  static bool attr_done = false;
+  if (!attr_done) {
+    BZ_HIP(hipFuncSetAttribute((const void*)k_gemv_mx4a4, hipFuncAttributeMaxDynamicSharedMemorySize, MX4_SMEM_MAX));
+    attr_done = true;
+  }
+  const int rpw = mx4a4_rows_per_wg(L.N);
+  const size_t smem = (size_t)KC * MX4_XCHUNK * 4 + 64 + (size_t)MX4A4_MAXG * MX4A4_WAVES * 16 * 8 + (size_t)KC * 16 * 17;
+  if (smem > MX4_SMEM_MAX) BZ_FAIL(BZ_E_UNSUPPORTED, "K=%d too large for the mxfp4 GEMV", L.K);
+  BZ_LAUNCH(lbl, L.algo_bytes, (k_gemv_mx4a4), dim3((L.N + rpw - 1) / rpw), dim3(MX4A4_NT), smem, s, (const unsigned char*)L.w, L.bias, L.N, L.K, rpw, pro, out.direct, act,
+            out.zero_buf, out.zero_n);
+  BZ_HIP(hipGetLastError());
   return BZ_OK;
 }

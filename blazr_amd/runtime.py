@@ -758,7 +758,8 @@ class LoadedModel:
         return y.to_numpy()
 
     def set_mxfp4_activations(self, mode):
-        """0: 16-bit activations (the default); 1: FP4 activations on the block-scaled FP4 MFMA wherever rows meet an MXFP4 linear in a GEMM"""
+        """0: 16-bit activations (the default); 1: FP4 activations on the block-scaled FP4 MFMA wherever rows meet an MXFP4 linear in a GEMM; 3: and for the single
+        row of a decode GEMV (single-token steps).  Set it before a step graph is captured."""
         L.check(L.lib().bz_model_set_mxfp4_activations(self.h, int(mode)))
 
     def mxfp4_quant_rows(self, x):

@@ -160,9 +160,12 @@ int bz_model_add_int8(bz_model* m, const char* name, int64_t N, int64_t K, const
  * decode graphs, the request engine, bz_prefill_matmul -- the rows are quantised to MXFP4 first (blocks of 32 along K, scale code clamp(floor(log2(max |x|)) - 2
  * + 127, 0, 252), 127 for an all-zero block; elements to the nearest E2M1 value, ties to the even significand, saturating at 6) and the product runs on the
  * block-scaled FP4 matrix instruction: y = R(f32(sum_k xq[k] W[n][k]) + bias[n]), accumulated in f32.  The single-stream decode GEMV, and prompts short enough to
- * stay on the decode kernels (BZ_EXACT_PREFILL_MAX rows), keep 16-bit activations in either mode.  The quantization_config's input_tensors entry of a checkpoint is
- * not read: only this call turns the mode on.  A graph captured earlier keeps the arithmetic it was captured with.  A model without an MXFP4 linear:
- * BZ_E_UNSUPPORTED; a mode other than 0 or 1: BZ_E_INVALID.  Beyond the reference.  New symbols only: BZ_ABI_VERSION is unchanged. */
+ * stay on the decode kernels (BZ_EXACT_PREFILL_MAX rows), keep 16-bit activations in modes 0 and 1.  mode 3: mode 1, and the single row of a decode GEMV
+ * (single-token steps, those short prompts, bz_quant_matmul on an MXFP4 name) is quantised the same way inside the GEMV launch, whose products run on the same
+ * instruction with the blocks' values summed in double and rounded to f32 once.  The mode reads as two bits -- bit 0 the GEMMs, bit 1 the GEMV -- and bit 1
+ * without bit 0 (mode 2) is refused.  The quantization_config's input_tensors entry of a checkpoint is not read: only this call turns a mode on.  Set the mode
+ * before a step graph is captured: a graph captured earlier keeps the kernels and the arithmetic it was captured with.  A model without an MXFP4 linear:
+ * BZ_E_UNSUPPORTED; a mode other than 0, 1 or 3: BZ_E_INVALID.  Beyond the reference.  New symbols only: BZ_ABI_VERSION is unchanged. */
 int bz_model_set_mxfp4_activations(bz_model* m, int mode);
 /* op level: that quantiser on x F32 [S,K] (K % 64 == 0), rounded to the model's activation dtype (f16 / bf16) first as bz_prefill_matmul does: codes U8 [S,K/2]
  * (the low nibble of byte j is element 2 j) and scales U8 [S,K/32], row-major.  Finite inputs only. */

@@ -8,7 +8,7 @@
 //          [--grammar FILE --vocab-bytes FILE [--grammar-regular]]
 //          [--draft <checkpoint> [--spec-tokens k] [--spec-adaptive]]
 //          [--lora <PEFT dir | adapter_model.safetensors>]... [--lora-targets q,v,...]
-//          [--mxfp4-a4]
+//          [--mxfp4-a4] [--mxfp4-a4-decode]
 //   bz-run <model> --prompt 1,2,3 --score [--top-logprobs K]
 //   bz-run <model> --prompt 1,2,3 --embed mean|cls|last|none [--normalize]
 //   bz-run <model> --prompts-file FILE --score [--top-logprobs K]  |  --embed mean|cls|last|none [--normalize]
@@ -31,7 +31,8 @@
 // and L2-normalised with --normalize: the vector on one line, comma separated (`none`: one line per position).
 // --prompts-file FILE (one comma-separated id list per line) with --score or --embed: all the inputs in ONE packed call (bz_score_batch / bz_embed_batch; the
 // per-text loops of server/embeddings.rs:180 and server/rerank.rs:144); per input what the single-prompt form prints, preceded by `# input i`.
-// --mxfp4-a4: an MXFP4 checkpoint runs its prompt and batch GEMMs with FP4 activations (bz_model_set_mxfp4_activations; single-token steps keep 16-bit ones).
+// --mxfp4-a4: an MXFP4 checkpoint runs its prompt and batch GEMMs with FP4 activations (bz_model_set_mxfp4_activations mode 1; single-token steps keep 16-bit ones).
+// --mxfp4-a4-decode: mode 3 -- the same, and single-token steps quantise their rows too (the FP4 decode GEMV).
 // prints the generated ids, comma separated, on stdout.
 #include <cmath>
 #include <algorithm>
@@ -107,7 +108,7 @@ int main(int argc, char** argv) {
   std::string requests_path; int rows = 0, pool_blocks = 0, prefill_chunk = 0, depth = 2; bool prefix_cache = false;
   std::vector<std::string> lora_paths; std::string lora_targets; std::vector<bz_lora*> loras;
   bool score = false; int top_logprobs = 0; std::string embed; bool normalize = false; std::string prompts_path;
-  bool mxfp4_a4 = false;
+  int mxfp4_a4 = 0;   // the mode of bz_model_set_mxfp4_activations
   int logprobs = -1; std::vector<uint32_t> bias_ids; std::vector<float> bias_vals;   // --requests: every request asks for K alternatives / carries this bias
   memset(&sc, 0, sizeof sc);
   for (int i = 2; i < argc; i++) {
@@ -156,7 +157,8 @@ int main(int argc, char** argv) {
         q = *end == ',' ? end + 1 : end;
       }
     }
-    else if (a == "--mxfp4-a4") mxfp4_a4 = true;
+    else if (a == "--mxfp4-a4") mxfp4_a4 = std::max(mxfp4_a4, 1);
+    else if (a == "--mxfp4-a4-decode") mxfp4_a4 = 3;
     else if (a == "--lora") lora_paths.push_back(next("--lora"));
     else if (a == "--lora-targets") lora_targets = next("--lora-targets");
     else { fprintf(stderr, "bz-run: unknown option %s\n", a.c_str()); return 2; }
@@ -191,7 +193,7 @@ int main(int argc, char** argv) {
     if (bz_device_open(device_id, &dev) != BZ_OK) return fail("device");
     bz_model* m = nullptr; bz_model_config cfg;
     if (bz_load_model(dev, model.c_str(), &m, &cfg) != BZ_OK) return fail("load");
-    if (mxfp4_a4 && bz_model_set_mxfp4_activations(m, 1) != BZ_OK) return fail("mxfp4-a4");       // before the engine captures its step
+    if (mxfp4_a4 && bz_model_set_mxfp4_activations(m, mxfp4_a4) != BZ_OK) return fail("mxfp4-a4");       // before the engine captures its step
     bz_engine_config ec;
     memset(&ec, 0, sizeof ec);
     ec.n_rows = rows; ec.block_size = gc.block_size; ec.max_seq_len = std::min(longest, cfg.max_seq_len); ec.prefill_chunk = prefill_chunk; ec.depth = depth;
@@ -291,7 +293,7 @@ int main(int argc, char** argv) {
   if (bz_device_open(device_id, &dev) != BZ_OK) return fail("device");                    // CudaDevice::new + CudaClient::new (run.rs:70-81)
   bz_model* m = nullptr; bz_model_config cfg;
   if (bz_load_model(dev, model.c_str(), &m, &cfg) != BZ_OK) return fail("load");          // detect_model_source + load_model (run.rs:88-118)
-  if (mxfp4_a4 && bz_model_set_mxfp4_activations(m, 1) != BZ_OK) return fail("mxfp4-a4");
+  if (mxfp4_a4 && bz_model_set_mxfp4_activations(m, mxfp4_a4) != BZ_OK) return fail("mxfp4-a4");
   if (int rc = setup_lora(dev, m, lora_paths, lora_targets, loras)) return rc;
   if (!loras.empty() && bz_model_set_lora(m, 0) != BZ_OK) return fail("set lora");          // single-sequence modes: the first adapter
   if (score || !embed.empty()) {
