@@ -239,12 +239,13 @@ extern "C" int bz_tensor_to_host_pipelined(const bz_tensor* t, uint64_t ev, void
 // ---------------------------------------------------------------------------------------------------------
 struct RawTensor {
   int kind = 0;  // 0 dense, 1 awq, 2 gptq, 3 gguf, 4 fp8 (d0 = e4m3 bytes [N][K], d1 = f32 scales [N]), 5 mxfp4 (d0 = e2m1 codes [N][K/2], d1 = e8m0 codes [N][K/32]),
-                 // 6 int8 w8a8 (d0 = int8 [N][K], d1 = f32 scales [N])
+                 // 6 int8 w8a8 (d0 = int8 [N][K], d1 = f32 scales [N]), 7 nvfp4 (d0 = e2m1 codes [N][K/2], d1 = e4m3 bytes [N][K/16], nv4_r = 1 / weight_global_scale)
   int dtype = BZ_F32;
   std::vector<int64_t> shape;
   int64_t N = 0, K = 0; int gs = 0; int ggml_type = 0;
   void* d0 = nullptr; void* d1 = nullptr; void* d2 = nullptr;  // dense data | qweight,scales,zeros/qzeros | blocks
   float* d_bias = nullptr;
+  float nv4_r = 1.f;
   std::vector<int32_t> g_idx;
   size_t bytes = 0;
   bool consumed = false;
@@ -618,6 +619,33 @@ extern "C" int bz_model_add_int8(bz_model* m, const char* name, int64_t N, int64
   BZ_API_END
 }
 
+// NVFP4 weights: E2M1 codes two per byte (low nibble first), one E4M3 scale byte per group of 16 along K and the tensor's weight_global_scale, a DIVISOR:
+// W[n][k] = e2m1(q[n][k]) e4m3(scale[n][k / 16]) r, r = f32(1 / global_scale) formed here in double.  A scale byte no kernel decodes is refused here: the
+// E4M3 NaN codes and every byte with the sign bit set (a group scale is a magnitude).
+extern "C" int bz_model_add_nvfp4(bz_model* m, const char* name, int64_t N, int64_t K, const uint8_t* packed, const uint8_t* scale, float global_scale, const float* bias) {
+  BZ_API_BEGIN
+  BZ_TRY(check_add(m, name));
+  if (!packed || !scale) BZ_FAIL(BZ_E_INVALID, "add_nvfp4 '%s': null data", name);
+  if (N <= 0 || K <= 0 || N % 64 || K % 64) BZ_FAIL(BZ_E_UNSUPPORTED, "add_nvfp4 '%s': N=%lld and K=%lld must be positive multiples of 64", name, (long long)N, (long long)K);
+  if ((uint64_t)N * (uint64_t)K >= (1ull << 32)) BZ_FAIL(BZ_E_UNSUPPORTED, "add_nvfp4 '%s': 2^32 weights or more", name);
+  if (!std::isfinite(global_scale) || !(global_scale > 0.f)) BZ_FAIL(BZ_E_INVALID, "add_nvfp4 '%s': weight_global_scale is not a finite positive number", name);
+  const float r = (float)(1.0 / (double)global_scale);
+  if (!std::isfinite(r) || !(r > 0.f)) BZ_FAIL(BZ_E_INVALID, "add_nvfp4 '%s': 1 / weight_global_scale is not a finite positive f32", name);
+  const size_t nw = (size_t)N * (size_t)(K / 2), ns = (size_t)N * (size_t)(K / 16);
+  for (size_t i = 0; i < ns; i++) {
+    if ((scale[i] & 0x7Fu) == 0x7Fu) BZ_FAIL(BZ_E_INVALID, "add_nvfp4 '%s': weight_scale[%zu] = 0x%02X is an E4M3 NaN code", name, i, (unsigned)scale[i]);
+    if (scale[i] & 0x80u) BZ_FAIL(BZ_E_INVALID, "add_nvfp4 '%s': weight_scale[%zu] = 0x%02X has its sign bit set (a group scale is a magnitude)", name, i, (unsigned)scale[i]);
+  }
+  if (bias) for (int64_t i = 0; i < N; i++) if (!std::isfinite(bias[i])) BZ_FAIL(BZ_E_INVALID, "add_nvfp4 '%s': bias[%lld] is not finite", name, (long long)i);
+  RawTensor t; t.kind = 7; t.N = N; t.K = K; t.shape = {N, K}; t.bytes = nw + ns + 4; t.nv4_r = r;
+  BZ_TRY(upload(m->dev, &t.d0, packed, nw));
+  BZ_TRY(upload(m->dev, &t.d1, scale, ns));
+  if (bias) { void* b; BZ_TRY(upload(m->dev, &b, bias, (size_t)N * 4)); t.d_bias = (float*)b; }
+  m->raw[name] = t;
+  return BZ_OK;
+  BZ_API_END
+}
+
 // --- finalize helpers ---------------------------------------------------------------------------------------
 static int choose_gw(int N, int K, int target) {
   const int G = K / 128, nst = (N + 255) / 256;
@@ -796,6 +824,38 @@ static int build_mx4(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* 
   return BZ_OK;
 }
 
+// NVFP4 tensors concatenated along N and repacked into the kernels' tiles (four rows x 512 k with their group scales, bz_nvfp4.hip), as build_mx4; each part's
+// r = 1 / weight_global_scale goes into a per-row f32 array, so fused q/k/v or gate/up parts keep their own
+static int build_nv4(bz_model* m, const std::vector<RawTensor*>& rs, LinearDev* L) {
+  const int K = (int)rs[0]->K;
+  int N = 0;
+  bool any_bias = false;
+  for (auto* r : rs) { N += (int)r->N; any_bias |= r->d_bias != nullptr; if (r->K != K) BZ_FAIL(BZ_E_UNSUPPORTED, "fused nvfp4 parts differ in K"); }
+  if ((uint64_t)N * (uint64_t)K >= (1ull << 32)) BZ_FAIL(BZ_E_UNSUPPORTED, "fused nvfp4 linear of 2^32 weights or more");
+  void *w, *f, *b = nullptr;
+  hipStream_t st = m->dev->stream;
+  BZ_TRY(dev_alloc(m, &w, bzk_nv4_bytes(N, K)));
+  BZ_TRY(dev_alloc(m, &f, (size_t)N * 4));
+  std::vector<float> rows((size_t)N);
+  size_t o = 0;
+  for (auto* r : rs) {
+    BZ_TRY(bzk_repack_nv4(st, r->d0, r->d1, (int)r->N, K, (char*)w + bzk_nv4_bytes((int)o, K)));
+    std::fill(rows.begin() + (ptrdiff_t)o, rows.begin() + (ptrdiff_t)(o + (size_t)r->N), r->nv4_r);
+    o += (size_t)r->N;
+  }
+  BZ_HIP(hipMemcpyAsync(f, rows.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
+  if (any_bias) {
+    BZ_TRY(dev_alloc(m, &b, (size_t)N * 4));
+    BZ_HIP(hipMemsetAsync(b, 0, (size_t)N * 4, st));
+    o = 0;
+    for (auto* r : rs) { if (r->d_bias) BZ_HIP(hipMemcpyAsync((float*)b + o, r->d_bias, (size_t)r->N * 4, hipMemcpyDeviceToDevice, st)); o += (size_t)r->N; }
+  }
+  BZ_HIP(hipStreamSynchronize(st));      // (`rows` lives until here)
+  L->kind = LK_NV4; L->N = N; L->K = K; L->gs = 16; L->wdt = BZ_U8; L->w = w; L->scales = f; L->bias = (float*)b; L->sk = 1;
+  L->bytes = bzk_nv4_bytes(N, K) + (size_t)N * 4; L->algo_bytes = (size_t)N * (size_t)(K / 2 + K / 16);      // 4.5 bits per weight on disk; the tiles pad K to 512
+  return BZ_OK;
+}
+
 // dense linear whose consumer reads plain f32 (lm_head logits, Mamba2 in_proj): no split-K
 static void force_direct(FusedLinear* F) {
   bool rows = true;
@@ -893,6 +953,7 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
     else if (g[0]->kind == 4) BZ_TRY(build_f8(m, g, &L));
     else if (g[0]->kind == 5) BZ_TRY(build_mx4(m, g, &L));
     else if (g[0]->kind == 6) BZ_TRY(build_i8(m, g, &L));
+    else if (g[0]->kind == 7) BZ_TRY(build_nv4(m, g, &L));
     else BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: tensor kind %d", g[0]->kind);
     F->parts.push_back(L); F->n_off.push_back(noff);
     // per-name views for the op-level API
@@ -915,6 +976,10 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
         V.w = (char*)L.w + bzk_mx4_bytes(sub, L.K);
         V.bias = L.bias ? L.bias + sub : nullptr;
         V.bytes = bzk_mx4_bytes(V.N, V.K); V.algo_bytes = (size_t)V.N * (size_t)(V.K / 2 + V.K / 32);
+      } else if (L.kind == LK_NV4) {
+        V.w = (char*)L.w + bzk_nv4_bytes(sub, L.K); V.scales = (float*)L.scales + sub;
+        V.bias = L.bias ? L.bias + sub : nullptr;
+        V.bytes = bzk_nv4_bytes(V.N, V.K) + (size_t)V.N * 4; V.algo_bytes = (size_t)V.N * (size_t)(V.K / 2 + V.K / 16);
       } else {
         const size_t t0 = (size_t)sub / 64, K = (size_t)L.K;
         if (L.kind == LK_Q80) { V.w = (char*)L.w + t0 * 64 * K; V.scales = (char*)L.scales + t0 * (K / 32) * 64 * 2; }
@@ -938,7 +1003,7 @@ static int build_fused(bz_model* m, const std::vector<std::string>& names, Fused
   for (auto& p : F->parts) if (p.kind == LK_ROWS && !no_sk) p.sk = bzk_rows_choose_sk(p.N, p.K);
   for (auto& p : F->parts) if (p.kind == LK_F8) p.sk = f8_choose_sk(p.N, p.K);
   for (auto& p : F->parts) if (p.kind == LK_I8) p.sk = i8_choose_sk(p.N, p.K);
-  auto is_fix = [](const LinearDev& p) { return (p.kind != LK_ROWS && p.kind != LK_F8 && p.kind != LK_MX4 && p.kind != LK_I8) || p.sk > 1; };   // (an mxfp4 linear never splits K)
+  auto is_fix = [](const LinearDev& p) { return (p.kind != LK_ROWS && p.kind != LK_F8 && p.kind != LK_MX4 && p.kind != LK_I8 && p.kind != LK_NV4) || p.sk > 1; };   // (an mxfp4 or nvfp4 linear never splits K across workgroups)
   F->fix_out = is_fix(F->parts[0]);
   for (auto& p : F->parts) if (is_fix(p) != F->fix_out) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: mixed fixed-point/direct parts in one fused linear");
   for (auto* r : rs) { raw_free(*r); r->consumed = true; }
@@ -1044,7 +1109,7 @@ static void fill_prompt_traits(bz_model* m) {
         // 16-bit activations: dense in the activation dtype or fp8 (fp8 weights expand to it exactly: the MFMA GEMM), or int4 without act-order (the
         // multi-row dot4 GEMM; exact_cap: what the exact rows can use of it)
         const bool one = F->parts.size() == 1;
-        const bool dense_ok = one && ((F->parts[0].kind == LK_ROWS && F->parts[0].wdt == act) || bzk_gemm_f8w_ok(F->parts[0], act) || bzk_gemm_mx4w_ok(F->parts[0], act) ||
+        const bool dense_ok = one && ((F->parts[0].kind == LK_ROWS && F->parts[0].wdt == act) || bzk_gemm_f8w_ok(F->parts[0], act) || bzk_gemm_mx4w_ok(F->parts[0], act) || bzk_gemm_nv4w_ok(F->parts[0], act) ||
                                      bzk_gemm_i8a8_ok(F->parts[0], act));
         const bool q4_ok = one && bzk_gemm_q4g_rows_ok(F->parts[0]);
         if (!dense_ok && !q4_ok) t.proj_16 = 0;
@@ -1168,6 +1233,10 @@ extern "C" int bz_model_finalize(bz_model* m) {
     for (auto& kv : m->raw) if (kv.second.kind == 6) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: int8 tensor '%s': int8 weights need f16 or bf16 activations", kv.first.c_str());
   if (m->cfg.arch != BZ_ARCH_LLAMA)
     for (auto& kv : m->raw) if (kv.second.kind == 6) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: int8 tensor '%s': int8 weights are built for the Llama family only", kv.first.c_str());
+  if (m->cfg.act_dtype == BZ_F32)   // (x e2m1(q) is exact in f32 for 16-bit activations only, and the GEMM builds 16-bit fragments)
+    for (auto& kv : m->raw) if (kv.second.kind == 7) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: nvfp4 tensor '%s': nvfp4 weights need f16 or bf16 activations", kv.first.c_str());
+  if (m->cfg.arch != BZ_ARCH_LLAMA)
+    for (auto& kv : m->raw) if (kv.second.kind == 7) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: nvfp4 tensor '%s': nvfp4 weights are built for the Llama family only", kv.first.c_str());
   if (m->cfg.arch == BZ_ARCH_MAMBA2) return finalize_mamba2(m);
   if (m->cfg.arch == BZ_ARCH_DEEPSEEK2) return finalize_dsv2(m);
   const bz_model_config& c = m->cfg;
@@ -1238,6 +1307,8 @@ extern "C" int bz_model_finalize(bz_model* m) {
       { auto it = m->raw.find("lm_head.weight"); if (it != m->raw.end() && it->second.kind == 5) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: mxfp4 tensor 'lm_head.weight': an mxfp4 lm_head is not built (keep it 16-bit)"); }
       // (likewise k_gemv_i8; the files keep lm_head on their `ignore` list)
       { auto it = m->raw.find("lm_head.weight"); if (it != m->raw.end() && it->second.kind == 6) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: int8 tensor 'lm_head.weight': an int8 lm_head is not built (keep it 16-bit)"); }
+      // (likewise k_gemv_nv4; the files keep lm_head on their `ignore` list)
+      { auto it = m->raw.find("lm_head.weight"); if (it != m->raw.end() && it->second.kind == 7) BZ_FAIL(BZ_E_UNSUPPORTED, "finalize: nvfp4 tensor 'lm_head.weight': an nvfp4 lm_head is not built (keep it 16-bit)"); }
       BZ_TRY(build_fused(m, {"lm_head"}, &m->lm_head));
       force_direct(&m->lm_head);
       // an fp8 lm_head takes the path of an int4 one: fixed-point output, converted after the launch (the split form, at least two slices)
@@ -2287,6 +2358,7 @@ static int pf_gemm(bz_model* m, const LinearDev& P, const void* x16, int n, floa
     return bzk_gemm_mx4a4(st, P, m->pf_xc4, m->pf_xs4, ld, n, act, y, m->pf_ws, m->pf_ws_bytes);
   }
   if (P.kind == LK_MX4) return bzk_gemm_mx4w(st, P, act, x16, n, act, y, m->pf_ws, m->pf_ws_bytes);
+  if (P.kind == LK_NV4) return bzk_gemm_nv4w(st, P, act, x16, n, act, y, m->pf_ws, m->pf_ws_bytes);
   if (P.kind == LK_I8) {   // W8A8: the rows quantised once (a fused q/k/v or gate/up is one linear, so one input is quantised once), then both operands on the int8 MFMA
     BZ_TRY(bzk_i8_quant_rows(st, act, x16, n, P.K, m->pf_xc8, m->pf_xs8));
     return bzk_gemm_i8a8(st, P, m->pf_xc8, m->pf_xs8, n, act, y);
@@ -2601,9 +2673,10 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
   const bool f8 = L.kind == LK_F8;    // fp8 weights x the model's 16-bit activations (the W8A16 GEMM)
   const bool mx4 = L.kind == LK_MX4;  // mxfp4 weights likewise (the W4A16 GEMM)
   const bool i8 = L.kind == LK_I8;    // int8 weights x the rows quantised to int8 (the W8A8 GEMM)
+  const bool nv4 = L.kind == LK_NV4;  // nvfp4 weights x the model's 16-bit activations (the W4A16 GEMM on scaled fragments)
   const int f8dt = m->cfg.act_dtype == BZ_F16 ? BZ_F16 : BZ_BF16;
-  if (i8 ? !bzk_gemm_i8a8_ok(L, f8dt) : mx4 ? !bzk_gemm_mx4w_ok(L, f8dt) : f8 ? !bzk_gemm_f8w_ok(L, f8dt) : q4 ? !bzk_gemm_q4g_mfma_ok(L, BZ_F16, S) : (L.kind != LK_ROWS || (L.wdt != BZ_F16 && L.wdt != BZ_BF16)))
-    BZ_FAIL(BZ_E_UNSUPPORTED, "prefill_matmul: '%s' is neither a dense f16 / bf16 weight, an fp8, mxfp4 or int8 weight nor an int4 weight without act-order (S >= 9)", name);
+  if (nv4 ? !bzk_gemm_nv4w_ok(L, f8dt) : i8 ? !bzk_gemm_i8a8_ok(L, f8dt) : mx4 ? !bzk_gemm_mx4w_ok(L, f8dt) : f8 ? !bzk_gemm_f8w_ok(L, f8dt) : q4 ? !bzk_gemm_q4g_mfma_ok(L, BZ_F16, S) : (L.kind != LK_ROWS || (L.wdt != BZ_F16 && L.wdt != BZ_BF16)))
+    BZ_FAIL(BZ_E_UNSUPPORTED, "prefill_matmul: '%s' is neither a dense f16 / bf16 weight, an fp8, mxfp4, nvfp4 or int8 weight nor an int4 weight without act-order (S >= 9)", name);
   if (!x || !y || x->dtype != BZ_F32 || y->dtype != BZ_F32 || S <= 0 || x->nbytes < (size_t)S * L.K * 4 || y->nbytes < (size_t)S * L.N * 4)
     BZ_FAIL(BZ_E_INVALID, "prefill_matmul: x must be F32 [S,%d], y F32 [S,%d]", L.K, L.N);
   BZ_HIP(hipSetDevice(m->dev->id));
@@ -2612,7 +2685,7 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
   const size_t ws_bytes = (size_t)48 << 20;      // split-K partials, as the prefill paths pass them
   BZ_HIP(hipMalloc(&x16, (size_t)S * L.K * 2));
   if (hipMalloc(&ws, ws_bytes) != hipSuccess) { hipFree(x16); BZ_FAIL(BZ_E_OOM, "prefill_matmul: workspace"); }
-  const int xdt = (f8 || mx4 || i8) ? f8dt : q4 ? BZ_F16 : L.wdt;
+  const int xdt = (f8 || mx4 || i8 || nv4) ? f8dt : q4 ? BZ_F16 : L.wdt;
   int rc = bzk_pf_cvt16(st, xdt, (const float*)x->ptr, (size_t)S * L.K, x16);
   if (rc == BZ_OK && mx4 && m->mx4_a4) {      // the model's mode: FP4 activations (the codes and scales take the head of the workspace, the partials the rest)
     const int ld = bzk_mx4_quant_ld(L.K);
@@ -2626,7 +2699,7 @@ extern "C" int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor*
     if (rc == BZ_OK) rc = bzk_i8_quant_rows(st, xdt, x16, S, L.K, ws, (float*)((char*)ws + cb));
     if (rc == BZ_OK) rc = bzk_gemm_i8a8(st, L, ws, (const float*)((char*)ws + cb), S, BZ_F32, (float*)y->ptr);
   } else
-  if (rc == BZ_OK) rc = mx4 ? bzk_gemm_mx4w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : f8 ? bzk_gemm_f8w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : q4 ? bzk_gemm_q4g_mfma(st, L, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes)
+  if (rc == BZ_OK) rc = nv4 ? bzk_gemm_nv4w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : mx4 ? bzk_gemm_mx4w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : f8 ? bzk_gemm_f8w(st, L, xdt, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes) : q4 ? bzk_gemm_q4g_mfma(st, L, x16, S, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes)
                            : bzk_gemm_nt(st, L.wdt, x16, L.w, L.bias, S, L.N, L.K, BZ_F32, (float*)y->ptr, (float*)ws, ws_bytes);
   hipStreamSynchronize(st);
   hipFree(x16); hipFree(ws);
@@ -4474,7 +4547,7 @@ extern "C" int bz_quant_matmul(bz_model* m, const char* name, const bz_tensor* x
   hipStream_t st = m->dev->stream;
   // op-level results are NOT rounded to the activation dtype: the caller sees the f32 accumulator
   long long* acc = nullptr;
-  const bool direct = L.kind == LK_ROWS || L.kind == LK_MX4 || ((L.kind == LK_F8 || L.kind == LK_I8) && L.sk <= 1);   // (an fp8 linear's split form goes through the accumulator like the int4 kinds)
+  const bool direct = L.kind == LK_ROWS || L.kind == LK_MX4 || L.kind == LK_NV4 || ((L.kind == LK_F8 || L.kind == LK_I8) && L.sk <= 1);   // (an fp8 linear's split form goes through the accumulator like the int4 kinds)
   const bool i8_split = L.kind == LK_I8 && L.sk > 1;   // integer partials in the accumulator; the finishing workgroup stores the f32 result itself and hands the accumulator back zeroed
   if (!direct) BZ_HIP(hipMalloc(&acc, (size_t)L.N * 8));
   int rc = BZ_OK;
@@ -4530,7 +4603,7 @@ extern "C" int bz_dequant(bz_model* m, const char* name, float* host) {
   float* d;
   BZ_HIP(hipMalloc(&d, n * 4));
   int rc = L.kind == LK_Q4G ? bzk_dequant_q4g(m->dev->stream, L, d) : L.kind == LK_ROWS ? bzk_dequant_rows(m->dev->stream, L, d)
-         : L.kind == LK_F8 ? bzk_dequant_f8(m->dev->stream, L, d) : L.kind == LK_I8 ? bzk_dequant_i8(m->dev->stream, L, d) : L.kind == LK_MX4 ? bzk_dequant_mx4(m->dev->stream, L, d) : bzk_dequant_gq(m->dev->stream, L, d);
+         : L.kind == LK_F8 ? bzk_dequant_f8(m->dev->stream, L, d) : L.kind == LK_I8 ? bzk_dequant_i8(m->dev->stream, L, d) : L.kind == LK_MX4 ? bzk_dequant_mx4(m->dev->stream, L, d) : L.kind == LK_NV4 ? bzk_dequant_nv4(m->dev->stream, L, d) : bzk_dequant_gq(m->dev->stream, L, d);
   std::vector<float> tmp;
   if (rc == BZ_OK) rc = hipStreamSynchronize(m->dev->stream) == hipSuccess ? BZ_OK : BZ_E_HIP;  // the stream is non-blocking
   if (rc == BZ_OK) {

@@ -307,14 +307,25 @@ int hf_config_to_pod(const JVal& j, bz_model_config* c, QuantInfo* q) {
     } else if (m == "compressed-tensors") {
       const std::string fmt = qc->str("format");
       const bool i8 = fmt == "int-quantized";      // INT8 W8A8: int8 weights per channel / tensor, int8 activations per token, dynamic and symmetric
-      if (fmt != "float-quantized" && !i8)
-        BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: compressed-tensors format '%s' is not implemented (float-quantized and int-quantized are)", fmt.c_str());
+      const bool nv4 = fmt == "nvfp4-pack-quantized";   // NVFP4: E2M1 weights in groups of 16 with an E4M3 scale and a global scale per tensor; run weight-only
+      if (fmt != "float-quantized" && !i8 && !nv4)
+        BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: compressed-tensors format '%s' is not implemented (float-quantized, int-quantized and nvfp4-pack-quantized are)", fmt.c_str());
       const JVal* groups = qc->get("config_groups");
       if (!groups || groups->t != JVal::OBJ || groups->o.empty()) BZ_FAIL(BZ_E_INVALID, "config.json: compressed-tensors quantization_config without config_groups");
       for (auto& g : groups->o) {
         const JVal* w = g.second.get("weights");
         if (!w || w->t != JVal::OBJ) BZ_FAIL(BZ_E_INVALID, "config.json: config_groups.%s has no weights entry", g.first.c_str());
         const std::string ty = w->str("type"), strategy = w->str("strategy", "tensor");
+        if (nv4) {
+          // every group: 4-bit float, tensor_group strategy, groups of 16, symmetric; input_activations (FP4 activations of the W4A4 files) is read past.
+          // ASSUMPTION: these field names could not be checked against a published file; tests/nvfp4_cases.py writes what this branch reads.
+          if (w->i64("num_bits", 0) != 4) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights.num_bits %lld is not implemented (4 is, for nvfp4-pack-quantized)", g.first.c_str(), w->i64("num_bits", 0));
+          if (ty != "float") BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights.type '%s' is not implemented (float is, for nvfp4-pack-quantized)", g.first.c_str(), ty.c_str());
+          if (strategy != "tensor_group") BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights.strategy '%s' is not implemented (tensor_group is, for nvfp4-pack-quantized)", g.first.c_str(), strategy.c_str());
+          if (w->i64("group_size", 0) != 16) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights.group_size %lld is not implemented (16, the NVFP4 group, is)", g.first.c_str(), w->i64("group_size", 0));
+          if (!w->boolean("symmetric", true)) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights.symmetric false is not implemented", g.first.c_str());
+          continue;
+        }
         if (w->i64("num_bits", 0) != 8 || ty != (i8 ? "int" : "float"))
           BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.weights: num_bits %lld type '%s' is not implemented (8-bit %s is)", g.first.c_str(), w->i64("num_bits", 0), ty.c_str(),
                   i8 ? "int" : "float");
@@ -332,7 +343,7 @@ int hf_config_to_pod(const JVal& j, bz_model_config* c, QuantInfo* q) {
         if (!a->boolean("symmetric", true)) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.input_activations.symmetric false is not implemented", g.first.c_str());
         if (astr != "token") BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: config_groups.%s.input_activations.strategy '%s' is not implemented (token is)", g.first.c_str(), astr.c_str());
       }
-      q->method = i8 ? 5 : 3;
+      q->method = nv4 ? 6 : i8 ? 5 : 3;
     } else if (m == "quark") {
       // Quark MXFP4 exports (the *-MXFP4 releases): E2M1 weights in groups of 32 with an E8M0 scale, one scheme for every linear off the `exclude` list; run
       // weight-only, so global_quant_config.input_tensors is read past.  ASSUMPTION: these field names could not be checked against a published file;
@@ -351,7 +362,7 @@ int hf_config_to_pod(const JVal& j, bz_model_config* c, QuantInfo* q) {
       }
       q->method = 4;
     }
-    q->group_size = q->method == 4 ? 32 : (int)qc->i64("group_size", 128);
+    q->group_size = q->method == 4 ? 32 : q->method == 6 ? 16 : (int)qc->i64("group_size", 128);
     if ((q->method == 1 || q->method == 2) && qc->i64("bits", 4) != 4) BZ_FAIL(BZ_E_UNSUPPORTED, "config.json: %lld-bit %s is not implemented (4-bit only)", qc->i64("bits", 4), m.c_str());
   }
   c->vocab = (int)j.i64("vocab_size", 0);
@@ -602,6 +613,34 @@ int load_safetensors(bz_device* dev, const std::string& path, bz_model** out, bz
       continue;
     }
     if (ends_with(name, ".bias") && st.find(name.substr(0, name.size() - 5) + ".qweight")) continue;   // gptq.rs:158-166: handled with its layer
+    // NVFP4 linears (before the FP8 branch: their group scales are F8_E4M3 tensors too): <base>.weight_packed U8 [N, K/2] (two E2M1 codes per byte, low nibble =
+    // even element) + <base>.weight_scale F8_E4M3 [N, K/16] + <base>.weight_global_scale F32 [1] (a divisor) + optional <base>.bias; run weight-only, so
+    // <base>.input_global_scale is read past.  ASSUMPTION: the nibble order, these tensor names and the global scale being a divisor could not be checked against
+    // a published file; one line each changes them.  The tensors on the config's `ignore` list (lm_head, embeddings, norms) are 16-bit and take the dense path.
+    if (q.method == 6) {
+      auto packed_of = [&](const std::string& base) { const StTensor* x = st.find(base + ".weight_packed"); return x && x->dtype == "U8"; };
+      if (ends_with(name, ".weight_scale") && packed_of(name.substr(0, name.size() - 13))) continue;
+      if (ends_with(name, ".weight_global_scale") && packed_of(name.substr(0, name.size() - 20))) continue;
+      if (ends_with(name, ".input_global_scale") && packed_of(name.substr(0, name.size() - 19))) continue;
+      if (ends_with(name, ".bias") && packed_of(name.substr(0, name.size() - 5))) continue;
+      if (t.dtype == "U8") {
+        if (!ends_with(name, ".weight_packed") || t.shape.size() != 2) { rc = BZ_E_UNSUPPORTED; bz_set_error("tensor '%s': U8 is read for 2-D <linear>.weight_packed tensors (packed E2M1) only", name.c_str()); break; }
+        const std::string base = name.substr(0, name.size() - 14);
+        const StTensor* sc = st.find(base + ".weight_scale"); const StTensor* gs = st.find(base + ".weight_global_scale"); const StTensor* bi = st.find(base + ".bias");
+        const int64_t N = t.shape[0], K = t.shape[1] * 2;
+        if (!sc || !gs) { rc = BZ_E_INVALID; bz_set_error("nvfp4 layer '%s': no .weight_scale or no .weight_global_scale beside the packed weight", base.c_str()); break; }
+        if (N <= 0 || K <= 0 || K % 16 || t.bytes != (size_t)N * (size_t)(K / 2)) { rc = BZ_E_INVALID; bz_set_error("nvfp4 layer '%s': weight_packed must be U8 [N, K/2] with K a multiple of 16, its bytes matching its shape", base.c_str()); break; }
+        if (sc->dtype != "F8_E4M3" || sc->shape.size() != 2 || sc->shape[0] != N || sc->shape[1] != K / 16 || sc->bytes != (size_t)N * (size_t)(K / 16))
+          { rc = BZ_E_INVALID; bz_set_error("nvfp4 layer '%s': weight_scale must be F8_E4M3 [%lld,%lld] (one scale per group of 16)", base.c_str(), (long long)N, (long long)(K / 16)); break; }
+        size_t ng = 0;
+        if (gs->dtype != "F32" || !shape_elems(gs->shape, &ng) || ng != 1 || !to_f32(gs, 1, &f32a))
+          { rc = BZ_E_INVALID; bz_set_error("nvfp4 layer '%s': weight_global_scale must be one F32 value", base.c_str()); break; }
+        if (bi && (bi->shape.size() != 1 || bi->shape[0] != N || !to_f32(bi, (size_t)N, &f32b)))
+          { rc = BZ_E_INVALID; bz_set_error("nvfp4 layer '%s': bias must be F32 / F16 / BF16 [%lld]", base.c_str(), (long long)N); break; }
+        rc = bz_model_add_nvfp4(m, (base + ".weight").c_str(), N, K, t.data, sc->data, f32a[0], bi ? f32b.data() : nullptr);
+        continue;
+      }
+    }
     // FP8 (E4M3) linears: <linear>.weight F8_E4M3 [N,K] + <linear>.weight_scale ([] / [1] / [N] / [N,1]) + optional <linear>.bias; run weight-only, so the
     // activation scales (<linear>.input_scale) are read past
     if (ends_with(name, ".weight_scale") && st.find(name.substr(0, name.size() - 6)) && st.find(name.substr(0, name.size() - 6))->dtype == "F8_E4M3") continue;

@@ -56,6 +56,7 @@ int bzk_gemv_form(const bz_linear_traits_t& L, const GemvPro& p, int out, int ac
   if (L.kind == LK_F8) return BZ_GEMV_F8;
   if (L.kind == LK_MX4) return BZ_GEMV_MX4;
   if (L.kind == LK_I8) return BZ_GEMV_I8;
+  if (L.kind == LK_NV4) return BZ_GEMV_NV4;
   if (L.kind == LK_Q4G) return act == BZ_F16 && bzk_gemv_slim_ok(L, p, sw) ? BZ_GEMV_Q4G_SLIM : BZ_GEMV_Q4G;
   if (L.kind == LK_ROWS) return bzk_rows2_ok(L, p, out, sw) ? BZ_GEMV_ROWS2 : BZ_GEMV_ROWS;
   if (bzk_gq_slim_ok(L, p, sw)) return BZ_GEMV_GQ_SLIM;

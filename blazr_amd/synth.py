@@ -75,6 +75,16 @@ PRESETS = {
                       tie_embeddings=True,
                       rope_scaling=dict(type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
                                         original_max_position_embeddings=64)),
+    # NVFP4 weight checkpoints (the *-NVFP4 releases): E2M1 codes in groups of 16 with an E4M3 scale and a global scale per tensor, 4.5 bits per weight,
+    # 16-bit head and embeddings
+    "llama3.1-8b-nvfp4": dict(arch="llama", hidden=4096, n_layers=32, n_heads=32, n_kv_heads=8, head_dim=128, inter=14336,
+                              vocab=128256, rms_eps=1e-5, rope_theta=500000.0, act_dtype="bf16", quant="nvfp4",
+                              max_seq_len=2048, tie_embeddings=False),
+    "tiny-nvfp4": dict(arch="llama", hidden=256, n_layers=2, n_heads=4, n_kv_heads=2, head_dim=64, inter=512, vocab=1024,
+                       rms_eps=1e-5, rope_theta=10000.0, act_dtype="bf16", quant="nvfp4", max_seq_len=256,
+                       tie_embeddings=True,
+                       rope_scaling=dict(type="llama3", factor=8.0, low_freq_factor=1.0, high_freq_factor=4.0,
+                                         original_max_position_embeddings=64)),
     "tiny-q8_0": dict(arch="llama", hidden=256, n_layers=2, n_heads=4, n_kv_heads=2, head_dim=64, inter=512, vocab=1024,
                       rms_eps=1e-5, rope_theta=10000.0, act_dtype="f32", quant="q8_0", max_seq_len=256,
                       tie_embeddings=False, rope_interleaved=1),
@@ -281,6 +291,20 @@ def mxfp4_linear(name, N, K, bias=False, seed=BASE_SEED):
     return d
 
 
+def nvfp4_linear(name, N, K, bias=False, global_scale=128.0, seed=BASE_SEED):
+    """NVFP4 weight [N, K/2] (two E2M1 codes per byte, low nibble first) with E4M3 scale bytes [N, K/16] and the tensor's global scale,
+    a divisor: W = e2m1(code) . e4m3(scale) / global_scale.  The codes are drawn directly, as for the MXFP4 fixtures; the scale bytes
+    0x30..0x3F (0.5 .. 1.875, every mantissa) under the default global scale 2^7 put the weights' standard deviation near 0.02.  A
+    power-of-two global scale keeps every weight exact in f32."""
+    r = _rng(name, seed)
+    packed = r.integers(0, 256, size=(N, K // 2), dtype=np.uint8)
+    scale = r.integers(0x30, 0x40, size=(N, K // 16), dtype=np.uint8)
+    d = dict(kind="nvfp4", N=N, K=K, weight=packed, scale=scale, global_scale=float(global_scale), bias=None)
+    if bias:
+        d["bias"] = _repr(r.standard_normal(N, dtype=np.float32) * 0.01, "bf16")
+    return d
+
+
 def int8_linear(name, N, K, strategy, bias=False, std=0.02, seed=BASE_SEED):
     """INT8 W8A8 weight [N, K] int8 with one f32 scale per output channel (`channel`) or per tensor (`tensor`): W = scale . weight.  The
     codes are drawn directly, uniform over all 256 values (-128 included; an 8B model in seconds); the scales put the weights' standard
@@ -346,6 +370,8 @@ def _linear(cfg, name, N, K, layer=None, role=None, seed=BASE_SEED):
         return fp8_linear(name, N, K, cfg.get("fp8_strategy", "channel"), bias=cfg.get("bias", False), seed=seed)
     if q == "mxfp4":
         return mxfp4_linear(name, N, K, bias=cfg.get("bias", False), seed=seed)
+    if q == "nvfp4":
+        return nvfp4_linear(name, N, K, bias=cfg.get("bias", False), seed=seed)
     if q == "int8":
         return int8_linear(name, N, K, cfg.get("int8_strategy", "channel"), bias=cfg.get("bias", False), seed=seed)
     return dense_linear(name, N, K, cfg["act_dtype"], seed=seed)
@@ -431,6 +457,9 @@ def algorithmic_bytes_per_token(cfg):
         head = V * H * act_b
     elif q == "mxfp4":
         wb = lin // 2 + lin // 32                                     # two codes per byte + a scale byte per block of 32
+        head = V * H * act_b
+    elif q == "nvfp4":
+        wb = lin // 2 + lin // 16                                     # two codes per byte + a scale byte per group of 16
         head = V * H * act_b
     elif q == "q4_k_m":
         six = sum(q4km_uses_q6k(i, L) for i in range(L))
