@@ -255,7 +255,7 @@ class LayerPlan(C.Structure):
                 ("mla_exact", C.c_int), ("moe_route_fused", C.c_int), ("moe_rows2", C.c_int)]
 
 
-(LIN_NONE, LIN_Q4G, LIN_ROWS, LIN_Q4K, LIN_Q6K, LIN_Q80, LIN_Q5K, LIN_Q40, LIN_Q41, LIN_Q50, LIN_Q51, LIN_F8, LIN_MX4, LIN_I8, LIN_NV4) = range(15)
+(LIN_NONE, LIN_Q4G, LIN_ROWS, LIN_Q4K, LIN_Q6K, LIN_Q80, LIN_Q5K, LIN_Q40, LIN_Q41, LIN_Q50, LIN_Q51, LIN_F8, LIN_MX4, LIN_I8, LIN_NV4, LIN_IQ4XS) = range(16)
 (GEMV_NONE, GEMV_F8, GEMV_Q4G_SLIM, GEMV_Q4G, GEMV_ROWS2, GEMV_ROWS, GEMV_GQ_SLIM, GEMV_GQ, GEMV_UNSUPPORTED, GEMV_MX4, GEMV_I8, GEMV_NV4) = range(12)
 ATTN_PLAIN, ATTN_FUSED_Q4G, ATTN_FUSED_DENSE, ATTN_FUSED_Q4K, ATTN_SPLIT, ATTN_SPLIT_FUSED = range(6)
 ATTN_K_DECODE, ATTN_K_ATTN2, ATTN_K_ATTN2F, ATTN_K_UNSUPPORTED = range(4)

@@ -8,6 +8,8 @@
 //   Q4_K : { f16 d, dmin; u8 scales[12]; u8 qs[128] }                              144 B / 256
 //   Q5_K : { f16 d, dmin; u8 scales[12]; u8 qh[32]; u8 qs[128] }                   176 B / 256   (5th bit of element l of sub-block j = bit j of qh[l])
 //   Q6_K : { u8 ql[128]; u8 qh[64]; int8 scales[16]; f16 d }                       210 B / 256
+//   IQ4_XS : { f16 d; u16 scales_h; u8 scales_l[4]; u8 qs[128] }                   136 B / 256   (4-bit codes into the 16-entry table IQ4_KV; sub-block ib of 32:
+//            weight j < 16 = low nibble of qs[16 ib + j], j + 16 its high nibble; 6-bit scale ls = 4 bits of scales_l | 2 bits of scales_h, value d (ls - 32) KV[code])
 // Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -43,6 +45,27 @@ __device__ __forceinline__ unsigned q5_1_raw(const unsigned char* blk, int j) {
   const unsigned char b = blk[8 + (j & 15)];
   return (j < 16 ? (b & 15u) : (unsigned)(b >> 4)) | ((((unsigned)blk[4 + (j >> 3)] >> (j & 7)) & 1u) << 4);
 }
+// IQ4_XS: the 16-entry code table {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113} as int8 bytes of four words (entry e = byte e & 3 of
+// word e >> 2), the form V_PERM_B32 looks bytes up in: {IQ4_T1, IQ4_T0} is the table's low half, {IQ4_T3, IQ4_T2} its high half
+#define IQ4_T0 0xBFAD9881u
+#define IQ4_T1 0xF6EADDCFu
+#define IQ4_T2 0x26190D01u
+#define IQ4_T3 0x71594535u
+__device__ __forceinline__ int iq4_kv(unsigned code) {   // table entry of one code (0..15)
+  const unsigned w = (code & 8u) ? __builtin_amdgcn_perm(IQ4_T3, IQ4_T2, code & 7u) : __builtin_amdgcn_perm(IQ4_T1, IQ4_T0, code & 7u);
+  return (int)(signed char)(w & 255u);
+}
+__device__ __forceinline__ unsigned iq4xs_raw(const unsigned char* blk, int k) {     // 4-bit code of weight k (0..255) of a raw block_iq4_xs
+  const unsigned char b = blk[8 + (k >> 5) * 16 + (k & 15)];
+  return (k & 16) ? (unsigned)(b >> 4) : (b & 15u);
+}
+// 6-bit scale ls (0..63) of sub-block ib from the header words {d | scales_h << 16, scales_l[4]} (the block's first 8 bytes, little-endian)
+__device__ __forceinline__ int iq4xs_ls(unsigned h0, unsigned h1, int ib) { return (int)(((h1 >> (4 * ib)) & 15u) | (((h0 >> (16 + 2 * ib)) & 3u) << 4)); }
+// one weight from its header words and code, in the spec's order: dl = d * (ls - 32), y = dl * KV[code], each one f32 product
+__device__ __forceinline__ float iq4xs_value(unsigned h0, unsigned h1, int ib, unsigned code) {
+  const float dl = __fmul_rn(__half2float(__ushort_as_half((unsigned short)(h0 & 0xffffu))), (float)(iq4xs_ls(h0, h1, ib) - 32));
+  return __fmul_rn(dl, (float)iq4_kv(code));
+}
 __host__ __device__ __forceinline__ bool ggml_is_legacy(int type) {
   return type == BZ_GGML_Q4_0 || type == BZ_GGML_Q4_1 || type == BZ_GGML_Q5_0 || type == BZ_GGML_Q5_1;
 }
@@ -58,7 +81,7 @@ __host__ __device__ __forceinline__ int ggml_blk_k(int type) { return type == BZ
 __host__ __device__ __forceinline__ size_t ggml_blk_row_bytes(int type, int K) {
   if (ggml_is_legacy(type)) return (size_t)(K / 32) * (type == BZ_GGML_Q4_0 ? 18 : type == BZ_GGML_Q4_1 ? 20 : type == BZ_GGML_Q5_0 ? 22 : 24);
   return type == BZ_GGML_Q8_0 ? (size_t)(K / 32) * 34 : type == BZ_GGML_Q4_K ? (size_t)(K / 256) * 144 : type == BZ_GGML_Q5_K ? (size_t)(K / 256) * 176
-       : type == BZ_GGML_Q6_K ? (size_t)(K / 256) * 210 : 0;
+       : type == BZ_GGML_Q6_K ? (size_t)(K / 256) * 210 : type == BZ_GGML_IQ4_XS ? (size_t)(K / 256) * 136 : 0;
 }
 // weight k of a raw ggml row, exactly as ggml's dequantize_row_* computes it (its products and differences in its order, no contraction)
 __device__ __forceinline__ float ggml_row_elem(int type, const unsigned char* row, int k) {
@@ -78,6 +101,12 @@ __device__ __forceinline__ float ggml_row_elem(int type, const unsigned char* ro
     const unsigned char* b = row + (size_t)(k >> 8) * 210;
     const int kk = k & 255;
     return __fmul_rn(__fmul_rn(f16_at(b + 208), (float)(signed char)b[192 + (kk >> 4)]), (float)((int)q6k_raw(b, kk) - 32));
+  }
+  if (type == BZ_GGML_IQ4_XS) {
+    const unsigned char* b = row + (size_t)(k >> 8) * 136;
+    const unsigned h0 = (unsigned)b[0] | ((unsigned)b[1] << 8) | ((unsigned)b[2] << 16) | ((unsigned)b[3] << 24);
+    const unsigned h1 = (unsigned)b[4] | ((unsigned)b[5] << 8) | ((unsigned)b[6] << 16) | ((unsigned)b[7] << 24);
+    return iq4xs_value(h0, h1, (k & 255) >> 5, iq4xs_raw(b, k & 255));
   }
   const bool five = type == BZ_GGML_Q5_K;   // Q4_K / Q5_K: y = (d * sc) * q - (dmin * m)
   const unsigned char* b = row + (size_t)(k >> 8) * (five ? 176 : 144);

@@ -55,7 +55,7 @@ struct Pro {
 
 // (the public BZ_LIN_* values: bz_linear_traits_t carries a kind as it is)
 enum { LK_NONE = BZ_LIN_NONE, LK_Q4G = BZ_LIN_Q4G, LK_ROWS = BZ_LIN_ROWS, LK_Q4K = BZ_LIN_Q4K, LK_Q6K = BZ_LIN_Q6K, LK_Q80 = BZ_LIN_Q80, LK_Q5K = BZ_LIN_Q5K, LK_Q40 = BZ_LIN_Q40,
-       LK_Q41 = BZ_LIN_Q41, LK_Q50 = BZ_LIN_Q50, LK_Q51 = BZ_LIN_Q51, LK_F8 = BZ_LIN_F8, LK_MX4 = BZ_LIN_MX4, LK_I8 = BZ_LIN_I8, LK_NV4 = BZ_LIN_NV4 };
+       LK_Q41 = BZ_LIN_Q41, LK_Q50 = BZ_LIN_Q50, LK_Q51 = BZ_LIN_Q51, LK_F8 = BZ_LIN_F8, LK_MX4 = BZ_LIN_MX4, LK_I8 = BZ_LIN_I8, LK_NV4 = BZ_LIN_NV4, LK_IQ4XS = BZ_LIN_IQ4XS };
 
 // Device-resident linear layer in kernel layout.
 struct LinearDev {

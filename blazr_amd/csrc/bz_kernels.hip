@@ -694,7 +694,7 @@ int bzk_gemm_q4g_rows(hipStream_t s, const LinearDev& L, int xdt, const void* x1
 }
 
 // =========================================================================================================
-// GGUF block-quantised GEMV: Q8_0 / Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1 / Q5_0 / Q5_1  (formats = public GGML block layouts, gguf.rs:33 hands
+// GGUF block-quantised GEMV: Q8_0 / Q4_K / Q5_K / Q6_K / IQ4_XS / Q4_0 / Q4_1 / Q5_0 / Q5_1  (formats = public GGML block layouts, gguf.rs:33 hands
 // the blocks over opaquely).  Same skeleton as k_gemv_q4g -- lane == output column, split-K over k-slices, fused
 // prologues, 3-plane int8 activations on V_DOT4_I32_I8, fixed-point atomics -- with the activation slice scaled per
 // 32-k chunk so that every format's sub-block structure (32 for Q8_0/Q4_K, 16 for Q6_K) falls on chunk boundaries.
@@ -710,12 +710,14 @@ int bzk_gemm_q4g_rows(hipStream_t s, const LinearDev& L, int xdt, const void* x1
 //          q  [N/64][K/32][64][16 B] plain nibbles (A/B order, as Q5_K),  Q5_0 / Q5_1: qh exactly Q5_K's 5th-bit plane,
 //          hdr [N/64][K/256][64][8 x f16 d] (Q4_0 / Q5_0, 16 B)  or  [N/64][K/256][64][8 x {f16 d, f16 m}] (Q4_1 / Q5_1, 32 B)
 //          -- 144 / 160 / 176 / 192 B per 256 weights = ggml's 18 / 20 / 22 / 24 B per 32
+//   IQ4_XS : q [N/64][K/32][64][16 B] 4-bit table codes (A/B order, as Q5_K),  hdr [N/64][K/256][64][8 B] = {d, scales_h, scales_l[4]} verbatim
+//          -- 128 + 8 = ggml's 136 B per 256 weights.  The codes index a signed 16-entry table (bz_ggml.h IQ4_T*): no min term, no sum of x
 // per-chunk activation parameters in LDS (2 x int4 per chunk):
 //   P0 = { sx (f32 bits), Sa_h, Sa_m, Sa_l }   P1 = { Sb_h, Sb_m, Sb_l, 0 }
 //   Q4_K: Sa = sum over the chunk, Sb = sum over k%8 >= 4 (for the signed high-nibble trick);  Q5_K and the legacy formats: Sa only;  Q6_K: Sa / Sb
-//   = sums over the first / second 16;  Q8_0: unused.
+//   = sums over the first / second 16;  Q8_0 and IQ4_XS: unused.
 // =========================================================================================================
-enum { GQ_Q80 = 0, GQ_Q4K = 1, GQ_Q6K = 2, GQ_MIX = 3, GQ_Q5K = 4, GQ_Q40 = 5, GQ_Q41 = 6, GQ_Q50 = 7, GQ_Q51 = 8 };   // MIX: Q4_K tiles followed by Q6_K
+enum { GQ_Q80 = 0, GQ_Q4K = 1, GQ_Q6K = 2, GQ_MIX = 3, GQ_Q5K = 4, GQ_Q40 = 5, GQ_Q41 = 6, GQ_Q50 = 7, GQ_Q51 = 8, GQ_IQ4XS = 9 };   // MIX: Q4_K tiles followed by Q6_K
                                                                                                                     // tiles in one launch (the Q4_K_M q/k + v split)
 __host__ __device__ constexpr bool gq_legacy(int f) { return f == GQ_Q40 || f == GQ_Q41 || f == GQ_Q50 || f == GQ_Q51; }
 __host__ __device__ constexpr bool gq_has5(int f) { return f == GQ_Q50 || f == GQ_Q51; }     // legacy formats with a 5th-bit plane
@@ -882,6 +884,35 @@ __device__ __forceinline__ void legacy_dm(const uint4& hd, const uint4& hd2, uns
   for (int c = 0; c < 8; c++) dm[c] = gq_affine(FMT) ? a[c] : (a[c >> 1] >> (16 * (c & 1)));
 }
 
+// IQ4_XS: four 4-bit codes -> four signed int8 table values, on the VALU.  idx = the codes & 7, one per byte: V_PERM_B32 looks each up in the table's low half
+// {IQ4_T1, IQ4_T0} and in its high half {IQ4_T3, IQ4_T2}.  Bit 3 of each code picks the half: s13 / s02 hold that bit of codes 1, 3 / 0, 2 in bits 15 and 31,
+// where V_PERM's sign-replicating selectors (8 .. 11: bit 7 of byte 1 / 3 of either source as 0x00 / 0xFF) turn them into a byte mask for V_BFI -- no multiply,
+// no LDS table
+__device__ __forceinline__ unsigned iq4_lut4(unsigned idx, unsigned s13, unsigned s02) {
+  const unsigned lo = __builtin_amdgcn_perm(IQ4_T1, IQ4_T0, idx), hi = __builtin_amdgcn_perm(IQ4_T3, IQ4_T2, idx);
+  const unsigned m = __builtin_amdgcn_perm(s02, s13, 0x090B080Au);   // byte b of m = bit 3 of code b, replicated
+  return (hi & m) | (lo & ~m);
+}
+// word pair j of a chunk's nibble piece (low nibbles = k-order word A_j, high nibbles = B_j) as table values: 14 VALU operations
+__device__ __forceinline__ void iq4xs_pair(unsigned ww, unsigned& wa, unsigned& wb) {
+  wa = iq4_lut4(ww & 0x07070707u, ww << 4, ww << 12);
+  wb = iq4_lut4((ww >> 4) & 0x07070707u, ww, ww << 8);
+}
+// y term of one IQ4_XS chunk: sx (d (ls - 32)) U, U = sum KV[code] x over the three planes (signed x signed V_DOT4); dl = d (ls - 32) of the chunk's sub-block
+__device__ __forceinline__ float iq4xs_chunk(const uint4& nib, float dl, const uint4* xh4, const uint4* xm4, const uint4* xl4, int cc, const int4* cpar) {
+  unsigned w[8];
+  iq4xs_pair(nib.x, w[0], w[1]); iq4xs_pair(nib.y, w[2], w[3]); iq4xs_pair(nib.z, w[4], w[5]); iq4xs_pair(nib.w, w[6], w[7]);
+  int u[3] = {0, 0, 0};
+  dot_chunk8(w, xh4, xm4, xl4, cc, u);
+  return __int_as_float(cpar[2 * cc].x) * (dl * planes_f(u[0], u[1], u[2]));
+}
+// the 8 sub-block factors d (ls - 32) of a superblock from its 8-byte header, once per superblock
+__device__ __forceinline__ void iq4xs_dl(unsigned h0, unsigned h1, float (&dl)[8]) {
+  const float d = __half2float(__ushort_as_half((unsigned short)(h0 & 0xffffu)));
+#pragma unroll
+  for (int ib = 0; ib < 8; ib++) dl[ib] = d * (float)(iq4xs_ls(h0, h1, ib) - 32);
+}
+
 #define GQ_E 8   // slice elements per thread (KR <= 2048)
 
 template <int FMT, int MODE, int FIX, int MAXJ>
@@ -930,6 +961,9 @@ __global__ __launch_bounds__(256) void k_gemv_gq(const uint4* __restrict__ Wq, c
       if (gq_affine(FMT)) {
         const uint4* ph = Hd + (((size_t)ntc * SB + sb) * 64 + lane) * 2;
         hd = ph[0]; hd2 = ph[1];
+      } else if (FMT == GQ_IQ4XS) {
+        const uint2 h2 = ((const uint2*)Hd)[((size_t)ntc * SB + sb) * 64 + lane];
+        hd.x = h2.x; hd.y = h2.y;
       } else {
         hd = Hd[((size_t)ntc * SB + sb) * 64 + lane];
       }
@@ -1019,6 +1053,11 @@ __global__ __launch_bounds__(256) void k_gemv_gq(const uint4* __restrict__ Wq, c
       legacy_dm<FMT>(hd, hd2, dm);
 #pragma unroll
       for (int c = 0; c < 8; c++) y += legacy_chunk<FMT>(q[c], gq_has5(FMT) ? hb[c] : 0u, dm[c], xh4, xm4, xl4, s * 8 + c, cpar);
+    } else if (FMT == GQ_IQ4XS) {
+      float dl[8];
+      iq4xs_dl(hd.x, hd.y, dl);
+#pragma unroll
+      for (int c = 0; c < 8; c++) y += iq4xs_chunk(q[c], dl[c], xh4, xm4, xl4, s * 8 + c, cpar);
     } else {  // Q6_K
       const unsigned sw[4] = {hd.x, hd.y, hd.z, hd.w};   // 16 int8 scales
       const float d = __half2float(dv[0]);
@@ -1067,7 +1106,7 @@ __global__ __launch_bounds__(256) void k_gemv_gq(const uint4* __restrict__ Wq, c
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Slim form of the GGUF block-quant GEMV (Q4_K / Q5_K / Q6_K / Q4_0 / Q4_1 / Q5_0 / Q5_1): the structure of k_gemv_q4g_slim -- 8 waves share ONE 256-k slice, which here is
+// Slim form of the GGUF block-quant GEMV (Q4_K / Q5_K / Q6_K / IQ4_XS / Q4_0 / Q4_1 / Q5_0 / Q5_1): the structure of k_gemv_q4g_slim -- 8 waves share ONE 256-k slice, which here is
 // exactly one superblock, each wave owns one 64-column tile (its 8 KiB of nibbles + header in flight before the prologue) -- with the
 // per-32-k-chunk activation planes and the block arithmetic of k_gemv_gq.  The generic kernel holds > 256 registers per lane (one
 // workgroup of 4 waves per CU) and runs q/k/v in two rounds: 18.2 us against 7.0 us for the same bytes in AWQ form.
@@ -1135,6 +1174,9 @@ __global__ __launch_bounds__(512) void k_gemv_gq_slim(const uint4* __restrict__ 
     if (gq_affine(FMT)) {
       const uint4* ph = Hd_ + (((size_t)tqc * SB + ksl) * 64 + lane) * 2;
       hd = ph[0]; hd2 = ph[1];
+    } else if (FMT == GQ_IQ4XS) {   // 8-byte header: one uint2 where Q4_K loads a uint4
+      const uint2 h2 = ((const uint2*)Hd_)[((size_t)tqc * SB + ksl) * 64 + lane];
+      hd = make_uint4(h2.x, h2.y, 0, 0);
     } else {
       hd = Hd_[((size_t)tqc * SB + ksl) * 64 + lane];
     }
@@ -1192,6 +1234,11 @@ __global__ __launch_bounds__(512) void k_gemv_gq_slim(const uint4* __restrict__ 
     legacy_dm<FMT>(hd, hd2, dm);
 #pragma unroll
     for (int c = 0; c < 8; c++) y += legacy_chunk<FMT>(q[c], gq_has5(FMT) ? hb[c] : 0u, dm[c], xh4, xm4, xl4, c, cpar);
+  } else if (FMT == GQ_IQ4XS) {
+    float dl[8];
+    iq4xs_dl(hd.x, hd.y, dl);
+#pragma unroll
+    for (int c = 0; c < 8; c++) y += iq4xs_chunk(q[c], dl[c], xh4, xm4, xl4, c, cpar);
   } else if (FMT == GQ_Q5K) {
     const unsigned hw[4] = {hd.x, hd.y, hd.z, hd.w};
     const unsigned hb[8] = {q5h[0].x, q5h[0].y, q5h[0].z, q5h[0].w, q5h[1].x, q5h[1].y, q5h[1].z, q5h[1].w};
@@ -1279,7 +1326,7 @@ __global__ __launch_bounds__(512) void k_gemv_gq_slim(const uint4* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Fused MLP for the GGUF block formats (Q4_K gate / up, Q4_K or Q6_K down: the Q4_K_M mix), the structure of k_mlp_q4g:
+// Fused MLP for the GGUF block formats (Q4_K gate / up, Q4_K or Q6_K down: the Q4_K_M mix; IQ4_XS gate / up and down), the structure of k_mlp_q4g:
 //   acc_down += Wd[:, slab] . (silu(Wg[slice] x) * (Wu[slice] x)),   x = RMSNorm(h + prev)        (f32 activations: gguf.rs:305)
 // grid = I / 64 workgroups of NW = H / 256 waves: wave w owns superblock w (256 k) of the slice's gate tile and up tile, then 64 / NW ... output tiles
 // of the workgroup's 64-k slab of down_proj (two 32-k chunks of one superblock, with that superblock's header).  Wave roles as in k_mlp_q4g: the
@@ -1352,7 +1399,8 @@ __device__ __forceinline__ float gq_chunk_q6k(const uint4& qc, const uint2& qhc,
   return __int_as_float(p0.x) * ((d * (float)s0) * f0 + (d * (float)s1) * f1);
 }
 
-template <int FMTD, int FIX, int NW, int TPW>   // FMTD: down_proj format (GQ_Q4K / GQ_Q6K); NW = H / 256 waves; TPW = H / 64 / NW down tiles per wave
+// FMTG: gate / up format (GQ_Q4K / GQ_IQ4XS); FMTD: down_proj format (GQ_Q4K / GQ_Q6K / GQ_IQ4XS); NW = H / 256 waves; TPW = H / 64 / NW down tiles per wave
+template <int FMTG, int FMTD, int FIX, int NW, int TPW>
 __global__ __launch_bounds__(NW * 64) void k_mlp_gq(const uint4* __restrict__ Wgu, const uint4* __restrict__ Hgu, const float* __restrict__ bgu, const uint4* __restrict__ Wd,
                                                 const uint2* __restrict__ Whd, const uint4* __restrict__ Hdd, const __half* __restrict__ Ddd, const float* __restrict__ bd,
                                                 int H, int I, Pro pro, long long* acc, long long* zero_buf, int zero_n) {
@@ -1407,7 +1455,7 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_gq(const uint4* __restrict__ Wg
     float x[8];
 #pragma unroll
     for (int e = 0; e < 8; e++) x[e] = round_act(nwv[e] * round_act(v[e] * rs, pro.act), pro.act);
-    quant8_x32<GQ_Q4K>(x, i0, true, lane, xh, xm, xl, cpar);
+    quant8_x32<FMTG>(x, i0, true, lane, xh, xm, xl, cpar);
     __builtin_amdgcn_s_waitcnt(0xc07f);
     if (lane == 0) atomicAdd((unsigned*)&cnt[1], 1u);
 #pragma unroll
@@ -1418,13 +1466,27 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_gq(const uint4* __restrict__ Wg
     for (int c = 0; c < 8; c++) { qg[c] = ldnt(pg + c * 64); qu[c] = ldnt(pu + c * 64); }
     zero_duty<NP * 64>(zero_buf, zero_n);
   }
-  const uint4 hg = Hgu[((size_t)sl * SBH + wave) * 64 + lane], hu = Hgu[((size_t)(NTI + sl) * SBH + wave) * 64 + lane];
+  uint4 hg, hu;
+  if (FMTG == GQ_IQ4XS) {
+    const uint2 g2 = ((const uint2*)Hgu)[((size_t)sl * SBH + wave) * 64 + lane], u2 = ((const uint2*)Hgu)[((size_t)(NTI + sl) * SBH + wave) * 64 + lane];
+    hg = make_uint4(g2.x, g2.y, 0, 0); hu = make_uint4(u2.x, u2.y, 0, 0);
+  } else {
+    hg = Hgu[((size_t)sl * SBH + wave) * 64 + lane]; hu = Hgu[((size_t)(NTI + sl) * SBH + wave) * 64 + lane];
+  }
   lds_wait_count(&cnt[1], NP);
   const uint4* xh4 = (const uint4*)xh;
   const uint4* xm4 = (const uint4*)xm;
   const uint4* xl4 = (const uint4*)xl;
   float yg = 0.f, yu = 0.f;
-  {
+  if (FMTG == GQ_IQ4XS) {
+    float dlg[8], dlu[8];
+    iq4xs_dl(hg.x, hg.y, dlg); iq4xs_dl(hu.x, hu.y, dlu);
+#pragma unroll
+    for (int c = 0; c < 8; c++) {
+      yg += iq4xs_chunk(qg[c], dlg[c], xh4, xm4, xl4, wave * 8 + c, cpar);
+      yu += iq4xs_chunk(qu[c], dlu[c], xh4, xm4, xl4, wave * 8 + c, cpar);
+    }
+  } else {
     const unsigned hwg[4] = {hg.x, hg.y, hg.z, hg.w}, hwu[4] = {hu.x, hu.y, hu.z, hu.w};
     const float dg = __half2float(__ushort_as_half((unsigned short)(hwg[0] & 0xffffu))), dming = __half2float(__ushort_as_half((unsigned short)(hwg[0] >> 16)));
     const float du = __half2float(__ushort_as_half((unsigned short)(hwu[0] & 0xffffu))), dminu = __half2float(__ushort_as_half((unsigned short)(hwu[0] >> 16)));
@@ -1442,7 +1504,12 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_gq(const uint4* __restrict__ Wg
     const int t = wave * TPW + q;
     const uint4* wp = Wd + ((size_t)t * C32D + 2 * sl) * 64 + lane;
     D[q][0] = ldnt(wp); D[q][1] = ldnt(wp + 64);
-    hdd[q] = Hdd[((size_t)t * SBD + sbd) * 64 + lane];
+    if (FMTD == GQ_IQ4XS) {
+      const uint2 h2 = ((const uint2*)Hdd)[((size_t)t * SBD + sbd) * 64 + lane];
+      hdd[q] = make_uint4(h2.x, h2.y, 0, 0);
+    } else {
+      hdd[q] = Hdd[((size_t)t * SBD + sbd) * 64 + lane];
+    }
     if (FMTD == GQ_Q6K) {
       const uint2* wh = Whd + ((size_t)t * C32D + 2 * sl) * 64 + lane;
       Dh[q][0] = wh[0]; Dh[q][1] = wh[64];
@@ -1465,7 +1532,7 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_gq(const uint4* __restrict__ Wg
     float x[8];
 #pragma unroll
     for (int e = 0; e < 8; e++) x[e] = lane < 8 ? av[lane * 8 + e] : 0.f;
-    if (FMTD == GQ_Q6K) quant8_x32<GQ_Q6K>(x, lane * 8, lane < 8, lane, ah, am_, al, apar); else quant8_x32<GQ_Q4K>(x, lane * 8, lane < 8, lane, ah, am_, al, apar);
+    quant8_x32<FMTD>(x, lane * 8, lane < 8, lane, ah, am_, al, apar);
   }
   __syncthreads();
   const uint4* ah4 = (const uint4*)ah;
@@ -1479,6 +1546,10 @@ __global__ __launch_bounds__(NW * 64) void k_mlp_gq(const uint4* __restrict__ Wg
       const float d = __half2float(__ushort_as_half((unsigned short)(hw[0] & 0xffffu))), dmin = __half2float(__ushort_as_half((unsigned short)(hw[0] >> 16)));
       y += gq_chunk_q4k(D[q][0], 0, cs0, hw, d, dmin, ah4, am4, al4, apar);
       y += gq_chunk_q4k(D[q][1], 1, cs0 + 1, hw, d, dmin, ah4, am4, al4, apar);
+    } else if (FMTD == GQ_IQ4XS) {
+      const float d = __half2float(__ushort_as_half((unsigned short)(hw[0] & 0xffffu)));
+      y += iq4xs_chunk(D[q][0], d * (float)(iq4xs_ls(hw[0], hw[1], cs0) - 32), ah4, am4, al4, 0, apar);
+      y += iq4xs_chunk(D[q][1], d * (float)(iq4xs_ls(hw[0], hw[1], cs0 + 1) - 32), ah4, am4, al4, 1, apar);
     } else {
       const float d = __half2float(ddd[q]);
       y += gq_chunk_q6k(D[q][0], Dh[q][0], 0, cs0, hw, d, ah4, am4, al4, apar);
@@ -1494,11 +1565,13 @@ int bzk_mlp_gq(hipStream_t s, const LinearDev& gu, const LinearDev& dn, int H, i
   if (!bzk_mlp_gq_fusable(lin_traits(gu), lin_traits(dn), H, I, pro.act, *bzk_step_switches())) BZ_FAIL(BZ_E_INVALID, "fused GGUF MLP does not apply to this shape");
   const size_t smem = mlp_gq_smem(H);
   const double bytes = (double)gu.algo_bytes + (double)dn.algo_bytes;
-#define LAUNCH_MGQ(FD, FIX, NW_, TP) BZ_LAUNCH("mlp_gguf<norm+gate/up+silu+down>", bytes, (k_mlp_gq<FD, FIX, NW_, TP>), dim3(I / 64), dim3(NW_ * 64), smem, s, (const uint4*)gu.w, \
+#define LAUNCH_MGQ(FG, FD, FIX, NW_, TP) BZ_LAUNCH("mlp_gguf<norm+gate/up+silu+down>", bytes, (k_mlp_gq<FG, FD, FIX, NW_, TP>), dim3(I / 64), dim3(NW_ * 64), smem, s, (const uint4*)gu.w, \
     (const uint4*)gu.hdr, gu.bias, (const uint4*)dn.w, (const uint2*)dn.zeros, (const uint4*)dn.hdr, (const __half*)dn.scales, dn.bias, H, I, pro, acc, zero_buf, zero_n)
-#define LAUNCH_MGQ_F(FD, NW_, TP) do { if (pro.src.fix) LAUNCH_MGQ(FD, 1, NW_, TP); else LAUNCH_MGQ(FD, 0, NW_, TP); } while (0)
-  if (H == 4096) { if (dn.kind == LK_Q6K) LAUNCH_MGQ_F(GQ_Q6K, 16, 4); else LAUNCH_MGQ_F(GQ_Q4K, 16, 4); }
-  else { if (dn.kind == LK_Q6K) LAUNCH_MGQ_F(GQ_Q6K, 8, 4); else LAUNCH_MGQ_F(GQ_Q4K, 8, 4); }
+#define LAUNCH_MGQ_F(FG, FD, NW_, TP) do { if (pro.src.fix) LAUNCH_MGQ(FG, FD, 1, NW_, TP); else LAUNCH_MGQ(FG, FD, 0, NW_, TP); } while (0)
+#define LAUNCH_MGQ_D(NW_, TP) do { if (gu.kind == LK_IQ4XS) LAUNCH_MGQ_F(GQ_IQ4XS, GQ_IQ4XS, NW_, TP); \
+  else if (dn.kind == LK_Q6K) LAUNCH_MGQ_F(GQ_Q4K, GQ_Q6K, NW_, TP); else LAUNCH_MGQ_F(GQ_Q4K, GQ_Q4K, NW_, TP); } while (0)
+  if (H == 4096) LAUNCH_MGQ_D(16, 4); else LAUNCH_MGQ_D(8, 4);
+#undef LAUNCH_MGQ_D
 #undef LAUNCH_MGQ_F
 #undef LAUNCH_MGQ
   BZ_HIP(hipGetLastError());
@@ -2321,7 +2394,7 @@ __global__ void k_repack_gq(int fmt, const unsigned char* raw, int N, int K, uin
     }
     return;
   }
-  const size_t bsz = fmt == GQ_Q4K ? 144 : (fmt == GQ_Q5K ? 176 : 210);
+  const size_t bsz = fmt == GQ_Q4K ? 144 : (fmt == GQ_Q5K ? 176 : fmt == GQ_IQ4XS ? 136 : 210);
   const size_t rb = (size_t)(K / 256) * bsz;
   const size_t total = (size_t)N * (K >> 3);                   // nibble words (8 weights each)
   for (size_t idx = gid; idx < total; idx += gsz) {
@@ -2340,6 +2413,8 @@ __global__ void k_repack_gq(int fmt, const unsigned char* raw, int N, int K, uin
       } else if (fmt == GQ_Q5K) {
         const unsigned q1 = q5k_raw(blk, kb + bb) & 15u, q2 = q5k_raw(blk, kb + 4 + bb) & 15u;
         word |= (q1 | (q2 << 4)) << (8 * bb);
+      } else if (fmt == GQ_IQ4XS) {
+        word |= (iq4xs_raw(blk, kb + bb) | (iq4xs_raw(blk, kb + 4 + bb) << 4)) << (8 * bb);
       } else {
         const unsigned q1 = q6k_raw(blk, kb + bb) & 15u, q2 = q6k_raw(blk, kb + 4 + bb) & 15u;
         word |= (q1 | (q2 << 4)) << (8 * bb);
@@ -2378,19 +2453,20 @@ __global__ void k_repack_gq(int fmt, const unsigned char* raw, int N, int K, uin
     }
   }
   const size_t nsb = (size_t)N * (K >> 8);
-  for (size_t idx = gid; idx < nsb * 4; idx += gsz) {          // 16-byte header per (superblock, lane)
-    const int wi = idx & 3, lane = (idx >> 2) & 63;
-    const size_t t = idx >> 8;
+  const int wpl = fmt == GQ_IQ4XS ? 2 : 4;                     // header words per (superblock, lane): 16 bytes, IQ4_XS 8 = {d, scales_h, scales_l[4]}
+  for (size_t idx = gid; idx < nsb * wpl; idx += gsz) {
+    const int wi = (int)(idx % wpl), lane = (int)((idx / wpl) & 63);
+    const size_t t = idx / wpl >> 6;
     const int sb = (int)(t % (size_t)(K >> 8)), nt = (int)(t / (size_t)(K >> 8));
     const unsigned char* blk = raw + (size_t)(nt * 64 + lane) * rb + (size_t)sb * bsz;
-    const unsigned char* src = fmt != GQ_Q6K ? blk + wi * 4 : blk + 192 + wi * 4;   // Q4_K / Q5_K: d,dmin,scales[12] ; Q6_K: scales[16]
+    const unsigned char* src = fmt != GQ_Q6K ? blk + wi * 4 : blk + 192 + wi * 4;   // Q4_K / Q5_K: d,dmin,scales[12] ; IQ4_XS: the block's first 8 bytes ; Q6_K: scales[16]
     hd[idx] = (unsigned)src[0] | ((unsigned)src[1] << 8) | ((unsigned)src[2] << 16) | ((unsigned)src[3] << 24);
     if (fmt == GQ_Q6K && wi == 0) dd[((size_t)nt * (K >> 8) + sb) * 64 + lane] = __ushort_as_half((unsigned short)(blk[208] | (blk[209] << 8)));
   }
 }
 static int gq_fmt_of(int kind) {
   return kind == LK_Q80 ? GQ_Q80 : kind == LK_Q4K ? GQ_Q4K : kind == LK_Q5K ? GQ_Q5K : kind == LK_Q40 ? GQ_Q40 : kind == LK_Q41 ? GQ_Q41 : kind == LK_Q50 ? GQ_Q50
-       : kind == LK_Q51 ? GQ_Q51 : GQ_Q6K;
+       : kind == LK_Q51 ? GQ_Q51 : kind == LK_IQ4XS ? GQ_IQ4XS : GQ_Q6K;
 }
 int bzk_repack_gq(hipStream_t s, int kind, const void* raw, int N, int K, void* wq, void* wh, void* hd, void* dd) {
   const int fmt = gq_fmt_of(kind);
@@ -2419,6 +2495,10 @@ __device__ __forceinline__ float gq_elem(int fmt, const uint32_t* wq, const uint
     const float d = __half2float(__ushort_as_half((unsigned short)(dm & 0xffffu)));
     if (gq_affine(fmt)) return __fadd_rn(__fmul_rn((float)q, d), __half2float(__ushort_as_half((unsigned short)(dm >> 16))));
     return __fmul_rn((float)((int)q - (fmt == GQ_Q40 ? 8 : 16)), d);
+  }
+  if (fmt == GQ_IQ4XS) {   // the spec's order, uncontracted: (d (ls - 32)) KV[code]
+    const size_t h2 = (((size_t)nt * (K >> 8) + (k >> 8)) * 64 + lane) * 2;
+    return iq4xs_value(hd[h2], hd[h2 + 1], (k & 255) >> 5, rr < 4 ? (byte & 15u) : (byte >> 4));
   }
   const size_t hi = (((size_t)nt * (K >> 8) + (k >> 8)) * 64 + lane) * 4;
   const unsigned hw[4] = {hd[hi], hd[hi + 1], hd[hi + 2], hd[hi + 3]};
@@ -2497,7 +2577,7 @@ __global__ __launch_bounds__(256) void k_gq_split3(int fmt, const uint32_t* wq, 
 }
 bool bzk_gq_split_ok(const LinearDev& L) {
   return (L.kind == LK_Q80 || L.kind == LK_Q4K || L.kind == LK_Q5K || L.kind == LK_Q6K || L.kind == LK_Q40 || L.kind == LK_Q41 || L.kind == LK_Q50 ||
-          L.kind == LK_Q51) && L.K % 64 == 0 && L.N % 64 == 0;
+          L.kind == LK_Q51 || L.kind == LK_IQ4XS) && L.K % 64 == 0 && L.N % 64 == 0;
 }
 // amax: device word holding the running maximum of the fused linear's parts (zeroed by the caller before the first part)
 int bzk_gq_absmax(hipStream_t s, const LinearDev& L, unsigned* amax) {
@@ -2604,6 +2684,7 @@ static int gemv_gq_slim(hipStream_t s, const LinearDev& L, const Pro& pro, const
   if (!out.acc) BZ_FAIL(BZ_E_INVALID, "block-quant gemv needs a fixed-point accumulator");
   const int nsb = L.K / 256, ntg = (L.N / 64 + 7) / 8;
   const char* label = L.kind == LK_Q4K ? "gemv_q4_K<slim>" : L.kind == LK_Q5K ? "gemv_q5_K<slim>" : L.kind == LK_Q6K ? "gemv_q6_K<slim>"
+                    : L.kind == LK_IQ4XS ? "gemv_iq4_xs<slim>"
                     : L.kind == LK_Q40 ? "gemv_q4_0<slim>" : L.kind == LK_Q41 ? "gemv_q4_1<slim>" : L.kind == LK_Q50 ? "gemv_q5_0<slim>" : "gemv_q5_1<slim>";
 #define LAUNCH_GQS(FMT, MODE, FIX, NJ) BZ_LAUNCH(label, L.algo_bytes, (k_gemv_gq_slim<FMT, MODE, FIX, NJ>), dim3(nsb * ntg), dim3(512), 0, s, (const uint4*)L.w, \
   (const uint2*)L.zeros, (const uint4*)L.hdr, (const __half*)L.scales, L.bias, L.N, L.K, pro, out.acc, out.zero_buf, out.zero_n, GqMix{})
@@ -2611,6 +2692,7 @@ static int gemv_gq_slim(hipStream_t s, const LinearDev& L, const Pro& pro, const
   else if (L.K == 4096) LAUNCH_GQS(FMT, PRO_NORM, FIX, 2); else LAUNCH_GQS(FMT, PRO_NORM, FIX, 4); } while (0)
 #define LAUNCH_GQS_F(FMT) do { if (pro.src.fix) LAUNCH_GQS_NJ(FMT, 1); else LAUNCH_GQS_NJ(FMT, 0); } while (0)
   if (L.kind == LK_Q4K) LAUNCH_GQS_F(GQ_Q4K); else if (L.kind == LK_Q5K) LAUNCH_GQS_F(GQ_Q5K); else if (L.kind == LK_Q6K) LAUNCH_GQS_F(GQ_Q6K);
+  else if (L.kind == LK_IQ4XS) LAUNCH_GQS_F(GQ_IQ4XS);
   else if (L.kind == LK_Q40) LAUNCH_GQS_F(GQ_Q40); else if (L.kind == LK_Q41) LAUNCH_GQS_F(GQ_Q41); else if (L.kind == LK_Q50) LAUNCH_GQS_F(GQ_Q50);
   else LAUNCH_GQS_F(GQ_Q51);
 #undef LAUNCH_GQS_F
@@ -2628,6 +2710,7 @@ static int gemv_gq(hipStream_t s, const LinearDev& L, const Pro& pro, const Gemv
   const size_t smem = gq_smem(SBW);
   const int maxj = pro.mode == PRO_NORM ? (pro.H + 1023) / 1024 : 1;
   const char* label = L.kind == LK_Q80 ? "gemv_q8_0" : L.kind == LK_Q4K ? "gemv_q4_K" : L.kind == LK_Q5K ? "gemv_q5_K" : L.kind == LK_Q6K ? "gemv_q6_K"
+                    : L.kind == LK_IQ4XS ? "gemv_iq4_xs"
                     : L.kind == LK_Q40 ? "gemv_q4_0" : L.kind == LK_Q41 ? "gemv_q4_1" : L.kind == LK_Q50 ? "gemv_q5_0" : "gemv_q5_1";
 #define LAUNCH_GQ(FMT, MODE, FIX, MJ) BZ_LAUNCH(label, L.algo_bytes, (k_gemv_gq<FMT, MODE, FIX, MJ>), dim3(grid), dim3(256), smem, s, (const uint4*)L.w, \
   (const uint2*)L.zeros, (const uint4*)L.hdr, (const __half*)L.scales, L.bias, L.N, L.K, SBW, nst, pro, out.acc, out.zero_buf, out.zero_n)
@@ -2637,6 +2720,7 @@ static int gemv_gq(hipStream_t s, const LinearDev& L, const Pro& pro, const Gemv
   else if (maxj <= 8) LAUNCH_GQ_F(FMT, PRO_NORM, 8); else BZ_FAIL(BZ_E_UNSUPPORTED, "hidden size %d too large for the fused norm prologue", pro.H); } while (0)
   if (L.kind == LK_Q80) LAUNCH_GQ_M(GQ_Q80); else if (L.kind == LK_Q4K) LAUNCH_GQ_M(GQ_Q4K); else if (L.kind == LK_Q5K) LAUNCH_GQ_M(GQ_Q5K);
   else if (L.kind == LK_Q6K) LAUNCH_GQ_M(GQ_Q6K); else if (L.kind == LK_Q40) LAUNCH_GQ_M(GQ_Q40); else if (L.kind == LK_Q41) LAUNCH_GQ_M(GQ_Q41);
+  else if (L.kind == LK_IQ4XS) LAUNCH_GQ_M(GQ_IQ4XS);
   else if (L.kind == LK_Q50) LAUNCH_GQ_M(GQ_Q50); else LAUNCH_GQ_M(GQ_Q51);
 #undef LAUNCH_GQ_M
 #undef LAUNCH_GQ_F

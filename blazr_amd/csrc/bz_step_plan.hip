@@ -28,7 +28,7 @@ bool bzk_gemv_slim_ok(const bz_linear_traits_t& L, const GemvPro& p, const bz_st
   return !sw.no_slim_qkv && L.kind == LK_Q4G && !L.act_order && p.mode == PRO_NORM && !p.perm && L.K == p.H && (L.K == 2048 || L.K == 4096 || L.K == 8192) && L.N % 64 == 0 &&
          L.N <= 16384;
 }
-static bool gq_kind(int kind) { return kind == LK_Q4K || kind == LK_Q5K || kind == LK_Q6K || kind == LK_Q40 || kind == LK_Q41 || kind == LK_Q50 || kind == LK_Q51; }
+static bool gq_kind(int kind) { return kind == LK_Q4K || kind == LK_Q5K || kind == LK_Q6K || kind == LK_Q40 || kind == LK_Q41 || kind == LK_Q50 || kind == LK_Q51 || kind == LK_IQ4XS; }
 bool bzk_gq_slim_ok(const bz_linear_traits_t& L, const GemvPro& p, const bz_step_switches_t& sw) {
   if (sw.no_gq_slim || !gq_kind(L.kind) || p.perm || L.N % 64 || L.K % 256) return false;
   if (p.mode == PRO_NORM) return L.K == p.H && (L.K == 2048 || L.K == 4096 || L.K == 8192);
@@ -81,7 +81,9 @@ bool bzk_mlp_gq_fusable(const bz_linear_traits_t& gu, const bz_linear_traits_t& 
   // box): the block formats cost ~2.5 VALU operations per weight (AND-unpack + three-plane V_DOT4 + a per-32-k epilogue of scale / min arithmetic), ~19 us
   // of issue per CU when 224 workgroups carry all of it -- the fused form serialises that behind its stream, the slim launches spread it over 256 CUs
   const bool on = sw.gguf_mlp_fusion && !sw.no_mlp_fusion;
-  return on && act == BZ_F32 && gu.kind == LK_Q4K && (dn.kind == LK_Q4K || dn.kind == LK_Q6K) && !gu.act_order && !dn.act_order && gu.N == 2 * I && gu.K == H && dn.N == H && dn.K == I &&
+  // (IQ4_XS gate / up with an IQ4_XS down: the same launch on the table-lookup chunk)
+  const bool kinds = (gu.kind == LK_Q4K && (dn.kind == LK_Q4K || dn.kind == LK_Q6K)) || (gu.kind == LK_IQ4XS && dn.kind == LK_IQ4XS);
+  return on && act == BZ_F32 && kinds && !gu.act_order && !dn.act_order && gu.N == 2 * I && gu.K == H && dn.N == H && dn.K == I &&
          (H == 2048 || H == 4096) && I % 256 == 0 && I % 64 == 0;
 }
 

@@ -43,7 +43,7 @@ enum {
 enum { BZ_F32 = 0, BZ_F16 = 1, BZ_BF16 = 2, BZ_I64 = 3, BZ_I32 = 4, BZ_U32 = 5, BZ_U8 = 6 };
 
 /* ggml type ids accepted by bz_model_add_gguf (format::Gguf tensor_info().ggml_type, loader/gguf.rs:33) */
-enum { BZ_GGML_F32 = 0, BZ_GGML_F16 = 1, BZ_GGML_Q4_0 = 2, BZ_GGML_Q4_1 = 3, BZ_GGML_Q5_0 = 6, BZ_GGML_Q5_1 = 7, BZ_GGML_Q8_0 = 8, BZ_GGML_Q4_K = 12, BZ_GGML_Q5_K = 13, BZ_GGML_Q6_K = 14, BZ_GGML_BF16 = 30 };
+enum { BZ_GGML_F32 = 0, BZ_GGML_F16 = 1, BZ_GGML_Q4_0 = 2, BZ_GGML_Q4_1 = 3, BZ_GGML_Q5_0 = 6, BZ_GGML_Q5_1 = 7, BZ_GGML_Q8_0 = 8, BZ_GGML_Q4_K = 12, BZ_GGML_Q5_K = 13, BZ_GGML_Q6_K = 14, BZ_GGML_IQ4_XS = 23, BZ_GGML_BF16 = 30 };
 
 enum { BZ_ARCH_LLAMA = 0, BZ_ARCH_MAMBA2 = 1, BZ_ARCH_DEEPSEEK2 = 2 };
 enum { BZ_ROPE_NONE = 0, BZ_ROPE_LINEAR = 1, BZ_ROPE_LLAMA3 = 2, BZ_ROPE_YARN = 3 };
@@ -849,7 +849,8 @@ int bz_quant_matmul(bz_model* m, const char* name, const bz_tensor* x, int S, bz
 /* Prefill GEMM on the matrix cores: y[S,N] = round16(x)[S,K] . W[N,K]^T, f32 accumulate, result unrounded.  Dense f16 / bf16 weights
  * (K % 64 == 0, x rounded to the weight dtype), or int4 group-quantised weights without act-order (AWQ / GPTQ: x rounded to f16, S >= 9).  The same kernel runs inside bz_forward_kv / bz_forward_paged when a dense 16-bit Llama-family model is given S >= 8 tokens
  * (regular.rs:89-117 bf16 SafeTensors path; boostr's matmul behind LoadedModel::forward_with_kv_cache at executor_generate.rs:357).  An MXFP4 name follows the model's
- * bz_model_set_mxfp4_activations mode. */
+ * bz_model_set_mxfp4_activations mode.  A GGUF block linear without bias (Q4_0 .. Q6_K, IQ4_XS): x unrounded, both operands as three f16 pieces through the same
+ * GEMM over 3 K, as GGUF prompts run. */
 int bz_prefill_matmul(bz_model* m, const char* name, const bz_tensor* x, int S, bz_tensor* y);
 /* DequantOps: whole weight -> F32 [N,K] on host (from the REPACKED device layout: validates the repack) */
 int bz_dequant(bz_model* m, const char* name, float* host_out);
@@ -943,7 +944,7 @@ int bz_packed_totals_spec(const bz_score_row* rows /*[T]*/, const int32_t* seq_l
  * keeps one plan per layer and cache dtype (F32 / F16 / BF16); the step dispatches on it and decides one thing per call: the short or the long attention form,
  * from the context and BZ_SPLIT_MIN.  A fused linear is described by its parts (at most three).  Flags are 0 / 1.  New symbols only: BZ_ABI_VERSION is unchanged. */
 enum { BZ_LIN_NONE = 0, BZ_LIN_Q4G = 1, BZ_LIN_ROWS = 2, BZ_LIN_Q4K = 3, BZ_LIN_Q6K = 4, BZ_LIN_Q80 = 5, BZ_LIN_Q5K = 6, BZ_LIN_Q40 = 7, BZ_LIN_Q41 = 8, BZ_LIN_Q50 = 9,
-       BZ_LIN_Q51 = 10, BZ_LIN_F8 = 11, BZ_LIN_MX4 = 12, BZ_LIN_I8 = 13, BZ_LIN_NV4 = 14 };
+       BZ_LIN_Q51 = 10, BZ_LIN_F8 = 11, BZ_LIN_MX4 = 12, BZ_LIN_I8 = 13, BZ_LIN_NV4 = 14, BZ_LIN_IQ4XS = 15 };
 typedef struct bz_linear_traits_t {
   int kind, N, K;        /* BZ_LIN_* */
   int wdt;               /* ROWS: the weights' dtype */
